@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — decoded Mpixels/s of the MI355X block-reconstruction engine on a synthetic stream.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 The unit of work is a closed GOP (openhevc_amd/parallel.py): 1 I picture, 3 reference B pictures and 12
@@ -16,6 +16,11 @@ all of them is one batch of independent pictures and every pass is one launch ov
 (oh_frames_execute), which fills the GPU where a single picture's dependency chain cannot.  With N GPUs every rank decodes its own 16 pictures per step and the four
 reference pictures of every rank are replicated with one RCCL all-gather per wave (weak scaling).
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else it can measure or check — the
+`kernel_only` region, the per-pass `roofline` (one more step with per-launch events), the picture check against the CPU
+checker, the CPU baselines and the `end_to_end` stream decode — runs with --full only.  --dump-outputs DIR writes a fixed,
+seeded sample of the pictures the last timed step decoded as DIR/<plane>.npy (float32), so two builds can be compared.
 """
 import argparse
 import json
@@ -335,10 +340,15 @@ def main():
                     "~30 GB/s where the copy engines move 41 (58-62 against 83 Gpixels/s; one DMA request per array: 47): the default is ordinary host "
                     "memory, staged into one pinned block by the calling thread and the engine's copy helpers, ONE DMA per picture")
     ap.add_argument("--host-threads", type=int, default=0, help="1: a single host thread enqueues every stream (default: one thread per stream)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the end-to-end stream decode through the drop-in library (ohevc_dec child processes, ~1-2 min)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the `kernel_only` region (one GPU), the per-pass `roofline` "
+                    "(one more step with per-launch events), the picture check against the CPU checker, the CPU baselines and the end-to-end "
+                    "stream decode; a plain run does none of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write a fixed, seeded sample of the pictures "
+                    "the last timed step decoded as DIR/{luma,cb,cr}.npy (float32, 48 MB at most)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines (and the end-to-end stream decode)")
+    ap.add_argument("--no-end-to-end", action="store_true", help="--full: skip the end-to-end stream decode through the drop-in library (ohevc_dec child processes, ~1-2 min)")
     ap.add_argument("--no-profile", action="store_true", help="no HIP events between passes in the timed region")
-    ap.add_argument("--no-check", action="store_true", help="skip the picture check after the timed region")
+    ap.add_argument("--no-check", action="store_true", help="--full: skip the picture check after the timed region")
     ap.add_argument("--profile-round", type=int, default=None, help="cite profiles/rNN_* of this round (default: the newest round that was taken with this tree's kernels)")
     args = ap.parse_args()
 
@@ -390,9 +400,11 @@ def main():
     per_chain = (args.waves * (world + 1) + max(args.tail, 1) * 2) * half_bytes       # parallel.GroupStore: other ranks' pictures keep one half
     per_chain += 2 * int(2.5 * half_bytes)                 # + the work lists in flight (this batch and the next): lists, prepared lists, residual pool
     # the second timed region (resident work lists, `kernel_only`) keeps EVERY list of every chain in HBM: one GPU only — with N > 1 the
-    # picture buffers of all ranks need that room, and the figure says nothing about the exchange
-    with_kernel_only = world == 1 or args.mode == "kernel_only"
-    if with_kernel_only:
+    # picture buffers of all ranks need that room, and the figure says nothing about the exchange.  Its room is kept with or without
+    # --full, so the chains in flight (and with them the headline) do not depend on whether the region runs
+    room_kernel_only = world == 1 or args.mode == "kernel_only"
+    with_kernel_only = args.mode == "kernel_only" or (room_kernel_only and args.full)
+    if room_kernel_only:
         per_chain += (args.waves + args.tail) * int(1.5 * half_bytes)
     free_b, _total_b = torch.cuda.mem_get_info()
     chains_asked = n_chains
@@ -644,6 +656,8 @@ def main():
     decode_exchange = None
     if args.mode == "decode":
         dt, dt_enq = timed(args.warmup, args.steps)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, params, chains, n_host)
         decode_exchange = list(exchange_stats)
         up_s = sum(be_k.upload_s for _, be_k, _, _ in chains)
         n_up = sum(be_k.uploads for _, be_k, _, _ in chains)
@@ -657,7 +671,7 @@ def main():
         up_bytes = sum(eng.upload_bytes() for eng in engines)
         host_profile["MB_over_pcie_per_picture"] = round(up_bytes / max(n_up, 1) / 1e6, 3)
         host_profile["pcie_GBps_in_region"] = round(up_bytes / dt / 1e9, 2)
-        decode = dict(dt=dt, dt_enqueue=dt_enq, roofline=collect(dt, args.steps) if rank == 0 else None, host_profile=host_profile,
+        decode = dict(dt=dt, dt_enqueue=dt_enq, roofline=collect(dt, args.steps) if rank == 0 and args.full else None, host_profile=host_profile,
                       upload_ms_per_picture=round(up_s * 1e3 / max(n_up, 1), 4),
                       host_ms_per_picture=dict(upload=round(up_s * 1e3 / max(n_up, 1), 4), execute_enqueue_incl_wait_for_preparation=round(ex_s * 1e3 / max(n_up, 1), 4),
                                                release=round(rl_s * 1e3 / max(n_up, 1), 4)))
@@ -672,13 +686,15 @@ def main():
                     be_k.make_resident()
         kdt, kdt_enq = timed(k_warm, k_steps)
         if args.mode == "kernel_only":
+            if args.dump_outputs and rank == 0:
+                dump_outputs(args.dump_outputs, params, chains, n_host)
             decode_exchange = list(exchange_stats)
-        kernel_only = dict(dt=kdt, dt_enqueue=kdt_enq, roofline=collect(kdt, k_steps) if rank == 0 else None)
+        kernel_only = dict(dt=kdt, dt_enqueue=kdt_enq, roofline=collect(kdt, k_steps) if rank == 0 and args.full else None)
 
     # the pictures of the timed regions are real pictures: one chain per (stream, host GOP) — together every distinct work list of the
     # run — against the checker (bit-exact) before anything is printed
     check = None
-    if rank == 0 and not args.no_check:
+    if rank == 0 and args.full and not args.no_check:
         seen, picked = set(), []
         for k, ch in enumerate(chains):
             key = (k % n_streams, k % n_host)
@@ -754,7 +770,7 @@ def main():
         eng.close()
     if rank == 0:
         out["cpu_baseline"] = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(params, plan_kwargs)
             dec = decoder_baseline(params)
             if dec is not None:
@@ -764,7 +780,7 @@ def main():
                         out["cpu_baseline"][k] = dec[k]["Mpixels_per_s"]
                 out["cpu_baseline"]["cpu_model"] = dec["cpu_model"]
         out["end_to_end"] = None
-        if world == 1 and not args.no_end_to_end and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_end_to_end and not args.no_cpu_baseline:
             try:
                 out["end_to_end"] = end_to_end()
             except Exception as exc:      # noqa: BLE001 - the bench line must come out
@@ -801,6 +817,45 @@ def check_pictures(params, chain, world):
         if world > 1:                                        # keep going from the engine's pictures: remote references are inputs
             want[host_id[pic.name]] = pics[host_id[pic.name]].copy()
     return dict(ok=not bad, pictures=len(names), mismatching=bad, checker="oracle/liboracle.so (pinned against the reference, tests/)")
+
+
+DUMP_BYTES = 48 << 20            # --dump-outputs: float32 bytes written in all (a 4K picture alone is 12.4 M samples)
+DUMP_CHAINS = 8                  # at most this many chains are downloaded
+DUMP_SEED = 0x4F555450
+
+
+def dump_outputs(out_dir, params, chains, n_host):
+    """--dump-outputs: what the timed path handed its caller in the last step — the decoded pictures, as oh_pic_download returns
+    their visible planes — for chains 0 .. min(n_host, DUMP_CHAINS) - 1 (chain k decodes host GOP k mod n_host, so these are the
+    distinct outputs of the run), every picture the chain decodes in decode order.  Each plane is sampled at the same fixed, seeded
+    positions in every picture and every run with the same arguments: DIR/luma.npy, DIR/cb.npy, DIR/cr.npy (4:0:0: luma only),
+    float32 [pictures][samples], pictures in chain order, DUMP_BYTES in all."""
+    import numpy as np
+
+    from openhevc_amd import frame as F
+    picked = chains[:max(1, min(n_host, DUMP_CHAINS))]
+    names = [p.name for p in picked[0][0].pictures()]
+    n_pics = len(picked) * len(names)
+    n_planes = F.n_planes(params)
+    weight = [2] + [1] * (n_planes - 1)                    # luma gets as many samples as both chroma planes together
+    where = []
+    for c in range(n_planes):
+        w, h = F.plane_dims(params, c)
+        k = min(w * h, DUMP_BYTES // 4 // n_pics * weight[c] // sum(weight))
+        idx = np.sort(np.random.default_rng(DUMP_SEED + c).choice(w * h, size=k, replace=False))
+        where.append((idx // w, idx % w))
+    out = [np.empty((n_pics, len(rows)), np.float32) for rows, _ in where]
+    i = 0
+    for _, be, _, _ in picked:
+        be.engine.sync()
+        for n in names:
+            hp = be.engine.pic_download(be.ids[n], params)
+            for c, (rows, cols) in enumerate(where):
+                out[c][i] = hp.visible(c)[rows, cols]
+            i += 1
+    os.makedirs(out_dir, exist_ok=True)
+    for c, a in enumerate(out):
+        np.save(os.path.join(out_dir, ("luma", "cb", "cr")[c] + ".npy"), a)
 
 
 if __name__ == "__main__":

@@ -28,7 +28,7 @@ def _free_port():
 def test_two_ranks_on_one_gpu(extra):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--workload", "480p_main8",
-           "--chains", "4", "--streams", "2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"] + extra
+           "--chains", "4", "--streams", "2", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=850, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
