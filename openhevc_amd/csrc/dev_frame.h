@@ -27,11 +27,11 @@ struct DevMcJob {
 };                                /* 20 bytes */
 enum { OH_MCF_FROM_L1 = 1 };      /* uni-prediction whose only list is list 1 (selects the weights) */
 
-/* LDS layout of the intra CTU kernel.  The sample area (uint16 units) holds per plane `main`: hc rows of
+/* LDS layout of the staged intra kernel.  The sample area (uint16 units) holds per plane `main`: hc rows of
  * rs = wc + 4 entries, sample (x,y) at [y*rs + x + 4] (column -1 at +3), then per plane `top`: row -1,
  * sample x at [x + 4], x in [-1, 2*wc).  The host resolves block offsets into it (DevIntra.cm_off/top_off);
  * the per-launch arrays behind it (descriptors, sub-level table, residual, per-wave edges) are sized by
- * the host from the level's CTUs (OhIntraLaunch). */
+ * the host from the launch's CTUs (OhIntraLaunch). */
 #define OH_CTU_MAX 64
 #define OH_MAX_CTU_BLOCKS 768                      /* 64x64 4:4:4 all 4x4 */
 #define OH_INTRA_WAVE_LDS 576                      /* per-wave edge arrays: 132 ints for one block or 4 x 36 ints for four
@@ -55,8 +55,7 @@ static __host__ __device__ inline OhCtuAreas oh_ctu_areas(int log2_ctb, int chro
     a.total = off;
     return a;
 }
-struct OhIntraLaunch {                             /* one wavefront level of a batch of pictures = one launch */
-    uint32_t level;                                /* index into DevFrame.lvl_start                           */
+struct OhIntraLaunch {                             /* the staged form's launch over a batch of pictures (intra.hip: intra_dag_kernel) */
     uint32_t off_items, off_sub, off_small, off_res, off_wave, lds_bytes;   /* byte offsets into the dynamic LDS block */
     uint32_t waves;                                /* waves per workgroup (CTU)                               */
     uint32_t staged;                               /* 1: the CTUs' residual spans are staged in LDS (all contiguous, and the launch is one the chip holds at once);
@@ -107,7 +106,7 @@ struct DevCross { uint16_t x, y; uint8_t c_idx, log2_size, flags; int8_t scale; 
  * sizes the launches (the host reads it — a few hundred bytes, copied to pinned memory behind the kernels — before the first
  * execute of the list) */
 enum { OH_PE_OK = 0, OH_PE_PU = 1, OH_PE_TU = 2, OH_PE_INTRA = 3, OH_PE_INTRA_TABLES = 4 };
-struct DevLevelStat {                 /* one intra wavefront level: what sizes the launch that runs it */
+struct DevLevelStat {                 /* one intra wavefront level: the levels' maxima and sums size the staged launch */
     uint32_t n_ctu, max_items, max_sub, max_res, staged, pad;
     uint64_t sum_items, sum_sub;
 };                                    /* 40 bytes */
@@ -124,7 +123,7 @@ enum { OH_AUX_PASSES = 0xffff,        /* wave passes of the entry: groups of fou
        OH_AUX_AWAITED = 1u << 30,     /* another entry waits for this one: it must publish its samples (release) and set ctu_done */
        OH_AUX_RES_SCATTERED = 1u << 31 };   /* its residual blocks do not lie together in the pool: not stageable in LDS */
 /* kernel-side failures latched in OhEngine's error word (reported by oh_engine_sync and everything that waits for the stream) */
-enum { OH_KE_OK = 0, OH_KE_ROW_TIMEOUT = 1, OH_KE_DAG_TIMEOUT = 2 };
+enum { OH_KE_OK = 0, OH_KE_DAG_TIMEOUT = 2 };
 struct OhPrepCounts { uint32_t n_pu, n_mc_luma, n_mc_chroma, n_tu, n_intra, n_sub, n_ictu, n_levels; };
 
 struct DevFrame {
@@ -172,7 +171,6 @@ struct DevFrame {
     uint32_t *intra_perm;             /* [n_intra]: position of block i after the <= 8x8-first partition of its sub-level */
     uint32_t *sub_small_w;            /* = sub_small, writable */
     uint32_t *ctu_seen;               /* [CTBs]: index + 1 of the schedule entry the CTU heads (one at most), 0: no intra block in it */
-    uint32_t *row_progress;           /* [CTB rows]: CTUs of the row finished by intra_rows_kernel */
     uint32_t *ctu_aux;                /* [n_ictu]: OH_AUX_*: wave passes of the entry, the neighbour CTUs its blocks read, flags */
     /* the schedule as a dependency graph (intra.hip: intra_dag_kernel / intra_direct_kernel run a whole picture in ONE launch):
      * entry k starts once the entries ctu_wait[4k .. 4k+3] (left, up-left, up, up-right neighbour CTUs of a LOWER level; ~0: none)
@@ -181,7 +179,7 @@ struct DevFrame {
     uint32_t *ctu_done;               /* [n_ictu] */
     uint32_t *ctu_lvl;                /* [n_ictu]: wavefront level of the entry (scratch of the preparation) */
     uint32_t *ctu_order;              /* [n_ictu]: dispatch order of intra_direct_kernel: entries on dependency chains first (prep_intra_order) */
-    uint32_t *err_word;               /* pinned host memory of the engine: [0] OH_KE_* of the first kernel-side failure, [1] cur_pic, [2] entry / row */
+    uint32_t *err_word;               /* pinned host memory of the engine: [0] OH_KE_* of the first kernel-side failure, [1] cur_pic, [2] schedule entry */
     int32_t   cur_pic_id;             /* for the error report */
     void     *summary;                /* DevSummary + DevLevelStat[n_levels] */
     void     *summary_host;           /* pinned host copy, written by prep_finish (no D2H copy on the stream) */

@@ -65,7 +65,7 @@ struct OhDevFrame {
     uint32_t   prep_err = 0, n_levels = 0;
     uint32_t   intra_area64 = 0, max_passes = 0;   /* from the summary: samples of the intra blocks / 64; wave passes of the heaviest CTU */
     const struct OhEngine *owner = nullptr;   /* picture ids and arenas belong to one engine */
-    struct Level {                        /* one wavefront level: what sizes the launch that runs it */
+    struct Level {                        /* one wavefront level: the levels' maxima and sums size the staged intra launch */
         uint32_t n_ctu, max_items, max_sub, max_res;
         bool     staged;                  /* every CTU has its residual span contiguous (stageable in LDS) */
         uint64_t sum_items, sum_sub;
@@ -140,9 +140,9 @@ struct OhEngine {
     bool        own_stream = true;
     std::vector<Pic> pics;
     std::string err;
-    int         profile = 0;             /* 0 off, 1 events between passes, 2 also around every intra launch */
+    int         profile = 0;             /* 0 off, 1 events between passes, 2 also around every batch's intra launches */
     std::vector<EventSet> ev_pool, ev_pending;
-    std::vector<hipEvent_t> lev_pool, lev_pending;   /* per-launch event pairs of the intra pass (profile mode) */
+    std::vector<hipEvent_t> lev_pool, lev_pending;   /* event pairs around every batch's intra launches (profile mode) */
     double      intra_launch_ms = 0;
     uint64_t    intra_launches = 0;
     double      pass_ms[OH_N_PASSES] = {};
@@ -167,8 +167,8 @@ struct OhEngine {
     uint64_t    up_bytes = 0;                    /* bytes of work lists sent over PCIe since the last reset */
     uint64_t   *dbg = nullptr;           /* diagnostics (OHEVC_STAMPS=1 + a -DOH_STAMPS build) */
     /* what a kernel can tell the host when it cannot go on (the table slots and the passes have no error channel: hevcdsp.h's slots
-     * return void): four words of pinned host memory, [0] OH_KE_* of the first failure, [1] picture id, [2] schedule entry / CTB
-     * row; read by everything that waits for the stream (kernel_error) */
+     * return void): four words of pinned host memory, [0] OH_KE_* of the first failure, [1] picture id, [2] schedule
+     * entry; read by everything that waits for the stream (kernel_error) */
     /* a ring of events, one behind every executed batch: a download of a finished picture waits for ITS batch (on the download
      * stream), not for everything enqueued since — a decoder fetches the picture it outputs while the passes of the pictures it
      * submitted later keep running */
@@ -221,11 +221,9 @@ static int kernel_error(OhEngine *e)
 {
     if (!e->kerr || !e->kerr[0])
         return OH_OK;
-    const uint32_t code = e->kerr[0], pic = e->kerr[1], where = e->kerr[2];
+    const uint32_t pic = e->kerr[1], where = e->kerr[2];     /* kerr[0] = OH_KE_DAG_TIMEOUT, the only code */
     e->kerr[0] = 0;
-    FAIL(e, OH_E_HIP, code == OH_KE_ROW_TIMEOUT
-             ? "intra pass (CTB rows in one launch): picture %u, CTB row %u gave up waiting for the row above; the picture's samples are not valid"
-             : "intra pass (one launch per picture): picture %u, schedule entry %u gave up waiting for a neighbour CTU; the picture's samples are not valid",
+    FAIL(e, OH_E_HIP, "intra pass (one launch per picture): picture %u, schedule entry %u gave up waiting for a neighbour CTU; the picture's samples are not valid",
          pic, where);
 }
 struct HostTimer {                       /* adds the scope's wall time to one slot of OhEngine::host_ms */
@@ -1172,7 +1170,6 @@ static int upload_one(OhEngine *e, const OhFrame *f, OhDevFrame **out)
     int s_ictu = add(nullptr, (size_t)cnt.n_ictu * sizeof(DevIntraCtu));
     int s_small = add(nullptr, (size_t)cnt.n_sub * sizeof(uint32_t));
     int s_perm = add(nullptr, (size_t)f->n_intra * sizeof(uint32_t));
-    int s_rowp = add(nullptr, cnt.n_intra ? (size_t)oh_ctb_height(&p) * sizeof(uint32_t) : 0);
     int s_wait = add(nullptr, (size_t)cnt.n_ictu * 4 * sizeof(uint32_t));
     int s_done = add(nullptr, (size_t)cnt.n_ictu * sizeof(uint32_t));
     int s_clvl = add(nullptr, (size_t)cnt.n_ictu * sizeof(uint32_t));
@@ -1264,7 +1261,6 @@ static int upload_one(OhEngine *e, const OhFrame *f, OhDevFrame **out)
     hd.sao_pending = has_pend ? AT(const uint8_t *, s_pend) : nullptr;
     hd.pu_off = AT(const uint32_t *, s_puoff); hd.ctu_aux = AT(uint32_t *, s_aux); hd.tu_keep = AT(uint8_t *, s_keep); hd.tu_cursor = AT(uint32_t *, s_cursor);
     hd.intra_perm = AT(uint32_t *, s_perm); hd.ctu_seen = AT(uint32_t *, s_seen); hd.summary = AT(void *, s_sum);
-    hd.row_progress = AT(uint32_t *, s_rowp);
     hd.ctu_wait = AT(uint32_t *, s_wait); hd.ctu_done = AT(uint32_t *, s_done); hd.ctu_lvl = AT(uint32_t *, s_clvl); hd.ctu_order = AT(uint32_t *, s_cord);
     hd.err_word = e->kerr; hd.cur_pic_id = f->cur_pic;
 #undef AT
@@ -1475,9 +1471,6 @@ static int read_summary(OhEngine *e, OhDevFrame *df, int index)
     return OH_OK;
 }
 
-/* Execute n mutually independent pictures: every pass is one launch over all of them (chunks of
- * OH_MAX_BATCH).  Nothing orders the pictures of a batch against each other, so none of them may be a
- * reference of another one. */
 /* the CTUs' residual spans staged in LDS, or every block fetching its own from the pool one sub-level ahead (intra.hip: slots_prepare)?
  * Staging costs ~11 KB of LDS per workgroup in a launch that holds one all-intra CTU, i.e. workgroups per CU (OHEVC_INTRA_RES_LDS=0 / 1
  * forces one way: experiments) */
@@ -1490,6 +1483,96 @@ static bool res_in_lds(const OhEngine *e, uint64_t workgroups)
     return workgroups <= (uint64_t)e->n_cu;
 }
 
+/* The intra pass of a batch (intra.hip), one launch per form:
+ *   direct  a wave per CTU working on the picture in HBM — pictures whose intra blocks cover less than half of their samples
+ *           (B / P pictures);
+ *   dag     a workgroup per CTU with the CTU staged in LDS — the others (I pictures).
+ * OHEVC_INTRA_MODE=dag / direct forces one form for every picture.  A CTU takes the schedule entry of the ticket it draws when it
+ * starts and waits only for lower tickets, so the launch drains whatever the dispatch order; a wait that gives up anyway (bounded by
+ * OHEVC_SPIN_LIMIT) is reported by kernel_error. */
+static int intra_pass(OhEngine *e, OhDevFrame *const *fr, int nb, const OhBatch *all, hipStream_t st)
+{
+    const OhPicParams *p = &fr[0]->p;
+    static const char *menv = getenv("OHEVC_INTRA_MODE");
+    const bool force_dag = menv && !strcmp(menv, "dag"), force_direct = menv && !strcmp(menv, "direct");
+    OhBatch bd, bs;                                  /* direct / staged dag */
+    memset(&bd, 0, sizeof(bd)); memset(&bs, 0, sizeof(bs));
+    int nd = 0, ns = 0;
+    uint32_t max_ictu_d = 0, max_ictu_s = 0, max_ictu_all = 0, max_items = 1, max_sub = 1, max_res = 0;
+    uint64_t sum_items = 0, sum_sub = 0, total_entries = 0;
+    bool staged = true;
+    const uint64_t pic_samples64 = ((uint64_t)p->width * p->height * (p->chroma_format_idc == 0 ? 2 : p->chroma_format_idc == 1 ? 3 : p->chroma_format_idc == 2 ? 4 : 6) / 2) >> 6;
+    for (int i = 0; i < nb; i++) {
+        if (fr[i]->levels.empty())
+            continue;
+        max_ictu_all = std::max(max_ictu_all, fr[i]->cnt.n_ictu);
+        const bool sparse = force_direct || (!force_dag && (uint64_t)fr[i]->intra_area64 * 2 < pic_samples64);
+        if (sparse) {
+            bd.f[nd++] = fr[i]->d;
+            max_ictu_d = std::max(max_ictu_d, fr[i]->cnt.n_ictu);
+            continue;
+        }
+        bs.f[ns++] = fr[i]->d;
+        max_ictu_s = std::max(max_ictu_s, fr[i]->cnt.n_ictu);
+        total_entries += fr[i]->cnt.n_ictu;
+        for (const OhDevFrame::Level &L : fr[i]->levels) {
+            max_items = std::max(max_items, L.max_items); max_sub = std::max(max_sub, L.max_sub); max_res = std::max(max_res, L.max_res);
+            sum_items += L.sum_items; sum_sub += L.sum_sub;
+            staged = staged && (L.staged || !L.n_ctu);
+        }
+    }
+    if (!nd && !ns)
+        return OH_OK;
+    /* the pass's launches as one bracket (they overlap nothing else on this stream); per-launch events are a sample, not a log:
+     * stop bracketing once 100 k launches are pending collection */
+    hipEvent_t a = nullptr, b = nullptr;
+    if (e->profile > 1 && e->lev_pending.size() < 200000) {
+        for (hipEvent_t *pe : { &a, &b }) {
+            if (!e->lev_pool.empty()) { *pe = e->lev_pool.back(); e->lev_pool.pop_back(); }
+            else HIPCHK(e, hipEventCreate(pe));
+        }
+    }
+    uint32_t *tk = e->tickets + (size_t)OhEngine::TICKET_WORDS * (e->ticket_seq++ % OhEngine::TICKET_RING);
+    ohk_intra_dag_reset(all, nb, max_ictu_all, tk, st);
+    if (a) HIPCHK(e, hipEventRecord(a, st));
+    if (nd)
+        ohk_intra_direct(&bd, nd, p, max_ictu_d, tk, e->spin_limit, st);
+    if (ns) {
+        OhIntraLaunch IL;
+        /* residual spans in LDS only while the chip holds the whole launch (a picture alone); else the blocks fetch theirs a sub-level ahead */
+        IL.staged = staged && res_in_lds(e, total_entries / 8);
+        /* waves per CTU: as many as blocks run side by side in a sub-level (more only hold LDS and wave slots); a small batch cannot
+         * fill the chip anyway: spend the waves on the single picture's latency (OHEVC_INTRA_WAVES forces them: experiments) */
+        static const char *wenv = getenv("OHEVC_INTRA_WAVES");
+        const double par = sum_sub ? (double)sum_items / (double)sum_sub : 1.0;
+        IL.waves = wenv ? (uint32_t)atoi(wenv) : par > (nb < 8 ? 2.5 : 4.5) ? 8 : par > 1.25 ? 4 : 2;
+        if (IL.waves != 2 && IL.waves != 4 && IL.waves != 8) IL.waves = 8;
+        /* sub-levels go round-robin to `phases` groups of waves (intra.hip): a group prepares its next sub-level while another
+         * finishes its own, so at least two */
+        static const char *penv = getenv("OHEVC_INTRA_PHASES");
+        IL.phases = penv ? (uint32_t)atoi(penv) : 2u;
+        if (IL.phases < 2 || IL.phases > IL.waves || IL.waves % IL.phases) IL.phases = 2;
+        const OhCtuAreas areas = oh_ctu_areas(p->log2_ctb_size, p->chroma_format_idc);
+        size_t off = align_up((size_t)areas.total * sizeof(uint16_t), 16);
+        IL.off_items = (uint32_t)off; off += (size_t)max_items * sizeof(DevIntra);
+        IL.off_sub = (uint32_t)off;   off += ((size_t)max_sub + 1) * sizeof(uint32_t);
+        IL.off_small = (uint32_t)off; off = align_up(off + (size_t)max_sub * sizeof(uint32_t), 16);
+        IL.off_res = (uint32_t)off;   off = align_up(off + (size_t)(IL.staged ? max_res : 0) * sizeof(int16_t), 16);
+        IL.off_wave = (uint32_t)off;  off += (size_t)IL.waves * OH_INTRA_WAVE_LDS;
+        IL.lds_bytes = (uint32_t)off;
+        ohk_intra_dag(&bs, ns, p, &IL, max_ictu_s, tk + OH_MAX_BATCH * 32, e->spin_limit, st);
+    }
+    if (b) {
+        HIPCHK(e, hipEventRecord(b, st));
+        e->lev_pending.push_back(a);
+        e->lev_pending.push_back(b);
+    }
+    return OH_OK;
+}
+
+/* Execute n mutually independent pictures: every pass is one launch over all of them (chunks of
+ * OH_MAX_BATCH).  Nothing orders the pictures of a batch against each other, so none of them may be a
+ * reference of another one. */
 extern "C" int oh_frames_execute(OhEngine *e, OhDevFrame *const *dfs, int n)
 {
     if (!e || n < 0 || (n && !dfs))
@@ -1565,9 +1648,7 @@ extern "C" int oh_frames_execute(OhEngine *e, OhDevFrame *const *dfs, int n)
             sg->busy = true;
         }
     }
-    /* per-launch events are a sample, not a log: stop bracketing once 100 k launches are pending collection */
-    const bool prof = e->profile > 0, prof_launch = e->profile > 1 && e->lev_pending.size() < 200000;
-    static const char *wenv = getenv("OHEVC_INTRA_WAVES");            /* experiments: force the waves per CTU */
+    const bool prof = e->profile > 0;
     for (int c0 = 0; c0 < n; c0 += OH_MAX_BATCH) {
         const int nb = n - c0 < OH_MAX_BATCH ? n - c0 : OH_MAX_BATCH;
         OhDevFrame *const *fr = dfs + c0;
@@ -1591,12 +1672,10 @@ extern "C" int oh_frames_execute(OhEngine *e, OhDevFrame *const *dfs, int n)
         OhBatch all;
         memset(&all, 0, sizeof(all));
         uint32_t max_luma = 0, max_chroma = 0, max_tu[4] = { 0, 0, 0, 0 };
-        size_t max_levels = 0;
         for (int i = 0; i < nb; i++) {
             all.f[i] = fr[i]->d;
             max_luma = std::max(max_luma, fr[i]->n_mc_luma); max_chroma = std::max(max_chroma, fr[i]->n_mc_chroma);
             for (int k = 0; k < 4; k++) max_tu[k] = std::max(max_tu[k], fr[i]->tu_cnt[k]);
-            max_levels = std::max(max_levels, fr[i]->levels.size());
         }
         ohk_inter(&all, nb, p, max_luma, max_chroma, st);
         MARK(OH_PASS_INTER);
@@ -1607,202 +1686,8 @@ extern "C" int oh_frames_execute(OhEngine *e, OhDevFrame *const *dfs, int n)
             ohk_cross(&all, nb, p, max_cross, st);
         }
         MARK(OH_PASS_RESIDUAL);
-        const OhCtuAreas areas = oh_ctu_areas(p->log2_ctb_size, p->chroma_format_idc);
-        /* How the intra pass of each picture runs (intra.hip):
-         *   direct  one launch, a wave per CTU working on the picture in HBM — pictures whose intra blocks cover less than half of
-         *           their samples (B / P pictures);
-         *   dag     one launch, a workgroup per CTU with the CTU staged in LDS, CTUs waiting for their neighbours' flags — the
-         *           others (I pictures);
-         *   levels  one launch per wavefront level (rounds 1-2), or CTU rows in one launch for a few deep pictures: kept for
-         *           comparison and as the form that needs nothing of the dispatcher (OHEVC_INTRA_MODE=levels).
-         * The one-launch forms never deadlock as long as the hardware hands out the workgroups of a grid in id order (per XCD):
-         * an entry only waits for lower ids.  HIP does not promise that order; it is what gfx950 does (guide: "blocks are dealt
-         * round-robin over the 8 XCDs"), every wait is bounded, and a wait that gives up is reported (kernel_error) instead of
-         * producing a silently wrong picture. */
-        static const char *menv = getenv("OHEVC_INTRA_MODE");
-        const int mode_env = !menv ? 0 : !strcmp(menv, "levels") ? 1 : !strcmp(menv, "dag") ? 2 : !strcmp(menv, "direct") ? 3 : 0;
-        bool in_rows[OH_MAX_BATCH] = {};                     /* handled by a one-launch form: not in the level launches below */
-        if (mode_env != 1) {
-            OhBatch bd, bs;                                  /* direct / staged dag */
-            memset(&bd, 0, sizeof(bd)); memset(&bs, 0, sizeof(bs));
-            int nd = 0, nsd = 0;
-            uint32_t max_ictu_d = 0, max_ictu_s = 0, max_ictu_all = 0, max_items = 1, max_sub = 1, max_res = 0;
-            uint64_t sum_items = 0, sum_sub = 0, total_entries = 0;
-            bool staged = true;
-            const uint64_t pic_samples64 = ((uint64_t)p->width * p->height * (p->chroma_format_idc == 0 ? 2 : p->chroma_format_idc == 1 ? 3 : p->chroma_format_idc == 2 ? 4 : 6) / 2) >> 6;
-            for (int i = 0; i < nb; i++) {
-                if (fr[i]->levels.empty())
-                    continue;
-                in_rows[i] = true;
-                max_ictu_all = std::max(max_ictu_all, fr[i]->cnt.n_ictu);
-                const bool sparse = mode_env == 3 || (mode_env == 0 && (uint64_t)fr[i]->intra_area64 * 2 < pic_samples64);
-                if (sparse) {
-                    bd.f[nd++] = fr[i]->d;
-                    max_ictu_d = std::max(max_ictu_d, fr[i]->cnt.n_ictu);
-                    continue;
-                }
-                bs.f[nsd++] = fr[i]->d;
-                max_ictu_s = std::max(max_ictu_s, fr[i]->cnt.n_ictu);
-                total_entries += fr[i]->cnt.n_ictu;
-                for (const OhDevFrame::Level &L : fr[i]->levels) {
-                    max_items = std::max(max_items, L.max_items); max_sub = std::max(max_sub, L.max_sub); max_res = std::max(max_res, L.max_res);
-                    sum_items += L.sum_items; sum_sub += L.sum_sub;
-                    staged = staged && (L.staged || !L.n_ctu);
-                }
-            }
-            hipEvent_t a = nullptr, b = nullptr;
-            if (prof_launch && (nd || nsd)) {                 /* the pass's launches as one bracket: they overlap nothing else on this stream */
-                for (hipEvent_t *pe : { &a, &b }) {
-                    if (!e->lev_pool.empty()) { *pe = e->lev_pool.back(); e->lev_pool.pop_back(); }
-                    else HIPCHK(e, hipEventCreate(pe));
-                }
-            }
-            uint32_t *tk = e->tickets + (size_t)OhEngine::TICKET_WORDS * (e->ticket_seq++ % OhEngine::TICKET_RING);
-            if (nd || nsd)
-                ohk_intra_dag_reset(&all, nb, max_ictu_all, tk, st);
-            if (a) HIPCHK(e, hipEventRecord(a, st));
-            if (nd)
-                ohk_intra_direct(&bd, nd, p, max_ictu_d, tk, e->spin_limit, st);
-            if (nsd) {
-                OhIntraLaunch IL;
-                /* residual spans in LDS only while the chip holds the whole launch (a picture alone); else the blocks fetch theirs a sub-level ahead */
-                IL.staged = staged && res_in_lds(e, total_entries / 8);
-                IL.level = 0;
-                const double par = sum_sub ? (double)sum_items / (double)sum_sub : 1.0;
-                IL.waves = wenv ? (uint32_t)atoi(wenv) : par > (nb < 8 ? 2.5 : 4.5) ? 8 : par > 1.25 ? 4 : 2;
-                if (IL.waves != 2 && IL.waves != 4 && IL.waves != 8) IL.waves = 8;
-                static const char *penv = getenv("OHEVC_INTRA_PHASES");
-                IL.phases = penv ? (uint32_t)atoi(penv) : 2u;
-                if (IL.phases < 2 || IL.phases > IL.waves || IL.waves % IL.phases) IL.phases = 2;
-                size_t off = align_up((size_t)areas.total * sizeof(uint16_t), 16);
-                IL.off_items = (uint32_t)off; off += (size_t)max_items * sizeof(DevIntra);
-                IL.off_sub = (uint32_t)off;   off += ((size_t)max_sub + 1) * sizeof(uint32_t);
-                IL.off_small = (uint32_t)off; off = align_up(off + (size_t)max_sub * sizeof(uint32_t), 16);
-                IL.off_res = (uint32_t)off;   off = align_up(off + (size_t)(IL.staged ? max_res : 0) * sizeof(int16_t), 16);
-                IL.off_wave = (uint32_t)off;  off += (size_t)IL.waves * OH_INTRA_WAVE_LDS;
-                IL.lds_bytes = (uint32_t)off;
-                ohk_intra_dag(&bs, nsd, p, &IL, max_ictu_s, tk + OH_MAX_BATCH * 32, e->spin_limit, st);
-            }
-            if (b) {
-                HIPCHK(e, hipEventRecord(b, st));
-                e->lev_pending.push_back(a);
-                e->lev_pending.push_back(b);
-            }
-        }
-        /* pictures whose levels are (nearly) the full CTU wavefront — I pictures — may run as CTU rows in ONE launch (intra.hip:
-         * intra_rows_kernel): their cost is then the critical path at the average CTU length, not the sum of the levels' slowest
-         * CTUs plus a launch per level (4K I picture alone: 6.6 ms against 9.1 ms).  A row's workgroup holds its slot while it
-         * waits for the row above, so this only pays while the rows of the batch's I pictures leave the chip room (one
-         * workgroup per CU at most); larger batches fill the level launches anyway and keep them, as do the pictures with a
-         * handful of levels (measured: 32 I pictures per batch as rows cost the 4-stream bench 22 %). */
-        static const char *renv = getenv("OHEVC_INTRA_ROWS");
-        const size_t row_threshold = renv && !atoi(renv) ? (size_t)-1 : (size_t)oh_ctb_width(p);
-        if (mode_env == 1) {
-            OhBatch rows;
-            memset(&rows, 0, sizeof(rows));
-            int nr = 0;
-            uint32_t max_items = 1, max_sub = 1, max_res = 0;
-            bool staged = true;
-            int deep = 0;
-            for (int i = 0; i < nb; i++)
-                deep += fr[i]->levels.size() >= row_threshold && !fr[i]->levels.empty();
-            if (deep * oh_ctb_height(p) > e->n_cu)
-                deep = 0;
-            for (int i = 0; i < nb && deep; i++) {
-                if (fr[i]->levels.size() < row_threshold || fr[i]->levels.empty())
-                    continue;
-                in_rows[i] = true;
-                rows.f[nr++] = fr[i]->d;
-                for (const OhDevFrame::Level &L : fr[i]->levels) {
-                    max_items = std::max(max_items, L.max_items); max_sub = std::max(max_sub, L.max_sub); max_res = std::max(max_res, L.max_res);
-                    staged = staged && (L.staged || !L.n_ctu);
-                }
-            }
-            if (nr) {
-                OhIntraLaunch IL;
-                IL.staged = staged && res_in_lds(e, (uint64_t)nr * oh_ctb_height(p)); IL.level = 0; IL.waves = 8; IL.phases = 2;
-                size_t off = align_up((size_t)areas.total * sizeof(uint16_t), 16);
-                IL.off_items = (uint32_t)off; off += (size_t)max_items * sizeof(DevIntra);
-                IL.off_sub = (uint32_t)off;   off += ((size_t)max_sub + 1) * sizeof(uint32_t);
-                IL.off_small = (uint32_t)off; off = align_up(off + (size_t)max_sub * sizeof(uint32_t), 16);
-                IL.off_res = (uint32_t)off;   off = align_up(off + (size_t)(IL.staged ? max_res : 0) * sizeof(int16_t), 16);
-                IL.off_wave = (uint32_t)off;  off += (size_t)IL.waves * OH_INTRA_WAVE_LDS;
-                IL.lds_bytes = (uint32_t)off;
-                hipEvent_t a = nullptr, b = nullptr;
-                if (prof_launch) {                            /* counted like a level launch: one launch of the pass */
-                    for (hipEvent_t *pe : { &a, &b }) {
-                        if (!e->lev_pool.empty()) { *pe = e->lev_pool.back(); e->lev_pool.pop_back(); }
-                        else HIPCHK(e, hipEventCreate(pe));
-                    }
-                    HIPCHK(e, hipEventRecord(a, st));
-                }
-                ohk_intra_rows(&rows, nr, p, &IL, e->spin_limit, st);
-                if (prof_launch) {
-                    HIPCHK(e, hipEventRecord(b, st));
-                    e->lev_pending.push_back(a);
-                    e->lev_pending.push_back(b);
-                }
-            }
-        }
-        for (size_t l = 0; l < max_levels; l++) {
-            /* the pictures that have this level, and the LDS carve-up that fits all of them */
-            OhBatch sub;
-            memset(&sub, 0, sizeof(sub));
-            int ns = 0;
-            uint32_t max_ctu = 0, max_items = 1, max_sub = 1, max_res = 0;
-            bool staged = true;
-            uint64_t sum_items = 0, sum_sub = 0;
-            for (int i = 0; i < nb; i++) {
-                if (l >= fr[i]->levels.size() || in_rows[i])
-                    continue;
-                const OhDevFrame::Level &L = fr[i]->levels[l];
-                sub.f[ns++] = fr[i]->d;
-                max_ctu = std::max(max_ctu, L.n_ctu); max_items = std::max(max_items, L.max_items);
-                max_sub = std::max(max_sub, L.max_sub); max_res = std::max(max_res, L.max_res);
-                sum_items += L.sum_items; sum_sub += L.sum_sub;
-                staged = staged && L.staged;
-            }
-            if (!ns)
-                continue;                                  /* every picture that has this level runs as rows */
-            OhIntraLaunch IL;
-            IL.staged = staged && res_in_lds(e, (uint64_t)max_ctu * ns);
-            IL.level = (uint32_t)l;
-            /* waves per CTU: as many as blocks run side by side in a sub-level (more only hold LDS and wave slots) */
-            const double par = sum_sub ? (double)sum_items / (double)sum_sub : 1.0;
-            /* a small batch cannot fill the chip anyway: spend the waves on the single picture's latency (8 as soon as
-             * sub-levels hold more than ~2 blocks); a large batch is issue-bound and runs best with 4 */
-            IL.waves = wenv ? (uint32_t)atoi(wenv) : par > (nb < 8 ? 2.5 : 4.5) ? 8 : par > 1.25 ? 4 : 2;
-            /* a launch of many more workgroups than the chip holds is bound by workgroups per CU x their latency, not by the latency of
-             * one: two waves per workgroup (twice the workgroups per CU; measured 87.7 against 85.9 Gpix/s, eight waves 76.5) */
-            if (!wenv && (uint64_t)max_ctu * ns > 5ull * (uint64_t)e->n_cu && par <= 4.5) IL.waves = 2;
-            if (IL.waves != 2 && IL.waves != 4 && IL.waves != 8) IL.waves = 8;
-            /* sub-levels go round-robin to `phases` groups of waves (intra.hip): a group prepares its next sub-level while
-             * the others finish theirs */
-            static const char *penv = getenv("OHEVC_INTRA_PHASES");
-            IL.phases = penv ? (uint32_t)atoi(penv) : 2u;
-            if (IL.phases < 2 || IL.phases > IL.waves || IL.waves % IL.phases) IL.phases = 2;   /* a group prepares while another finishes: at least two */
-            size_t off = align_up((size_t)areas.total * sizeof(uint16_t), 16);
-            IL.off_items = (uint32_t)off; off += (size_t)max_items * sizeof(DevIntra);
-            IL.off_sub = (uint32_t)off;   off += ((size_t)max_sub + 1) * sizeof(uint32_t);
-            IL.off_small = (uint32_t)off; off = align_up(off + (size_t)max_sub * sizeof(uint32_t), 16);
-            IL.off_res = (uint32_t)off;   off = align_up(off + (size_t)(IL.staged ? max_res : 0) * sizeof(int16_t), 16);
-            IL.off_wave = (uint32_t)off;  off += (size_t)IL.waves * OH_INTRA_WAVE_LDS;
-            IL.lds_bytes = (uint32_t)off;
-            hipEvent_t a = nullptr, b = nullptr;
-            if (prof_launch) {                            /* bracket every launch: the pass is many dependent launches */
-                for (hipEvent_t *pe : { &a, &b }) {
-                    if (!e->lev_pool.empty()) { *pe = e->lev_pool.back(); e->lev_pool.pop_back(); }
-                    else HIPCHK(e, hipEventCreate(pe));
-                }
-                HIPCHK(e, hipEventRecord(a, st));
-            }
-            ohk_intra_level(&sub, ns, p, &IL, max_ctu, st);
-            if (prof_launch) {
-                HIPCHK(e, hipEventRecord(b, st));
-                e->lev_pending.push_back(a);
-                e->lev_pending.push_back(b);
-            }
-        }
+        if (const int rc = intra_pass(e, fr, nb, &all, st))
+            return rc;
         MARK(OH_PASS_INTRA);
         if (p->deblock_enabled)
             ohk_deblock(&all, nb, p, 0, st);

@@ -8,7 +8,16 @@
  * pass 3: intra prediction as a CTU wavefront — hevcpred_template.c:30-538
  * (constrained_intra_pred_flag == 0), each block followed by its residual (transform_add).
  *
- * One workgroup reconstructs one CTU.  The CTU's samples (with the one-sample border above and
+ * The pass of a batch of pictures is ONE launch in one of two forms, chosen per picture by the engine (engine.hip: intra_pass):
+ *   intra_dag_kernel     a workgroup per schedule entry (a CTU with intra blocks), the CTU staged in LDS (intra_ctu_body,
+ *                        below) — pictures whose intra blocks cover at least half of their samples (I pictures);
+ *   intra_direct_kernel  a wave per schedule entry working on the picture in HBM — the others (B / P pictures).
+ * An entry waits for the entries of the neighbour CTUs its blocks gather from (ctu_wait[], all of a lower wavefront level) and
+ * publishes its own (ctu_done[]).  A workgroup takes the entry of the TICKET it draws when it starts, not of its blockIdx, and a
+ * wait only points at a lower ticket: the lowest unfinished ticket is held by a running workgroup and never waits, so the launch
+ * drains whatever the order in which the hardware dispatches workgroups (intra_dag_kernel).
+ *
+ * Staged form: one workgroup reconstructs one CTU.  The CTU's samples (with the one-sample border above and
  * to the left that intra_pred() gathers from, :164-183), the CTU's block descriptors and residual
  * blocks are staged in LDS once; the waves then take the blocks of the current SUB-LEVEL (blocks
  * of one sub-level never read each other).  Blocks of up to 8x8 samples go four per wave (slots_prepare /
@@ -23,7 +32,7 @@
  *     writes the staged CTU in LDS (for the next sub-level); the finished CTU goes to HBM in one coalesced sweep.
  * Sub-levels are separated by an LDS-only workgroup barrier, so the dependent chain inside a CTU
  * costs a handful of LDS round trips per block inside one CU — no kernel launch, no HBM round
- * trip.  CTUs of one launch are mutually independent (same wavefront level, recorder.c).
+ * trip.
  * ======================================================================================= */
 #define INTRA_MAX_WAVES 8
 #define OH_TICKET_STRIDE 32u                       /* words between ticket counters: a cache line each */
@@ -45,7 +54,7 @@ static __device__ __forceinline__ int wave_shr1(int v, int fill) { return __buil
 static __device__ __forceinline__ int wave_shl1(int v, int fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x130, 0xf, 0xf, false); }
 
 /* four finished samples of one row -> the staged CTU (8-byte aligned by construction); the CTU goes to HBM in one
- * coalesced sweep when its last sub-level is done (intra_ctu_kernel) */
+ * coalesced sweep when its last sub-level is done (intra_ctu_body) */
 static __device__ __forceinline__ void put4(uint16_t *__restrict__ lds, int v0, int v1, int v2, int v3)
 {
     *(uint2v *)lds = uint2v{ (unsigned)(v0 | (v1 << 16)), (unsigned)(v2 | (v3 << 16)) };
@@ -626,7 +635,7 @@ static __device__ __forceinline__ void dag_latch_error(const DevFrame *__restric
     }
 }
 /* called by ONE wave (all 64 lanes): lanes 0..3 poll one awaited entry each */
-static __device__ __forceinline__ void dag_wait_wave(const DevFrame *__restrict__ f, const uint32_t entry, const int lane, const uint32_t spin_limit, const int exp = 0)
+static __device__ __forceinline__ void dag_wait_wave(const DevFrame *__restrict__ f, const uint32_t entry, const int lane, const uint32_t spin_limit)
 {
     const uint32_t w = lane < 4 ? G_CONST(uint32_t, f->ctu_wait)[4 * entry + lane] : ~0u;
     uint32_t *done = f->ctu_done;
@@ -642,7 +651,6 @@ static __device__ __forceinline__ void dag_wait_wave(const DevFrame *__restrict_
         }
         __builtin_amdgcn_s_sleep(8);
     }
-    if (exp & 8) return;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");            /* the awaited CTUs' samples: not from this CU's L1 / stale L2 lines */
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              /* ... and the invalidate has completed before anyone loads */
 }
@@ -657,8 +665,8 @@ static __device__ __forceinline__ void dag_publish_lane(const DevFrame *__restri
 }
 
 /* one CTU by the whole workgroup: schedule entry `entry` of picture f.  Every thread of the workgroup calls it (barriers inside).
- * DAG: the entry waits for / publishes to other entries of the same launch (above). */
-template <typename PX, bool CIP, bool STAGED, bool DAG>
+ * The entry waits for / publishes to other entries of the same launch (above). */
+template <typename PX, bool CIP, bool STAGED>
 static __device__ __forceinline__ void intra_ctu_body(const DevFrame *__restrict__ f, const OhIntraLaunch &L, const uint32_t entry, unsigned char *smem,
                                                       const uint32_t spin_limit)
 {
@@ -703,14 +711,11 @@ static __device__ __forceinline__ void intra_ctu_body(const DevFrame *__restrict
         if (STAGED)
             for (uint32_t e = tid; e < ctu.res_cnt / 4; e += nthr) ((short4v *)res_l)[e] = rsrc[e];
     }
-    uint32_t aux = 0;
-    if (DAG) {
-        /* descriptors and residual are on their way; now the neighbours.  Wave 0 polls and acquires, the barrier holds the others */
-        aux = __builtin_amdgcn_readfirstlane(G_CONST(uint32_t, f->ctu_aux)[entry]);
-        if (aux & OH_AUX_WAITS) {
-            if (wave == 0) dag_wait_wave(f, entry, lane, spin_limit);
-            __syncthreads();
-        }
+    /* descriptors and residual are on their way; now the neighbours.  Wave 0 polls and acquires, the barrier holds the others */
+    const uint32_t aux = __builtin_amdgcn_readfirstlane(G_CONST(uint32_t, f->ctu_aux)[entry]);
+    if (aux & OH_AUX_WAITS) {
+        if (wave == 0) dag_wait_wave(f, entry, lane, spin_limit);
+        __syncthreads();
     }
     /* stage the part of the CTU its blocks read (DevIntraCtu.bx0..by1): samples reconstructed by passes
      * 1-2 (inter), the column left of the CTU and the row above it (up to 2*wc samples: the up-right CTU) —
@@ -795,7 +800,7 @@ static __device__ __forceinline__ void intra_ctu_body(const DevFrame *__restrict
     /* The last sub-level's barrier has been passed.  A CTU that is mostly INTER (B pictures: a few intra blocks scattered over a
      * rectangle that spans the CTU) stores its blocks, a quarter wave per block, instead of the rectangle: measured on the
      * >= 16 k-workgroup launches of B pictures the rectangle's write-back was 19 % of the launch (profiles/r02_intra_staging_experiment.txt) */
-    const bool wt = DAG && (aux & OH_AUX_AWAITED);          /* another CTU of this launch reads these samples: write-through stores, no L2 write-back */
+    const bool wt = (aux & OH_AUX_AWAITED) != 0u;           /* another CTU of this launch reads these samples: write-through stores, no L2 write-back */
     if (blockwise) {
         const uint64_t gp0 = (uint64_t)f->cur.p[0], gp1 = (uint64_t)f->cur.p[1], gp2 = (uint64_t)f->cur.p[2];
         const int st0 = f->cur.stride[0], st1 = f->cur.stride[1];
@@ -845,7 +850,7 @@ static __device__ __forceinline__ void intra_ctu_body(const DevFrame *__restrict
                 }
             }
     }
-    if (DAG && (aux & OH_AUX_AWAITED)) {
+    if (wt) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      /* this wave's stores of the CTU have left */
         __syncthreads();
         if (tid == 0) dag_publish_lane<true>(f, entry);
@@ -864,35 +869,23 @@ static __device__ __forceinline__ void intra_ctu_body(const DevFrame *__restrict
 #endif
 }
 
-/* waves_per_eu(6, 8): 80 VGPRs instead of 86, i.e. six waves per SIMD instead of five for the wide B-picture launches (no spills;
- * asking for seven or eight spills and loses more than the occupancy gains) */
-template <typename PX, bool CIP, bool STAGED>
-__global__ __launch_bounds__(64 * INTRA_MAX_WAVES) __attribute__((amdgpu_waves_per_eu(6, 8))) void intra_ctu_kernel(const OhBatch B, const OhIntraLaunch L)
-{
-    const DevFrame *__restrict__ f = B.f[blockIdx.y];
-    const uint32_t first_ctu = f->lvl_start[L.level];
-    if (blockIdx.x >= f->lvl_start[L.level + 1] - first_ctu)
-        return;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    intra_ctu_body<PX, CIP, STAGED, false>(f, L, first_ctu + blockIdx.x, smem, 0u);
-}
-
-
 /* =========================================================================================
  * The whole picture's intra pass in ONE launch, staged form: a workgroup per schedule entry.  A workgroup does not take the entry of
  * its blockIdx: when it STARTS it draws a ticket from a counter (atomicAdd): ticket t = schedule entry t / pictures of picture
  * t % pictures, i.e. the entries in schedule order (level by level) interleaved over the pictures of the batch.  It stages its
- * entry's descriptors, waits for the entries it depends on (ctu_wait[]: lower tickets), and runs the same body as a level launch.
+ * entry's descriptors, waits for the entries it depends on (ctu_wait[]: lower tickets), and runs intra_ctu_body.
  * A ticket is only ever held by a workgroup that is RUNNING, and a wait only points at lower tickets — drawn earlier, by running
  * workgroups, or finished — so the lowest unfinished ticket never waits: progress depends neither on the order in which the hardware
  * dispatches workgroups nor on what other streams' kernels hold on the chip.  (With entry = blockIdx two such launches on two
  * streams deadlocked: each filled the CUs the other's not-yet-dispatched low ids needed — seen with six streams.  Persistent
  * workgroups looping over tickets are as safe but keep their CUs until the queue is empty: the other streams' kernels, which fill
- * the gaps of this latency-bound pass, lost more than the loop saved.)  No level launches, no launch as long as its slowest CTU: an
- * I picture costs its dependency chain at the CTUs' own lengths and a B picture's handful of levels overlap.
+ * the gaps of this latency-bound pass, lost more than the loop saved.)  No launch per wavefront level, none as long as its slowest
+ * CTU: an I picture costs its dependency chain at the CTUs' own lengths and a B picture's handful of levels overlap.
+ * waves_per_eu(6, 8): 80 VGPRs instead of 86, i.e. six waves per SIMD instead of five for wide launches (no spills; asking for seven
+ * or eight spills and loses more than the occupancy gains).
  * ======================================================================================= */
 template <typename PX, bool CIP, bool STAGED>
-__global__ __launch_bounds__(64 * INTRA_MAX_WAVES) __attribute__((amdgpu_waves_per_eu(6, 8))) void intra_dag_kernel(const OhBatch B, const OhIntraLaunch L, const int n_pics, const uint32_t total, uint32_t *__restrict__ ticket, const uint32_t spin_limit)
+__global__ __launch_bounds__(64 * INTRA_MAX_WAVES) __attribute__((amdgpu_waves_per_eu(6, 8))) void intra_dag_kernel(const OhBatch B, const OhIntraLaunch L, const int n_pics, uint32_t *__restrict__ ticket, const uint32_t spin_limit)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ uint32_t s_ticket;
@@ -903,9 +896,8 @@ __global__ __launch_bounds__(64 * INTRA_MAX_WAVES) __attribute__((amdgpu_waves_p
     __syncthreads();
     const uint32_t k = s_ticket;
     const DevFrame *__restrict__ f = B.f[pic];
-    (void)total;
     if (k < f->n_ictu)
-        intra_ctu_body<PX, CIP, STAGED, true>(f, L, k, smem, spin_limit);
+        intra_ctu_body<PX, CIP, STAGED>(f, L, k, smem, spin_limit);
 }
 
 /* =========================================================================================
@@ -919,7 +911,7 @@ __global__ __launch_bounds__(64 * INTRA_MAX_WAVES) __attribute__((amdgpu_waves_p
  * the rectangles and ran 5 workgroups per CU: profiles/r02_intra_staging_experiment.txt).  Hand-off between entries as above.
  * ======================================================================================= */
 template <typename PX, bool CIP>
-__global__ __launch_bounds__(64) void intra_direct_kernel(const OhBatch B, const int n_pics, const uint32_t total, uint32_t *__restrict__ ticket, const uint32_t spin_limit, const int exp)
+__global__ __launch_bounds__(64) void intra_direct_kernel(const OhBatch B, const int n_pics, uint32_t *__restrict__ ticket, const uint32_t spin_limit)
 {
     /* per wave: the edge arrays, and a window of 64 block descriptors (a wave reads its entry's lists front to back: tables and
      * descriptors arrive 64 at a time, so a pass waits for ONE round trip to HBM — its samples and residual — not for four) */
@@ -931,10 +923,9 @@ __global__ __launch_bounds__(64) void intra_direct_kernel(const OhBatch B, const
     if (lane == 0) pos = atomicAdd(ticket + OH_TICKET_STRIDE * pic, 1u);
     pos = __builtin_amdgcn_readfirstlane(pos);
     const DevFrame *__restrict__ f = B.f[pic];
-    (void)total;
     if (pos >= f->n_ictu)
         return;
-    const uint32_t k = (exp & 4) ? pos : G_CONST(uint32_t, f->ctu_order)[pos];      /* chains first (prep_intra_order) */
+    const uint32_t k = G_CONST(uint32_t, f->ctu_order)[pos];      /* chains first (prep_intra_order) */
     const DevIntraCtu ctu = gload(f->ictu + k);
     const uint32_t aux = __builtin_amdgcn_readfirstlane(G_CONST(uint32_t, f->ctu_aux)[k]);
     const GLOBAL uint32_t *__restrict__ ss = G_CONST(uint32_t, f->sub_start) + ctu.sub_first;
@@ -957,8 +948,8 @@ __global__ __launch_bounds__(64) void intra_direct_kernel(const OhBatch B, const
         WSYNC();
     };
     window(item0);
-    if ((aux & OH_AUX_WAITS) && !(exp & 1))
-        dag_wait_wave(f, k, lane, spin_limit, exp);
+    if (aux & OH_AUX_WAITS)
+        dag_wait_wave(f, k, lane, spin_limit);
     SlotState st;
     for (int cb = 0; cb < n_sub; cb += 63) {                 /* sub-level tables: 64 entries of sub_start (63 sub-levels) per round trip, one per lane */
         const uint32_t t_ss = ss[min(cb + lane, n_sub)], t_sm = sm[min(cb + lane, n_sub - 1)];
@@ -980,7 +971,7 @@ __global__ __launch_bounds__(64) void intra_direct_kernel(const OhBatch B, const
             }
         }
     }
-    if ((aux & OH_AUX_AWAITED) && !(exp & 2)) {
+    if (aux & OH_AUX_AWAITED) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane == 0) dag_publish_lane<true>(f, k);
     }
@@ -996,90 +987,12 @@ __global__ __launch_bounds__(256) void intra_dag_reset_kernel(const OhBatch B, u
 }
 
 /* =========================================================================================
- * The same pass for pictures whose CTUs nearly all depend on their neighbours (I pictures: 126 levels for 4K): instead of one
- * launch per wavefront level — each as long as its slowest CTU, plus launch and staging overhead, 126 times — ONE launch whose
- * workgroups are the CTU ROWS (what pthread_slice.c's wavefront threads are, hevc.c:2829-2990): row y walks its CTUs left to right
- * and starts CTU x when row y-1 has finished min(x + 2, ctbw) CTUs (ff_thread_await_progress2 / the two-CTB lag of WPP, a superset
- * of the dependencies the recorder found).  A picture then costs its critical path (ctbw + 2 (ctbh - 1) CTU times at the AVERAGE
- * CTU length) instead of the sum of the levels' maxima.
- *
- * Progress is a counter per row in HBM: the finishing workgroup makes its samples visible (release fence at agent scope behind a
- * barrier) and stores x + 1; the waiting workgroup polls it (one lane, relaxed agent-scope loads) and every wave then takes an acquire fence (L1 and the XCD's non-coherent L2 lines dropped) before it stages.  Workgroup
- * ids are row-major over (row, picture), rows ascending: a waiting workgroup only ever waits for a LOWER id, and the dispatcher of
- * each XCD hands workgroups out in id order, so the lowest unfinished workgroup is always resident and never waits on a
- * non-resident one — no deadlock whatever the occupancy (in-order dispatch is what the hardware does, not what HIP promises: see
- * engine.hip where the path is chosen).  The poll is bounded all the same: a wave that gives up latches OH_KE_ROW_TIMEOUT in the
- * engine's error word — every wait on the stream then fails with picture and row — and continues, so the grid always drains.
- * ======================================================================================= */
-template <typename PX, bool CIP, bool STAGED>
-__global__ __launch_bounds__(64 * INTRA_MAX_WAVES) void intra_rows_kernel(const OhBatch B, const OhIntraLaunch L, const int n_pics, const uint32_t spin_limit)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int row = blockIdx.x / n_pics, pic = blockIdx.x - row * n_pics;
-    const DevFrame *__restrict__ f = B.f[pic];
-    const OhPicParams &pp = f->pp;
-    const int lc = pp.log2_ctb_size, ctbw = (pp.width + (1 << lc) - 1) >> lc, ctbh = (pp.height + (1 << lc) - 1) >> lc;
-    if (row >= ctbh)
-        return;
-    uint32_t *__restrict__ progress = f->row_progress;
-    const GLOBAL uint32_t *__restrict__ entry_of = G_CONST(uint32_t, f->ctu_seen);
-    for (int x = 0; x < ctbw; x++) {
-        const uint32_t e = entry_of[row * ctbw + x];                 /* index + 1 of the CTU's schedule entry, 0: no intra block */
-        if (e) {
-            if (row > 0) {
-                const uint32_t need = (uint32_t)min(x + 2, ctbw);
-                if (threadIdx.x == 0) {
-                    uint32_t spin = 0;                                   /* the default limit is ~1 s: never reached while the rows above make progress */
-                    while (__hip_atomic_load(&progress[row - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {   /* the acquire is the fence below */
-                        if (++spin >= spin_limit) {                      /* give up, but not silently: oh_engine_sync reports picture and row */
-                            dag_latch_error(f, OH_KE_ROW_TIMEOUT, (uint32_t)row);
-                            break;
-                        }
-                        __builtin_amdgcn_s_sleep(8);
-                    }
-                }
-                __syncthreads();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   /* samples written by other workgroups: not from this CU's L1 */
-            }
-            intra_ctu_body<PX, CIP, STAGED, false>(f, L, e - 1, smem, 0u);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");       /* every thread's stores of the CTU */
-            __syncthreads();                                         /* ... and the LDS is free for the next CTU */
-        }
-        if (threadIdx.x == 0)
-            __hip_atomic_store(&progress[row], (uint32_t)x + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-__global__ __launch_bounds__(64) void intra_rows_reset_kernel(const OhBatch B)
-{
-    const DevFrame *__restrict__ f = B.f[blockIdx.x];
-    const int lc = f->pp.log2_ctb_size, ctbh = (f->pp.height + (1 << lc) - 1) >> lc;
-    for (int r = threadIdx.x; r < ctbh; r += 64) f->row_progress[r] = 0;
-}
-
-/* =========================================================================================
  * launcher
  * ======================================================================================= */
 int ohk_init_intra(void)
 {
-    /* the intra kernel's LDS block is sized per launch and exceeds 64 KiB for 4:4:4 CTUs full of 4x4 blocks */
+    /* the staged kernel's LDS block is sized per launch and exceeds 64 KiB for 4:4:4 CTUs full of 4x4 blocks */
     const int max_lds = 128 * 1024;
-    const void *intra_kernels[8] = {
-        (const void *)intra_ctu_kernel<uint8_t, false, false>, (const void *)intra_ctu_kernel<uint8_t, false, true>,
-        (const void *)intra_ctu_kernel<uint8_t, true, false>, (const void *)intra_ctu_kernel<uint8_t, true, true>,
-        (const void *)intra_ctu_kernel<uint16_t, false, false>, (const void *)intra_ctu_kernel<uint16_t, false, true>,
-        (const void *)intra_ctu_kernel<uint16_t, true, false>, (const void *)intra_ctu_kernel<uint16_t, true, true> };
-    const void *row_kernels[8] = {
-        (const void *)intra_rows_kernel<uint8_t, false, false>, (const void *)intra_rows_kernel<uint8_t, false, true>,
-        (const void *)intra_rows_kernel<uint8_t, true, false>, (const void *)intra_rows_kernel<uint8_t, true, true>,
-        (const void *)intra_rows_kernel<uint16_t, false, false>, (const void *)intra_rows_kernel<uint16_t, false, true>,
-        (const void *)intra_rows_kernel<uint16_t, true, false>, (const void *)intra_rows_kernel<uint16_t, true, true> };
-    for (const void *k : intra_kernels)
-        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds) != hipSuccess)
-            return -1;
-    for (const void *k : row_kernels)
-        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds) != hipSuccess)
-            return -1;
     const void *dag_kernels[8] = {
         (const void *)intra_dag_kernel<uint8_t, false, false>, (const void *)intra_dag_kernel<uint8_t, false, true>,
         (const void *)intra_dag_kernel<uint8_t, true, false>, (const void *)intra_dag_kernel<uint8_t, true, true>,
@@ -1098,14 +1011,14 @@ extern "C" void ohk_intra_dag_reset(const OhBatch *B, int n, uint32_t max_ictu, 
     hipLaunchKernelGGL(intra_dag_reset_kernel, dim3((max_ictu + 255) / 256, n), dim3(256), 0, st, *B, tickets);
 }
 
-/* n pictures, each one's whole schedule, staged form: l = the LDS carve-up that fits every CTU of all of them (l->level unused) */
+/* n pictures, each one's whole schedule, staged form: l = the LDS carve-up that fits every CTU of all of them; instantiations:
+ * constrained intra pred carries a slow path the common one must not pay for, STAGED = every CTU has its residual span in LDS */
 extern "C" void ohk_intra_dag(const OhBatch *B, int n, const OhPicParams *p, const OhIntraLaunch *l, uint32_t max_ictu, uint32_t *ticket,
                               uint32_t spin_limit, hipStream_t st)
 {
     if (n <= 0 || !max_ictu) return;
-    const uint32_t total = max_ictu * (uint32_t)n;
-    dim3 g(total), b(64 * l->waves);
-#define DAG_LAUNCH(PX, CIP, ST) hipLaunchKernelGGL(HIP_KERNEL_NAME(intra_dag_kernel<PX, CIP, ST>), g, b, l->lds_bytes, st, *B, *l, n, total, ticket, spin_limit)
+    dim3 g(max_ictu * (uint32_t)n), b(64 * l->waves);
+#define DAG_LAUNCH(PX, CIP, ST) hipLaunchKernelGGL(HIP_KERNEL_NAME(intra_dag_kernel<PX, CIP, ST>), g, b, l->lds_bytes, st, *B, *l, n, ticket, spin_limit)
 #define DAG_BY_FLAGS(PX)                                                                       \
     do {                                                                                       \
         if (p->constrained_intra_pred) { if (l->staged) DAG_LAUNCH(PX, true, true); else DAG_LAUNCH(PX, true, false); }   \
@@ -1120,47 +1033,9 @@ extern "C" void ohk_intra_dag(const OhBatch *B, int n, const OhPicParams *p, con
 extern "C" void ohk_intra_direct(const OhBatch *B, int n, const OhPicParams *p, uint32_t max_ictu, uint32_t *ticket, uint32_t spin_limit, hipStream_t st)
 {
     if (n <= 0 || !max_ictu) return;
-    const uint32_t total = max_ictu * (uint32_t)n;
-    dim3 g(total), b(64);
-    static const char *xenv = getenv("OHEVC_EXP");           /* experiments only: 1 no waits, 2 no publishing (wrong pictures) */
-    const int exp = xenv ? atoi(xenv) : 0;
-#define DIRECT_LAUNCH(PX, CIP) hipLaunchKernelGGL(HIP_KERNEL_NAME(intra_direct_kernel<PX, CIP>), g, b, 0, st, *B, n, total, ticket, spin_limit, exp)
+    dim3 g(max_ictu * (uint32_t)n), b(64);
+#define DIRECT_LAUNCH(PX, CIP) hipLaunchKernelGGL(HIP_KERNEL_NAME(intra_direct_kernel<PX, CIP>), g, b, 0, st, *B, n, ticket, spin_limit)
     if (p->bit_depth == 8) { if (p->constrained_intra_pred) DIRECT_LAUNCH(uint8_t, true); else DIRECT_LAUNCH(uint8_t, false); }
     else                   { if (p->constrained_intra_pred) DIRECT_LAUNCH(uint16_t, true); else DIRECT_LAUNCH(uint16_t, false); }
 #undef DIRECT_LAUNCH
-}
-
-/* n pictures whose intra pass runs as CTU rows (intra_rows_kernel); l: the LDS carve-up that fits every CTU of all of them */
-extern "C" void ohk_intra_rows(const OhBatch *B, int n, const OhPicParams *p, const OhIntraLaunch *l, uint32_t spin_limit, hipStream_t st)
-{
-    if (n <= 0) return;
-    const int lc = p->log2_ctb_size, ctbh = (p->height + (1 << lc) - 1) >> lc;
-    hipLaunchKernelGGL(intra_rows_reset_kernel, dim3(n), dim3(64), 0, st, *B);
-    dim3 g(ctbh * n), b(64 * l->waves);
-#define ROWS_LAUNCH(PX, CIP, ST) hipLaunchKernelGGL(HIP_KERNEL_NAME(intra_rows_kernel<PX, CIP, ST>), g, b, l->lds_bytes, st, *B, *l, n, spin_limit)
-#define ROWS_BY_FLAGS(PX)                                                                      \
-    do {                                                                                       \
-        if (p->constrained_intra_pred) { if (l->staged) ROWS_LAUNCH(PX, true, true); else ROWS_LAUNCH(PX, true, false); }   \
-        else                           { if (l->staged) ROWS_LAUNCH(PX, false, true); else ROWS_LAUNCH(PX, false, false); } \
-    } while (0)
-    if (p->bit_depth == 8) ROWS_BY_FLAGS(uint8_t); else ROWS_BY_FLAGS(uint16_t);
-#undef ROWS_BY_FLAGS
-#undef ROWS_LAUNCH
-}
-
-extern "C" void ohk_intra_level(const OhBatch *B, int n, const OhPicParams *p, const OhIntraLaunch *l, uint32_t max_ctu, hipStream_t st)
-{
-    if (!max_ctu) return;
-    dim3 g(max_ctu, n), b(64 * l->waves);
-    /* instantiations: constrained intra pred carries a slow path the common one must not pay for; STAGED = every CTU of the
-     * launch has its residual span in LDS (otherwise the blocks read it from HBM) */
-#define INTRA_LAUNCH(PX, CIP, ST) hipLaunchKernelGGL(HIP_KERNEL_NAME(intra_ctu_kernel<PX, CIP, ST>), g, b, l->lds_bytes, st, *B, *l)
-#define INTRA_BY_FLAGS(PX)                                                                     \
-    do {                                                                                       \
-        if (p->constrained_intra_pred) { if (l->staged) INTRA_LAUNCH(PX, true, true); else INTRA_LAUNCH(PX, true, false); }   \
-        else                           { if (l->staged) INTRA_LAUNCH(PX, false, true); else INTRA_LAUNCH(PX, false, false); } \
-    } while (0)
-    if (p->bit_depth == 8) INTRA_BY_FLAGS(uint8_t); else INTRA_BY_FLAGS(uint16_t);
-#undef INTRA_BY_FLAGS
-#undef INTRA_LAUNCH
 }

@@ -11,8 +11,8 @@
  *   hand-over prep.hip   prep_*           raw lists -> MC jobs, TU size buckets, intra descriptors, level statistics (one launch set per 32 lists)
  *   pass 1  mc.hip        mc_kernel         a wave runs four <=8x8 blocks of one plane (16 lanes each): windows in LDS, v_dot2 h- and v-pass
  *   pass 2  residual.hip  residual_kernel   one launch per size; sixteen 4x4 / four 8x8 / one 16x16 / one 32x32 block per wave, two LDS matrix passes
- *   pass 3  intra.hip     intra_ctu_kernel  one workgroup per CTU of one wavefront level; <=8x8 blocks four per wave, prepared one sub-level ahead
- *                         intra_rows_kernel one workgroup per CTU row of an I picture, rows two CTUs apart like the reference's WPP threads (one launch)
+ *   pass 3  intra.hip     intra_dag_kernel  one launch: a workgroup per CTU staged in LDS (I pictures); <=8x8 blocks four per wave, prepared one sub-level ahead
+ *                         intra_direct_kernel  one launch: a wave per CTU on the picture in HBM (B / P pictures); CTUs wait for lower tickets' flags
  *   pass 4  deblock.hip   deblock_*_kernel  one lane per 4-line edge segment, V pass then H pass, in place
  *   pass 5  sao.hip       sao_kernel        eight samples per lane, CTB-uniform waves, half 0 -> half 1
  *   BS      bs.hip        bs_kernel         optional: both boundary-strength grids from the motion field, one lane per 4x4 cell
@@ -22,7 +22,7 @@
 #include "kernels_common.h"
 
 /* per-file set-up: the interpolation taps and the transform bases are packed on the host once (g_mctab in
- * mc.hip, g_basis in residual.hip); the intra kernels raise their dynamic-LDS limit */
+ * mc.hip, g_basis in residual.hip); the staged intra kernels raise their dynamic-LDS limit */
 int ohk_init_mc(void);
 int ohk_init_residual(void);
 int ohk_init_intra(void);

@@ -537,8 +537,8 @@ __global__ __launch_bounds__(64) void prep_intra_levels(const OhBatch B)
 
 /* The schedule as a dependency graph, for the one-launch forms of the intra pass (intra.hip): one thread per entry looks up the
  * entries of the neighbour CTUs its blocks gather from; it waits for those of a LOWER level (the level table is the contract: a
- * block never reads intra samples of a CTU of its own or a higher level), which sit at lower indices of ictu[] — the one-launch
- * kernels dispatch in index order, so a wait always points at a workgroup dispatched earlier.  The awaited entry learns that it
+ * block never reads intra samples of a CTU of its own or a higher level), which sit at lower indices of ictu[] — a workgroup takes
+ * the entry of the ticket it draws (intra.hip), so a wait always points at a LOWER ticket.  The awaited entry learns that it
  * has to publish (OH_AUX_AWAITED). */
 __global__ __launch_bounds__(256) void prep_intra_wait(const OhBatch B)
 {

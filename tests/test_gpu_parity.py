@@ -672,17 +672,17 @@ def test_intra_wave_layouts(waves, phases):
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-2000:] + r.stderr[-4000:]
 
 
-@pytest.mark.parametrize("mode", ["levels", "dag", "direct"])
+@pytest.mark.parametrize("mode", ["dag", "direct"])
 def test_intra_pass_forms(mode):
     """The intra pass of a picture runs in one launch — a wave per CTU on the picture in HBM (`direct`: pictures with few intra blocks)
-    or a workgroup per CTU staged in LDS (`dag`), CTUs waiting for their neighbours' flags — or as one launch per wavefront level
-    (`levels`, rounds 1-2).  The engine chooses per picture; OHEVC_INTRA_MODE forces one form for every picture: I and B pictures
-    of several formats through each (child process: the switch is read once)."""
+    or a workgroup per CTU staged in LDS (`dag`), CTUs waiting for their neighbours' flags.  The engine chooses per picture;
+    OHEVC_INTRA_MODE forces one form for every picture: I and B pictures of several formats through each (child process: the
+    switch is read once)."""
     import subprocess
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
     env = dict(os.environ, OHEVC_INTRA_MODE=mode)
-    for k in ("OHEVC_INTRA_WAVES", "OHEVC_INTRA_PHASES", "OHEVC_INTRA_ROWS", "OHEVC_INTRA_RES_LDS"):
+    for k in ("OHEVC_INTRA_WAVES", "OHEVC_INTRA_PHASES", "OHEVC_INTRA_RES_LDS"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-c", _WAVES_SCRIPT.format(tests=here, root=os.path.dirname(here))], env=env,
                        capture_output=True, text=True, timeout=300)
@@ -715,10 +715,10 @@ eng.close()
 """
 
 
-@pytest.mark.parametrize("mode", ["levels", "dag", "direct"])
+@pytest.mark.parametrize("mode", ["dag", "direct"])
 def test_intra_wait_that_gives_up_is_reported(mode):
-    """A CTU (or CTB row) that waits for its neighbours polls a bounded number of times; when it gives up, the kernel latches
-    picture and schedule entry / row in the engine's error word and oh_engine_sync fails with them — never a silently wrong
+    """A CTU that waits for its neighbours polls a bounded number of times; when it gives up, the kernel latches
+    picture and schedule entry in the engine's error word and oh_engine_sync fails with them — never a silently wrong
     picture.  OHEVC_SPIN_LIMIT=1 makes every wait give up at its first unsuccessful poll: a 1080p I picture (hundreds of dependent CTUs)
     cannot get through without one."""
     import subprocess
@@ -730,17 +730,15 @@ def test_intra_wait_that_gives_up_is_reported(mode):
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-2000:] + r.stderr[-4000:]
 
 
-@pytest.mark.parametrize("rows,res_lds", [(0, 0), (0, 1), (1, 0), (1, 1)])
-def test_intra_rows_and_levels(rows, res_lds):
-    """a picture whose wavefront is (nearly) full — an I picture — runs its intra pass as CTU rows in one launch
-    (intra_rows_kernel) while the batch's rows leave the chip room, as one launch per level otherwise; OHEVC_INTRA_ROWS=0
-    forces the levels.  The CTUs' residual spans are staged in LDS in launches the chip holds at once, fetched per block from HBM in
-    the prepare stage in wider ones; OHEVC_INTRA_RES_LDS forces one way.  All four combinations over the same I / B pictures (child
-    process: the switches are read once)."""
+@pytest.mark.parametrize("res_lds", [0, 1])
+def test_intra_residual_staging(res_lds):
+    """The staged form (intra_dag_kernel) stages the CTUs' residual spans in LDS in launches the chip holds at once and fetches them
+    per block from HBM in the prepare stage in wider ones; OHEVC_INTRA_RES_LDS forces one way.  Both over the same I / B pictures,
+    every picture through the staged form (child process: the switches are read once)."""
     import subprocess
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
-    env = dict(os.environ, OHEVC_INTRA_MODE="levels", OHEVC_INTRA_ROWS=str(rows), OHEVC_INTRA_RES_LDS=str(res_lds))
+    env = dict(os.environ, OHEVC_INTRA_MODE="dag", OHEVC_INTRA_RES_LDS=str(res_lds))
     env.pop("OHEVC_INTRA_WAVES", None)
     env.pop("OHEVC_INTRA_PHASES", None)
     r = subprocess.run([sys.executable, "-c", _WAVES_SCRIPT.format(tests=here, root=os.path.dirname(here))], env=env,

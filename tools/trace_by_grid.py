@@ -9,7 +9,7 @@ import sys
 from collections import defaultdict
 
 path = sys.argv[1]
-want = sys.argv[2] if len(sys.argv) > 2 else "intra_ctu_kernel"
+want = sys.argv[2] if len(sys.argv) > 2 else "intra_dag_kernel"
 files = [path] if os.path.isfile(path) else glob.glob(os.path.join(path, "**", "*kernel_trace.csv"), recursive=True)
 rows = []
 for fn in files:

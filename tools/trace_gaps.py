@@ -25,7 +25,7 @@ def main():
     # the intra pass by launch size
     big = collections.defaultdict(lambda: [0, 0.0])
     for r in rows:
-        if "intra_ctu_kernel" in r["Kernel_Name"]:
+        if "intra_dag_kernel" in r["Kernel_Name"]:
             wg = int(r["Grid_Size_X"]) // max(int(r["Workgroup_Size_X"]), 1) * int(r["Grid_Size_Y"]) // max(int(r["Workgroup_Size_Y"]), 1)
             b = 1
             while b < wg:
