@@ -107,7 +107,9 @@ int oh_pics_md5(OhEngine *e, const int *pic_ids, int n, uint8_t *digests);
 /* SHVC inter-layer reference picture: resample the finished base-layer picture src_pic into
  * the enhancement-layer picture dst_pic, bit-exact with the reference's whole-picture slot
  * HEVCDSPContext.upsample_base_layer_frame (hevcdsp_template.c:2164-2438, call site hevc.c:3241).
- * 8-bit 4:2:0 only, like that routine (OH_E_UNSUPPORTED otherwise).  u: oh_upsample_setup(). */
+ * 8-bit 4:2:0 only, like that routine (OH_E_UNSUPPORTED otherwise).  u: oh_upsample_setup().
+ * The reference's default build never calls that slot (ACTIVE_PU_UPSAMPLING hevc.h:117): what it decodes is the CTB path of
+ * oh_pic_upsample_blocks below, which differs with offsets, phase alignment and x1.5 beyond 2048 EL columns / rows. */
 int oh_pic_upsample(OhEngine *e, int dst_pic, int src_pic, const OhUpsample *u);
 /* The same resampling for a LIST of CTBs of the enhancement-layer picture (raster addresses for CTBs of 1 << log2_ctb_size luma
  * samples; the rest of dst_pic is left as it is): the granularity of the reference's default build, which up-samples a CTB when
@@ -116,8 +118,30 @@ int oh_pic_upsample(OhEngine *e, int dst_pic, int src_pic, const OhUpsample *u);
  * before the picture's work list.  Same samples as the reference's CTB path wherever that path and its whole-picture slot agree:
  * no scaled reference layer offsets and no phase alignment (tests/test_upsample_vs_ref.py); offsets are refused
  * (OH_E_UNSUPPORTED — use oh_pic_upsample).  The motion-field half of that path (ff_upscale_mv_block, hevc_filter.c:1311-1368)
- * feeds merge / AMVP derivation (hevc_mvs.c), host work by SURVEY §8, and stays with the host decoder. */
+ * feeds merge / AMVP derivation (hevc_mvs.c), host work by SURVEY §8, and stays with the host decoder.
+ * For the reference's own CTB arithmetic everywhere it is defined (offsets, phase alignment, x1.5 at any size): oh_pic_upsample_blocks. */
 int oh_pic_upsample_ctbs(OhEngine *e, int dst_pic, int src_pic, const OhUpsample *u, int log2_ctb_size, const uint32_t *ctb_addrs, int n);
+/* The reference's CTB path itself: per listed EL CTB what its block driver computes (upsample_block_luma / upsample_block_mc,
+ * hevc_filter.c:1175-1309) — its base-layer window estimates and margins, one emulated edge per call (emulated_edge_up_h / _v,
+ * videodsp_template.c:103-160) and the slot variant u->idx picks (upsample_filter_block_*, hevcdsp_template.c:1834-2162: x2 fixed
+ * phases, x1.5 exact thirds, the 16.16 generic one, a copy at x1).  ctb_addrs == NULL: every CTB (n ignored); CTBs not listed keep
+ * their samples, and so do chroma rows outside the scaled reference layer window (the chroma v slots store at the clipped row).
+ * Where the reference's CTB path reads samples no call of its own wrote (see oh_upsample_blocks_defined) the call returns
+ * OH_E_UNSUPPORTED and names the CTB and the reason; it never computes something else.  el_conf_win: the enhancement layer's
+ * conformance window, by which the driver positions (hevc_filter.c:1196-1197, 1257-1258); only an empty one (or NULL) for now.
+ * 8-bit 4:2:0 only. */
+int oh_pic_upsample_blocks(OhEngine *e, int dst_pic, int src_pic, const OhUpsample *u, int log2_ctb_size,
+                           const OhWindow *el_conf_win, const uint32_t *ctb_addrs, int n);
+/* Host only (no device needed): 1 when every CTB of the picture pair, up-sampled by the reference's CTB path with an empty EL
+ * conformance window, reads only samples that its own call wrote or the base layer holds; 0 otherwise, with *first_bad_ctb the
+ * first such CTB (raster address; -1 when the scale itself is out of range).  It is 0 where a CTB's vertical slot reads an
+ * intermediate row the short window estimate (hevc_filter.c:1260 "FIXME") did not filter — scratch of an earlier call, so the
+ * result depends on call order —, reads base-layer samples beyond an edge its call did not emulate (one edge per call:
+ * videodsp_template.c:110-116, 141-151, e.g. an EL of a single CTB row or column) or base-layer rows the picture does not have
+ * (the chroma height of hevc_filter.c:1252 at vertical ratios above 2), overwrites base-layer samples with its left edge
+ * emulation, or stores chroma rows of another CTB.  The edge replications themselves are deterministic and are reproduced.
+ * OH_E_ARG for a bad geometry. */
+int oh_upsample_blocks_defined(const OhUpsample *u, int w_bl, int h_bl, int w_el, int h_el, int log2_ctb_size, int *first_bad_ctb);
 
 /* work lists.  OhFrame.cur_pic / ref_pics[] hold engine picture ids.
  * upload copies every array to HBM (after it returns the host arrays may be reused);

@@ -106,6 +106,12 @@ typedef struct OhStream {
 void oh_stream_defaults(OhStreamParams *p, int width, int height, uint64_t seed);
 /* returns 0, or a negative value when the parameters are outside what the writer covers */
 int  oh_stream_write(const OhStreamParams *p, OhStream *out);
+/* oh_stream_write with options (opts = 0: the same call).  OH_STREAM_SHVC_BLOCK_PATH: a two-layer stream is meant for a decoder whose
+ * inter-layer reference is the reference decoder's CTB up-sampling path (its default build; the engine's oh_pic_upsample_blocks), so
+ * x1.5 enhancement layers beyond 2048 columns or rows are written (the whole-picture slot differs there; without the option they are
+ * refused).  Unknown bits: -1. */
+enum { OH_STREAM_SHVC_BLOCK_PATH = 1u << 0 };
+int  oh_stream_write_opts(const OhStreamParams *p, unsigned opts, OhStream *out);
 /* the same stream with a decoded-picture-hash SEI (MD5, payload type 132, suffix SEI NAL) behind every picture;
  * md5[i * 48 ..]: the three plane digests of picture i in decode order */
 int  oh_stream_add_md5(const OhStream *in, const uint8_t *md5, OhStream *out);

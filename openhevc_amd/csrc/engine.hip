@@ -669,6 +669,135 @@ extern "C" int oh_pic_upsample_ctbs(OhEngine *e, int dst_pic, int src_pic, const
     return upsample_tiles(e, dst_pic, src_pic, u, log2_ctb_size, n ? ctb_addrs : &none, n, "oh_pic_upsample_ctbs");
 }
 
+/* ---- the reference's CTB path (upblock.h): where its output is defined, and the call ---- */
+static void upb_geoms(OhUpBlkGeom g[2], const OhUpsample *u, int w_bl, int h_bl, int w_el, int h_el, int log2_ctb, const OhWindow *conf)
+{
+    for (int c = 0; c < 2; c++) {
+        OhUpBlkGeom &q = g[c];
+        q.cr = c; q.idx = u->idx; q.log2_ctb = log2_ctb;
+        q.w_el = w_el >> c; q.h_el = h_el >> c;
+        q.bl_w = w_bl >> c; q.bl_w_act = w_bl >> c; q.bl_h_act = h_bl >> c;
+        q.bl_h = c ? (h_bl > q.h_el ? h_bl : q.h_el) >> 1 : h_bl;          /* hevc_filter.c:1252 */
+        q.left = u->win_left >> c; q.right_end = q.w_el - (u->win_right >> c);
+        q.top = u->win_top >> c; q.bottom_end = q.h_el - (u->win_bottom >> c);
+        q.sx = c ? u->scale_x_cr : u->scale_x_lum; q.ax = c ? u->add_x_cr : u->add_x_lum;
+        q.sy = c ? u->scale_y_cr : u->scale_y_lum; q.ay = c ? u->add_y_cr : u->add_y_lum;
+        q.dsx = u->scale_x_lum; q.dax = u->add_x_lum; q.dsy = u->scale_y_lum; q.day = u->add_y_lum;
+        q.conf_left = conf ? conf->left >> c : 0; q.conf_top = conf ? conf->top >> c : 0;
+    }
+}
+
+static const char *upb_reason(int r)
+{
+    switch (r) {
+    case UPB_STALE_ROW:    return "its vertical slot reads an intermediate row the window estimate (hevc_filter.c:1260) did not filter: scratch of an earlier call";
+    case UPB_BL_ROW:       return "it reads base-layer rows outside the picture";
+    case UPB_BL_COL:       return "it reads base-layer columns beyond an edge its call did not emulate";
+    case UPB_BL_OVERWRITE: return "its left edge emulation writes over base-layer samples other CTBs read";
+    case UPB_FOREIGN_ROW:  return "its chroma rows clip into another CTB's rows";
+    }
+    return "?";
+}
+
+/* the first CTB of the list (all CTBs: ctbs == nullptr) whose output the reference does not define; *reason: UPB_*, *plane: 0 luma 1 chroma */
+static int upb_first_bad(const OhUpBlkGeom g[2], int w_el, int h_el, int log2_ctb, const uint32_t *ctbs, int n, int *reason, int *plane)
+{
+    const int size = 1 << log2_ctb, cw = (w_el + size - 1) >> log2_ctb, nall = cw * ((h_el + size - 1) >> log2_ctb);
+    for (int k = 0; k < (ctbs ? n : nall); k++) {
+        const int a = ctbs ? (int)ctbs[k] : k, x0 = (a % cw) << log2_ctb, y0 = (a / cw) << log2_ctb;
+        for (int c = 0; c < 2; c++) {
+            const int r = upb_check(g[c], x0 >> c, y0 >> c);
+            if (r) {
+                *reason = r; *plane = c;
+                return a;
+            }
+        }
+    }
+    return -1;
+}
+
+static bool upb_args_ok(const OhUpsample *u, int w_bl, int h_bl, int w_el, int h_el, int log2_ctb)
+{
+    return u && w_bl > 0 && h_bl > 0 && w_el > 0 && h_el > 0 && log2_ctb >= 4 && log2_ctb <= 6 && u->win_left >= 0 && u->win_right >= 0 &&
+           u->win_top >= 0 && u->win_bottom >= 0 && u->win_left + u->win_right < w_el && u->win_top + u->win_bottom < h_el &&
+           u->scale_x_lum > 0 && u->scale_y_lum > 0 && u->scale_x_cr > 0 && u->scale_y_cr > 0 && u->idx >= OH_UP_DEFAULT && u->idx <= OH_UP_SNR;
+}
+
+extern "C" int oh_upsample_blocks_defined(const OhUpsample *u, int w_bl, int h_bl, int w_el, int h_el, int log2_ctb_size, int *first_bad_ctb)
+{
+    if (first_bad_ctb)
+        *first_bad_ctb = -1;
+    if (!upb_args_ok(u, w_bl, h_bl, w_el, h_el, log2_ctb_size))
+        return OH_E_ARG;
+    if (u->scale_x_lum > 65536 || u->scale_y_lum > 65536 || u->scale_x_cr > 65536 || u->scale_y_cr > 65536)
+        return 0;                                          /* EL smaller than BL: no spatial scalability, and the windows are unbounded */
+    OhUpBlkGeom g[2];
+    upb_geoms(g, u, w_bl, h_bl, w_el, h_el, log2_ctb_size, nullptr);
+    int reason, plane;
+    const int bad = upb_first_bad(g, w_el, h_el, log2_ctb_size, nullptr, 0, &reason, &plane);
+    if (first_bad_ctb)
+        *first_bad_ctb = bad;
+    return bad < 0;
+}
+
+extern "C" int oh_pic_upsample_blocks(OhEngine *e, int dst_pic, int src_pic, const OhUpsample *u, int log2_ctb_size,
+                                      const OhWindow *el_conf_win, const uint32_t *ctb_addrs, int n)
+{
+    if (!e || !u || (!ctb_addrs && n) || n < 0)
+        return OH_E_ARG;
+    Pic *el = get_pic(e, dst_pic), *bl = get_pic(e, src_pic);
+    if (!el || !bl || el == bl)
+        FAIL(e, OH_E_ARG, "oh_pic_upsample_blocks: bad picture ids");
+    if (el->p.bit_depth != 8 || bl->p.bit_depth != 8 || el->p.chroma_format_idc != 1 || bl->p.chroma_format_idc != 1)
+        FAIL(e, OH_E_UNSUPPORTED, "oh_pic_upsample_blocks: the reference's up-sampler is written for 8-bit 4:2:0 (byte edge buffers, shift 12)");
+    const int w_el = el->p.width, h_el = el->p.height, w_bl = bl->p.width, h_bl = bl->p.height;
+    if (!upb_args_ok(u, w_bl, h_bl, w_el, h_el, log2_ctb_size))
+        FAIL(e, OH_E_ARG, "oh_pic_upsample_blocks: bad window / scale / CTB size");
+    if (u->scale_x_lum > 65536 || u->scale_y_lum > 65536 || u->scale_x_cr > 65536 || u->scale_y_cr > 65536)
+        FAIL(e, OH_E_UNSUPPORTED, "oh_pic_upsample_blocks: the enhancement layer is smaller than the base layer (scale > 1): not a spatial-scalability configuration");
+    if (el_conf_win && (el_conf_win->left || el_conf_win->right || el_conf_win->top || el_conf_win->bottom))
+        FAIL(e, OH_E_UNSUPPORTED, "oh_pic_upsample_blocks: a non-zero enhancement-layer conformance window (the driver positions by it, hevc_filter.c:1196-1197) is not covered yet");
+    const int size = 1 << log2_ctb_size, n_all = ((w_el + size - 1) >> log2_ctb_size) * ((h_el + size - 1) >> log2_ctb_size);
+    for (int i = 0; ctb_addrs && i < n; i++)
+        if (ctb_addrs[i] >= (uint32_t)n_all)
+            FAIL(e, OH_E_ARG, "oh_pic_upsample_blocks: CTB address %u of %d", ctb_addrs[i], n_all);
+    OhUpBlkArgs a;
+    upb_geoms(a.g, u, w_bl, h_bl, w_el, h_el, log2_ctb_size, el_conf_win);
+    a.g[1].bl_h_act = bl->h[1] < a.g[1].bl_h_act ? bl->h[1] : a.g[1].bl_h_act;
+    int reason = 0, plane = 0;
+    const int bad = upb_first_bad(a.g, w_el, h_el, log2_ctb_size, ctb_addrs, n, &reason, &plane);
+    if (bad >= 0)
+        FAIL(e, OH_E_UNSUPPORTED, "oh_pic_upsample_blocks: the reference's CTB path does not define CTB %d (%s): %s", bad, plane ? "chroma" : "luma",
+             upb_reason(reason));
+    el->done_seq = 0;
+    const int cnt = ctb_addrs ? n : n_all;
+    if (!cnt)
+        return OH_OK;
+    HIPCHK(e, hipSetDevice(e->device));
+    const uint32_t *dlist = nullptr;
+    OhEngine::Stage *sg = nullptr;
+    if (ctb_addrs) {
+        sg = stage_acquire(e, (size_t)n * sizeof(uint32_t));      /* pinned and mapped: the kernel reads the list there */
+        if (!sg)
+            FAIL(e, OH_E_NOMEM, "oh_pic_upsample_blocks: no staging buffer");
+        memcpy(sg->p, ctb_addrs, (size_t)n * sizeof(uint32_t));
+        dlist = (const uint32_t *)sg->p;
+    }
+    void *const *src = bl->final_b ? bl->b : bl->a, *const *dst = el->final_b ? el->b : el->a;   /* CTBs not listed keep their samples */
+    for (int c = 0; c < 3; c++) {
+        a.src[c] = src[c]; a.sstride[c] = (int32_t)bl->stride[c];
+        a.dst[c] = dst[c]; a.dstride[c] = (int32_t)el->stride[c];
+    }
+    a.ctbs_x = (w_el + size - 1) >> log2_ctb_size;
+    ohk_upsample_blocks(&a, dlist, cnt, e->stream);
+    HIPCHK(e, hipGetLastError());
+    if (sg) {
+        HIPCHK(e, hipEventRecord(sg->done, e->stream));
+        sg->busy = true;
+    }
+    return OH_OK;
+}
+
 extern "C" int oh_pic_upload(OhEngine *e, int pic_id, const uint8_t *const planes[3], const ptrdiff_t strides[3])
 {
     if (!e || !planes || !strides)

@@ -4,6 +4,15 @@
 
 #include <hip/hip_runtime.h>
 #include "dev_frame.h"
+#include "upblock.h"
+
+/* the reference's CTB up-sampling path (upsample.hip: upsample_block_kernel): planes and their geometry (g[0] luma, g[1] chroma) */
+struct OhUpBlkArgs {
+    OhUpBlkGeom g[2];
+    const void *src[3]; void *dst[3];
+    int32_t sstride[3], dstride[3];
+    int32_t ctbs_x;
+};
 
 /* one MD5 chain: a plane's packed rows (md5.hip) */
 struct OhMd5Job {
@@ -26,6 +35,7 @@ void ohk_intra_dag(const OhBatch *B, int n, const OhPicParams *p, const OhIntraL
 void ohk_intra_direct(const OhBatch *B, int n, const OhPicParams *p, uint32_t max_ictu, uint32_t *ticket, uint32_t spin_limit, hipStream_t st);
 void ohk_deblock(const OhBatch *B, int n, const OhPicParams *p, int horiz, hipStream_t st);
 void ohk_upsample_plane(const OhUpPlane *a, int taps, int tw, int th, const uint32_t *list, int n_list, hipStream_t st);
+void ohk_upsample_blocks(const OhUpBlkArgs *a, const uint32_t *list, int n, hipStream_t st);
 void ohk_sao(const OhBatch *B, int n, const OhPicParams *p, hipStream_t st);
 /* one array of a page-locked work list: where it lies on the host, where it goes in the arena */
 struct OhPullSeg { const void *src; void *dst; uint64_t bytes; };

@@ -1,8 +1,10 @@
 /*
- * upsample.hip — SHVC inter-layer up-sampling of a whole base-layer picture
- * (gfx950; overview of the passes: kernels.hip; bit-exactness: tests/test_gpu_parity.py)
+ * upsample.hip — SHVC inter-layer up-sampling: the reference's whole-picture slot (upsample_tile_kernel) and its CTB path
+ * (upsample_block_kernel) (gfx950; overview of the passes: kernels.hip; bit-exactness: tests/test_gpu_parity.py,
+ * tests/test_gpu_shvc_block_path.py)
  */
 #include "kernels_common.h"
+#include "upblock.h"
 
 /* =========================================================================================
  * SHVC inter-layer up-sampling: upsample_base_layer_frame, hevcdsp_template.c:2164-2438 —
@@ -83,4 +85,35 @@ extern "C" void ohk_upsample_plane(const OhUpPlane *a, int taps, int tw, int th,
     if (n <= 0) return;
     if (taps == 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(upsample_tile_kernel<8>), dim3(n), dim3(256), 0, st, *a, tw, th, tiles_x, list);
     else           hipLaunchKernelGGL(HIP_KERNEL_NAME(upsample_tile_kernel<4>), dim3(n), dim3(256), 0, st, *a, tw, th, tiles_x, list);
+}
+
+/* =========================================================================================
+ * The reference's CTB path itself (its default build: ACTIVE_PU_UPSAMPLING hevc.h:117, ff_upsample_block hevc_filter.c:1370-1426):
+ * per listed enhancement-layer CTB what upsample_block_luma / upsample_block_mc compute for it (hevc_filter.c:1175-1309) — the
+ * driver's base-layer window with its size estimates and margins, the one-edge-per-call emulation (emulated_edge_up_h / _v) and the
+ * slot variant UpsamplInf.idx picks (x2 fixed phases, x1.5 exact thirds, the 16.16 generic one, a copy at x1).  The arithmetic is
+ * upblock.h's, shared with the host predicate.  One workgroup per CTB and plane (blockIdx.y: Y, Cb, Cr); the base-layer window and
+ * the int16 intermediate (with its replicated rows) live in LDS.
+ * ======================================================================================= */
+__global__ __launch_bounds__(256) void upsample_block_kernel(const OhUpBlkArgs a, const uint32_t *list)
+{
+    __shared__ uint8_t srcL[UPB_SRC_H][UPB_SRC_W];
+    __shared__ int16_t tmpL[UPB_TMP_H][64];
+    const int c = blockIdx.y, ctb = list ? (int)list[blockIdx.x] : (int)blockIdx.x;
+    const OhUpBlkGeom &g = a.g[c ? 1 : 0];
+    const int size = 1 << (g.log2_ctb - g.cr), x0 = (ctb % a.ctbs_x) * size, y0 = (ctb / a.ctbs_x) * size;
+    if (x0 >= g.w_el || y0 >= g.h_el)
+        return;
+    const GLOBAL uint8_t *__restrict__ src = G_CONST(uint8_t, a.src[c]);
+    GLOBAL uint8_t *__restrict__ dst = G_MUT(uint8_t, a.dst[c]);
+    auto sync = [] { __syncthreads(); };
+    if (c == 0) upb_run<8>(g, x0, y0, src, a.sstride[c], dst, a.dstride[c], srcL, tmpL, (int)threadIdx.x, 256, sync);
+    else        upb_run<4>(g, x0, y0, src, a.sstride[c], dst, a.dstride[c], srcL, tmpL, (int)threadIdx.x, 256, sync);
+}
+
+/* the listed CTBs (raster addresses over ctbs_x columns; device memory) or, list == nullptr, n = every CTB */
+extern "C" void ohk_upsample_blocks(const OhUpBlkArgs *a, const uint32_t *list, int n, hipStream_t st)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(upsample_block_kernel, dim3(n, 3), dim3(256), 0, st, *a, list);
 }

@@ -60,6 +60,8 @@ def lib():
         L.oh_pic_download_start.argtypes = [V, I, C.POINTER(OhWindow), C.POINTER(C.c_void_p)]
         L.oh_download_finish.argtypes = [V, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_ssize_t)]
         L.oh_pic_upsample_ctbs.argtypes = [V, I, I, C.c_void_p, I, C.POINTER(C.c_uint32), I]
+        L.oh_pic_upsample_blocks.argtypes = [V, I, I, C.c_void_p, I, C.POINTER(OhWindow), C.POINTER(C.c_uint32), I]
+        L.oh_upsample_blocks_defined.argtypes = [C.c_void_p, I, I, I, I, I, C.POINTER(I)]
         L.oh_pics_md5.argtypes = [V, C.POINTER(C.c_int), I, C.POINTER(C.c_uint8)]
         L.oh_frame_upload.argtypes = [V, C.POINTER(F.OhFrame), PP]
         L.oh_frames_upload.argtypes = [V, C.POINTER(C.POINTER(F.OhFrame)), I, PP]
@@ -86,6 +88,16 @@ def lib():
         L.oh_pic_device_planes.argtypes = [V, I, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         _lib = L
     return _lib
+
+
+def upsample_blocks_defined(u, w_bl, h_bl, w_el, h_el, log2_ctb_size):
+    """oh_upsample_blocks_defined (host only, no GPU): (True, -1) when the reference's CTB up-sampling path defines every CTB of the
+    enhancement-layer picture, else (False, first CTB address that reads samples no call of its own wrote; -1: scale out of range)"""
+    bad = C.c_int(-1)
+    rc = lib().oh_upsample_blocks_defined(C.byref(u), w_bl, h_bl, w_el, h_el, log2_ctb_size, C.byref(bad))
+    if rc < 0:
+        raise EngineError(f"oh_upsample_blocks_defined: bad geometry ({rc})")
+    return rc == 1, bad.value
 
 
 class Engine:
@@ -232,6 +244,15 @@ class Engine:
     def pic_upsample_ctbs(self, dst_pid, src_pid, u, log2_ctb_size, ctb_addrs):
         a = (C.c_uint32 * max(len(ctb_addrs), 1))(*ctb_addrs)
         self._chk(self.L.oh_pic_upsample_ctbs(self.h, dst_pid, src_pid, C.byref(u), log2_ctb_size, a, len(ctb_addrs)), "oh_pic_upsample_ctbs")
+
+    def pic_upsample_blocks(self, dst_pid, src_pid, u, log2_ctb_size, ctb_addrs=None, el_conf_win=None):
+        """the reference's CTB up-sampling path (oh_pic_upsample_blocks) for the listed CTBs, all when ctb_addrs is None;
+        el_conf_win: (left, right, top, bottom) of the enhancement layer's conformance window (only an empty one is covered).
+        Raises EngineError (OH_E_UNSUPPORTED) where the reference's output is not defined (upsample_blocks_defined)."""
+        a = None if ctb_addrs is None else (C.c_uint32 * max(len(ctb_addrs), 1))(*ctb_addrs)
+        w = None if el_conf_win is None else C.byref(OhWindow(*el_conf_win))
+        self._chk(self.L.oh_pic_upsample_blocks(self.h, dst_pid, src_pid, C.byref(u), log2_ctb_size, w, a, 0 if a is None else len(ctb_addrs)),
+                  "oh_pic_upsample_blocks")
 
     def frame_upload(self, frame):
         df = C.c_void_p()

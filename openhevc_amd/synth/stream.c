@@ -1497,7 +1497,7 @@ static void w_free(W *w)
     free(w->slice_of); free(w->tile_of); free(w->rs_of_ts); free(w->ts_of_rs);
 }
 
-int oh_stream_write(const OhStreamParams *p, OhStream *out)
+static int stream_write(const OhStreamParams *p, unsigned opts, OhStream *out)
 {
     if (!p || !out || p->width < 8 || p->height < 8 || (p->width & 7) || (p->height & 7) || (p->bit_depth != 8 && p->bit_depth != 9 && p->bit_depth != 10 && p->bit_depth != 12) ||
         p->log2_ctb_size < 4 || p->log2_ctb_size > 6 || p->log2_min_tb_size < 2 || p->log2_min_tb_size > 4 || p->log2_min_tb_size > p->log2_max_tb_size || p->log2_max_tb_size > 5 || p->log2_max_tb_size > p->log2_ctb_size ||
@@ -1549,10 +1549,12 @@ int oh_stream_write(const OhStreamParams *p, OhStream *out)
          * bottom (the engine follows the whole-picture slot: tests/test_upsample_vs_ref.py), so there is no single reference output;
          * (4) x1.5 beyond 2048 enhancement-layer columns or rows — the x1.5 block slots position by exact thirds ((x << 1) / 3, x % 3:
          * hevcdsp_template.c:2073-2077), the whole-picture slot by the 16.16 fixed-point scale 43691, whose rounding reaches a sixteenth
-         * of a sample at x = 2048: the two paths pick different filter phases from there on */
+         * of a sample at x = 2048: the two paths pick different filter phases from there on.  OH_STREAM_SHVC_BLOCK_PATH lifts (4) for a
+         * decoder whose inter-layer reference is the CTB path's own (oh_pic_upsample_blocks), the reference's default build */
         const int ctb = 1 << (p->log2_ctb_size ? p->log2_ctb_size : 6);
         const int x1_5 = 2 * p->shvc_el_width == 3 * p->width || 2 * p->shvc_el_height == 3 * p->height;
-        if (rext_profile(p) || (x1_5 && (p->shvc_el_width > 2048 || p->shvc_el_height > 2048)) || p->shvc_el_width < ctb + 16 || p->shvc_el_height < ctb + 16 || p->shvc_el_width > 2 * p->width || p->shvc_el_height > 2 * p->height ||
+        const int x1_5_ok = (opts & OH_STREAM_SHVC_BLOCK_PATH) || (p->shvc_el_width <= 2048 && p->shvc_el_height <= 2048);   /* (4) */
+        if (rext_profile(p) || (x1_5 && !x1_5_ok) || p->shvc_el_width < ctb + 16 || p->shvc_el_height < ctb + 16 || p->shvc_el_width > 2 * p->width || p->shvc_el_height > 2 * p->height ||
             p->bit_depth != 8 || p->chroma_format_idc != 1 || p->gop == 3 || p->shvc_el_width < p->width || p->shvc_el_height < p->height ||
             (p->shvc_el_width & ((1 << mcb_log2) - 1)) || (p->shvc_el_height & ((1 << mcb_log2) - 1)) || p->trace || p->levels ||
             p->conf_win_left || p->conf_win_right || p->conf_win_top || p->conf_win_bottom) {
@@ -1624,6 +1626,18 @@ int oh_stream_write(const OhStreamParams *p, OhStream *out)
     w_free(&w);
     if (two) { w_free(&we); free(we.out.buf); }
     return 0;
+}
+
+int oh_stream_write(const OhStreamParams *p, OhStream *out)
+{
+    return stream_write(p, 0, out);
+}
+
+int oh_stream_write_opts(const OhStreamParams *p, unsigned opts, OhStream *out)
+{
+    if (opts & ~(unsigned)OH_STREAM_SHVC_BLOCK_PATH)
+        return -1;
+    return stream_write(p, opts, out);
 }
 
 int oh_stream_add_md5(const OhStream *in, const uint8_t *md5, OhStream *out)
