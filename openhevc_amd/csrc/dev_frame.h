@@ -103,18 +103,16 @@ struct DevTu { OhTu t; uint32_t sparse_off; };     /* 16 bytes */
 struct DevCross { uint16_t x, y; uint8_t c_idx, log2_size, flags; int8_t scale; uint32_t res_c, res_y; };    /* 16 bytes */
 
 /* what the preparation kernels (prep.hip) report back to the host: the first violation found in the work list, and what
- * sizes the launches (the host reads it — a few hundred bytes, copied to pinned memory behind the kernels — before the first
- * execute of the list) */
+ * sizes the launches (the host reads it — copied to pinned memory behind the kernels — before the first execute of the list) */
 enum { OH_PE_OK = 0, OH_PE_PU = 1, OH_PE_TU = 2, OH_PE_INTRA = 3, OH_PE_INTRA_TABLES = 4 };
-struct DevLevelStat {                 /* one intra wavefront level: the levels' maxima and sums size the staged launch */
-    uint32_t n_ctu, max_items, max_sub, max_res, staged, pad;
-    uint64_t sum_items, sum_sub;
-};                                    /* 40 bytes */
 struct DevSummary {
     uint32_t err, err_item;           /* OH_PE_*, index of the offending item */
-    uint32_t tu_cnt[4], n_cross, n_levels;
+    uint32_t tu_cnt[4], n_cross;
     uint32_t intra_area64, max_passes;/* samples the intra blocks cover / 64 (all planes); wave passes of the heaviest schedule entry */
-    /* DevLevelStat[n_levels] follows */
+    /* over the schedule entries: what lays out the staged intra launch (engine.hip: intra_pass) */
+    uint32_t max_items, max_sub, max_res;
+    uint32_t res_scattered;           /* some entry is OH_AUX_RES_SCATTERED: the residual cannot be staged in LDS */
+    uint64_t sum_items, sum_sub;
 };
 /* DevFrame.ctu_aux[k] */
 enum { OH_AUX_PASSES = 0xffff,        /* wave passes of the entry: groups of four <= 8x8 blocks + the bigger blocks */
@@ -124,7 +122,7 @@ enum { OH_AUX_PASSES = 0xffff,        /* wave passes of the entry: groups of fou
        OH_AUX_RES_SCATTERED = 1u << 31 };   /* its residual blocks do not lie together in the pool: not stageable in LDS */
 /* kernel-side failures latched in OhEngine's error word (reported by oh_engine_sync and everything that waits for the stream) */
 enum { OH_KE_OK = 0, OH_KE_DAG_TIMEOUT = 2 };
-struct OhPrepCounts { uint32_t n_pu, n_mc_luma, n_mc_chroma, n_tu, n_intra, n_sub, n_ictu, n_levels; };
+struct OhPrepCounts { uint32_t n_pu, n_mc_luma, n_mc_chroma, n_tu, n_intra, n_sub, n_ictu; };
 
 struct DevFrame {
     OhPicParams pp;
@@ -181,7 +179,7 @@ struct DevFrame {
     uint32_t *ctu_order;              /* [n_ictu]: dispatch order of intra_direct_kernel: entries on dependency chains first (prep_intra_order) */
     uint32_t *err_word;               /* pinned host memory of the engine: [0] OH_KE_* of the first kernel-side failure, [1] cur_pic, [2] schedule entry */
     int32_t   cur_pic_id;             /* for the error report */
-    void     *summary;                /* DevSummary + DevLevelStat[n_levels] */
+    void     *summary;                /* DevSummary */
     void     *summary_host;           /* pinned host copy, written by prep_finish (no D2H copy on the stream) */
     uint32_t *zero_ptr; uint32_t zero_words;      /* scratch the preparation starts from cleared (prep_clear) */
     /* 16x16 CTBs with horizontally subsampled chroma only (else null): the first chroma column of every CTB on the two rows of

@@ -43,7 +43,6 @@ struct OhDevFrame {
     size_t     arena_bytes = 0;
     DevFrame  *d = nullptr;
     OhPicParams p{};
-    uint32_t   n_mc_luma = 0, n_mc_chroma = 0, n_tu = 0, n_intra = 0;
     uint32_t   tu_cnt[4] = { 0, 0, 0, 0 };
     uint32_t   n_cross = 0;
     bool       has_sao = false;
@@ -57,20 +56,17 @@ struct OhDevFrame {
     uint16_t   ref_used = 0;      /* bit i: some PU predicts from slot i */
     hipEvent_t ready = nullptr;   /* recorded on the copy stream behind the work list's H2D copy, preparation kernels and summary */
     bool       waited = false;    /* the engine stream already waits for `ready` */
-    void      *sum_host = nullptr;/* pinned: DevSummary + DevLevelStat[n_levels] as the preparation kernels left them */
-    size_t     sum_bytes = 0;
-    bool       sum_pooled = false, summary_read = false;
+    void      *sum_host = nullptr;/* pinned: the DevSummary the preparation kernels left */
+    bool       summary_read = false;
     void      *sum_dev = nullptr; /* the summary in the arena */
     OhPrepCounts cnt{};           /* sizes of the preparation launches */
-    uint32_t   prep_err = 0, n_levels = 0;
+    uint32_t   prep_err = 0;
     uint32_t   intra_area64 = 0, max_passes = 0;   /* from the summary: samples of the intra blocks / 64; wave passes of the heaviest CTU */
+    /* from the summary, over the schedule entries: what lays out the staged intra launch */
+    uint32_t   max_items = 0, max_sub = 0, max_res = 0;
+    bool       res_scattered = false;             /* some CTU's residual span is not contiguous (not stageable in LDS) */
+    uint64_t   sum_items = 0, sum_sub = 0;
     const struct OhEngine *owner = nullptr;   /* picture ids and arenas belong to one engine */
-    struct Level {                        /* one wavefront level: the levels' maxima and sums size the staged intra launch */
-        uint32_t n_ctu, max_items, max_sub, max_res;
-        bool     staged;                  /* every CTU has its residual span contiguous (stageable in LDS) */
-        uint64_t sum_items, sum_sub;
-    };
-    std::vector<Level> levels;
 };
 
 /* helper threads for the one host copy of the hand-over (the work list into a pinned staging buffer): the lists of a 4K picture are
@@ -161,7 +157,7 @@ struct OhEngine {
     std::vector<Arena> arenas;               /* free device arenas */
     uint64_t    arenas_alive = 0, arena_bytes_alive = 0;      /* device arenas allocated and not freed (pooled or holding a work list): oh_engine_memory */
     std::vector<hipEvent_t> sync_events;     /* pool of timing-disabled events (ready / free_ev) */
-    std::vector<void *> sum_pool;            /* pinned OH_SUMMARY_BLOCK-byte blocks */
+    std::vector<void *> sum_pool;            /* pinned blocks of sizeof(DevSummary) bytes */
     double      host_ms[OH_N_HOST_TIMES] = {};   /* where the host time of the hand-over path goes (oh_engine_host_times) */
     uint64_t    host_calls[OH_N_HOST_TIMES] = {};
     uint64_t    up_bytes = 0;                    /* bytes of work lists sent over PCIe since the last reset */
@@ -231,7 +227,7 @@ struct HostTimer {                       /* adds the scope's wall time to one sl
     HostTimer(OhEngine *e_, int slot_);
     ~HostTimer();
 };
-enum { OH_MAX_STAGES = 48, OH_SUMMARY_BLOCK = 32768 };             /* pinned staging buffers per engine before the host is made to wait */
+enum { OH_MAX_STAGES = 48 };             /* pinned staging buffers per engine before the host is made to wait */
 
 HostTimer::HostTimer(OhEngine *e_, int slot_) : e(e_), slot(slot_), t0(std::chrono::steady_clock::now()) {}
 HostTimer::~HostTimer()
@@ -374,7 +370,7 @@ static void free_dev_frame(OhEngine *e, OhDevFrame *df, bool in_flight = false)
     if (e && df->ready)
         sync_event_put(e, df->ready);
     if (df->sum_host) {
-        if (e && df->sum_pooled && e->sum_pool.size() < 4096) e->sum_pool.push_back(df->sum_host);
+        if (e && e->sum_pool.size() < 4096) e->sum_pool.push_back(df->sum_host);
         else (void)hipHostFree(df->sum_host);
     }
     if (df->arena) {
@@ -1106,7 +1102,7 @@ static bool same_geometry(const OhPicParams &a, const OhPicParams &b)
  * Hand-over of a work list.  The host copies the RAW lists (include/ohevc_frame.h, exactly as recorded) into one pinned
  * buffer, counts what sizes the device arena — blocks per PU, transform blocks per size: two light loops — and enqueues on the
  * copy stream:   H2D copy  ->  preparation kernels (prep.hip: validation of every index a pass kernel will follow, the
- * <= 8x8 MC block lists, the transform-size buckets, the intra block descriptors, the per-level launch statistics)  ->
+ * <= 8x8 MC block lists, the transform-size buckets, the intra block descriptors, schedule and statistics)  ->
  * boundary strengths from the motion field when the list carries bs_in (bs.hip)  ->  the summary back to pinned memory  ->
  * `ready`.  Nothing of it touches samples, so it overlaps the passes of the pictures before.  A malformed list is
  * reported by the first oh_frame(s)_execute that includes it (OH_E_ARG, before any of its passes is launched).
@@ -1156,7 +1152,8 @@ static int check_host_side(OhEngine *e, const OhFrame *f, const Pic *cur, OhPrep
     if (f->n_intra && p.constrained_intra_pred && !f->is_intra)
         FAIL(e, OH_E_ARG, "constrained_intra_pred without the is_intra map");
     if (f->n_intra) {
-        /* the level table sizes the launches (grid = CTUs of the level): checked here; everything below it on the GPU */
+        /* the level table is the contract behind the waits between CTUs (prep_intra_wait: a CTU waits only for lower levels), and
+         * prep_intra_ctu looks every entry's level up in it: checked here; everything below it on the GPU */
         if (!f->level_start || !f->n_levels || !f->ictu || !f->n_ictu || !f->sub_start || !f->n_sub ||
             f->level_start[0] != 0 || f->level_start[f->n_levels] != f->n_ictu)
             FAIL(e, OH_E_ARG, "intra wavefront tables inconsistent");
@@ -1183,17 +1180,15 @@ static int check_host_side(OhEngine *e, const OhFrame *f, const Pic *cur, OhPrep
         FAIL(e, OH_E_ARG, "is_pcm map required when pcm loop-filter disable / transquant bypass is on");
     cnt->n_pu = f->n_pu; cnt->n_mc_luma = (uint32_t)nl; cnt->n_mc_chroma = (uint32_t)nc; cnt->n_tu = f->n_tu;
     cnt->n_intra = f->n_intra; cnt->n_sub = f->n_intra ? f->n_sub : 0; cnt->n_ictu = f->n_intra ? f->n_ictu : 0;
-    cnt->n_levels = f->n_intra ? f->n_levels : 0;
     return OH_OK;
 }
 
 /* pinned block the summary of one work list lands in */
-static void *summary_block_get(OhEngine *e, size_t bytes, bool *pooled)
+static void *summary_block_get(OhEngine *e)
 {
     void *p = nullptr;
-    *pooled = bytes <= OH_SUMMARY_BLOCK;
-    if (*pooled && !e->sum_pool.empty()) { p = e->sum_pool.back(); e->sum_pool.pop_back(); return p; }
-    return hipHostMalloc(&p, *pooled ? (size_t)OH_SUMMARY_BLOCK : bytes, hipHostMallocDefault) == hipSuccess ? p : nullptr;
+    if (!e->sum_pool.empty()) { p = e->sum_pool.back(); e->sum_pool.pop_back(); return p; }
+    return hipHostMalloc(&p, sizeof(DevSummary), hipHostMallocDefault) == hipSuccess ? p : nullptr;
 }
 
 /* the host part of one hand-over and its H2D copy; finish_uploads() enqueues the preparation kernels behind it */
@@ -1253,7 +1248,8 @@ static int upload_one(OhEngine *e, const OhFrame *f, OhDevFrame **out)
     int s_scaling = add(f->scaling, f->scaling ? sizeof(OhScalingList) : 0);
     int s_inr = add(f->intra, (size_t)f->n_intra * sizeof(OhIntra));
     int s_ictur = add(cnt.n_ictu ? f->ictu : nullptr, (size_t)cnt.n_ictu * sizeof(OhIntraCtu));
-    int s_lvl = add(cnt.n_levels ? f->level_start : nullptr, cnt.n_levels ? ((size_t)cnt.n_levels + 1) * sizeof(uint32_t) : 0);
+    const uint32_t n_levels = f->n_intra ? f->n_levels : 0;
+    int s_lvl = add(n_levels ? f->level_start : nullptr, n_levels ? ((size_t)n_levels + 1) * sizeof(uint32_t) : 0);
     int s_sub = add(cnt.n_sub ? f->sub_start : nullptr, cnt.n_sub ? ((size_t)cnt.n_sub + 1) * sizeof(uint32_t) : 0);
     const bool cip = p.constrained_intra_pred && f->is_intra;
     int s_isin = add(cip ? f->is_intra : nullptr, cip ? n_pcm : 0);
@@ -1283,10 +1279,9 @@ static int upload_one(OhEngine *e, const OhFrame *f, OhDevFrame **out)
     /* the dense pool is the last copied segment: when every block came as levels nothing of it crosses PCIe */
     const size_t copy_bytes = any_dense || !f->n_tu ? total : seg[s_coef].off;
     /* device only.  The first four are cleared before the preparation kernels run. */
-    const size_t sum_bytes = sizeof(DevSummary) + (size_t)cnt.n_levels * sizeof(DevLevelStat);
     const size_t zero_off = total;
     int s_cursor = add(nullptr, 16 * sizeof(uint32_t));
-    int s_sum = add(nullptr, sum_bytes);
+    int s_sum = add(nullptr, sizeof(DevSummary));
     int s_seen = add(nullptr, cnt.n_intra ? n_ctb * sizeof(uint32_t) : 0);
     int s_keep = add(nullptr, f->n_tu);
     const size_t zero_bytes = total - zero_off;
@@ -1394,7 +1389,7 @@ static int upload_one(OhEngine *e, const OhFrame *f, OhDevFrame **out)
     hd.err_word = e->kerr; hd.cur_pic_id = f->cur_pic;
 #undef AT
     hd.n_pu = f->n_pu; hd.n_mc_luma = cnt.n_mc_luma; hd.n_mc_chroma = cnt.n_mc_chroma; hd.n_tu = f->n_tu; hd.n_intra = f->n_intra;
-    hd.n_ictu = cnt.n_ictu; hd.n_sub = cnt.n_sub; hd.n_levels = cnt.n_levels; hd.n_wp = f->n_wp; hd.n_sparse = f->sparse ? f->n_sparse : 0;
+    hd.n_ictu = cnt.n_ictu; hd.n_sub = cnt.n_sub; hd.n_levels = n_levels; hd.n_wp = f->n_wp; hd.n_sparse = f->sparse ? f->n_sparse : 0;
     hd.ref_ok = ref_ok; hd.n_coeff = f->n_coeff;
     hd.n_cross = n_cross;
     hd.zero_ptr = (uint32_t *)(base + zero_off); hd.zero_words = (uint32_t)(zero_bytes / 4);
@@ -1411,8 +1406,7 @@ static int upload_one(OhEngine *e, const OhFrame *f, OhDevFrame **out)
     { HostTimer t(e, OH_HT_UPLOAD_STAGE_WAIT);
     sg = stage_acquire(e, direct ? own_bytes : copy_bytes);   /* a pinned buffer whose previous copy has completed */
     }
-    df->sum_host = summary_block_get(e, sum_bytes, &df->sum_pooled);
-    df->sum_bytes = sum_bytes;
+    df->sum_host = summary_block_get(e);
     hd.summary_host = df->sum_host;                        /* pinned, device-accessible: prep_finish stores the summary there */
     if (!sg || !df->sum_host) {
         free_dev_frame(e, df);
@@ -1499,11 +1493,9 @@ static int upload_one(OhEngine *e, const OhFrame *f, OhDevFrame **out)
     }
     df->d = (DevFrame *)base;
     df->p = p;
-    df->n_mc_luma = cnt.n_mc_luma; df->n_mc_chroma = cnt.n_mc_chroma; df->n_tu = f->n_tu; df->n_intra = f->n_intra;
     for (int k = 0; k < 4; k++) df->tu_cnt[k] = tu_cnt[k];
     df->n_cross = n_cross;
     df->has_sao = has_sao;
-    df->n_levels = cnt.n_levels;
     df->cur_pic = f->cur_pic;                  /* which half of cur_pic is final changes when the list is EXECUTED, not here */
     df->owner = e;
     *out = df;
@@ -1528,7 +1520,7 @@ static int finish_uploads(OhEngine *e, OhDevFrame *const *dfs, int n)
             B.f[i] = df->d;
             mx.n_pu = std::max(mx.n_pu, df->cnt.n_pu); mx.n_tu = std::max(mx.n_tu, df->cnt.n_tu);
             mx.n_intra = std::max(mx.n_intra, df->cnt.n_intra); mx.n_sub = std::max(mx.n_sub, df->cnt.n_sub);
-            mx.n_ictu = std::max(mx.n_ictu, df->cnt.n_ictu); mx.n_levels = std::max(mx.n_levels, df->cnt.n_levels);
+            mx.n_ictu = std::max(mx.n_ictu, df->cnt.n_ictu);
             max_runs = std::max(max_runs, ((df->cnt.n_mc_luma + 63) >> 6) + ((df->cnt.n_mc_chroma + 63) >> 6));
             max_cross = std::max(max_cross, df->n_cross);
         }
@@ -1590,13 +1582,8 @@ static int read_summary(OhEngine *e, OhDevFrame *df, int index)
         if (s->tu_cnt[k] != df->tu_cnt[k])
             FAIL(e, OH_E_ARG, "work list %d: transform block counts changed between hand-over and preparation", index);
     df->intra_area64 = s->intra_area64; df->max_passes = s->max_passes;
-    const DevLevelStat *ls = (const DevLevelStat *)(s + 1);
-    df->levels.resize(df->n_levels);
-    for (uint32_t l = 0; l < df->n_levels; l++) {
-        OhDevFrame::Level &L = df->levels[l];
-        L.n_ctu = ls[l].n_ctu; L.max_items = ls[l].max_items; L.max_sub = ls[l].max_sub; L.max_res = ls[l].max_res;
-        L.staged = ls[l].staged != 0; L.sum_items = ls[l].sum_items; L.sum_sub = ls[l].sum_sub;
-    }
+    df->max_items = s->max_items; df->max_sub = s->max_sub; df->max_res = s->max_res; df->res_scattered = s->res_scattered != 0;
+    df->sum_items = s->sum_items; df->sum_sub = s->sum_sub;
     return OH_OK;
 }
 
@@ -1632,7 +1619,7 @@ static int intra_pass(OhEngine *e, OhDevFrame *const *fr, int nb, const OhBatch 
     bool staged = true;
     const uint64_t pic_samples64 = ((uint64_t)p->width * p->height * (p->chroma_format_idc == 0 ? 2 : p->chroma_format_idc == 1 ? 3 : p->chroma_format_idc == 2 ? 4 : 6) / 2) >> 6;
     for (int i = 0; i < nb; i++) {
-        if (fr[i]->levels.empty())
+        if (!fr[i]->cnt.n_ictu)
             continue;
         max_ictu_all = std::max(max_ictu_all, fr[i]->cnt.n_ictu);
         const bool sparse = force_direct || (!force_dag && (uint64_t)fr[i]->intra_area64 * 2 < pic_samples64);
@@ -1644,11 +1631,10 @@ static int intra_pass(OhEngine *e, OhDevFrame *const *fr, int nb, const OhBatch 
         bs.f[ns++] = fr[i]->d;
         max_ictu_s = std::max(max_ictu_s, fr[i]->cnt.n_ictu);
         total_entries += fr[i]->cnt.n_ictu;
-        for (const OhDevFrame::Level &L : fr[i]->levels) {
-            max_items = std::max(max_items, L.max_items); max_sub = std::max(max_sub, L.max_sub); max_res = std::max(max_res, L.max_res);
-            sum_items += L.sum_items; sum_sub += L.sum_sub;
-            staged = staged && (L.staged || !L.n_ctu);
-        }
+        const OhDevFrame &d = *fr[i];
+        max_items = std::max(max_items, d.max_items); max_sub = std::max(max_sub, d.max_sub); max_res = std::max(max_res, d.max_res);
+        sum_items += d.sum_items; sum_sub += d.sum_sub;
+        staged = staged && !d.res_scattered;
     }
     if (!nd && !ns)
         return OH_OK;
@@ -1803,7 +1789,7 @@ extern "C" int oh_frames_execute(OhEngine *e, OhDevFrame *const *dfs, int n)
         uint32_t max_luma = 0, max_chroma = 0, max_tu[4] = { 0, 0, 0, 0 };
         for (int i = 0; i < nb; i++) {
             all.f[i] = fr[i]->d;
-            max_luma = std::max(max_luma, fr[i]->n_mc_luma); max_chroma = std::max(max_chroma, fr[i]->n_mc_chroma);
+            max_luma = std::max(max_luma, fr[i]->cnt.n_mc_luma); max_chroma = std::max(max_chroma, fr[i]->cnt.n_mc_chroma);
             for (int k = 0; k < 4; k++) max_tu[k] = std::max(max_tu[k], fr[i]->tu_cnt[k]);
         }
         ohk_inter(&all, nb, p, max_luma, max_chroma, st);

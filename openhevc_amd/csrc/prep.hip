@@ -12,8 +12,10 @@
  *   OhIntra[], sub_start       prep_intra_sub         <= 8x8 blocks first inside a sub-level (four of them share a wave)
  *                              prep_intra_items       DevIntra: LDS offsets, edge sizes, filter / class flags, angles, the
  *                                                     constrained-intra masks (hevcpred_template.c:116-163)
- *   OhIntraCtu[], level_start  prep_intra_ctu / _levels  DevIntraCtu (residual span, staged rectangle); the per-level launch
- *                                                     statistics the host sizes the intra launches with (DevSummary)
+ *   OhIntraCtu[], level_start  prep_intra_ctu         DevIntraCtu (residual span, staged rectangle), the entry's level
+ *                              prep_intra_wait        the entries each entry waits for (ctu_wait: neighbours of a lower level)
+ *                              prep_intra_order       the dispatch order of the wave-per-CTU form; the statistics the host lays
+ *                                                     out the staged intra launch with (DevSummary)
  *
  * Every index a pass kernel will follow is checked HERE (what engine.hip's host loop used to do): the first violation is
  * latched in DevSummary.err, the remaining preparation kernels and — because oh_frames_execute reads the summary before it
@@ -407,9 +409,9 @@ __global__ __launch_bounds__(256) void prep_intra_items(const OhBatch B)
     o[0] = q[0]; o[1] = q[1];
 }
 
-/* One wave per entry of the schedule (a CTU that holds intra blocks): the entry is checked (the level -> ictu[] -> sub_start[]
- * -> intra[] nesting the intra kernel follows blindly), its residual span and the rectangle to stage are reduced over its
- * blocks, lanes taking the blocks in turn; ctu_aux[k] keeps what the level statistics need of it. */
+/* One wave per entry of the schedule (a CTU that holds intra blocks): the entry is checked (the ictu[] -> sub_start[] -> intra[]
+ * nesting the intra kernel follows blindly), its residual span and the rectangle to stage are reduced over its blocks, lanes
+ * taking the blocks in turn; ctu_aux[k] keeps what prep_intra_wait and prep_intra_order need of it, ctu_lvl[k] its level. */
 __global__ __launch_bounds__(64) void prep_intra_ctu(const OhBatch B)
 {
     const DevFrame *__restrict__ f = B.f[blockIdx.y];
@@ -491,47 +493,17 @@ __global__ __launch_bounds__(64) void prep_intra_ctu(const OhBatch B)
         GLOBAL uint4v *o = (GLOBAL uint4v *)((DevIntraCtu *)f->ictu + k);
         o[0] = q[0]; o[1] = q[1];
         f->ctu_aux[k] = min(slot_passes, (uint32_t)OH_AUX_PASSES) | (uint32_t)dep << OH_AUX_DEP_SHIFT | (any_res && !res_cnt ? (uint32_t)OH_AUX_RES_SCATTERED : 0u);
+        /* the level of entry k: the last l with lvl_start[l] <= k (empty levels are skipped; the host checked the table: it starts
+         * at 0, ends at n_ictu and does not fall) */
+        uint32_t l0 = 0, l1 = f->n_levels;                     /* lvl_start[l0] <= k < lvl_start[l1] */
+        while (l1 - l0 > 1) {
+            const uint32_t m = (l0 + l1) / 2;
+            if (f->lvl_start[m] <= k) l0 = m; else l1 = m;
+        }
+        f->ctu_lvl[k] = l0;
         DevSummary *sm = summary_of(f);
         atomicAdd(&sm->intra_area64, (area + 63) >> 6);
         atomicMax(&sm->max_passes, slot_passes);
-    }
-}
-
-/* one wave per wavefront level: the launch statistics of the level, reduced over its CTUs into the summary */
-__global__ __launch_bounds__(64) void prep_intra_levels(const OhBatch B)
-{
-    const DevFrame *__restrict__ f = B.f[blockIdx.y];
-    const uint32_t l = blockIdx.x;
-    if (l >= f->n_levels || failed(f))
-        return;
-    const uint32_t k0 = f->lvl_start[l], k1 = f->lvl_start[l + 1];         /* the host checked the level table (it needs it) */
-    uint32_t max_items = 1, max_sub = 1, max_res = 0, staged = 1;
-    unsigned long long sum_items = 0, sum_sub = 0;
-    for (uint32_t k = k0 + threadIdx.x; k < k1; k += 64) {
-        const DevIntraCtu d = gload(f->ictu + k);
-        const uint32_t aux = f->ctu_aux[k];
-        f->ctu_lvl[k] = l;
-        if (aux & OH_AUX_RES_SCATTERED) staged = 0;
-        max_items = max(max_items, min(d.n_items & 0xffffu, (uint32_t)OH_MAX_CTU_BLOCKS));
-        max_sub = max(max_sub, min((uint32_t)d.n_sub, (uint32_t)OH_MAX_CTU_BLOCKS));
-        max_res = max(max_res, d.res_cnt);
-        sum_items += aux & OH_AUX_PASSES;
-        sum_sub += d.n_sub;
-    }
-#pragma unroll
-    for (int d = 32; d; d >>= 1) {
-        max_items = max(max_items, (uint32_t)__shfl_xor((int)max_items, d));
-        max_sub = max(max_sub, (uint32_t)__shfl_xor((int)max_sub, d));
-        max_res = max(max_res, (uint32_t)__shfl_xor((int)max_res, d));
-        staged = min(staged, (uint32_t)__shfl_xor((int)staged, d));
-        sum_items += __shfl_xor(sum_items, d);
-        sum_sub += __shfl_xor(sum_sub, d);
-    }
-    if (threadIdx.x == 0) {
-        DevLevelStat s;
-        s.n_ctu = k1 - k0; s.max_items = max_items; s.max_sub = max_sub; s.max_res = max_res; s.staged = staged; s.pad = 0;
-        s.sum_items = sum_items; s.sum_sub = sum_sub;
-        *((DevLevelStat *)(summary_of(f) + 1) + l) = s;
     }
 }
 
@@ -573,7 +545,8 @@ __global__ __launch_bounds__(256) void prep_intra_wait(const OhBatch B)
  * wait still points at a lower position), then the entries nothing depends on.  The chains — a B picture's few levels, each as long
  * as one CTU's latency — then start with the launch and the independent CTUs, the bulk, fill the chip around them; in plain schedule
  * order a chain's second link is not even dispatched before every independent CTU of the batch has been.  One workgroup per
- * picture: a stable partition by a block-wide scan. */
+ * picture: a stable partition by a block-wide scan.  The same workgroup reduces the picture's statistics for the layout of the
+ * staged form (engine.hip: intra_pass) into the summary. */
 __global__ __launch_bounds__(256) void prep_intra_order(const OhBatch B)
 {
     const DevFrame *__restrict__ f = B.f[blockIdx.x];
@@ -581,7 +554,35 @@ __global__ __launch_bounds__(256) void prep_intra_order(const OhBatch B)
     if (!n || failed(f))
         return;
     __shared__ uint32_t cnt[256];
+    __shared__ uint32_t wmax[4][4];
+    __shared__ unsigned long long wsum[2][4];
     const uint32_t t = threadIdx.x, per = (n + 255u) / 256u, b0 = min(t * per, n), b1 = min(b0 + per, n);
+    uint32_t max_items = 1, max_sub = 1, max_res = 0, scattered = 0;
+    unsigned long long sum_items = 0, sum_sub = 0;
+    for (uint32_t k = t; k < n; k += 256) {
+        const DevIntraCtu d = gload(f->ictu + k);
+        const uint32_t aux = f->ctu_aux[k];
+        scattered |= (aux & OH_AUX_RES_SCATTERED) != 0u;
+        max_items = max(max_items, min(d.n_items & 0xffffu, (uint32_t)OH_MAX_CTU_BLOCKS));
+        max_sub = max(max_sub, min((uint32_t)d.n_sub, (uint32_t)OH_MAX_CTU_BLOCKS));
+        max_res = max(max_res, d.res_cnt);
+        sum_items += aux & OH_AUX_PASSES;
+        sum_sub += d.n_sub;
+    }
+#pragma unroll
+    for (int d = 32; d; d >>= 1) {
+        max_items = max(max_items, (uint32_t)__shfl_xor((int)max_items, d));
+        max_sub = max(max_sub, (uint32_t)__shfl_xor((int)max_sub, d));
+        max_res = max(max_res, (uint32_t)__shfl_xor((int)max_res, d));
+        scattered |= (uint32_t)__shfl_xor((int)scattered, d);
+        sum_items += __shfl_xor(sum_items, d);
+        sum_sub += __shfl_xor(sum_sub, d);
+    }
+    if ((t & 63) == 0) {
+        const uint32_t w = t >> 6;
+        wmax[0][w] = max_items; wmax[1][w] = max_sub; wmax[2][w] = max_res; wmax[3][w] = scattered;
+        wsum[0][w] = sum_items; wsum[1][w] = sum_sub;
+    }
     uint32_t c = 0;
     for (uint32_t k = b0; k < b1; k++)
         c += (f->ctu_aux[k] & (OH_AUX_WAITS | OH_AUX_AWAITED)) != 0u;
@@ -594,6 +595,15 @@ __global__ __launch_bounds__(256) void prep_intra_order(const OhBatch B)
         __syncthreads();
     }
     const uint32_t n_chain = cnt[255];
+    if (t == 0) {                                              /* wave 0's totals + the other waves' */
+        for (int w = 1; w < 4; w++) {
+            max_items = max(max_items, wmax[0][w]); max_sub = max(max_sub, wmax[1][w]); max_res = max(max_res, wmax[2][w]);
+            scattered |= wmax[3][w]; sum_items += wsum[0][w]; sum_sub += wsum[1][w];
+        }
+        DevSummary *s = summary_of(f);
+        s->max_items = max_items; s->max_sub = max_sub; s->max_res = max_res; s->res_scattered = scattered;
+        s->sum_items = sum_items; s->sum_sub = sum_sub;
+    }
     uint32_t pc = cnt[t] - c, pi = n_chain + (b0 - pc);       /* chain entries before this segment; independent ones likewise */
     for (uint32_t k = b0; k < b1; k++) {
         if (f->ctu_aux[k] & (OH_AUX_WAITS | OH_AUX_AWAITED)) f->ctu_order[pc++] = k;
@@ -602,7 +612,7 @@ __global__ __launch_bounds__(256) void prep_intra_order(const OhBatch B)
 }
 
 /* last: the counts are compared with the host's (the bucket ranges were laid out for them) and the summary — error, counts,
- * level statistics — goes to the list's pinned host block with plain stores: visible to the host once the event behind this
+ * intra statistics — goes to the list's pinned host block with plain stores: visible to the host once the event behind this
  * kernel has completed */
 __global__ __launch_bounds__(64) void prep_finish(const OhBatch B)
 {
@@ -617,10 +627,9 @@ __global__ __launch_bounds__(64) void prep_finish(const OhBatch B)
         if (f->tu_cursor[9] != f->n_cross) fail(f, OH_PE_TU, 0xffffffffu);
     }
     __syncthreads();
-    const uint32_t words = (uint32_t)((sizeof(DevSummary) + (size_t)f->n_levels * sizeof(DevLevelStat)) / 4);
     const uint32_t *src = (const uint32_t *)s;
     uint32_t *dst = (uint32_t *)f->summary_host;
-    for (uint32_t i = threadIdx.x; i < words; i += 64)
+    for (uint32_t i = threadIdx.x; i < sizeof(DevSummary) / 4; i += 64)
         dst[i] = *(volatile const uint32_t *)(src + i);
 }
 
@@ -692,7 +701,6 @@ extern "C" void ohk_prepare(const OhBatch *B, int nb, const OhPrepCounts *n, uin
         hipLaunchKernelGGL(prep_intra_sub, dim3((n->n_sub + 255) / 256, nb), dim3(256), 0, st, *B);
         hipLaunchKernelGGL(prep_intra_items, dim3((n->n_intra + 255) / 256, nb), dim3(256), 0, st, *B);
         hipLaunchKernelGGL(prep_intra_ctu, dim3(n->n_ictu, nb), dim3(64), 0, st, *B);
-        hipLaunchKernelGGL(prep_intra_levels, dim3(n->n_levels, nb), dim3(64), 0, st, *B);
         hipLaunchKernelGGL(prep_intra_wait, dim3((n->n_ictu + 255) / 256, nb), dim3(256), 0, st, *B);
         hipLaunchKernelGGL(prep_intra_order, dim3(nb), dim3(256), 0, st, *B);
     }
