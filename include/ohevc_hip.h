@@ -30,6 +30,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "ohevc_frame.h"
+#include "ohevc_annexb.h"                  /* OhPictureHash */
 
 #ifdef __cplusplus
 extern "C" {
@@ -103,6 +104,11 @@ int oh_download_finish(OhEngine *e, OhDownload *d, uint8_t *const planes[3], con
 /* MD5 of the three planes of n finished pictures computed on the GPU — the digests of the decoded-picture-hash SEI (hevc.c:4146-4162,
  * calc_md5 hevc.c:4623-4638: whole coded planes, rows packed, little-endian samples).  digests: n x 3 x 16 bytes.  Waits for the engine. */
 int oh_pics_md5(OhEngine *e, const int *pic_ids, int n, uint8_t *digests);
+/* hash_type 0 MD5 (what oh_pics_md5 computes), 1 CRC, 2 checksum (H.265 Annex D decoded picture hash) of the whole coded planes
+ * of n finished pictures; out[i]: present = 1, hash_type, and the plane values (planes a monochrome picture lacks: 0), in the
+ * layout oh_sei_picture_hash fills, so a check is a comparison.  Waits for the engine stream.  n == 0: OH_OK.
+ * OH_E_ARG: an unknown picture or hash_type outside 0..2. */
+int oh_pics_hash(OhEngine *e, const int *pic_ids, int n, int hash_type, OhPictureHash *out);
 
 /* SHVC inter-layer reference picture: resample the finished base-layer picture src_pic into
  * the enhancement-layer picture dst_pic, bit-exact with the reference's whole-picture slot

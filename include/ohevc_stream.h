@@ -115,6 +115,9 @@ int  oh_stream_write_opts(const OhStreamParams *p, unsigned opts, OhStream *out)
 /* the same stream with a decoded-picture-hash SEI (MD5, payload type 132, suffix SEI NAL) behind every picture;
  * md5[i * 48 ..]: the three plane digests of picture i in decode order */
 int  oh_stream_add_md5(const OhStream *in, const uint8_t *md5, OhStream *out);
+/* the same for any hash_type of the SEI (0 MD5, 1 CRC, 2 checksum; else -1): payload holds, per picture in decode order, its three
+ * plane values of 16, 2 or 4 bytes as the message carries them (CRC and checksum big-endian); oh_stream_add_md5 is hash_type 0 */
+int  oh_stream_add_hash(const OhStream *in, int hash_type, const uint8_t *payload, OhStream *out);
 void oh_stream_free(OhStream *s);
 
 #ifdef __cplusplus

@@ -188,6 +188,8 @@ struct OhEngine {
     uint64_t    dl_count = 0;
     std::vector<CopyJob> copy_jobs;
     uint32_t   *kerr = nullptr;
+    void       *hash_dev = nullptr;      /* oh_pics_hash (CRC / checksum): the job table, its tasks and their values in HBM */
+    size_t      hash_dev_bytes = 0;
     uint32_t    spin_limit = 1u << 22;   /* polls (with s_sleep between them, ~1 s in all) before a waiting workgroup gives up; OHEVC_SPIN_LIMIT */
 };
 
@@ -434,6 +436,7 @@ extern "C" void oh_engine_destroy(OhEngine *e)
     for (auto *c : e->dl_stages) { (void)hipEventDestroy(c->done); (void)hipHostFree(c->p); delete c; }
     if (e->kerr) (void)hipHostFree(e->kerr);
     if (e->tickets) (void)hipFree(e->tickets);
+    if (e->hash_dev) (void)hipFree(e->hash_dev);
     for (auto &ev : e->batch_ev) if (ev) (void)hipEventDestroy(ev);
     if (e->dl_stream) { (void)hipStreamSynchronize(e->dl_stream); (void)hipStreamDestroy(e->dl_stream); }
     if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);
@@ -1025,19 +1028,41 @@ extern "C" int oh_pic_download_window(OhEngine *e, int pic_id, const OhWindow *w
     return rc2;
 }
 
+/* the planes of n pictures (ids checked) as hash jobs, the half that holds the final samples; slot[i * 3 + c]: the job of plane c of
+ * picture i, -1 for the planes a monochrome picture lacks.  Returns the number of jobs. */
+static int plane_jobs(OhEngine *e, const int *pic_ids, int n, OhMd5Job *jobs, int *slot)
+{
+    int nj = 0;
+    for (int i = 0; i < n; i++) {
+        const Pic *p = get_pic(e, pic_ids[i]);
+        const uint32_t bpp = p->p.bit_depth > 8 ? 2 : 1;
+        for (int c = 0; c < 3; c++) {
+            slot[i * 3 + c] = -1;
+            if (c && !p->p.chroma_format_idc)
+                continue;
+            OhMd5Job &j = jobs[nj];
+            j.base = p->final_b ? p->b[c] : p->a[c];
+            j.pitch = (uint32_t)p->stride[c] * bpp; j.row_bytes = (uint32_t)p->w[c] * bpp; j.rows = (uint32_t)p->h[c]; j.bps = bpp;
+            slot[i * 3 + c] = nj++;
+        }
+    }
+    return nj;
+}
+
+static int check_pics(OhEngine *e, const int *pic_ids, int n, const char *who)
+{
+    for (int i = 0; i < n; i++)
+        if (!get_pic(e, pic_ids[i]))
+            FAIL(e, OH_E_ARG, "%s: unknown picture %d", who, pic_ids[i]);
+    return OH_OK;
+}
+
 /* Picture hash on the GPU: the three plane digests of the reference's SEI check (hevc.c:4146-4162 over calc_md5,
  * hevc.c:4623-4638: the whole coded planes, sps->width x sps->height and the chroma sizes, packed rows) for n finished pictures in one
  * launch of one chain per (picture, plane) — md5.hip.  48 bytes per picture come back instead of the picture.  Waits for the engine
- * stream.  digests: n x 3 x 16 bytes (monochrome: planes 1, 2 zero). */
-extern "C" int oh_pics_md5(OhEngine *e, const int *pic_ids, int n, uint8_t *digests)
+ * stream.  digests: n x 3 x 16 bytes (monochrome: planes 1, 2 zero).  pic_ids checked. */
+static int pics_md5(OhEngine *e, const int *pic_ids, int n, uint8_t *digests)
 {
-    if (!e || n < 0 || (n && (!pic_ids || !digests)))
-        return OH_E_ARG;
-    if (!n)
-        return OH_OK;
-    for (int i = 0; i < n; i++)
-        if (!get_pic(e, pic_ids[i]))
-            FAIL(e, OH_E_ARG, "oh_pics_md5: unknown picture %d", pic_ids[i]);
     HIPCHK(e, hipSetDevice(e->device));
     const size_t jobs_bytes = align_up((size_t)n * 3 * sizeof(OhMd5Job), 256);
     OhEngine::Stage *sg = stage_acquire(e, jobs_bytes + (size_t)n * 48);
@@ -1045,18 +1070,8 @@ extern "C" int oh_pics_md5(OhEngine *e, const int *pic_ids, int n, uint8_t *dige
         FAIL(e, OH_E_NOMEM, "hipHostMalloc for %d picture hashes failed", n);
     OhMd5Job *jobs = (OhMd5Job *)sg->p;
     uint8_t *out = (uint8_t *)sg->p + jobs_bytes;
-    int nj = 0;
-    std::vector<int> slot((size_t)n * 3, -1);
-    for (int i = 0; i < n; i++) {
-        const Pic *p = get_pic(e, pic_ids[i]);
-        const uint32_t bpp = p->p.bit_depth > 8 ? 2 : 1;
-        for (int c = 0; c < (p->p.chroma_format_idc ? 3 : 1); c++) {
-            OhMd5Job &j = jobs[nj];
-            j.base = p->final_b ? p->b[c] : p->a[c];
-            j.pitch = (uint32_t)p->stride[c] * bpp; j.row_bytes = (uint32_t)p->w[c] * bpp; j.rows = (uint32_t)p->h[c]; j.pad = 0;
-            slot[(size_t)i * 3 + c] = nj++;
-        }
-    }
+    std::vector<int> slot((size_t)n * 3);
+    const int nj = plane_jobs(e, pic_ids, n, jobs, slot.data());
     ohk_md5(jobs, nj, out, e->stream);                        /* pinned host memory is mapped: the kernel reads the jobs and writes the digests there */
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -1064,6 +1079,92 @@ extern "C" int oh_pics_md5(OhEngine *e, const int *pic_ids, int n, uint8_t *dige
     for (size_t k = 0; k < slot.size(); k++) {
         if (slot[k] >= 0) memcpy(digests + k * 16, out + (size_t)slot[k] * 16, 16);
         else memset(digests + k * 16, 0, 16);
+    }
+    return OH_OK;
+}
+
+extern "C" int oh_pics_md5(OhEngine *e, const int *pic_ids, int n, uint8_t *digests)
+{
+    if (!e || n < 0 || (n && (!pic_ids || !digests)))
+        return OH_E_ARG;
+    if (!n)
+        return OH_OK;
+    { const int rc = check_pics(e, pic_ids, n, "oh_pics_md5"); if (rc) return rc; }
+    return pics_md5(e, pic_ids, n, digests);
+}
+
+/* CRC (kind 1) or checksum (kind 2) of every plane of n pictures (ids checked): vals[i * 3 + c], 0 for planes a monochrome picture
+ * lacks.  hash.hip: one workgroup per OH_HASH_TASK bytes of every plane in one launch, then one per plane to combine.  The job table
+ * and the task list are staged in pinned memory and copied to HBM in one piece; the values come back through the pinned buffer. */
+static int pics_crc_checksum(OhEngine *e, const int *pic_ids, int n, int kind, uint32_t *vals)
+{
+    HIPCHK(e, hipSetDevice(e->device));
+    std::vector<int> slot((size_t)n * 3);
+    std::vector<OhMd5Job> jv((size_t)n * 3);
+    const int nj = plane_jobs(e, pic_ids, n, jv.data(), slot.data());
+    std::vector<uint32_t> first((size_t)nj + 1, 0);
+    for (int k = 0; k < nj; k++) {
+        const uint64_t bytes = (uint64_t)jv[k].row_bytes * jv[k].rows;
+        first[k + 1] = first[k] + (uint32_t)((bytes + OH_HASH_TASK - 1) / OH_HASH_TASK);
+    }
+    const uint32_t nt = first[nj];
+    const size_t o_first = align_up((size_t)nj * sizeof(OhMd5Job), 256), o_map = o_first + align_up(((size_t)nj + 1) * 4, 256),
+                 o_part = o_map + align_up((size_t)nt * 8, 256), dev_bytes = o_part + align_up((size_t)nt * 4, 256);
+    if (dev_bytes > e->hash_dev_bytes) {                     /* every call ends with a wait: the old buffer is idle */
+        if (e->hash_dev) (void)hipFree(e->hash_dev);
+        e->hash_dev = nullptr; e->hash_dev_bytes = 0;
+        const size_t want = align_up(dev_bytes, (size_t)1 << 20);
+        HIPCHK(e, hipMalloc(&e->hash_dev, want));
+        e->hash_dev_bytes = want;
+    }
+    OhEngine::Stage *sg = stage_acquire(e, o_part + (size_t)nj * 4);
+    if (!sg)
+        FAIL(e, OH_E_NOMEM, "hipHostMalloc for %d picture hashes failed", n);
+    char *h = (char *)sg->p, *d = (char *)e->hash_dev;
+    memcpy(h, jv.data(), (size_t)nj * sizeof(OhMd5Job));
+    memcpy(h + o_first, first.data(), ((size_t)nj + 1) * 4);
+    uint32_t *map = (uint32_t *)(h + o_map);
+    for (int k = 0; k < nj; k++)
+        for (uint32_t t = first[k]; t < first[k + 1]; t++) { map[2 * t] = (uint32_t)k; map[2 * t + 1] = t - first[k]; }
+    uint32_t *out = (uint32_t *)(h + o_part);                 /* pinned and mapped: the combine kernel writes the plane values there */
+    HIPCHK(e, hipMemcpyAsync(d, h, o_part, hipMemcpyHostToDevice, e->stream));
+    ohk_hash(kind, (const OhMd5Job *)d, (const uint32_t *)(d + o_first), (const uint32_t *)(d + o_map), nj, (int)nt, (uint32_t *)(d + o_part), out,
+             e->stream);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    { const int ke = kernel_error(e); if (ke) return ke; }
+    for (size_t k = 0; k < slot.size(); k++)
+        vals[k] = slot[k] >= 0 ? out[slot[k]] : 0;
+    return OH_OK;
+}
+
+extern "C" int oh_pics_hash(OhEngine *e, const int *pic_ids, int n, int hash_type, OhPictureHash *out)
+{
+    if (!e || n < 0 || (n && (!pic_ids || !out)))
+        return OH_E_ARG;
+    if (hash_type < 0 || hash_type > 2)
+        FAIL(e, OH_E_ARG, "oh_pics_hash: hash_type %d (0 MD5, 1 CRC, 2 checksum)", hash_type);
+    if (!n)
+        return OH_OK;
+    { const int rc = check_pics(e, pic_ids, n, "oh_pics_hash"); if (rc) return rc; }
+    if (hash_type == 0) {
+        std::vector<uint8_t> dg((size_t)n * 48);
+        const int rc = pics_md5(e, pic_ids, n, dg.data());
+        if (rc) return rc;
+        for (int i = 0; i < n; i++) {
+            memset(&out[i], 0, sizeof(out[i]));
+            out[i].present = 1;
+            memcpy(out[i].md5, dg.data() + (size_t)i * 48, 48);
+        }
+        return OH_OK;
+    }
+    std::vector<uint32_t> v((size_t)n * 3);
+    const int rc = pics_crc_checksum(e, pic_ids, n, hash_type, v.data());
+    if (rc) return rc;
+    for (int i = 0; i < n; i++) {
+        memset(&out[i], 0, sizeof(out[i]));
+        out[i].present = 1; out[i].hash_type = hash_type;
+        for (int c = 0; c < 3; c++) (hash_type == 1 ? out[i].crc : out[i].checksum)[c] = v[(size_t)i * 3 + c];
     }
     return OH_OK;
 }

@@ -14,18 +14,21 @@ struct OhUpBlkArgs {
     int32_t ctbs_x;
 };
 
-/* one MD5 chain: a plane's packed rows (md5.hip) */
+/* one plane to hash: its packed rows (one MD5 chain, md5.hip; CRC / checksum tasks, hash.hip) */
 struct OhMd5Job {
     const void *base;            /* first sample of the plane */
     uint32_t    pitch;           /* bytes between rows */
     uint32_t    row_bytes;       /* bytes hashed per row */
     uint32_t    rows;
-    uint32_t    pad;
+    uint32_t    bps;             /* bytes per sample (1, 2): the checksum's sample column; MD5 does not read it */
 };
+enum { OH_HASH_TASK = 128 << 10 };   /* packed plane bytes per CRC / checksum workgroup (hash.hip) */
 
 extern "C" {
 int  ohk_init(void);
 void ohk_md5(const OhMd5Job *jobs, int n, void *digests, hipStream_t st);
+void ohk_hash(int kind, const OhMd5Job *jobs, const uint32_t *first, const uint32_t *task_map, int n_jobs, int n_tasks, uint32_t *partials,
+              uint32_t *out, hipStream_t st);
 void ohk_inter(const OhBatch *B, int n, const OhPicParams *p, uint32_t max_luma, uint32_t max_chroma, hipStream_t st);
 void ohk_residual(const OhBatch *B, int n, const OhPicParams *p, const uint32_t max_cnt[4], hipStream_t st);
 void ohk_cross(const OhBatch *B, int n, const OhPicParams *p, uint32_t max_cross, hipStream_t st);

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 
 from . import frame as F
+from .annexb import OhPictureHash
 
 OH_N_PASSES = 6
 PASS_NAMES = ("inter", "residual", "intra", "deblock_v", "deblock_h", "sao")
@@ -63,6 +64,7 @@ def lib():
         L.oh_pic_upsample_blocks.argtypes = [V, I, I, C.c_void_p, I, C.POINTER(OhWindow), C.POINTER(C.c_uint32), I]
         L.oh_upsample_blocks_defined.argtypes = [C.c_void_p, I, I, I, I, I, C.POINTER(I)]
         L.oh_pics_md5.argtypes = [V, C.POINTER(C.c_int), I, C.POINTER(C.c_uint8)]
+        L.oh_pics_hash.argtypes = [V, C.POINTER(C.c_int), I, I, C.POINTER(OhPictureHash)]
         L.oh_frame_upload.argtypes = [V, C.POINTER(F.OhFrame), PP]
         L.oh_frames_upload.argtypes = [V, C.POINTER(C.POINTER(F.OhFrame)), I, PP]
         L.oh_frame_execute.argtypes = [V, V]
@@ -223,6 +225,17 @@ class Engine:
         self._chk(self.L.oh_pics_md5(self.h, ids, n, out), "oh_pics_md5")
         raw = bytes(out)
         return [[raw[48 * i + 16 * c:48 * i + 16 * c + 16] for c in range(3)] for i in range(n)]
+
+    def pics_hash(self, pids, hash_type):
+        """[(hash_type, [plane 0, 1, 2])] of finished pictures, computed on the GPU (oh_pics_hash): hash_type 0 MD5 (16-byte values),
+        1 CRC, 2 checksum (ints) — the shape annexb.picture_hash gives for a decoded-picture-hash SEI"""
+        n = len(pids)
+        ids = (C.c_int * max(n, 1))(*pids)
+        out = (OhPictureHash * max(n, 1))()
+        self._chk(self.L.oh_pics_hash(self.h, ids, n, hash_type, out), "oh_pics_hash")
+        if hash_type == 0:
+            return [(0, [bytes(out[i].md5[c]) for c in range(3)]) for i in range(n)]
+        return [(hash_type, list(out[i].crc if hash_type == 1 else out[i].checksum)) for i in range(n)]
 
     def pic_device_planes(self, pid):
         p = (C.c_void_p * 3)()

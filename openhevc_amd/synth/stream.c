@@ -1640,9 +1640,10 @@ int oh_stream_write_opts(const OhStreamParams *p, unsigned opts, OhStream *out)
     return stream_write(p, opts, out);
 }
 
-int oh_stream_add_md5(const OhStream *in, const uint8_t *md5, OhStream *out)
+int oh_stream_add_hash(const OhStream *in, int hash_type, const uint8_t *payload, OhStream *out)
 {
-    if (!in || !md5 || !out)
+    const size_t per = hash_type == 0 ? 16 : hash_type == 1 ? 2 : hash_type == 2 ? 4 : 0;     /* bytes per plane value */
+    if (!in || !payload || !out || !per)
         return -1;
     Bits b = { 0 };
     out->au_offset = (size_t *)calloc((size_t)in->n_pictures + 1, sizeof(size_t));
@@ -1650,10 +1651,11 @@ int oh_stream_add_md5(const OhStream *in, const uint8_t *md5, OhStream *out)
         out->au_offset[i] = b.n / 8;
         for (size_t k = in->au_offset[i]; k < in->au_offset[i + 1]; k++) put_bits(&b, in->data[k], 8);
         uint8_t sei[2 + 1 + 48];
-        sei[0] = 132; sei[1] = 49; sei[2] = 0;             /* payload type: decoded picture hash; size; hash_type MD5 */
-        memcpy(sei + 3, md5 + (size_t)i * 48, 48);
+        const size_t len = 1 + 3 * per;
+        sei[0] = 132; sei[1] = (uint8_t)len; sei[2] = (uint8_t)hash_type;   /* payload type: decoded picture hash; size; hash_type */
+        memcpy(sei + 3, payload + (size_t)i * 3 * per, 3 * per);
         Bits r = { 0 };
-        for (size_t k = 0; k < sizeof(sei); k++) put_bits(&r, sei[k], 8);
+        for (size_t k = 0; k < 2 + len; k++) put_bits(&r, sei[k], 8);
         rbsp_trailing(&r);
         emit_nal(&b, 40, r.buf, r.n / 8);                  /* SUFFIX_SEI_NUT */
         free(r.buf);
@@ -1661,6 +1663,11 @@ int oh_stream_add_md5(const OhStream *in, const uint8_t *md5, OhStream *out)
     out->au_offset[in->n_pictures] = b.n / 8;
     out->data = b.buf; out->size = b.n / 8; out->n_pictures = in->n_pictures;
     return 0;
+}
+
+int oh_stream_add_md5(const OhStream *in, const uint8_t *md5, OhStream *out)
+{
+    return oh_stream_add_hash(in, 0, md5, out);
 }
 
 void oh_stream_free(OhStream *s)
