@@ -110,6 +110,41 @@ int oh_pics_md5(OhEngine *e, const int *pic_ids, int n, uint8_t *digests);
  * OH_E_ARG: an unknown picture or hash_type outside 0..2. */
 int oh_pics_hash(OhEngine *e, const int *pic_ids, int n, int hash_type, OhPictureHash *out);
 
+/* Output to the GPU's own consumers: n finished pictures, cropped to a window, as standard images in caller-owned DEVICE memory
+ * (DESIGN.md §3b has the exact definitions, which the tests check bit for bit).
+ *   OH_CONV_PLANAR      the packed Y plane, then Cb, then Cr (I420 / I422 / I444; 4:0:0 gives Y only)
+ *   OH_CONV_SEMIPLANAR  the packed Y plane, then one interleaved CbCr plane (NV12 / NV16 / NV24; P010 / P210 / P410 above 8 bit)
+ *   OH_CONV_RGB_PLANAR  3 x H x W;  OH_CONV_RGB  H x W x 3;  OH_CONV_RGBA  H x W x 4 (alpha at full scale)
+ * sample: NATIVE (YUV only: the stored samples, u8 at 8 bit, u16 above — LSB-aligned planar, MSB-aligned semi-planar) or U8 for the
+ * YUV formats; U8, U16, F16 or F32 for the RGB formats, which up-sample the chroma (0 nearest, 1 linear with chroma_sample_loc_type 0
+ * siting) and apply the H.273 matrix in the given range with integer coefficients (oh_convert_coeffs).  The matrix is read by the RGB
+ * formats only. */
+enum { OH_CONV_PLANAR = 0, OH_CONV_SEMIPLANAR, OH_CONV_RGB_PLANAR, OH_CONV_RGB, OH_CONV_RGBA };
+enum { OH_CONV_NATIVE = 0, OH_CONV_U8, OH_CONV_U16, OH_CONV_F16, OH_CONV_F32 };
+enum { OH_CONV_MAX_PICS = 64,     /* pictures per launch; a call with more is split into several launches */
+       OH_CONV_NCOEFFS = 9 };     /* oh_convert_coeffs: cy, crv, cgu, cgv, cbu, y offset, chroma mid, shift S, target depth D */
+typedef struct OhConvert {
+    int32_t format;               /* OH_CONV_PLANAR .. OH_CONV_RGBA */
+    int32_t sample;               /* OH_CONV_NATIVE .. OH_CONV_F32 */
+    int32_t matrix;               /* H.273 matrix_coefficients: 1 BT.709, 5 or 6 BT.601, 9 BT.2020 non-constant luminance */
+    int32_t full_range;           /* video_full_range_flag */
+    int32_t chroma_filter;        /* 0 nearest, 1 linear (chroma_sample_loc_type 0) */
+    OhWindow win;                 /* conformance window, luma samples, as for oh_pic_download_window */
+} OhConvert;
+/* n finished pictures with identical OhPicParams -> n images in caller-owned device memory of the engine's device, image i at
+ * dst + i * image_stride.  Reads each picture's finished half; enqueued on the engine stream behind the work that finished the
+ * pictures, returns without waiting (a kernel failure latched earlier surfaces at the next sync).  n == 0: OH_OK.
+ * OH_E_ARG, nothing written: an unknown picture, pictures whose params differ, an empty window or one whose offsets are not multiples
+ * of SubWidthC / SubHeightC, image_stride < oh_convert_image_bytes, image_stride or dst not a multiple of the output sample size,
+ * (n - 1) * image_stride + image bytes > dst_bytes, a dst that is not device memory of the engine's device (or whose allocation ends
+ * before the last image).  OH_E_UNSUPPORTED: a sample type that does not fit the format, a matrix outside
+ * {1, 5, 6, 9} (RGB formats), a semi-planar image of a 4:0:0 picture. */
+int    oh_pics_convert(OhEngine *e, const int *pic_ids, int n, const OhConvert *cv, void *dst, size_t image_stride, size_t dst_bytes);
+/* host only: bytes of one image; 0 when the combination is not valid (what oh_pics_convert would refuse for these params) */
+size_t oh_convert_image_bytes(const OhPicParams *p, const OhConvert *cv);
+/* host only: the integers the kernel uses for an RGB conversion of bit_depth-bit pictures, OH_CONV_NCOEFFS of them (n: room in out) */
+int    oh_convert_coeffs(const OhConvert *cv, int bit_depth, int32_t *out, int n);
+
 /* SHVC inter-layer reference picture: resample the finished base-layer picture src_pic into
  * the enhancement-layer picture dst_pic, bit-exact with the reference's whole-picture slot
  * HEVCDSPContext.upsample_base_layer_frame (hevcdsp_template.c:2164-2438, call site hevc.c:3241).

@@ -1169,6 +1169,169 @@ extern "C" int oh_pics_hash(OhEngine *e, const int *pic_ids, int n, int hash_typ
     return OH_OK;
 }
 
+/* ---------------- conversion to standard images (convert.hip) ---------------- */
+static int conv_sample_bytes(const OhConvert *cv, int bit_depth)
+{
+    switch (cv->sample) {
+    case OH_CONV_NATIVE: return bit_depth > 8 ? 2 : 1;
+    case OH_CONV_U8:     return 1;
+    case OH_CONV_F32:    return 4;
+    default:             return 2;
+    }
+}
+
+/* what oh_pics_convert checks of the combination itself (not of pictures or memory); *bytes: one image */
+static int conv_check(const OhPicParams *p, const OhConvert *cv, size_t *bytes, std::string *why)
+{
+    char buf[256];
+    if (!p || !cv) { *why = "no params or no OhConvert"; return OH_E_ARG; }
+    const int cf = p->chroma_format_idc, bd = p->bit_depth;
+    if (p->width <= 0 || p->height <= 0 || cf < 0 || cf > 3 || (bd != 8 && bd != 9 && bd != 10 && bd != 12)) {
+        *why = "bad picture params"; return OH_E_ARG;
+    }
+    if (cv->format < OH_CONV_PLANAR || cv->format > OH_CONV_RGBA || cv->sample < OH_CONV_NATIVE || cv->sample > OH_CONV_F32) {
+        snprintf(buf, sizeof(buf), "format %d / sample %d unknown", cv->format, cv->sample); *why = buf; return OH_E_UNSUPPORTED;
+    }
+    const bool yuv = cv->format <= OH_CONV_SEMIPLANAR;
+    if (yuv ? cv->sample > OH_CONV_U8 : cv->sample == OH_CONV_NATIVE) {
+        snprintf(buf, sizeof(buf), "sample %d does not fit format %d (YUV: NATIVE or U8; RGB: U8, U16, F16, F32)", cv->sample, cv->format);
+        *why = buf; return OH_E_UNSUPPORTED;
+    }
+    if (!yuv && cv->matrix != 1 && cv->matrix != 5 && cv->matrix != 6 && cv->matrix != 9) {
+        snprintf(buf, sizeof(buf), "matrix_coefficients %d (1 BT.709, 5 / 6 BT.601, 9 BT.2020 NCL)", cv->matrix); *why = buf; return OH_E_UNSUPPORTED;
+    }
+    if (cv->format == OH_CONV_SEMIPLANAR && cf == 0) { *why = "a 4:0:0 picture has no semi-planar form"; return OH_E_UNSUPPORTED; }
+    if ((cv->full_range != 0 && cv->full_range != 1) || (cv->chroma_filter != 0 && cv->chroma_filter != 1)) {
+        *why = "full_range and chroma_filter are 0 or 1"; return OH_E_ARG;
+    }
+    const OhWindow &w = cv->win;
+    const int sw = (cf == 1 || cf == 2) ? 2 : 1, sh = cf == 1 ? 2 : 1;
+    const int W = p->width - w.left - w.right, H = p->height - w.top - w.bottom;
+    if (w.left < 0 || w.right < 0 || w.top < 0 || w.bottom < 0 || W <= 0 || H <= 0 || w.left % sw || w.right % sw || w.top % sh || w.bottom % sh) {
+        snprintf(buf, sizeof(buf), "window (%d,%d,%d,%d) of %dx%d: empty, or offsets not multiples of %dx%d", w.left, w.right, w.top, w.bottom,
+                 p->width, p->height, sw, sh);
+        *why = buf; return OH_E_ARG;
+    }
+    size_t samples;
+    if (cv->format <= OH_CONV_SEMIPLANAR)
+        samples = (size_t)W * H + (cf ? 2 * (size_t)(W / sw) * (H / sh) : 0);
+    else
+        samples = (size_t)W * H * (cv->format == OH_CONV_RGBA ? 4 : 3);
+    *bytes = samples * (size_t)conv_sample_bytes(cv, bd);
+    return OH_OK;
+}
+
+extern "C" size_t oh_convert_image_bytes(const OhPicParams *p, const OhConvert *cv)
+{
+    size_t bytes = 0;
+    std::string why;
+    return conv_check(p, cv, &bytes, &why) == OH_OK ? bytes : 0;
+}
+
+/* the integers of an RGB conversion: R = clamp((cy (Y - yoff) + crv (Cr - mid) + 2^(S-1)) >> S, 0, 2^D - 1), G with cgu, cgv, B with
+ * cbu; each coefficient round(2^S (2^D - 1) entry / scale) of the H.273 inverse matrix, S the largest shift that keeps every term and
+ * every sum inside int32 for all samples of bit_depth bits */
+extern "C" int oh_convert_coeffs(const OhConvert *cv, int bit_depth, int32_t *out, int n)
+{
+    if (!cv || !out || n < OH_CONV_NCOEFFS || (bit_depth != 8 && bit_depth != 9 && bit_depth != 10 && bit_depth != 12))
+        return OH_E_ARG;
+    if (cv->format < OH_CONV_RGB_PLANAR || cv->format > OH_CONV_RGBA || cv->sample < OH_CONV_U8 || cv->sample > OH_CONV_F32)
+        return OH_E_UNSUPPORTED;
+    double kr, kb;
+    switch (cv->matrix) {
+    case 1:  kr = 0.2126; kb = 0.0722; break;
+    case 5:
+    case 6:  kr = 0.299;  kb = 0.114;  break;
+    case 9:  kr = 0.2627; kb = 0.0593; break;
+    default: return OH_E_UNSUPPORTED;
+    }
+    if (cv->full_range != 0 && cv->full_range != 1)
+        return OH_E_ARG;
+    const int B = bit_depth, D = cv->sample == OH_CONV_U8 ? 8 : 16;
+    const double kg = 1.0 - kr - kb, full = (double)((1 << B) - 1), unit = (double)(1 << (B - 8));
+    const double ys = cv->full_range ? full : 219.0 * unit, cs = cv->full_range ? full : 224.0 * unit;
+    const int yoff = cv->full_range ? 0 : 16 << (B - 8), mid = 1 << (B - 1);
+    const double ent[5] = { 1.0 / ys, 2.0 * (1.0 - kr) / cs, -2.0 * kb * (1.0 - kb) / (kg * cs), -2.0 * kr * (1.0 - kr) / (kg * cs),
+                            2.0 * (1.0 - kb) / cs };              /* cy, crv, cgu, cgv, cbu */
+    const int64_t dy = std::max(yoff, (1 << B) - 1 - yoff), dc = mid;   /* largest |Y - yoff|, |C - mid| */
+    const double scale = (double)((1 << D) - 1);
+    for (int S = 30; S >= 1; S--) {
+        int64_t c[5];
+        for (int i = 0; i < 5; i++) c[i] = llround(ldexp(scale * ent[i], S));
+        const int64_t r = (int64_t)1 << (S - 1), ty = std::llabs(c[0]) * dy;
+        const int64_t worst = std::max({ ty + std::llabs(c[1]) * dc + r, ty + (std::llabs(c[2]) + std::llabs(c[3])) * dc + r,
+                                         ty + std::llabs(c[4]) * dc + r });
+        if (worst > INT32_MAX)
+            continue;
+        for (int i = 0; i < 5; i++) out[i] = (int32_t)c[i];
+        out[5] = yoff; out[6] = mid; out[7] = S; out[8] = D;
+        return OH_OK;
+    }
+    return OH_E_UNSUPPORTED;
+}
+
+extern "C" int oh_pics_convert(OhEngine *e, const int *pic_ids, int n, const OhConvert *cv, void *dst, size_t image_stride, size_t dst_bytes)
+{
+    if (!e || n < 0 || !cv || (n && !pic_ids))
+        return OH_E_ARG;
+    if (!n)
+        return OH_OK;
+    { const int rc = check_pics(e, pic_ids, n, "oh_pics_convert"); if (rc) return rc; }
+    const Pic *p0 = get_pic(e, pic_ids[0]);
+    for (int i = 1; i < n; i++)
+        if (memcmp(&get_pic(e, pic_ids[i])->p, &p0->p, sizeof(OhPicParams)))
+            FAIL(e, OH_E_ARG, "oh_pics_convert: picture %d has other params than picture %d", pic_ids[i], pic_ids[0]);
+    size_t ib = 0;
+    std::string why;
+    { const int rc = conv_check(&p0->p, cv, &ib, &why); if (rc) FAIL(e, rc, "oh_pics_convert: %s", why.c_str()); }
+    const size_t ob = (size_t)conv_sample_bytes(cv, p0->p.bit_depth);
+    if (image_stride < ib || image_stride % ob || (uintptr_t)dst % ob)
+        FAIL(e, OH_E_ARG, "oh_pics_convert: image_stride %zu (an image takes %zu bytes) or dst not a multiple of the %zu-byte sample", image_stride, ib, ob);
+    if (!dst || ib > dst_bytes || (size_t)(n - 1) > (dst_bytes - ib) / image_stride)
+        FAIL(e, OH_E_ARG, "oh_pics_convert: %d images of %zu bytes, %zu apart, do not fit %zu bytes", n, ib, image_stride, dst_bytes);
+    const size_t total = (size_t)(n - 1) * image_stride + ib;
+    HIPCHK(e, hipSetDevice(e->device));
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, dst) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->device) {
+        (void)hipGetLastError();
+        FAIL(e, OH_E_ARG, "oh_pics_convert: dst is not device memory of device %d", e->device);
+    }
+    void *base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, dst) == hipSuccess) {
+        if ((char *)dst + total > (char *)base + size)
+            FAIL(e, OH_E_ARG, "oh_pics_convert: %zu bytes at dst run past the end of its allocation", total);
+    } else {
+        (void)hipGetLastError();
+    }
+    OhConvArgs a;
+    memset(&a, 0, sizeof(a));
+    const OhPicParams &p = p0->p;
+    const int bpp = p.bit_depth > 8 ? 2 : 1;
+    for (int c = 0; c < 3; c++) a.pitch[c] = p0->stride[c] * bpp;
+    a.cw = p0->w[1]; a.ch = p0->h[1];
+    a.left = cv->win.left; a.top = cv->win.top;
+    a.W = p.width - cv->win.left - cv->win.right; a.H = p.height - cv->win.top - cv->win.bottom;
+    a.cf = p.chroma_format_idc; a.bd = p.bit_depth; a.filter = cv->chroma_filter;
+    a.nc = cv->format == OH_CONV_RGBA ? 4 : 3;
+    a.image_stride = image_stride;
+    if (cv->format >= OH_CONV_RGB_PLANAR) {
+        const int rc = oh_convert_coeffs(cv, p.bit_depth, a.k, OH_CONV_NCOEFFS);
+        if (rc) FAIL(e, rc, "oh_pics_convert: no coefficients for this conversion");
+    }
+    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
+        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+        for (int i = 0; i < m; i++) {
+            const Pic *q = get_pic(e, pic_ids[i0 + i]);
+            for (int c = 0; c < 3; c++) a.src[i][c] = p.chroma_format_idc || !c ? (q->final_b ? q->b[c] : q->a[c]) : nullptr;
+        }
+        a.dst = (char *)dst + (size_t)i0 * image_stride;
+        ohk_convert(&a, cv->format, cv->sample, m, e->stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    return OH_OK;
+}
+
 extern "C" int oh_pic_device_planes(OhEngine *e, int pic_id, void *planes[3], int32_t stride[3], int32_t width[3], int32_t height[3])
 {
     if (!e)

@@ -24,9 +24,26 @@ struct OhMd5Job {
 };
 enum { OH_HASH_TASK = 128 << 10 };   /* packed plane bytes per CRC / checksum workgroup (hash.hip) */
 
+/* picture conversion (convert.hip): what one launch needs, passed by value in the kernel arguments (no job table in memory that a
+ * later call could overwrite before the launch runs).  Every picture of a launch has the same geometry; src: its finished planes. */
+struct OhConvArgs {
+    const void *src[64][3];      /* OH_CONV_MAX_PICS pictures x planes */
+    void       *dst;             /* image of the launch's first picture */
+    uint64_t    image_stride;    /* bytes from one image to the next */
+    int32_t     pitch[3];        /* bytes between rows of each plane */
+    int32_t     cw, ch;          /* coded chroma plane size (clamping of the linear filter) */
+    int32_t     left, top, W, H; /* window, luma samples */
+    int32_t     cf, bd;          /* chroma_format_idc, bit depth */
+    int32_t     filter;          /* 0 nearest, 1 linear */
+    int32_t     nc;              /* interleaved RGB: 3 or 4 channels */
+    int32_t     k[9];            /* oh_convert_coeffs: cy, crv, cgu, cgv, cbu, yoff, mid, S, D */
+};
+
 extern "C" {
 int  ohk_init(void);
 void ohk_md5(const OhMd5Job *jobs, int n, void *digests, hipStream_t st);
+/* format / sample: OH_CONV_* (checked by the caller); n pictures of a.src */
+void ohk_convert(const OhConvArgs *a, int format, int sample, int n, hipStream_t st);
 void ohk_hash(int kind, const OhMd5Job *jobs, const uint32_t *first, const uint32_t *task_map, int n_jobs, int n_tasks, uint32_t *partials,
               uint32_t *out, hipStream_t st);
 void ohk_inter(const OhBatch *B, int n, const OhPicParams *p, uint32_t max_luma, uint32_t max_chroma, hipStream_t st);

@@ -18,6 +18,7 @@
  *   BS      bs.hip        bs_kernel         optional: both boundary-strength grids from the motion field, one lane per 4x4 cell
  *   SHVC    upsample.hip  upsample_tile_kernel  one workgroup per tile (CTB), window and horizontal rows in LDS
  *   output  md5.hip       md5_kernel        one wave per (picture, plane) MD5 chain
+ *           convert.hip   convert_*_kernel  pictures -> YUV / RGB images: a workgroup per row segment, rows staged in LDS, 16-byte stores
  */
 #include "kernels_common.h"
 

@@ -5,6 +5,7 @@ There is no CPU fallback: creating an Engine without the built library or withou
 import ctypes as C
 import os
 import subprocess
+import sys
 
 import numpy as np
 
@@ -15,14 +16,58 @@ OH_N_PASSES = 6
 PASS_NAMES = ("inter", "residual", "intra", "deblock_v", "deblock_h", "sao")
 
 _lib = None
+_torch_first = False
 
 
 class EngineError(RuntimeError):
-    pass
+    code = None                                               # the OH_E_* code of the failed call, where one is known
 
 
 class OhWindow(C.Structure):                                  # include/ohevc_hip.h
     _fields_ = [("left", C.c_int32), ("right", C.c_int32), ("top", C.c_int32), ("bottom", C.c_int32)]
+
+
+OH_E_HIP, OH_E_ARG, OH_E_NOMEM, OH_E_UNSUPPORTED = -1, -2, -3, -4
+CONV_FORMATS = {"planar": 0, "semiplanar": 1, "rgb_planar": 2, "rgb": 3, "rgba": 4}      # OH_CONV_PLANAR .. OH_CONV_RGBA
+CONV_NATIVE, CONV_U8, CONV_U16, CONV_F16, CONV_F32 = range(5)                           # OH_CONV_NATIVE .. OH_CONV_F32
+CONV_MAX_PICS, CONV_NCOEFFS = 64, 9
+
+
+class OhConvert(C.Structure):                                 # include/ohevc_hip.h
+    _fields_ = [("format", C.c_int32), ("sample", C.c_int32), ("matrix", C.c_int32), ("full_range", C.c_int32),
+                ("chroma_filter", C.c_int32), ("win", OhWindow)]
+
+
+def conv_format(fmt):
+    """a format name of CONV_FORMATS or its OH_CONV_* number -> the number"""
+    if isinstance(fmt, str):
+        if fmt not in CONV_FORMATS:
+            raise ValueError(f"unknown format {fmt!r}: one of {sorted(CONV_FORMATS)}")
+        return CONV_FORMATS[fmt]
+    return int(fmt)
+
+
+def make_convert(fmt, sample, window=(0, 0, 0, 0), matrix=1, full_range=False, chroma="linear"):
+    """OhConvert for oh_pics_convert: window = (left, right, top, bottom) in luma samples, chroma "linear" or "nearest" """
+    if chroma not in ("linear", "nearest"):
+        raise ValueError(f"chroma must be 'linear' or 'nearest', not {chroma!r}")
+    return OhConvert(conv_format(fmt), int(sample), int(matrix), int(bool(full_range)), 1 if chroma == "linear" else 0, OhWindow(*window))
+
+
+def convert_image_bytes(params, cv):
+    """oh_convert_image_bytes (host only): bytes of one image, 0 when the combination is not valid"""
+    return int(lib().oh_convert_image_bytes(C.byref(params), C.byref(cv)))
+
+
+def convert_coeffs(cv, bit_depth):
+    """oh_convert_coeffs (host only): (cy, crv, cgu, cgv, cbu, yoff, mid, S, D), the integers of an RGB conversion"""
+    out = (C.c_int32 * CONV_NCOEFFS)()
+    rc = lib().oh_convert_coeffs(C.byref(cv), bit_depth, out, CONV_NCOEFFS)
+    if rc != 0:
+        err = EngineError(f"oh_convert_coeffs failed ({rc})")
+        err.code = rc
+        raise err
+    return tuple(out)
 
 
 def lib_path():
@@ -38,6 +83,10 @@ def lib():
     if _lib is None:
         if not os.path.exists(lib_path()):
             raise EngineError("libohevc_hip.so is not built (run __graft_entry__.build()); there is no CPU fallback")
+        global _torch_first
+        # torch's HIP libraries link the runtime as libamdhip64.so, this library as libamdhip64.so.7: loaded after this library, torch
+        # brings a second HIP runtime that sees no GPU.  Loaded before it, both share torch's (what Engine.pics_convert needs).
+        _torch_first = "torch" in sys.modules
         L = C.CDLL(lib_path())
         V, I = C.c_void_p, C.c_int
         PP = C.POINTER(C.c_void_p)
@@ -65,6 +114,10 @@ def lib():
         L.oh_upsample_blocks_defined.argtypes = [C.c_void_p, I, I, I, I, I, C.POINTER(I)]
         L.oh_pics_md5.argtypes = [V, C.POINTER(C.c_int), I, C.POINTER(C.c_uint8)]
         L.oh_pics_hash.argtypes = [V, C.POINTER(C.c_int), I, I, C.POINTER(OhPictureHash)]
+        L.oh_pics_convert.argtypes = [V, C.POINTER(C.c_int), I, C.POINTER(OhConvert), V, C.c_size_t, C.c_size_t]
+        L.oh_convert_image_bytes.argtypes = [C.POINTER(F.OhPicParams), C.POINTER(OhConvert)]
+        L.oh_convert_image_bytes.restype = C.c_size_t
+        L.oh_convert_coeffs.argtypes = [C.POINTER(OhConvert), I, C.POINTER(C.c_int32), I]
         L.oh_frame_upload.argtypes = [V, C.POINTER(F.OhFrame), PP]
         L.oh_frames_upload.argtypes = [V, C.POINTER(C.POINTER(F.OhFrame)), I, PP]
         L.oh_frame_execute.argtypes = [V, V]
@@ -114,15 +167,21 @@ class Engine:
         if rc != 0:
             raise EngineError(f"oh_engine_create(device={device}) failed with {rc}: no usable MI355X / HIP device")
         self.h = h
+        self.device = device
+        self._torch_stream = None
+        self._params = {}                                     # picture id -> its OhPicParams (the image shapes of pics_convert)
 
     def _chk(self, rc, what):
         if rc != 0:
-            raise EngineError(f"{what} failed ({rc}): {self.L.oh_engine_last_error(self.h).decode()}")
+            err = EngineError(f"{what} failed ({rc}): {self.L.oh_engine_last_error(self.h).decode()}")
+            err.code = rc
+            raise err
 
     def close(self):
         if getattr(self, "h", None):
             self.L.oh_engine_destroy(self.h)
             self.h = None
+            self._torch_stream = None
 
     def __del__(self):
         try:
@@ -137,12 +196,14 @@ class Engine:
     def pic_alloc(self, params):
         pid = C.c_int(-1)
         self._chk(self.L.oh_pic_alloc(self.h, C.byref(params), C.byref(pid)), "oh_pic_alloc")
+        self._params[pid.value] = F.OhPicParams.from_buffer_copy(params)
         return pid.value
 
     def pic_wrap(self, params, half0_ptr, half1_ptr, half_bytes):
         pid = C.c_int(-1)
         self._chk(self.L.oh_pic_wrap(self.h, C.byref(params), C.c_void_p(half0_ptr), C.c_void_p(half1_ptr), half_bytes,
                                      C.byref(pid)), "oh_pic_wrap")
+        self._params[pid.value] = F.OhPicParams.from_buffer_copy(params)
         return pid.value
 
     def pic_final_half(self, pid):
@@ -156,6 +217,7 @@ class Engine:
 
     def pic_free(self, pid):
         self._chk(self.L.oh_pic_free(self.h, pid), "oh_pic_free")
+        self._params.pop(pid, None)
 
     @staticmethod
     def _plane_args(hp):
@@ -236,6 +298,75 @@ class Engine:
         if hash_type == 0:
             return [(0, [bytes(out[i].md5[c]) for c in range(3)]) for i in range(n)]
         return [(hash_type, list(out[i].crc if hash_type == 1 else out[i].checksum)) for i in range(n)]
+
+    def pics_convert(self, pids, fmt, *, dtype=None, window=(0, 0, 0, 0), matrix=1, full_range=False, chroma="linear", out=None):
+        """finished pictures -> one torch tensor on the engine's device (oh_pics_convert): fmt "planar" / "semiplanar" (N, rows, W),
+        "rgb_planar" (N, 3, H, W), "rgb" / "rgba" (N, H, W, 3 | 4).  dtype: None (YUV: the stored samples, RGB: uint8), torch.uint8,
+        torch.uint16 (YUV: the stored samples of a picture above 8 bit; an 8-bit picture has no uint16 YUV form and raises),
+        torch.float16 or torch.float32.  window = (left, right, top, bottom), luma samples.  out: a preallocated contiguous tensor of
+        that shape, dtype and device.  Ordered with torch both ways: the engine stream waits for torch's current
+        stream before it writes, torch's current stream waits for the engine stream afterwards.  torch must have been imported before
+        the first Engine was created (one HIP runtime)."""
+        import torch
+        if not _torch_first:
+            raise EngineError("Engine.pics_convert: import torch before the first Engine is created (the engine must share torch's HIP "
+                              "runtime to write into its tensors)")
+        pids = list(pids)
+        n = len(pids)
+        fmt_i = conv_format(fmt)
+        yuv = fmt_i <= CONV_FORMATS["semiplanar"]
+        dev = torch.device("cuda", self.device)
+        if n == 0:
+            raise ValueError("pics_convert needs at least one picture (the image shape follows the pictures' params)")
+        params = self._pic_params(pids[0])
+        # YUV + uint16: the stored samples of a picture above 8 bit; an 8-bit picture has no uint16 YUV form (OH_E_UNSUPPORTED below)
+        yuv16 = CONV_NATIVE if params.bit_depth > 8 else CONV_U16
+        samples = {None: CONV_NATIVE if yuv else CONV_U8, torch.uint8: CONV_U8, torch.uint16: yuv16 if yuv else CONV_U16,
+                   torch.float16: CONV_F16, torch.float32: CONV_F32}
+        if dtype not in samples:
+            raise ValueError(f"dtype {dtype}: one of uint8, uint16, float16, float32")
+        sample = samples[dtype]
+        cv = make_convert(fmt_i, sample, window, matrix, full_range, chroma)
+        ib = convert_image_bytes(params, cv)
+        if ib == 0:                                           # not a valid combination: the C call says why (and with which code)
+            self._chk(self.L.oh_pics_convert(self.h, (C.c_int * n)(*pids), n, C.byref(cv), None, 0, 0), "oh_pics_convert")
+            raise EngineError("oh_pics_convert: invalid conversion")
+        left, right, top, bottom = window
+        W, H = params.width - left - right, params.height - top - bottom
+        tdt = {CONV_U8: torch.uint8, CONV_U16: torch.uint16, CONV_F16: torch.float16, CONV_F32: torch.float32,
+               CONV_NATIVE: torch.uint8 if params.bit_depth == 8 else torch.uint16}[sample]
+        esz = torch.empty((), dtype=tdt).element_size()
+        if yuv:
+            shape = (n, ib // esz // W, W)
+        elif fmt_i == CONV_FORMATS["rgb_planar"]:
+            shape = (n, 3, H, W)
+        else:
+            shape = (n, H, W, 4 if fmt_i == CONV_FORMATS["rgba"] else 3)
+        if out is None:
+            out = torch.empty(shape, dtype=tdt, device=dev)
+        elif tuple(out.shape) != shape or out.dtype != tdt or out.device != dev or not out.is_contiguous():
+            raise ValueError(f"out: want a contiguous {tdt} tensor of shape {shape} on {dev}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        cur = torch.cuda.current_stream(dev)
+        same = (self.stream() or 0) == cur.cuda_stream        # an engine created on torch's current stream: nothing to order
+        if not same:
+            if self._torch_stream is None:
+                self._torch_stream = torch.cuda.ExternalStream(self.stream() or 0, device=dev)
+            es = self._torch_stream
+            es.wait_stream(cur)                               # the allocator may hand out memory a queued kernel still uses
+        self._chk(self.L.oh_pics_convert(self.h, (C.c_int * n)(*pids), n, C.byref(cv), C.c_void_p(out.data_ptr()), ib,
+                                         out.numel() * esz), "oh_pics_convert")
+        if not same:
+            # torch's stream waits for the write, so whatever torch does with the memory later (a free and a reuse included) is ordered
+            # behind it.  No record_stream on the engine stream: the image usually outlives the engine, and the allocator would record
+            # an event on the destroyed stream when the tensor is freed.
+            cur.wait_stream(es)
+        return out
+
+    def _pic_params(self, pid):
+        p = self._params.get(pid)
+        if p is None:
+            raise EngineError(f"picture {pid} was not allocated through this Engine object")
+        return p
 
     def pic_device_planes(self, pid):
         p = (C.c_void_p * 3)()
