@@ -145,6 +145,37 @@ size_t oh_convert_image_bytes(const OhPicParams *p, const OhConvert *cv);
 /* host only: the integers the kernel uses for an RGB conversion of bit_depth-bit pictures, OH_CONV_NCOEFFS of them (n: room in out) */
 int    oh_convert_coeffs(const OhConvert *cv, int bit_depth, int32_t *out, int n);
 
+/* Resizing of finished pictures into engine pictures (DESIGN.md §3c has the exact definition, which the tests check bit for bit
+ * against tests/resize_model.py): every plane is resampled on its own in integer arithmetic, separably, horizontal pass first, with
+ * an anti-aliased triangle (BILINEAR) or Keys cubic a = -1/2 (BICUBIC) filter whose taps are re-normalised at the window's edges.
+ * The chroma planes of 4:2:0 and 4:2:2 are co-sited with the even luma column (chroma_sample_loc_type 0), centred vertically. */
+enum { OH_RESIZE_BILINEAR = 0, OH_RESIZE_BICUBIC };
+enum { OH_RESIZE_MAX_PICS = 64,   /* pictures per launch set (fewer when the intermediate of 64 would pass 512 MiB); a call with more is split */
+       OH_RESIZE_MAX_DOWN = 128,  /* largest source : destination ratio per axis */
+       OH_RESIZE_MAX_UP = 16 };   /* largest destination : source ratio per axis */
+typedef struct OhResize {
+    int32_t  filter;              /* OH_RESIZE_BILINEAR, OH_RESIZE_BICUBIC */
+    OhWindow win;                 /* source window, luma samples, rules as for oh_pics_convert */
+    int32_t  width, height;       /* size of the resized image, luma samples, inside the destination pictures */
+} OhResize;
+/* n finished source pictures (identical params) -> n destination pictures (identical params, same bit depth and chroma format as the
+ * sources).  The image takes the top-left width x height of each destination; the rest of its coded planes replicates the image's
+ * last column and last row.  Reads each source's finished half, writes half 0 of each destination and marks it finished; enqueued on
+ * the engine stream behind the work that finished the sources, returns without waiting.  n == 0: OH_OK.
+ * OH_E_ARG, nothing written: unknown pictures; sources (or destinations) whose params differ among themselves; a picture that is both
+ * source and destination, or a destination listed twice; an empty window or one whose offsets are not multiples of SubWidthC /
+ * SubHeightC; width / height below 1, above the destination's coded size or not multiples of SubWidthC / SubHeightC; an unknown filter.
+ * OH_E_UNSUPPORTED: destinations whose bit depth or chroma format differs from the sources'; a plane whose window extent is more
+ * than OH_RESIZE_MAX_DOWN times, or less than 1 / OH_RESIZE_MAX_UP of, its image extent on either axis. */
+int oh_pics_resize(OhEngine *e, const int *src_ids, const int *dst_ids, int n, const OhResize *rs);
+/* host only: the integers the kernels receive for one axis.  phase: 2 (samples centred in their cells) or 1 (co-sited chroma columns).
+ * Output sample x uses n_taps[x] source samples from first[x] (an index inside the window) with coeffs[x * max_taps + 0 .. n_taps[x])
+ * (the rest of the row is zero), which sum to 1 << 14.  OH_E_ARG: extents below 1 or above 16384, an unknown filter or phase, max_taps
+ * below oh_resize_max_taps.  OH_E_UNSUPPORTED: some output's absolute coefficients sum to 1 << 15 or more (no such geometry is known). */
+int oh_resize_taps(int src_extent, int dst_extent, int filter, int phase, int32_t *first, int16_t *coeffs, int max_taps, int *n_taps);
+/* host only: the largest number of taps of an output sample of that axis (OH_E_ARG as above) */
+int oh_resize_max_taps(int src_extent, int dst_extent, int filter);
+
 /* SHVC inter-layer reference picture: resample the finished base-layer picture src_pic into
  * the enhancement-layer picture dst_pic, bit-exact with the reference's whole-picture slot
  * HEVCDSPContext.upsample_base_layer_frame (hevcdsp_template.c:2164-2438, call site hevc.c:3241).

@@ -190,6 +190,8 @@ struct OhEngine {
     uint32_t   *kerr = nullptr;
     void       *hash_dev = nullptr;      /* oh_pics_hash (CRC / checksum): the job table, its tasks and their values in HBM */
     size_t      hash_dev_bytes = 0;
+    void       *resize_dev = nullptr;    /* oh_pics_resize: the tap tables of the call, then the int16 intermediate of one launch set */
+    size_t      resize_dev_bytes = 0;
     uint32_t    spin_limit = 1u << 22;   /* polls (with s_sleep between them, ~1 s in all) before a waiting workgroup gives up; OHEVC_SPIN_LIMIT */
 };
 
@@ -437,6 +439,7 @@ extern "C" void oh_engine_destroy(OhEngine *e)
     if (e->kerr) (void)hipHostFree(e->kerr);
     if (e->tickets) (void)hipFree(e->tickets);
     if (e->hash_dev) (void)hipFree(e->hash_dev);
+    if (e->resize_dev) (void)hipFree(e->resize_dev);
     for (auto &ev : e->batch_ev) if (ev) (void)hipEventDestroy(ev);
     if (e->dl_stream) { (void)hipStreamSynchronize(e->dl_stream); (void)hipStreamDestroy(e->dl_stream); }
     if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);
@@ -1327,6 +1330,253 @@ extern "C" int oh_pics_convert(OhEngine *e, const int *pic_ids, int n, const OhC
         }
         a.dst = (char *)dst + (size_t)i0 * image_stride;
         ohk_convert(&a, cv->format, cv->sample, m, e->stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    return OH_OK;
+}
+
+/* ---------------- resizing into engine pictures (resize.hip) ---------------- */
+typedef __int128 i128;
+static i128 floor_div(i128 a, i128 b) { const i128 q = a / b; return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q; }   /* b > 0 */
+
+static bool resize_axis_ok(int S, int T, int filter, int phase)
+{
+    return S >= 1 && T >= 1 && S <= 16384 && T <= 16384 && (filter == OH_RESIZE_BILINEAR || filter == OH_RESIZE_BICUBIC) && (phase == 1 || phase == 2);
+}
+
+extern "C" int oh_resize_max_taps(int src_extent, int dst_extent, int filter)
+{
+    if (!resize_axis_ok(src_extent, dst_extent, filter, 2))
+        return OH_E_ARG;
+    const int64_t S = src_extent, T = dst_extent, D = 4 * std::max(S, T), R = filter == OH_RESIZE_BICUBIC ? 2 : 1;
+    return (int)std::min<int64_t>(S, (2 * R * D - 2) / (4 * T) + 1);          /* source samples strictly inside a span of 2RD */
+}
+
+/* the taps of one axis, all positions in units of 1/(4T) source samples */
+extern "C" int oh_resize_taps(int src_extent, int dst_extent, int filter, int phase, int32_t *first, int16_t *coeffs, int max_taps, int *n_taps)
+{
+    if (!first || !coeffs || !n_taps || !resize_axis_ok(src_extent, dst_extent, filter, phase) ||
+        max_taps < oh_resize_max_taps(src_extent, dst_extent, filter))
+        return OH_E_ARG;
+    const int64_t S = src_extent, T = dst_extent, p = phase, D = 4 * std::max(S, T), R = filter == OH_RESIZE_BICUBIC ? 2 : 1;
+    std::vector<i128> w;
+    std::vector<int64_t> k;
+    for (int64_t x = 0; x < T; x++) {
+        const int64_t c = (4 * x + p) * S;
+        int64_t lo = -(int64_t)floor_div(-(c - R * D - p * T + 1), 4 * T), hi = (int64_t)floor_div(c + R * D - p * T - 1, 4 * T);
+        lo = std::max<int64_t>(lo, 0); hi = std::min(hi, S - 1);
+        const int n = (int)(hi - lo + 1);
+        if (n < 1 || n > max_taps)
+            return OH_E_ARG;
+        w.assign((size_t)n, 0); k.assign((size_t)n, 0);
+        i128 sum = 0;
+        for (int j = 0; j < n; j++) {
+            const i128 v = std::llabs((4 * (lo + j) + p) * T - c), d = D;
+            w[j] = R == 1 ? d - v : v <= d ? 3 * v * v * v - 5 * v * v * d + 2 * d * d * d : -(v * v * v - 5 * v * v * d + 8 * v * d * d - 4 * d * d * d);
+            sum += w[j];
+        }
+        if (sum <= 0)
+            return OH_E_UNSUPPORTED;
+        int64_t ks = 0, ka = 0;
+        int best = 0;
+        for (int j = 0; j < n; j++) {
+            k[j] = (int64_t)floor_div(2 * w[j] * (1 << 14) + sum, 2 * sum);
+            ks += k[j];
+            if (k[j] > k[best]) best = j;
+        }
+        k[best] += (1 << 14) - ks;
+        for (int j = 0; j < n; j++) ka += std::llabs(k[j]);
+        if (ka >= 1 << 15)
+            return OH_E_UNSUPPORTED;
+        first[x] = (int32_t)lo; n_taps[x] = n;
+        int16_t *row = coeffs + (size_t)x * max_taps;
+        for (int j = 0; j < max_taps; j++) row[j] = j < n ? (int16_t)k[j] : 0;
+    }
+    return OH_OK;
+}
+
+namespace {
+struct ResizeAxis { std::vector<int32_t> first, cnt; std::vector<int16_t> k; int mt = 0; };
+}
+
+static int resize_axis(int S, int T, int filter, int phase, ResizeAxis *ax)
+{
+    ax->mt = oh_resize_max_taps(S, T, filter);
+    if (ax->mt < 1) return OH_E_ARG;
+    ax->first.resize((size_t)T); ax->cnt.resize((size_t)T); ax->k.resize((size_t)T * ax->mt);
+    return oh_resize_taps(S, T, filter, phase, ax->first.data(), ax->k.data(), ax->mt, ax->cnt.data());
+}
+
+extern "C" int oh_pics_resize(OhEngine *e, const int *src_ids, const int *dst_ids, int n, const OhResize *rs)
+{
+    if (!e || n < 0 || !rs || (n && (!src_ids || !dst_ids)))
+        return OH_E_ARG;
+    if (!n)
+        return OH_OK;
+    { const int rc = check_pics(e, src_ids, n, "oh_pics_resize"); if (rc) return rc; }
+    { const int rc = check_pics(e, dst_ids, n, "oh_pics_resize"); if (rc) return rc; }
+    const Pic *s0 = get_pic(e, src_ids[0]), *d0 = get_pic(e, dst_ids[0]);
+    for (int i = 1; i < n; i++)
+        if (memcmp(&get_pic(e, src_ids[i])->p, &s0->p, sizeof(OhPicParams)) || memcmp(&get_pic(e, dst_ids[i])->p, &d0->p, sizeof(OhPicParams)))
+            FAIL(e, OH_E_ARG, "oh_pics_resize: pictures %d -> %d have other params than pictures %d -> %d", src_ids[i], dst_ids[i], src_ids[0], dst_ids[0]);
+    {
+        std::vector<int> d(dst_ids, dst_ids + n), s(src_ids, src_ids + n);
+        std::sort(d.begin(), d.end()); std::sort(s.begin(), s.end());
+        if (std::adjacent_find(d.begin(), d.end()) != d.end())
+            FAIL(e, OH_E_ARG, "oh_pics_resize: a destination is listed twice");
+        for (int i = 0; i < n; i++)
+            if (std::binary_search(s.begin(), s.end(), d[i]))
+                FAIL(e, OH_E_ARG, "oh_pics_resize: picture %d is both source and destination", d[i]);
+    }
+    const OhPicParams &sp = s0->p, &dp = d0->p;
+    if (rs->filter != OH_RESIZE_BILINEAR && rs->filter != OH_RESIZE_BICUBIC)
+        FAIL(e, OH_E_ARG, "oh_pics_resize: filter %d (0 bilinear, 1 bicubic)", rs->filter);
+    const int cf = sp.chroma_format_idc, hs = cf == 1 || cf == 2, vs = cf == 1, sw = 1 << hs, sv = 1 << vs;
+    const OhWindow &w = rs->win;
+    const int W = sp.width - w.left - w.right, H = sp.height - w.top - w.bottom;
+    if (w.left < 0 || w.right < 0 || w.top < 0 || w.bottom < 0 || W <= 0 || H <= 0 || w.left % sw || w.right % sw || w.top % sv || w.bottom % sv)
+        FAIL(e, OH_E_ARG, "oh_pics_resize: window (%d,%d,%d,%d) of %dx%d: empty, or offsets not multiples of %dx%d", w.left, w.right, w.top, w.bottom,
+             sp.width, sp.height, sw, sv);
+    /* the size rules read the SOURCES' chroma format: a destination of another format is refused below */
+    if (rs->width < 1 || rs->height < 1 || rs->width > dp.width || rs->height > dp.height || rs->width % sw || rs->height % sv)
+        FAIL(e, OH_E_ARG, "oh_pics_resize: image %dx%d: below 1, above the destination's %dx%d, or not multiples of %dx%d", rs->width, rs->height,
+             dp.width, dp.height, sw, sv);
+    if (dp.bit_depth != sp.bit_depth || dp.chroma_format_idc != cf)
+        FAIL(e, OH_E_UNSUPPORTED, "oh_pics_resize: destinations of %d bit, chroma format %d; sources of %d bit, chroma format %d", dp.bit_depth,
+             dp.chroma_format_idc, sp.bit_depth, cf);
+    const int ncls = cf ? 2 : 1, bpp = sp.bit_depth > 8 ? 2 : 1;
+    for (int c = 0; c < ncls; c++) {
+        const int64_t ext[4] = { W >> (c ? hs : 0), rs->width >> (c ? hs : 0), H >> (c ? vs : 0), rs->height >> (c ? vs : 0) };
+        for (int a = 0; a < 4; a += 2)
+            if (ext[a] > OH_RESIZE_MAX_DOWN * ext[a + 1] || ext[a + 1] > OH_RESIZE_MAX_UP * ext[a])
+                FAIL(e, OH_E_UNSUPPORTED, "oh_pics_resize: %d -> %d samples is outside %d:1 .. 1:%d", (int)ext[a], (int)ext[a + 1], OH_RESIZE_MAX_DOWN,
+                     OH_RESIZE_MAX_UP);
+    }
+
+    OhResizeArgs a;
+    memset(&a, 0, sizeof(a));
+    a.np = cf ? 3 : 1; a.bd = sp.bit_depth;
+    ResizeAxis hx[2], vx[2];
+    size_t off[2][9], tab = 0;                                  /* h_first, h_cnt, h_k, v_first, v_cnt, v_off, v_k, h_f4, h_n4 in the table blob */
+    std::vector<int32_t> h_f4[2], h_n4[2];
+    std::vector<int32_t> v_lo[2], v_np[2], v_off[2];
+    uint64_t mid_pic = 0;
+    for (int c = 0; c < ncls; c++) {
+        OhResizeClass &k = a.k[c];
+        const int Sw = W >> (c ? hs : 0), Sh = H >> (c ? vs : 0);
+        k.x0 = w.left >> (c ? hs : 0); k.y0 = w.top >> (c ? vs : 0); k.sh = Sh;
+        k.tw = rs->width >> (c ? hs : 0); k.th = rs->height >> (c ? vs : 0);
+        k.cw = d0->w[c]; k.ch = d0->h[c];
+        k.src_pitch = s0->stride[c] * bpp; k.dst_pitch = d0->stride[c] * bpp;
+        k.mid_stride = (int32_t)align_up((size_t)k.tw + 1, 64);
+        int rc = resize_axis(Sw, k.tw, rs->filter, c && hs ? 1 : 2, &hx[c]);
+        if (!rc) rc = resize_axis(Sh, k.th, rs->filter, 2, &vx[c]);
+        if (rc) FAIL(e, rc, "oh_pics_resize: no taps for %dx%d -> %dx%d", Sw, Sh, k.tw, k.th);
+        /* horizontal pass: the widest power-of-two segment whose source columns fit a staged row, then as many rows as fit the LDS */
+        int span = 0;
+        for (k.segw = 256; ; k.segw >>= 1) {
+            span = 0;
+            for (int x = 0; x < k.tw; x += k.segw) {
+                const int xl = std::min(x + k.segw, k.tw) - 1;
+                span = std::max(span, hx[c].first[xl] + hx[c].cnt[xl] - hx[c].first[x]);
+            }
+            if (span <= OH_RESIZE_SPAN || k.segw == 1) break;
+        }
+        if (span > OH_RESIZE_SPAN)
+            FAIL(e, OH_E_UNSUPPORTED, "oh_pics_resize: one image column reads %d source columns (at most %d)", span, OH_RESIZE_SPAN);
+        k.row_bytes = (int32_t)align_up((size_t)span * bpp, 16) + 32;
+        k.rpw = std::max(1, std::min({ (int)OH_RESIZE_HROWS, OH_RESIZE_LDS / k.row_bytes, Sh }));
+        k.h_stride = (int32_t)align_up((size_t)k.tw, 32);
+        /* the taps of a column as QUADS of source columns that start at a multiple of four columns of the plane (an 8- or 4-byte
+         * aligned LDS read): zero coefficients in front of the first tap and behind the last */
+        int quads = 0;
+        for (int x = 0; x < k.tw; x++) {
+            const int lead = (k.x0 + hx[c].first[x]) & 3;
+            h_f4[c].push_back(hx[c].first[x] - lead);
+            h_n4[c].push_back((lead + hx[c].cnt[x] + 3) / 4);
+            quads = std::max(quads, h_n4[c].back());
+        }
+        k.h_groups = (Sh + k.rpw - 1) / k.rpw;
+        /* vertical pass: per group of image rows the intermediate rows it reads, in pairs */
+        k.v_groups = (k.th + OH_RESIZE_VROWS - 1) / OH_RESIZE_VROWS;
+        int32_t pairs = 0;
+        for (int g = 0; g < k.v_groups; g++) {
+            const int y0 = g * OH_RESIZE_VROWS, y1 = std::min(y0 + OH_RESIZE_VROWS, k.th) - 1;
+            const int lo = vx[c].first[y0], np = (vx[c].first[y1] + vx[c].cnt[y1] - lo + 1) / 2;
+            v_lo[c].push_back(lo); v_np[c].push_back(np); v_off[c].push_back(pairs);
+            pairs += np;
+        }
+        const size_t sz[9] = { (size_t)k.tw * 4, (size_t)k.tw * 4, (size_t)quads * k.h_stride * 8, (size_t)k.v_groups * 4, (size_t)k.v_groups * 4,
+                               (size_t)k.v_groups * 4, (size_t)pairs * OH_RESIZE_VROWS * 4, (size_t)k.tw * 4, (size_t)k.tw * 4 };
+        for (int i = 0; i < 9; i++) { off[c][i] = tab; tab += align_up(sz[i], 256); }
+        for (int pl = c ? 1 : 0; pl < (c ? 3 : 1); pl++) {
+            a.mid_plane[pl] = mid_pic;
+            mid_pic += align_up((size_t)(Sh + 1) * k.mid_stride, 128);     /* a spare row: the odd half of a group's last pair */
+        }
+    }
+    a.mid_pic = mid_pic;
+    const size_t mid_bytes = (size_t)mid_pic * 2;
+    const int per_set = (int)std::max<size_t>(1, std::min<size_t>(OH_RESIZE_MAX_PICS, ((size_t)512 << 20) / mid_bytes));
+    const size_t need = tab + (size_t)std::min(n, per_set) * mid_bytes;
+    HIPCHK(e, hipSetDevice(e->device));
+    if (need > e->resize_dev_bytes) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));              /* launches of earlier calls still use the old buffer */
+        if (e->resize_dev) (void)hipFree(e->resize_dev);
+        e->resize_dev = nullptr; e->resize_dev_bytes = 0;
+        const size_t want = align_up(need, (size_t)1 << 20);
+        HIPCHK(e, hipMalloc(&e->resize_dev, want));
+        e->resize_dev_bytes = want;
+    }
+    /* the tables: built in a pinned buffer of the pool, copied on the engine stream — behind the launches of an earlier call that
+     * read the device copy, in front of this call's */
+    OhEngine::Stage *sg = stage_acquire(e, tab);
+    if (!sg)
+        FAIL(e, OH_E_NOMEM, "oh_pics_resize: no staging buffer for %zu bytes of tap tables", tab);
+    char *h = (char *)sg->p, *d = (char *)e->resize_dev;
+    memset(h, 0, tab);
+    for (int c = 0; c < ncls; c++) {
+        OhResizeClass &k = a.k[c];
+        memcpy(h + off[c][0], hx[c].first.data(), (size_t)k.tw * 4);
+        memcpy(h + off[c][1], hx[c].cnt.data(), (size_t)k.tw * 4);
+        memcpy(h + off[c][7], h_f4[c].data(), (size_t)k.tw * 4);
+        memcpy(h + off[c][8], h_n4[c].data(), (size_t)k.tw * 4);
+        int16_t *hk = (int16_t *)(h + off[c][2]);                /* [quad][column][4] */
+        for (int x = 0; x < k.tw; x++) {
+            const int lead = hx[c].first[x] - h_f4[c][x];
+            for (int j = 0; j < hx[c].cnt[x]; j++)
+                hk[((size_t)((lead + j) / 4) * k.h_stride + x) * 4 + (lead + j) % 4] = hx[c].k[(size_t)x * hx[c].mt + j];
+        }
+        memcpy(h + off[c][3], v_lo[c].data(), (size_t)k.v_groups * 4);
+        memcpy(h + off[c][4], v_np[c].data(), (size_t)k.v_groups * 4);
+        memcpy(h + off[c][5], v_off[c].data(), (size_t)k.v_groups * 4);
+        int16_t *vk = (int16_t *)(h + off[c][6]);                /* [pair][image row of the group][even row, odd row] */
+        for (int y = 0; y < k.th; y++) {
+            const int g = y / OH_RESIZE_VROWS, i = y % OH_RESIZE_VROWS;
+            for (int j = 0; j < vx[c].cnt[y]; j++) {
+                const int r = vx[c].first[y] + j - v_lo[c][g];
+                vk[(((size_t)v_off[c][g] + r / 2) * OH_RESIZE_VROWS + i) * 2 + (r & 1)] = vx[c].k[(size_t)y * vx[c].mt + j];
+            }
+        }
+        k.h_first = (const int32_t *)(d + off[c][0]); k.h_cnt = (const int32_t *)(d + off[c][1]); k.h_k = (const int16_t *)(d + off[c][2]);
+        k.h_f4 = (const int32_t *)(d + off[c][7]); k.h_n4 = (const int32_t *)(d + off[c][8]);
+        k.v_first = (const int32_t *)(d + off[c][3]); k.v_cnt = (const int32_t *)(d + off[c][4]); k.v_off = (const int32_t *)(d + off[c][5]);
+        k.v_k = (const int32_t *)(d + off[c][6]);
+    }
+    HIPCHK(e, hipMemcpyAsync(d, h, tab, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipEventRecord(sg->done, e->stream));
+    sg->busy = true;
+    a.mid = (int16_t *)(d + tab);
+    const int pad = rs->width < dp.width || rs->height < dp.height;
+    for (int i0 = 0; i0 < n; i0 += per_set) {
+        const int m = std::min(n - i0, per_set);
+        for (int i = 0; i < m; i++) {
+            const Pic *s = get_pic(e, src_ids[i0 + i]);
+            Pic *q = get_pic(e, dst_ids[i0 + i]);
+            for (int c = 0; c < a.np; c++) { a.src[i][c] = s->final_b ? s->b[c] : s->a[c]; a.dst[i][c] = q->a[c]; }
+            q->final_b = false;                                  /* the image is a finished picture in half 0 */
+            q->done_seq = 0;
+        }
+        ohk_resize(&a, m, pad, e->stream);
         HIPCHK(e, hipGetLastError());
     }
     return OH_OK;

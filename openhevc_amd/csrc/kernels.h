@@ -39,8 +39,44 @@ struct OhConvArgs {
     int32_t     k[9];            /* oh_convert_coeffs: cy, crv, cgu, cgv, cbu, yoff, mid, S, D */
 };
 
+/* picture resizing (resize.hip): what one launch set needs, by value in the kernel arguments like OhConvArgs.  Two plane
+ * classes (0 luma, 1 chroma), each with its own geometry and tap tables; the tables live in device memory that the engine owns and
+ * fills on the stream in front of the launches. */
+enum { OH_RESIZE_VROWS = 8,          /* image rows per workgroup of the vertical pass */
+       OH_RESIZE_LDS = 32 << 10,     /* bytes of staged source rows per workgroup of the horizontal pass */
+       OH_RESIZE_SPAN = 4096,        /* most source samples of one staged row */
+       OH_RESIZE_HROWS = 16 };       /* most source rows per workgroup of the horizontal pass */
+struct OhResizeClass {
+    int32_t  x0, y0;                 /* window origin in the plane */
+    int32_t  sh;                     /* window rows */
+    int32_t  tw, th;                 /* image size in the plane */
+    int32_t  cw, ch;                 /* coded size of the destination plane */
+    int32_t  src_pitch, dst_pitch;   /* bytes between rows */
+    int32_t  mid_stride;             /* int16 between rows of the intermediate (even) */
+    int32_t  segw, rpw, row_bytes;   /* horizontal pass: image columns and source rows per workgroup, LDS bytes per staged row */
+    int32_t  h_stride;               /* columns between the quad rows of h_k */
+    int32_t  h_groups, v_groups;     /* workgroup rows of the two passes for one plane of this class */
+    const int32_t *h_first, *h_cnt;  /* per image column: first source column inside the window, taps */
+    const int32_t *h_f4, *h_n4;      /* the same as quads of source columns: h_first moved down to a multiple of four plane columns, quads */
+    const int16_t *h_k;              /* [quad][h_stride][4]: coefficients of each image column, zero in front of its first and behind its last tap */
+    const int32_t *v_first, *v_cnt, *v_off;  /* per group of OH_RESIZE_VROWS image rows: first intermediate row, row PAIRS, offset into v_k */
+    const int32_t *v_k;              /* [pair][OH_RESIZE_VROWS]: (coefficient of the even row, of the odd row) of each image row, zero where a row has no tap */
+};
+struct OhResizeArgs {
+    const void *src[64][3];          /* OH_RESIZE_MAX_PICS pictures x planes: the finished half */
+    void       *dst[64][3];          /* the half the image is written to */
+    int16_t    *mid;                 /* intermediate of the launch set's first picture */
+    uint64_t    mid_pic;             /* int16 from one picture's intermediate to the next */
+    uint64_t    mid_plane[3];        /* int16 from there to each plane's */
+    OhResizeClass k[2];
+    int32_t     np;                  /* planes: 1 or 3 */
+    int32_t     bd;
+};
+
 extern "C" {
 int  ohk_init(void);
+/* n pictures of a: horizontal pass into a.mid, vertical pass into the destinations, then the replicated padding where pad is set */
+void ohk_resize(const OhResizeArgs *a, int n, int pad, hipStream_t st);
 void ohk_md5(const OhMd5Job *jobs, int n, void *digests, hipStream_t st);
 /* format / sample: OH_CONV_* (checked by the caller); n pictures of a.src */
 void ohk_convert(const OhConvArgs *a, int format, int sample, int n, hipStream_t st);

@@ -19,6 +19,7 @@
  *   SHVC    upsample.hip  upsample_tile_kernel  one workgroup per tile (CTB), window and horizontal rows in LDS
  *   output  md5.hip       md5_kernel        one wave per (picture, plane) MD5 chain
  *           convert.hip   convert_*_kernel  pictures -> YUV / RGB images: a workgroup per row segment, rows staged in LDS, 16-byte stores
+ *           resize.hip    resize_*_kernel   pictures -> resized pictures: horizontal pass out of LDS into an int16 intermediate, vertical pass, v_dot2 in both
  */
 #include "kernels_common.h"
 

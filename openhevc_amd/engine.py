@@ -54,6 +54,43 @@ def make_convert(fmt, sample, window=(0, 0, 0, 0), matrix=1, full_range=False, c
     return OhConvert(conv_format(fmt), int(sample), int(matrix), int(bool(full_range)), 1 if chroma == "linear" else 0, OhWindow(*window))
 
 
+class OhResize(C.Structure):                                  # include/ohevc_hip.h
+    _fields_ = [("filter", C.c_int32), ("win", OhWindow), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+RESIZE_FILTERS = {"bilinear": 0, "bicubic": 1}                                          # OH_RESIZE_BILINEAR, OH_RESIZE_BICUBIC
+RESIZE_MAX_PICS, RESIZE_MAX_DOWN, RESIZE_MAX_UP = 64, 128, 16
+
+
+def resize_filter(filt):
+    """a filter name of RESIZE_FILTERS or its OH_RESIZE_* number -> the number"""
+    if isinstance(filt, str):
+        if filt not in RESIZE_FILTERS:
+            raise ValueError(f"unknown filter {filt!r}: one of {sorted(RESIZE_FILTERS)}")
+        return RESIZE_FILTERS[filt]
+    return int(filt)
+
+
+def resize_taps(src_extent, dst_extent, filter="bilinear", phase=2):
+    """oh_resize_taps (host only): per sample of the resized axis (first source index inside the window, [integer coefficients]),
+    the integers the kernels receive; phase 2: centred samples, 1: the co-sited chroma columns of 4:2:0 / 4:2:2"""
+    f = resize_filter(filter)
+    mt = lib().oh_resize_max_taps(src_extent, dst_extent, f)
+    if mt < 1:
+        err = EngineError(f"oh_resize_max_taps({src_extent}, {dst_extent}, {f}) failed ({mt})")
+        err.code = mt
+        raise err
+    n = max(dst_extent, 1)
+    first, cnt, k = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, mt), np.int16)
+    rc = lib().oh_resize_taps(src_extent, dst_extent, f, phase, first.ctypes.data_as(C.POINTER(C.c_int32)),
+                              k.ctypes.data_as(C.POINTER(C.c_int16)), mt, cnt.ctypes.data_as(C.POINTER(C.c_int)))
+    if rc != 0:
+        err = EngineError(f"oh_resize_taps failed ({rc})")
+        err.code = rc
+        raise err
+    return [(int(first[x]), [int(v) for v in k[x, :cnt[x]]]) for x in range(dst_extent)]
+
+
 def convert_image_bytes(params, cv):
     """oh_convert_image_bytes (host only): bytes of one image, 0 when the combination is not valid"""
     return int(lib().oh_convert_image_bytes(C.byref(params), C.byref(cv)))
@@ -118,6 +155,9 @@ def lib():
         L.oh_convert_image_bytes.argtypes = [C.POINTER(F.OhPicParams), C.POINTER(OhConvert)]
         L.oh_convert_image_bytes.restype = C.c_size_t
         L.oh_convert_coeffs.argtypes = [C.POINTER(OhConvert), I, C.POINTER(C.c_int32), I]
+        L.oh_pics_resize.argtypes = [V, C.POINTER(C.c_int), C.POINTER(C.c_int), I, C.POINTER(OhResize)]
+        L.oh_resize_taps.argtypes = [I, I, I, I, C.POINTER(C.c_int32), C.POINTER(C.c_int16), I, C.POINTER(C.c_int)]
+        L.oh_resize_max_taps.argtypes = [I, I, I]
         L.oh_frame_upload.argtypes = [V, C.POINTER(F.OhFrame), PP]
         L.oh_frames_upload.argtypes = [V, C.POINTER(C.POINTER(F.OhFrame)), I, PP]
         L.oh_frame_execute.argtypes = [V, V]
@@ -361,6 +401,39 @@ class Engine:
             # an event on the destroyed stream when the tensor is freed.
             cur.wait_stream(es)
         return out
+
+    def pics_resize(self, pids, size, *, window=(0, 0, 0, 0), filter="bilinear", out=None):
+        """finished pictures -> resized engine pictures (oh_pics_resize): size = (width, height) of the image in luma samples, window =
+        (left, right, top, bottom) of the sources in luma samples, filter "bilinear" or "bicubic" (anti-aliased when shrinking).
+        out: destination pictures to reuse; None allocates pictures with the sources' params and the size rounded up to the minimum
+        coding block.  Returns (destination ids, dst_window): the image is the top-left of each destination, dst_window the window to
+        pass to pics_convert / pic_download_window for it.  Enqueued on the engine stream; does not wait."""
+        pids = list(pids)
+        n = len(pids)
+        if n == 0:
+            raise ValueError("pics_resize needs at least one picture (the destinations follow the pictures' params)")
+        width, height = int(size[0]), int(size[1])
+        rs = OhResize(resize_filter(filter), OhWindow(*window), width, height)
+        fresh = out is None
+        if fresh:
+            sp = self._pic_params(pids[0])
+            if width < 1 or height < 1:
+                raise ValueError(f"size {size}: at least 1 x 1")
+            dp = F.OhPicParams.from_buffer_copy(sp)
+            mcb = 1 << sp.log2_min_cb_size
+            dp.width, dp.height = -(-width // mcb) * mcb, -(-height // mcb) * mcb
+            out = [self.pic_alloc(dp) for _ in range(n)]
+        else:
+            out = list(out)
+            if len(out) != n:
+                raise ValueError(f"out: {len(out)} pictures for {n} sources")
+        rc = self.L.oh_pics_resize(self.h, (C.c_int * n)(*pids), (C.c_int * n)(*out), n, C.byref(rs))
+        if rc != 0 and fresh:
+            for pid in out:
+                self.pic_free(pid)
+        self._chk(rc, "oh_pics_resize")
+        dp = self._pic_params(out[0])
+        return out, (0, dp.width - width, 0, dp.height - height)
 
     def _pic_params(self, pid):
         p = self._params.get(pid)
