@@ -1,223 +1,14 @@
 /*
  * engine.hip — host side of the MI355X engine: device-resident pictures (the DPB lives in HBM),
- * work-list upload, pass scheduling on one HIP stream, per-pass event timing.
+ * work-list upload, pass scheduling on one HIP stream, per-pass event timing.  What runs on finished
+ * pictures beside that path is in engine_pics.hip and engine_shvc.hip; engine_impl.h is what they share.
  * C ABI in include/ohevc_hip.h.  No CPU fallback exists: without a usable device every entry
  * point returns OH_E_HIP.
  */
-#include <hip/hip_runtime.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <algorithm>
-#include <chrono>
-#include <string>
-#include <condition_variable>
-#include <mutex>
-#include <thread>
-#include <vector>
-
-#include "../../include/ohevc_hip.h"
-#include "dev_frame.h"
-#include "kernels.h"
-
-namespace {
-
-struct Pic {
-    bool        used = false;
-    OhPicParams p{};
-    void       *base = nullptr;          /* one allocation: planes A (recon/deblock) then B (SAO out) */
-    bool        owned = true;            /* false: caller-owned memory (oh_pic_wrap)                   */
-    void       *a[3] = {}, *b[3] = {};
-    int32_t     stride[3] = {}, w[3] = {}, h[3] = {};
-    bool        final_b = false;         /* which buffer holds the finished picture */
-    uint32_t    gen = 0;                 /* bumped whenever the id is (re)installed: uploaded work lists remember it */
-    uint64_t    done_seq = 0;            /* the batch that last reconstructed the picture (OhEngine::batch_ev ring); 0: written by something else, or never */
-};
-
-struct EventSet { hipEvent_t ev[OH_N_PASSES + 1]; int n_frames = 1; };
-
-} // namespace
-
-struct OhDevFrame {
-    void      *arena = nullptr;
-    size_t     arena_bytes = 0;
-    DevFrame  *d = nullptr;
-    OhPicParams p{};
-    uint32_t   tu_cnt[4] = { 0, 0, 0, 0 };
-    uint32_t   n_cross = 0;
-    bool       has_sao = false;
-    int        cur_pic = -1;      /* engine id of the picture the list reconstructs */
-    uint32_t   cur_gen = 0;
-    /* reference slots as uploaded: picture id, its generation, and which half DevFrame.refs[] points at — looked up again at
-     * every execute (a reference finished or received AFTER the upload moves to its other half: oh_pic_set_final_half, SAO) */
-    int        ref_id[OH_MAX_REFS];
-    uint32_t   ref_gen[OH_MAX_REFS];
-    uint8_t    ref_half[OH_MAX_REFS];
-    uint16_t   ref_used = 0;      /* bit i: some PU predicts from slot i */
-    hipEvent_t ready = nullptr;   /* recorded on the copy stream behind the work list's H2D copy, preparation kernels and summary */
-    bool       waited = false;    /* the engine stream already waits for `ready` */
-    void      *sum_host = nullptr;/* pinned: the DevSummary the preparation kernels left */
-    bool       summary_read = false;
-    void      *sum_dev = nullptr; /* the summary in the arena */
-    OhPrepCounts cnt{};           /* sizes of the preparation launches */
-    uint32_t   prep_err = 0;
-    uint32_t   intra_area64 = 0, max_passes = 0;   /* from the summary: samples of the intra blocks / 64; wave passes of the heaviest CTU */
-    /* from the summary, over the schedule entries: what lays out the staged intra launch */
-    uint32_t   max_items = 0, max_sub = 0, max_res = 0;
-    bool       res_scattered = false;             /* some CTU's residual span is not contiguous (not stageable in LDS) */
-    uint64_t   sum_items = 0, sum_sub = 0;
-    const struct OhEngine *owner = nullptr;   /* picture ids and arenas belong to one engine */
-};
-
-/* helper threads for the one host copy of the hand-over (the work list into a pinned staging buffer): the lists of a 4K picture are
- * ~4 MB, 0.22 ms for one thread — most of what the hand-over costs the decoder's thread.  The calling thread keeps a share. */
-struct CopyJob { char *dst; const char *src; size_t n; bool pack; };
-static void pack_bs(uint8_t *dst, const uint8_t *src, size_t n);
-struct CopyPool {
-    std::vector<std::thread> th;
-    std::mutex mu;
-    std::condition_variable cv, done_cv;
-    const std::vector<CopyJob> *jobs = nullptr;
-    int pending = 0;
-    uint64_t gen = 0;
-    bool stop = false;
-    static void run_share(const std::vector<CopyJob> &jobs, int share, int shares)
-    {
-        for (size_t i = (size_t)share; i < jobs.size(); i += (size_t)shares) {
-            const CopyJob &j = jobs[i];
-            if (j.pack) pack_bs((uint8_t *)j.dst, (const uint8_t *)j.src, j.n);
-            else memcpy(j.dst, j.src, j.n);
-        }
-    }
-    void worker(int k)
-    {
-        uint64_t seen = 0;
-        for (;;) {
-            const std::vector<CopyJob> *my;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return stop || gen != seen; });
-                if (stop) return;
-                seen = gen;
-                my = jobs;
-            }
-            run_share(*my, k + 1, (int)th.size() + 1);
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                if (--pending == 0) done_cv.notify_one();
-            }
-        }
-    }
-    void start(int n) { for (int k = 0; k < n; k++) th.emplace_back(&CopyPool::worker, this, k); }
-    void run(const std::vector<CopyJob> &j)                    /* returns when every job has been copied */
-    {
-        if (th.empty()) { run_share(j, 0, 1); return; }
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            jobs = &j; pending = (int)th.size(); gen++;
-        }
-        cv.notify_all();
-        run_share(j, 0, (int)th.size() + 1);
-        std::unique_lock<std::mutex> lk(mu);
-        done_cv.wait(lk, [&] { return pending == 0; });
-    }
-    ~CopyPool()
-    {
-        { std::lock_guard<std::mutex> lk(mu); stop = true; }
-        cv.notify_all();
-        for (auto &t : th) t.join();
-    }
-};
-
-struct OhEngine {
-    int         device = 0;
-    int         n_cu = 256;              /* compute units of the device */
-    hipStream_t stream = nullptr;
-    bool        own_stream = true;
-    std::vector<Pic> pics;
-    std::string err;
-    int         profile = 0;             /* 0 off, 1 events between passes, 2 also around every batch's intra launches */
-    std::vector<EventSet> ev_pool, ev_pending;
-    std::vector<hipEvent_t> lev_pool, lev_pending;   /* event pairs around every batch's intra launches (profile mode) */
-    double      intra_launch_ms = 0;
-    uint64_t    intra_launches = 0;
-    double      pass_ms[OH_N_PASSES] = {};
-    uint64_t    executes = 0;
-    std::vector<OhDevFrame *> deferred;
-    uint32_t    pic_gen = 0;
-    /* upload path: pinned staging buffers and device arenas are recycled (hipHostMalloc / hipMalloc cost milliseconds);
-     * a staging buffer is busy until the H2D copy that reads it has passed `done` */
-    struct Stage { void *p; size_t bytes; hipEvent_t done; bool busy; };
-    std::vector<Stage> stages;
-    /* work lists travel on their own stream so that the copy of picture n+1 overlaps the passes of picture n; the engine stream
-     * waits for a list's `ready` event before the first kernel that reads it, and a recycled arena is not overwritten before
-     * the engine stream has passed the event recorded when it was released */
-    hipStream_t copy_stream = nullptr;
-    struct Arena { void *p; size_t bytes; hipEvent_t free_ev; };
-    std::vector<Arena> arenas;               /* free device arenas */
-    uint64_t    arenas_alive = 0, arena_bytes_alive = 0;      /* device arenas allocated and not freed (pooled or holding a work list): oh_engine_memory */
-    std::vector<hipEvent_t> sync_events;     /* pool of timing-disabled events (ready / free_ev) */
-    std::vector<void *> sum_pool;            /* pinned blocks of sizeof(DevSummary) bytes */
-    double      host_ms[OH_N_HOST_TIMES] = {};   /* where the host time of the hand-over path goes (oh_engine_host_times) */
-    uint64_t    host_calls[OH_N_HOST_TIMES] = {};
-    uint64_t    up_bytes = 0;                    /* bytes of work lists sent over PCIe since the last reset */
-    uint64_t   *dbg = nullptr;           /* diagnostics (OHEVC_STAMPS=1 + a -DOH_STAMPS build) */
-    /* what a kernel can tell the host when it cannot go on (the table slots and the passes have no error channel: hevcdsp.h's slots
-     * return void): four words of pinned host memory, [0] OH_KE_* of the first failure, [1] picture id, [2] schedule
-     * entry; read by everything that waits for the stream (kernel_error) */
-    /* a ring of events, one behind every executed batch: a download of a finished picture waits for ITS batch (on the download
-     * stream), not for everything enqueued since — a decoder fetches the picture it outputs while the passes of the pictures it
-     * submitted later keep running */
-    enum { BATCH_RING = 64 };
-    hipEvent_t  batch_ev[BATCH_RING] = {};
-    uint64_t    batch_seq = 0;
-    hipStream_t dl_stream = nullptr;
-    /* ticket counters of the one-launch intra forms: a ring of pairs (direct, staged) in HBM; a batch uses the next pair, cleared on
-     * the stream in front of its launches (a pair comes round again 128 batches later: long after its launch has drained) */
-    enum { TICKET_RING = 128, TICKET_WORDS = 2 * OH_MAX_BATCH * 32 };      /* per batch: (direct, staged) x pictures, a cache line each (intra.hip: OH_TICKET_STRIDE) */
-    uint32_t   *tickets = nullptr;
-    uint64_t    ticket_seq = 0;
-    CopyPool   *copiers = nullptr;      /* created with the first hand-over (OHEVC_COPY_THREADS helpers, default 2) */
-    /* output fetch (oh_pic_download_start / oh_download_finish): its own pinned buffers and copy helpers, usable while another thread
-     * drives the engine */
-    std::mutex  dl_mu, dl_copy_mu;
-    std::vector<Stage *> dl_stages;
-    CopyPool   *dl_copiers = nullptr;   /* created with the first fetch (OHEVC_FETCH_THREADS helpers, default 3) */
-    std::vector<CopyJob> dl_jobs;
-    double      dl_wait_ms = 0, dl_copy_ms = 0;     /* OHEVC_FETCH_TIMING: where the time of the fetches went (printed when the engine is destroyed) */
-    uint64_t    dl_count = 0;
-    std::vector<CopyJob> copy_jobs;
-    uint32_t   *kerr = nullptr;
-    void       *hash_dev = nullptr;      /* oh_pics_hash (CRC / checksum): the job table, its tasks and their values in HBM */
-    size_t      hash_dev_bytes = 0;
-    void       *resize_dev = nullptr;    /* oh_pics_resize: the tap tables of the call, then the int16 intermediate of one launch set */
-    size_t      resize_dev_bytes = 0;
-    uint32_t    spin_limit = 1u << 22;   /* polls (with s_sleep between them, ~1 s in all) before a waiting workgroup gives up; OHEVC_SPIN_LIMIT */
-};
-
-#define HIPCHK(e, call)                                                                           \
-    do {                                                                                          \
-        hipError_t rc_ = (call);                                                                  \
-        if (rc_ != hipSuccess) {                                                                  \
-            char buf_[512];                                                                       \
-            snprintf(buf_, sizeof(buf_), "%s failed: %s (%s:%d)", #call, hipGetErrorString(rc_), __FILE__, __LINE__); \
-            (e)->err = buf_;                                                                      \
-            return OH_E_HIP;                                                                      \
-        }                                                                                         \
-    } while (0)
-
-#define FAIL(e, code, ...)                                                                        \
-    do {                                                                                          \
-        char buf_[512];                                                                           \
-        snprintf(buf_, sizeof(buf_), __VA_ARGS__);                                                \
-        (e)->err = buf_;                                                                          \
-        return (code);                                                                            \
-    } while (0)
-
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+#include "engine_impl.h"
 
 /* after a wait on the engine's stream: did a kernel latch a failure (intra.hip: dag_latch_error)?  Reported once, then cleared. */
-static int kernel_error(OhEngine *e)
+int kernel_error(OhEngine *e)
 {
     if (!e->kerr || !e->kerr[0])
         return OH_OK;
@@ -226,12 +17,6 @@ static int kernel_error(OhEngine *e)
     FAIL(e, OH_E_HIP, "intra pass (one launch per picture): picture %u, schedule entry %u gave up waiting for a neighbour CTU; the picture's samples are not valid",
          pic, where);
 }
-struct HostTimer {                       /* adds the scope's wall time to one slot of OhEngine::host_ms */
-    OhEngine *e; int slot; std::chrono::steady_clock::time_point t0;
-    HostTimer(OhEngine *e_, int slot_);
-    ~HostTimer();
-};
-enum { OH_MAX_STAGES = 48 };             /* pinned staging buffers per engine before the host is made to wait */
 
 HostTimer::HostTimer(OhEngine *e_, int slot_) : e(e_), slot(slot_), t0(std::chrono::steady_clock::now()) {}
 HostTimer::~HostTimer()
@@ -438,8 +223,8 @@ extern "C" void oh_engine_destroy(OhEngine *e)
     for (auto *c : e->dl_stages) { (void)hipEventDestroy(c->done); (void)hipHostFree(c->p); delete c; }
     if (e->kerr) (void)hipHostFree(e->kerr);
     if (e->tickets) (void)hipFree(e->tickets);
-    if (e->hash_dev) (void)hipFree(e->hash_dev);
-    if (e->resize_dev) (void)hipFree(e->resize_dev);
+    if (e->hash_dev.p) (void)hipFree(e->hash_dev.p);
+    if (e->resize_dev.p) (void)hipFree(e->resize_dev.p);
     for (auto &ev : e->batch_ev) if (ev) (void)hipEventDestroy(ev);
     if (e->dl_stream) { (void)hipStreamSynchronize(e->dl_stream); (void)hipStreamDestroy(e->dl_stream); }
     if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);
@@ -539,11 +324,19 @@ extern "C" int oh_pic_wrap(OhEngine *e, const OhPicParams *p, void *half0, void 
     return pic_install(e, p, half0, half1, false, pic_id);
 }
 
-static Pic *get_pic(OhEngine *e, int id)
+Pic *get_pic(OhEngine *e, int id)
 {
     if (id < 0 || (size_t)id >= e->pics.size() || !e->pics[id].used)
         return nullptr;
     return &e->pics[id];
+}
+
+int check_pics(OhEngine *e, const int *pic_ids, int n, const char *who)
+{
+    for (int i = 0; i < n; i++)
+        if (!get_pic(e, pic_ids[i]))
+            FAIL(e, OH_E_ARG, "%s: unknown picture %d", who, pic_ids[i]);
+    return OH_OK;
 }
 
 extern "C" int oh_pic_free(OhEngine *e, int pic_id)
@@ -581,263 +374,9 @@ extern "C" int oh_pic_set_final_half(OhEngine *e, int pic_id, int half)
     return OH_OK;
 }
 
-/* SHVC inter-layer reference: upsample_base_layer_frame (hevcdsp_template.c:2164-2438, called at hevc.c:3241) */
-static OhEngine::Stage *stage_acquire(OhEngine *e, size_t bytes);
-
-/* SHVC up-sampling of tiles of the enhancement-layer picture: ctbs == nullptr: the whole picture (the reference's whole-picture
- * slot, hevc.c:3241); else the listed CTBs (raster addresses, CTB size 1 << log2_ctb) — the on-demand granularity of the
- * reference's default build (ff_upsample_block, hevc_filter.c:1370-1426: a CTB is up-sampled when a PU first predicts from it) */
-static int upsample_tiles(OhEngine *e, int dst_pic, int src_pic, const OhUpsample *u, int log2_ctb, const uint32_t *ctbs, int n_ctbs, const char *who)
-{
-    if (!e || !u)
-        return OH_E_ARG;
-    Pic *el = get_pic(e, dst_pic), *bl = get_pic(e, src_pic);
-    if (!el || !bl || el == bl)
-        FAIL(e, OH_E_ARG, "%s: bad picture ids", who);
-    el->done_seq = 0;
-    if (el->p.bit_depth != 8 || bl->p.bit_depth != 8 || el->p.chroma_format_idc != 1 || bl->p.chroma_format_idc != 1)
-        FAIL(e, OH_E_UNSUPPORTED, "%s: the reference's up-sampler is written for 8-bit 4:2:0 (byte edge buffers, shift 12)", who);
-    const int w_el = el->p.width, h_el = el->p.height, w_bl = bl->p.width, h_bl = bl->p.height;
-    if (u->win_left < 0 || u->win_right < 0 || u->win_top < 0 || u->win_bottom < 0 || u->win_left + u->win_right >= w_el ||
-        u->win_top + u->win_bottom >= h_el || u->scale_x_lum <= 0 || u->scale_y_lum <= 0 || u->scale_x_cr <= 0 || u->scale_y_cr <= 0)
-        FAIL(e, OH_E_ARG, "%s: bad window / scale", who);
-    if (u->scale_x_lum > 65536 || u->scale_y_lum > 65536 || u->scale_x_cr > 65536 || u->scale_y_cr > 65536)
-        FAIL(e, OH_E_UNSUPPORTED, "%s: the enhancement layer is smaller than the base layer (scale > 1): not a spatial-scalability configuration", who);
-    HIPCHK(e, hipSetDevice(e->device));
-    const int tile = ctbs ? 1 << log2_ctb : 64;
-    const uint32_t *dlist = nullptr;
-    OhEngine::Stage *sg = nullptr;
-    if (ctbs) {
-        if (log2_ctb < 4 || log2_ctb > 6 || n_ctbs < 0)
-            FAIL(e, OH_E_ARG, "%s: CTB size / count", who);
-        if (!n_ctbs)
-            return OH_OK;
-        const uint32_t n_ctb = (uint32_t)(((w_el + tile - 1) / tile) * ((h_el + tile - 1) / tile));
-        for (int i = 0; i < n_ctbs; i++)
-            if (ctbs[i] >= n_ctb)
-                FAIL(e, OH_E_ARG, "%s: CTB address %u of %u", who, ctbs[i], n_ctb);
-        sg = stage_acquire(e, (size_t)n_ctbs * sizeof(uint32_t));       /* pinned and mapped: the kernels read the list there */
-        if (!sg)
-            FAIL(e, OH_E_NOMEM, "%s: no staging buffer", who);
-        memcpy(sg->p, ctbs, (size_t)n_ctbs * sizeof(uint32_t));
-        dlist = (const uint32_t *)sg->p;
-    }
-    void *const *src = bl->final_b ? bl->b : bl->a;
-    OhUpPlane a;
-    /* luma: BL rows = min(BL height, EL height) (:2220); x clipped to [left, right_end] inclusive (:2223) */
-    a.src = src[0]; a.sstride = bl->stride[0]; a.w_bl = w_bl; a.h_bl = h_bl <= h_el ? h_bl : h_el;
-    a.dst = el->a[0]; a.dstride = el->stride[0]; a.w_el = w_el; a.h_el = h_el;
-    a.left = u->win_left; a.right_end_h = w_el - u->win_right; a.right_end_v = w_el - u->win_right;
-    a.top = u->win_top; a.bottom_end = h_el - u->win_bottom;
-    a.scale_x = u->scale_x_lum; a.add_x = u->add_x_lum; a.scale_y = u->scale_y_lum; a.add_y = u->add_y_lum; a.y_bias = 0;
-    ohk_upsample_plane(&a, 8, tile, tile, dlist, n_ctbs, e->stream);
-    /* chroma: BL rows = max(BL height, EL chroma height) >> 1 (:2317-2320); x clipped to [left, right_end - 1] (:2324);
-     * the vertical position carries the -4 of :2384.  A CTB's chroma tile has the same index in a grid of half-size tiles. */
-    const int wc_el = w_el >> 1, hc_el = h_el >> 1;
-    for (int c = 1; c <= 2; c++) {
-        a.src = src[c]; a.sstride = bl->stride[c]; a.w_bl = w_bl >> 1; a.h_bl = (h_bl > hc_el ? h_bl : hc_el) >> 1;
-        if (a.h_bl > bl->h[c]) a.h_bl = bl->h[c];
-        a.dst = el->a[c]; a.dstride = el->stride[c]; a.w_el = wc_el; a.h_el = hc_el;
-        a.left = u->win_left >> 1; a.right_end_v = wc_el - (u->win_right >> 1); a.right_end_h = a.right_end_v - 1;
-        a.top = u->win_top >> 1; a.bottom_end = hc_el - (u->win_bottom >> 1);
-        a.scale_x = u->scale_x_cr; a.add_x = u->add_x_cr; a.scale_y = u->scale_y_cr; a.add_y = u->add_y_cr; a.y_bias = 4;
-        ohk_upsample_plane(&a, 4, tile >> 1, tile >> 1, dlist, n_ctbs, e->stream);
-    }
-    HIPCHK(e, hipGetLastError());
-    if (sg) {
-        HIPCHK(e, hipEventRecord(sg->done, e->stream));
-        sg->busy = true;
-    }
-    el->final_b = false;                                   /* the resampled picture is a finished picture in half 0 */
-    return OH_OK;
-}
-
-extern "C" int oh_pic_upsample(OhEngine *e, int dst_pic, int src_pic, const OhUpsample *u)
-{
-    return upsample_tiles(e, dst_pic, src_pic, u, 6, nullptr, 0, "oh_pic_upsample");
-}
-
-extern "C" int oh_pic_upsample_ctbs(OhEngine *e, int dst_pic, int src_pic, const OhUpsample *u, int log2_ctb_size, const uint32_t *ctb_addrs, int n)
-{
-    if (!ctb_addrs && n)
-        return OH_E_ARG;
-    /* the reference's block path positions by its block driver and its x2 / x1.5 slots ignore the phase: with scaled reference
-     * layer offsets or phase alignment it produces OTHER samples than the whole-picture slot (tests/test_upsample_vs_ref.py
-     * records both).  This entry point is the whole-picture arithmetic per CTB, so it stands for the block path only where the
-     * reference's two paths agree. */
-    if (u && (u->win_left || u->win_right || u->win_top || u->win_bottom))
-        FAIL(e, OH_E_UNSUPPORTED, "oh_pic_upsample_ctbs: scaled reference layer offsets — the reference's CTB path and its whole-picture slot differ there; use oh_pic_upsample");
-    static const uint32_t none = 0;
-    return upsample_tiles(e, dst_pic, src_pic, u, log2_ctb_size, n ? ctb_addrs : &none, n, "oh_pic_upsample_ctbs");
-}
-
-/* ---- the reference's CTB path (upblock.h): where its output is defined, and the call ---- */
-static void upb_geoms(OhUpBlkGeom g[2], const OhUpsample *u, int w_bl, int h_bl, int w_el, int h_el, int log2_ctb, const OhWindow *conf)
-{
-    for (int c = 0; c < 2; c++) {
-        OhUpBlkGeom &q = g[c];
-        q.cr = c; q.idx = u->idx; q.log2_ctb = log2_ctb;
-        q.w_el = w_el >> c; q.h_el = h_el >> c;
-        q.bl_w = w_bl >> c; q.bl_w_act = w_bl >> c; q.bl_h_act = h_bl >> c;
-        q.bl_h = c ? (h_bl > q.h_el ? h_bl : q.h_el) >> 1 : h_bl;          /* hevc_filter.c:1252 */
-        q.left = u->win_left >> c; q.right_end = q.w_el - (u->win_right >> c);
-        q.top = u->win_top >> c; q.bottom_end = q.h_el - (u->win_bottom >> c);
-        q.sx = c ? u->scale_x_cr : u->scale_x_lum; q.ax = c ? u->add_x_cr : u->add_x_lum;
-        q.sy = c ? u->scale_y_cr : u->scale_y_lum; q.ay = c ? u->add_y_cr : u->add_y_lum;
-        q.dsx = u->scale_x_lum; q.dax = u->add_x_lum; q.dsy = u->scale_y_lum; q.day = u->add_y_lum;
-        q.conf_left = conf ? conf->left >> c : 0; q.conf_top = conf ? conf->top >> c : 0;
-    }
-}
-
-static const char *upb_reason(int r)
-{
-    switch (r) {
-    case UPB_STALE_ROW:    return "its vertical slot reads an intermediate row the window estimate (hevc_filter.c:1260) did not filter: scratch of an earlier call";
-    case UPB_BL_ROW:       return "it reads base-layer rows outside the picture";
-    case UPB_BL_COL:       return "it reads base-layer columns beyond an edge its call did not emulate";
-    case UPB_BL_OVERWRITE: return "its left edge emulation writes over base-layer samples other CTBs read";
-    case UPB_FOREIGN_ROW:  return "its chroma rows clip into another CTB's rows";
-    }
-    return "?";
-}
-
-/* the first CTB of the list (all CTBs: ctbs == nullptr) whose output the reference does not define; *reason: UPB_*, *plane: 0 luma 1 chroma */
-static int upb_first_bad(const OhUpBlkGeom g[2], int w_el, int h_el, int log2_ctb, const uint32_t *ctbs, int n, int *reason, int *plane)
-{
-    const int size = 1 << log2_ctb, cw = (w_el + size - 1) >> log2_ctb, nall = cw * ((h_el + size - 1) >> log2_ctb);
-    for (int k = 0; k < (ctbs ? n : nall); k++) {
-        const int a = ctbs ? (int)ctbs[k] : k, x0 = (a % cw) << log2_ctb, y0 = (a / cw) << log2_ctb;
-        for (int c = 0; c < 2; c++) {
-            const int r = upb_check(g[c], x0 >> c, y0 >> c);
-            if (r) {
-                *reason = r; *plane = c;
-                return a;
-            }
-        }
-    }
-    return -1;
-}
-
-static bool upb_args_ok(const OhUpsample *u, int w_bl, int h_bl, int w_el, int h_el, int log2_ctb)
-{
-    return u && w_bl > 0 && h_bl > 0 && w_el > 0 && h_el > 0 && log2_ctb >= 4 && log2_ctb <= 6 && u->win_left >= 0 && u->win_right >= 0 &&
-           u->win_top >= 0 && u->win_bottom >= 0 && u->win_left + u->win_right < w_el && u->win_top + u->win_bottom < h_el &&
-           u->scale_x_lum > 0 && u->scale_y_lum > 0 && u->scale_x_cr > 0 && u->scale_y_cr > 0 && u->idx >= OH_UP_DEFAULT && u->idx <= OH_UP_SNR;
-}
-
-extern "C" int oh_upsample_blocks_defined(const OhUpsample *u, int w_bl, int h_bl, int w_el, int h_el, int log2_ctb_size, int *first_bad_ctb)
-{
-    if (first_bad_ctb)
-        *first_bad_ctb = -1;
-    if (!upb_args_ok(u, w_bl, h_bl, w_el, h_el, log2_ctb_size))
-        return OH_E_ARG;
-    if (u->scale_x_lum > 65536 || u->scale_y_lum > 65536 || u->scale_x_cr > 65536 || u->scale_y_cr > 65536)
-        return 0;                                          /* EL smaller than BL: no spatial scalability, and the windows are unbounded */
-    OhUpBlkGeom g[2];
-    upb_geoms(g, u, w_bl, h_bl, w_el, h_el, log2_ctb_size, nullptr);
-    int reason, plane;
-    const int bad = upb_first_bad(g, w_el, h_el, log2_ctb_size, nullptr, 0, &reason, &plane);
-    if (first_bad_ctb)
-        *first_bad_ctb = bad;
-    return bad < 0;
-}
-
-extern "C" int oh_pic_upsample_blocks(OhEngine *e, int dst_pic, int src_pic, const OhUpsample *u, int log2_ctb_size,
-                                      const OhWindow *el_conf_win, const uint32_t *ctb_addrs, int n)
-{
-    if (!e || !u || (!ctb_addrs && n) || n < 0)
-        return OH_E_ARG;
-    Pic *el = get_pic(e, dst_pic), *bl = get_pic(e, src_pic);
-    if (!el || !bl || el == bl)
-        FAIL(e, OH_E_ARG, "oh_pic_upsample_blocks: bad picture ids");
-    if (el->p.bit_depth != 8 || bl->p.bit_depth != 8 || el->p.chroma_format_idc != 1 || bl->p.chroma_format_idc != 1)
-        FAIL(e, OH_E_UNSUPPORTED, "oh_pic_upsample_blocks: the reference's up-sampler is written for 8-bit 4:2:0 (byte edge buffers, shift 12)");
-    const int w_el = el->p.width, h_el = el->p.height, w_bl = bl->p.width, h_bl = bl->p.height;
-    if (!upb_args_ok(u, w_bl, h_bl, w_el, h_el, log2_ctb_size))
-        FAIL(e, OH_E_ARG, "oh_pic_upsample_blocks: bad window / scale / CTB size");
-    if (u->scale_x_lum > 65536 || u->scale_y_lum > 65536 || u->scale_x_cr > 65536 || u->scale_y_cr > 65536)
-        FAIL(e, OH_E_UNSUPPORTED, "oh_pic_upsample_blocks: the enhancement layer is smaller than the base layer (scale > 1): not a spatial-scalability configuration");
-    if (el_conf_win && (el_conf_win->left || el_conf_win->right || el_conf_win->top || el_conf_win->bottom))
-        FAIL(e, OH_E_UNSUPPORTED, "oh_pic_upsample_blocks: a non-zero enhancement-layer conformance window (the driver positions by it, hevc_filter.c:1196-1197) is not covered yet");
-    const int size = 1 << log2_ctb_size, n_all = ((w_el + size - 1) >> log2_ctb_size) * ((h_el + size - 1) >> log2_ctb_size);
-    for (int i = 0; ctb_addrs && i < n; i++)
-        if (ctb_addrs[i] >= (uint32_t)n_all)
-            FAIL(e, OH_E_ARG, "oh_pic_upsample_blocks: CTB address %u of %d", ctb_addrs[i], n_all);
-    OhUpBlkArgs a;
-    upb_geoms(a.g, u, w_bl, h_bl, w_el, h_el, log2_ctb_size, el_conf_win);
-    a.g[1].bl_h_act = bl->h[1] < a.g[1].bl_h_act ? bl->h[1] : a.g[1].bl_h_act;
-    int reason = 0, plane = 0;
-    const int bad = upb_first_bad(a.g, w_el, h_el, log2_ctb_size, ctb_addrs, n, &reason, &plane);
-    if (bad >= 0)
-        FAIL(e, OH_E_UNSUPPORTED, "oh_pic_upsample_blocks: the reference's CTB path does not define CTB %d (%s): %s", bad, plane ? "chroma" : "luma",
-             upb_reason(reason));
-    el->done_seq = 0;
-    const int cnt = ctb_addrs ? n : n_all;
-    if (!cnt)
-        return OH_OK;
-    HIPCHK(e, hipSetDevice(e->device));
-    const uint32_t *dlist = nullptr;
-    OhEngine::Stage *sg = nullptr;
-    if (ctb_addrs) {
-        sg = stage_acquire(e, (size_t)n * sizeof(uint32_t));      /* pinned and mapped: the kernel reads the list there */
-        if (!sg)
-            FAIL(e, OH_E_NOMEM, "oh_pic_upsample_blocks: no staging buffer");
-        memcpy(sg->p, ctb_addrs, (size_t)n * sizeof(uint32_t));
-        dlist = (const uint32_t *)sg->p;
-    }
-    void *const *src = bl->final_b ? bl->b : bl->a, *const *dst = el->final_b ? el->b : el->a;   /* CTBs not listed keep their samples */
-    for (int c = 0; c < 3; c++) {
-        a.src[c] = src[c]; a.sstride[c] = (int32_t)bl->stride[c];
-        a.dst[c] = dst[c]; a.dstride[c] = (int32_t)el->stride[c];
-    }
-    a.ctbs_x = (w_el + size - 1) >> log2_ctb_size;
-    ohk_upsample_blocks(&a, dlist, cnt, e->stream);
-    HIPCHK(e, hipGetLastError());
-    if (sg) {
-        HIPCHK(e, hipEventRecord(sg->done, e->stream));
-        sg->busy = true;
-    }
-    return OH_OK;
-}
-
-extern "C" int oh_pic_upload(OhEngine *e, int pic_id, const uint8_t *const planes[3], const ptrdiff_t strides[3])
-{
-    if (!e || !planes || !strides)
-        return OH_E_ARG;
-    Pic *p = get_pic(e, pic_id);
-    if (!p)
-        FAIL(e, OH_E_ARG, "oh_pic_upload: unknown picture %d", pic_id);
-    HIPCHK(e, hipSetDevice(e->device));
-    const size_t bpp = p->p.bit_depth > 8 ? 2 : 1;
-    for (int c = 0; c < (p->p.chroma_format_idc ? 3 : 1); c++)
-        HIPCHK(e, hipMemcpy2DAsync(p->a[c], (size_t)p->stride[c] * bpp, planes[c], (size_t)strides[c], (size_t)p->w[c] * bpp,
-                                   (size_t)p->h[c], hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    p->final_b = false;
-    p->done_seq = 0;
-    return OH_OK;
-}
-
-extern "C" int oh_pic_download(OhEngine *e, int pic_id, uint8_t *const planes[3], const ptrdiff_t strides[3])
-{
-    if (!e || !planes || !strides)
-        return OH_E_ARG;
-    Pic *p = get_pic(e, pic_id);
-    if (!p)
-        FAIL(e, OH_E_ARG, "oh_pic_download: unknown picture %d", pic_id);
-    HIPCHK(e, hipSetDevice(e->device));
-    const size_t bpp = p->p.bit_depth > 8 ? 2 : 1;
-    for (int c = 0; c < (p->p.chroma_format_idc ? 3 : 1); c++)
-        HIPCHK(e, hipMemcpy2DAsync(planes[c], (size_t)strides[c], p->final_b ? p->b[c] : p->a[c], (size_t)p->stride[c] * bpp,
-                                   (size_t)p->w[c] * bpp, (size_t)p->h[c], hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    { const int ke = kernel_error(e); if (ke) return ke; }     /* a kernel that gave up: these samples are not the picture */
-    return OH_OK;
-}
-
 /* n boundary strengths (0..2, one per byte: hevc_filter.c's vertical_bs / horizontal_bs) -> (n + 3) / 4 bytes, entry i in bits
  * 2 (i & 3) of byte i >> 2 — the form the deblock pass reads.  Four bytes per multiply: the 2-bit fields land in the top byte. */
-static void pack_bs(uint8_t *dst, const uint8_t *src, size_t n)
+void pack_bs(uint8_t *dst, const uint8_t *src, size_t n)
 {
     size_t i = 0;
     for (; i + 4 <= n; i += 4) {
@@ -852,8 +391,18 @@ static void pack_bs(uint8_t *dst, const uint8_t *src, size_t n)
     }
 }
 
+/* a new pinned buffer of at least `bytes` (4 MiB steps) with its event, not busy; false: nothing was allocated */
+bool stage_create(OhEngine::Stage *c, size_t bytes)
+{
+    c->bytes = align_up(bytes, (size_t)4 << 20); c->busy = false; c->p = nullptr; c->done = nullptr;
+    if (hipHostMalloc(&c->p, c->bytes, hipHostMallocDefault) == hipSuccess && hipEventCreateWithFlags(&c->done, hipEventDisableTiming) == hipSuccess)
+        return true;
+    if (c->p) (void)hipHostFree(c->p);
+    return false;
+}
+
 /* a pinned buffer of at least `bytes` whose previous copy has completed (uploads and downloads share the pool) */
-static OhEngine::Stage *stage_acquire(OhEngine *e, size_t bytes)
+OhEngine::Stage *stage_acquire(OhEngine *e, size_t bytes)
 {
     OhEngine::Stage *sg = nullptr;
     for (auto &c : e->stages) {
@@ -876,723 +425,25 @@ static OhEngine::Stage *stage_acquire(OhEngine *e, size_t bytes)
             }
     }
     OhEngine::Stage c;
-    c.bytes = align_up(bytes, (size_t)4 << 20); c.busy = false; c.p = nullptr; c.done = nullptr;
-    if (hipHostMalloc(&c.p, c.bytes, hipHostMallocDefault) != hipSuccess || hipEventCreateWithFlags(&c.done, hipEventDisableTiming) != hipSuccess) {
-        if (c.p) (void)hipHostFree(c.p);
+    if (!stage_create(&c, bytes))
         return nullptr;
-    }
     e->stages.push_back(c);
     return &e->stages.back();
 }
 
-/* Output side of the path: the conformance-window crop of ff_hevc_output_frame (hevc_refs.c:248-254:
- * plane pointers advanced by (left >> hshift, top >> vshift)) followed by libOpenHevcGetOutputCpy's packed row copies
- * (openHevcWrapper.c:353-398: `height >> vshift` rows of `(width >> hshift) << pixel_shift` bytes, width / height = the cropped
- * size).  One strided device-to-pinned copy per plane, one wait, then the rows go to the caller's pitches. */
-/* The output fetch in two halves, for a decoder whose threads share ONE engine behind a lock (the drop-in library: frame-thread
- * workers hand pictures over while the application's thread fetches the one that was released):
- *   oh_pic_download_start   (under the caller's engine lock, microseconds) validates, takes a pinned DOWNLOAD staging buffer — a list
- *                           of its own, guarded by its own mutex — and enqueues the strided device-to-host copies behind the batch
- *                           that finished the picture (download stream), then records an event;
- *   oh_download_finish      (NO engine lock needed, any thread) waits for that event, copies the rows into the caller's planes with
- *                           the download copy helpers, and gives the staging buffer back.
- * oh_pic_download_window is the two in a row. */
-struct OhDownload {
-    OhEngine::Stage *sg;
-    size_t row[3], rows[3], off[3];
-    int np;
-};
-
-extern "C" int oh_pic_download_start(OhEngine *e, int pic_id, const OhWindow *win, OhDownload **out)
+/* a host list where the kernels read it: copied into a pinned buffer of the pool (pinned host memory is mapped) */
+OhEngine::Stage *stage_list(OhEngine *e, const void *list, size_t bytes)
 {
-    if (!e || !win || !out)
-        return OH_E_ARG;
-    *out = nullptr;
-    Pic *p = get_pic(e, pic_id);
-    if (!p)
-        FAIL(e, OH_E_ARG, "oh_pic_download_window: unknown picture %d", pic_id);
-    const int W = p->p.width - win->left - win->right, H = p->p.height - win->top - win->bottom;
-    if (win->left < 0 || win->right < 0 || win->top < 0 || win->bottom < 0 || W <= 0 || H <= 0)
-        FAIL(e, OH_E_ARG, "oh_pic_download_window: window (%d,%d,%d,%d) leaves nothing of %dx%d", win->left, win->right, win->top, win->bottom,
-             p->p.width, p->p.height);
-    HIPCHK(e, hipSetDevice(e->device));
-    const size_t bpp = p->p.bit_depth > 8 ? 2 : 1;
-    OhDownload d;
-    d.np = p->p.chroma_format_idc ? 3 : 1;
-    size_t total = 0;
-    for (int c = 0; c < d.np; c++) {
-        const int hs = oh_hshift(&p->p, c), vs = oh_vshift(&p->p, c);
-        d.row[c] = (size_t)(W >> hs) * bpp; d.rows[c] = (size_t)(H >> vs);
-        d.off[c] = total; total += align_up(d.row[c] * d.rows[c], 256);
-    }
-    {   /* a free download buffer that fits, else a new one (a decoder has one or two fetches in flight) */
-        std::lock_guard<std::mutex> lk(e->dl_mu);
-        d.sg = nullptr;
-        for (auto *c : e->dl_stages)
-            if (!c->busy && c->bytes >= total && (!d.sg || c->bytes < d.sg->bytes)) d.sg = c;
-        if (!d.sg) {
-            OhEngine::Stage *c = new OhEngine::Stage();
-            c->bytes = align_up(total, (size_t)4 << 20); c->busy = false; c->p = nullptr; c->done = nullptr;
-            if (hipHostMalloc(&c->p, c->bytes, hipHostMallocDefault) != hipSuccess || hipEventCreateWithFlags(&c->done, hipEventDisableTiming) != hipSuccess) {
-                if (c->p) (void)hipHostFree(c->p);
-                delete c;
-                FAIL(e, OH_E_NOMEM, "hipHostMalloc(%zu) failed", total);
-            }
-            e->dl_stages.push_back(c);
-            d.sg = c;
-        }
-        d.sg->busy = true;
-    }
-    /* a picture a batch of this engine finished, and whose event is still in the ring: the copies run on the download stream behind
-     * THAT batch; anything else (uploaded, up-sampled, received from another GPU, long ago): behind everything on the engine stream */
-    hipStream_t dl = e->stream;
-    if (p->done_seq && e->batch_seq - p->done_seq < OhEngine::BATCH_RING - 1) {
-        if (!e->dl_stream) HIPCHK(e, hipStreamCreateWithFlags(&e->dl_stream, hipStreamNonBlocking));
-        HIPCHK(e, hipStreamWaitEvent(e->dl_stream, e->batch_ev[p->done_seq % OhEngine::BATCH_RING], 0));
-        dl = e->dl_stream;
-    }
-    hipError_t he = hipSuccess;
-    for (int c = 0; c < d.np && he == hipSuccess; c++) {
-        const int hs = oh_hshift(&p->p, c), vs = oh_vshift(&p->p, c);
-        const uint8_t *src = (const uint8_t *)(p->final_b ? p->b[c] : p->a[c]) + ((size_t)(win->top >> vs) * p->stride[c] + (size_t)(win->left >> hs)) * bpp;
-        he = hipMemcpy2DAsync((char *)d.sg->p + d.off[c], d.row[c], src, (size_t)p->stride[c] * bpp, d.row[c], d.rows[c], hipMemcpyDeviceToHost, dl);
-    }
-    if (he == hipSuccess) he = hipEventRecord(d.sg->done, dl);
-    if (he != hipSuccess) {
-        std::lock_guard<std::mutex> lk(e->dl_mu);
-        d.sg->busy = false;
-        FAIL(e, OH_E_HIP, "oh_pic_download_window: %s", hipGetErrorString(he));
-    }
-    *out = new OhDownload(d);
-    return OH_OK;
+    OhEngine::Stage *sg = stage_acquire(e, bytes);
+    if (sg) memcpy(sg->p, list, bytes);
+    return sg;
 }
 
-extern "C" int oh_download_finish(OhEngine *e, OhDownload *d, uint8_t *const planes[3], const ptrdiff_t strides[3])
+/* what is enqueued on `st` so far reads the buffer: it is busy until the stream has passed this point */
+int stage_in_use(OhEngine *e, OhEngine::Stage *sg, hipStream_t st)
 {
-    if (!e || !d)
-        return OH_E_ARG;
-    int rc = OH_OK;
-    if (!planes || !strides)
-        rc = OH_E_ARG;
-    for (int c = 0; c < d->np && !rc; c++)
-        if (!planes[c] || (ptrdiff_t)d->row[c] > strides[c])
-            rc = OH_E_ARG;
-    const auto t_w0 = std::chrono::steady_clock::now();
-    const hipError_t he = hipEventSynchronize(d->sg->done);    /* also when the arguments are bad: the buffer goes back only after its copy */
-    const auto t_w1 = std::chrono::steady_clock::now();
-    if (!rc && he != hipSuccess) rc = OH_E_HIP;
-    if (!rc) rc = kernel_error(e);                             /* a kernel that gave up: these samples are not the picture */
-    if (!rc) {
-        std::lock_guard<std::mutex> lk(e->dl_copy_mu);         /* one fetch at a time uses the helpers */
-        if (!e->dl_copiers) {
-            const char *v = getenv("OHEVC_FETCH_THREADS");
-            const int n = v ? atoi(v) : 3;
-            e->dl_copiers = new CopyPool();
-            e->dl_copiers->start(n < 0 ? 0 : (n > 15 ? 15 : n));
-        }
-        /* pieces of at most 1 MiB (packed planes) or single rows (pitched planes), dealt round-robin to the helpers and this thread */
-        std::vector<CopyJob> &jobs = e->dl_jobs;
-        jobs.clear();
-        for (int c = 0; c < d->np; c++) {
-            const char *src = (const char *)d->sg->p + d->off[c];
-            if ((size_t)strides[c] == d->row[c]) {
-                const size_t n = d->row[c] * d->rows[c], piece = (size_t)1 << 20;
-                for (size_t o = 0; o < n; o += piece) jobs.push_back(CopyJob{ (char *)planes[c] + o, src + o, n - o < piece ? n - o : piece, false });
-            } else {
-                for (size_t y = 0; y < d->rows[c]; y++) jobs.push_back(CopyJob{ (char *)planes[c] + (ptrdiff_t)y * strides[c], src + y * d->row[c], d->row[c], false });
-            }
-        }
-        e->dl_copiers->run(jobs);
-        e->dl_wait_ms += std::chrono::duration<double, std::milli>(t_w1 - t_w0).count();
-        e->dl_copy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_w1).count();
-        e->dl_count++;
-    }
-    {
-        std::lock_guard<std::mutex> lk(e->dl_mu);
-        d->sg->busy = false;
-    }
-    delete d;
-    return rc;
-}
-
-extern "C" int oh_pic_download_window(OhEngine *e, int pic_id, const OhWindow *win, uint8_t *const planes[3], const ptrdiff_t strides[3])
-{
-    if (!e || !win || !planes || !strides)
-        return OH_E_ARG;
-    OhDownload *d = nullptr;
-    const int rc = oh_pic_download_start(e, pic_id, win, &d);
-    if (rc)
-        return rc;
-    const int rc2 = oh_download_finish(e, d, planes, strides);
-    if (rc2 == OH_E_ARG)
-        FAIL(e, OH_E_ARG, "oh_pic_download_window: a destination plane is missing or its pitch is smaller than a row");
-    if (rc2 == OH_E_HIP)
-        FAIL(e, OH_E_HIP, "oh_pic_download_window: the device-to-host copy failed");
-    return rc2;
-}
-
-/* the planes of n pictures (ids checked) as hash jobs, the half that holds the final samples; slot[i * 3 + c]: the job of plane c of
- * picture i, -1 for the planes a monochrome picture lacks.  Returns the number of jobs. */
-static int plane_jobs(OhEngine *e, const int *pic_ids, int n, OhMd5Job *jobs, int *slot)
-{
-    int nj = 0;
-    for (int i = 0; i < n; i++) {
-        const Pic *p = get_pic(e, pic_ids[i]);
-        const uint32_t bpp = p->p.bit_depth > 8 ? 2 : 1;
-        for (int c = 0; c < 3; c++) {
-            slot[i * 3 + c] = -1;
-            if (c && !p->p.chroma_format_idc)
-                continue;
-            OhMd5Job &j = jobs[nj];
-            j.base = p->final_b ? p->b[c] : p->a[c];
-            j.pitch = (uint32_t)p->stride[c] * bpp; j.row_bytes = (uint32_t)p->w[c] * bpp; j.rows = (uint32_t)p->h[c]; j.bps = bpp;
-            slot[i * 3 + c] = nj++;
-        }
-    }
-    return nj;
-}
-
-static int check_pics(OhEngine *e, const int *pic_ids, int n, const char *who)
-{
-    for (int i = 0; i < n; i++)
-        if (!get_pic(e, pic_ids[i]))
-            FAIL(e, OH_E_ARG, "%s: unknown picture %d", who, pic_ids[i]);
-    return OH_OK;
-}
-
-/* Picture hash on the GPU: the three plane digests of the reference's SEI check (hevc.c:4146-4162 over calc_md5,
- * hevc.c:4623-4638: the whole coded planes, sps->width x sps->height and the chroma sizes, packed rows) for n finished pictures in one
- * launch of one chain per (picture, plane) — md5.hip.  48 bytes per picture come back instead of the picture.  Waits for the engine
- * stream.  digests: n x 3 x 16 bytes (monochrome: planes 1, 2 zero).  pic_ids checked. */
-static int pics_md5(OhEngine *e, const int *pic_ids, int n, uint8_t *digests)
-{
-    HIPCHK(e, hipSetDevice(e->device));
-    const size_t jobs_bytes = align_up((size_t)n * 3 * sizeof(OhMd5Job), 256);
-    OhEngine::Stage *sg = stage_acquire(e, jobs_bytes + (size_t)n * 48);
-    if (!sg)
-        FAIL(e, OH_E_NOMEM, "hipHostMalloc for %d picture hashes failed", n);
-    OhMd5Job *jobs = (OhMd5Job *)sg->p;
-    uint8_t *out = (uint8_t *)sg->p + jobs_bytes;
-    std::vector<int> slot((size_t)n * 3);
-    const int nj = plane_jobs(e, pic_ids, n, jobs, slot.data());
-    ohk_md5(jobs, nj, out, e->stream);                        /* pinned host memory is mapped: the kernel reads the jobs and writes the digests there */
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    { const int ke = kernel_error(e); if (ke) return ke; }     /* a kernel that gave up: these samples are not the picture */
-    for (size_t k = 0; k < slot.size(); k++) {
-        if (slot[k] >= 0) memcpy(digests + k * 16, out + (size_t)slot[k] * 16, 16);
-        else memset(digests + k * 16, 0, 16);
-    }
-    return OH_OK;
-}
-
-extern "C" int oh_pics_md5(OhEngine *e, const int *pic_ids, int n, uint8_t *digests)
-{
-    if (!e || n < 0 || (n && (!pic_ids || !digests)))
-        return OH_E_ARG;
-    if (!n)
-        return OH_OK;
-    { const int rc = check_pics(e, pic_ids, n, "oh_pics_md5"); if (rc) return rc; }
-    return pics_md5(e, pic_ids, n, digests);
-}
-
-/* CRC (kind 1) or checksum (kind 2) of every plane of n pictures (ids checked): vals[i * 3 + c], 0 for planes a monochrome picture
- * lacks.  hash.hip: one workgroup per OH_HASH_TASK bytes of every plane in one launch, then one per plane to combine.  The job table
- * and the task list are staged in pinned memory and copied to HBM in one piece; the values come back through the pinned buffer. */
-static int pics_crc_checksum(OhEngine *e, const int *pic_ids, int n, int kind, uint32_t *vals)
-{
-    HIPCHK(e, hipSetDevice(e->device));
-    std::vector<int> slot((size_t)n * 3);
-    std::vector<OhMd5Job> jv((size_t)n * 3);
-    const int nj = plane_jobs(e, pic_ids, n, jv.data(), slot.data());
-    std::vector<uint32_t> first((size_t)nj + 1, 0);
-    for (int k = 0; k < nj; k++) {
-        const uint64_t bytes = (uint64_t)jv[k].row_bytes * jv[k].rows;
-        first[k + 1] = first[k] + (uint32_t)((bytes + OH_HASH_TASK - 1) / OH_HASH_TASK);
-    }
-    const uint32_t nt = first[nj];
-    const size_t o_first = align_up((size_t)nj * sizeof(OhMd5Job), 256), o_map = o_first + align_up(((size_t)nj + 1) * 4, 256),
-                 o_part = o_map + align_up((size_t)nt * 8, 256), dev_bytes = o_part + align_up((size_t)nt * 4, 256);
-    if (dev_bytes > e->hash_dev_bytes) {                     /* every call ends with a wait: the old buffer is idle */
-        if (e->hash_dev) (void)hipFree(e->hash_dev);
-        e->hash_dev = nullptr; e->hash_dev_bytes = 0;
-        const size_t want = align_up(dev_bytes, (size_t)1 << 20);
-        HIPCHK(e, hipMalloc(&e->hash_dev, want));
-        e->hash_dev_bytes = want;
-    }
-    OhEngine::Stage *sg = stage_acquire(e, o_part + (size_t)nj * 4);
-    if (!sg)
-        FAIL(e, OH_E_NOMEM, "hipHostMalloc for %d picture hashes failed", n);
-    char *h = (char *)sg->p, *d = (char *)e->hash_dev;
-    memcpy(h, jv.data(), (size_t)nj * sizeof(OhMd5Job));
-    memcpy(h + o_first, first.data(), ((size_t)nj + 1) * 4);
-    uint32_t *map = (uint32_t *)(h + o_map);
-    for (int k = 0; k < nj; k++)
-        for (uint32_t t = first[k]; t < first[k + 1]; t++) { map[2 * t] = (uint32_t)k; map[2 * t + 1] = t - first[k]; }
-    uint32_t *out = (uint32_t *)(h + o_part);                 /* pinned and mapped: the combine kernel writes the plane values there */
-    HIPCHK(e, hipMemcpyAsync(d, h, o_part, hipMemcpyHostToDevice, e->stream));
-    ohk_hash(kind, (const OhMd5Job *)d, (const uint32_t *)(d + o_first), (const uint32_t *)(d + o_map), nj, (int)nt, (uint32_t *)(d + o_part), out,
-             e->stream);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    { const int ke = kernel_error(e); if (ke) return ke; }
-    for (size_t k = 0; k < slot.size(); k++)
-        vals[k] = slot[k] >= 0 ? out[slot[k]] : 0;
-    return OH_OK;
-}
-
-extern "C" int oh_pics_hash(OhEngine *e, const int *pic_ids, int n, int hash_type, OhPictureHash *out)
-{
-    if (!e || n < 0 || (n && (!pic_ids || !out)))
-        return OH_E_ARG;
-    if (hash_type < 0 || hash_type > 2)
-        FAIL(e, OH_E_ARG, "oh_pics_hash: hash_type %d (0 MD5, 1 CRC, 2 checksum)", hash_type);
-    if (!n)
-        return OH_OK;
-    { const int rc = check_pics(e, pic_ids, n, "oh_pics_hash"); if (rc) return rc; }
-    if (hash_type == 0) {
-        std::vector<uint8_t> dg((size_t)n * 48);
-        const int rc = pics_md5(e, pic_ids, n, dg.data());
-        if (rc) return rc;
-        for (int i = 0; i < n; i++) {
-            memset(&out[i], 0, sizeof(out[i]));
-            out[i].present = 1;
-            memcpy(out[i].md5, dg.data() + (size_t)i * 48, 48);
-        }
-        return OH_OK;
-    }
-    std::vector<uint32_t> v((size_t)n * 3);
-    const int rc = pics_crc_checksum(e, pic_ids, n, hash_type, v.data());
-    if (rc) return rc;
-    for (int i = 0; i < n; i++) {
-        memset(&out[i], 0, sizeof(out[i]));
-        out[i].present = 1; out[i].hash_type = hash_type;
-        for (int c = 0; c < 3; c++) (hash_type == 1 ? out[i].crc : out[i].checksum)[c] = v[(size_t)i * 3 + c];
-    }
-    return OH_OK;
-}
-
-/* ---------------- conversion to standard images (convert.hip) ---------------- */
-static int conv_sample_bytes(const OhConvert *cv, int bit_depth)
-{
-    switch (cv->sample) {
-    case OH_CONV_NATIVE: return bit_depth > 8 ? 2 : 1;
-    case OH_CONV_U8:     return 1;
-    case OH_CONV_F32:    return 4;
-    default:             return 2;
-    }
-}
-
-/* what oh_pics_convert checks of the combination itself (not of pictures or memory); *bytes: one image */
-static int conv_check(const OhPicParams *p, const OhConvert *cv, size_t *bytes, std::string *why)
-{
-    char buf[256];
-    if (!p || !cv) { *why = "no params or no OhConvert"; return OH_E_ARG; }
-    const int cf = p->chroma_format_idc, bd = p->bit_depth;
-    if (p->width <= 0 || p->height <= 0 || cf < 0 || cf > 3 || (bd != 8 && bd != 9 && bd != 10 && bd != 12)) {
-        *why = "bad picture params"; return OH_E_ARG;
-    }
-    if (cv->format < OH_CONV_PLANAR || cv->format > OH_CONV_RGBA || cv->sample < OH_CONV_NATIVE || cv->sample > OH_CONV_F32) {
-        snprintf(buf, sizeof(buf), "format %d / sample %d unknown", cv->format, cv->sample); *why = buf; return OH_E_UNSUPPORTED;
-    }
-    const bool yuv = cv->format <= OH_CONV_SEMIPLANAR;
-    if (yuv ? cv->sample > OH_CONV_U8 : cv->sample == OH_CONV_NATIVE) {
-        snprintf(buf, sizeof(buf), "sample %d does not fit format %d (YUV: NATIVE or U8; RGB: U8, U16, F16, F32)", cv->sample, cv->format);
-        *why = buf; return OH_E_UNSUPPORTED;
-    }
-    if (!yuv && cv->matrix != 1 && cv->matrix != 5 && cv->matrix != 6 && cv->matrix != 9) {
-        snprintf(buf, sizeof(buf), "matrix_coefficients %d (1 BT.709, 5 / 6 BT.601, 9 BT.2020 NCL)", cv->matrix); *why = buf; return OH_E_UNSUPPORTED;
-    }
-    if (cv->format == OH_CONV_SEMIPLANAR && cf == 0) { *why = "a 4:0:0 picture has no semi-planar form"; return OH_E_UNSUPPORTED; }
-    if ((cv->full_range != 0 && cv->full_range != 1) || (cv->chroma_filter != 0 && cv->chroma_filter != 1)) {
-        *why = "full_range and chroma_filter are 0 or 1"; return OH_E_ARG;
-    }
-    const OhWindow &w = cv->win;
-    const int sw = (cf == 1 || cf == 2) ? 2 : 1, sh = cf == 1 ? 2 : 1;
-    const int W = p->width - w.left - w.right, H = p->height - w.top - w.bottom;
-    if (w.left < 0 || w.right < 0 || w.top < 0 || w.bottom < 0 || W <= 0 || H <= 0 || w.left % sw || w.right % sw || w.top % sh || w.bottom % sh) {
-        snprintf(buf, sizeof(buf), "window (%d,%d,%d,%d) of %dx%d: empty, or offsets not multiples of %dx%d", w.left, w.right, w.top, w.bottom,
-                 p->width, p->height, sw, sh);
-        *why = buf; return OH_E_ARG;
-    }
-    size_t samples;
-    if (cv->format <= OH_CONV_SEMIPLANAR)
-        samples = (size_t)W * H + (cf ? 2 * (size_t)(W / sw) * (H / sh) : 0);
-    else
-        samples = (size_t)W * H * (cv->format == OH_CONV_RGBA ? 4 : 3);
-    *bytes = samples * (size_t)conv_sample_bytes(cv, bd);
-    return OH_OK;
-}
-
-extern "C" size_t oh_convert_image_bytes(const OhPicParams *p, const OhConvert *cv)
-{
-    size_t bytes = 0;
-    std::string why;
-    return conv_check(p, cv, &bytes, &why) == OH_OK ? bytes : 0;
-}
-
-/* the integers of an RGB conversion: R = clamp((cy (Y - yoff) + crv (Cr - mid) + 2^(S-1)) >> S, 0, 2^D - 1), G with cgu, cgv, B with
- * cbu; each coefficient round(2^S (2^D - 1) entry / scale) of the H.273 inverse matrix, S the largest shift that keeps every term and
- * every sum inside int32 for all samples of bit_depth bits */
-extern "C" int oh_convert_coeffs(const OhConvert *cv, int bit_depth, int32_t *out, int n)
-{
-    if (!cv || !out || n < OH_CONV_NCOEFFS || (bit_depth != 8 && bit_depth != 9 && bit_depth != 10 && bit_depth != 12))
-        return OH_E_ARG;
-    if (cv->format < OH_CONV_RGB_PLANAR || cv->format > OH_CONV_RGBA || cv->sample < OH_CONV_U8 || cv->sample > OH_CONV_F32)
-        return OH_E_UNSUPPORTED;
-    double kr, kb;
-    switch (cv->matrix) {
-    case 1:  kr = 0.2126; kb = 0.0722; break;
-    case 5:
-    case 6:  kr = 0.299;  kb = 0.114;  break;
-    case 9:  kr = 0.2627; kb = 0.0593; break;
-    default: return OH_E_UNSUPPORTED;
-    }
-    if (cv->full_range != 0 && cv->full_range != 1)
-        return OH_E_ARG;
-    const int B = bit_depth, D = cv->sample == OH_CONV_U8 ? 8 : 16;
-    const double kg = 1.0 - kr - kb, full = (double)((1 << B) - 1), unit = (double)(1 << (B - 8));
-    const double ys = cv->full_range ? full : 219.0 * unit, cs = cv->full_range ? full : 224.0 * unit;
-    const int yoff = cv->full_range ? 0 : 16 << (B - 8), mid = 1 << (B - 1);
-    const double ent[5] = { 1.0 / ys, 2.0 * (1.0 - kr) / cs, -2.0 * kb * (1.0 - kb) / (kg * cs), -2.0 * kr * (1.0 - kr) / (kg * cs),
-                            2.0 * (1.0 - kb) / cs };              /* cy, crv, cgu, cgv, cbu */
-    const int64_t dy = std::max(yoff, (1 << B) - 1 - yoff), dc = mid;   /* largest |Y - yoff|, |C - mid| */
-    const double scale = (double)((1 << D) - 1);
-    for (int S = 30; S >= 1; S--) {
-        int64_t c[5];
-        for (int i = 0; i < 5; i++) c[i] = llround(ldexp(scale * ent[i], S));
-        const int64_t r = (int64_t)1 << (S - 1), ty = std::llabs(c[0]) * dy;
-        const int64_t worst = std::max({ ty + std::llabs(c[1]) * dc + r, ty + (std::llabs(c[2]) + std::llabs(c[3])) * dc + r,
-                                         ty + std::llabs(c[4]) * dc + r });
-        if (worst > INT32_MAX)
-            continue;
-        for (int i = 0; i < 5; i++) out[i] = (int32_t)c[i];
-        out[5] = yoff; out[6] = mid; out[7] = S; out[8] = D;
-        return OH_OK;
-    }
-    return OH_E_UNSUPPORTED;
-}
-
-extern "C" int oh_pics_convert(OhEngine *e, const int *pic_ids, int n, const OhConvert *cv, void *dst, size_t image_stride, size_t dst_bytes)
-{
-    if (!e || n < 0 || !cv || (n && !pic_ids))
-        return OH_E_ARG;
-    if (!n)
-        return OH_OK;
-    { const int rc = check_pics(e, pic_ids, n, "oh_pics_convert"); if (rc) return rc; }
-    const Pic *p0 = get_pic(e, pic_ids[0]);
-    for (int i = 1; i < n; i++)
-        if (memcmp(&get_pic(e, pic_ids[i])->p, &p0->p, sizeof(OhPicParams)))
-            FAIL(e, OH_E_ARG, "oh_pics_convert: picture %d has other params than picture %d", pic_ids[i], pic_ids[0]);
-    size_t ib = 0;
-    std::string why;
-    { const int rc = conv_check(&p0->p, cv, &ib, &why); if (rc) FAIL(e, rc, "oh_pics_convert: %s", why.c_str()); }
-    const size_t ob = (size_t)conv_sample_bytes(cv, p0->p.bit_depth);
-    if (image_stride < ib || image_stride % ob || (uintptr_t)dst % ob)
-        FAIL(e, OH_E_ARG, "oh_pics_convert: image_stride %zu (an image takes %zu bytes) or dst not a multiple of the %zu-byte sample", image_stride, ib, ob);
-    if (!dst || ib > dst_bytes || (size_t)(n - 1) > (dst_bytes - ib) / image_stride)
-        FAIL(e, OH_E_ARG, "oh_pics_convert: %d images of %zu bytes, %zu apart, do not fit %zu bytes", n, ib, image_stride, dst_bytes);
-    const size_t total = (size_t)(n - 1) * image_stride + ib;
-    HIPCHK(e, hipSetDevice(e->device));
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, dst) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->device) {
-        (void)hipGetLastError();
-        FAIL(e, OH_E_ARG, "oh_pics_convert: dst is not device memory of device %d", e->device);
-    }
-    void *base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, dst) == hipSuccess) {
-        if ((char *)dst + total > (char *)base + size)
-            FAIL(e, OH_E_ARG, "oh_pics_convert: %zu bytes at dst run past the end of its allocation", total);
-    } else {
-        (void)hipGetLastError();
-    }
-    OhConvArgs a;
-    memset(&a, 0, sizeof(a));
-    const OhPicParams &p = p0->p;
-    const int bpp = p.bit_depth > 8 ? 2 : 1;
-    for (int c = 0; c < 3; c++) a.pitch[c] = p0->stride[c] * bpp;
-    a.cw = p0->w[1]; a.ch = p0->h[1];
-    a.left = cv->win.left; a.top = cv->win.top;
-    a.W = p.width - cv->win.left - cv->win.right; a.H = p.height - cv->win.top - cv->win.bottom;
-    a.cf = p.chroma_format_idc; a.bd = p.bit_depth; a.filter = cv->chroma_filter;
-    a.nc = cv->format == OH_CONV_RGBA ? 4 : 3;
-    a.image_stride = image_stride;
-    if (cv->format >= OH_CONV_RGB_PLANAR) {
-        const int rc = oh_convert_coeffs(cv, p.bit_depth, a.k, OH_CONV_NCOEFFS);
-        if (rc) FAIL(e, rc, "oh_pics_convert: no coefficients for this conversion");
-    }
-    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
-        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
-        for (int i = 0; i < m; i++) {
-            const Pic *q = get_pic(e, pic_ids[i0 + i]);
-            for (int c = 0; c < 3; c++) a.src[i][c] = p.chroma_format_idc || !c ? (q->final_b ? q->b[c] : q->a[c]) : nullptr;
-        }
-        a.dst = (char *)dst + (size_t)i0 * image_stride;
-        ohk_convert(&a, cv->format, cv->sample, m, e->stream);
-        HIPCHK(e, hipGetLastError());
-    }
-    return OH_OK;
-}
-
-/* ---------------- resizing into engine pictures (resize.hip) ---------------- */
-typedef __int128 i128;
-static i128 floor_div(i128 a, i128 b) { const i128 q = a / b; return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q; }   /* b > 0 */
-
-static bool resize_axis_ok(int S, int T, int filter, int phase)
-{
-    return S >= 1 && T >= 1 && S <= 16384 && T <= 16384 && (filter == OH_RESIZE_BILINEAR || filter == OH_RESIZE_BICUBIC) && (phase == 1 || phase == 2);
-}
-
-extern "C" int oh_resize_max_taps(int src_extent, int dst_extent, int filter)
-{
-    if (!resize_axis_ok(src_extent, dst_extent, filter, 2))
-        return OH_E_ARG;
-    const int64_t S = src_extent, T = dst_extent, D = 4 * std::max(S, T), R = filter == OH_RESIZE_BICUBIC ? 2 : 1;
-    return (int)std::min<int64_t>(S, (2 * R * D - 2) / (4 * T) + 1);          /* source samples strictly inside a span of 2RD */
-}
-
-/* the taps of one axis, all positions in units of 1/(4T) source samples */
-extern "C" int oh_resize_taps(int src_extent, int dst_extent, int filter, int phase, int32_t *first, int16_t *coeffs, int max_taps, int *n_taps)
-{
-    if (!first || !coeffs || !n_taps || !resize_axis_ok(src_extent, dst_extent, filter, phase) ||
-        max_taps < oh_resize_max_taps(src_extent, dst_extent, filter))
-        return OH_E_ARG;
-    const int64_t S = src_extent, T = dst_extent, p = phase, D = 4 * std::max(S, T), R = filter == OH_RESIZE_BICUBIC ? 2 : 1;
-    std::vector<i128> w;
-    std::vector<int64_t> k;
-    for (int64_t x = 0; x < T; x++) {
-        const int64_t c = (4 * x + p) * S;
-        int64_t lo = -(int64_t)floor_div(-(c - R * D - p * T + 1), 4 * T), hi = (int64_t)floor_div(c + R * D - p * T - 1, 4 * T);
-        lo = std::max<int64_t>(lo, 0); hi = std::min(hi, S - 1);
-        const int n = (int)(hi - lo + 1);
-        if (n < 1 || n > max_taps)
-            return OH_E_ARG;
-        w.assign((size_t)n, 0); k.assign((size_t)n, 0);
-        i128 sum = 0;
-        for (int j = 0; j < n; j++) {
-            const i128 v = std::llabs((4 * (lo + j) + p) * T - c), d = D;
-            w[j] = R == 1 ? d - v : v <= d ? 3 * v * v * v - 5 * v * v * d + 2 * d * d * d : -(v * v * v - 5 * v * v * d + 8 * v * d * d - 4 * d * d * d);
-            sum += w[j];
-        }
-        if (sum <= 0)
-            return OH_E_UNSUPPORTED;
-        int64_t ks = 0, ka = 0;
-        int best = 0;
-        for (int j = 0; j < n; j++) {
-            k[j] = (int64_t)floor_div(2 * w[j] * (1 << 14) + sum, 2 * sum);
-            ks += k[j];
-            if (k[j] > k[best]) best = j;
-        }
-        k[best] += (1 << 14) - ks;
-        for (int j = 0; j < n; j++) ka += std::llabs(k[j]);
-        if (ka >= 1 << 15)
-            return OH_E_UNSUPPORTED;
-        first[x] = (int32_t)lo; n_taps[x] = n;
-        int16_t *row = coeffs + (size_t)x * max_taps;
-        for (int j = 0; j < max_taps; j++) row[j] = j < n ? (int16_t)k[j] : 0;
-    }
-    return OH_OK;
-}
-
-namespace {
-struct ResizeAxis { std::vector<int32_t> first, cnt; std::vector<int16_t> k; int mt = 0; };
-}
-
-static int resize_axis(int S, int T, int filter, int phase, ResizeAxis *ax)
-{
-    ax->mt = oh_resize_max_taps(S, T, filter);
-    if (ax->mt < 1) return OH_E_ARG;
-    ax->first.resize((size_t)T); ax->cnt.resize((size_t)T); ax->k.resize((size_t)T * ax->mt);
-    return oh_resize_taps(S, T, filter, phase, ax->first.data(), ax->k.data(), ax->mt, ax->cnt.data());
-}
-
-extern "C" int oh_pics_resize(OhEngine *e, const int *src_ids, const int *dst_ids, int n, const OhResize *rs)
-{
-    if (!e || n < 0 || !rs || (n && (!src_ids || !dst_ids)))
-        return OH_E_ARG;
-    if (!n)
-        return OH_OK;
-    { const int rc = check_pics(e, src_ids, n, "oh_pics_resize"); if (rc) return rc; }
-    { const int rc = check_pics(e, dst_ids, n, "oh_pics_resize"); if (rc) return rc; }
-    const Pic *s0 = get_pic(e, src_ids[0]), *d0 = get_pic(e, dst_ids[0]);
-    for (int i = 1; i < n; i++)
-        if (memcmp(&get_pic(e, src_ids[i])->p, &s0->p, sizeof(OhPicParams)) || memcmp(&get_pic(e, dst_ids[i])->p, &d0->p, sizeof(OhPicParams)))
-            FAIL(e, OH_E_ARG, "oh_pics_resize: pictures %d -> %d have other params than pictures %d -> %d", src_ids[i], dst_ids[i], src_ids[0], dst_ids[0]);
-    {
-        std::vector<int> d(dst_ids, dst_ids + n), s(src_ids, src_ids + n);
-        std::sort(d.begin(), d.end()); std::sort(s.begin(), s.end());
-        if (std::adjacent_find(d.begin(), d.end()) != d.end())
-            FAIL(e, OH_E_ARG, "oh_pics_resize: a destination is listed twice");
-        for (int i = 0; i < n; i++)
-            if (std::binary_search(s.begin(), s.end(), d[i]))
-                FAIL(e, OH_E_ARG, "oh_pics_resize: picture %d is both source and destination", d[i]);
-    }
-    const OhPicParams &sp = s0->p, &dp = d0->p;
-    if (rs->filter != OH_RESIZE_BILINEAR && rs->filter != OH_RESIZE_BICUBIC)
-        FAIL(e, OH_E_ARG, "oh_pics_resize: filter %d (0 bilinear, 1 bicubic)", rs->filter);
-    const int cf = sp.chroma_format_idc, hs = cf == 1 || cf == 2, vs = cf == 1, sw = 1 << hs, sv = 1 << vs;
-    const OhWindow &w = rs->win;
-    const int W = sp.width - w.left - w.right, H = sp.height - w.top - w.bottom;
-    if (w.left < 0 || w.right < 0 || w.top < 0 || w.bottom < 0 || W <= 0 || H <= 0 || w.left % sw || w.right % sw || w.top % sv || w.bottom % sv)
-        FAIL(e, OH_E_ARG, "oh_pics_resize: window (%d,%d,%d,%d) of %dx%d: empty, or offsets not multiples of %dx%d", w.left, w.right, w.top, w.bottom,
-             sp.width, sp.height, sw, sv);
-    /* the size rules read the SOURCES' chroma format: a destination of another format is refused below */
-    if (rs->width < 1 || rs->height < 1 || rs->width > dp.width || rs->height > dp.height || rs->width % sw || rs->height % sv)
-        FAIL(e, OH_E_ARG, "oh_pics_resize: image %dx%d: below 1, above the destination's %dx%d, or not multiples of %dx%d", rs->width, rs->height,
-             dp.width, dp.height, sw, sv);
-    if (dp.bit_depth != sp.bit_depth || dp.chroma_format_idc != cf)
-        FAIL(e, OH_E_UNSUPPORTED, "oh_pics_resize: destinations of %d bit, chroma format %d; sources of %d bit, chroma format %d", dp.bit_depth,
-             dp.chroma_format_idc, sp.bit_depth, cf);
-    const int ncls = cf ? 2 : 1, bpp = sp.bit_depth > 8 ? 2 : 1;
-    for (int c = 0; c < ncls; c++) {
-        const int64_t ext[4] = { W >> (c ? hs : 0), rs->width >> (c ? hs : 0), H >> (c ? vs : 0), rs->height >> (c ? vs : 0) };
-        for (int a = 0; a < 4; a += 2)
-            if (ext[a] > OH_RESIZE_MAX_DOWN * ext[a + 1] || ext[a + 1] > OH_RESIZE_MAX_UP * ext[a])
-                FAIL(e, OH_E_UNSUPPORTED, "oh_pics_resize: %d -> %d samples is outside %d:1 .. 1:%d", (int)ext[a], (int)ext[a + 1], OH_RESIZE_MAX_DOWN,
-                     OH_RESIZE_MAX_UP);
-    }
-
-    OhResizeArgs a;
-    memset(&a, 0, sizeof(a));
-    a.np = cf ? 3 : 1; a.bd = sp.bit_depth;
-    ResizeAxis hx[2], vx[2];
-    size_t off[2][9], tab = 0;                                  /* h_first, h_cnt, h_k, v_first, v_cnt, v_off, v_k, h_f4, h_n4 in the table blob */
-    std::vector<int32_t> h_f4[2], h_n4[2];
-    std::vector<int32_t> v_lo[2], v_np[2], v_off[2];
-    uint64_t mid_pic = 0;
-    for (int c = 0; c < ncls; c++) {
-        OhResizeClass &k = a.k[c];
-        const int Sw = W >> (c ? hs : 0), Sh = H >> (c ? vs : 0);
-        k.x0 = w.left >> (c ? hs : 0); k.y0 = w.top >> (c ? vs : 0); k.sh = Sh;
-        k.tw = rs->width >> (c ? hs : 0); k.th = rs->height >> (c ? vs : 0);
-        k.cw = d0->w[c]; k.ch = d0->h[c];
-        k.src_pitch = s0->stride[c] * bpp; k.dst_pitch = d0->stride[c] * bpp;
-        k.mid_stride = (int32_t)align_up((size_t)k.tw + 1, 64);
-        int rc = resize_axis(Sw, k.tw, rs->filter, c && hs ? 1 : 2, &hx[c]);
-        if (!rc) rc = resize_axis(Sh, k.th, rs->filter, 2, &vx[c]);
-        if (rc) FAIL(e, rc, "oh_pics_resize: no taps for %dx%d -> %dx%d", Sw, Sh, k.tw, k.th);
-        /* horizontal pass: the widest power-of-two segment whose source columns fit a staged row, then as many rows as fit the LDS */
-        int span = 0;
-        for (k.segw = 256; ; k.segw >>= 1) {
-            span = 0;
-            for (int x = 0; x < k.tw; x += k.segw) {
-                const int xl = std::min(x + k.segw, k.tw) - 1;
-                span = std::max(span, hx[c].first[xl] + hx[c].cnt[xl] - hx[c].first[x]);
-            }
-            if (span <= OH_RESIZE_SPAN || k.segw == 1) break;
-        }
-        if (span > OH_RESIZE_SPAN)
-            FAIL(e, OH_E_UNSUPPORTED, "oh_pics_resize: one image column reads %d source columns (at most %d)", span, OH_RESIZE_SPAN);
-        k.row_bytes = (int32_t)align_up((size_t)span * bpp, 16) + 32;
-        k.rpw = std::max(1, std::min({ (int)OH_RESIZE_HROWS, OH_RESIZE_LDS / k.row_bytes, Sh }));
-        k.h_stride = (int32_t)align_up((size_t)k.tw, 32);
-        /* the taps of a column as QUADS of source columns that start at a multiple of four columns of the plane (an 8- or 4-byte
-         * aligned LDS read): zero coefficients in front of the first tap and behind the last */
-        int quads = 0;
-        for (int x = 0; x < k.tw; x++) {
-            const int lead = (k.x0 + hx[c].first[x]) & 3;
-            h_f4[c].push_back(hx[c].first[x] - lead);
-            h_n4[c].push_back((lead + hx[c].cnt[x] + 3) / 4);
-            quads = std::max(quads, h_n4[c].back());
-        }
-        k.h_groups = (Sh + k.rpw - 1) / k.rpw;
-        /* vertical pass: per group of image rows the intermediate rows it reads, in pairs */
-        k.v_groups = (k.th + OH_RESIZE_VROWS - 1) / OH_RESIZE_VROWS;
-        int32_t pairs = 0;
-        for (int g = 0; g < k.v_groups; g++) {
-            const int y0 = g * OH_RESIZE_VROWS, y1 = std::min(y0 + OH_RESIZE_VROWS, k.th) - 1;
-            const int lo = vx[c].first[y0], np = (vx[c].first[y1] + vx[c].cnt[y1] - lo + 1) / 2;
-            v_lo[c].push_back(lo); v_np[c].push_back(np); v_off[c].push_back(pairs);
-            pairs += np;
-        }
-        const size_t sz[9] = { (size_t)k.tw * 4, (size_t)k.tw * 4, (size_t)quads * k.h_stride * 8, (size_t)k.v_groups * 4, (size_t)k.v_groups * 4,
-                               (size_t)k.v_groups * 4, (size_t)pairs * OH_RESIZE_VROWS * 4, (size_t)k.tw * 4, (size_t)k.tw * 4 };
-        for (int i = 0; i < 9; i++) { off[c][i] = tab; tab += align_up(sz[i], 256); }
-        for (int pl = c ? 1 : 0; pl < (c ? 3 : 1); pl++) {
-            a.mid_plane[pl] = mid_pic;
-            mid_pic += align_up((size_t)(Sh + 1) * k.mid_stride, 128);     /* a spare row: the odd half of a group's last pair */
-        }
-    }
-    a.mid_pic = mid_pic;
-    const size_t mid_bytes = (size_t)mid_pic * 2;
-    const int per_set = (int)std::max<size_t>(1, std::min<size_t>(OH_RESIZE_MAX_PICS, ((size_t)512 << 20) / mid_bytes));
-    const size_t need = tab + (size_t)std::min(n, per_set) * mid_bytes;
-    HIPCHK(e, hipSetDevice(e->device));
-    if (need > e->resize_dev_bytes) {
-        HIPCHK(e, hipStreamSynchronize(e->stream));              /* launches of earlier calls still use the old buffer */
-        if (e->resize_dev) (void)hipFree(e->resize_dev);
-        e->resize_dev = nullptr; e->resize_dev_bytes = 0;
-        const size_t want = align_up(need, (size_t)1 << 20);
-        HIPCHK(e, hipMalloc(&e->resize_dev, want));
-        e->resize_dev_bytes = want;
-    }
-    /* the tables: built in a pinned buffer of the pool, copied on the engine stream — behind the launches of an earlier call that
-     * read the device copy, in front of this call's */
-    OhEngine::Stage *sg = stage_acquire(e, tab);
-    if (!sg)
-        FAIL(e, OH_E_NOMEM, "oh_pics_resize: no staging buffer for %zu bytes of tap tables", tab);
-    char *h = (char *)sg->p, *d = (char *)e->resize_dev;
-    memset(h, 0, tab);
-    for (int c = 0; c < ncls; c++) {
-        OhResizeClass &k = a.k[c];
-        memcpy(h + off[c][0], hx[c].first.data(), (size_t)k.tw * 4);
-        memcpy(h + off[c][1], hx[c].cnt.data(), (size_t)k.tw * 4);
-        memcpy(h + off[c][7], h_f4[c].data(), (size_t)k.tw * 4);
-        memcpy(h + off[c][8], h_n4[c].data(), (size_t)k.tw * 4);
-        int16_t *hk = (int16_t *)(h + off[c][2]);                /* [quad][column][4] */
-        for (int x = 0; x < k.tw; x++) {
-            const int lead = hx[c].first[x] - h_f4[c][x];
-            for (int j = 0; j < hx[c].cnt[x]; j++)
-                hk[((size_t)((lead + j) / 4) * k.h_stride + x) * 4 + (lead + j) % 4] = hx[c].k[(size_t)x * hx[c].mt + j];
-        }
-        memcpy(h + off[c][3], v_lo[c].data(), (size_t)k.v_groups * 4);
-        memcpy(h + off[c][4], v_np[c].data(), (size_t)k.v_groups * 4);
-        memcpy(h + off[c][5], v_off[c].data(), (size_t)k.v_groups * 4);
-        int16_t *vk = (int16_t *)(h + off[c][6]);                /* [pair][image row of the group][even row, odd row] */
-        for (int y = 0; y < k.th; y++) {
-            const int g = y / OH_RESIZE_VROWS, i = y % OH_RESIZE_VROWS;
-            for (int j = 0; j < vx[c].cnt[y]; j++) {
-                const int r = vx[c].first[y] + j - v_lo[c][g];
-                vk[(((size_t)v_off[c][g] + r / 2) * OH_RESIZE_VROWS + i) * 2 + (r & 1)] = vx[c].k[(size_t)y * vx[c].mt + j];
-            }
-        }
-        k.h_first = (const int32_t *)(d + off[c][0]); k.h_cnt = (const int32_t *)(d + off[c][1]); k.h_k = (const int16_t *)(d + off[c][2]);
-        k.h_f4 = (const int32_t *)(d + off[c][7]); k.h_n4 = (const int32_t *)(d + off[c][8]);
-        k.v_first = (const int32_t *)(d + off[c][3]); k.v_cnt = (const int32_t *)(d + off[c][4]); k.v_off = (const int32_t *)(d + off[c][5]);
-        k.v_k = (const int32_t *)(d + off[c][6]);
-    }
-    HIPCHK(e, hipMemcpyAsync(d, h, tab, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipEventRecord(sg->done, e->stream));
+    HIPCHK(e, hipEventRecord(sg->done, st));
     sg->busy = true;
-    a.mid = (int16_t *)(d + tab);
-    const int pad = rs->width < dp.width || rs->height < dp.height;
-    for (int i0 = 0; i0 < n; i0 += per_set) {
-        const int m = std::min(n - i0, per_set);
-        for (int i = 0; i < m; i++) {
-            const Pic *s = get_pic(e, src_ids[i0 + i]);
-            Pic *q = get_pic(e, dst_ids[i0 + i]);
-            for (int c = 0; c < a.np; c++) { a.src[i][c] = s->final_b ? s->b[c] : s->a[c]; a.dst[i][c] = q->a[c]; }
-            q->final_b = false;                                  /* the image is a finished picture in half 0 */
-            q->done_seq = 0;
-        }
-        ohk_resize(&a, m, pad, e->stream);
-        HIPCHK(e, hipGetLastError());
-    }
-    return OH_OK;
-}
-
-extern "C" int oh_pic_device_planes(OhEngine *e, int pic_id, void *planes[3], int32_t stride[3], int32_t width[3], int32_t height[3])
-{
-    if (!e)
-        return OH_E_ARG;
-    Pic *p = get_pic(e, pic_id);
-    if (!p)
-        FAIL(e, OH_E_ARG, "unknown picture %d", pic_id);
-    for (int c = 0; c < 3; c++) {
-        planes[c] = p->final_b ? p->b[c] : p->a[c];
-        stride[c] = p->stride[c]; width[c] = p->w[c]; height[c] = p->h[c];
-    }
     return OH_OK;
 }
 

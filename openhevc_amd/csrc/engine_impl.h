@@ -1,0 +1,239 @@
+/*
+ * engine_impl.h — what the engine's translation units share: the engine and picture structures, the error macros and the few
+ * helpers more than one of them uses.  engine.hip: engine and picture lifecycle, work-list hand-over, passes, profiling;
+ * engine_pics.hip: plane transfers, hashes, conversion and resizing of finished pictures; engine_shvc.hip: SHVC up-sampling.
+ * Internal: the C ABI is include/ohevc_hip.h.
+ */
+#ifndef OHEVC_ENGINE_IMPL_H
+#define OHEVC_ENGINE_IMPL_H
+
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <algorithm>
+#include <chrono>
+#include <string>
+#include <condition_variable>
+#include <mutex>
+#include <thread>
+#include <vector>
+
+#include "../../include/ohevc_hip.h"
+#include "dev_frame.h"
+#include "kernels.h"
+
+#define OH_INTERNAL __attribute__((visibility("hidden")))    /* shared between the engine's files, not part of the library's ABI */
+
+struct Pic {
+    bool        used = false;
+    OhPicParams p{};
+    void       *base = nullptr;          /* one allocation: planes A (recon/deblock) then B (SAO out) */
+    bool        owned = true;            /* false: caller-owned memory (oh_pic_wrap)                   */
+    void       *a[3] = {}, *b[3] = {};
+    int32_t     stride[3] = {}, w[3] = {}, h[3] = {};
+    bool        final_b = false;         /* which buffer holds the finished picture */
+    uint32_t    gen = 0;                 /* bumped whenever the id is (re)installed: uploaded work lists remember it */
+    uint64_t    done_seq = 0;            /* the batch that last reconstructed the picture (OhEngine::batch_ev ring); 0: written by something else, or never */
+};
+
+struct EventSet { hipEvent_t ev[OH_N_PASSES + 1]; int n_frames = 1; };
+
+struct OhDevFrame {
+    void      *arena = nullptr;
+    size_t     arena_bytes = 0;
+    DevFrame  *d = nullptr;
+    OhPicParams p{};
+    uint32_t   tu_cnt[4] = { 0, 0, 0, 0 };
+    uint32_t   n_cross = 0;
+    bool       has_sao = false;
+    int        cur_pic = -1;      /* engine id of the picture the list reconstructs */
+    uint32_t   cur_gen = 0;
+    /* reference slots as uploaded: picture id, its generation, and which half DevFrame.refs[] points at — looked up again at
+     * every execute (a reference finished or received AFTER the upload moves to its other half: oh_pic_set_final_half, SAO) */
+    int        ref_id[OH_MAX_REFS];
+    uint32_t   ref_gen[OH_MAX_REFS];
+    uint8_t    ref_half[OH_MAX_REFS];
+    uint16_t   ref_used = 0;      /* bit i: some PU predicts from slot i */
+    hipEvent_t ready = nullptr;   /* recorded on the copy stream behind the work list's H2D copy, preparation kernels and summary */
+    bool       waited = false;    /* the engine stream already waits for `ready` */
+    void      *sum_host = nullptr;/* pinned: the DevSummary the preparation kernels left */
+    bool       summary_read = false;
+    void      *sum_dev = nullptr; /* the summary in the arena */
+    OhPrepCounts cnt{};           /* sizes of the preparation launches */
+    uint32_t   prep_err = 0;
+    uint32_t   intra_area64 = 0, max_passes = 0;   /* from the summary: samples of the intra blocks / 64; wave passes of the heaviest CTU */
+    /* from the summary, over the schedule entries: what lays out the staged intra launch */
+    uint32_t   max_items = 0, max_sub = 0, max_res = 0;
+    bool       res_scattered = false;             /* some CTU's residual span is not contiguous (not stageable in LDS) */
+    uint64_t   sum_items = 0, sum_sub = 0;
+    const struct OhEngine *owner = nullptr;   /* picture ids and arenas belong to one engine */
+};
+
+/* helper threads for the one host copy of the hand-over (the work list into a pinned staging buffer): the lists of a 4K picture are
+ * ~4 MB, 0.22 ms for one thread — most of what the hand-over costs the decoder's thread.  The calling thread keeps a share. */
+struct CopyJob { char *dst; const char *src; size_t n; bool pack; };
+OH_INTERNAL void pack_bs(uint8_t *dst, const uint8_t *src, size_t n);
+struct CopyPool {
+    std::vector<std::thread> th;
+    std::mutex mu;
+    std::condition_variable cv, done_cv;
+    const std::vector<CopyJob> *jobs = nullptr;
+    int pending = 0;
+    uint64_t gen = 0;
+    bool stop = false;
+    static void run_share(const std::vector<CopyJob> &jobs, int share, int shares)
+    {
+        for (size_t i = (size_t)share; i < jobs.size(); i += (size_t)shares) {
+            const CopyJob &j = jobs[i];
+            if (j.pack) pack_bs((uint8_t *)j.dst, (const uint8_t *)j.src, j.n);
+            else memcpy(j.dst, j.src, j.n);
+        }
+    }
+    void worker(int k)
+    {
+        uint64_t seen = 0;
+        for (;;) {
+            const std::vector<CopyJob> *my;
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return stop || gen != seen; });
+                if (stop) return;
+                seen = gen;
+                my = jobs;
+            }
+            run_share(*my, k + 1, (int)th.size() + 1);
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                if (--pending == 0) done_cv.notify_one();
+            }
+        }
+    }
+    void start(int n) { for (int k = 0; k < n; k++) th.emplace_back(&CopyPool::worker, this, k); }
+    void run(const std::vector<CopyJob> &j)                    /* returns when every job has been copied */
+    {
+        if (th.empty()) { run_share(j, 0, 1); return; }
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            jobs = &j; pending = (int)th.size(); gen++;
+        }
+        cv.notify_all();
+        run_share(j, 0, (int)th.size() + 1);
+        std::unique_lock<std::mutex> lk(mu);
+        done_cv.wait(lk, [&] { return pending == 0; });
+    }
+    ~CopyPool()
+    {
+        { std::lock_guard<std::mutex> lk(mu); stop = true; }
+        cv.notify_all();
+        for (auto &t : th) t.join();
+    }
+};
+
+struct OhEngine {
+    int         device = 0;
+    int         n_cu = 256;              /* compute units of the device */
+    hipStream_t stream = nullptr;
+    bool        own_stream = true;
+    std::vector<Pic> pics;
+    std::string err;
+    int         profile = 0;             /* 0 off, 1 events between passes, 2 also around every batch's intra launches */
+    std::vector<EventSet> ev_pool, ev_pending;
+    std::vector<hipEvent_t> lev_pool, lev_pending;   /* event pairs around every batch's intra launches (profile mode) */
+    double      intra_launch_ms = 0;
+    uint64_t    intra_launches = 0;
+    double      pass_ms[OH_N_PASSES] = {};
+    uint64_t    executes = 0;
+    std::vector<OhDevFrame *> deferred;
+    uint32_t    pic_gen = 0;
+    /* upload path: pinned staging buffers and device arenas are recycled (hipHostMalloc / hipMalloc cost milliseconds);
+     * a staging buffer is busy until the H2D copy that reads it has passed `done` */
+    struct Stage { void *p; size_t bytes; hipEvent_t done; bool busy; };
+    std::vector<Stage> stages;
+    /* work lists travel on their own stream so that the copy of picture n+1 overlaps the passes of picture n; the engine stream
+     * waits for a list's `ready` event before the first kernel that reads it, and a recycled arena is not overwritten before
+     * the engine stream has passed the event recorded when it was released */
+    hipStream_t copy_stream = nullptr;
+    struct Arena { void *p; size_t bytes; hipEvent_t free_ev; };
+    std::vector<Arena> arenas;               /* free device arenas */
+    uint64_t    arenas_alive = 0, arena_bytes_alive = 0;      /* device arenas allocated and not freed (pooled or holding a work list): oh_engine_memory */
+    std::vector<hipEvent_t> sync_events;     /* pool of timing-disabled events (ready / free_ev) */
+    std::vector<void *> sum_pool;            /* pinned blocks of sizeof(DevSummary) bytes */
+    double      host_ms[OH_N_HOST_TIMES] = {};   /* where the host time of the hand-over path goes (oh_engine_host_times) */
+    uint64_t    host_calls[OH_N_HOST_TIMES] = {};
+    uint64_t    up_bytes = 0;                    /* bytes of work lists sent over PCIe since the last reset */
+    uint64_t   *dbg = nullptr;           /* diagnostics (OHEVC_STAMPS=1 + a -DOH_STAMPS build) */
+    /* what a kernel can tell the host when it cannot go on (the table slots and the passes have no error channel: hevcdsp.h's slots
+     * return void): four words of pinned host memory, [0] OH_KE_* of the first failure, [1] picture id, [2] schedule
+     * entry; read by everything that waits for the stream (kernel_error) */
+    /* a ring of events, one behind every executed batch: a download of a finished picture waits for ITS batch (on the download
+     * stream), not for everything enqueued since — a decoder fetches the picture it outputs while the passes of the pictures it
+     * submitted later keep running */
+    enum { BATCH_RING = 64 };
+    hipEvent_t  batch_ev[BATCH_RING] = {};
+    uint64_t    batch_seq = 0;
+    hipStream_t dl_stream = nullptr;
+    /* ticket counters of the one-launch intra forms: a ring of pairs (direct, staged) in HBM; a batch uses the next pair, cleared on
+     * the stream in front of its launches (a pair comes round again 128 batches later: long after its launch has drained) */
+    enum { TICKET_RING = 128, TICKET_WORDS = 2 * OH_MAX_BATCH * 32 };      /* per batch: (direct, staged) x pictures, a cache line each (intra.hip: OH_TICKET_STRIDE) */
+    uint32_t   *tickets = nullptr;
+    uint64_t    ticket_seq = 0;
+    CopyPool   *copiers = nullptr;      /* created with the first hand-over (OHEVC_COPY_THREADS helpers, default 2) */
+    /* output fetch (oh_pic_download_start / oh_download_finish): its own pinned buffers and copy helpers, usable while another thread
+     * drives the engine */
+    std::mutex  dl_mu, dl_copy_mu;
+    std::vector<Stage *> dl_stages;
+    CopyPool   *dl_copiers = nullptr;   /* created with the first fetch (OHEVC_FETCH_THREADS helpers, default 3) */
+    std::vector<CopyJob> dl_jobs;
+    double      dl_wait_ms = 0, dl_copy_ms = 0;     /* OHEVC_FETCH_TIMING: where the time of the fetches went (printed when the engine is destroyed) */
+    uint64_t    dl_count = 0;
+    std::vector<CopyJob> copy_jobs;
+    uint32_t   *kerr = nullptr;
+    /* grow-only device scratch (engine_pics.hip: scratch_reserve); reallocated only while the engine stream is idle */
+    struct Scratch { void *p = nullptr; size_t bytes = 0; };
+    Scratch     hash_dev;                /* oh_pics_hash (CRC / checksum): the job table, its tasks and their values in HBM */
+    Scratch     resize_dev;              /* oh_pics_resize: the tap tables of the call, then the int16 intermediate of one launch set */
+    uint32_t    spin_limit = 1u << 22;   /* polls (with s_sleep between them, ~1 s in all) before a waiting workgroup gives up; OHEVC_SPIN_LIMIT */
+};
+
+#define HIPCHK(e, call)                                                                           \
+    do {                                                                                          \
+        hipError_t rc_ = (call);                                                                  \
+        if (rc_ != hipSuccess) {                                                                  \
+            char buf_[512];                                                                       \
+            snprintf(buf_, sizeof(buf_), "%s failed: %s (%s:%d)", #call, hipGetErrorString(rc_), __FILE__, __LINE__); \
+            (e)->err = buf_;                                                                      \
+            return OH_E_HIP;                                                                      \
+        }                                                                                         \
+    } while (0)
+
+#define FAIL(e, code, ...)                                                                        \
+    do {                                                                                          \
+        char buf_[512];                                                                           \
+        snprintf(buf_, sizeof(buf_), __VA_ARGS__);                                                \
+        (e)->err = buf_;                                                                          \
+        return (code);                                                                            \
+    } while (0)
+
+static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+struct HostTimer {                       /* adds the scope's wall time to one slot of OhEngine::host_ms */
+    OhEngine *e; int slot; std::chrono::steady_clock::time_point t0;
+    HostTimer(OhEngine *e_, int slot_);
+    ~HostTimer();
+};
+enum { OH_MAX_STAGES = 48 };             /* pinned staging buffers per engine before the host is made to wait */
+
+/* the planes of the half that holds the finished picture, and the bytes of one of its samples */
+static inline void *const *final_planes(const Pic *p) { return p->final_b ? p->b : p->a; }
+static inline int sample_bytes(int bit_depth) { return bit_depth > 8 ? 2 : 1; }
+
+OH_INTERNAL int kernel_error(OhEngine *e);
+OH_INTERNAL Pic *get_pic(OhEngine *e, int id);
+OH_INTERNAL int check_pics(OhEngine *e, const int *pic_ids, int n, const char *who);
+OH_INTERNAL bool stage_create(OhEngine::Stage *c, size_t bytes);
+OH_INTERNAL OhEngine::Stage *stage_acquire(OhEngine *e, size_t bytes);
+OH_INTERNAL OhEngine::Stage *stage_list(OhEngine *e, const void *list, size_t bytes);
+OH_INTERNAL int stage_in_use(OhEngine *e, OhEngine::Stage *sg, hipStream_t st);
+
+#endif

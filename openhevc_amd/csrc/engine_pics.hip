@@ -1,0 +1,795 @@
+/*
+ * engine_pics.hip — what the engine does with finished pictures beside the reconstruction path (host side; the kernels are md5.hip,
+ * hash.hip, convert.hip and resize.hip): plane upload and download, the two-phase window fetch, picture hashes, conversion to
+ * YUV / RGB images and resizing into engine pictures.
+ */
+#include "engine_impl.h"
+
+/* at least `bytes` of device scratch, grow-only in 1 MiB steps.  Growing frees the old block: the caller has made sure that nothing
+ * enqueued still uses it. */
+static int scratch_reserve(OhEngine *e, OhEngine::Scratch *s, size_t bytes)
+{
+    if (bytes <= s->bytes)
+        return OH_OK;
+    if (s->p) (void)hipFree(s->p);
+    s->p = nullptr; s->bytes = 0;
+    const size_t want = align_up(bytes, (size_t)1 << 20);
+    HIPCHK(e, hipMalloc(&s->p, want));
+    s->bytes = want;
+    return OH_OK;
+}
+
+/* a crop window of a picture: offsets not negative, something left and — aligned — the offsets multiples of the chroma sub-sampling.
+ * false: *why says what is wrong. */
+static bool crop_window_ok(const OhPicParams *p, const OhWindow &w, bool aligned, std::string *why)
+{
+    const int cf = p->chroma_format_idc, sw = aligned && (cf == 1 || cf == 2) ? 2 : 1, sh = aligned && cf == 1 ? 2 : 1;
+    const int W = p->width - w.left - w.right, H = p->height - w.top - w.bottom;
+    if (w.left >= 0 && w.right >= 0 && w.top >= 0 && w.bottom >= 0 && W > 0 && H > 0 && !(w.left % sw) && !(w.right % sw) && !(w.top % sh) && !(w.bottom % sh))
+        return true;
+    char buf[256];
+    if (aligned)
+        snprintf(buf, sizeof(buf), "window (%d,%d,%d,%d) of %dx%d: empty, or offsets not multiples of %dx%d", w.left, w.right, w.top, w.bottom,
+                 p->width, p->height, sw, sh);
+    else
+        snprintf(buf, sizeof(buf), "window (%d,%d,%d,%d) leaves nothing of %dx%d", w.left, w.right, w.top, w.bottom, p->width, p->height);
+    *why = buf;
+    return false;
+}
+
+/* the first of n pictures (ids checked) whose params differ from those of the first; n: all are equal */
+static int first_other_params(OhEngine *e, const int *pic_ids, int n)
+{
+    for (int i = 1; i < n; i++)
+        if (memcmp(&get_pic(e, pic_ids[i])->p, &get_pic(e, pic_ids[0])->p, sizeof(OhPicParams)))
+            return i;
+    return n;
+}
+
+extern "C" int oh_pic_upload(OhEngine *e, int pic_id, const uint8_t *const planes[3], const ptrdiff_t strides[3])
+{
+    if (!e || !planes || !strides)
+        return OH_E_ARG;
+    Pic *p = get_pic(e, pic_id);
+    if (!p)
+        FAIL(e, OH_E_ARG, "oh_pic_upload: unknown picture %d", pic_id);
+    HIPCHK(e, hipSetDevice(e->device));
+    const size_t bpp = sample_bytes(p->p.bit_depth);
+    for (int c = 0; c < (p->p.chroma_format_idc ? 3 : 1); c++)
+        HIPCHK(e, hipMemcpy2DAsync(p->a[c], (size_t)p->stride[c] * bpp, planes[c], (size_t)strides[c], (size_t)p->w[c] * bpp,
+                                   (size_t)p->h[c], hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    p->final_b = false;
+    p->done_seq = 0;
+    return OH_OK;
+}
+
+extern "C" int oh_pic_download(OhEngine *e, int pic_id, uint8_t *const planes[3], const ptrdiff_t strides[3])
+{
+    if (!e || !planes || !strides)
+        return OH_E_ARG;
+    Pic *p = get_pic(e, pic_id);
+    if (!p)
+        FAIL(e, OH_E_ARG, "oh_pic_download: unknown picture %d", pic_id);
+    HIPCHK(e, hipSetDevice(e->device));
+    const size_t bpp = sample_bytes(p->p.bit_depth);
+    for (int c = 0; c < (p->p.chroma_format_idc ? 3 : 1); c++)
+        HIPCHK(e, hipMemcpy2DAsync(planes[c], (size_t)strides[c], final_planes(p)[c], (size_t)p->stride[c] * bpp,
+                                   (size_t)p->w[c] * bpp, (size_t)p->h[c], hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    { const int ke = kernel_error(e); if (ke) return ke; }     /* a kernel that gave up: these samples are not the picture */
+    return OH_OK;
+}
+
+/* Output side of the path: the conformance-window crop of ff_hevc_output_frame (hevc_refs.c:248-254:
+ * plane pointers advanced by (left >> hshift, top >> vshift)) followed by libOpenHevcGetOutputCpy's packed row copies
+ * (openHevcWrapper.c:353-398: `height >> vshift` rows of `(width >> hshift) << pixel_shift` bytes, width / height = the cropped
+ * size).  One strided device-to-pinned copy per plane, one wait, then the rows go to the caller's pitches. */
+/* The output fetch in two halves, for a decoder whose threads share ONE engine behind a lock (the drop-in library: frame-thread
+ * workers hand pictures over while the application's thread fetches the one that was released):
+ *   oh_pic_download_start   (under the caller's engine lock, microseconds) validates, takes a pinned DOWNLOAD staging buffer — a list
+ *                           of its own, guarded by its own mutex — and enqueues the strided device-to-host copies behind the batch
+ *                           that finished the picture (download stream), then records an event;
+ *   oh_download_finish      (NO engine lock needed, any thread) waits for that event, copies the rows into the caller's planes with
+ *                           the download copy helpers, and gives the staging buffer back.
+ * oh_pic_download_window is the two in a row. */
+struct OhDownload {
+    OhEngine::Stage *sg;
+    size_t row[3], rows[3], off[3];
+    int np;
+};
+
+extern "C" int oh_pic_download_start(OhEngine *e, int pic_id, const OhWindow *win, OhDownload **out)
+{
+    if (!e || !win || !out)
+        return OH_E_ARG;
+    *out = nullptr;
+    Pic *p = get_pic(e, pic_id);
+    if (!p)
+        FAIL(e, OH_E_ARG, "oh_pic_download_window: unknown picture %d", pic_id);
+    std::string why;
+    if (!crop_window_ok(&p->p, *win, false, &why))
+        FAIL(e, OH_E_ARG, "oh_pic_download_window: %s", why.c_str());
+    const int W = p->p.width - win->left - win->right, H = p->p.height - win->top - win->bottom;
+    HIPCHK(e, hipSetDevice(e->device));
+    const size_t bpp = sample_bytes(p->p.bit_depth);
+    OhDownload d;
+    d.np = p->p.chroma_format_idc ? 3 : 1;
+    size_t total = 0;
+    for (int c = 0; c < d.np; c++) {
+        const int hs = oh_hshift(&p->p, c), vs = oh_vshift(&p->p, c);
+        d.row[c] = (size_t)(W >> hs) * bpp; d.rows[c] = (size_t)(H >> vs);
+        d.off[c] = total; total += align_up(d.row[c] * d.rows[c], 256);
+    }
+    {   /* a free download buffer that fits, else a new one (a decoder has one or two fetches in flight) */
+        std::lock_guard<std::mutex> lk(e->dl_mu);
+        d.sg = nullptr;
+        for (auto *c : e->dl_stages)
+            if (!c->busy && c->bytes >= total && (!d.sg || c->bytes < d.sg->bytes)) d.sg = c;
+        if (!d.sg) {
+            OhEngine::Stage *c = new OhEngine::Stage();
+            if (!stage_create(c, total)) {
+                delete c;
+                FAIL(e, OH_E_NOMEM, "hipHostMalloc(%zu) failed", total);
+            }
+            e->dl_stages.push_back(c);
+            d.sg = c;
+        }
+        d.sg->busy = true;
+    }
+    /* a picture a batch of this engine finished, and whose event is still in the ring: the copies run on the download stream behind
+     * THAT batch; anything else (uploaded, up-sampled, received from another GPU, long ago): behind everything on the engine stream */
+    hipStream_t dl = e->stream;
+    if (p->done_seq && e->batch_seq - p->done_seq < OhEngine::BATCH_RING - 1) {
+        if (!e->dl_stream) HIPCHK(e, hipStreamCreateWithFlags(&e->dl_stream, hipStreamNonBlocking));
+        HIPCHK(e, hipStreamWaitEvent(e->dl_stream, e->batch_ev[p->done_seq % OhEngine::BATCH_RING], 0));
+        dl = e->dl_stream;
+    }
+    hipError_t he = hipSuccess;
+    for (int c = 0; c < d.np && he == hipSuccess; c++) {
+        const int hs = oh_hshift(&p->p, c), vs = oh_vshift(&p->p, c);
+        const uint8_t *src = (const uint8_t *)final_planes(p)[c] + ((size_t)(win->top >> vs) * p->stride[c] + (size_t)(win->left >> hs)) * bpp;
+        he = hipMemcpy2DAsync((char *)d.sg->p + d.off[c], d.row[c], src, (size_t)p->stride[c] * bpp, d.row[c], d.rows[c], hipMemcpyDeviceToHost, dl);
+    }
+    if (he == hipSuccess) he = hipEventRecord(d.sg->done, dl);
+    if (he != hipSuccess) {
+        std::lock_guard<std::mutex> lk(e->dl_mu);
+        d.sg->busy = false;
+        FAIL(e, OH_E_HIP, "oh_pic_download_window: %s", hipGetErrorString(he));
+    }
+    *out = new OhDownload(d);
+    return OH_OK;
+}
+
+extern "C" int oh_download_finish(OhEngine *e, OhDownload *d, uint8_t *const planes[3], const ptrdiff_t strides[3])
+{
+    if (!e || !d)
+        return OH_E_ARG;
+    int rc = OH_OK;
+    if (!planes || !strides)
+        rc = OH_E_ARG;
+    for (int c = 0; c < d->np && !rc; c++)
+        if (!planes[c] || (ptrdiff_t)d->row[c] > strides[c])
+            rc = OH_E_ARG;
+    const auto t_w0 = std::chrono::steady_clock::now();
+    const hipError_t he = hipEventSynchronize(d->sg->done);    /* also when the arguments are bad: the buffer goes back only after its copy */
+    const auto t_w1 = std::chrono::steady_clock::now();
+    if (!rc && he != hipSuccess) rc = OH_E_HIP;
+    if (!rc) rc = kernel_error(e);                             /* a kernel that gave up: these samples are not the picture */
+    if (!rc) {
+        std::lock_guard<std::mutex> lk(e->dl_copy_mu);         /* one fetch at a time uses the helpers */
+        if (!e->dl_copiers) {
+            const char *v = getenv("OHEVC_FETCH_THREADS");
+            const int n = v ? atoi(v) : 3;
+            e->dl_copiers = new CopyPool();
+            e->dl_copiers->start(n < 0 ? 0 : (n > 15 ? 15 : n));
+        }
+        /* pieces of at most 1 MiB (packed planes) or single rows (pitched planes), dealt round-robin to the helpers and this thread */
+        std::vector<CopyJob> &jobs = e->dl_jobs;
+        jobs.clear();
+        for (int c = 0; c < d->np; c++) {
+            const char *src = (const char *)d->sg->p + d->off[c];
+            if ((size_t)strides[c] == d->row[c]) {
+                const size_t n = d->row[c] * d->rows[c], piece = (size_t)1 << 20;
+                for (size_t o = 0; o < n; o += piece) jobs.push_back(CopyJob{ (char *)planes[c] + o, src + o, n - o < piece ? n - o : piece, false });
+            } else {
+                for (size_t y = 0; y < d->rows[c]; y++) jobs.push_back(CopyJob{ (char *)planes[c] + (ptrdiff_t)y * strides[c], src + y * d->row[c], d->row[c], false });
+            }
+        }
+        e->dl_copiers->run(jobs);
+        e->dl_wait_ms += std::chrono::duration<double, std::milli>(t_w1 - t_w0).count();
+        e->dl_copy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_w1).count();
+        e->dl_count++;
+    }
+    {
+        std::lock_guard<std::mutex> lk(e->dl_mu);
+        d->sg->busy = false;
+    }
+    delete d;
+    return rc;
+}
+
+extern "C" int oh_pic_download_window(OhEngine *e, int pic_id, const OhWindow *win, uint8_t *const planes[3], const ptrdiff_t strides[3])
+{
+    if (!e || !win || !planes || !strides)
+        return OH_E_ARG;
+    OhDownload *d = nullptr;
+    const int rc = oh_pic_download_start(e, pic_id, win, &d);
+    if (rc)
+        return rc;
+    const int rc2 = oh_download_finish(e, d, planes, strides);
+    if (rc2 == OH_E_ARG)
+        FAIL(e, OH_E_ARG, "oh_pic_download_window: a destination plane is missing or its pitch is smaller than a row");
+    if (rc2 == OH_E_HIP)
+        FAIL(e, OH_E_HIP, "oh_pic_download_window: the device-to-host copy failed");
+    return rc2;
+}
+
+/* the planes of n pictures (ids checked) as hash jobs, the half that holds the final samples; slot[i * 3 + c]: the job of plane c of
+ * picture i, -1 for the planes a monochrome picture lacks.  Returns the number of jobs. */
+static int plane_jobs(OhEngine *e, const int *pic_ids, int n, OhMd5Job *jobs, int *slot)
+{
+    int nj = 0;
+    for (int i = 0; i < n; i++) {
+        const Pic *p = get_pic(e, pic_ids[i]);
+        const uint32_t bpp = sample_bytes(p->p.bit_depth);
+        for (int c = 0; c < 3; c++) {
+            slot[i * 3 + c] = -1;
+            if (c && !p->p.chroma_format_idc)
+                continue;
+            OhMd5Job &j = jobs[nj];
+            j.base = final_planes(p)[c];
+            j.pitch = (uint32_t)p->stride[c] * bpp; j.row_bytes = (uint32_t)p->w[c] * bpp; j.rows = (uint32_t)p->h[c]; j.bps = bpp;
+            slot[i * 3 + c] = nj++;
+        }
+    }
+    return nj;
+}
+
+/* Picture hash on the GPU: the three plane digests of the reference's SEI check (hevc.c:4146-4162 over calc_md5,
+ * hevc.c:4623-4638: the whole coded planes, sps->width x sps->height and the chroma sizes, packed rows) for n finished pictures in one
+ * launch of one chain per (picture, plane) — md5.hip.  48 bytes per picture come back instead of the picture.  Waits for the engine
+ * stream.  digests: n x 3 x 16 bytes (monochrome: planes 1, 2 zero).  pic_ids checked. */
+static int pics_md5(OhEngine *e, const int *pic_ids, int n, uint8_t *digests)
+{
+    HIPCHK(e, hipSetDevice(e->device));
+    const size_t jobs_bytes = align_up((size_t)n * 3 * sizeof(OhMd5Job), 256);
+    OhEngine::Stage *sg = stage_acquire(e, jobs_bytes + (size_t)n * 48);
+    if (!sg)
+        FAIL(e, OH_E_NOMEM, "hipHostMalloc for %d picture hashes failed", n);
+    OhMd5Job *jobs = (OhMd5Job *)sg->p;
+    uint8_t *out = (uint8_t *)sg->p + jobs_bytes;
+    std::vector<int> slot((size_t)n * 3);
+    const int nj = plane_jobs(e, pic_ids, n, jobs, slot.data());
+    ohk_md5(jobs, nj, out, e->stream);                        /* pinned host memory is mapped: the kernel reads the jobs and writes the digests there */
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    { const int ke = kernel_error(e); if (ke) return ke; }     /* a kernel that gave up: these samples are not the picture */
+    for (size_t k = 0; k < slot.size(); k++) {
+        if (slot[k] >= 0) memcpy(digests + k * 16, out + (size_t)slot[k] * 16, 16);
+        else memset(digests + k * 16, 0, 16);
+    }
+    return OH_OK;
+}
+
+extern "C" int oh_pics_md5(OhEngine *e, const int *pic_ids, int n, uint8_t *digests)
+{
+    if (!e || n < 0 || (n && (!pic_ids || !digests)))
+        return OH_E_ARG;
+    if (!n)
+        return OH_OK;
+    { const int rc = check_pics(e, pic_ids, n, "oh_pics_md5"); if (rc) return rc; }
+    return pics_md5(e, pic_ids, n, digests);
+}
+
+/* CRC (kind 1) or checksum (kind 2) of every plane of n pictures (ids checked): vals[i * 3 + c], 0 for planes a monochrome picture
+ * lacks.  hash.hip: one workgroup per OH_HASH_TASK bytes of every plane in one launch, then one per plane to combine.  The job table
+ * and the task list are staged in pinned memory and copied to HBM in one piece; the values come back through the pinned buffer. */
+static int pics_crc_checksum(OhEngine *e, const int *pic_ids, int n, int kind, uint32_t *vals)
+{
+    HIPCHK(e, hipSetDevice(e->device));
+    std::vector<int> slot((size_t)n * 3);
+    std::vector<OhMd5Job> jv((size_t)n * 3);
+    const int nj = plane_jobs(e, pic_ids, n, jv.data(), slot.data());
+    std::vector<uint32_t> first((size_t)nj + 1, 0);
+    for (int k = 0; k < nj; k++) {
+        const uint64_t bytes = (uint64_t)jv[k].row_bytes * jv[k].rows;
+        first[k + 1] = first[k] + (uint32_t)((bytes + OH_HASH_TASK - 1) / OH_HASH_TASK);
+    }
+    const uint32_t nt = first[nj];
+    const size_t o_first = align_up((size_t)nj * sizeof(OhMd5Job), 256), o_map = o_first + align_up(((size_t)nj + 1) * 4, 256),
+                 o_part = o_map + align_up((size_t)nt * 8, 256), dev_bytes = o_part + align_up((size_t)nt * 4, 256);
+    { const int rc = scratch_reserve(e, &e->hash_dev, dev_bytes); if (rc) return rc; }    /* every call ends with a wait: the old buffer is idle */
+    OhEngine::Stage *sg = stage_acquire(e, o_part + (size_t)nj * 4);
+    if (!sg)
+        FAIL(e, OH_E_NOMEM, "hipHostMalloc for %d picture hashes failed", n);
+    char *h = (char *)sg->p, *d = (char *)e->hash_dev.p;
+    memcpy(h, jv.data(), (size_t)nj * sizeof(OhMd5Job));
+    memcpy(h + o_first, first.data(), ((size_t)nj + 1) * 4);
+    uint32_t *map = (uint32_t *)(h + o_map);
+    for (int k = 0; k < nj; k++)
+        for (uint32_t t = first[k]; t < first[k + 1]; t++) { map[2 * t] = (uint32_t)k; map[2 * t + 1] = t - first[k]; }
+    uint32_t *out = (uint32_t *)(h + o_part);                 /* pinned and mapped: the combine kernel writes the plane values there */
+    HIPCHK(e, hipMemcpyAsync(d, h, o_part, hipMemcpyHostToDevice, e->stream));
+    ohk_hash(kind, (const OhMd5Job *)d, (const uint32_t *)(d + o_first), (const uint32_t *)(d + o_map), nj, (int)nt, (uint32_t *)(d + o_part), out,
+             e->stream);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    { const int ke = kernel_error(e); if (ke) return ke; }
+    for (size_t k = 0; k < slot.size(); k++)
+        vals[k] = slot[k] >= 0 ? out[slot[k]] : 0;
+    return OH_OK;
+}
+
+extern "C" int oh_pics_hash(OhEngine *e, const int *pic_ids, int n, int hash_type, OhPictureHash *out)
+{
+    if (!e || n < 0 || (n && (!pic_ids || !out)))
+        return OH_E_ARG;
+    if (hash_type < 0 || hash_type > 2)
+        FAIL(e, OH_E_ARG, "oh_pics_hash: hash_type %d (0 MD5, 1 CRC, 2 checksum)", hash_type);
+    if (!n)
+        return OH_OK;
+    { const int rc = check_pics(e, pic_ids, n, "oh_pics_hash"); if (rc) return rc; }
+    std::vector<uint32_t> v((size_t)n * 12);                  /* per picture: MD5 three 16-byte digests, else three values */
+    uint8_t *dg = (uint8_t *)v.data();
+    const int rc = hash_type == 0 ? pics_md5(e, pic_ids, n, dg) : pics_crc_checksum(e, pic_ids, n, hash_type, v.data());
+    if (rc) return rc;
+    for (int i = 0; i < n; i++) {
+        memset(&out[i], 0, sizeof(out[i]));
+        out[i].present = 1; out[i].hash_type = hash_type;
+        if (hash_type == 0) memcpy(out[i].md5, dg + (size_t)i * 48, 48);
+        else memcpy(hash_type == 1 ? out[i].crc : out[i].checksum, &v[(size_t)i * 3], 3 * sizeof(uint32_t));
+    }
+    return OH_OK;
+}
+
+/* ---------------- conversion to standard images (convert.hip) ---------------- */
+static int conv_sample_bytes(const OhConvert *cv, int bit_depth)
+{
+    switch (cv->sample) {
+    case OH_CONV_NATIVE: return sample_bytes(bit_depth);
+    case OH_CONV_U8:     return 1;
+    case OH_CONV_F32:    return 4;
+    default:             return 2;
+    }
+}
+
+/* what oh_pics_convert checks of the combination itself (not of pictures or memory); *bytes: one image */
+static int conv_check(const OhPicParams *p, const OhConvert *cv, size_t *bytes, std::string *why)
+{
+    char buf[256];
+    if (!p || !cv) { *why = "no params or no OhConvert"; return OH_E_ARG; }
+    const int cf = p->chroma_format_idc, bd = p->bit_depth;
+    if (p->width <= 0 || p->height <= 0 || cf < 0 || cf > 3 || (bd != 8 && bd != 9 && bd != 10 && bd != 12)) {
+        *why = "bad picture params"; return OH_E_ARG;
+    }
+    if (cv->format < OH_CONV_PLANAR || cv->format > OH_CONV_RGBA || cv->sample < OH_CONV_NATIVE || cv->sample > OH_CONV_F32) {
+        snprintf(buf, sizeof(buf), "format %d / sample %d unknown", cv->format, cv->sample); *why = buf; return OH_E_UNSUPPORTED;
+    }
+    const bool yuv = cv->format <= OH_CONV_SEMIPLANAR;
+    if (yuv ? cv->sample > OH_CONV_U8 : cv->sample == OH_CONV_NATIVE) {
+        snprintf(buf, sizeof(buf), "sample %d does not fit format %d (YUV: NATIVE or U8; RGB: U8, U16, F16, F32)", cv->sample, cv->format);
+        *why = buf; return OH_E_UNSUPPORTED;
+    }
+    if (!yuv && cv->matrix != 1 && cv->matrix != 5 && cv->matrix != 6 && cv->matrix != 9) {
+        snprintf(buf, sizeof(buf), "matrix_coefficients %d (1 BT.709, 5 / 6 BT.601, 9 BT.2020 NCL)", cv->matrix); *why = buf; return OH_E_UNSUPPORTED;
+    }
+    if (cv->format == OH_CONV_SEMIPLANAR && cf == 0) { *why = "a 4:0:0 picture has no semi-planar form"; return OH_E_UNSUPPORTED; }
+    if ((cv->full_range != 0 && cv->full_range != 1) || (cv->chroma_filter != 0 && cv->chroma_filter != 1)) {
+        *why = "full_range and chroma_filter are 0 or 1"; return OH_E_ARG;
+    }
+    if (!crop_window_ok(p, cv->win, true, why))
+        return OH_E_ARG;
+    const int sw = (cf == 1 || cf == 2) ? 2 : 1, sh = cf == 1 ? 2 : 1;
+    const int W = p->width - cv->win.left - cv->win.right, H = p->height - cv->win.top - cv->win.bottom;
+    size_t samples;
+    if (cv->format <= OH_CONV_SEMIPLANAR)
+        samples = (size_t)W * H + (cf ? 2 * (size_t)(W / sw) * (H / sh) : 0);
+    else
+        samples = (size_t)W * H * (cv->format == OH_CONV_RGBA ? 4 : 3);
+    *bytes = samples * (size_t)conv_sample_bytes(cv, bd);
+    return OH_OK;
+}
+
+extern "C" size_t oh_convert_image_bytes(const OhPicParams *p, const OhConvert *cv)
+{
+    size_t bytes = 0;
+    std::string why;
+    return conv_check(p, cv, &bytes, &why) == OH_OK ? bytes : 0;
+}
+
+/* the integers of an RGB conversion: R = clamp((cy (Y - yoff) + crv (Cr - mid) + 2^(S-1)) >> S, 0, 2^D - 1), G with cgu, cgv, B with
+ * cbu; each coefficient round(2^S (2^D - 1) entry / scale) of the H.273 inverse matrix, S the largest shift that keeps every term and
+ * every sum inside int32 for all samples of bit_depth bits */
+extern "C" int oh_convert_coeffs(const OhConvert *cv, int bit_depth, int32_t *out, int n)
+{
+    if (!cv || !out || n < OH_CONV_NCOEFFS || (bit_depth != 8 && bit_depth != 9 && bit_depth != 10 && bit_depth != 12))
+        return OH_E_ARG;
+    if (cv->format < OH_CONV_RGB_PLANAR || cv->format > OH_CONV_RGBA || cv->sample < OH_CONV_U8 || cv->sample > OH_CONV_F32)
+        return OH_E_UNSUPPORTED;
+    double kr, kb;
+    switch (cv->matrix) {
+    case 1:  kr = 0.2126; kb = 0.0722; break;
+    case 5:
+    case 6:  kr = 0.299;  kb = 0.114;  break;
+    case 9:  kr = 0.2627; kb = 0.0593; break;
+    default: return OH_E_UNSUPPORTED;
+    }
+    if (cv->full_range != 0 && cv->full_range != 1)
+        return OH_E_ARG;
+    const int B = bit_depth, D = cv->sample == OH_CONV_U8 ? 8 : 16;
+    const double kg = 1.0 - kr - kb, full = (double)((1 << B) - 1), unit = (double)(1 << (B - 8));
+    const double ys = cv->full_range ? full : 219.0 * unit, cs = cv->full_range ? full : 224.0 * unit;
+    const int yoff = cv->full_range ? 0 : 16 << (B - 8), mid = 1 << (B - 1);
+    const double ent[5] = { 1.0 / ys, 2.0 * (1.0 - kr) / cs, -2.0 * kb * (1.0 - kb) / (kg * cs), -2.0 * kr * (1.0 - kr) / (kg * cs),
+                            2.0 * (1.0 - kb) / cs };              /* cy, crv, cgu, cgv, cbu */
+    const int64_t dy = std::max(yoff, (1 << B) - 1 - yoff), dc = mid;   /* largest |Y - yoff|, |C - mid| */
+    const double scale = (double)((1 << D) - 1);
+    for (int S = 30; S >= 1; S--) {
+        int64_t c[5];
+        for (int i = 0; i < 5; i++) c[i] = llround(ldexp(scale * ent[i], S));
+        const int64_t r = (int64_t)1 << (S - 1), ty = std::llabs(c[0]) * dy;
+        const int64_t worst = std::max({ ty + std::llabs(c[1]) * dc + r, ty + (std::llabs(c[2]) + std::llabs(c[3])) * dc + r,
+                                         ty + std::llabs(c[4]) * dc + r });
+        if (worst > INT32_MAX)
+            continue;
+        for (int i = 0; i < 5; i++) out[i] = (int32_t)c[i];
+        out[5] = yoff; out[6] = mid; out[7] = S; out[8] = D;
+        return OH_OK;
+    }
+    return OH_E_UNSUPPORTED;
+}
+
+extern "C" int oh_pics_convert(OhEngine *e, const int *pic_ids, int n, const OhConvert *cv, void *dst, size_t image_stride, size_t dst_bytes)
+{
+    if (!e || n < 0 || !cv || (n && !pic_ids))
+        return OH_E_ARG;
+    if (!n)
+        return OH_OK;
+    { const int rc = check_pics(e, pic_ids, n, "oh_pics_convert"); if (rc) return rc; }
+    const Pic *p0 = get_pic(e, pic_ids[0]);
+    const int other = first_other_params(e, pic_ids, n);
+    if (other < n)
+        FAIL(e, OH_E_ARG, "oh_pics_convert: picture %d has other params than picture %d", pic_ids[other], pic_ids[0]);
+    size_t ib = 0;
+    std::string why;
+    { const int rc = conv_check(&p0->p, cv, &ib, &why); if (rc) FAIL(e, rc, "oh_pics_convert: %s", why.c_str()); }
+    const size_t ob = (size_t)conv_sample_bytes(cv, p0->p.bit_depth);
+    if (image_stride < ib || image_stride % ob || (uintptr_t)dst % ob)
+        FAIL(e, OH_E_ARG, "oh_pics_convert: image_stride %zu (an image takes %zu bytes) or dst not a multiple of the %zu-byte sample", image_stride, ib, ob);
+    if (!dst || ib > dst_bytes || (size_t)(n - 1) > (dst_bytes - ib) / image_stride)
+        FAIL(e, OH_E_ARG, "oh_pics_convert: %d images of %zu bytes, %zu apart, do not fit %zu bytes", n, ib, image_stride, dst_bytes);
+    const size_t total = (size_t)(n - 1) * image_stride + ib;
+    HIPCHK(e, hipSetDevice(e->device));
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, dst) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->device) {
+        (void)hipGetLastError();
+        FAIL(e, OH_E_ARG, "oh_pics_convert: dst is not device memory of device %d", e->device);
+    }
+    void *base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, dst) == hipSuccess) {
+        if ((char *)dst + total > (char *)base + size)
+            FAIL(e, OH_E_ARG, "oh_pics_convert: %zu bytes at dst run past the end of its allocation", total);
+    } else {
+        (void)hipGetLastError();
+    }
+    OhConvArgs a;
+    memset(&a, 0, sizeof(a));
+    const OhPicParams &p = p0->p;
+    const int bpp = sample_bytes(p.bit_depth);
+    for (int c = 0; c < 3; c++) a.pitch[c] = p0->stride[c] * bpp;
+    a.cw = p0->w[1]; a.ch = p0->h[1];
+    a.left = cv->win.left; a.top = cv->win.top;
+    a.W = p.width - cv->win.left - cv->win.right; a.H = p.height - cv->win.top - cv->win.bottom;
+    a.cf = p.chroma_format_idc; a.bd = p.bit_depth; a.filter = cv->chroma_filter;
+    a.nc = cv->format == OH_CONV_RGBA ? 4 : 3;
+    a.image_stride = image_stride;
+    if (cv->format >= OH_CONV_RGB_PLANAR) {
+        const int rc = oh_convert_coeffs(cv, p.bit_depth, a.k, OH_CONV_NCOEFFS);
+        if (rc) FAIL(e, rc, "oh_pics_convert: no coefficients for this conversion");
+    }
+    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
+        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+        for (int i = 0; i < m; i++) {
+            const Pic *q = get_pic(e, pic_ids[i0 + i]);
+            for (int c = 0; c < 3; c++) a.src[i][c] = p.chroma_format_idc || !c ? final_planes(q)[c] : nullptr;
+        }
+        a.dst = (char *)dst + (size_t)i0 * image_stride;
+        ohk_convert(&a, cv->format, cv->sample, m, e->stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    return OH_OK;
+}
+
+/* ---------------- resizing into engine pictures (resize.hip) ---------------- */
+typedef __int128 i128;
+static i128 floor_div(i128 a, i128 b) { const i128 q = a / b; return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q; }   /* b > 0 */
+
+static bool resize_axis_ok(int S, int T, int filter, int phase)
+{
+    return S >= 1 && T >= 1 && S <= 16384 && T <= 16384 && (filter == OH_RESIZE_BILINEAR || filter == OH_RESIZE_BICUBIC) && (phase == 1 || phase == 2);
+}
+
+extern "C" int oh_resize_max_taps(int src_extent, int dst_extent, int filter)
+{
+    if (!resize_axis_ok(src_extent, dst_extent, filter, 2))
+        return OH_E_ARG;
+    const int64_t S = src_extent, T = dst_extent, D = 4 * std::max(S, T), R = filter == OH_RESIZE_BICUBIC ? 2 : 1;
+    return (int)std::min<int64_t>(S, (2 * R * D - 2) / (4 * T) + 1);          /* source samples strictly inside a span of 2RD */
+}
+
+/* the taps of one axis, all positions in units of 1/(4T) source samples */
+extern "C" int oh_resize_taps(int src_extent, int dst_extent, int filter, int phase, int32_t *first, int16_t *coeffs, int max_taps, int *n_taps)
+{
+    if (!first || !coeffs || !n_taps || !resize_axis_ok(src_extent, dst_extent, filter, phase) ||
+        max_taps < oh_resize_max_taps(src_extent, dst_extent, filter))
+        return OH_E_ARG;
+    const int64_t S = src_extent, T = dst_extent, p = phase, D = 4 * std::max(S, T), R = filter == OH_RESIZE_BICUBIC ? 2 : 1;
+    std::vector<i128> w;
+    std::vector<int64_t> k;
+    for (int64_t x = 0; x < T; x++) {
+        const int64_t c = (4 * x + p) * S;
+        int64_t lo = -(int64_t)floor_div(-(c - R * D - p * T + 1), 4 * T), hi = (int64_t)floor_div(c + R * D - p * T - 1, 4 * T);
+        lo = std::max<int64_t>(lo, 0); hi = std::min(hi, S - 1);
+        const int n = (int)(hi - lo + 1);
+        if (n < 1 || n > max_taps)
+            return OH_E_ARG;
+        w.assign((size_t)n, 0); k.assign((size_t)n, 0);
+        i128 sum = 0;
+        for (int j = 0; j < n; j++) {
+            const i128 v = std::llabs((4 * (lo + j) + p) * T - c), d = D;
+            w[j] = R == 1 ? d - v : v <= d ? 3 * v * v * v - 5 * v * v * d + 2 * d * d * d : -(v * v * v - 5 * v * v * d + 8 * v * d * d - 4 * d * d * d);
+            sum += w[j];
+        }
+        if (sum <= 0)
+            return OH_E_UNSUPPORTED;
+        int64_t ks = 0, ka = 0;
+        int best = 0;
+        for (int j = 0; j < n; j++) {
+            k[j] = (int64_t)floor_div(2 * w[j] * (1 << 14) + sum, 2 * sum);
+            ks += k[j];
+            if (k[j] > k[best]) best = j;
+        }
+        k[best] += (1 << 14) - ks;
+        for (int j = 0; j < n; j++) ka += std::llabs(k[j]);
+        if (ka >= 1 << 15)
+            return OH_E_UNSUPPORTED;
+        first[x] = (int32_t)lo; n_taps[x] = n;
+        int16_t *row = coeffs + (size_t)x * max_taps;
+        for (int j = 0; j < max_taps; j++) row[j] = j < n ? (int16_t)k[j] : 0;
+    }
+    return OH_OK;
+}
+
+namespace {
+struct ResizeAxis { std::vector<int32_t> first, cnt; std::vector<int16_t> k; int mt = 0; };
+/* what a call works out per plane class (0 luma, 1 chroma) beside its OhResizeClass: the taps of both axes, the quads of the horizontal
+ * pass, the row groups of the vertical pass, and where each table lies in the blob of `tab` bytes that goes to the device */
+struct ResizePlan {
+    int ncls = 0;
+    ResizeAxis hx[2], vx[2];
+    std::vector<int32_t> h_f4[2], h_n4[2], v_lo[2], v_np[2], v_off[2];
+    size_t off[2][9] = {}, tab = 0;                             /* h_first, h_cnt, h_k, v_first, v_cnt, v_off, v_k, h_f4, h_n4 */
+};
+}
+
+static int resize_axis(int S, int T, int filter, int phase, ResizeAxis *ax)
+{
+    ax->mt = oh_resize_max_taps(S, T, filter);
+    if (ax->mt < 1) return OH_E_ARG;
+    ax->first.resize((size_t)T); ax->cnt.resize((size_t)T); ax->k.resize((size_t)T * ax->mt);
+    return oh_resize_taps(S, T, filter, phase, ax->first.data(), ax->k.data(), ax->mt, ax->cnt.data());
+}
+
+/* what oh_pics_resize checks of its arguments (n > 0, the lists present) */
+static int resize_check(OhEngine *e, const int *src_ids, const int *dst_ids, int n, const OhResize *rs)
+{
+    { const int rc = check_pics(e, src_ids, n, "oh_pics_resize"); if (rc) return rc; }
+    { const int rc = check_pics(e, dst_ids, n, "oh_pics_resize"); if (rc) return rc; }
+    const int other = std::min(first_other_params(e, src_ids, n), first_other_params(e, dst_ids, n));
+    if (other < n)
+        FAIL(e, OH_E_ARG, "oh_pics_resize: pictures %d -> %d have other params than pictures %d -> %d", src_ids[other], dst_ids[other], src_ids[0], dst_ids[0]);
+    {
+        std::vector<int> d(dst_ids, dst_ids + n), s(src_ids, src_ids + n);
+        std::sort(d.begin(), d.end()); std::sort(s.begin(), s.end());
+        if (std::adjacent_find(d.begin(), d.end()) != d.end())
+            FAIL(e, OH_E_ARG, "oh_pics_resize: a destination is listed twice");
+        for (int i = 0; i < n; i++)
+            if (std::binary_search(s.begin(), s.end(), d[i]))
+                FAIL(e, OH_E_ARG, "oh_pics_resize: picture %d is both source and destination", d[i]);
+    }
+    const OhPicParams &sp = get_pic(e, src_ids[0])->p, &dp = get_pic(e, dst_ids[0])->p;
+    if (rs->filter != OH_RESIZE_BILINEAR && rs->filter != OH_RESIZE_BICUBIC)
+        FAIL(e, OH_E_ARG, "oh_pics_resize: filter %d (0 bilinear, 1 bicubic)", rs->filter);
+    const int cf = sp.chroma_format_idc, hs = cf == 1 || cf == 2, vs = cf == 1, sw = 1 << hs, sv = 1 << vs;
+    std::string why;
+    if (!crop_window_ok(&sp, rs->win, true, &why))
+        FAIL(e, OH_E_ARG, "oh_pics_resize: %s", why.c_str());
+    /* the size rules read the SOURCES' chroma format: a destination of another format is refused below */
+    if (rs->width < 1 || rs->height < 1 || rs->width > dp.width || rs->height > dp.height || rs->width % sw || rs->height % sv)
+        FAIL(e, OH_E_ARG, "oh_pics_resize: image %dx%d: below 1, above the destination's %dx%d, or not multiples of %dx%d", rs->width, rs->height,
+             dp.width, dp.height, sw, sv);
+    if (dp.bit_depth != sp.bit_depth || dp.chroma_format_idc != cf)
+        FAIL(e, OH_E_UNSUPPORTED, "oh_pics_resize: destinations of %d bit, chroma format %d; sources of %d bit, chroma format %d", dp.bit_depth,
+             dp.chroma_format_idc, sp.bit_depth, cf);
+    const int W = sp.width - rs->win.left - rs->win.right, H = sp.height - rs->win.top - rs->win.bottom;
+    for (int c = 0; c < (cf ? 2 : 1); c++) {
+        const int64_t ext[4] = { W >> (c ? hs : 0), rs->width >> (c ? hs : 0), H >> (c ? vs : 0), rs->height >> (c ? vs : 0) };
+        for (int a = 0; a < 4; a += 2)
+            if (ext[a] > OH_RESIZE_MAX_DOWN * ext[a + 1] || ext[a + 1] > OH_RESIZE_MAX_UP * ext[a])
+                FAIL(e, OH_E_UNSUPPORTED, "oh_pics_resize: %d -> %d samples is outside %d:1 .. 1:%d", (int)ext[a], (int)ext[a + 1], OH_RESIZE_MAX_DOWN,
+                     OH_RESIZE_MAX_UP);
+    }
+    return OH_OK;
+}
+
+/* the geometry of every plane class from the first source and destination (all pictures of a call are alike): *a but for the device
+ * pointers and the pictures, *pl with the contents and the layout of the tables */
+static int resize_plan(OhEngine *e, const Pic *s0, const Pic *d0, const OhResize *rs, OhResizeArgs *a, ResizePlan *pl)
+{
+    const OhPicParams &sp = s0->p;
+    const OhWindow &w = rs->win;
+    const int cf = sp.chroma_format_idc, hs = cf == 1 || cf == 2, vs = cf == 1, bpp = sample_bytes(sp.bit_depth);
+    const int W = sp.width - w.left - w.right, H = sp.height - w.top - w.bottom;
+    memset(a, 0, sizeof(*a));
+    a->np = cf ? 3 : 1; a->bd = sp.bit_depth;
+    pl->ncls = cf ? 2 : 1;
+    uint64_t mid_pic = 0;
+    for (int c = 0; c < pl->ncls; c++) {
+        OhResizeClass &k = a->k[c];
+        const ResizeAxis &hx = pl->hx[c], &vx = pl->vx[c];
+        const int Sw = W >> (c ? hs : 0), Sh = H >> (c ? vs : 0);
+        k.x0 = w.left >> (c ? hs : 0); k.y0 = w.top >> (c ? vs : 0); k.sh = Sh;
+        k.tw = rs->width >> (c ? hs : 0); k.th = rs->height >> (c ? vs : 0);
+        k.cw = d0->w[c]; k.ch = d0->h[c];
+        k.src_pitch = s0->stride[c] * bpp; k.dst_pitch = d0->stride[c] * bpp;
+        k.mid_stride = (int32_t)align_up((size_t)k.tw + 1, 64);
+        int rc = resize_axis(Sw, k.tw, rs->filter, c && hs ? 1 : 2, &pl->hx[c]);
+        if (!rc) rc = resize_axis(Sh, k.th, rs->filter, 2, &pl->vx[c]);
+        if (rc) FAIL(e, rc, "oh_pics_resize: no taps for %dx%d -> %dx%d", Sw, Sh, k.tw, k.th);
+        /* horizontal pass: the widest power-of-two segment whose source columns fit a staged row, then as many rows as fit the LDS */
+        int span = 0;
+        for (k.segw = 256; ; k.segw >>= 1) {
+            span = 0;
+            for (int x = 0; x < k.tw; x += k.segw) {
+                const int xl = std::min(x + k.segw, k.tw) - 1;
+                span = std::max(span, hx.first[xl] + hx.cnt[xl] - hx.first[x]);
+            }
+            if (span <= OH_RESIZE_SPAN || k.segw == 1) break;
+        }
+        if (span > OH_RESIZE_SPAN)
+            FAIL(e, OH_E_UNSUPPORTED, "oh_pics_resize: one image column reads %d source columns (at most %d)", span, OH_RESIZE_SPAN);
+        k.row_bytes = (int32_t)align_up((size_t)span * bpp, 16) + 32;
+        k.rpw = std::max(1, std::min({ (int)OH_RESIZE_HROWS, OH_RESIZE_LDS / k.row_bytes, Sh }));
+        k.h_stride = (int32_t)align_up((size_t)k.tw, 32);
+        /* the taps of a column as QUADS of source columns that start at a multiple of four columns of the plane (an 8- or 4-byte
+         * aligned LDS read): zero coefficients in front of the first tap and behind the last */
+        int quads = 0;
+        for (int x = 0; x < k.tw; x++) {
+            const int lead = (k.x0 + hx.first[x]) & 3;
+            pl->h_f4[c].push_back(hx.first[x] - lead);
+            pl->h_n4[c].push_back((lead + hx.cnt[x] + 3) / 4);
+            quads = std::max(quads, pl->h_n4[c].back());
+        }
+        k.h_groups = (Sh + k.rpw - 1) / k.rpw;
+        /* vertical pass: per group of image rows the intermediate rows it reads, in pairs */
+        k.v_groups = (k.th + OH_RESIZE_VROWS - 1) / OH_RESIZE_VROWS;
+        int32_t pairs = 0;
+        for (int g = 0; g < k.v_groups; g++) {
+            const int y0 = g * OH_RESIZE_VROWS, y1 = std::min(y0 + OH_RESIZE_VROWS, k.th) - 1;
+            const int lo = vx.first[y0], np = (vx.first[y1] + vx.cnt[y1] - lo + 1) / 2;
+            pl->v_lo[c].push_back(lo); pl->v_np[c].push_back(np); pl->v_off[c].push_back(pairs);
+            pairs += np;
+        }
+        const size_t sz[9] = { (size_t)k.tw * 4, (size_t)k.tw * 4, (size_t)quads * k.h_stride * 8, (size_t)k.v_groups * 4, (size_t)k.v_groups * 4,
+                               (size_t)k.v_groups * 4, (size_t)pairs * OH_RESIZE_VROWS * 4, (size_t)k.tw * 4, (size_t)k.tw * 4 };
+        for (int i = 0; i < 9; i++) { pl->off[c][i] = pl->tab; pl->tab += align_up(sz[i], 256); }
+        for (int p = c ? 1 : 0; p < (c ? 3 : 1); p++) {
+            a->mid_plane[p] = mid_pic;
+            mid_pic += align_up((size_t)(Sh + 1) * k.mid_stride, 128);     /* a spare row: the odd half of a group's last pair */
+        }
+    }
+    a->mid_pic = mid_pic;
+    return OH_OK;
+}
+
+/* the tables of the plan into the host copy h of the blob; *a gets their addresses in the device copy d */
+static void resize_fill(const ResizePlan &pl, OhResizeArgs *a, char *h, const char *d)
+{
+    memset(h, 0, pl.tab);
+    for (int c = 0; c < pl.ncls; c++) {
+        OhResizeClass &k = a->k[c];
+        const ResizeAxis &hx = pl.hx[c], &vx = pl.vx[c];
+        const size_t *off = pl.off[c];
+        memcpy(h + off[0], hx.first.data(), (size_t)k.tw * 4);
+        memcpy(h + off[1], hx.cnt.data(), (size_t)k.tw * 4);
+        memcpy(h + off[7], pl.h_f4[c].data(), (size_t)k.tw * 4);
+        memcpy(h + off[8], pl.h_n4[c].data(), (size_t)k.tw * 4);
+        int16_t *hk = (int16_t *)(h + off[2]);                   /* [quad][column][4] */
+        for (int x = 0; x < k.tw; x++) {
+            const int lead = hx.first[x] - pl.h_f4[c][x];
+            for (int j = 0; j < hx.cnt[x]; j++)
+                hk[((size_t)((lead + j) / 4) * k.h_stride + x) * 4 + (lead + j) % 4] = hx.k[(size_t)x * hx.mt + j];
+        }
+        memcpy(h + off[3], pl.v_lo[c].data(), (size_t)k.v_groups * 4);
+        memcpy(h + off[4], pl.v_np[c].data(), (size_t)k.v_groups * 4);
+        memcpy(h + off[5], pl.v_off[c].data(), (size_t)k.v_groups * 4);
+        int16_t *vk = (int16_t *)(h + off[6]);                   /* [pair][image row of the group][even row, odd row] */
+        for (int y = 0; y < k.th; y++) {
+            const int g = y / OH_RESIZE_VROWS, i = y % OH_RESIZE_VROWS;
+            for (int j = 0; j < vx.cnt[y]; j++) {
+                const int r = vx.first[y] + j - pl.v_lo[c][g];
+                vk[(((size_t)pl.v_off[c][g] + r / 2) * OH_RESIZE_VROWS + i) * 2 + (r & 1)] = vx.k[(size_t)y * vx.mt + j];
+            }
+        }
+        k.h_first = (const int32_t *)(d + off[0]); k.h_cnt = (const int32_t *)(d + off[1]); k.h_k = (const int16_t *)(d + off[2]);
+        k.h_f4 = (const int32_t *)(d + off[7]); k.h_n4 = (const int32_t *)(d + off[8]);
+        k.v_first = (const int32_t *)(d + off[3]); k.v_cnt = (const int32_t *)(d + off[4]); k.v_off = (const int32_t *)(d + off[5]);
+        k.v_k = (const int32_t *)(d + off[6]);
+    }
+}
+
+/* the pictures of the call in sets of at most per_set (what the intermediate has room for), one launch set each */
+static int resize_launch(OhEngine *e, const int *src_ids, const int *dst_ids, int n, int per_set, int pad, OhResizeArgs *a)
+{
+    for (int i0 = 0; i0 < n; i0 += per_set) {
+        const int m = std::min(n - i0, per_set);
+        for (int i = 0; i < m; i++) {
+            const Pic *s = get_pic(e, src_ids[i0 + i]);
+            Pic *q = get_pic(e, dst_ids[i0 + i]);
+            for (int c = 0; c < a->np; c++) { a->src[i][c] = final_planes(s)[c]; a->dst[i][c] = q->a[c]; }
+            q->final_b = false;                                  /* the image is a finished picture in half 0 */
+            q->done_seq = 0;
+        }
+        ohk_resize(a, m, pad, e->stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    return OH_OK;
+}
+
+extern "C" int oh_pics_resize(OhEngine *e, const int *src_ids, const int *dst_ids, int n, const OhResize *rs)
+{
+    if (!e || n < 0 || !rs || (n && (!src_ids || !dst_ids)))
+        return OH_E_ARG;
+    if (!n)
+        return OH_OK;
+    { const int rc = resize_check(e, src_ids, dst_ids, n, rs); if (rc) return rc; }
+    const Pic *s0 = get_pic(e, src_ids[0]), *d0 = get_pic(e, dst_ids[0]);
+    OhResizeArgs a;
+    ResizePlan pl;
+    { const int rc = resize_plan(e, s0, d0, rs, &a, &pl); if (rc) return rc; }
+    const size_t mid_bytes = (size_t)a.mid_pic * 2;
+    const int per_set = (int)std::max<size_t>(1, std::min<size_t>(OH_RESIZE_MAX_PICS, ((size_t)512 << 20) / mid_bytes));
+    const size_t need = pl.tab + (size_t)std::min(n, per_set) * mid_bytes;
+    HIPCHK(e, hipSetDevice(e->device));
+    if (need > e->resize_dev.bytes)
+        HIPCHK(e, hipStreamSynchronize(e->stream));              /* launches of earlier calls still use the old buffer */
+    { const int rc = scratch_reserve(e, &e->resize_dev, need); if (rc) return rc; }
+    /* the tables: built in a pinned buffer of the pool, copied on the engine stream — behind the launches of an earlier call that
+     * read the device copy, in front of this call's */
+    OhEngine::Stage *sg = stage_acquire(e, pl.tab);
+    if (!sg)
+        FAIL(e, OH_E_NOMEM, "oh_pics_resize: no staging buffer for %zu bytes of tap tables", pl.tab);
+    char *d = (char *)e->resize_dev.p;
+    resize_fill(pl, &a, (char *)sg->p, d);
+    HIPCHK(e, hipMemcpyAsync(d, sg->p, pl.tab, hipMemcpyHostToDevice, e->stream));
+    { const int rc = stage_in_use(e, sg, e->stream); if (rc) return rc; }
+    a.mid = (int16_t *)(d + pl.tab);
+    return resize_launch(e, src_ids, dst_ids, n, per_set, rs->width < d0->p.width || rs->height < d0->p.height, &a);
+}
+
+extern "C" int oh_pic_device_planes(OhEngine *e, int pic_id, void *planes[3], int32_t stride[3], int32_t width[3], int32_t height[3])
+{
+    if (!e)
+        return OH_E_ARG;
+    Pic *p = get_pic(e, pic_id);
+    if (!p)
+        FAIL(e, OH_E_ARG, "unknown picture %d", pic_id);
+    for (int c = 0; c < 3; c++) {
+        planes[c] = final_planes(p)[c];
+        stride[c] = p->stride[c]; width[c] = p->w[c]; height[c] = p->h[c];
+    }
+    return OH_OK;
+}
+

@@ -3,7 +3,7 @@
  * the window arithmetic of its block driver (upsample_block_luma / upsample_block_mc, hevc_filter.c:1175-1309), the edge emulation
  * it calls (emulated_edge_up_h / _v, videodsp_template.c:103-160) and the block slots (upsample_filter_block_{luma,cr}_{h,v}_{all,x2,x1_5},
  * hevcdsp_template.c:1834-2162).  Shared by the kernel (upsample.hip: upsample_block_kernel) and the host predicate that says where
- * the reference's output is defined (engine.hip: oh_upsample_blocks_defined), so both read the same arithmetic.
+ * the reference's output is defined (engine_shvc.hip: oh_upsample_blocks_defined), so both read the same arithmetic.
  */
 #ifndef OHEVC_UPBLOCK_H
 #define OHEVC_UPBLOCK_H
