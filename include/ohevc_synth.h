@@ -44,6 +44,9 @@ typedef struct OhSynthParams {
     int32_t  n_slices;          /* > 1: that many slices at random CTB addresses (raster scan, no tiles)                      */
     int32_t  tile_cols, tile_rows; /* > 1: uniform tile grid; see OH_SYNTH_SLICE_PER_TILE                                       */
     int32_t  slice_knobs;       /* OH_SYNTH_* bits                                                                          */
+    /* low-activity content (both 0 = off: no draw is added or changed, every older seed gives the list it gave before) */
+    int32_t  coeff_shift;       /* dense coefficients and sparse levels are divided by 1 << coeff_shift (the rare saturating values stay) */
+    int32_t  pcm_flat;          /* 1: a PCM block is one drawn level plus jitter of -1..2 instead of noise                    */
 } OhSynthParams;
 enum { OH_SYNTH_NO_LF_ACROSS_SLICES = 1,   /* about half of the slices get slice_loop_filter_across_slices_enabled_flag = 0   */
        OH_SYNTH_NO_LF_ACROSS_TILES = 2,    /* pps->loop_filter_across_tiles_enabled_flag = 0                                  */

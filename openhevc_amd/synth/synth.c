@@ -66,21 +66,28 @@ static int laplace(Gen *g, int scale)
 static void gen_coeffs(Gen *g, int log2, int kind)
 {
     int n = 1 << log2, n2 = n * n;
+    const int div = 1 << g->sp->coeff_shift;       /* low-activity content: the same draws, smaller values */
     memset(g->blk, 0, sizeof(int16_t) * (size_t)n2);
     if (kind == OH_TU_SKIP || kind == OH_TU_BYPASS) {
         for (int i = 0; i < n2; i++)
-            g->blk[i] = (int16_t)(pct(g, 60) ? laplace(g, kind == OH_TU_SKIP ? 400 : 24) : 0);
+            g->blk[i] = (int16_t)(pct(g, 60) ? laplace(g, kind == OH_TU_SKIP ? 400 : 24) / div : 0);
         return;
     }
     if (kind == OH_TU_PCM) {
         int mx = (1 << g->p.bit_depth) - 1;
+        if (g->sp->pcm_flat) {                     /* one level per block with a little texture (no draw of this kind when off) */
+            int base = rnd(g, mx + 1);
+            for (int i = 0; i < n2; i++)
+                g->blk[i] = (int16_t)clipi(base + rnd_range(g, -1, 2), 0, mx);
+            return;
+        }
         for (int i = 0; i < n2; i++)
             g->blk[i] = (int16_t)rnd(g, mx + 1);
         return;
     }
     int shape = rnd(g, 10);
     if (shape < 3) {                               /* DC only (idct_dc in the reference) */
-        g->blk[0] = (int16_t)clipi(laplace(g, 6000), -32768, 32767);
+        g->blk[0] = (int16_t)(clipi(laplace(g, 6000), -32768, 32767) / div);
         if (!g->blk[0]) g->blk[0] = 64;
         return;
     }
@@ -90,7 +97,7 @@ static void gen_coeffs(Gen *g, int log2, int kind)
         int x = rnd(g, lim), y = rnd(g, lim);
         if (rnd(g, 3)) { x = rnd(g, x + 1); y = rnd(g, y + 1); }
         int sc = (x + y == 0) ? 5000 : 1800 / (1 + (x + y) / 2);
-        g->blk[y * n + x] = (int16_t)clipi(laplace(g, sc), -32768, 32767);
+        g->blk[y * n + x] = (int16_t)(clipi(laplace(g, sc), -32768, 32767) / div);
     }
     if (rnd(g, 40) == 0)                            /* rare saturating block */
         g->blk[rnd(g, n2)] = (int16_t)(rnd(g, 2) ? 32767 : -32768);
@@ -189,7 +196,7 @@ static uint32_t emit_tb(Gen *g, const CuInfo *cu, int c_idx, int xl, int yl, int
             memset(g->blk, 0, sizeof(int16_t) * (size_t)(n * n));        /* marks the positions already taken */
             for (int i = 0; i < nz; i++) {
                 int px = shape < 3 ? 0 : rnd(g, lim), py = shape < 3 ? 0 : rnd(g, lim);
-                int lvl = clipi(laplace(g, px + py == 0 ? 60 : 12), -32768, 32767);
+                int lvl = clipi(laplace(g, px + py == 0 ? 60 : 12), -32768, 32767) / (1 << g->sp->coeff_shift);
                 if (!lvl) lvl = 1;
                 if (rnd(g, 60) == 0) lvl = rnd(g, 2) ? 32767 : -32768;                  /* rare saturating level */
                 if (g->blk[py * n + px]) continue;

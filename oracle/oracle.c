@@ -46,6 +46,25 @@ static const uint8_t oh_beta_table[52] = {
 static inline int oh_clip3(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 static inline int oh_clip16(int v) { return oh_clip3(v, -32768, 32767); }
 
+/* ---- decision counters (oh_or_counters, oracle.h): which content-dependent branches the pictures of a test reached.
+ * Plain increments beside the arithmetic; the deblock pass says which edge direction and strengths a luma call belongs to
+ * (dir < 0: a slot-level call from outside the pass, not counted). ---- */
+static __thread uint64_t g_cnt[OH_CNT_N];
+static __thread struct { int dir, bs[2]; } g_cnt_ctx = { -1, { 0, 0 } };
+static inline int oh_clip3_cnt(int v, int lo, int hi, uint64_t *hits)
+{
+    if (hits && (v < lo || v > hi))
+        (*hits)++;
+    return oh_clip3(v, lo, hi);
+}
+void oh_or_counters(uint64_t *out, int n, int reset)
+{
+    for (int i = 0; out && i < n && i < OH_CNT_N; i++)
+        out[i] = g_cnt[i];
+    if (reset)
+        memset(g_cnt, 0, sizeof(g_cnt));
+}
+
 /* The 32x32 inverse-DCT matrix (hevcdsp.c:879-944) is the integer cosine table c[m] ~
  * 64*sqrt(2)*cos(m*pi/64) unfolded by symmetry: M[k][n] = +-c[fold(k*(2n+1) mod 128)]. */
 static int8_t oh_dct[32][32];
@@ -538,8 +557,10 @@ int oh_or_pass_deblock(const OhFrame *f, OhHostPic *pics)
                 no_p[0] = (uint8_t)get_pcm(f, x - 1, y); no_p[1] = (uint8_t)get_pcm(f, x - 1, y + 4);
                 no_q[0] = (uint8_t)get_pcm(f, x, y);     no_q[1] = (uint8_t)get_pcm(f, x, y + 4);
             }
+            g_cnt_ctx.dir = 0; g_cnt_ctx.bs[0] = bs0; g_cnt_ctx.bs[1] = bs1;
             oh_or_loop_filter_luma(bd, cur->data[0] + (ptrdiff_t)y * cur->stride[0] + x * bpp,
                                    bpp, cur->stride[0], beta, tc, no_p, no_q);
+            g_cnt_ctx.dir = -1;
         }
     if (p->chroma_format_idc)
         for (int y = 0; y < H; y += 8 * vv)
@@ -585,8 +606,10 @@ int oh_or_pass_deblock(const OhFrame *f, OhHostPic *pics)
                 no_p[0] = (uint8_t)get_pcm(f, x, y - 1); no_p[1] = (uint8_t)get_pcm(f, x + 4, y - 1);
                 no_q[0] = (uint8_t)get_pcm(f, x, y);     no_q[1] = (uint8_t)get_pcm(f, x + 4, y);
             }
+            g_cnt_ctx.dir = 1; g_cnt_ctx.bs[0] = bs0; g_cnt_ctx.bs[1] = bs1;
             oh_or_loop_filter_luma(bd, cur->data[0] + (ptrdiff_t)y * cur->stride[0] + x * bpp,
                                    cur->stride[0], bpp, beta, tc, no_p, no_q);
+            g_cnt_ctx.dir = -1;
         }
     if (p->chroma_format_idc && sao_sees_stale_column(p)) {
         for (int c = 1; c < 3; c++) {

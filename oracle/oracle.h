@@ -117,6 +117,29 @@ int  oh_or_upsample_frame(const OhHostPic *bl, OhHostPic *el, const OhUpsample *
 /* boundary strengths from the maps ff_hevc_deblocking_boundary_strengths reads (hevc_filter.c:584-941); vbs / hbs: oh_bs_size(p) bytes */
 int  oh_or_bs_derive(const OhPicParams *p, const OhBsInputs *in, uint8_t *vbs, uint8_t *hbs);
 
+/* ---- decision counters: which content-dependent branches of the luma deblocking filter and of the intra smoothing the pictures
+ * run so far on this thread reached (tests/test_structured_content.py keeps the structured test content honest with them).
+ * Per edge direction d (0 vertical, 1 horizontal) counter k is out[d * OH_CNT_PER_DIR + k]; luma segments (4 lines) with bs > 0
+ * inside oh_or_pass_deblock only.  Copies min(n, OH_CNT_N) counters to out (may be NULL), then clears them when reset != 0. */
+enum {
+    OH_CNT_SEGMENTS = 0,        /* segments seen                                                           */
+    OH_CNT_FILTER_ON,           /* d0 + d3 < beta                                                          */
+    OH_CNT_FILTER_ON_PCM,       /* ... with no_p || no_q (PCM / bypass block on a side)                    */
+    OH_CNT_STRONG,              /* strong filter                                                           */
+    OH_CNT_STRONG_PCM,          /* ... with no_p || no_q                                                   */
+    OH_CNT_NORMAL,              /* normal filter                                                           */
+    OH_CNT_NORMAL_PCM,          /* ... with no_p || no_q                                                   */
+    OH_CNT_ND_P,                /* normal filter that also corrects p1 (nd_p, and the P side is written)   */
+    OH_CNT_ND_Q,                /* the same for q1                                                         */
+    OH_CNT_LINES_SKIPPED,       /* lines left alone by |delta| >= 10 * tc                                  */
+    OH_CNT_LINES_PX_CLIPPED,    /* lines where p0 + delta or q0 - delta left the sample range              */
+    OH_CNT_STRONG_TC2_HITS,     /* strong-filter samples whose correction was clipped to +-2 * tc          */
+    OH_CNT_PER_DIR,
+    OH_CNT_INTRA_STRONG_32 = 2 * OH_CNT_PER_DIR,   /* luma 32x32 intra blocks with the strong (bi-linear) smoothing */
+    OH_CNT_N
+};
+void oh_or_counters(uint64_t *out, int n, int reset);
+
 #ifdef __cplusplus
 }
 #endif

@@ -366,6 +366,7 @@ static void FN(intra_pred)(const OhPicParams *p, PX *plane, ptrdiff_t stride, in
                 l = abs(left[-1] + left[63] - 2 * left[31]);
             }
             if (p->strong_intra_smoothing && c_idx == 0 && log2 == 5 && t < lim && l < lim) {
+                g_cnt[OH_CNT_INTRA_STRONG_32]++;
                 ftop[-1] = top[-1];  ftop[63] = top[63];
                 fleft[-1] = left[-1]; fleft[63] = left[63];
                 for (int i = 0; i < 63; i++) {
@@ -391,7 +392,8 @@ static void FN(intra_pred)(const OhPicParams *p, PX *plane, ptrdiff_t stride, in
     else                FN(pred_angular)(bd, src, top, left, stride, log2, c_idx, mode);
 }
 
-/* ---- deblocking of one 8-sample edge: hevcdsp_template.c:1629-1757 ---- */
+/* ---- deblocking of one 8-sample edge: hevcdsp_template.c:1629-1757 ----
+ * The CNT() lines count which decisions the content reached (oh_or_counters, oracle.h); they change no sample. */
 static void FN(loop_filter_luma)(int bd, PX *pix, ptrdiff_t xs, ptrdiff_t ys, int beta,
                                  const int *tc_, const uint8_t *no_p_, const uint8_t *no_q_)
 {
@@ -400,6 +402,9 @@ static void FN(loop_filter_luma)(int bd, PX *pix, ptrdiff_t xs, ptrdiff_t ys, in
         PX *l0 = pix, *l3 = pix + 3 * ys;
         int tc = tc_[seg] << (bd - 8);
         int no_p = no_p_[seg], no_q = no_q_[seg];
+        const int cnt = g_cnt_ctx.dir >= 0 && g_cnt_ctx.bs[seg] > 0;      /* a luma segment with bs > 0 inside oh_or_pass_deblock */
+#define CNT(k) do { if (cnt) g_cnt[g_cnt_ctx.dir * OH_CNT_PER_DIR + (k)]++; } while (0)
+        CNT(OH_CNT_SEGMENTS);
         int dp0 = abs(l0[-3 * xs] - 2 * l0[-2 * xs] + l0[-xs]);
         int dq0 = abs(l0[2 * xs] - 2 * l0[xs] + l0[0]);
         int dp3 = abs(l3[-3 * xs] - 2 * l3[-2 * xs] + l3[-xs]);
@@ -407,6 +412,8 @@ static void FN(loop_filter_luma)(int bd, PX *pix, ptrdiff_t xs, ptrdiff_t ys, in
         int d0 = dp0 + dq0, d3 = dp3 + dq3;
         if (d0 + d3 >= beta)
             continue;
+        CNT(OH_CNT_FILTER_ON);
+        if (no_p || no_q) CNT(OH_CNT_FILTER_ON_PCM);
         int beta3 = beta >> 3, beta2 = beta >> 2, tc25 = (tc * 5 + 1) >> 1;
         int strong =
             abs(l0[-4 * xs] - l0[-xs]) + abs(l0[3 * xs] - l0[0]) < beta3 && abs(l0[-xs] - l0[0]) < tc25 &&
@@ -414,32 +421,44 @@ static void FN(loop_filter_luma)(int bd, PX *pix, ptrdiff_t xs, ptrdiff_t ys, in
             (d0 << 1) < beta2 && (d3 << 1) < beta2;
         if (strong) {
             int tc2 = tc << 1;
+            CNT(OH_CNT_STRONG);
+            if (no_p || no_q) CNT(OH_CNT_STRONG_PCM);
+#define CLIP_TC2(v) oh_clip3_cnt(v, -tc2, tc2, cnt ? &g_cnt[g_cnt_ctx.dir * OH_CNT_PER_DIR + OH_CNT_STRONG_TC2_HITS] : NULL)
             for (int d = 0; d < 4; d++) {
                 PX *q = pix + d * ys;
                 int p3 = q[-4 * xs], p2 = q[-3 * xs], p1 = q[-2 * xs], p0 = q[-xs];
                 int q0 = q[0], q1 = q[xs], q2 = q[2 * xs], q3 = q[3 * xs];
                 if (!no_p) {
-                    q[-xs]     = (PX)(p0 + oh_clip3(((p2 + 2 * p1 + 2 * p0 + 2 * q0 + q1 + 4) >> 3) - p0, -tc2, tc2));
-                    q[-2 * xs] = (PX)(p1 + oh_clip3(((p2 + p1 + p0 + q0 + 2) >> 2) - p1, -tc2, tc2));
-                    q[-3 * xs] = (PX)(p2 + oh_clip3(((2 * p3 + 3 * p2 + p1 + p0 + q0 + 4) >> 3) - p2, -tc2, tc2));
+                    q[-xs]     = (PX)(p0 + CLIP_TC2(((p2 + 2 * p1 + 2 * p0 + 2 * q0 + q1 + 4) >> 3) - p0));
+                    q[-2 * xs] = (PX)(p1 + CLIP_TC2(((p2 + p1 + p0 + q0 + 2) >> 2) - p1));
+                    q[-3 * xs] = (PX)(p2 + CLIP_TC2(((2 * p3 + 3 * p2 + p1 + p0 + q0 + 4) >> 3) - p2));
                 }
                 if (!no_q) {
-                    q[0]      = (PX)(q0 + oh_clip3(((p1 + 2 * p0 + 2 * q0 + 2 * q1 + q2 + 4) >> 3) - q0, -tc2, tc2));
-                    q[xs]     = (PX)(q1 + oh_clip3(((p0 + q0 + q1 + q2 + 2) >> 2) - q1, -tc2, tc2));
-                    q[2 * xs] = (PX)(q2 + oh_clip3(((2 * q3 + 3 * q2 + q1 + q0 + p0 + 4) >> 3) - q2, -tc2, tc2));
+                    q[0]      = (PX)(q0 + CLIP_TC2(((p1 + 2 * p0 + 2 * q0 + 2 * q1 + q2 + 4) >> 3) - q0));
+                    q[xs]     = (PX)(q1 + CLIP_TC2(((p0 + q0 + q1 + q2 + 2) >> 2) - q1));
+                    q[2 * xs] = (PX)(q2 + CLIP_TC2(((2 * q3 + 3 * q2 + q1 + q0 + p0 + 4) >> 3) - q2));
                 }
             }
+#undef CLIP_TC2
         } else {
             int side = (beta + (beta >> 1)) >> 3, tc_2 = tc >> 1;
             int nd_p = dp0 + dp3 < side, nd_q = dq0 + dq3 < side;
+            CNT(OH_CNT_NORMAL);
+            if (no_p || no_q) CNT(OH_CNT_NORMAL_PCM);
+            if (!no_p && nd_p) CNT(OH_CNT_ND_P);
+            if (!no_q && nd_q) CNT(OH_CNT_ND_Q);
             for (int d = 0; d < 4; d++) {
                 PX *q = pix + d * ys;
                 int p2 = q[-3 * xs], p1 = q[-2 * xs], p0 = q[-xs];
                 int q0 = q[0], q1 = q[xs], q2 = q[2 * xs];
                 int delta = (9 * (q0 - p0) - 3 * (q1 - p1) + 8) >> 4;
-                if (abs(delta) >= 10 * tc)
+                if (abs(delta) >= 10 * tc) {
+                    CNT(OH_CNT_LINES_SKIPPED);
                     continue;
+                }
                 delta = oh_clip3(delta, -tc, tc);
+                if ((!no_p && FN(clip_px)(p0 + delta, bd) != p0 + delta) || (!no_q && FN(clip_px)(q0 - delta, bd) != q0 - delta))
+                    CNT(OH_CNT_LINES_PX_CLIPPED);
                 if (!no_p) q[-xs] = (PX)FN(clip_px)(p0 + delta, bd);
                 if (!no_q) q[0]   = (PX)FN(clip_px)(q0 - delta, bd);
                 if (!no_p && nd_p)
@@ -448,6 +467,7 @@ static void FN(loop_filter_luma)(int bd, PX *pix, ptrdiff_t xs, ptrdiff_t ys, in
                     q[xs]      = (PX)FN(clip_px)(q1 + oh_clip3((((q2 + q0 + 1) >> 1) - q1 - delta) >> 1, -tc_2, tc_2), bd);
             }
         }
+#undef CNT
     }
 }
 

@@ -120,6 +120,24 @@ def oracle():
     return _oracle
 
 
+# oracle.h: the decision counters, per edge direction (0 vertical, 1 horizontal) counter k is [d * CNT_PER_DIR + k]
+CNT_NAMES = ("segments", "filter_on", "filter_on_pcm", "strong", "strong_pcm", "normal", "normal_pcm", "nd_p", "nd_q",
+             "lines_skipped", "lines_px_clipped", "strong_tc2_hits")
+CNT_PER_DIR = len(CNT_NAMES)
+CNT_N = 2 * CNT_PER_DIR + 1
+
+
+def oracle_counters(reset=True):
+    """{"v": {name: count}, "h": {name: count}, "intra_strong_32": count} of the pictures the oracle ran on this thread since
+    the last reset (luma deblocking segments with bs > 0; 32x32 luma intra blocks with the strong smoothing)"""
+    fn = oracle().oh_or_counters
+    fn.argtypes, fn.restype = [C.POINTER(C.c_uint64), C.c_int, C.c_int], None
+    out = (C.c_uint64 * CNT_N)()
+    fn(out, CNT_N, int(reset))
+    return {"v": dict(zip(CNT_NAMES, out[:CNT_PER_DIR])), "h": dict(zip(CNT_NAMES, out[CNT_PER_DIR:2 * CNT_PER_DIR])),
+            "intra_strong_32": out[2 * CNT_PER_DIR]}
+
+
 def have_ref():
     return os.path.exists(os.path.join(ORACLE_DIR, "_ref", "libohevc_ref.so")) or os.path.isdir(REF_TREE)
 

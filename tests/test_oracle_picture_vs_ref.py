@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from content import smooth_picture
 from openhevc_amd import frame as F
 from oracle_lib import have_ref, host_pic_array, oracle, plane_ptrs, ref
 
@@ -138,20 +139,6 @@ def decode_order(rec, f):
     g.intra = C.cast(arr, C.POINTER(F.OhIntra))
     g._keep = arr
     return g
-
-
-def smooth_picture(p, rng):
-    """low-activity content so that deblocking decisions and SAO categories all occur"""
-    hp = F.HostPic(p)
-    for c, pl in enumerate(hp.planes):
-        h, w = pl.shape
-        yy, xx = np.mgrid[0:h, 0:w]
-        base = (np.sin(xx / 37.0) + np.cos(yy / 23.0)) * (40 << (p.bit_depth - 8)) + (128 << (p.bit_depth - 8))
-        blocks = rng.integers(-6, 7, size=(h // 8 + 1, w // 8 + 1)) * (1 << (p.bit_depth - 8))
-        noise = rng.integers(-2, 3, size=(h, w)) * (1 << (p.bit_depth - 8))
-        v = base + np.kron(blocks, np.ones((8, 8)))[:h, :w] + noise
-        pl[:] = np.clip(v, 0, (1 << p.bit_depth) - 1).astype(pl.dtype)
-    return hp
 
 
 @pytest.mark.parametrize("w,h,bd,chroma,lc", CASES)
