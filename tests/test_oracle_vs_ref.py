@@ -121,7 +121,7 @@ def test_transform_add_saturates(bd):
             assert np.array_equal(a, b)
 
 
-MC_WIDTHS = [4, 8, 12, 16, 24, 32, 48, 64]
+MC_WIDTHS = [2, 4, 6, 8, 12, 16, 24, 32, 48, 64]             # 2 and 6: the chroma job widths of 4- and 12-wide PUs
 
 
 @pytest.mark.parametrize("bd", DEPTHS)
