@@ -145,6 +145,40 @@ size_t oh_convert_image_bytes(const OhPicParams *p, const OhConvert *cv);
 /* host only: the integers the kernel uses for an RGB conversion of bit_depth-bit pictures, OH_CONV_NCOEFFS of them (n: room in out) */
 int    oh_convert_coeffs(const OhConvert *cv, int bit_depth, int32_t *out, int n);
 
+/* Colour conversion on top of the RGB formats (DESIGN.md §3d has the exact definition, which the tests check bit for bit against
+ * tests/colour_model.py): the non-linear R'G'B' of oh_pics_convert at 16 bit goes through the source's transfer curve to linear light,
+ * one gain on a norm (the HLG OOTF and / or the BT.2390 tone curve), the primaries' 3 x 3 matrix with a clip, and the output curve —
+ * every curve a table of integers built on the host (oh_colour_tables), the kernel all integer but for the one multiply of LINEAR. */
+enum { OH_COL_LINEAR = 0, OH_COL_SRGB, OH_COL_GAMMA24 };      /* out_transfer */
+enum { OH_TONE_NONE = 0, OH_TONE_BT2390 };
+enum { OH_NORM_MAXRGB = 0, OH_NORM_LUMA };
+enum { OH_COL_NA = 4097,          /* entries of the source-curve table A */
+       OH_COL_NP = 1602,          /* entries of the piecewise-logarithmic tables G (gain) and B (output curve) */
+       OH_COL_NMISC = 20 };       /* misc: M[3][3] Q20 (0..8), luminance weights Q14 (9..11), norm (12), output by table (13: 0 LINEAR),
+                                     bits of the f32 K (14), gain stage active (15), matrix stage active (16), rest 0 */
+typedef struct OhColour {
+    int32_t in_transfer;          /* H.273: 16 PQ, 18 HLG, 13 sRGB, 1 / 6 / 14 / 15 SDR video (decoded with the BT.1886 display gamma 2.4) */
+    int32_t in_primaries;         /* H.273: 1 BT.709, 9 BT.2020, 12 P3-D65 */
+    int32_t out_primaries;
+    int32_t out_transfer;         /* OH_COL_* */
+    int32_t tone, norm;           /* OH_TONE_*, OH_NORM_* */
+    float   src_peak;             /* nits: PQ mastering peak (read by the tone curve only), HLG nominal peak Lw, SDR / sRGB peak white */
+    float   dst_peak;             /* nits at output code 1.0 (SRGB / GAMMA24) */
+    float   white;                /* nits at output value 1.0 (LINEAR) */
+} OhColour;
+/* oh_pics_convert with the colour stages behind the matrix: everything oh_pics_convert says about pictures, windows, dst, strides,
+ * ordering, n == 0 and splitting holds; image sizes are those of oh_convert_image_bytes.
+ * OH_E_ARG, nothing written: a null col, an enum value (out_transfer, tone, norm) outside its list, a peak or white that is not finite
+ * and positive.  OH_E_UNSUPPORTED: a YUV format; a transfer or primaries code outside the lists above; U8 or U16 samples with
+ * OH_COL_LINEAR; HLG with OH_NORM_MAXRGB (its OOTF is defined on luminance) or with src_peak outside [400, 10000]; OH_TONE_BT2390
+ * with dst_peak >= src_peak or with a knee at or below black (dst_peak below about a third of src_peak in the PQ domain); a table
+ * whose neighbouring entries differ by more than its interpolation holds (2^19 or more between interpolated entries of G and B,
+ * 2^24 or more or downwards in A). */
+int    oh_pics_convert_colour(OhEngine *e, const int *pic_ids, int n, const OhConvert *cv, const OhColour *col, void *dst,
+                              size_t image_stride, size_t dst_bytes);
+/* host only: exactly the integers the kernel receives — A[OH_COL_NA], G[OH_COL_NP], B[OH_COL_NP], misc[OH_COL_NMISC] */
+int    oh_colour_tables(const OhColour *col, int32_t *A, int32_t *G, int32_t *B, int32_t *misc);
+
 /* Resizing of finished pictures into engine pictures (DESIGN.md §3c has the exact definition, which the tests check bit for bit
  * against tests/resize_model.py): every plane is resampled on its own in integer arithmetic, separably, horizontal pass first, with
  * an anti-aliased triangle (BILINEAR) or Keys cubic a = -1/2 (BICUBIC) filter whose taps are re-normalised at the window's edges.

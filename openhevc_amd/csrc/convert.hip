@@ -15,80 +15,9 @@
  * Templates on what changes the inner loop (input sample type, output sample type, layout); the chroma format, filter, range and
  * channel count are uniform branches.
  */
-#include "../../include/ohevc_hip.h"
-#include "kernels_common.h"
+#include "convert_common.h"
 
 namespace {
-
-constexpr int THREADS = 256;
-enum { L_PLANAR, L_SEMI, L_RGBP, L_RGBI };          /* YUV planar, YUV semi-planar, RGB planar, RGB / RGBA interleaved */
-enum { O_U8, O_U16, O_F16, O_F32 };                 /* output sample type */
-
-template <int O> struct OutT { typedef uint8_t T; };
-template <> struct OutT<O_U16> { typedef uint16_t T; };
-template <> struct OutT<O_F16> { typedef uint16_t T; };
-template <> struct OutT<O_F32> { typedef float T; };
-
-/* n samples of type T at p (a plane row in HBM) -> LDS at lds, as the 16-byte granules that cover them; returns the index (in T) of
- * p[0] in lds.  lds must hold n * sizeof(T) + 30 bytes. */
-template <typename T>
-__device__ __forceinline__ int stage(uint8_t *lds, const void *p, int n)
-{
-    const uintptr_t a = (uintptr_t)p, a0 = a & ~(uintptr_t)15, a1 = (a + (uintptr_t)n * sizeof(T) + 15) & ~(uintptr_t)15;
-    const int g = (int)((a1 - a0) >> 4);
-    for (int i = threadIdx.x; i < g; i += THREADS)
-        *(uint4v *)(lds + 16 * i) = *(const GLOBAL uint4v *)(a0 + 16 * (uintptr_t)i);
-    return (int)((a - a0) / sizeof(T));
-}
-
-/* nbytes bytes to dst from img, the LDS image that holds the byte for dst + i at img[(dst & 15) + i] */
-__device__ __forceinline__ void store_out(uint8_t *dst, const uint8_t *img, int nbytes)
-{
-    const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (uintptr_t)nbytes, a0 = (d0 + 15) & ~(uintptr_t)15, a1 = d1 & ~(uintptr_t)15;
-    const int o = (int)(d0 & 15), t = threadIdx.x;
-    if (a0 >= a1) {
-        for (int i = t; i < nbytes; i += THREADS)
-            G_MUT(uint8_t, dst)[i] = img[o + i];
-        return;
-    }
-    const int head = (int)(a0 - d0), tail = (int)(d1 - a1), g = (int)((a1 - a0) >> 4);
-    if (t < head)
-        G_MUT(uint8_t, dst)[t] = img[o + t];
-    else if (t >= 64 && t - 64 < tail)
-        G_MUT(uint8_t, a1)[t - 64] = img[o + (int)(a1 - d0) + t - 64];
-    for (int i = t; i < g; i += THREADS)                        /* img + o + head is 16-byte aligned: o + head is 0 or 16 */
-        *(GLOBAL uint4v *)(a0 + 16 * (uintptr_t)i) = *(const uint4v *)(img + o + head + 16 * i);
-}
-
-/* the f16 nearest (ties to even) to a non-negative finite f32 below 65520, in integer arithmetic.  A plain conversion of the product
- * below is folded into one v_fma_mixlo_f16, which rounds the exact product to f16 once instead of rounding the f32 product. */
-__device__ __forceinline__ uint16_t f16_rne(float f)
-{
-    const uint32_t x = __float_as_uint(f);
-    if (!x)
-        return 0;
-    const int e = (int)(x >> 23) - 127 + 15;                  /* f16 biased exponent of a normal result */
-    const uint32_t m = (x & 0x7FFFFF) | 0x800000;
-    const int s = min(13 + max(0, 1 - e), 31);                /* significand bits that go: 13, more for a subnormal result */
-    uint32_t q = m >> s;
-    const uint32_t r = m & ((1u << s) - 1), half = 1u << (s - 1);
-    q += (r > half || (r == half && (q & 1))) ? 1u : 0u;
-    return (uint16_t)((e >= 1 ? (uint32_t)(e - 1) << 10 : 0u) + q);   /* a carry out of the significand raises the exponent */
-}
-
-/* an integer RGB value of D bits -> the output sample: u8 / u16 as is, F32 = value x (the f32 nearest to 1/65535), F16 = that f32
- * rounded to nearest-even */
-template <int O>
-__device__ __forceinline__ typename OutT<O>::T out_sample(int v)
-{
-    constexpr float K = 1.0f / 65535.0f;
-    if constexpr (O == O_F32)
-        return __fmul_rn((float)v, K);
-    else if constexpr (O == O_F16)
-        return f16_rne(__fmul_rn((float)v, K));
-    else
-        return (typename OutT<O>::T)v;
-}
 
 /* YUV formats: image row r is a row of the Y plane, of Cb or Cr (planar) or of the interleaved CbCr plane (semi-planar).
  * TI -> O: u8 -> u8 (copy), u16 -> u16 (copy, shifted to the MSB in the semi-planar form), u16 -> u8 (rounded, saturated). */
@@ -159,26 +88,11 @@ __global__ __launch_bounds__(THREADS) void convert_rgb_kernel(const OhConvArgs a
     if (x0 >= W)
         return;
     const int cnt = min(CW, W - x0), X0 = a.left + x0, Y = a.top + y;
-    const int hs = a.cf == 1 || a.cf == 2, vs = a.cf == 1, lin = a.filter;
-    const int bl = stage<TI>(lum, (const uint8_t *)a.src[pic][0] + (size_t)Y * a.pitch[0] + (size_t)X0 * sizeof(TI), cnt);
-    int c_lo = 0, bu0 = 0, bu1 = 0, bv0 = 0, bv1 = 0;
-    if (a.cf) {
-        c_lo = X0 >> hs;
-        const int m = min((X0 + cnt) >> hs, a.cw - 1) - c_lo + 1;                    /* with the right neighbour of the linear filter */
-        const int j0 = Y >> vs;
-        bu0 = stage<TI>(chr, (const uint8_t *)a.src[pic][1] + (size_t)j0 * a.pitch[1] + (size_t)c_lo * sizeof(TI), m);
-        bv0 = stage<TI>(chr + 2 * RB, (const uint8_t *)a.src[pic][2] + (size_t)j0 * a.pitch[2] + (size_t)c_lo * sizeof(TI), m);
-        if (lin && vs) {                                        /* chroma row j sits between luma rows 2j and 2j + 1 */
-            const int j1 = min(max(j0 - 1 + 2 * (Y & 1), 0), a.ch - 1);
-            bu1 = stage<TI>(chr + RB, (const uint8_t *)a.src[pic][1] + (size_t)j1 * a.pitch[1] + (size_t)c_lo * sizeof(TI), m);
-            bv1 = stage<TI>(chr + 3 * RB, (const uint8_t *)a.src[pic][2] + (size_t)j1 * a.pitch[2] + (size_t)c_lo * sizeof(TI), m);
-        }
-    }
+    RgbRows<TI> in;
+    in.stage_rows(a, pic, X0, Y, cnt, lum, chr, RB);
     __syncthreads();
-    const TI *L = (const TI *)lum, *U0 = (const TI *)chr, *U1 = (const TI *)(chr + RB), *V0 = (const TI *)(chr + 2 * RB),
-             *V1 = (const TI *)(chr + 3 * RB);
-    const int cy = a.k[0], crv = a.k[1], cgu = a.k[2], cgv = a.k[3], cbu = a.k[4], yoff = a.k[5], mid = a.k[6], S = a.k[7];
-    const int rnd = 1 << (S - 1), mx = (1 << a.k[8]) - 1, nc = a.nc, cwm = a.cw - 1;
+    const RgbMatrix mt(a.k);
+    const int nc = a.nc;
     const size_t plane = (size_t)W * H;
     uint8_t *dst = (uint8_t *)a.dst + pic * a.image_stride + ((size_t)y * W + x0) * (LAY == L_RGBP ? 1 : nc) * sizeof(TO);
     TO *o0 = (TO *)(out_l[0] + ((uintptr_t)dst & 15));
@@ -188,35 +102,15 @@ __global__ __launch_bounds__(THREADS) void convert_rgb_kernel(const OhConvArgs a
         o2 = (TO *)(out_l[LAY == L_RGBP ? 2 : 0] + ((uintptr_t)(dst + 2 * plane * sizeof(TO)) & 15));
     }
     for (int i = threadIdx.x; i < cnt; i += THREADS) {
-        const int X = X0 + i;
-        int u = mid, v = mid;
-        if (a.cf == 3) {
-            u = U0[bu0 + i]; v = V0[bv0 + i];
-        } else if (a.cf) {
-            const int k = (X >> 1) - c_lo, k2 = (X & 1) ? min((X + 1) >> 1, cwm) - c_lo : k;
-            if (!lin) {
-                u = U0[bu0 + k]; v = V0[bv0 + k];
-            } else {
-                const int hu = U0[bu0 + k] + U0[bu0 + k2], hv = V0[bv0 + k] + V0[bv0 + k2];   /* 2x scale */
-                if (vs) {
-                    u = (3 * hu + U1[bu1 + k] + U1[bu1 + k2] + 4) >> 3;
-                    v = (3 * hv + V1[bv1 + k] + V1[bv1 + k2] + 4) >> 3;
-                } else {
-                    u = (hu + 1) >> 1;
-                    v = (hv + 1) >> 1;
-                }
-            }
-        }
-        const int dy = cy * ((int)L[bl + i] - yoff) + rnd, du = u - mid, dv = v - mid;
-        const int R = min(max((dy + crv * dv) >> S, 0), mx);
-        const int G = min(max((dy + cgu * du + cgv * dv) >> S, 0), mx);
-        const int B = min(max((dy + cbu * du) >> S, 0), mx);
+        int u, v, R, G, B;
+        in.chroma(a, X0 + i, i, mt.mid, u, v);
+        mt.rgb((int)in.L[i], u, v, R, G, B);
         if constexpr (LAY == L_RGBP) {
             o0[i] = out_sample<O>(R); o1[i] = out_sample<O>(G); o2[i] = out_sample<O>(B);
         } else {
             TO *q = o0 + i * nc;
             q[0] = out_sample<O>(R); q[1] = out_sample<O>(G); q[2] = out_sample<O>(B);
-            if (nc == 4) q[3] = out_sample<O>(mx);
+            if (nc == 4) q[3] = out_sample<O>(mt.mx);
         }
     }
     __syncthreads();

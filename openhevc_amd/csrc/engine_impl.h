@@ -193,6 +193,13 @@ struct OhEngine {
     struct Scratch { void *p = nullptr; size_t bytes = 0; };
     Scratch     hash_dev;                /* oh_pics_hash (CRC / checksum): the job table, its tasks and their values in HBM */
     Scratch     resize_dev;              /* oh_pics_resize: the tap tables of the call, then the int16 intermediate of one launch set */
+    Scratch     colour_dev;              /* oh_pics_convert_colour: the three tables of the call (OH_COLT_N int32) */
+    /* the tables of the last OhColour a call built (the host's work: a few thousand pow calls); colour_on_dev: the device copy holds
+     * them too, so a call with the same OhColour copies nothing */
+    OhColour    colour_last;
+    bool        colour_cached = false, colour_on_dev = false;
+    std::vector<int32_t> colour_tab;     /* OH_COLT_N, laid out as on the device */
+    int32_t     colour_misc[OH_COL_NMISC];
     uint32_t    spin_limit = 1u << 22;   /* polls (with s_sleep between them, ~1 s in all) before a waiting workgroup gives up; OHEVC_SPIN_LIMIT */
 };
 

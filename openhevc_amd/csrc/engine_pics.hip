@@ -1,8 +1,9 @@
 /*
  * engine_pics.hip — what the engine does with finished pictures beside the reconstruction path (host side; the kernels are md5.hip,
- * hash.hip, convert.hip and resize.hip): plane upload and download, the two-phase window fetch, picture hashes, conversion to
- * YUV / RGB images and resizing into engine pictures.
+ * hash.hip, convert.hip, colour.hip and resize.hip): plane upload and download, the two-phase window fetch, picture hashes, conversion
+ * to YUV / RGB images, with the colour tables of the HDR forms, and resizing into engine pictures.
  */
+#include <cmath>
 #include "engine_impl.h"
 
 /* at least `bytes` of device scratch, grow-only in 1 MiB steps.  Growing frees the old block: the caller has made sure that nothing
@@ -440,42 +441,55 @@ extern "C" int oh_convert_coeffs(const OhConvert *cv, int bit_depth, int32_t *ou
     return OH_E_UNSUPPORTED;
 }
 
+/* oh_pics_convert and oh_pics_convert_colour (col set: its tables are staged in front of the launches, which are colour.hip's) */
+static int pics_convert(OhEngine *e, const char *who, const int *pic_ids, int n, const OhConvert *cv, const OhColour *col, void *dst,
+                        size_t image_stride, size_t dst_bytes);
+
 extern "C" int oh_pics_convert(OhEngine *e, const int *pic_ids, int n, const OhConvert *cv, void *dst, size_t image_stride, size_t dst_bytes)
 {
     if (!e || n < 0 || !cv || (n && !pic_ids))
         return OH_E_ARG;
     if (!n)
         return OH_OK;
-    { const int rc = check_pics(e, pic_ids, n, "oh_pics_convert"); if (rc) return rc; }
+    return pics_convert(e, "oh_pics_convert", pic_ids, n, cv, nullptr, dst, image_stride, dst_bytes);
+}
+
+static int colour_stage(OhEngine *e, const OhColour *col, OhColArgs *ca);
+
+static int pics_convert(OhEngine *e, const char *who, const int *pic_ids, int n, const OhConvert *cv, const OhColour *col, void *dst,
+                        size_t image_stride, size_t dst_bytes)
+{
+    { const int rc = check_pics(e, pic_ids, n, who); if (rc) return rc; }
     const Pic *p0 = get_pic(e, pic_ids[0]);
     const int other = first_other_params(e, pic_ids, n);
     if (other < n)
-        FAIL(e, OH_E_ARG, "oh_pics_convert: picture %d has other params than picture %d", pic_ids[other], pic_ids[0]);
+        FAIL(e, OH_E_ARG, "%s: picture %d has other params than picture %d", who, pic_ids[other], pic_ids[0]);
     size_t ib = 0;
     std::string why;
-    { const int rc = conv_check(&p0->p, cv, &ib, &why); if (rc) FAIL(e, rc, "oh_pics_convert: %s", why.c_str()); }
+    { const int rc = conv_check(&p0->p, cv, &ib, &why); if (rc) FAIL(e, rc, "%s: %s", who, why.c_str()); }
     const size_t ob = (size_t)conv_sample_bytes(cv, p0->p.bit_depth);
     if (image_stride < ib || image_stride % ob || (uintptr_t)dst % ob)
-        FAIL(e, OH_E_ARG, "oh_pics_convert: image_stride %zu (an image takes %zu bytes) or dst not a multiple of the %zu-byte sample", image_stride, ib, ob);
+        FAIL(e, OH_E_ARG, "%s: image_stride %zu (an image takes %zu bytes) or dst not a multiple of the %zu-byte sample", who, image_stride, ib, ob);
     if (!dst || ib > dst_bytes || (size_t)(n - 1) > (dst_bytes - ib) / image_stride)
-        FAIL(e, OH_E_ARG, "oh_pics_convert: %d images of %zu bytes, %zu apart, do not fit %zu bytes", n, ib, image_stride, dst_bytes);
+        FAIL(e, OH_E_ARG, "%s: %d images of %zu bytes, %zu apart, do not fit %zu bytes", who, n, ib, image_stride, dst_bytes);
     const size_t total = (size_t)(n - 1) * image_stride + ib;
     HIPCHK(e, hipSetDevice(e->device));
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, dst) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->device) {
         (void)hipGetLastError();
-        FAIL(e, OH_E_ARG, "oh_pics_convert: dst is not device memory of device %d", e->device);
+        FAIL(e, OH_E_ARG, "%s: dst is not device memory of device %d", who, e->device);
     }
     void *base = nullptr;
     size_t size = 0;
     if (hipMemGetAddressRange(&base, &size, dst) == hipSuccess) {
         if ((char *)dst + total > (char *)base + size)
-            FAIL(e, OH_E_ARG, "oh_pics_convert: %zu bytes at dst run past the end of its allocation", total);
+            FAIL(e, OH_E_ARG, "%s: %zu bytes at dst run past the end of its allocation", who, total);
     } else {
         (void)hipGetLastError();
     }
-    OhConvArgs a;
-    memset(&a, 0, sizeof(a));
+    OhColArgs ca;
+    OhConvArgs &a = ca.c;
+    memset(&ca, 0, sizeof(ca));
     const OhPicParams &p = p0->p;
     const int bpp = sample_bytes(p.bit_depth);
     for (int c = 0; c < 3; c++) a.pitch[c] = p0->stride[c] * bpp;
@@ -486,9 +500,12 @@ extern "C" int oh_pics_convert(OhEngine *e, const int *pic_ids, int n, const OhC
     a.nc = cv->format == OH_CONV_RGBA ? 4 : 3;
     a.image_stride = image_stride;
     if (cv->format >= OH_CONV_RGB_PLANAR) {
-        const int rc = oh_convert_coeffs(cv, p.bit_depth, a.k, OH_CONV_NCOEFFS);
-        if (rc) FAIL(e, rc, "oh_pics_convert: no coefficients for this conversion");
+        OhConvert k16 = *cv;
+        if (col) k16.sample = OH_CONV_U16;                      /* the colour stages start from the 16-bit R'G'B' */
+        const int rc = oh_convert_coeffs(&k16, p.bit_depth, a.k, OH_CONV_NCOEFFS);
+        if (rc) FAIL(e, rc, "%s: no coefficients for this conversion", who);
     }
+    if (col) { const int rc = colour_stage(e, col, &ca); if (rc) return rc; }
     for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
         const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
         for (int i = 0; i < m; i++) {
@@ -496,10 +513,274 @@ extern "C" int oh_pics_convert(OhEngine *e, const int *pic_ids, int n, const OhC
             for (int c = 0; c < 3; c++) a.src[i][c] = p.chroma_format_idc || !c ? final_planes(q)[c] : nullptr;
         }
         a.dst = (char *)dst + (size_t)i0 * image_stride;
-        ohk_convert(&a, cv->format, cv->sample, m, e->stream);
+        if (col) ohk_colour(&ca, cv->format, cv->sample, m, e->stream);
+        else     ohk_convert(&a, cv->format, cv->sample, m, e->stream);
         HIPCHK(e, hipGetLastError());
     }
     return OH_OK;
+}
+
+/* ---------------- colour conversion (colour.hip) ---------------- */
+namespace {
+const double PQ_M1 = 2610.0 / 16384.0, PQ_M2 = 2523.0 / 4096.0 * 128.0, PQ_C1 = 3424.0 / 4096.0, PQ_C2 = 2413.0 / 4096.0 * 32.0,
+             PQ_C3 = 2392.0 / 4096.0 * 32.0;
+/* ST 2084: signal -> luminance / 10000 and back */
+double pq_eotf(double x)
+{
+    const double xp = pow(std::max(x, 0.0), 1.0 / PQ_M2);
+    return pow(std::max(xp - PQ_C1, 0.0) / (PQ_C2 - PQ_C3 * xp), 1.0 / PQ_M1);
+}
+double pq_inv(double y)
+{
+    const double yp = pow(std::max(y, 0.0), PQ_M1);
+    return pow((PQ_C1 + PQ_C2 * yp) / (1.0 + PQ_C3 * yp), PQ_M2);
+}
+/* BT.2100 HLG inverse OETF: signal -> scene linear, 1 at signal 1 */
+double hlg_inv_oetf(double x)
+{
+    const double a = 0.17883277, b = 1.0 - 4.0 * a, c = 0.5 - a * log(4.0 * a);
+    return x <= 0.5 ? x * x / 3.0 : (exp((x - c) / a) + b) / 12.0;
+}
+double srgb_eotf(double x) { return x <= 0.04045 ? x / 12.92 : pow((x + 0.055) / 1.055, 2.4); }
+double srgb_inv(double l) { return l <= 0.0031308 ? 12.92 * l : 1.055 * pow(l, 1.0 / 2.4) - 0.055; }
+
+bool is_sdr_video(int t) { return t == 1 || t == 6 || t == 14 || t == 15; }
+
+/* BT.2390 EETF, black 0: nits -> nits.  Identity below the knee (exactly), the Hermite spline in the PQ domain above it, the target
+ * peak from the source peak on (the spline ends there with slope 0) */
+struct Eetf {
+    double src_pq, mx, ks;
+    Eetf(double src_peak, double dst_peak) : src_pq(pq_inv(src_peak / 10000.0)), mx(pq_inv(dst_peak / 10000.0) / src_pq), ks(1.5 * mx - 0.5) {}
+    double gain(double nits) const
+    {
+        if (!(nits > 0))
+            return 1.0;
+        const double e1 = std::min(pq_inv(nits / 10000.0) / src_pq, 1.0);
+        if (e1 <= ks)
+            return 1.0;
+        const double t = (e1 - ks) / (1.0 - ks), t2 = t * t, t3 = t2 * t;
+        const double e2 = (2 * t3 - 3 * t2 + 1) * ks + (t3 - 2 * t2 + t) * (1.0 - ks) + (-2 * t3 + 3 * t2) * mx;
+        return 10000.0 * pq_eotf(e2 * src_pq) / nits;
+    }
+};
+
+void inv3(const double P[9], double inv[9])
+{
+    const double det = P[0] * (P[4] * P[8] - P[5] * P[7]) - P[1] * (P[3] * P[8] - P[5] * P[6]) + P[2] * (P[3] * P[7] - P[4] * P[6]);
+    inv[0] = (P[4] * P[8] - P[5] * P[7]) / det; inv[1] = (P[2] * P[7] - P[1] * P[8]) / det; inv[2] = (P[1] * P[5] - P[2] * P[4]) / det;
+    inv[3] = (P[5] * P[6] - P[3] * P[8]) / det; inv[4] = (P[0] * P[8] - P[2] * P[6]) / det; inv[5] = (P[2] * P[3] - P[0] * P[5]) / det;
+    inv[6] = (P[3] * P[7] - P[4] * P[6]) / det; inv[7] = (P[1] * P[6] - P[0] * P[7]) / det; inv[8] = (P[0] * P[4] - P[1] * P[3]) / det;
+}
+
+/* linear RGB -> XYZ of a set of primaries with the D65 white, row-major; false: a code outside the list */
+bool rgb_to_xyz(int prim, double m[9])
+{
+    double xy[6];
+    switch (prim) {
+    case 1:  { const double v[6] = { 0.640, 0.330, 0.300, 0.600, 0.150, 0.060 }; memcpy(xy, v, sizeof(v)); break; }
+    case 9:  { const double v[6] = { 0.708, 0.292, 0.170, 0.797, 0.131, 0.046 }; memcpy(xy, v, sizeof(v)); break; }
+    case 12: { const double v[6] = { 0.680, 0.320, 0.265, 0.690, 0.150, 0.060 }; memcpy(xy, v, sizeof(v)); break; }
+    default: return false;
+    }
+    const double xw = 0.3127, yw = 0.3290, W[3] = { xw / yw, 1.0, (1.0 - xw - yw) / yw };
+    double P[9];
+    for (int i = 0; i < 3; i++) {
+        const double x = xy[2 * i], y = xy[2 * i + 1];
+        P[i] = x / y; P[3 + i] = 1.0; P[6 + i] = (1.0 - x - y) / y;
+    }
+    double inv[9];
+    inv3(P, inv);
+    for (int i = 0; i < 3; i++) {
+        const double S = inv[3 * i] * W[0] + inv[3 * i + 1] * W[1] + inv[3 * i + 2] * W[2];
+        for (int r = 0; r < 3; r++) m[3 * r + i] = P[3 * r + i] * S;
+    }
+    return true;
+}
+
+/* a row of fractions that sum to 1 with q fraction bits, the largest entry corrected so that the integers sum to exactly 2^q */
+void q_row(const double r[3], int q, int32_t out[3])
+{
+    int best = 0, sum = 0;
+    for (int j = 0; j < 3; j++) {
+        out[j] = (int32_t)llround(ldexp(r[j], q));
+        sum += out[j];
+        if (out[j] > out[best]) best = j;
+    }
+    out[best] += (1 << q) - sum;
+}
+
+/* the node of entry k of a piecewise-logarithmic table, in units of 2^-30 of the full scale */
+double node_of(int k) { return k < 128 ? (double)k : ldexp((double)(64 + (k & 63)), (k >> 6) - 1); }
+
+/* rounded values into a table; false: a value, or a step between neighbours from entry `from` on (the entries the kernel interpolates
+ * between), that its interpolation does not hold: max_step or more, or — rising — downwards */
+bool narrow(const std::vector<double> &v, int32_t *out, int64_t max_step, size_t from, bool rising)
+{
+    int64_t prev = 0;
+    for (size_t i = 0; i < v.size(); i++) {
+        if (!std::isfinite(v[i]) || fabs(v[i]) > 2e9)
+            return false;
+        const int64_t r = llround(v[i]);
+        if (i > from && (std::llabs(r - prev) >= max_step || (rising && r < prev)))
+            return false;
+        out[i] = (int32_t)r;
+        prev = r;
+    }
+    return true;
+}
+}
+
+/* what is wrong with an OhColour, by itself: OH_E_ARG, OH_E_UNSUPPORTED or OH_OK */
+static int colour_check(const OhColour *col, std::string *why)
+{
+    char buf[256];
+    if (col->out_transfer < OH_COL_LINEAR || col->out_transfer > OH_COL_GAMMA24 || col->tone < OH_TONE_NONE || col->tone > OH_TONE_BT2390 ||
+        col->norm < OH_NORM_MAXRGB || col->norm > OH_NORM_LUMA) {
+        snprintf(buf, sizeof(buf), "out_transfer %d, tone %d or norm %d outside its list", col->out_transfer, col->tone, col->norm);
+        *why = buf; return OH_E_ARG;
+    }
+    const float pk[3] = { col->src_peak, col->dst_peak, col->white };
+    for (int i = 0; i < 3; i++)
+        if (!std::isfinite(pk[i]) || !(pk[i] > 0)) { *why = "src_peak, dst_peak and white are finite and positive"; return OH_E_ARG; }
+    const int t = col->in_transfer;
+    if (t != 16 && t != 18 && t != 13 && !is_sdr_video(t)) {
+        snprintf(buf, sizeof(buf), "transfer_characteristics %d (16 PQ, 18 HLG, 13 sRGB, 1 / 6 / 14 / 15 SDR video)", t); *why = buf; return OH_E_UNSUPPORTED;
+    }
+    double m[9];
+    if (!rgb_to_xyz(col->in_primaries, m) || !rgb_to_xyz(col->out_primaries, m)) {
+        snprintf(buf, sizeof(buf), "colour_primaries %d -> %d (1 BT.709, 9 BT.2020, 12 P3-D65)", col->in_primaries, col->out_primaries);
+        *why = buf; return OH_E_UNSUPPORTED;
+    }
+    if (t == 18 && col->norm == OH_NORM_MAXRGB) { *why = "HLG takes OH_NORM_LUMA: its OOTF is defined on luminance"; return OH_E_UNSUPPORTED; }
+    if (t == 18 && !(col->src_peak >= 400.0f && col->src_peak <= 10000.0f)) { *why = "HLG with a nominal peak outside [400, 10000] nits"; return OH_E_UNSUPPORTED; }
+    if (col->tone == OH_TONE_BT2390) {
+        if (col->dst_peak >= col->src_peak) { *why = "OH_TONE_BT2390 with dst_peak >= src_peak"; return OH_E_UNSUPPORTED; }
+        if (Eetf(col->src_peak, col->dst_peak).ks <= 0) { *why = "OH_TONE_BT2390 with a knee at or below black"; return OH_E_UNSUPPORTED; }
+    }
+    return OH_OK;
+}
+
+/* the tables in the layout of the device copy (tab: OH_COLT_N int32, zero-padded) and misc */
+static int colour_build(const OhColour *col, int32_t *tab, int32_t *misc, std::string *why)
+{
+    { const int rc = colour_check(col, why); if (rc) return rc; }
+    const int t = col->in_transfer;
+    const bool pq = t == 16, hlg = t == 18;
+    const double Lfs = pq ? 10000.0 : (double)col->src_peak, src = col->src_peak, dstp = col->dst_peak;
+    memset(tab, 0, (size_t)OH_COLT_N * sizeof(int32_t));
+    memset(misc, 0, (size_t)OH_COL_NMISC * sizeof(int32_t));
+    std::vector<double> v((size_t)OH_COL_NA);
+    for (int i = 0; i < OH_COL_NA; i++) {
+        const double x = 16.0 * i / 65535.0;
+        v[i] = ldexp(pq ? pq_eotf(x) : hlg ? hlg_inv_oetf(x) : t == 13 ? srgb_eotf(x) : pow(x, 2.4), 30);
+    }
+    if (!narrow(v, tab, (int64_t)1 << 24, 0, true)) { *why = "the source curve's table falls or steps by 2^24 or more"; return OH_E_UNSUPPORTED; }
+    const bool tone = col->tone == OH_TONE_BT2390;
+    const double gamma = hlg ? 1.2 + 0.42 * log10(src / 1000.0) : 1.0;
+    const Eetf tm(src, dstp);
+    v.resize((size_t)OH_COL_NP);
+    for (int k = 0; k < OH_COL_NP; k++) {
+        const double x = ldexp(node_of(k), -30);
+        double g = 1.0;
+        if (hlg) g = x > 0 ? pow(x, gamma - 1.0) : 0.0;
+        if (tone) g *= tm.gain(hlg ? src * pow(x, gamma) : Lfs * x);
+        v[k] = ldexp(std::min(g, 1.0), 20);
+    }
+    if (!narrow(v, tab + OH_COLT_G, (int64_t)1 << 19, 128, false)) { *why = "the gain table steps by 2^19 or more"; return OH_E_UNSUPPORTED; }
+    if (col->out_transfer != OH_COL_LINEAR) {
+        for (int k = 0; k < OH_COL_NP; k++) {
+            const double x = ldexp(node_of(k), -30) * Lfs / dstp;
+            v[k] = 65535.0 * (col->out_transfer == OH_COL_SRGB ? srgb_inv(x) : pow(x, 1.0 / 2.4));
+        }
+        if (!narrow(v, tab + OH_COLT_B, (int64_t)1 << 19, 128, false)) { *why = "the output curve's table steps by 2^19 or more"; return OH_E_UNSUPPORTED; }
+    }
+    double si[9], so[9], soi[9];
+    rgb_to_xyz(col->in_primaries, si);
+    rgb_to_xyz(col->out_primaries, so);
+    inv3(so, soi);
+    for (int r = 0; r < 3; r++) {
+        double row[3];
+        for (int j = 0; j < 3; j++) row[j] = soi[3 * r] * si[j] + soi[3 * r + 1] * si[3 + j] + soi[3 * r + 2] * si[6 + j];
+        q_row(row, 20, misc + 3 * r);
+        if (col->in_primaries == col->out_primaries)
+            for (int j = 0; j < 3; j++) misc[3 * r + j] = r == j ? 1 << 20 : 0;
+    }
+    q_row(si + 3, 14, misc + 9);
+    misc[12] = col->norm;
+    misc[13] = col->out_transfer != OH_COL_LINEAR;
+    const float K = (float)(Lfs / ((double)col->white * 1073741824.0));
+    if (!std::isfinite(K) || !(K > 0)) { *why = "white is out of the f32 range of the output scale"; return OH_E_UNSUPPORTED; }
+    memcpy(&misc[14], &K, 4);
+    misc[15] = hlg || tone;
+    misc[16] = col->in_primaries != col->out_primaries;
+    return OH_OK;
+}
+
+extern "C" int oh_colour_tables(const OhColour *col, int32_t *A, int32_t *G, int32_t *B, int32_t *misc)
+{
+    if (!col || !A || !G || !B || !misc)
+        return OH_E_ARG;
+    std::vector<int32_t> tab((size_t)OH_COLT_N);
+    int32_t m[OH_COL_NMISC];
+    std::string why;
+    const int rc = colour_build(col, tab.data(), m, &why);
+    if (rc) return rc;
+    memcpy(A, tab.data(), (size_t)OH_COL_NA * 4);
+    memcpy(G, tab.data() + OH_COLT_G, (size_t)OH_COL_NP * 4);
+    memcpy(B, tab.data() + OH_COLT_B, (size_t)OH_COL_NP * 4);
+    memcpy(misc, m, sizeof(m));
+    return OH_OK;
+}
+
+/* the tables of col in the engine's device copy, in front of the launches that follow on the engine stream: built on the host unless
+ * col is the last call's, staged in a pinned buffer of the pool and copied on the engine stream — behind the launches of an earlier
+ * call that read the device copy — unless the device copy holds them already */
+static int colour_stage(OhEngine *e, const OhColour *col, OhColArgs *ca)
+{
+    if (!e->colour_cached || memcmp(&e->colour_last, col, sizeof(*col))) {
+        e->colour_cached = false;
+        e->colour_tab.resize((size_t)OH_COLT_N);
+        std::string why;
+        const int rc = colour_build(col, e->colour_tab.data(), e->colour_misc, &why);
+        if (rc) FAIL(e, rc, "oh_pics_convert_colour: %s", why.c_str());
+        e->colour_last = *col;
+        e->colour_cached = true;
+        e->colour_on_dev = false;
+    }
+    const size_t bytes = (size_t)OH_COLT_N * sizeof(int32_t);
+    if (!e->colour_dev.p) {
+        const int rc = scratch_reserve(e, &e->colour_dev, bytes);
+        if (rc) return rc;
+        e->colour_on_dev = false;
+    }
+    if (!e->colour_on_dev) {
+        OhEngine::Stage *sg = stage_acquire(e, bytes);
+        if (!sg)
+            FAIL(e, OH_E_NOMEM, "oh_pics_convert_colour: no staging buffer for %zu bytes of tables", bytes);
+        memcpy(sg->p, e->colour_tab.data(), bytes);
+        HIPCHK(e, hipMemcpyAsync(e->colour_dev.p, sg->p, bytes, hipMemcpyHostToDevice, e->stream));
+        { const int rc = stage_in_use(e, sg, e->stream); if (rc) return rc; }
+        e->colour_on_dev = true;
+    }
+    ca->tab = (const int32_t *)e->colour_dev.p;
+    memcpy(ca->misc, e->colour_misc, sizeof(ca->misc));
+    return OH_OK;
+}
+
+extern "C" int oh_pics_convert_colour(OhEngine *e, const int *pic_ids, int n, const OhConvert *cv, const OhColour *col, void *dst,
+                                      size_t image_stride, size_t dst_bytes)
+{
+    if (!e || n < 0 || !cv || !col || (n && !pic_ids))
+        return OH_E_ARG;
+    std::string why;
+    { const int rc = colour_check(col, &why); if (rc) FAIL(e, rc, "oh_pics_convert_colour: %s", why.c_str()); }
+    if (cv->format >= OH_CONV_PLANAR && cv->format <= OH_CONV_SEMIPLANAR)
+        FAIL(e, OH_E_UNSUPPORTED, "oh_pics_convert_colour: format %d is a YUV format", cv->format);
+    if (col->out_transfer == OH_COL_LINEAR && (cv->sample == OH_CONV_U8 || cv->sample == OH_CONV_U16))
+        FAIL(e, OH_E_UNSUPPORTED, "oh_pics_convert_colour: OH_COL_LINEAR takes F16 or F32 samples");
+    if (!n)
+        return OH_OK;
+    return pics_convert(e, "oh_pics_convert_colour", pic_ids, n, cv, col, dst, image_stride, dst_bytes);
 }
 
 /* ---------------- resizing into engine pictures (resize.hip) ---------------- */

@@ -39,6 +39,17 @@ struct OhConvArgs {
     int32_t     k[9];            /* oh_convert_coeffs: cy, crv, cgu, cgv, cbu, yoff, mid, S, D */
 };
 
+/* colour conversion (colour.hip): the geometry and the matrix of an RGB conversion (k: the coefficients for 16 bit), the
+ * integers of oh_colour_tables' misc, and the three tables in device memory that the engine owns and fills on the stream in front of the
+ * launches: A at int32 0, G at OH_COLT_G, B at OH_COLT_B, OH_COLT_N in all (each table padded to whole 16-byte granules). */
+enum { OH_COLT_G = 4100, OH_COLT_B = 4100 + 1604, OH_COLT_N = 4100 + 2 * 1604,
+       OH_COL_ROWS = 8 };            /* image rows per workgroup: it loads the tables once for all of them */
+struct OhColArgs {
+    OhConvArgs     c;
+    const int32_t *tab;
+    int32_t        misc[20];         /* OH_COL_NMISC */
+};
+
 /* picture resizing (resize.hip): what one launch set needs, by value in the kernel arguments like OhConvArgs.  Two plane
  * classes (0 luma, 1 chroma), each with its own geometry and tap tables; the tables live in device memory that the engine owns and
  * fills (engine_pics.hip: oh_pics_resize) on the stream in front of the launches. */
@@ -80,6 +91,8 @@ void ohk_resize(const OhResizeArgs *a, int n, int pad, hipStream_t st);
 void ohk_md5(const OhMd5Job *jobs, int n, void *digests, hipStream_t st);
 /* format / sample: OH_CONV_* (checked by the caller); n pictures of a.src */
 void ohk_convert(const OhConvArgs *a, int format, int sample, int n, hipStream_t st);
+/* format: an RGB format, sample: U8 .. F32 (checked by the caller); n pictures of a.c.src */
+void ohk_colour(const OhColArgs *a, int format, int sample, int n, hipStream_t st);
 void ohk_hash(int kind, const OhMd5Job *jobs, const uint32_t *first, const uint32_t *task_map, int n_jobs, int n_tasks, uint32_t *partials,
               uint32_t *out, hipStream_t st);
 void ohk_inter(const OhBatch *B, int n, const OhPicParams *p, uint32_t max_luma, uint32_t max_chroma, hipStream_t st);

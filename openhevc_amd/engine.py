@@ -54,6 +54,40 @@ def make_convert(fmt, sample, window=(0, 0, 0, 0), matrix=1, full_range=False, c
     return OhConvert(conv_format(fmt), int(sample), int(matrix), int(bool(full_range)), 1 if chroma == "linear" else 0, OhWindow(*window))
 
 
+class OhColour(C.Structure):                                  # include/ohevc_hip.h
+    _fields_ = [("in_transfer", C.c_int32), ("in_primaries", C.c_int32), ("out_primaries", C.c_int32), ("out_transfer", C.c_int32),
+                ("tone", C.c_int32), ("norm", C.c_int32), ("src_peak", C.c_float), ("dst_peak", C.c_float), ("white", C.c_float)]
+
+
+COL_OUT = {"linear": 0, "srgb": 1, "gamma24": 2}                                        # OH_COL_LINEAR .. OH_COL_GAMMA24
+COL_TONE = {"none": 0, "bt2390": 1}                                                     # OH_TONE_NONE, OH_TONE_BT2390
+COL_NORM = {"maxrgb": 0, "luma": 1}                                                     # OH_NORM_MAXRGB, OH_NORM_LUMA
+COL_NA, COL_NP, COL_NMISC = 4097, 1602, 20
+
+
+def make_colour(in_transfer, in_primaries, out="srgb", out_primaries=1, tone="bt2390", norm="maxrgb", src_peak=1000.0, dst_peak=100.0,
+                white=203.0):
+    """OhColour for oh_pics_convert_colour: in_transfer / in_primaries / out_primaries are H.273 codes, out "srgb", "gamma24" or
+    "linear", tone "bt2390" or "none", norm "maxrgb" or "luma" (HLG takes "luma"); the peaks and white in nits"""
+    for name, v, d in (("out", out, COL_OUT), ("tone", tone, COL_TONE), ("norm", norm, COL_NORM)):
+        if v not in d:
+            raise ValueError(f"{name} must be one of {sorted(d)}, not {v!r}")
+    return OhColour(int(in_transfer), int(in_primaries), int(out_primaries), COL_OUT[out], COL_TONE[tone], COL_NORM[norm],
+                    float(src_peak), float(dst_peak), float(white))
+
+
+def colour_tables(col):
+    """oh_colour_tables (host only): (A, G, B, misc) as int32 arrays, exactly the integers the kernel receives"""
+    A, G, B, misc = np.zeros(COL_NA, np.int32), np.zeros(COL_NP, np.int32), np.zeros(COL_NP, np.int32), np.zeros(COL_NMISC, np.int32)
+    P = C.POINTER(C.c_int32)
+    rc = lib().oh_colour_tables(C.byref(col), A.ctypes.data_as(P), G.ctypes.data_as(P), B.ctypes.data_as(P), misc.ctypes.data_as(P))
+    if rc != 0:
+        err = EngineError(f"oh_colour_tables failed ({rc})")
+        err.code = rc
+        raise err
+    return A, G, B, misc
+
+
 class OhResize(C.Structure):                                  # include/ohevc_hip.h
     _fields_ = [("filter", C.c_int32), ("win", OhWindow), ("width", C.c_int32), ("height", C.c_int32)]
 
@@ -155,6 +189,8 @@ def lib():
         L.oh_convert_image_bytes.argtypes = [C.POINTER(F.OhPicParams), C.POINTER(OhConvert)]
         L.oh_convert_image_bytes.restype = C.c_size_t
         L.oh_convert_coeffs.argtypes = [C.POINTER(OhConvert), I, C.POINTER(C.c_int32), I]
+        L.oh_pics_convert_colour.argtypes = [V, C.POINTER(C.c_int), I, C.POINTER(OhConvert), C.POINTER(OhColour), V, C.c_size_t, C.c_size_t]
+        L.oh_colour_tables.argtypes = [C.POINTER(OhColour)] + [C.POINTER(C.c_int32)] * 4
         L.oh_pics_resize.argtypes = [V, C.POINTER(C.c_int), C.POINTER(C.c_int), I, C.POINTER(OhResize)]
         L.oh_resize_taps.argtypes = [I, I, I, I, C.POINTER(C.c_int32), C.POINTER(C.c_int16), I, C.POINTER(C.c_int)]
         L.oh_resize_max_taps.argtypes = [I, I, I]
@@ -339,12 +375,14 @@ class Engine:
             return [(0, [bytes(out[i].md5[c]) for c in range(3)]) for i in range(n)]
         return [(hash_type, list(out[i].crc if hash_type == 1 else out[i].checksum)) for i in range(n)]
 
-    def pics_convert(self, pids, fmt, *, dtype=None, window=(0, 0, 0, 0), matrix=1, full_range=False, chroma="linear", out=None):
+    def pics_convert(self, pids, fmt, *, dtype=None, window=(0, 0, 0, 0), matrix=1, full_range=False, chroma="linear", out=None,
+                     colour=None):
         """finished pictures -> one torch tensor on the engine's device (oh_pics_convert): fmt "planar" / "semiplanar" (N, rows, W),
         "rgb_planar" (N, 3, H, W), "rgb" / "rgba" (N, H, W, 3 | 4).  dtype: None (YUV: the stored samples, RGB: uint8), torch.uint8,
         torch.uint16 (YUV: the stored samples of a picture above 8 bit; an 8-bit picture has no uint16 YUV form and raises),
         torch.float16 or torch.float32.  window = (left, right, top, bottom), luma samples.  out: a preallocated contiguous tensor of
-        that shape, dtype and device.  Ordered with torch both ways: the engine stream waits for torch's current
+        that shape, dtype and device.  colour: an OhColour (make_colour) sends an RGB format through oh_pics_convert_colour: the
+        source's transfer curve, tone curve, primaries and the output curve behind the matrix.  Ordered with torch both ways: the engine stream waits for torch's current
         stream before it writes, torch's current stream waits for the engine stream afterwards.  torch must have been imported before
         the first Engine was created (one HIP runtime)."""
         import torch
@@ -393,8 +431,12 @@ class Engine:
                 self._torch_stream = torch.cuda.ExternalStream(self.stream() or 0, device=dev)
             es = self._torch_stream
             es.wait_stream(cur)                               # the allocator may hand out memory a queued kernel still uses
-        self._chk(self.L.oh_pics_convert(self.h, (C.c_int * n)(*pids), n, C.byref(cv), C.c_void_p(out.data_ptr()), ib,
-                                         out.numel() * esz), "oh_pics_convert")
+        if colour is None:
+            self._chk(self.L.oh_pics_convert(self.h, (C.c_int * n)(*pids), n, C.byref(cv), C.c_void_p(out.data_ptr()), ib,
+                                             out.numel() * esz), "oh_pics_convert")
+        else:
+            self._chk(self.L.oh_pics_convert_colour(self.h, (C.c_int * n)(*pids), n, C.byref(cv), C.byref(colour),
+                                                    C.c_void_p(out.data_ptr()), ib, out.numel() * esz), "oh_pics_convert_colour")
         if not same:
             # torch's stream waits for the write, so whatever torch does with the memory later (a free and a reuse included) is ordered
             # behind it.  No record_stream on the engine stream: the image usually outlives the engine, and the allocator would record
