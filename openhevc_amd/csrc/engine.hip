@@ -1,7 +1,8 @@
 /*
- * engine.hip — host side of the MI355X engine: device-resident pictures (the DPB lives in HBM),
- * work-list upload, pass scheduling on one HIP stream, per-pass event timing.  What runs on finished
- * pictures beside that path is in engine_pics.hip and engine_shvc.hip; engine_impl.h is what they share.
+ * engine.hip — host side of the MI355X engine: device-resident pictures (the DPB lives in HBM), staging buffers,
+ * pass scheduling on one HIP stream, release of executed work lists, per-pass event timing.  Work lists are handed over
+ * in engine_handover.hip; what runs on finished pictures beside that path is in engine_pics.hip and engine_shvc.hip;
+ * engine_impl.h is what they share.
  * C ABI in include/ohevc_hip.h.  No CPU fallback exists: without a usable device every entry
  * point returns OH_E_HIP.
  */
@@ -138,49 +139,6 @@ extern "C" int oh_engine_memory(OhEngine *e, uint64_t out[6])
 extern "C" const char *oh_engine_last_error(const OhEngine *e) { return e ? e->err.c_str() : "no engine"; }
 extern "C" void *oh_engine_stream(OhEngine *e) { return e ? (void *)e->stream : nullptr; }
 
-static hipEvent_t sync_event_get(OhEngine *e)
-{
-    hipEvent_t ev = nullptr;
-    if (!e->sync_events.empty()) { ev = e->sync_events.back(); e->sync_events.pop_back(); return ev; }
-    return hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess ? ev : nullptr;
-}
-static void sync_event_put(OhEngine *e, hipEvent_t ev)
-{
-    if (!ev) return;
-    if (e->sync_events.size() < 4096) e->sync_events.push_back(ev); else (void)hipEventDestroy(ev);
-}
-
-/* arenas go back to the engine's pool.  in_flight: kernels enqueued on the engine stream may still read the arena — an event
- * recorded there now tells the copy stream when the next work list may overwrite it. */
-static void free_dev_frame(OhEngine *e, OhDevFrame *df, bool in_flight = false)
-{
-    if (!df)
-        return;
-    if (e && df->ready)
-        sync_event_put(e, df->ready);
-    if (df->sum_host) {
-        if (e && e->sum_pool.size() < 4096) e->sum_pool.push_back(df->sum_host);
-        else (void)hipHostFree(df->sum_host);
-    }
-    if (df->arena) {
-        if (e && e->arenas.size() < 1024) {
-            hipEvent_t fe = nullptr;
-            if (in_flight && (fe = sync_event_get(e)) != nullptr && hipEventRecord(fe, e->stream) != hipSuccess) {
-                sync_event_put(e, fe);
-                fe = nullptr;
-            }
-            if (in_flight && !fe)
-                (void)hipStreamSynchronize(e->stream);           /* no event to be had: wait instead */
-            e->arenas.push_back({ df->arena, df->arena_bytes, fe });
-        } else {
-            if (in_flight) (void)hipStreamSynchronize(e->stream);
-            (void)hipFree(df->arena);
-            if (e) { e->arenas_alive--; e->arena_bytes_alive -= df->arena_bytes; }
-        }
-    }
-    delete df;
-}
-
 extern "C" int oh_engine_sync(OhEngine *e)
 {
     if (!e)
@@ -235,7 +193,7 @@ extern "C" void oh_engine_destroy(OhEngine *e)
 }
 
 /* ---------------- pictures ---------------- */
-static int check_params(OhEngine *e, const OhPicParams *p)
+int check_params(OhEngine *e, const OhPicParams *p)
 {
     if (!p || p->width <= 0 || p->height <= 0 || p->width > 16384 || p->height > 16384)
         FAIL(e, OH_E_ARG, "bad picture size");
@@ -375,23 +333,6 @@ extern "C" int oh_pic_set_final_half(OhEngine *e, int pic_id, int half)
     return OH_OK;
 }
 
-/* n boundary strengths (0..2, one per byte: hevc_filter.c's vertical_bs / horizontal_bs) -> (n + 3) / 4 bytes, entry i in bits
- * 2 (i & 3) of byte i >> 2 — the form the deblock pass reads.  Four bytes per multiply: the 2-bit fields land in the top byte. */
-void pack_bs(uint8_t *dst, const uint8_t *src, size_t n)
-{
-    size_t i = 0;
-    for (; i + 4 <= n; i += 4) {
-        uint32_t x;
-        memcpy(&x, src + i, 4);
-        dst[i >> 2] = (uint8_t)(((x & 0x03030303u) * 0x01041040u) >> 24);
-    }
-    if (i < n) {
-        uint32_t v = 0;
-        for (size_t k = i; k < n; k++) v |= (uint32_t)(src[k] & 3) << ((k & 3) * 2);
-        dst[i >> 2] = (uint8_t)v;
-    }
-}
-
 /* a new pinned buffer of at least `bytes` (4 MiB steps) with its event, not busy; false: nothing was allocated */
 bool stage_create(OhEngine::Stage *c, size_t bytes)
 {
@@ -446,486 +387,6 @@ int stage_in_use(OhEngine *e, OhEngine::Stage *sg, hipStream_t st)
     HIPCHK(e, hipEventRecord(sg->done, st));
     sg->busy = true;
     return OH_OK;
-}
-
-/* ---------------- work lists ---------------- */
-static void fill_planes(DevPlanes *dp, const Pic *p, bool use_b)
-{
-    for (int c = 0; c < 3; c++) {
-        dp->p[c] = use_b ? p->b[c] : p->a[c];
-        dp->stride[c] = p->stride[c];
-        dp->w[c] = p->w[c];
-        dp->h[c] = p->h[c];
-    }
-}
-
-static bool same_geometry(const OhPicParams &a, const OhPicParams &b)
-{
-    return a.width == b.width && a.height == b.height && a.bit_depth == b.bit_depth && a.chroma_format_idc == b.chroma_format_idc;
-}
-
-/* ---------------------------------------------------------------------------------------------------------------------
- * Hand-over of a work list.  The host copies the RAW lists (include/ohevc_frame.h, exactly as recorded) into one pinned
- * buffer, counts what sizes the device arena — blocks per PU, transform blocks per size: two light loops — and enqueues on the
- * copy stream:   H2D copy  ->  preparation kernels (prep.hip: validation of every index a pass kernel will follow, the
- * <= 8x8 MC block lists, the transform-size buckets, the intra block descriptors, schedule and statistics)  ->
- * boundary strengths from the motion field when the list carries bs_in (bs.hip)  ->  the summary back to pinned memory  ->
- * `ready`.  Nothing of it touches samples, so it overlaps the passes of the pictures before.  A malformed list is
- * reported by the first oh_frame(s)_execute that includes it (OH_E_ARG, before any of its passes is launched).
- * ------------------------------------------------------------------------------------------------------------------- */
-static int check_host_side(OhEngine *e, const OhFrame *f, const Pic *cur, OhPrepCounts *cnt, uint32_t tu_cnt[4], uint32_t *n_cross,
-                           bool *any_dense, uint16_t *ref_used, uint32_t *ref_ok, std::vector<uint32_t> &pu_off)
-{
-    const OhPicParams &p = f->p;
-    *ref_ok = 0; *ref_used = 0; *n_cross = 0; *any_dense = false;
-    for (int i = 0; i < OH_MAX_REFS; i++) {
-        Pic *r = get_pic(e, f->ref_pics[i]);
-        if (r && same_geometry(r->p, p) && r != cur)
-            *ref_ok |= 1u << i;
-    }
-    if ((f->n_pu && !f->pu) || (f->n_wp && !f->wp) || (f->n_tu && !f->tu) || (f->n_intra && !f->intra))
-        FAIL(e, OH_E_ARG, "a non-zero item count comes with a NULL array (pu / wp / tu / intra)");
-    /* blocks per PU: sizes the MC block lists (prep_pu_scan repeats the sums on the GPU and validates every PU) */
-    uint64_t nl = 0, nc = 0;
-    const int hs = oh_hshift(&p, 1), vs = oh_vshift(&p, 1), two = p.chroma_format_idc ? 2 : 0;
-    if ((uint64_t)f->n_pu * 2048 >= (1ull << 31))
-        FAIL(e, OH_E_ARG, "PU list too long");
-    pu_off.resize(2 * ((size_t)f->n_pu + 1));
-    uint32_t *ol = pu_off.data(), *oc = ol + f->n_pu + 1;       /* running sums: where every PU's blocks start in the two lists */
-    for (uint32_t i = 0; i < f->n_pu; i++) {
-        const OhPu &pu = f->pu[i];
-        ol[i] = (uint32_t)nl; oc[i] = (uint32_t)nc;
-        nl += (uint64_t)(((pu.w + 7) >> 3) * ((pu.h + 7) >> 3));
-        nc += (uint64_t)(two * ((((pu.w >> hs) + 7) >> 3) * (((pu.h >> vs) + 7) >> 3)));
-        for (int l = 0; l < 2; l++)
-            if (pu.ref[l] < OH_MAX_REFS) *ref_used |= (uint16_t)(1u << pu.ref[l]);
-    }
-    ol[f->n_pu] = (uint32_t)nl; oc[f->n_pu] = (uint32_t)nc;
-    for (uint32_t i = 0; i < f->n_wp; i++)
-        if (f->wp[i].log2_denom[0] > 7 || f->wp[i].log2_denom[1] > 7)
-            FAIL(e, OH_E_ARG, "weights %u: log2 denominator out of range", i);
-    tu_cnt[0] = tu_cnt[1] = tu_cnt[2] = tu_cnt[3] = 0;
-    for (uint32_t i = 0; i < f->n_tu; i++) {                  /* launch sizes of the residual pass; is any block dense? */
-        const OhTu &t = f->tu[i];
-        tu_cnt[(t.log2_size - 2) & 3]++;
-        *n_cross += (t.flags & OH_TUF_CROSS) != 0;
-        *any_dense = *any_dense || !(t.flags & OH_TUF_SPARSE);
-    }
-    if (*any_dense && f->n_coeff && !f->coeffs)
-        FAIL(e, OH_E_ARG, "dense transform blocks but coeffs[] is NULL");
-    if (*n_cross && !f->tu_cross)
-        FAIL(e, OH_E_ARG, "cross-component blocks without tu_cross[]");
-    if (f->n_intra && p.constrained_intra_pred && !f->is_intra)
-        FAIL(e, OH_E_ARG, "constrained_intra_pred without the is_intra map");
-    if (f->n_intra) {
-        /* the level table is the contract behind the waits between CTUs (prep_intra_wait: a CTU waits only for lower levels), and
-         * prep_intra_ctu looks every entry's level up in it: checked here; everything below it on the GPU */
-        if (!f->level_start || !f->n_levels || !f->ictu || !f->n_ictu || !f->sub_start || !f->n_sub ||
-            f->level_start[0] != 0 || f->level_start[f->n_levels] != f->n_ictu)
-            FAIL(e, OH_E_ARG, "intra wavefront tables inconsistent");
-        for (uint32_t l = 0; l < f->n_levels; l++)
-            if (f->level_start[l] > f->level_start[l + 1])
-                FAIL(e, OH_E_ARG, "intra level table not monotonic");
-    }
-    if (p.deblock_enabled) {
-        const OhBsInputs *bi = f->bs_in;                      /* boundary strengths derived on the GPU instead of handed over */
-        if (bi && (!bi->mvf || !bi->cbf_luma || !bi->call_log2 || !bi->ctb_flags))
-            FAIL(e, OH_E_ARG, "bs_in: all four maps are required");
-        if (bi && (p.log2_min_pu_size < 2 || p.log2_min_tb_size < 2))
-            FAIL(e, OH_E_ARG, "bs_in: min PU / TB size below 4");
-        if (bi) {
-            const size_t n_cells = (size_t)(p.width >> p.log2_min_tb_size) * (p.height >> p.log2_min_tb_size);
-            for (size_t i = 0; i < n_cells; i++)
-                if (bi->call_log2[i] && (bi->call_log2[i] < p.log2_min_tb_size || bi->call_log2[i] > p.log2_ctb_size))
-                    FAIL(e, OH_E_ARG, "bs_in: call_log2[%zu] = %d is not a block size of this picture", i, bi->call_log2[i]);
-        }
-        if ((!bi && (!f->vertical_bs || !f->horizontal_bs || f->bs_size < oh_bs_size(&p))) || !f->qp_y_tab || !f->deblock)
-            FAIL(e, OH_E_ARG, "deblock side arrays missing or too small");
-    }
-    if ((p.pcm_loop_filter_disable || p.transquant_bypass_enable) && !f->is_pcm)
-        FAIL(e, OH_E_ARG, "is_pcm map required when pcm loop-filter disable / transquant bypass is on");
-    cnt->n_pu = f->n_pu; cnt->n_mc_luma = (uint32_t)nl; cnt->n_mc_chroma = (uint32_t)nc; cnt->n_tu = f->n_tu;
-    cnt->n_intra = f->n_intra; cnt->n_sub = f->n_intra ? f->n_sub : 0; cnt->n_ictu = f->n_intra ? f->n_ictu : 0;
-    return OH_OK;
-}
-
-/* pinned block the summary of one work list lands in */
-static void *summary_block_get(OhEngine *e)
-{
-    void *p = nullptr;
-    if (!e->sum_pool.empty()) { p = e->sum_pool.back(); e->sum_pool.pop_back(); return p; }
-    return hipHostMalloc(&p, sizeof(DevSummary), hipHostMallocDefault) == hipSuccess ? p : nullptr;
-}
-
-/* the host part of one hand-over and its H2D copy; finish_uploads() enqueues the preparation kernels behind it */
-static int upload_one(OhEngine *e, const OhFrame *f, OhDevFrame **out)
-{
-    *out = nullptr;
-    int rc = check_params(e, &f->p);
-    if (rc)
-        return rc;
-    Pic *cur = get_pic(e, f->cur_pic);
-    if (!cur || !same_geometry(cur->p, f->p))
-        FAIL(e, OH_E_ARG, "cur_pic %d is not an allocated picture of this geometry", f->cur_pic);
-    static const bool timing = getenv("OHEVC_UPLOAD_TIMING") != nullptr;      /* diagnostic: where the host time of an upload goes */
-    auto tnow = [] { return std::chrono::steady_clock::now(); };
-    auto t_begin = tnow();
-    OhPrepCounts cnt;
-    uint32_t tu_cnt[4], n_cross = 0, ref_ok = 0;
-    uint16_t ref_used = 0;
-    bool any_dense = false;
-    static thread_local std::vector<uint32_t> pu_off;
-    HostTimer t_all(e, OH_HT_UPLOAD);
-    { HostTimer t(e, OH_HT_UPLOAD_COUNT);
-    rc = check_host_side(e, f, cur, &cnt, tu_cnt, &n_cross, &any_dense, &ref_used, &ref_ok, pu_off);
-    }
-    if (rc)
-        return rc;
-    auto t_valid = tnow();
-    HIPCHK(e, hipSetDevice(e->device));
-
-    const OhPicParams &p = f->p;
-    const size_t n_ctb = (size_t)oh_ctb_width(&p) * oh_ctb_height(&p);
-    const size_t n_pcm = (size_t)oh_min_pu_width(&p) * oh_min_pu_height(&p);
-    const bool has_sao = p.sao_enabled && f->sao;
-    const bool has_db = p.deblock_enabled != 0;
-
-    /* arena: [copied: header, raw lists, side arrays, coefficient pool] [device only: prepared lists, scratch, residual pool] */
-    struct Seg { const void *src; size_t bytes, off; size_t pack_n; };     /* pack_n != 0: src holds pack_n boundary strengths, one per byte */
-    Seg seg[56];
-    int ns = 0;
-    size_t total = 0;
-    auto add = [&](const void *src, size_t bytes) {
-        if (ns >= 56) abort();                                  /* a segment was added without growing seg[] */
-        seg[ns].src = src; seg[ns].bytes = bytes; seg[ns].off = total; seg[ns].pack_n = 0;
-        total += align_up(bytes ? bytes : 1, 256);
-        return ns++;
-    };
-    DevFrame hd;
-    memset(&hd, 0, sizeof(hd));
-    int s_hdr = add(&hd, sizeof(DevFrame));
-    int s_pu = add(f->pu, (size_t)f->n_pu * sizeof(OhPu));
-    int s_puoff = add(pu_off.data(), 2 * ((size_t)f->n_pu + 1) * sizeof(uint32_t));
-    int s_wp = add(f->wp, (size_t)f->n_wp * sizeof(OhWeights));
-    int s_tur = add(f->tu, (size_t)f->n_tu * sizeof(OhTu));
-    int s_tusp = add(f->tu_sparse, f->tu_sparse ? (size_t)f->n_tu * sizeof(uint32_t) : 0);
-    int s_tucr = add(f->tu_cross, f->tu_cross ? (size_t)f->n_tu * sizeof(uint32_t) : 0);
-    int s_sparse = add(f->sparse, (size_t)(f->sparse ? f->n_sparse : 0) * sizeof(uint32_t));
-    int s_scaling = add(f->scaling, f->scaling ? sizeof(OhScalingList) : 0);
-    int s_inr = add(f->intra, (size_t)f->n_intra * sizeof(OhIntra));
-    int s_ictur = add(cnt.n_ictu ? f->ictu : nullptr, (size_t)cnt.n_ictu * sizeof(OhIntraCtu));
-    const uint32_t n_levels = f->n_intra ? f->n_levels : 0;
-    int s_lvl = add(n_levels ? f->level_start : nullptr, n_levels ? ((size_t)n_levels + 1) * sizeof(uint32_t) : 0);
-    int s_sub = add(cnt.n_sub ? f->sub_start : nullptr, cnt.n_sub ? ((size_t)cnt.n_sub + 1) * sizeof(uint32_t) : 0);
-    const bool cip = p.constrained_intra_pred && f->is_intra;
-    int s_isin = add(cip ? f->is_intra : nullptr, cip ? n_pcm : 0);
-    const OhBsInputs *bsi = has_db ? f->bs_in : nullptr;
-    const size_t bs_bytes = bsi ? oh_bs_size(&p) : f->bs_size;
-    /* the grids cross PCIe and live in HBM four strengths to the byte (0..2 each: 2 bits) — a megabyte less per 4K picture */
-    const size_t bs_packed = (bs_bytes + 3) / 4;
-    int s_vbs = add(has_db && !bsi ? f->vertical_bs : nullptr, has_db ? bs_packed : 0);    /* with bs_in: written by bs_kernel after the copy */
-    int s_hbs = add(has_db && !bsi ? f->horizontal_bs : nullptr, has_db ? bs_packed : 0);
-    const bool bs_packed_in = (f->flags & OH_FRAME_BS_PACKED) != 0;          /* the grids come four to the byte already */
-    if (has_db && !bsi && !bs_packed_in) seg[s_vbs].pack_n = seg[s_hbs].pack_n = bs_bytes;
-    const size_t n_mtb = (size_t)(p.width >> p.log2_min_tb_size) * (p.height >> p.log2_min_tb_size);
-    int s_mvf = add(bsi ? bsi->mvf : nullptr, bsi ? n_pcm * sizeof(OhMvField) : 0);
-    int s_cbf = add(bsi ? bsi->cbf_luma : nullptr, bsi ? n_mtb : 0);
-    int s_call = add(bsi ? bsi->call_log2 : nullptr, bsi ? n_mtb : 0);
-    int s_bsf = add(bsi ? bsi->ctb_flags : nullptr, bsi ? n_ctb : 0);
-    int s_qp = add(has_db ? f->qp_y_tab : nullptr, has_db ? oh_qp_tab_size(&p) : 0);
-    /* the PCM / bypass map is read by the deblock and SAO passes only under these two flags (hevc_filter.c:180, 337; deblock.hip, sao.hip):
-     * without them its half megabyte per 4K picture stays on the host */
-    const bool need_pcm = f->is_pcm && (p.pcm_loop_filter_disable || p.transquant_bypass_enable);
-    int s_pcm = add(need_pcm ? f->is_pcm : nullptr, need_pcm ? n_pcm : 0);
-    int s_db = add(has_db ? f->deblock : nullptr, has_db ? n_ctb * sizeof(OhDeblockCtb) : 0);
-    int s_sao = add(has_sao ? f->sao : nullptr, has_sao ? n_ctb * sizeof(OhSaoCtb) : 0);
-    const bool has_pend = has_sao && f->sao_pending && oh_sao_stale_config(&p);     /* tiled pictures: the driver order as bits per CTB */
-    int s_pend = add(has_pend ? f->sao_pending : nullptr, has_pend ? n_ctb : 0);
-    int s_coef = add(f->coeffs, (size_t)f->n_coeff * sizeof(int16_t));
-    /* the dense pool is the last copied segment: when every block came as levels nothing of it crosses PCIe */
-    const size_t copy_bytes = any_dense || !f->n_tu ? total : seg[s_coef].off;
-    /* device only.  The first four are cleared before the preparation kernels run. */
-    const size_t zero_off = total;
-    int s_cursor = add(nullptr, 16 * sizeof(uint32_t));
-    int s_sum = add(nullptr, sizeof(DevSummary));
-    int s_seen = add(nullptr, cnt.n_intra ? n_ctb * sizeof(uint32_t) : 0);
-    int s_keep = add(nullptr, f->n_tu);
-    const size_t zero_bytes = total - zero_off;
-    int s_mcl = add(nullptr, (size_t)cnt.n_mc_luma * sizeof(DevMcJob));
-    int s_mcc = add(nullptr, (size_t)cnt.n_mc_chroma * sizeof(DevMcJob));
-    int s_aux = add(nullptr, (size_t)cnt.n_ictu * sizeof(uint32_t));
-    int s_tu = add(nullptr, (size_t)f->n_tu * sizeof(DevTu));
-    int s_cross = add(nullptr, (size_t)n_cross * sizeof(DevCross));
-    int s_intra = add(nullptr, (size_t)f->n_intra * sizeof(DevIntra));
-    int s_ictu = add(nullptr, (size_t)cnt.n_ictu * sizeof(DevIntraCtu));
-    int s_small = add(nullptr, (size_t)cnt.n_sub * sizeof(uint32_t));
-    int s_perm = add(nullptr, (size_t)f->n_intra * sizeof(uint32_t));
-    int s_wait = add(nullptr, (size_t)cnt.n_ictu * 4 * sizeof(uint32_t));
-    int s_done = add(nullptr, (size_t)cnt.n_ictu * sizeof(uint32_t));
-    int s_clvl = add(nullptr, (size_t)cnt.n_ictu * sizeof(uint32_t));
-    int s_cord = add(nullptr, (size_t)cnt.n_ictu * sizeof(uint32_t));
-    const size_t res_off = total;
-    total += align_up((size_t)(f->n_coeff ? f->n_coeff : 1) * sizeof(int16_t), 256);
-    const bool stale_cfg = has_db && has_sao && oh_sao_stale_config(&p);       /* see DevFrame.sao_stale */
-    const size_t stale_off = total;
-    if (stale_cfg)
-        total += align_up(oh_sao_stale_index(&p, 3, 0, 0) * sizeof(uint16_t), 256);
-
-    auto t_lists = tnow();
-    bool best_was_new = false;
-    OhDevFrame *df = new OhDevFrame();
-    {   /* a pooled arena that fits (within 2x), else a new one rounded up to 1 MiB */
-        HostTimer t(e, OH_HT_UPLOAD_ARENA);
-        /* oldest first (the pool is in release order): an arena released long ago has no pass left that reads it, so the copy
-         * need not wait for the engine stream; the most recently released one would stall the copy stream behind the passes
-         * of the batch that just let go of it */
-        int best = -1;
-        best_was_new = false;
-        for (size_t i = 0; i < e->arenas.size() && best < 0; i++)
-            if (e->arenas[i].bytes >= total && e->arenas[i].bytes <= 2 * total + (1u << 20))
-                best = (int)i;
-        if (best >= 0 && e->arenas[best].free_ev && hipEventQuery(e->arenas[best].free_ev) != hipSuccess && e->arenas.size() < 512)
-            best = -1;                                      /* even the oldest fit is still in flight: a new arena beats a stall */
-        if (best >= 0) {
-            df->arena = e->arenas[best].p; df->arena_bytes = e->arenas[best].bytes;
-            if (e->arenas[best].free_ev) {                  /* released while passes were in flight: the copy must stay behind them */
-                (void)hipStreamWaitEvent(e->copy_stream, e->arenas[best].free_ev, 0);
-                sync_event_put(e, e->arenas[best].free_ev);
-            }
-            e->arenas.erase(e->arenas.begin() + best);
-        } else {
-            best_was_new = true;
-            df->arena_bytes = align_up(total, (size_t)1 << 20);
-            if (hipMalloc(&df->arena, df->arena_bytes) != hipSuccess) {
-                (void)hipStreamSynchronize(e->stream);
-                for (auto &a : e->arenas) { sync_event_put(e, a.free_ev); (void)hipFree(a.p); e->arenas_alive--; e->arena_bytes_alive -= a.bytes; }      /* the pool may be what is in the way */
-                e->arenas.clear();
-                if (hipMalloc(&df->arena, df->arena_bytes) != hipSuccess) {
-                    df->arena = nullptr;
-                    delete df;
-                    FAIL(e, OH_E_NOMEM, "hipMalloc(%zu) for the work list failed", total);
-                }
-            }
-        }
-    }
-    if (best_was_new) { e->arenas_alive++; e->arena_bytes_alive += df->arena_bytes; }
-    char *base = (char *)df->arena;
-    hd.pp = p;
-    fill_planes(&hd.cur, cur, false);
-    fill_planes(&hd.out, cur, has_sao);
-    for (int i = 0; i < OH_MAX_REFS; i++) {
-        Pic *r = get_pic(e, f->ref_pics[i]);
-        df->ref_id[i] = -1; df->ref_gen[i] = 0; df->ref_half[i] = 0;
-        if (ref_ok >> i & 1) {
-            fill_planes(&hd.refs[i], r, r->final_b);
-            df->ref_id[i] = f->ref_pics[i]; df->ref_gen[i] = r->gen; df->ref_half[i] = r->final_b ? 1 : 0;
-        }
-    }
-    df->ref_used = ref_used;
-    df->cur_gen = cur->gen;
-#define AT(T, s) ((T)(base + seg[s].off))
-    hd.pu = AT(const OhPu *, s_pu);
-    hd.mc_luma = AT(const DevMcJob *, s_mcl); hd.mc_chroma = AT(const DevMcJob *, s_mcc);
-    hd.wp = AT(const OhWeights *, s_wp);
-    hd.tu = AT(const DevTu *, s_tu); hd.tu_raw = AT(const OhTu *, s_tur);
-    hd.tu_sparse = f->tu_sparse ? AT(const uint32_t *, s_tusp) : nullptr;
-    hd.tu_cross = f->tu_cross ? AT(const uint32_t *, s_tucr) : nullptr;
-    hd.sparse = f->sparse ? AT(const uint32_t *, s_sparse) : nullptr;
-    hd.cross = AT(const DevCross *, s_cross);
-    hd.scaling = f->scaling ? AT(const OhScalingList *, s_scaling) : nullptr;
-    hd.coeffs = AT(const int16_t *, s_coef);
-    hd.coeffs_present = f->coeffs != nullptr;
-    hd.res = (int16_t *)(base + res_off);
-    hd.sao_stale = stale_cfg ? (uint16_t *)(base + stale_off) : nullptr;
-    hd.intra = AT(const DevIntra *, s_intra); hd.intra_raw = AT(const OhIntra *, s_inr);
-    hd.ictu = AT(const DevIntraCtu *, s_ictu); hd.ictu_raw = AT(const OhIntraCtu *, s_ictur);
-    hd.sub_start = AT(const uint32_t *, s_sub);
-    hd.sub_small = AT(const uint32_t *, s_small); hd.sub_small_w = AT(uint32_t *, s_small);
-    hd.lvl_start = AT(const uint32_t *, s_lvl);
-    hd.is_intra = cip ? AT(const uint8_t *, s_isin) : nullptr;
-    hd.vbs = AT(const uint8_t *, s_vbs); hd.hbs = AT(const uint8_t *, s_hbs);
-    hd.qp = AT(const int8_t *, s_qp);
-    hd.is_pcm = need_pcm ? AT(const uint8_t *, s_pcm) : nullptr;
-    hd.db = AT(const OhDeblockCtb *, s_db);
-    hd.sao = has_sao ? AT(const OhSaoCtb *, s_sao) : nullptr;
-    hd.sao_pending = has_pend ? AT(const uint8_t *, s_pend) : nullptr;
-    hd.pu_off = AT(const uint32_t *, s_puoff); hd.ctu_aux = AT(uint32_t *, s_aux); hd.tu_keep = AT(uint8_t *, s_keep); hd.tu_cursor = AT(uint32_t *, s_cursor);
-    hd.intra_perm = AT(uint32_t *, s_perm); hd.ctu_seen = AT(uint32_t *, s_seen); hd.summary = AT(void *, s_sum);
-    hd.ctu_wait = AT(uint32_t *, s_wait); hd.ctu_done = AT(uint32_t *, s_done); hd.ctu_lvl = AT(uint32_t *, s_clvl); hd.ctu_order = AT(uint32_t *, s_cord);
-    hd.err_word = e->kerr; hd.cur_pic_id = f->cur_pic;
-#undef AT
-    hd.n_pu = f->n_pu; hd.n_mc_luma = cnt.n_mc_luma; hd.n_mc_chroma = cnt.n_mc_chroma; hd.n_tu = f->n_tu; hd.n_intra = f->n_intra;
-    hd.n_ictu = cnt.n_ictu; hd.n_sub = cnt.n_sub; hd.n_levels = n_levels; hd.n_wp = f->n_wp; hd.n_sparse = f->sparse ? f->n_sparse : 0;
-    hd.ref_ok = ref_ok; hd.n_coeff = f->n_coeff;
-    hd.n_cross = n_cross;
-    hd.zero_ptr = (uint32_t *)(base + zero_off); hd.zero_words = (uint32_t)(zero_bytes / 4);
-    for (int k = 0, first = 0; k < 4; k++) { hd.tu_first[k] = (uint32_t)first; hd.tu_cnt[k] = tu_cnt[k]; first += (int)tu_cnt[k]; }
-    hd.dbg = e->dbg;
-    (void)s_hdr;
-
-    /* stage everything in one host buffer -> one H2D copy; a list that lies in pinned memory (OH_FRAME_PINNED) is copied by DMA from
-     * where it lies, segment by segment: only what this function made itself (the header, the PU block offsets) is staged */
-    auto t_alloc = tnow();
-    const bool direct = (f->flags & OH_FRAME_PINNED) != 0 && !(has_db && !bsi && !bs_packed_in);     /* byte grids still have to be packed on the way */
-    const size_t own_bytes = align_up(sizeof(DevFrame), 256) + align_up(2 * ((size_t)f->n_pu + 1) * sizeof(uint32_t), 256) + 64 * sizeof(OhPullSeg);
-    OhEngine::Stage *sg;
-    { HostTimer t(e, OH_HT_UPLOAD_STAGE_WAIT);
-    sg = stage_acquire(e, direct ? own_bytes : copy_bytes);   /* a pinned buffer whose previous copy has completed */
-    }
-    df->sum_host = summary_block_get(e);
-    hd.summary_host = df->sum_host;                        /* pinned, device-accessible: prep_finish stores the summary there */
-    if (!sg || !df->sum_host) {
-        free_dev_frame(e, df);
-        FAIL(e, OH_E_NOMEM, "hipHostMalloc(%zu) failed", copy_bytes);
-    }
-    void *stage = sg->p;
-    hipStream_t cs = e->copy_stream;
-    hipError_t hrc = hipSuccess;
-    if (direct) {
-        /* the GPU pulls the list: the two segments made here (header, PU block offsets) and the table of segments stand in the staging
-         * buffer, every other segment is read from the caller's pinned memory where it lies — ONE kernel launch (prep_pull), no host
-         * copy of the lists and no DMA request per array (fifteen of those per picture cost the host as much as the copy they replaced) */
-        OhPullSeg *tab;
-        int nt = 0;
-        size_t pulled = 0;
-        { HostTimer t(e, OH_HT_UPLOAD_MEMCPY);
-        char *sp = (char *)stage;
-        memcpy(sp, seg[s_hdr].src, seg[s_hdr].bytes);
-        char *po = sp + align_up(sizeof(DevFrame), 256);
-        if (seg[s_puoff].bytes) memcpy(po, seg[s_puoff].src, seg[s_puoff].bytes);
-        tab = (OhPullSeg *)(po + align_up(seg[s_puoff].bytes, 256));
-        tab[nt++] = OhPullSeg{ sp, (char *)df->arena, seg[s_hdr].bytes };
-        if (seg[s_puoff].bytes) tab[nt++] = OhPullSeg{ po, (char *)df->arena + seg[s_puoff].off, seg[s_puoff].bytes };
-        for (int i = 0; i < ns; i++)
-            if (i != s_hdr && i != s_puoff && seg[i].bytes && seg[i].src && seg[i].off + seg[i].bytes <= copy_bytes) {
-                tab[nt++] = OhPullSeg{ seg[i].src, (char *)df->arena + seg[i].off, seg[i].bytes };
-                pulled += seg[i].bytes;
-            }
-        }
-        HostTimer t_enq(e, OH_HT_UPLOAD_ENQUEUE);
-        ohk_pull(tab, nt, pulled, cs);
-        hrc = hipGetLastError();
-    } else {
-        { HostTimer t(e, OH_HT_UPLOAD_MEMCPY);
-        if (!e->copiers) {
-            static const char *cenv = getenv("OHEVC_COPY_THREADS");
-            e->copiers = new CopyPool();
-            e->copiers->start(cenv ? std::max(0, std::min(atoi(cenv), 8)) : 2);
-        }
-        /* pieces of at most 128 KB, dealt round-robin to the calling thread and the helpers */
-        std::vector<CopyJob> &jobs = e->copy_jobs;
-        jobs.clear();
-        const size_t piece = 128 * 1024;
-        for (int i = 0; i < ns; i++)
-            if (seg[i].bytes && seg[i].src && seg[i].off + seg[i].bytes <= copy_bytes) {
-                if (seg[i].pack_n) {                                      /* four source bytes per byte: pieces of 4 x 128 KB strengths */
-                    for (size_t o = 0; o < seg[i].pack_n; o += 4 * piece)
-                        jobs.push_back({ (char *)stage + seg[i].off + o / 4, (const char *)seg[i].src + o, std::min(4 * piece, seg[i].pack_n - o), true });
-                } else {
-                    for (size_t o = 0; o < seg[i].bytes; o += piece)
-                        jobs.push_back({ (char *)stage + seg[i].off + o, (const char *)seg[i].src + o, std::min(piece, seg[i].bytes - o), false });
-                }
-            }
-        e->copiers->run(jobs);
-        }
-        /* asynchronous: the caller's arrays are already copied out; the pinned buffer stays busy until `done` */
-        HostTimer t_enq(e, OH_HT_UPLOAD_ENQUEUE);
-        hrc = hipMemcpyAsync(df->arena, stage, copy_bytes, hipMemcpyHostToDevice, cs);
-    }
-    HostTimer t_enq(e, OH_HT_UPLOAD_ENQUEUE);
-    if (hrc == hipSuccess)
-        hrc = hipEventRecord(sg->done, cs);
-    sg->busy = hrc == hipSuccess;
-    e->up_bytes += copy_bytes;
-    if (hrc == hipSuccess && bsi) {                        /* both grids from the maps: once per work list, the maps never change */
-        hrc = hipMemsetAsync(base + seg[s_vbs].off, 0, align_up(bs_packed, 4), cs);          /* bs_kernel ORs the non-zero strengths in; the padded tail is read by the deblock pass */
-        if (hrc == hipSuccess) hrc = hipMemsetAsync(base + seg[s_hbs].off, 0, align_up(bs_packed, 4), cs);
-        if (hrc == hipSuccess)
-            ohk_bs_derive(&p, base + seg[s_mvf].off, base + seg[s_cbf].off, base + seg[s_call].off, base + seg[s_bsf].off, bsi->loop_filter_across_tiles,
-                          base + seg[s_vbs].off, base + seg[s_hbs].off, cs);
-    }
-    df->sum_dev = base + seg[s_sum].off;
-    df->cnt = cnt;
-    if (hrc != hipSuccess) {
-        (void)hipStreamSynchronize(cs);
-        free_dev_frame(e, df);
-        FAIL(e, OH_E_HIP, "work-list upload failed: %s", hipGetErrorString(hrc));
-    }
-    if (timing) {
-        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        auto t_end = tnow();
-        fprintf(stderr, "oh_frame_upload: host checks + counting %.3f ms, layout %.3f ms, arena %.3f ms, staging copy + enqueue %.3f ms (%zu bytes)\n",
-                ms(t_begin, t_valid), ms(t_valid, t_lists), ms(t_lists, t_alloc), ms(t_alloc, t_end), copy_bytes);
-    }
-    df->d = (DevFrame *)base;
-    df->p = p;
-    for (int k = 0; k < 4; k++) df->tu_cnt[k] = tu_cnt[k];
-    df->n_cross = n_cross;
-    df->has_sao = has_sao;
-    df->cur_pic = f->cur_pic;                  /* which half of cur_pic is final changes when the list is EXECUTED, not here */
-    df->owner = e;
-    *out = df;
-    return OH_OK;
-}
-
-/* preparation kernels of n freshly copied work lists (one set of launches per 32 of them: the kernels pick the list with a grid
- * dimension, like the passes), their summaries back to pinned memory, their `ready` events */
-static int finish_uploads(OhEngine *e, OhDevFrame *const *dfs, int n)
-{
-    HostTimer t_enq(e, OH_HT_UPLOAD_ENQUEUE);
-    hipStream_t cs = e->copy_stream;
-    for (int c0 = 0; c0 < n; c0 += OH_MAX_BATCH) {
-        const int nb = n - c0 < OH_MAX_BATCH ? n - c0 : OH_MAX_BATCH;
-        OhBatch B;
-        memset(&B, 0, sizeof(B));
-        OhPrepCounts mx;
-        memset(&mx, 0, sizeof(mx));
-        uint32_t max_cross = 0, max_runs = 0;
-        for (int i = 0; i < nb; i++) {
-            const OhDevFrame *df = dfs[c0 + i];
-            B.f[i] = df->d;
-            mx.n_pu = std::max(mx.n_pu, df->cnt.n_pu); mx.n_tu = std::max(mx.n_tu, df->cnt.n_tu);
-            mx.n_intra = std::max(mx.n_intra, df->cnt.n_intra); mx.n_sub = std::max(mx.n_sub, df->cnt.n_sub);
-            mx.n_ictu = std::max(mx.n_ictu, df->cnt.n_ictu);
-            max_runs = std::max(max_runs, ((df->cnt.n_mc_luma + 63) >> 6) + ((df->cnt.n_mc_chroma + 63) >> 6));
-            max_cross = std::max(max_cross, df->n_cross);
-        }
-        ohk_prepare(&B, nb, &mx, max_runs, max_cross, cs);
-        HIPCHK(e, hipGetLastError());
-    }
-    /* one point in the copy stream makes all of them ready: an event per list, recorded back to back */
-    for (int i = 0; i < n; i++) {
-        OhDevFrame *df = dfs[i];
-        if ((df->ready = sync_event_get(e)) == nullptr)
-            FAIL(e, OH_E_NOMEM, "no event for the work list");
-        HIPCHK(e, hipEventRecord(df->ready, cs));
-    }
-    return OH_OK;
-}
-
-extern "C" int oh_frames_upload(OhEngine *e, const OhFrame *const *fs, int n, OhDevFrame **out)
-{
-    if (!e || n < 0 || (n && (!fs || !out)))
-        return OH_E_ARG;
-    for (int i = 0; i < n; i++) out[i] = nullptr;
-    int rc = OH_OK;
-    int done = 0;
-    for (; done < n && rc == OH_OK; done++)
-        rc = fs[done] ? upload_one(e, fs[done], &out[done]) : OH_E_ARG;
-    if (rc == OH_OK)
-        rc = finish_uploads(e, out, n);
-    if (rc != OH_OK) {                                     /* all or nothing */
-        (void)hipStreamSynchronize(e->copy_stream);
-        for (int i = 0; i < n; i++) { free_dev_frame(e, out[i]); out[i] = nullptr; }
-    }
-    return rc;
-}
-
-extern "C" int oh_frame_upload(OhEngine *e, const OhFrame *f, OhDevFrame **out)
-{
-    if (!e || !f || !out)
-        return OH_E_ARG;
-    return oh_frames_upload(e, &f, 1, out);
 }
 
 /* the summary the preparation kernels left (prep.hip): waits for the list's `ready` event the first time */
@@ -1074,7 +535,6 @@ extern "C" int oh_frames_execute(OhEngine *e, OhDevFrame *const *dfs, int n)
         if (memcmp(&a, &b, sizeof(a)) != 0)
             FAIL(e, OH_E_ARG, "batch: picture %d has other parameters than picture 0", i);
     }
-    HIPCHK(e, hipSetDevice(e->device));
     hipStream_t st = e->stream;
     {
         /* Pictures are looked up NOW, not at upload: the work list may have been uploaded before its references were decoded or
@@ -1125,8 +585,8 @@ extern "C" int oh_frames_execute(OhEngine *e, OhDevFrame *const *dfs, int n)
                 hp[k] = patches[k].v;
                 HIPCHK(e, hipMemcpyAsync(patches[k].dst, &hp[k], sizeof(DevPlanes), hipMemcpyHostToDevice, st));
             }
-            HIPCHK(e, hipEventRecord(sg->done, st));
-            sg->busy = true;
+            if (const int rc = stage_in_use(e, sg, st))
+                return rc;
         }
     }
     const bool prof = e->profile > 0;

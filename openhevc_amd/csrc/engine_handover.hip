@@ -1,0 +1,413 @@
+/*
+ * engine_handover.hip — hand-over of work lists to the engine: host-side checks and counts, the device arena (laid out by
+ * handover_layout.h, taken from the engine's pool), the header, the staging copy or the pull out of pinned memory, and the
+ * preparation kernels behind it on the copy stream.  oh_frames_upload / oh_frame_upload of the C ABI (include/ohevc_hip.h).
+ */
+#include "engine_impl.h"
+
+hipEvent_t sync_event_get(OhEngine *e)
+{
+    hipEvent_t ev = nullptr;
+    if (!e->sync_events.empty()) { ev = e->sync_events.back(); e->sync_events.pop_back(); return ev; }
+    return hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess ? ev : nullptr;
+}
+void sync_event_put(OhEngine *e, hipEvent_t ev)
+{
+    if (!ev) return;
+    if (e->sync_events.size() < 4096) e->sync_events.push_back(ev); else (void)hipEventDestroy(ev);
+}
+
+/* ---------------- device arenas ---------------- */
+/* the two places that allocate and free an arena: what oh_engine_memory reports as alive (pooled or holding a work list) is counted here */
+static void *arena_new(OhEngine *e, size_t bytes)
+{
+    void *p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess)
+        return nullptr;
+    e->arenas_alive++; e->arena_bytes_alive += bytes;
+    return p;
+}
+static void arena_delete(OhEngine *e, void *p, size_t bytes)
+{
+    (void)hipFree(p);
+    if (e) { e->arenas_alive--; e->arena_bytes_alive -= bytes; }
+}
+
+/* an arena of at least `total` bytes for df: a pooled one that fits (within 2x), else a new one rounded up to 1 MiB */
+static int arena_take(OhEngine *e, size_t total, OhDevFrame *df)
+{
+    /* oldest first (the pool is in release order): an arena released long ago has no pass left that reads it, so the copy
+     * need not wait for the engine stream; the most recently released one would stall the copy stream behind the passes
+     * of the batch that just let go of it */
+    int best = -1;
+    for (size_t i = 0; i < e->arenas.size() && best < 0; i++)
+        if (e->arenas[i].bytes >= total && e->arenas[i].bytes <= 2 * total + (1u << 20))
+            best = (int)i;
+    if (best >= 0 && e->arenas[best].free_ev && hipEventQuery(e->arenas[best].free_ev) != hipSuccess && e->arenas.size() < 512)
+        best = -1;                                      /* even the oldest fit is still in flight: a new arena beats a stall */
+    if (best >= 0) {
+        df->arena = e->arenas[best].p; df->arena_bytes = e->arenas[best].bytes;
+        if (e->arenas[best].free_ev) {                  /* released while passes were in flight: the copy must stay behind them */
+            (void)hipStreamWaitEvent(e->copy_stream, e->arenas[best].free_ev, 0);
+            sync_event_put(e, e->arenas[best].free_ev);
+        }
+        e->arenas.erase(e->arenas.begin() + best);
+        return OH_OK;
+    }
+    df->arena_bytes = align_up(total, (size_t)1 << 20);
+    if ((df->arena = arena_new(e, df->arena_bytes)) == nullptr) {
+        (void)hipStreamSynchronize(e->stream);
+        for (auto &a : e->arenas) { sync_event_put(e, a.free_ev); arena_delete(e, a.p, a.bytes); }      /* the pool may be what is in the way */
+        e->arenas.clear();
+        if ((df->arena = arena_new(e, df->arena_bytes)) == nullptr)
+            FAIL(e, OH_E_NOMEM, "hipMalloc(%zu) for the work list failed", total);
+    }
+    return OH_OK;
+}
+
+/* arenas go back to the engine's pool.  in_flight: kernels enqueued on the engine stream may still read the arena — an event
+ * recorded there now tells the copy stream when the next work list may overwrite it. */
+void free_dev_frame(OhEngine *e, OhDevFrame *df, bool in_flight)
+{
+    if (!df)
+        return;
+    if (e && df->ready)
+        sync_event_put(e, df->ready);
+    if (df->sum_host) {
+        if (e && e->sum_pool.size() < 4096) e->sum_pool.push_back(df->sum_host);
+        else (void)hipHostFree(df->sum_host);
+    }
+    if (df->arena) {
+        if (e && e->arenas.size() < 1024) {
+            hipEvent_t fe = nullptr;
+            if (in_flight && (fe = sync_event_get(e)) != nullptr && hipEventRecord(fe, e->stream) != hipSuccess) {
+                sync_event_put(e, fe);
+                fe = nullptr;
+            }
+            if (in_flight && !fe)
+                (void)hipStreamSynchronize(e->stream);           /* no event to be had: wait instead */
+            e->arenas.push_back({ df->arena, df->arena_bytes, fe });
+        } else {
+            if (in_flight) (void)hipStreamSynchronize(e->stream);
+            arena_delete(e, df->arena, df->arena_bytes);
+        }
+    }
+    delete df;
+}
+
+/* ---------------- work lists ---------------- */
+static bool same_geometry(const OhPicParams &a, const OhPicParams &b)
+{
+    return a.width == b.width && a.height == b.height && a.bit_depth == b.bit_depth && a.chroma_format_idc == b.chroma_format_idc;
+}
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Hand-over of a work list.  The host copies the RAW lists (include/ohevc_frame.h, exactly as recorded) into one pinned
+ * buffer, counts what sizes the device arena — blocks per PU, transform blocks per size: two light loops — and enqueues on the
+ * copy stream:   H2D copy  ->  preparation kernels (prep.hip: validation of every index a pass kernel will follow, the
+ * <= 8x8 MC block lists, the transform-size buckets, the intra block descriptors, schedule and statistics)  ->
+ * boundary strengths from the motion field when the list carries bs_in (bs.hip)  ->  the summary back to pinned memory  ->
+ * `ready`.  Nothing of it touches samples, so it overlaps the passes of the pictures before.  A malformed list is
+ * reported by the first oh_frame(s)_execute that includes it (OH_E_ARG, before any of its passes is launched).
+ * ------------------------------------------------------------------------------------------------------------------- */
+static int check_host_side(OhEngine *e, const OhFrame *f, const Pic *cur, HostSide *h)
+{
+    const OhPicParams &p = f->p;
+    h->ref_ok = 0; h->ref_used = 0; h->n_cross = 0; h->any_dense = false;
+    for (int i = 0; i < OH_MAX_REFS; i++) {
+        Pic *r = get_pic(e, f->ref_pics[i]);
+        if (r && same_geometry(r->p, p) && r != cur)
+            h->ref_ok |= 1u << i;
+    }
+    if ((f->n_pu && !f->pu) || (f->n_wp && !f->wp) || (f->n_tu && !f->tu) || (f->n_intra && !f->intra))
+        FAIL(e, OH_E_ARG, "a non-zero item count comes with a NULL array (pu / wp / tu / intra)");
+    /* blocks per PU: sizes the MC block lists (prep_pu_scan repeats the sums on the GPU and validates every PU) */
+    uint64_t nl = 0, nc = 0;
+    const int hs = oh_hshift(&p, 1), vs = oh_vshift(&p, 1), two = p.chroma_format_idc ? 2 : 0;
+    if ((uint64_t)f->n_pu * 2048 >= (1ull << 31))
+        FAIL(e, OH_E_ARG, "PU list too long");
+    static thread_local std::vector<uint32_t> pu_off;
+    pu_off.resize(2 * ((size_t)f->n_pu + 1));
+    uint32_t *ol = pu_off.data(), *oc = ol + f->n_pu + 1;       /* running sums: where every PU's blocks start in the two lists */
+    h->pu_off = ol;
+    for (uint32_t i = 0; i < f->n_pu; i++) {
+        const OhPu &pu = f->pu[i];
+        ol[i] = (uint32_t)nl; oc[i] = (uint32_t)nc;
+        nl += (uint64_t)(((pu.w + 7) >> 3) * ((pu.h + 7) >> 3));
+        nc += (uint64_t)(two * ((((pu.w >> hs) + 7) >> 3) * (((pu.h >> vs) + 7) >> 3)));
+        for (int l = 0; l < 2; l++)
+            if (pu.ref[l] < OH_MAX_REFS) h->ref_used |= (uint16_t)(1u << pu.ref[l]);
+    }
+    ol[f->n_pu] = (uint32_t)nl; oc[f->n_pu] = (uint32_t)nc;
+    for (uint32_t i = 0; i < f->n_wp; i++)
+        if (f->wp[i].log2_denom[0] > 7 || f->wp[i].log2_denom[1] > 7)
+            FAIL(e, OH_E_ARG, "weights %u: log2 denominator out of range", i);
+    h->tu_cnt[0] = h->tu_cnt[1] = h->tu_cnt[2] = h->tu_cnt[3] = 0;
+    for (uint32_t i = 0; i < f->n_tu; i++) {                  /* launch sizes of the residual pass; is any block dense? */
+        const OhTu &t = f->tu[i];
+        h->tu_cnt[(t.log2_size - 2) & 3]++;
+        h->n_cross += (t.flags & OH_TUF_CROSS) != 0;
+        h->any_dense = h->any_dense || !(t.flags & OH_TUF_SPARSE);
+    }
+    if (h->any_dense && f->n_coeff && !f->coeffs)
+        FAIL(e, OH_E_ARG, "dense transform blocks but coeffs[] is NULL");
+    if (h->n_cross && !f->tu_cross)
+        FAIL(e, OH_E_ARG, "cross-component blocks without tu_cross[]");
+    if (f->n_intra && p.constrained_intra_pred && !f->is_intra)
+        FAIL(e, OH_E_ARG, "constrained_intra_pred without the is_intra map");
+    if (f->n_intra) {
+        /* the level table is the contract behind the waits between CTUs (prep_intra_wait: a CTU waits only for lower levels), and
+         * prep_intra_ctu looks every entry's level up in it: checked here; everything below it on the GPU */
+        if (!f->level_start || !f->n_levels || !f->ictu || !f->n_ictu || !f->sub_start || !f->n_sub ||
+            f->level_start[0] != 0 || f->level_start[f->n_levels] != f->n_ictu)
+            FAIL(e, OH_E_ARG, "intra wavefront tables inconsistent");
+        for (uint32_t l = 0; l < f->n_levels; l++)
+            if (f->level_start[l] > f->level_start[l + 1])
+                FAIL(e, OH_E_ARG, "intra level table not monotonic");
+    }
+    if (p.deblock_enabled) {
+        const OhBsInputs *bi = f->bs_in;                      /* boundary strengths derived on the GPU instead of handed over */
+        if (bi && (!bi->mvf || !bi->cbf_luma || !bi->call_log2 || !bi->ctb_flags))
+            FAIL(e, OH_E_ARG, "bs_in: all four maps are required");
+        if (bi && (p.log2_min_pu_size < 2 || p.log2_min_tb_size < 2))
+            FAIL(e, OH_E_ARG, "bs_in: min PU / TB size below 4");
+        if (bi) {
+            const size_t n_cells = (size_t)(p.width >> p.log2_min_tb_size) * (p.height >> p.log2_min_tb_size);
+            for (size_t i = 0; i < n_cells; i++)
+                if (bi->call_log2[i] && (bi->call_log2[i] < p.log2_min_tb_size || bi->call_log2[i] > p.log2_ctb_size))
+                    FAIL(e, OH_E_ARG, "bs_in: call_log2[%zu] = %d is not a block size of this picture", i, bi->call_log2[i]);
+        }
+        if ((!bi && (!f->vertical_bs || !f->horizontal_bs || f->bs_size < oh_bs_size(&p))) || !f->qp_y_tab || !f->deblock)
+            FAIL(e, OH_E_ARG, "deblock side arrays missing or too small");
+    }
+    if ((p.pcm_loop_filter_disable || p.transquant_bypass_enable) && !f->is_pcm)
+        FAIL(e, OH_E_ARG, "is_pcm map required when pcm loop-filter disable / transquant bypass is on");
+    OhPrepCounts *cnt = &h->cnt;
+    cnt->n_pu = f->n_pu; cnt->n_mc_luma = (uint32_t)nl; cnt->n_mc_chroma = (uint32_t)nc; cnt->n_tu = f->n_tu;
+    cnt->n_intra = f->n_intra; cnt->n_sub = f->n_intra ? f->n_sub : 0; cnt->n_ictu = f->n_intra ? f->n_ictu : 0;
+    return OH_OK;
+}
+
+/* pinned block the summary of one work list lands in */
+static void *summary_block_get(OhEngine *e)
+{
+    void *p = nullptr;
+    if (!e->sum_pool.empty()) { p = e->sum_pool.back(); e->sum_pool.pop_back(); return p; }
+    return hipHostMalloc(&p, sizeof(DevSummary), hipHostMallocDefault) == hipSuccess ? p : nullptr;
+}
+
+/* everything of the header but summary_host: pictures, pointers into df's arena, counts; and which references df was uploaded with */
+static void fill_header(OhEngine *e, const OhFrame *f, const Pic *cur, const HostSide &h, const HandoverLayout &L, OhDevFrame *df, HandoverHeader *H)
+{
+    DevFrame &hd = H->d;
+    hd.pp = f->p;
+    fill_planes(&hd.cur, cur, false);
+    fill_planes(&hd.out, cur, f->p.sao_enabled && f->sao);
+    for (int i = 0; i < OH_MAX_REFS; i++) {
+        Pic *r = get_pic(e, f->ref_pics[i]);
+        df->ref_id[i] = -1; df->ref_gen[i] = 0; df->ref_half[i] = 0;
+        if (h.ref_ok >> i & 1) {
+            fill_planes(&hd.refs[i], r, r->final_b);
+            df->ref_id[i] = f->ref_pics[i]; df->ref_gen[i] = r->gen; df->ref_half[i] = r->final_b ? 1 : 0;
+        }
+    }
+    df->ref_used = h.ref_used;
+    df->cur_gen = cur->gen;
+    handover_bind(L, (char *)df->arena, H);
+    hd.coeffs_present = f->coeffs != nullptr;
+    hd.err_word = e->kerr; hd.cur_pic_id = f->cur_pic;
+    hd.n_pu = f->n_pu; hd.n_mc_luma = h.cnt.n_mc_luma; hd.n_mc_chroma = h.cnt.n_mc_chroma; hd.n_tu = f->n_tu; hd.n_intra = f->n_intra;
+    hd.n_ictu = h.cnt.n_ictu; hd.n_sub = h.cnt.n_sub; hd.n_levels = f->n_intra ? f->n_levels : 0; hd.n_wp = f->n_wp; hd.n_sparse = f->sparse ? f->n_sparse : 0;
+    hd.ref_ok = h.ref_ok; hd.n_coeff = f->n_coeff;
+    hd.n_cross = h.n_cross;
+    for (int k = 0, first = 0; k < 4; k++) { hd.tu_first[k] = (uint32_t)first; hd.tu_cnt[k] = h.tu_cnt[k]; first += (int)h.tu_cnt[k]; }
+    hd.dbg = e->dbg;
+}
+
+/* The two forms of the copy.  A list that lies in pinned memory (OH_FRAME_PINNED) is pulled by the GPU: the segments made here (the
+ * header, the PU block offsets) and the table of segments stand in the staging buffer, every other segment is read from the caller's
+ * pinned memory where it lies — ONE kernel launch (prep_pull), no host copy of the lists and no DMA request per array (fifteen of
+ * those per picture cost the host as much as the copy they replaced). */
+enum { PULL_TABLE = 64 };
+static_assert(HL_N_SEGS <= PULL_TABLE, "a table entry per copied segment");
+static size_t pulled_stage_bytes(const HandoverLayout &L) { return L.own_bytes + PULL_TABLE * sizeof(OhPullSeg); }
+static hipError_t stage_pulled(OhEngine *e, const HandoverLayout &L, char *arena, OhEngine::Stage *sg)
+{
+    char *sp = (char *)sg->p;
+    OhPullSeg *tab = (OhPullSeg *)(sp + L.own_bytes);
+    int nt = 0;
+    size_t pulled = 0;
+    { HostTimer t(e, OH_HT_UPLOAD_MEMCPY);
+    for (int i = 0; i < L.ns; i++)
+        if (L.seg[i].own && L.seg[i].bytes) {
+            memcpy(sp, L.seg[i].src, L.seg[i].bytes);
+            tab[nt++] = OhPullSeg{ sp, arena + L.seg[i].off, L.seg[i].bytes };
+            sp += align_up(L.seg[i].bytes, 256);
+        }
+    for (int i = 0; i < L.ns; i++)
+        if (!L.seg[i].own && L.copied(L.seg[i])) {
+            tab[nt++] = OhPullSeg{ L.seg[i].src, arena + L.seg[i].off, L.seg[i].bytes };
+            pulled += L.seg[i].bytes;
+        }
+    }
+    HostTimer t_enq(e, OH_HT_UPLOAD_ENQUEUE);
+    ohk_pull(tab, nt, pulled, e->copy_stream);
+    return hipGetLastError();
+}
+
+/* Any other list is staged: everything in one host buffer laid out like the arena -> one H2D copy */
+static hipError_t stage_copied(OhEngine *e, const HandoverLayout &L, char *arena, OhEngine::Stage *sg)
+{
+    { HostTimer t(e, OH_HT_UPLOAD_MEMCPY);
+    if (!e->copiers) {
+        static const char *cenv = getenv("OHEVC_COPY_THREADS");
+        e->copiers = new CopyPool();
+        e->copiers->start(cenv ? std::max(0, std::min(atoi(cenv), 8)) : 2);
+    }
+    handover_copy_jobs(L, (char *)sg->p, e->copy_jobs);     /* dealt round-robin to the calling thread and the helpers */
+    e->copiers->run(e->copy_jobs);
+    }
+    /* asynchronous: the caller's arrays are already copied out; the pinned buffer stays busy until `done` */
+    HostTimer t_enq(e, OH_HT_UPLOAD_ENQUEUE);
+    return hipMemcpyAsync(arena, sg->p, L.copy_bytes, hipMemcpyHostToDevice, e->copy_stream);
+}
+
+/* with bs_in, behind the copy: both grids from the maps — once per work list, the maps never change */
+static hipError_t enqueue_bs_derive(const OhFrame *f, const HandoverHeader &H, hipStream_t cs)
+{
+    const size_t bs_packed = (oh_bs_size(&f->p) + 3) / 4;
+    hipError_t hrc = hipMemsetAsync((void *)H.d.vbs, 0, align_up(bs_packed, 4), cs);     /* bs_kernel ORs the non-zero strengths in; the padded tail is read by the deblock pass */
+    if (hrc == hipSuccess) hrc = hipMemsetAsync((void *)H.d.hbs, 0, align_up(bs_packed, 4), cs);
+    if (hrc == hipSuccess)
+        ohk_bs_derive(&f->p, H.mvf, H.cbf_luma, H.call_log2, H.ctb_flags, f->bs_in->loop_filter_across_tiles, (void *)H.d.vbs, (void *)H.d.hbs, cs);
+    return hrc;
+}
+
+/* the host part of one hand-over and its H2D copy; finish_uploads() enqueues the preparation kernels behind it */
+static int upload_one(OhEngine *e, const OhFrame *f, OhDevFrame **out)
+{
+    *out = nullptr;
+    int rc = check_params(e, &f->p);
+    if (rc)
+        return rc;
+    Pic *cur = get_pic(e, f->cur_pic);
+    if (!cur || !same_geometry(cur->p, f->p))
+        FAIL(e, OH_E_ARG, "cur_pic %d is not an allocated picture of this geometry", f->cur_pic);
+    HostTimer t_all(e, OH_HT_UPLOAD);
+    HostSide h;
+    { HostTimer t(e, OH_HT_UPLOAD_COUNT);
+    rc = check_host_side(e, f, cur, &h);
+    }
+    if (rc)
+        return rc;
+    HIPCHK(e, hipSetDevice(e->device));
+    HandoverHeader H;
+    memset(&H, 0, sizeof(H));
+    const HandoverLayout L = handover_layout(f, h, &H.d);
+    OhDevFrame *df = new OhDevFrame();
+    { HostTimer t(e, OH_HT_UPLOAD_ARENA);
+    rc = arena_take(e, L.total, df);
+    }
+    if (rc) {
+        delete df;
+        return rc;
+    }
+    fill_header(e, f, cur, h, L, df, &H);
+
+    /* byte grids still have to be packed on the way: such a list is staged even when it lies in pinned memory */
+    const bool pull = (f->flags & OH_FRAME_PINNED) != 0 && !L.packs;
+    OhEngine::Stage *sg;
+    { HostTimer t(e, OH_HT_UPLOAD_STAGE_WAIT);
+    sg = stage_acquire(e, pull ? pulled_stage_bytes(L) : L.copy_bytes);   /* a pinned buffer whose previous copy has completed */
+    }
+    df->sum_host = summary_block_get(e);
+    H.d.summary_host = df->sum_host;                       /* pinned, device-accessible: prep_finish stores the summary there */
+    if (!sg || !df->sum_host) {
+        free_dev_frame(e, df);
+        FAIL(e, OH_E_NOMEM, "hipHostMalloc(%zu) failed", L.copy_bytes);
+    }
+    hipStream_t cs = e->copy_stream;
+    hipError_t hrc = pull ? stage_pulled(e, L, (char *)df->arena, sg) : stage_copied(e, L, (char *)df->arena, sg);
+    HostTimer t_enq(e, OH_HT_UPLOAD_ENQUEUE);
+    if (hrc == hipSuccess && stage_in_use(e, sg, cs) != OH_OK)
+        hrc = hipGetLastError();
+    e->up_bytes += L.copy_bytes;
+    if (hrc == hipSuccess && H.mvf)
+        hrc = enqueue_bs_derive(f, H, cs);
+    if (hrc != hipSuccess) {
+        (void)hipStreamSynchronize(cs);
+        free_dev_frame(e, df);
+        FAIL(e, OH_E_HIP, "work-list upload failed: %s", hipGetErrorString(hrc));
+    }
+    df->sum_dev = H.d.summary;
+    df->cnt = h.cnt;
+    df->d = (DevFrame *)df->arena;
+    df->p = f->p;
+    for (int k = 0; k < 4; k++) df->tu_cnt[k] = h.tu_cnt[k];
+    df->n_cross = h.n_cross;
+    df->has_sao = f->p.sao_enabled && f->sao;
+    df->cur_pic = f->cur_pic;                  /* which half of cur_pic is final changes when the list is EXECUTED, not here */
+    df->owner = e;
+    *out = df;
+    return OH_OK;
+}
+
+/* preparation kernels of n freshly copied work lists (one set of launches per 32 of them: the kernels pick the list with a grid
+ * dimension, like the passes), their summaries back to pinned memory, their `ready` events */
+static int finish_uploads(OhEngine *e, OhDevFrame *const *dfs, int n)
+{
+    HostTimer t_enq(e, OH_HT_UPLOAD_ENQUEUE);
+    hipStream_t cs = e->copy_stream;
+    for (int c0 = 0; c0 < n; c0 += OH_MAX_BATCH) {
+        const int nb = n - c0 < OH_MAX_BATCH ? n - c0 : OH_MAX_BATCH;
+        OhBatch B;
+        memset(&B, 0, sizeof(B));
+        OhPrepCounts mx;
+        memset(&mx, 0, sizeof(mx));
+        uint32_t max_cross = 0, max_runs = 0;
+        for (int i = 0; i < nb; i++) {
+            const OhDevFrame *df = dfs[c0 + i];
+            B.f[i] = df->d;
+            mx.n_pu = std::max(mx.n_pu, df->cnt.n_pu); mx.n_tu = std::max(mx.n_tu, df->cnt.n_tu);
+            mx.n_intra = std::max(mx.n_intra, df->cnt.n_intra); mx.n_sub = std::max(mx.n_sub, df->cnt.n_sub);
+            mx.n_ictu = std::max(mx.n_ictu, df->cnt.n_ictu);
+            max_runs = std::max(max_runs, ((df->cnt.n_mc_luma + 63) >> 6) + ((df->cnt.n_mc_chroma + 63) >> 6));
+            max_cross = std::max(max_cross, df->n_cross);
+        }
+        ohk_prepare(&B, nb, &mx, max_runs, max_cross, cs);
+        HIPCHK(e, hipGetLastError());
+    }
+    /* one point in the copy stream makes all of them ready: an event per list, recorded back to back */
+    for (int i = 0; i < n; i++) {
+        OhDevFrame *df = dfs[i];
+        if ((df->ready = sync_event_get(e)) == nullptr)
+            FAIL(e, OH_E_NOMEM, "no event for the work list");
+        HIPCHK(e, hipEventRecord(df->ready, cs));
+    }
+    return OH_OK;
+}
+
+extern "C" int oh_frames_upload(OhEngine *e, const OhFrame *const *fs, int n, OhDevFrame **out)
+{
+    if (!e || n < 0 || (n && (!fs || !out)))
+        return OH_E_ARG;
+    for (int i = 0; i < n; i++) out[i] = nullptr;
+    int rc = OH_OK;
+    int done = 0;
+    for (; done < n && rc == OH_OK; done++)
+        rc = fs[done] ? upload_one(e, fs[done], &out[done]) : OH_E_ARG;
+    if (rc == OH_OK)
+        rc = finish_uploads(e, out, n);
+    if (rc != OH_OK) {                                     /* all or nothing */
+        (void)hipStreamSynchronize(e->copy_stream);
+        for (int i = 0; i < n; i++) { free_dev_frame(e, out[i]); out[i] = nullptr; }
+    }
+    return rc;
+}
+
+extern "C" int oh_frame_upload(OhEngine *e, const OhFrame *f, OhDevFrame **out)
+{
+    if (!e || !f || !out)
+        return OH_E_ARG;
+    return oh_frames_upload(e, &f, 1, out);
+}

@@ -1,7 +1,8 @@
 /*
  * engine_impl.h — what the engine's translation units share: the engine and picture structures, the error macros and the few
- * helpers more than one of them uses.  engine.hip: engine and picture lifecycle, work-list hand-over, passes, profiling;
- * engine_pics.hip: plane transfers, hashes, conversion and resizing of finished pictures; engine_shvc.hip: SHVC up-sampling.
+ * helpers more than one of them uses.  engine.hip: engine and picture lifecycle, staging buffers, passes, profiling;
+ * engine_handover.hip: work-list hand-over and the arena pool; engine_pics.hip: plane transfers, hashes, conversion and resizing
+ * of finished pictures; engine_shvc.hip: SHVC up-sampling.
  * Internal: the C ABI is include/ohevc_hip.h.
  */
 #ifndef OHEVC_ENGINE_IMPL_H
@@ -20,7 +21,7 @@
 #include <vector>
 
 #include "../../include/ohevc_hip.h"
-#include "dev_frame.h"
+#include "handover_layout.h"
 #include "kernels.h"
 
 #define OH_INTERNAL __attribute__((visibility("hidden")))    /* shared between the engine's files, not part of the library's ABI */
@@ -72,8 +73,6 @@ struct OhDevFrame {
 
 /* helper threads for the one host copy of the hand-over (the work list into a pinned staging buffer): the lists of a 4K picture are
  * ~4 MB, 0.22 ms for one thread — most of what the hand-over costs the decoder's thread.  The calling thread keeps a share. */
-struct CopyJob { char *dst; const char *src; size_t n; bool pack; };
-OH_INTERNAL void pack_bs(uint8_t *dst, const uint8_t *src, size_t n);
 struct CopyPool {
     std::vector<std::thread> th;
     std::mutex mu;
@@ -222,8 +221,6 @@ struct OhEngine {
         return (code);                                                                            \
     } while (0)
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 struct HostTimer {                       /* adds the scope's wall time to one slot of OhEngine::host_ms */
     OhEngine *e; int slot; std::chrono::steady_clock::time_point t0;
     HostTimer(OhEngine *e_, int slot_);
@@ -234,13 +231,26 @@ enum { OH_MAX_STAGES = 48 };             /* pinned staging buffers per engine be
 /* the planes of the half that holds the finished picture, and the bytes of one of its samples */
 static inline void *const *final_planes(const Pic *p) { return p->final_b ? p->b : p->a; }
 static inline int sample_bytes(int bit_depth) { return bit_depth > 8 ? 2 : 1; }
+static inline void fill_planes(DevPlanes *dp, const Pic *p, bool use_b)
+{
+    for (int c = 0; c < 3; c++) {
+        dp->p[c] = use_b ? p->b[c] : p->a[c];
+        dp->stride[c] = p->stride[c];
+        dp->w[c] = p->w[c];
+        dp->h[c] = p->h[c];
+    }
+}
 
 OH_INTERNAL int kernel_error(OhEngine *e);
+OH_INTERNAL int check_params(OhEngine *e, const OhPicParams *p);
 OH_INTERNAL Pic *get_pic(OhEngine *e, int id);
 OH_INTERNAL int check_pics(OhEngine *e, const int *pic_ids, int n, const char *who);
 OH_INTERNAL bool stage_create(OhEngine::Stage *c, size_t bytes);
 OH_INTERNAL OhEngine::Stage *stage_acquire(OhEngine *e, size_t bytes);
 OH_INTERNAL OhEngine::Stage *stage_list(OhEngine *e, const void *list, size_t bytes);
 OH_INTERNAL int stage_in_use(OhEngine *e, OhEngine::Stage *sg, hipStream_t st);
+OH_INTERNAL hipEvent_t sync_event_get(OhEngine *e);
+OH_INTERNAL void sync_event_put(OhEngine *e, hipEvent_t ev);
+OH_INTERNAL void free_dev_frame(OhEngine *e, OhDevFrame *df, bool in_flight = false);
 
 #endif

@@ -322,12 +322,16 @@ class FrameCopy:
     """Deep copy of a finished work list: every array the OhFrame points at is copied into memory this object owns, so the
     list outlives the recorder's next picture.  `.frame` is an OhFrame over the copies (cur_pic / ref_pics as recorded)."""
 
-    def __init__(self, f, pinned_by=None):
+    def __init__(self, f, pinned_by=None, pack_bs=None):
         """pinned_by: the engine library (ctypes handle with oh_host_alloc / oh_host_free): every array is copied into page-locked memory
         from oh_host_alloc and the boundary-strength grids are packed four to the byte (oh_pack_bs), i.e. the list is what a recorder
         that writes into blocks lent by the engine hands over: OhFrame.flags = OH_FRAME_PINNED | OH_FRAME_BS_PACKED, the engine
-        copies it to the GPU by DMA from where it lies."""
+        copies it to the GPU by DMA from where it lies.
+        pack_bs: whether byte grids are packed (OH_FRAME_BS_PACKED) — None: exactly when the list is pinned; True / False give the two
+        other forms of hand-over: ordinary memory with packed grids, pinned memory with byte grids."""
         p = f.p
+        if pack_bs is None:
+            pack_bs = pinned_by is not None
         self.keep = []
         self._pinned, self._lib = [], pinned_by
         g = OhFrame()
@@ -366,7 +370,7 @@ class FrameCopy:
         g.ictu = dup(f.ictu, f.n_ictu * C.sizeof(OhIntraCtu), OhIntraCtu)
         g.sub_start = dup(f.sub_start, (f.n_sub + 1) * 4 if f.n_intra else 0, C.c_uint32)
         g.level_start = dup(f.level_start, (f.n_levels + 1) * 4 if f.n_intra else 0, C.c_uint32)
-        if pinned_by is not None and f.vertical_bs and f.horizontal_bs and not (f.flags & OH_FRAME_BS_PACKED):
+        if pack_bs and f.vertical_bs and f.horizontal_bs and not (f.flags & OH_FRAME_BS_PACKED):
             g.vertical_bs = dup(f.vertical_bs, f.bs_size, C.c_uint8, packed(f.vertical_bs, f.bs_size))
             g.horizontal_bs = dup(f.horizontal_bs, f.bs_size, C.c_uint8, packed(f.horizontal_bs, f.bs_size))
             g.flags |= OH_FRAME_BS_PACKED

@@ -41,6 +41,17 @@ def run_both(eng, p, frame, pics):
     return want_pics[frame.cur_pic], got
 
 
+def sent_by_upload(eng, p, frame):
+    """the bytes of work list that one hand-over of `frame` (cur_pic 2, references 0 and 1) sends to the GPU"""
+    from openhevc_amd.engine import remap_frame
+    ids = {k: eng.pic_alloc(p) for k in (0, 1, 2)}
+    before = eng.upload_bytes()
+    eng.frame_free(eng.frame_upload(remap_frame(frame, ids)))
+    for v in ids.values():
+        eng.pic_free(v)
+    return eng.upload_bytes() - before
+
+
 def assert_same(want, got, tag):
     for c in range(len(want.planes)):
         a, b = want.visible(c), got.visible(c)
@@ -129,11 +140,20 @@ PINNED_CASES = ("i8", "b8_weighted", "b8_ctb16", "b12", "b10_444", "i8_mono", "b
                 "i10_444_ccp_sparse", "b10_bs_from_motion", "b10_ctb16_slices", "b10_tiles_slices")
 
 
-@pytest.mark.parametrize("case", [c for c in CASES if c[0] in PINNED_CASES], ids=[c[0] for c in CASES if c[0] in PINNED_CASES])
-def test_pinned_lists_are_pulled_by_the_gpu(eng, case):
+# the two other forms of hand-over, both staged: ordinary memory with packed grids (a copy with no packing jobs), pinned memory with
+# byte grids (packed out of pinned memory) — on the smallest pictures that reach every optional segment of the arena
+OTHER_FORM_CASES = ("tiny", "b8_ctb16", "b8_422_pcm_bypass", "b10_sparse_lists")
+FORMS = {"pinned_packed": (True, True), "pageable_packed": (False, True), "pinned_bytes": (True, False), "pageable_bytes": (False, False)}
+PINNED_PARAMS = [pytest.param(c, "pinned_packed", id=c[0]) for c in CASES if c[0] in PINNED_CASES] + \
+                [pytest.param(c, form, id=f"{c[0]}-{form}") for c in CASES if c[0] in OTHER_FORM_CASES for form in ("pageable_packed", "pinned_bytes")]
+
+
+@pytest.mark.parametrize("case,form", PINNED_PARAMS)
+def test_pinned_lists_are_pulled_by_the_gpu(eng, case, form):
     """OH_FRAME_PINNED: the same pictures with every array of the work list in page-locked memory from oh_host_alloc (boundary strengths
     packed four to the byte): no staging copy on the host — prep_pull reads the arrays over PCIe from where they lie (odd sizes, tails
-    and every optional array included)"""
+    and every optional array included).  The forms in between (pageable_packed, pinned_bytes) are staged like an ordinary list; whatever
+    the form, the same bytes of a list cross PCIe."""
     name, w, h, bd, chroma, lc, st, knobs = case
     pcm = "pcm" in name
     p = F.pic_params(w, h, bit_depth=bd, chroma_format_idc=chroma, log2_ctb_size=lc,
@@ -141,13 +161,22 @@ def test_pinned_lists_are_pulled_by_the_gpu(eng, case):
                      cb_qp_offset=2 if "weighted" in name else 0, cr_qp_offset=-3 if "weighted" in name else 0)
     rec = F.Recorder(p)
     f = rec.synth(F.synth_params(st, 4100, **knobs), 2, [0, 1])
-    fc = F.FrameCopy(f, pinned_by=eng.L)
-    assert fc.frame.flags & F.OH_FRAME_PINNED
+    pinned, packed = FORMS[form]
+    fc = F.FrameCopy(f, pinned_by=eng.L if pinned else None, pack_bs=packed)
+    assert bool(fc.frame.flags & F.OH_FRAME_PINNED) == pinned
+    assert bool(fc.frame.flags & F.OH_FRAME_BS_PACKED) == (packed and bool(f.vertical_bs))
     rng = np.random.default_rng(41)
     pics = {0: F.HostPic(p, rng=rng), 1: F.HostPic(p, rng=rng), 2: F.HostPic(p, rng=rng)}
+    before = eng.upload_bytes()
     want, got = run_both(eng, p, fc.frame, pics)
-    assert_same(want, got, f"{name} pinned")
+    assert_same(want, got, f"{name} {form}")
+    sent = eng.upload_bytes() - before
     del fc
+    if form != "pinned_packed":                       # copy_bytes does not depend on the form: all four send the same bytes
+        for other, (opin, opack) in FORMS.items():
+            oc = F.FrameCopy(f, pinned_by=eng.L if opin else None, pack_bs=opack)
+            assert sent_by_upload(eng, p, oc.frame) == sent, f"{name}: {other} and {form} send different bytes"
+            del oc
     rec.close()
 
 
