@@ -60,6 +60,23 @@ typedef struct OhPictureHash {
  * SEI, 256 in a prefix SEI as the reference also accepts) fills *out.  Returns 1 found, 0 none, -1 malformed / not an SEI NAL unit. */
 int oh_sei_picture_hash(const uint8_t *nal, size_t size, OhPictureHash *out);
 
+/* The HDR messages of H.265 Annex D, which the reference does not parse: mastering display colour volume (payload type 137, 24 bytes),
+ * content light level information (144, 4 bytes) and alternative transfer characteristics (147, 1 byte); every field big-endian. */
+typedef struct OhHdrSei {
+    int32_t  has_mastering;
+    uint16_t primaries[3][2], white[2];     /* display_primaries_x / _y [c] and white_point_x / _y as coded (units of 0.00002) */
+    uint32_t max_lum, min_lum;              /* payload 137; raw units: 0.0001 cd/m2 both (max_lum / 10000 = nits) */
+    int32_t  has_cll;
+    uint16_t max_cll, max_fall;             /* payload 144: cd/m2; 0 = unknown */
+    int32_t  has_alt_transfer;
+    int32_t  preferred_transfer;            /* payload 147: preferred_transfer_characteristics (H.273) */
+} OhHdrSei;
+/* nal[0 .. size): one (escaped) SEI NAL unit, header first.  The same message walk as oh_sei_picture_hash.  The three messages count
+ * in a prefix SEI only (D.2.1); in a suffix SEI they are passed over.  Returns how many of the three kinds were found (0 .. 3; *out is
+ * zero where nothing was), or -1: not an SEI NAL unit, a message that runs past the unit, or one of the three with a payload shorter
+ * than its fields. */
+int oh_sei_hdr(const uint8_t *nal, size_t size, OhHdrSei *out);
+
 #ifdef __cplusplus
 }
 #endif

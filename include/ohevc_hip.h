@@ -179,6 +179,49 @@ int    oh_pics_convert_colour(OhEngine *e, const int *pic_ids, int n, const OhCo
 /* host only: exactly the integers the kernel receives — A[OH_COL_NA], G[OH_COL_NP], B[OH_COL_NP], misc[OH_COL_NMISC] */
 int    oh_colour_tables(const OhColour *col, int32_t *A, int32_t *G, int32_t *B, int32_t *misc);
 
+/* Light-level statistics of finished pictures (DESIGN.md §3e has the exact definition, which the tests check bit for bit against
+ * tests/light_model.py): what a caller needs to choose OhColour.src_peak from the pictures themselves, where the stream's MaxCLL is
+ * absent or wrong.  Every pixel of the window goes through oh_pics_convert's chroma placement and 16-bit matrix (cv->matrix,
+ * full_range, chroma_filter, win; cv->format and cv->sample are not read; a 4:0:0 picture has Cb = Cr = mid) and the source curve of
+ * oh_pics_convert_colour to linear light l, 2^30 = full scale: 10000 nits for PQ, src_peak nits otherwise.  For HLG that is
+ * SCENE-linear light, before the OOTF (full scale = the nominal peak's scene value 1).  The norm v of a pixel is max(lR, lG, lB)
+ * (OH_NORM_MAXRGB) or its luminance (wR lR + wG lG + wB lB + 2^13) >> 14 (OH_NORM_LUMA).  The curve A and the weights are those of
+ * oh_colour_tables (A, misc[9..11]) for { in_transfer, in_primaries, in_primaries, OH_COL_LINEAR, OH_TONE_NONE, OH_NORM_LUMA,
+ * src_peak, 100, src_peak } (HLG: with 1000 for src_peak; neither depends on it).
+ * The histogram has 16 bins per octave: bin 0 holds v < 2^14 (below 0.15 nits of PQ), bin 1 + 16 (e - 14) + ((v >> (e - 4)) & 15)
+ * the v with floor(log2 v) = e in 14 .. 30; bin 257 is v = 2^30 alone. */
+enum { OH_LL_NBINS = 258 };
+typedef struct OhLightSpec {
+    int32_t in_transfer;          /* H.273: 16 PQ, 18 HLG, 13 sRGB, 1 / 6 / 14 / 15 SDR video */
+    int32_t in_primaries;         /* H.273: 1 BT.709, 9 BT.2020, 12 P3-D65 (the luminance weights of OH_NORM_LUMA) */
+    int32_t norm;                 /* OH_NORM_MAXRGB, OH_NORM_LUMA */
+    float   src_peak;             /* nits at full scale for every transfer except PQ */
+} OhLightSpec;
+typedef struct OhLightLevel {
+    uint64_t pixels, sum;         /* pixels of the window; the sum of their v */
+    uint32_t max, min;            /* of v */
+    uint32_t hist[OH_LL_NBINS];   /* pixels per bin */
+} OhLightLevel;
+/* n finished pictures with identical OhPicParams -> out[0 .. n).  Reads each picture's finished half on the engine stream behind the
+ * work that finished the pictures, waits for the stream like oh_pics_hash and fills out on the host; every call starts from zero.
+ * More than OH_CONV_MAX_PICS pictures are split into several launches.  The results are exact integers and do not depend on the
+ * order of accumulation.  n == 0: OH_OK.
+ * OH_E_ARG, out untouched: a null cv, sp or out, an unknown picture, pictures whose params differ, an empty window or one whose offsets
+ * are not multiples of SubWidthC / SubHeightC, a norm outside its list, a src_peak that is not finite and positive.
+ * OH_E_UNSUPPORTED, out untouched: a transfer or primaries code outside the lists, a matrix outside {1, 5, 6, 9}, a table that
+ * oh_colour_tables would refuse.  HLG takes either norm and any src_peak here (oh_pics_convert_colour restricts both for its OOTF). */
+int      oh_pics_light_level(OhEngine *e, const int *pic_ids, int n, const OhConvert *cv, const OhLightSpec *sp, OhLightLevel *out);
+/* host only: bin(v), v clamped to 2^30 */
+int      oh_light_bin(uint32_t v);
+/* host only: the largest v of a bin: 2^14 - 1 for bin 0, min(((17 + j) << (e - 4)) - 1, 2^30) for bin 1 + 16 (e - 14) + j; a bin
+ * below 0 gives 0, one above 257 gives 2^30 */
+uint32_t oh_light_bin_upper(int bin);
+/* host only: the n pictures pooled as one scene.  b = the smallest bin whose cumulative count times 10^6 reaches ppm times the pixels
+ * of all n (64-bit integers); *value = min(oh_light_bin_upper(b), the largest max of the n): at least ppm / 10^6
+ * of the pixels are at or below *value.  OH_E_ARG: a null pointer, n < 1,
+ * ppm > 10^6, no pixels. */
+int      oh_light_percentile(const OhLightLevel *ll, int n, uint32_t ppm, uint32_t *value);
+
 /* Resizing of finished pictures into engine pictures (DESIGN.md §3c has the exact definition, which the tests check bit for bit
  * against tests/resize_model.py): every plane is resampled on its own in integer arithmetic, separably, horizontal pass first, with
  * an anti-aliased triangle (BILINEAR) or Keys cubic a = -1/2 (BICUBIC) filter whose taps are re-normalised at the window's edges.

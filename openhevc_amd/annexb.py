@@ -1,4 +1,4 @@
-"""ctypes view of include/ohevc_annexb.h (libohevc_host.so): access-unit splitter, NAL scan, NAL unescape, picture-hash SEI."""
+"""ctypes view of include/ohevc_annexb.h (libohevc_host.so): access-unit splitter, NAL scan, NAL unescape, picture-hash SEI, HDR SEIs."""
 import ctypes as C
 import os
 
@@ -17,6 +17,12 @@ class OhNal(C.Structure):
 
 class OhPictureHash(C.Structure):
     _fields_ = [("present", C.c_int32), ("hash_type", C.c_int32), ("md5", (C.c_uint8 * 16) * 3), ("crc", C.c_uint32 * 3), ("checksum", C.c_uint32 * 3)]
+
+
+class OhHdrSei(C.Structure):
+    _fields_ = [("has_mastering", C.c_int32), ("primaries", (C.c_uint16 * 2) * 3), ("white", C.c_uint16 * 2), ("max_lum", C.c_uint32),
+                ("min_lum", C.c_uint32), ("has_cll", C.c_int32), ("max_cll", C.c_uint16), ("max_fall", C.c_uint16),
+                ("has_alt_transfer", C.c_int32), ("preferred_transfer", C.c_int32)]
 
 
 _lib = None
@@ -41,6 +47,8 @@ def lib():
         L.oh_nal_unescape.restype = C.c_long
         L.oh_sei_picture_hash.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(OhPictureHash)]
         L.oh_sei_picture_hash.restype = C.c_int
+        L.oh_sei_hdr.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(OhHdrSei)]
+        L.oh_sei_hdr.restype = C.c_int
         _lib = L
     return _lib
 
@@ -94,3 +102,25 @@ def picture_hash(nal):
     if h.hash_type == 0:
         return 0, [bytes(h.md5[c]) for c in range(3)]
     return h.hash_type, list(h.crc if h.hash_type == 1 else h.checksum)
+
+
+def hdr_sei(nal):
+    """None, or a dict of what the HDR messages of one prefix SEI NAL unit carry (oh_sei_hdr): "primaries" ([(x, y)] * 3), "white",
+    "max_lum", "min_lum" (raw: 0.00002 for the chromaticities, 0.0001 cd/m2 for the luminances) from a mastering display colour volume;
+    "max_cll", "max_fall" (cd/m2, 0 unknown) from a content light level; "preferred_transfer" from alternative transfer
+    characteristics.  Keys of messages the unit does not hold are absent."""
+    h = OhHdrSei()
+    r = lib().oh_sei_hdr(nal, len(nal), C.byref(h))
+    if r < 0:
+        raise ValueError("malformed SEI NAL unit")
+    if not r:
+        return None
+    d = {}
+    if h.has_mastering:
+        d.update(primaries=[(h.primaries[c][0], h.primaries[c][1]) for c in range(3)], white=(h.white[0], h.white[1]),
+                 max_lum=int(h.max_lum), min_lum=int(h.min_lum))
+    if h.has_cll:
+        d.update(max_cll=int(h.max_cll), max_fall=int(h.max_fall))
+    if h.has_alt_transfer:
+        d["preferred_transfer"] = int(h.preferred_transfer)
+    return d

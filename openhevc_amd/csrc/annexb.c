@@ -1,5 +1,5 @@
 /*
- * annexb.c — Annex-B byte stream: access-unit splitter, NAL scan, NAL unescape, picture-hash SEI.  See include/ohevc_annexb.h for the
+ * annexb.c — Annex-B byte stream: access-unit splitter, NAL scan, NAL unescape, picture-hash SEI, HDR SEIs.  See include/ohevc_annexb.h for the
  * reference lines each entry point follows.  Plain C, no dependencies.
  */
 #include "../../include/ohevc_annexb.h"
@@ -141,9 +141,12 @@ long oh_nal_unescape(const uint8_t *src, size_t length, uint8_t *dst, size_t *ds
     return (long)si;
 }
 
-int oh_sei_picture_hash(const uint8_t *nal, size_t size, OhPictureHash *out)
+/* The message walk both SEI readers share: nal[0 .. size) is one (escaped) SEI NAL unit, header first.  Calls on_msg(ctx, nut,
+ * payloadType, payload, payloadSize) for every sei_message(); on_msg returns -1 for a payload it cannot accept.  Returns 0, or -1: not
+ * an SEI NAL unit, a message that runs past the unit, or on_msg said so (the walk stops there). */
+typedef int (*SeiMsgFn)(void *ctx, int nut, unsigned type, const uint8_t *payload, unsigned len);
+static int sei_walk(const uint8_t *nal, size_t size, SeiMsgFn on_msg, void *ctx)
 {
-    memset(out, 0, sizeof(*out));
     if (size < 3)
         return -1;
     const int nut = (nal[0] >> 1) & 0x3F;
@@ -155,9 +158,9 @@ int oh_sei_picture_hash(const uint8_t *nal, size_t size, OhPictureHash *out)
     size_t n = 0;
     oh_nal_unescape(nal, size, rbsp, &n, NULL, 0, NULL);
     size_t p = 2;                                             /* behind the NAL header */
-    int found = 0, bad = 0;
+    int bad = 0;
     /* sei_message()s until only rbsp_trailing_bits are left (hevc_sei.c:183-200 more_rbsp_data): the LAST byte being 0x80.  A 0x80
-     * anywhere else is a payloadType (128, structure_of_pictures_info), not the end: a hash message may follow it in the same NAL */
+     * anywhere else is a payloadType (128, structure_of_pictures_info), not the end: another message may follow it in the same NAL */
     while (n > 0 && rbsp[n - 1] == 0) n--;                    /* cabac_zero_words / trailing zero bytes behind the trailing bits */
     while (p < n && !(p == n - 1 && rbsp[p] == 0x80)) {
         unsigned type = 0, len = 0;
@@ -168,25 +171,82 @@ int oh_sei_picture_hash(const uint8_t *nal, size_t size, OhPictureHash *out)
         if (p >= n) { bad = 1; break; }
         len += rbsp[p++];
         if (p + len > n) { bad = 1; break; }
-        if ((nut == NAL_SEI_SUFFIX && type == 132) || (nut == NAL_SEI_PREFIX && type == 256)) {
-            const uint8_t *q = rbsp + p;
-            if (len < 1) { bad = 1; break; }
-            const int ht = q[0];
-            const unsigned per = ht == 0 ? 16 : ht == 1 ? 2 : ht == 2 ? 4 : 0;
-            if (!per || len < 1 + per) { bad = 1; break; }
-            const unsigned planes = (len - 1) / per < 3 ? (len - 1) / per : 3;      /* monochrome streams carry one */
-            out->present = 1;
-            out->hash_type = ht;
-            for (unsigned c = 0; c < planes; c++) {
-                const uint8_t *v = q + 1 + c * per;
-                if (ht == 0) memcpy(out->md5[c], v, 16);
-                else if (ht == 1) out->crc[c] = ((uint32_t)v[0] << 8) | v[1];
-                else out->checksum[c] = ((uint32_t)v[0] << 24) | ((uint32_t)v[1] << 16) | ((uint32_t)v[2] << 8) | v[3];
-            }
-            found = 1;
-        }
+        if (on_msg(ctx, nut, type, rbsp + p, len) < 0) { bad = 1; break; }
         p += len;
     }
     free(rbsp);
-    return bad ? -1 : found;
+    return bad ? -1 : 0;
+}
+
+static int hash_msg(void *ctx, int nut, unsigned type, const uint8_t *q, unsigned len)
+{
+    OhPictureHash *out = (OhPictureHash *)ctx;
+    if (!((nut == NAL_SEI_SUFFIX && type == 132) || (nut == NAL_SEI_PREFIX && type == 256)))
+        return 0;
+    if (len < 1)
+        return -1;
+    const int ht = q[0];
+    const unsigned per = ht == 0 ? 16 : ht == 1 ? 2 : ht == 2 ? 4 : 0;
+    if (!per || len < 1 + per)
+        return -1;
+    const unsigned planes = (len - 1) / per < 3 ? (len - 1) / per : 3;      /* monochrome streams carry one */
+    out->present = 1;
+    out->hash_type = ht;
+    for (unsigned c = 0; c < planes; c++) {
+        const uint8_t *v = q + 1 + c * per;
+        if (ht == 0) memcpy(out->md5[c], v, 16);
+        else if (ht == 1) out->crc[c] = ((uint32_t)v[0] << 8) | v[1];
+        else out->checksum[c] = ((uint32_t)v[0] << 24) | ((uint32_t)v[1] << 16) | ((uint32_t)v[2] << 8) | v[3];
+    }
+    return 0;
+}
+
+int oh_sei_picture_hash(const uint8_t *nal, size_t size, OhPictureHash *out)
+{
+    memset(out, 0, sizeof(*out));
+    if (sei_walk(nal, size, hash_msg, out) < 0)
+        return -1;
+    return out->present;
+}
+
+static unsigned be16(const uint8_t *v) { return ((unsigned)v[0] << 8) | v[1]; }
+static uint32_t be32(const uint8_t *v) { return ((uint32_t)v[0] << 24) | ((uint32_t)v[1] << 16) | ((uint32_t)v[2] << 8) | v[3]; }
+
+static int hdr_msg(void *ctx, int nut, unsigned type, const uint8_t *q, unsigned len)
+{
+    OhHdrSei *out = (OhHdrSei *)ctx;
+    if (nut != NAL_SEI_PREFIX)
+        return 0;
+    if (type == 137) {                                        /* D.2.28 mastering_display_colour_volume */
+        if (len < 24)
+            return -1;
+        for (int c = 0; c < 3; c++) {
+            out->primaries[c][0] = (uint16_t)be16(q + 4 * c);
+            out->primaries[c][1] = (uint16_t)be16(q + 4 * c + 2);
+        }
+        out->white[0] = (uint16_t)be16(q + 12); out->white[1] = (uint16_t)be16(q + 14);
+        out->max_lum = be32(q + 16); out->min_lum = be32(q + 20);
+        out->has_mastering = 1;
+    } else if (type == 144) {                                 /* D.2.35 content_light_level_info */
+        if (len < 4)
+            return -1;
+        out->max_cll = (uint16_t)be16(q); out->max_fall = (uint16_t)be16(q + 2);
+        out->has_cll = 1;
+    } else if (type == 147) {                                 /* D.2.38 alternative_transfer_characteristics */
+        if (len < 1)
+            return -1;
+        out->preferred_transfer = q[0];
+        out->has_alt_transfer = 1;
+    }
+    return 0;
+}
+
+int oh_sei_hdr(const uint8_t *nal, size_t size, OhHdrSei *out)
+{
+    memset(out, 0, sizeof(*out));
+    if (sei_walk(nal, size, hdr_msg, out) < 0) {
+        memset(out, 0, sizeof(*out));
+        return -1;
+    }
+    return out->has_mastering + out->has_cll + out->has_alt_transfer;
 }

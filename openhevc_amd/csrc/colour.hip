@@ -16,23 +16,9 @@
  * its segment, so the table loads (out of L2) stay a fraction of the pixel traffic.  Stages 2 and 3 are skipped (uniform branches)
  * where they are the identity: no tone curve and no HLG; equal primaries.
  */
-#include "convert_common.h"
+#include "colour_common.h"
 
 namespace {
-
-constexpr int FS = 1 << 30;                                    /* full scale of linear light */
-
-/* 32 x 32 -> 64 bit products as one v_mad_i64_i32 / v_mad_u64_u32 each (the u form where both factors are known not negative) */
-__device__ __forceinline__ int64_t mul64(int a, int b) { return (int64_t)a * (int64_t)b; }
-__device__ __forceinline__ uint64_t mulu64(int a, int b) { return (uint64_t)(uint32_t)a * (uint64_t)(uint32_t)b; }
-
-/* stage 1: a 16-bit code through the source curve.  A does not decrease and steps by less than 2^24 (oh_colour_tables refuses a curve
- * that would not): the product is a full-rate 24-bit multiply. */
-__device__ __forceinline__ int src_curve(const int32_t *A, int v)
-{
-    const int i = v >> 4, f = v & 15, t0 = A[i], t1 = A[i + 1];
-    return min(t0 + (int)((__umul24((unsigned)(t1 - t0), (unsigned)f) + 8u) >> 4), FS);
-}
 
 /* P(T, l) of DESIGN.md §3d for 0 <= l <= 2^30, without a branch: below 128 s is 0, so k = l, the fraction is 0 and the second read
  * (T[l + 1], which exists) does not count.  x is l with its bit s + 6 moved to bit 30: the six bits below it are l >> s, the twelve
@@ -110,8 +96,7 @@ __global__ __launch_bounds__(THREADS) void colour_rgb_kernel(const OhColArgs ca)
             mt.rgb((int)in.L[i], u, v, R, G, B);
             int l0 = src_curve(A, R), l1 = src_curve(A, G), l2 = src_curve(A, B);
             if (gain_on) {
-                const int nrm = luma_norm ? (int)((mulu64(mc[9], l0) + mulu64(mc[10], l1) + mulu64(mc[11], l2) + (1u << 13)) >> 14)
-                                          : max(l0, max(l1, l2));
+                const int nrm = luma_norm ? luma_norm_of(mc[9], mc[10], mc[11], l0, l1, l2) : max(l0, max(l1, l2));
                 const int g = lut(Gt, nrm);
                 l0 = (int)((mulu64(l0, g) + (1u << 19)) >> 20);
                 l1 = (int)((mulu64(l1, g) + (1u << 19)) >> 20);

@@ -1,5 +1,6 @@
 /*
- * convert_common.h — what the picture-to-image kernels share (convert.hip: oh_pics_convert; colour.hip: oh_pics_convert_colour):
+ * convert_common.h — what the kernels that read pictures as images share (convert.hip: oh_pics_convert; colour.hip: oh_pics_convert_colour;
+ * light.hip: oh_pics_light_level):
  * staging of source rows into LDS as 16-byte granules, the aligned store of an LDS image of the destination bytes, the chroma filter
  * and the integer matrix of DESIGN.md §3b, and the output sample types.  Device code only.
  */

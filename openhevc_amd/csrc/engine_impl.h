@@ -199,6 +199,13 @@ struct OhEngine {
     bool        colour_cached = false, colour_on_dev = false;
     std::vector<int32_t> colour_tab;     /* OH_COLT_N, laid out as on the device */
     int32_t     colour_misc[OH_COL_NMISC];
+    /* oh_pics_light_level: table A of its last source curve, host and device, apart from colour_* (neither call disturbs the tables
+     * the other has cached), and the results of the call in HBM */
+    Scratch     light_dev, light_res;
+    OhColour    light_last;
+    bool        light_cached = false, light_on_dev = false;
+    std::vector<int32_t> light_tab;      /* OH_COLT_N as colour_build lays them out; OH_COLT_G of them go to the device */
+    int32_t     light_misc[OH_COL_NMISC];
     uint32_t    spin_limit = 1u << 22;   /* polls (with s_sleep between them, ~1 s in all) before a waiting workgroup gives up; OHEVC_SPIN_LIMIT */
 };
 

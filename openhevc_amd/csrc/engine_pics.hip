@@ -1,7 +1,7 @@
 /*
  * engine_pics.hip — what the engine does with finished pictures beside the reconstruction path (host side; the kernels are md5.hip,
- * hash.hip, convert.hip, colour.hip and resize.hip): plane upload and download, the two-phase window fetch, picture hashes, conversion
- * to YUV / RGB images, with the colour tables of the HDR forms, and resizing into engine pictures.
+ * hash.hip, convert.hip, colour.hip, light.hip and resize.hip): plane upload and download, the two-phase window fetch, picture hashes,
+ * conversion to YUV / RGB images, with the colour tables of the HDR forms, light-level statistics, and resizing into engine pictures.
  */
 #include <cmath>
 #include "engine_impl.h"
@@ -781,6 +781,164 @@ extern "C" int oh_pics_convert_colour(OhEngine *e, const int *pic_ids, int n, co
     if (!n)
         return OH_OK;
     return pics_convert(e, "oh_pics_convert_colour", pic_ids, n, cv, col, dst, image_stride, dst_bytes);
+}
+
+/* ---------------- light-level statistics (light.hip) ---------------- */
+extern "C" int oh_light_bin(uint32_t v)
+{
+    v = std::min(v, (uint32_t)1 << 30);
+    if (v < (1u << 14))
+        return 0;
+    const int e = 31 - __builtin_clz(v);
+    return 1 + 16 * (e - 14) + (int)((v >> (e - 4)) & 15);
+}
+
+extern "C" uint32_t oh_light_bin_upper(int bin)
+{
+    if (bin <= 0)
+        return bin < 0 ? 0 : (1u << 14) - 1;
+    if (bin >= OH_LL_NBINS)
+        return 1u << 30;
+    const int e = 14 + (bin - 1) / 16, j = (bin - 1) % 16;
+    return (uint32_t)std::min<uint64_t>(((uint64_t)(17 + j) << (e - 4)) - 1, (uint64_t)1 << 30);
+}
+
+extern "C" int oh_light_percentile(const OhLightLevel *ll, int n, uint32_t ppm, uint32_t *value)
+{
+    if (!ll || !value || n < 1 || ppm > 1000000u)
+        return OH_E_ARG;
+    uint64_t total = 0;
+    uint32_t top = 0;
+    for (int i = 0; i < n; i++) {
+        total += ll[i].pixels;
+        top = std::max(top, ll[i].max);
+    }
+    if (!total)
+        return OH_E_ARG;
+    const uint64_t need = (uint64_t)ppm * total;
+    uint64_t cum = 0;
+    int b = 0;
+    for (; b < OH_LL_NBINS - 1; b++) {                          /* histograms that hold fewer than `pixels` end in the last bin */
+        for (int i = 0; i < n; i++) cum += ll[i].hist[b];
+        if (cum * 1000000u >= need)
+            break;
+    }
+    *value = std::min(oh_light_bin_upper(b), top);
+    return OH_OK;
+}
+
+/* the OhColour whose table A and luminance weights the light-level pass uses.  Neither depends on src_peak; HLG is built with 1000
+ * nits so that a peak outside what oh_pics_convert_colour takes for its OOTF passes colour_check */
+static OhColour light_colour(const OhLightSpec *sp)
+{
+    OhColour c;
+    memset(&c, 0, sizeof(c));
+    c.in_transfer = sp->in_transfer;
+    c.in_primaries = c.out_primaries = sp->in_primaries;
+    c.out_transfer = OH_COL_LINEAR; c.tone = OH_TONE_NONE; c.norm = OH_NORM_LUMA;
+    c.src_peak = c.white = sp->in_transfer == 18 ? 1000.0f : sp->src_peak;
+    c.dst_peak = 100.0f;
+    return c;
+}
+
+/* table A of col in the engine's device copy for this call, as colour_stage does for the three tables of oh_pics_convert_colour, with
+ * a cache and a device buffer of its own.  Every light-level call ends with a wait: no launch reads the device copy while it changes. */
+static int light_stage(OhEngine *e, const OhColour *col, OhLightArgs *la)
+{
+    if (!e->light_cached || memcmp(&e->light_last, col, sizeof(*col))) {
+        e->light_cached = false;
+        e->light_tab.resize((size_t)OH_COLT_N);
+        std::string why;
+        const int rc = colour_build(col, e->light_tab.data(), e->light_misc, &why);
+        if (rc) FAIL(e, rc == OH_E_ARG ? OH_E_UNSUPPORTED : rc, "oh_pics_light_level: %s", why.c_str());
+        e->light_last = *col;
+        e->light_cached = true;
+        e->light_on_dev = false;
+    }
+    const size_t bytes = (size_t)OH_COLT_G * sizeof(int32_t);
+    if (!e->light_dev.p) {
+        const int rc = scratch_reserve(e, &e->light_dev, bytes);
+        if (rc) return rc;
+        e->light_on_dev = false;
+    }
+    if (!e->light_on_dev) {
+        OhEngine::Stage *sg = stage_acquire(e, bytes);
+        if (!sg)
+            FAIL(e, OH_E_NOMEM, "oh_pics_light_level: no staging buffer for %zu bytes of table", bytes);
+        memcpy(sg->p, e->light_tab.data(), bytes);
+        HIPCHK(e, hipMemcpyAsync(e->light_dev.p, sg->p, bytes, hipMemcpyHostToDevice, e->stream));
+        { const int rc = stage_in_use(e, sg, e->stream); if (rc) return rc; }
+        e->light_on_dev = true;
+    }
+    la->tab = (const int32_t *)e->light_dev.p;
+    for (int j = 0; j < 3; j++) la->w[j] = e->light_misc[9 + j];
+    return OH_OK;
+}
+
+extern "C" int oh_pics_light_level(OhEngine *e, const int *pic_ids, int n, const OhConvert *cv, const OhLightSpec *sp, OhLightLevel *out)
+{
+    const char *who = "oh_pics_light_level";
+    if (!e || n < 0 || !cv || !sp || !out || (n && !pic_ids))
+        return OH_E_ARG;
+    if (sp->norm < OH_NORM_MAXRGB || sp->norm > OH_NORM_LUMA)
+        FAIL(e, OH_E_ARG, "%s: norm %d outside its list", who, sp->norm);
+    if (!std::isfinite(sp->src_peak) || !(sp->src_peak > 0))
+        FAIL(e, OH_E_ARG, "%s: src_peak is finite and positive", who);
+    const OhColour col = light_colour(sp);
+    std::string why;
+    { const int rc = colour_check(&col, &why); if (rc) FAIL(e, OH_E_UNSUPPORTED, "%s: %s", who, why.c_str()); }
+    if (!n)
+        return OH_OK;
+    { const int rc = check_pics(e, pic_ids, n, who); if (rc) return rc; }
+    const Pic *p0 = get_pic(e, pic_ids[0]);
+    const int other = first_other_params(e, pic_ids, n);
+    if (other < n)
+        FAIL(e, OH_E_ARG, "%s: picture %d has other params than picture %d", who, pic_ids[other], pic_ids[0]);
+    OhConvert k16 = *cv;                                        /* format and sample are not the caller's to set: the 16-bit R'G'B' */
+    k16.format = OH_CONV_RGB; k16.sample = OH_CONV_U16;
+    size_t ib = 0;
+    { const int rc = conv_check(&p0->p, &k16, &ib, &why); if (rc) FAIL(e, rc, "%s: %s", who, why.c_str()); }
+    HIPCHK(e, hipSetDevice(e->device));
+    OhLightArgs la;
+    OhConvArgs &a = la.c;
+    memset(&la, 0, sizeof(la));
+    const OhPicParams &p = p0->p;
+    const int bpp = sample_bytes(p.bit_depth);
+    for (int c = 0; c < 3; c++) a.pitch[c] = p0->stride[c] * bpp;
+    a.cw = p0->w[1]; a.ch = p0->h[1];
+    a.left = cv->win.left; a.top = cv->win.top;
+    a.W = p.width - cv->win.left - cv->win.right; a.H = p.height - cv->win.top - cv->win.bottom;
+    a.cf = p.chroma_format_idc; a.bd = p.bit_depth; a.filter = cv->chroma_filter;
+    { const int rc = oh_convert_coeffs(&k16, p.bit_depth, a.k, OH_CONV_NCOEFFS); if (rc) FAIL(e, rc, "%s: no coefficients for this conversion", who); }
+    la.luma = sp->norm == OH_NORM_LUMA;
+    { const int rc = light_stage(e, &col, &la); if (rc) return rc; }
+    const size_t bytes = (size_t)n * sizeof(OhLightDev);
+    { const int rc = scratch_reserve(e, &e->light_res, bytes); if (rc) return rc; }       /* every call ends with a wait: the old buffer is idle */
+    OhEngine::Stage *sg = stage_acquire(e, bytes);
+    if (!sg)
+        FAIL(e, OH_E_NOMEM, "%s: no staging buffer for %d results", who, n);
+    HIPCHK(e, hipMemsetAsync(e->light_res.p, 0, bytes, e->stream));
+    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
+        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+        for (int i = 0; i < m; i++) {
+            const Pic *q = get_pic(e, pic_ids[i0 + i]);
+            for (int c = 0; c < 3; c++) a.src[i][c] = p.chroma_format_idc || !c ? final_planes(q)[c] : nullptr;
+        }
+        la.res = (OhLightDev *)e->light_res.p + i0;
+        ohk_light(&la, m, e->stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    HIPCHK(e, hipMemcpyAsync(sg->p, e->light_res.p, bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    { const int ke = kernel_error(e); if (ke) return ke; }     /* a kernel that gave up: these samples are not the picture */
+    const OhLightDev *r = (const OhLightDev *)sg->p;
+    for (int i = 0; i < n; i++) {
+        out[i].pixels = (uint64_t)a.W * (uint64_t)a.H;
+        out[i].sum = r[i].sum;
+        out[i].max = r[i].max; out[i].min = ~r[i].not_min;
+        memcpy(out[i].hist, r[i].hist, sizeof(out[i].hist));
+    }
+    return OH_OK;
 }
 
 /* ---------------- resizing into engine pictures (resize.hip) ---------------- */

@@ -50,6 +50,24 @@ struct OhColArgs {
     int32_t        misc[20];         /* OH_COL_NMISC */
 };
 
+/* light-level statistics (light.hip): the geometry and the 16-bit matrix of an RGB conversion (c.dst, c.image_stride and
+ * c.nc are not read), table A of oh_colour_tables in device memory (OH_COLT_G int32: padded to whole 16-byte granules) and the result
+ * of the launch's first picture, both in device memory that the engine owns and prepares on the stream in front of the launch. */
+enum { OH_LL_ROWS = 32,              /* image rows per workgroup: it loads the table once for all of them */
+       OH_LL_CW = 1024 };            /* image columns per workgroup */
+struct OhLightDev {                  /* one picture's sums; cleared to zero in front of the launch */
+    unsigned long long sum;
+    uint32_t max, not_min;           /* not_min: the largest ~v, so that zero is the neutral start of all four */
+    uint32_t hist[258];              /* OH_LL_NBINS */
+};
+struct OhLightArgs {
+    OhConvArgs     c;
+    const int32_t *tab;
+    OhLightDev    *res;
+    int32_t        w[3];             /* Q14 luminance weights (misc[9..11] of oh_colour_tables) */
+    int32_t        luma;             /* 1: OH_NORM_LUMA, 0: OH_NORM_MAXRGB */
+};
+
 /* picture resizing (resize.hip): what one launch set needs, by value in the kernel arguments like OhConvArgs.  Two plane
  * classes (0 luma, 1 chroma), each with its own geometry and tap tables; the tables live in device memory that the engine owns and
  * fills (engine_pics.hip: oh_pics_resize) on the stream in front of the launches. */
@@ -93,6 +111,8 @@ void ohk_md5(const OhMd5Job *jobs, int n, void *digests, hipStream_t st);
 void ohk_convert(const OhConvArgs *a, int format, int sample, int n, hipStream_t st);
 /* format: an RGB format, sample: U8 .. F32 (checked by the caller); n pictures of a.c.src */
 void ohk_colour(const OhColArgs *a, int format, int sample, int n, hipStream_t st);
+/* n pictures of a.c.src into a.res[0 .. n) */
+void ohk_light(const OhLightArgs *a, int n, hipStream_t st);
 void ohk_hash(int kind, const OhMd5Job *jobs, const uint32_t *first, const uint32_t *task_map, int n_jobs, int n_tasks, uint32_t *partials,
               uint32_t *out, hipStream_t st);
 void ohk_inter(const OhBatch *B, int n, const OhPicParams *p, uint32_t max_luma, uint32_t max_chroma, hipStream_t st);

@@ -88,6 +88,85 @@ def colour_tables(col):
     return A, G, B, misc
 
 
+LL_NBINS, LL_FULL = 258, 1 << 30                                                       # OH_LL_NBINS; full scale of linear light
+
+
+class OhLightSpec(C.Structure):                               # include/ohevc_hip.h
+    _fields_ = [("in_transfer", C.c_int32), ("in_primaries", C.c_int32), ("norm", C.c_int32), ("src_peak", C.c_float)]
+
+
+class OhLightLevel(C.Structure):                              # include/ohevc_hip.h
+    _fields_ = [("pixels", C.c_uint64), ("sum", C.c_uint64), ("max", C.c_uint32), ("min", C.c_uint32), ("hist", C.c_uint32 * LL_NBINS)]
+
+
+class LightLevel:
+    """the light-level statistics of one picture (OhLightLevel): pixels, sum, max, min of the norm v (2^30 = full scale) and hist, a
+    numpy uint32 array of LL_NBINS counts; full_scale: the nits of 2^30 they were measured with (None: not known)"""
+    __slots__ = ("pixels", "sum", "max", "min", "hist", "full_scale")
+
+    def __init__(self, pixels, sum, max, min, hist, full_scale=None):
+        self.pixels, self.sum, self.max, self.min = int(pixels), int(sum), int(max), int(min)
+        self.hist = np.ascontiguousarray(hist, dtype=np.uint32)
+        if self.hist.shape != (LL_NBINS,):
+            raise ValueError(f"hist: {LL_NBINS} counts, not {self.hist.shape}")
+        self.full_scale = None if full_scale is None else float(full_scale)
+
+    def __repr__(self):
+        return f"LightLevel(pixels={self.pixels}, sum={self.sum}, max={self.max}, min={self.min})"
+
+    def as_struct(self):
+        ll = OhLightLevel(self.pixels, self.sum, self.max, self.min)
+        C.memmove(ll.hist, self.hist.ctypes.data, 4 * LL_NBINS)
+        return ll
+
+
+def light_bin(v):
+    """oh_light_bin (host only): the histogram bin of a norm v, v clamped to 2^30"""
+    return int(lib().oh_light_bin(int(v)))
+
+
+def light_bin_upper(b):
+    """oh_light_bin_upper (host only): the largest v of a bin"""
+    return int(lib().oh_light_bin_upper(int(b)))
+
+
+def light_percentile(lls, ppm=999900):
+    """oh_light_percentile (host only): the pictures of lls (LightLevel) pooled as one scene -> the upper edge of the first bin at
+    which ppm millionths of the pixels are reached, at most the largest max; in units of 2^-30 of the full scale"""
+    lls = list(lls)
+    arr = (OhLightLevel * max(len(lls), 1))(*[ll.as_struct() for ll in lls])
+    v = C.c_uint32()
+    rc = lib().oh_light_percentile(arr, len(lls), int(ppm), C.byref(v))
+    if rc != 0:
+        err = EngineError(f"oh_light_percentile failed ({rc})")
+        err.code = rc
+        raise err
+    return v.value
+
+
+def light_nits(value, in_transfer, src_peak):
+    """a norm value of the light-level pass in nits: 2^30 is 10000 nits for PQ (in_transfer 16), src_peak nits otherwise (HLG: of scene
+    light, before the OOTF)"""
+    return value / LL_FULL * (10000.0 if int(in_transfer) == 16 else float(src_peak))
+
+
+def source_peak(in_transfer, lls=None, sei=None, ppm=999900, default=1000.0):
+    """src_peak in nits for make_colour, from the first of these that is there: the measured percentile of lls (LightLevel of
+    Engine.pics_light_level, pooled as one scene; other transfers than PQ scale by the full scale they were measured with, default
+    where that is not known); the SEI's MaxCLL (sei: the dict of annexb.hdr_sei) when it is not zero; the mastering display's
+    max_lum / 10000 when present and not zero; default.  A result at or below the display's dst_peak means the content fits the
+    display: convert with tone="none" (OH_TONE_BT2390 refuses dst_peak >= src_peak)."""
+    if lls:
+        lls = list(lls)
+        return light_nits(light_percentile(lls, ppm), in_transfer, lls[0].full_scale if lls[0].full_scale is not None else default)
+    if sei:
+        if sei.get("max_cll"):
+            return float(sei["max_cll"])
+        if sei.get("max_lum"):
+            return sei["max_lum"] / 10000.0
+    return float(default)
+
+
 class OhResize(C.Structure):                                  # include/ohevc_hip.h
     _fields_ = [("filter", C.c_int32), ("win", OhWindow), ("width", C.c_int32), ("height", C.c_int32)]
 
@@ -191,6 +270,11 @@ def lib():
         L.oh_convert_coeffs.argtypes = [C.POINTER(OhConvert), I, C.POINTER(C.c_int32), I]
         L.oh_pics_convert_colour.argtypes = [V, C.POINTER(C.c_int), I, C.POINTER(OhConvert), C.POINTER(OhColour), V, C.c_size_t, C.c_size_t]
         L.oh_colour_tables.argtypes = [C.POINTER(OhColour)] + [C.POINTER(C.c_int32)] * 4
+        L.oh_pics_light_level.argtypes = [V, C.POINTER(C.c_int), I, C.POINTER(OhConvert), C.POINTER(OhLightSpec), C.POINTER(OhLightLevel)]
+        L.oh_light_bin.argtypes = [C.c_uint32]
+        L.oh_light_bin_upper.argtypes = [I]
+        L.oh_light_bin_upper.restype = C.c_uint32
+        L.oh_light_percentile.argtypes = [C.POINTER(OhLightLevel), I, C.c_uint32, C.POINTER(C.c_uint32)]
         L.oh_pics_resize.argtypes = [V, C.POINTER(C.c_int), C.POINTER(C.c_int), I, C.POINTER(OhResize)]
         L.oh_resize_taps.argtypes = [I, I, I, I, C.POINTER(C.c_int32), C.POINTER(C.c_int16), I, C.POINTER(C.c_int)]
         L.oh_resize_max_taps.argtypes = [I, I, I]
@@ -443,6 +527,23 @@ class Engine:
             # an event on the destroyed stream when the tensor is freed.
             cur.wait_stream(es)
         return out
+
+    def pics_light_level(self, pids, in_transfer, *, in_primaries=9, norm="maxrgb", src_peak=1000.0, window=(0, 0, 0, 0), matrix=9,
+                         full_range=False, chroma="linear"):
+        """light-level statistics of finished pictures, computed on the GPU (oh_pics_light_level): a LightLevel per picture over the
+        norm ("maxrgb" or "luma") of every pixel's linear-light R, G, B, 2^30 = full scale (10000 nits for PQ, src_peak nits
+        otherwise).  in_transfer / in_primaries / matrix are H.273 codes; window = (left, right, top, bottom), luma samples.  Waits
+        for the engine stream."""
+        if norm not in COL_NORM:
+            raise ValueError(f"norm must be one of {sorted(COL_NORM)}, not {norm!r}")
+        pids = list(pids)
+        n = len(pids)
+        cv = make_convert("rgb", CONV_U16, window, matrix, full_range, chroma)
+        sp = OhLightSpec(int(in_transfer), int(in_primaries), COL_NORM[norm], float(src_peak))
+        out = (OhLightLevel * max(n, 1))()
+        self._chk(self.L.oh_pics_light_level(self.h, (C.c_int * max(n, 1))(*pids), n, C.byref(cv), C.byref(sp), out), "oh_pics_light_level")
+        fs = 10000.0 if int(in_transfer) == 16 else float(src_peak)
+        return [LightLevel(o.pixels, o.sum, o.max, o.min, np.frombuffer(o.hist, dtype=np.uint32).copy(), fs) for o in out[:n]]
 
     def pics_resize(self, pids, size, *, window=(0, 0, 0, 0), filter="bilinear", out=None):
         """finished pictures -> resized engine pictures (oh_pics_resize): size = (width, height) of the image in luma samples, window =
