@@ -253,6 +253,45 @@ int oh_resize_taps(int src_extent, int dst_extent, int filter, int phase, int32_
 /* host only: the largest number of taps of an output sample of that axis (OH_E_ARG as above) */
 int oh_resize_max_taps(int src_extent, int dst_extent, int filter);
 
+/* Comparison of finished pictures (DESIGN.md §3f has the exact definition, which the tests check bit for bit against
+ * tests/compare_model.py): per plane of a pair (a, b) the number of differing samples, sum |a - b|, sum (a - b)^2, max |a - b|, the
+ * first differing sample in raster order, and SSIM over 8x8 windows at stride 4 as an exact integer sum of Q30 window values — what
+ * PSNR and mean SSIM are made of, and the answer to "which plane, how many samples, where is the first one" behind a hash mismatch,
+ * without a host copy of a picture.  Every field is an integer sum, count or extremum: the result does not depend on the order of
+ * accumulation. */
+enum { OH_CMP_SSIM = 1 };                     /* flags: also compute SSIM; without it the ssim_* fields are 0 */
+enum { OH_CMP_NONE = 0xFFFFFFFFu };           /* first_x / first_y of a plane without a differing sample */
+typedef struct OhCompareSpec {
+    OhWindow win;                             /* luma samples, rules as for oh_pics_convert; plane c's window is it shifted by oh_hshift / oh_vshift */
+    int32_t  flags;                           /* 0 or OH_CMP_SSIM */
+} OhCompareSpec;
+typedef struct OhPlaneDiff {
+    uint64_t samples;                         /* samples of the plane's window */
+    uint64_t differing;                       /* samples with a != b */
+    uint64_t sad, sse;                        /* sum |a - b|, sum (a - b)^2 */
+    uint32_t max_abs;                         /* max |a - b| */
+    uint32_t first_x, first_y;                /* first differing sample in raster order, plane-window coordinates */
+    uint64_t ssim_windows;                    /* 8x8 windows evaluated */
+    int64_t  ssim_sum;                        /* sum over the windows of their SSIM in Q30 (signed) */
+} OhPlaneDiff;
+typedef struct OhCompare { OhPlaneDiff plane[3]; } OhCompare;   /* planes a 4:0:0 picture lacks: all zero, first_* = OH_CMP_NONE */
+/* n pairs (a_ids[i], b_ids[i]) of finished pictures, all 2n with identical OhPicParams -> out[0 .. n).  Reads each picture's finished
+ * half on the engine stream behind the work that finished the pictures, waits for the stream like oh_pics_light_level and fills out on
+ * the host; every call starts from zero.  More than OH_CONV_MAX_PICS pairs are split into several launches.  A picture may appear in
+ * many pairs and as both members of one; nothing is written to pictures.  n == 0: OH_OK.
+ * OH_E_ARG, out untouched: a null sp, out or id array, an unknown picture, pictures whose params differ anywhere among the 2n (so
+ * pictures of different bit depth, chroma format or size are an OH_E_ARG, never OH_E_UNSUPPORTED), an empty window or one whose offsets
+ * are not multiples of SubWidthC / SubHeightC, flag bits other than OH_CMP_SSIM.  No combination gives OH_E_UNSUPPORTED. */
+int     oh_pics_compare(OhEngine *e, const int *a_ids, const int *b_ids, int n, const OhCompareSpec *sp, OhCompare *out);
+/* host only: c1 = (64 M^2 + 5000) / 10000 and c2 = (9 * 64 * 63 M^2 + 5000) / 10000 with M = 2^bit_depth - 1, in 64-bit integers (8 bit:
+ * 416 and 235963).  OH_E_ARG: a null pointer, a bit depth outside 8 / 9 / 10 / 12. */
+int     oh_compare_ssim_consts(int bit_depth, int64_t *c1, int64_t *c2);
+/* host only: the Q30 value of one 8x8 window from its sums s1 = sum a, s2 = sum b, ss = sum a^2 + sum b^2, s12 = sum ab — the very
+ * function the kernel evaluates (csrc/compare_common.h).  A bit depth outside 8 / 9 / 10 / 12 gives 0. */
+int64_t oh_compare_ssim_window(int bit_depth, uint32_t s1, uint32_t s2, uint64_t ss, uint64_t s12);
+/* host only: 10 log10(M^2 samples / sse) in dB; +infinity for sse 0; NaN for samples 0 */
+double  oh_compare_psnr(uint64_t sse, uint64_t samples, int bit_depth);
+
 /* SHVC inter-layer reference picture: resample the finished base-layer picture src_pic into
  * the enhancement-layer picture dst_pic, bit-exact with the reference's whole-picture slot
  * HEVCDSPContext.upsample_base_layer_frame (hevcdsp_template.c:2164-2438, call site hevc.c:3241).

@@ -1,10 +1,13 @@
 /*
  * engine_pics.hip — what the engine does with finished pictures beside the reconstruction path (host side; the kernels are md5.hip,
- * hash.hip, convert.hip, colour.hip, light.hip and resize.hip): plane upload and download, the two-phase window fetch, picture hashes,
- * conversion to YUV / RGB images, with the colour tables of the HDR forms, light-level statistics, and resizing into engine pictures.
+ * hash.hip, convert.hip, colour.hip, light.hip, compare.hip and resize.hip): plane upload and download, the two-phase window fetch,
+ * picture hashes, conversion to YUV / RGB images, with the colour tables of the HDR forms, light-level statistics, comparison of two
+ * pictures, and resizing into engine pictures.
  */
 #include <cmath>
+#include <limits>
 #include "engine_impl.h"
+#include "compare_common.h"
 
 /* at least `bytes` of device scratch, grow-only in 1 MiB steps.  Growing frees the old block: the caller has made sure that nothing
  * enqueued still uses it. */
@@ -937,6 +940,124 @@ extern "C" int oh_pics_light_level(OhEngine *e, const int *pic_ids, int n, const
         out[i].sum = r[i].sum;
         out[i].max = r[i].max; out[i].min = ~r[i].not_min;
         memcpy(out[i].hist, r[i].hist, sizeof(out[i].hist));
+    }
+    return OH_OK;
+}
+
+/* ---------------- comparison of two pictures (compare.hip) ---------------- */
+static bool compare_depth_ok(int bit_depth) { return bit_depth == 8 || bit_depth == 9 || bit_depth == 10 || bit_depth == 12; }
+
+extern "C" int oh_compare_ssim_consts(int bit_depth, int64_t *c1, int64_t *c2)
+{
+    if (!c1 || !c2 || !compare_depth_ok(bit_depth))
+        return OH_E_ARG;
+    compare_ssim_consts(bit_depth, c1, c2);
+    return OH_OK;
+}
+
+extern "C" int64_t oh_compare_ssim_window(int bit_depth, uint32_t s1, uint32_t s2, uint64_t ss, uint64_t s12)
+{
+    if (!compare_depth_ok(bit_depth))
+        return 0;
+    int64_t c1, c2;
+    compare_ssim_consts(bit_depth, &c1, &c2);
+    return compare_ssim_window(c1, c2, s1, s2, ss, s12);
+}
+
+extern "C" double oh_compare_psnr(uint64_t sse, uint64_t samples, int bit_depth)
+{
+    if (!samples)
+        return std::numeric_limits<double>::quiet_NaN();
+    if (!sse)
+        return std::numeric_limits<double>::infinity();
+    const double M = (double)((1u << bit_depth) - 1);
+    return 10.0 * std::log10(M * M * (double)samples / (double)sse);
+}
+
+extern "C" int oh_pics_compare(OhEngine *e, const int *a_ids, const int *b_ids, int n, const OhCompareSpec *sp, OhCompare *out)
+{
+    const char *who = "oh_pics_compare";
+    if (!e || n < 0 || !sp || !out || (n && (!a_ids || !b_ids)))
+        return OH_E_ARG;
+    if (sp->flags & ~OH_CMP_SSIM)
+        FAIL(e, OH_E_ARG, "%s: flags %#x: OH_CMP_SSIM is the only one", who, (unsigned)sp->flags);
+    if (!n)
+        return OH_OK;
+    { const int rc = check_pics(e, a_ids, n, who); if (rc) return rc; }
+    { const int rc = check_pics(e, b_ids, n, who); if (rc) return rc; }
+    std::vector<int> all(a_ids, a_ids + n);
+    all.insert(all.end(), b_ids, b_ids + n);
+    const int other = first_other_params(e, all.data(), 2 * n);
+    if (other < 2 * n)
+        FAIL(e, OH_E_ARG, "%s: picture %d has other params than picture %d", who, all[other], all[0]);
+    const Pic *p0 = get_pic(e, a_ids[0]);
+    const OhPicParams &p = p0->p;
+    std::string why;
+    if (!crop_window_ok(&p, sp->win, true, &why))
+        FAIL(e, OH_E_ARG, "%s: %s", who, why.c_str());
+    HIPCHK(e, hipSetDevice(e->device));
+    OhCmpArgs a;
+    memset(&a, 0, sizeof(a));
+    const int np = p.chroma_format_idc ? 3 : 1, bpp = sample_bytes(p.bit_depth);
+    const int W = p.width - sp->win.left - sp->win.right, H = p.height - sp->win.top - sp->win.bottom;
+    for (int c = 0; c < np; c++) a.pitch[c] = p0->stride[c] * bpp;
+    for (int c = 0; c < (np > 1 ? 2 : 1); c++) {
+        OhCmpClass &k = a.k[c];
+        const int hs = oh_hshift(&p, c), vs = oh_vshift(&p, c);
+        k.x0 = sp->win.left >> hs; k.y0 = sp->win.top >> vs;
+        k.w = W >> hs; k.h = H >> vs;
+        k.tx = std::max(1, ((k.w >> 2) + OH_CMP_TW / 4 - 1) / (OH_CMP_TW / 4));
+        k.ty = std::max(1, ((k.h >> 2) + OH_CMP_TH / 4 - 1) / (OH_CMP_TH / 4));
+    }
+    a.np = np; a.bd = p.bit_depth; a.ssim = (sp->flags & OH_CMP_SSIM) != 0;
+    const size_t bytes = (size_t)n * 3 * OH_CMP_SLOTS * sizeof(OhCmpDev);
+    { const int rc = scratch_reserve(e, &e->compare_res, bytes); if (rc) return rc; }     /* every call ends with a wait: the old buffer is idle */
+    OhEngine::Stage *sg = stage_acquire(e, bytes);
+    if (!sg)
+        FAIL(e, OH_E_NOMEM, "%s: no staging buffer for %d results", who, n);
+    HIPCHK(e, hipMemsetAsync(e->compare_res.p, 0, bytes, e->stream));
+    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
+        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+        for (int i = 0; i < m; i++) {
+            const Pic *qa = get_pic(e, a_ids[i0 + i]), *qb = get_pic(e, b_ids[i0 + i]);
+            for (int c = 0; c < 3; c++) {
+                a.a[i][c] = c < np ? final_planes(qa)[c] : nullptr;
+                a.b[i][c] = c < np ? final_planes(qb)[c] : nullptr;
+            }
+        }
+        a.res = (OhCmpDev *)e->compare_res.p + (size_t)i0 * 3 * OH_CMP_SLOTS;
+        ohk_compare(&a, m, e->stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    HIPCHK(e, hipMemcpyAsync(sg->p, e->compare_res.p, bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    { const int ke = kernel_error(e); if (ke) return ke; }     /* a kernel that gave up: these samples are not the pictures */
+    const OhCmpDev *r = (const OhCmpDev *)sg->p;
+    for (int i = 0; i < n; i++) {
+        memset(&out[i], 0, sizeof(out[i]));
+        for (int c = 0; c < 3; c++) {
+            OhPlaneDiff &d = out[i].plane[c];
+            d.first_x = d.first_y = OH_CMP_NONE;
+            if (c >= np)
+                continue;
+            const OhCmpClass &k = a.k[c != 0];
+            uint32_t not_first = 0;
+            uint64_t ssim_sum = 0;
+            for (int s = 0; s < OH_CMP_SLOTS; s++) {            /* the slots the tiles added into */
+                const OhCmpDev &v = r[((size_t)i * 3 + c) * OH_CMP_SLOTS + s];
+                d.differing += v.differing; d.sad += v.sad; d.sse += v.sse; ssim_sum += v.ssim_sum;
+                d.max_abs = std::max(d.max_abs, v.max_abs); not_first = std::max(not_first, v.not_first);
+            }
+            d.samples = (uint64_t)k.w * (uint64_t)k.h;
+            if (not_first) {
+                const uint32_t key = ~not_first;
+                d.first_x = key % (uint32_t)k.w; d.first_y = key / (uint32_t)k.w;
+            }
+            if (a.ssim) {
+                d.ssim_windows = (uint64_t)std::max((k.w >> 2) - 1, 0) * (uint64_t)std::max((k.h >> 2) - 1, 0);
+                d.ssim_sum = (int64_t)ssim_sum;
+            }
+        }
     }
     return OH_OK;
 }

@@ -68,6 +68,31 @@ struct OhLightArgs {
     int32_t        luma;             /* 1: OH_NORM_LUMA, 0: OH_NORM_MAXRGB */
 };
 
+/* picture comparison (compare.hip): the finished planes of the pairs of one launch by value in the kernel arguments, two
+ * plane classes (0 luma, 1 chroma) with the plane's window and its tiling, and the results of the launch's first pair in device memory
+ * that the engine owns and clears on the stream in front of the launch. */
+enum { OH_CMP_TW = 256,              /* plane columns per workgroup tile: 64 blocks of 4 x 4 */
+       OH_CMP_TH = 32,               /* plane rows per workgroup tile: 8 block rows */
+       OH_CMP_SLOTS = 8 };           /* partial results per plane of a pair: tile t adds into slot t % OH_CMP_SLOTS, the host combines them */
+struct OhCmpDev {                    /* one slot of one plane of one pair, a 64-byte line of its own; cleared to zero in front of the launch */
+    unsigned long long differing, sad, sse;
+    unsigned long long ssim_sum;     /* two's complement of the signed sum */
+    uint32_t max_abs, not_first;     /* not_first: the largest ~(y * w + x) of a differing sample, so that zero is the neutral start */
+    uint32_t pad[6];
+};
+struct OhCmpClass {
+    int32_t x0, y0, w, h;            /* the plane's window: origin in the plane, size */
+    int32_t tx, ty;                  /* tiles across and down: at least one each */
+};
+struct OhCmpArgs {
+    const void *a[64][3], *b[64][3]; /* OH_CONV_MAX_PICS pairs x planes: the finished halves */
+    OhCmpDev   *res;                 /* [pair][3][OH_CMP_SLOTS] */
+    OhCmpClass  k[2];
+    int32_t     pitch[3];            /* bytes between rows of each plane */
+    int32_t     np, bd;              /* planes: 1 or 3; bit depth */
+    int32_t     ssim;                /* 1: OH_CMP_SSIM */
+};
+
 /* picture resizing (resize.hip): what one launch set needs, by value in the kernel arguments like OhConvArgs.  Two plane
  * classes (0 luma, 1 chroma), each with its own geometry and tap tables; the tables live in device memory that the engine owns and
  * fills (engine_pics.hip: oh_pics_resize) on the stream in front of the launches. */
@@ -113,6 +138,8 @@ void ohk_convert(const OhConvArgs *a, int format, int sample, int n, hipStream_t
 void ohk_colour(const OhColArgs *a, int format, int sample, int n, hipStream_t st);
 /* n pictures of a.c.src into a.res[0 .. n) */
 void ohk_light(const OhLightArgs *a, int n, hipStream_t st);
+/* n pairs of a.a / a.b into a.res[0 .. 3 n OH_CMP_SLOTS) */
+void ohk_compare(const OhCmpArgs *a, int n, hipStream_t st);
 void ohk_hash(int kind, const OhMd5Job *jobs, const uint32_t *first, const uint32_t *task_map, int n_jobs, int n_tasks, uint32_t *partials,
               uint32_t *out, hipStream_t st);
 void ohk_inter(const OhBatch *B, int n, const OhPicParams *p, uint32_t max_luma, uint32_t max_chroma, hipStream_t st);

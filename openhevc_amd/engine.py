@@ -167,6 +167,83 @@ def source_peak(in_transfer, lls=None, sei=None, ppm=999900, default=1000.0):
     return float(default)
 
 
+CMP_SSIM, CMP_NONE = 1, 0xFFFFFFFF                                                      # OH_CMP_SSIM, OH_CMP_NONE
+CMP_TW, CMP_TH = 256, 32                                                                # OH_CMP_TW, OH_CMP_TH (csrc/kernels.h): the kernel's tile
+
+
+class OhCompareSpec(C.Structure):                             # include/ohevc_hip.h
+    _fields_ = [("win", OhWindow), ("flags", C.c_int32)]
+
+
+class OhPlaneDiff(C.Structure):                               # include/ohevc_hip.h
+    _fields_ = [("samples", C.c_uint64), ("differing", C.c_uint64), ("sad", C.c_uint64), ("sse", C.c_uint64), ("max_abs", C.c_uint32),
+                ("first_x", C.c_uint32), ("first_y", C.c_uint32), ("ssim_windows", C.c_uint64), ("ssim_sum", C.c_int64)]
+
+
+class OhCompare(C.Structure):                                 # include/ohevc_hip.h
+    _fields_ = [("plane", OhPlaneDiff * 3)]
+
+
+def compare_psnr(sse, samples, bit_depth):
+    """oh_compare_psnr (host only): 10 log10(M^2 samples / sse) in dB, inf for sse 0, NaN for samples 0"""
+    return float(lib().oh_compare_psnr(int(sse), int(samples), int(bit_depth)))
+
+
+def compare_ssim_consts(bit_depth):
+    """oh_compare_ssim_consts (host only): (c1, c2) of the SSIM windows at that bit depth"""
+    c1, c2 = C.c_int64(), C.c_int64()
+    rc = lib().oh_compare_ssim_consts(int(bit_depth), C.byref(c1), C.byref(c2))
+    if rc != 0:
+        err = EngineError(f"oh_compare_ssim_consts failed ({rc})")
+        err.code = rc
+        raise err
+    return c1.value, c2.value
+
+
+def compare_ssim_window(bit_depth, s1, s2, ss, s12):
+    """oh_compare_ssim_window (host only): the Q30 value of one 8x8 window from its sums, by the function the kernel evaluates"""
+    return int(lib().oh_compare_ssim_window(int(bit_depth), int(s1), int(s2), int(ss), int(s12)))
+
+
+class PlaneDiff:
+    """one plane of a compared pair (OhPlaneDiff): samples, differing, sad, sse, max_abs, first (None or (x, y) in plane-window
+    coordinates), ssim_windows, ssim_sum (Q30); psnr, mse and ssim derive from them"""
+    __slots__ = ("samples", "differing", "sad", "sse", "max_abs", "first", "ssim_windows", "ssim_sum", "bit_depth")
+
+    def __init__(self, d, bit_depth):
+        self.samples, self.differing, self.sad, self.sse, self.max_abs = int(d.samples), int(d.differing), int(d.sad), int(d.sse), int(d.max_abs)
+        self.first = None if d.first_x == CMP_NONE else (int(d.first_x), int(d.first_y))
+        self.ssim_windows, self.ssim_sum = int(d.ssim_windows), int(d.ssim_sum)
+        self.bit_depth = int(bit_depth)
+
+    def __repr__(self):
+        return (f"PlaneDiff(samples={self.samples}, differing={self.differing}, sad={self.sad}, sse={self.sse}, max_abs={self.max_abs}, "
+                f"first={self.first}, ssim_windows={self.ssim_windows}, ssim_sum={self.ssim_sum})")
+
+    @property
+    def psnr(self):
+        return compare_psnr(self.sse, self.samples, self.bit_depth)
+
+    @property
+    def mse(self):
+        return self.sse / self.samples if self.samples else None
+
+    @property
+    def ssim(self):
+        return self.ssim_sum / self.ssim_windows / (1 << 30) if self.ssim_windows else None
+
+
+class Compare:
+    """a compared pair (OhCompare): plane, three PlaneDiff (those a 4:0:0 picture lacks are all zero)"""
+    __slots__ = ("plane",)
+
+    def __init__(self, o, bit_depth):
+        self.plane = [PlaneDiff(o.plane[c], bit_depth) for c in range(3)]
+
+    def __repr__(self):
+        return f"Compare({self.plane})"
+
+
 class OhResize(C.Structure):                                  # include/ohevc_hip.h
     _fields_ = [("filter", C.c_int32), ("win", OhWindow), ("width", C.c_int32), ("height", C.c_int32)]
 
@@ -275,6 +352,12 @@ def lib():
         L.oh_light_bin_upper.argtypes = [I]
         L.oh_light_bin_upper.restype = C.c_uint32
         L.oh_light_percentile.argtypes = [C.POINTER(OhLightLevel), I, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.oh_pics_compare.argtypes = [V, C.POINTER(C.c_int), C.POINTER(C.c_int), I, C.POINTER(OhCompareSpec), C.POINTER(OhCompare)]
+        L.oh_compare_ssim_consts.argtypes = [I, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.oh_compare_ssim_window.argtypes = [I, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64]
+        L.oh_compare_ssim_window.restype = C.c_int64
+        L.oh_compare_psnr.argtypes = [C.c_uint64, C.c_uint64, I]
+        L.oh_compare_psnr.restype = C.c_double
         L.oh_pics_resize.argtypes = [V, C.POINTER(C.c_int), C.POINTER(C.c_int), I, C.POINTER(OhResize)]
         L.oh_resize_taps.argtypes = [I, I, I, I, C.POINTER(C.c_int32), C.POINTER(C.c_int16), I, C.POINTER(C.c_int)]
         L.oh_resize_max_taps.argtypes = [I, I, I]
@@ -544,6 +627,20 @@ class Engine:
         self._chk(self.L.oh_pics_light_level(self.h, (C.c_int * max(n, 1))(*pids), n, C.byref(cv), C.byref(sp), out), "oh_pics_light_level")
         fs = 10000.0 if int(in_transfer) == 16 else float(src_peak)
         return [LightLevel(o.pixels, o.sum, o.max, o.min, np.frombuffer(o.hist, dtype=np.uint32).copy(), fs) for o in out[:n]]
+
+    def pics_compare(self, a_pids, b_pids, *, window=(0, 0, 0, 0), ssim=True):
+        """finished pictures compared pair by pair on the GPU (oh_pics_compare): a Compare per pair (a_pids[i], b_pids[i]) with a
+        PlaneDiff per plane — differing samples, sad, sse, max_abs, the first differing sample and, with ssim, the SSIM sum over
+        8x8 windows; window = (left, right, top, bottom), luma samples.  Waits for the engine stream."""
+        a_pids, b_pids = list(a_pids), list(b_pids)
+        n = len(a_pids)
+        if len(b_pids) != n:
+            raise ValueError(f"pics_compare: {n} pictures against {len(b_pids)}")
+        sp = OhCompareSpec(OhWindow(*window), CMP_SSIM if ssim else 0)
+        out = (OhCompare * max(n, 1))()
+        self._chk(self.L.oh_pics_compare(self.h, (C.c_int * max(n, 1))(*a_pids), (C.c_int * max(n, 1))(*b_pids), n, C.byref(sp), out),
+                  "oh_pics_compare")
+        return [Compare(out[i], self._pic_params(a_pids[i]).bit_depth) for i in range(n)]
 
     def pics_resize(self, pids, size, *, window=(0, 0, 0, 0), filter="bilinear", out=None):
         """finished pictures -> resized engine pictures (oh_pics_resize): size = (width, height) of the image in luma samples, window =
