@@ -145,6 +145,27 @@ size_t oh_convert_image_bytes(const OhPicParams *p, const OhConvert *cv);
 /* host only: the integers the kernel uses for an RGB conversion of bit_depth-bit pictures, OH_CONV_NCOEFFS of them (n: room in out) */
 int    oh_convert_coeffs(const OhConvert *cv, int bit_depth, int32_t *out, int n);
 
+/* The inverse of oh_pics_convert: n images in caller-owned DEVICE memory, in exactly the layouts oh_pics_convert writes, become n
+ * finished engine pictures without a host round trip (DESIGN.md §3g has the exact definitions, which the tests check bit for bit
+ * against tests/import_model.py).  cv describes the images: format, sample type, matrix, range, the chroma siting the RGB formats are
+ * sub-sampled with (chroma_filter 0: the co-sited pixel, 1: the 1-2-1 filter of chroma_sample_loc_type 0) and win, the window of the
+ * destination pictures that an image fills; image i lies at src + i * image_stride and takes oh_convert_image_bytes(params of the
+ * destinations, cv) bytes.  YUV images must have the pictures' chroma format: NATIVE planar samples are clamped to the bit depth,
+ * NATIVE semi-planar ones shifted down from the MSB, U8 ones shifted up.  RGB images go through the H.273 forward matrix in int32
+ * (oh_import_coeffs), F16 / F32 samples as clamp(v, 0, 1) at 16 bit.  The rest of the coded planes replicates the window's edges, so
+ * the whole picture is defined.  Writes half 0 of every destination (oh_pic_wrap pictures too) and marks it finished; enqueued on the
+ * engine stream, returns without waiting: src must stay valid until the stream has passed the call.  n == 0: OH_OK.  More than
+ * OH_CONV_MAX_PICS images are split into several launches.
+ * OH_E_ARG, nothing written: a null argument, an unknown picture, destinations whose params differ, a destination listed twice, an
+ * empty window or one whose offsets are not multiples of SubWidthC / SubHeightC, image_stride < the image size, image_stride or src not
+ * a multiple of the sample size, (n - 1) * image_stride + image bytes > src_bytes, a src that is not device memory of the engine's
+ * device (or whose allocation ends before the last image).  OH_E_UNSUPPORTED: what oh_pics_convert refuses with that code. */
+enum { OH_IMPORT_NCOEFFS = 13 };  /* oh_import_coeffs: ry gy by  ru gu bu  rv gv bv  y offset, chroma mid, shift S, input depth D */
+int    oh_pics_import(OhEngine *e, const int *pic_ids, int n, const OhConvert *cv, const void *src, size_t image_stride, size_t src_bytes);
+/* host only: the integers the kernel uses for an RGB image of cv->sample (D = 8 for U8, else 16) into bit_depth-bit pictures,
+ * OH_IMPORT_NCOEFFS of them (n: room in out) */
+int    oh_import_coeffs(const OhConvert *cv, int bit_depth, int32_t *out, int n);
+
 /* Colour conversion on top of the RGB formats (DESIGN.md §3d has the exact definition, which the tests check bit for bit against
  * tests/colour_model.py): the non-linear R'G'B' of oh_pics_convert at 16 bit goes through the source's transfer curve to linear light,
  * one gain on a norm (the HLG OOTF and / or the BT.2390 tone curve), the primaries' 3 x 3 matrix with a clip, and the output curve —

@@ -1,7 +1,7 @@
 /*
  * engine_impl.h — what the engine's translation units share: the engine and picture structures, the error macros and the few
  * helpers more than one of them uses.  engine.hip: engine and picture lifecycle, staging buffers, passes, profiling;
- * engine_handover.hip: work-list hand-over and the arena pool; engine_pics.hip: plane transfers, hashes, conversion, measurement,
+ * engine_handover.hip: work-list hand-over and the arena pool; engine_pics.hip: plane transfers, hashes, conversion, import, measurement,
  * comparison and resizing of finished pictures; engine_shvc.hip: SHVC up-sampling.
  * Internal: the C ABI is include/ohevc_hip.h.
  */

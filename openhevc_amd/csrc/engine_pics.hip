@@ -1,7 +1,7 @@
 /*
  * engine_pics.hip — what the engine does with finished pictures beside the reconstruction path (host side; the kernels are md5.hip,
- * hash.hip, convert.hip, colour.hip, light.hip, compare.hip and resize.hip): plane upload and download, the two-phase window fetch,
- * picture hashes, conversion to YUV / RGB images, with the colour tables of the HDR forms, light-level statistics, comparison of two
+ * hash.hip, convert.hip, import.hip, colour.hip, light.hip, compare.hip and resize.hip): plane upload and download, the two-phase window fetch,
+ * picture hashes, conversion to YUV / RGB images and back, with the colour tables of the HDR forms, light-level statistics, comparison of two
  * pictures, and resizing into engine pictures.
  */
 #include <cmath>
@@ -518,6 +518,127 @@ static int pics_convert(OhEngine *e, const char *who, const int *pic_ids, int n,
         a.dst = (char *)dst + (size_t)i0 * image_stride;
         if (col) ohk_colour(&ca, cv->format, cv->sample, m, e->stream);
         else     ohk_convert(&a, cv->format, cv->sample, m, e->stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    return OH_OK;
+}
+
+/* ---------------- import of standard images (import.hip) ---------------- */
+/* the integers of an RGB import: Y = clamp((ry R + gy G + by B + (yoff << S) + 2^(S-1)) >> S, 0, 2^B - 1), Cb with the u row and mid,
+ * Cr with the v row; each row sums to the exact scale (greys give mid, white gives peak luma); S the largest shift that keeps
+ * (|c0| + |c1| + |c2|) (2^D - 1) + (offset << S) + 2^(S-1) of every row inside int32: every term and every partial sum, in whatever
+ * order they are added */
+extern "C" int oh_import_coeffs(const OhConvert *cv, int bit_depth, int32_t *out, int n)
+{
+    if (!cv || !out || n < OH_IMPORT_NCOEFFS || (bit_depth != 8 && bit_depth != 9 && bit_depth != 10 && bit_depth != 12))
+        return OH_E_ARG;
+    if (cv->format < OH_CONV_RGB_PLANAR || cv->format > OH_CONV_RGBA || cv->sample < OH_CONV_U8 || cv->sample > OH_CONV_F32)
+        return OH_E_UNSUPPORTED;
+    double kr, kb;
+    switch (cv->matrix) {
+    case 1:  kr = 0.2126; kb = 0.0722; break;
+    case 5:
+    case 6:  kr = 0.299;  kb = 0.114;  break;
+    case 9:  kr = 0.2627; kb = 0.0593; break;
+    default: return OH_E_UNSUPPORTED;
+    }
+    if (cv->full_range != 0 && cv->full_range != 1)
+        return OH_E_ARG;
+    const int B = bit_depth, D = cv->sample == OH_CONV_U8 ? 8 : 16;
+    const double full = (double)((1 << B) - 1), unit = (double)(1 << (B - 8)), M = (double)((1 << D) - 1);
+    const double ys = cv->full_range ? full : 219.0 * unit, cs = cv->full_range ? full : 224.0 * unit;
+    const int64_t yoff = cv->full_range ? 0 : 16 << (B - 8), mid = 1 << (B - 1), Mi = ((int64_t)1 << D) - 1;
+    for (int S = 30; S >= 1; S--) {
+        int64_t c[9];
+        c[0] = llround(ldexp(ys * kr / M, S));
+        c[2] = llround(ldexp(ys * kb / M, S));
+        c[1] = llround(ldexp(ys / M, S)) - c[0] - c[2];
+        c[5] = c[6] = llround(ldexp(cs / (2.0 * M), S));
+        c[3] = llround(ldexp(-cs * kr / (2.0 * (1.0 - kb) * M), S));
+        c[4] = -c[3] - c[5];
+        c[8] = llround(ldexp(-cs * kb / (2.0 * (1.0 - kr) * M), S));
+        c[7] = -c[6] - c[8];
+        const int64_t r = (int64_t)1 << (S - 1);
+        int64_t worst = 0;
+        for (int row = 0; row < 3; row++)
+            worst = std::max<int64_t>(worst, (std::llabs(c[3 * row]) + std::llabs(c[3 * row + 1]) + std::llabs(c[3 * row + 2])) * Mi +
+                                                 ((row ? mid : yoff) << S) + r);
+        if (worst > INT32_MAX)
+            continue;
+        for (int i = 0; i < 9; i++) out[i] = (int32_t)c[i];
+        out[9] = (int32_t)yoff; out[10] = (int32_t)mid; out[11] = S; out[12] = D;
+        return OH_OK;
+    }
+    return OH_E_UNSUPPORTED;
+}
+
+extern "C" int oh_pics_import(OhEngine *e, const int *pic_ids, int n, const OhConvert *cv, const void *src, size_t image_stride, size_t src_bytes)
+{
+    const char *who = "oh_pics_import";
+    if (!e || n < 0 || !cv || (n && !pic_ids))
+        return OH_E_ARG;
+    if (!n)
+        return OH_OK;
+    { const int rc = check_pics(e, pic_ids, n, who); if (rc) return rc; }
+    const Pic *p0 = get_pic(e, pic_ids[0]);
+    const int other = first_other_params(e, pic_ids, n);
+    if (other < n)
+        FAIL(e, OH_E_ARG, "%s: picture %d has other params than picture %d", who, pic_ids[other], pic_ids[0]);
+    {
+        std::vector<int> d(pic_ids, pic_ids + n);
+        std::sort(d.begin(), d.end());
+        if (std::adjacent_find(d.begin(), d.end()) != d.end())
+            FAIL(e, OH_E_ARG, "%s: a destination is listed twice", who);
+    }
+    size_t ib = 0;
+    std::string why;
+    { const int rc = conv_check(&p0->p, cv, &ib, &why); if (rc) FAIL(e, rc, "%s: %s", who, why.c_str()); }
+    const size_t sb = (size_t)conv_sample_bytes(cv, p0->p.bit_depth);
+    if (image_stride < ib || image_stride % sb || (uintptr_t)src % sb)
+        FAIL(e, OH_E_ARG, "%s: image_stride %zu (an image takes %zu bytes) or src not a multiple of the %zu-byte sample", who, image_stride, ib, sb);
+    if (!src || ib > src_bytes || (size_t)(n - 1) > (src_bytes - ib) / image_stride)
+        FAIL(e, OH_E_ARG, "%s: %d images of %zu bytes, %zu apart, do not fit %zu bytes", who, n, ib, image_stride, src_bytes);
+    const size_t total = (size_t)(n - 1) * image_stride + ib;
+    HIPCHK(e, hipSetDevice(e->device));
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, src) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->device) {
+        (void)hipGetLastError();
+        FAIL(e, OH_E_ARG, "%s: src is not device memory of device %d", who, e->device);
+    }
+    void *base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(src)) == hipSuccess) {
+        if ((const char *)src + total > (const char *)base + size)
+            FAIL(e, OH_E_ARG, "%s: %zu bytes at src run past the end of its allocation", who, total);
+    } else {
+        (void)hipGetLastError();
+    }
+    OhImpArgs a;
+    memset(&a, 0, sizeof(a));
+    const OhPicParams &p = p0->p;
+    const int bpp = sample_bytes(p.bit_depth), np = p.chroma_format_idc ? 3 : 1;
+    for (int c = 0; c < np; c++) a.pitch[c] = p0->stride[c] * bpp;
+    a.pw[0] = p0->w[0]; a.ph[0] = p0->h[0];
+    a.pw[1] = np > 1 ? p0->w[1] : 0; a.ph[1] = np > 1 ? p0->h[1] : 0;
+    a.left = cv->win.left; a.top = cv->win.top;
+    a.W = p.width - cv->win.left - cv->win.right; a.H = p.height - cv->win.top - cv->win.bottom;
+    a.cf = p.chroma_format_idc; a.bd = p.bit_depth; a.filter = cv->chroma_filter;
+    a.nc = cv->format == OH_CONV_RGBA ? 4 : 3;
+    a.image_stride = image_stride;
+    if (cv->format >= OH_CONV_RGB_PLANAR) {
+        const int rc = oh_import_coeffs(cv, p.bit_depth, a.k, OH_IMPORT_NCOEFFS);
+        if (rc) FAIL(e, rc, "%s: no coefficients for this conversion", who);
+    }
+    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
+        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+        for (int i = 0; i < m; i++) {
+            Pic *q = get_pic(e, pic_ids[i0 + i]);
+            for (int c = 0; c < np; c++) a.dst[i][c] = q->a[c];
+            q->final_b = false;                                  /* the image is a finished picture in half 0 */
+            q->done_seq = 0;
+        }
+        a.src = (const char *)src + (size_t)i0 * image_stride;
+        ohk_import(&a, cv->format, cv->sample, m, e->stream);
         HIPCHK(e, hipGetLastError());
     }
     return OH_OK;

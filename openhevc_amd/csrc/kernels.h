@@ -39,6 +39,21 @@ struct OhConvArgs {
     int32_t     k[9];            /* oh_convert_coeffs: cy, crv, cgu, cgv, cbu, yoff, mid, S, D */
 };
 
+/* picture import (import.hip): the inverse of OhConvArgs.  dst: half 0 of the destination pictures, src: the image of the
+ * launch's first picture in caller-owned device memory; every picture of a launch has the same geometry. */
+struct OhImpArgs {
+    void       *dst[64][3];      /* OH_CONV_MAX_PICS pictures x planes */
+    const void *src;             /* image of the launch's first picture */
+    uint64_t    image_stride;    /* bytes from one image to the next */
+    int32_t     pitch[3];        /* bytes between rows of each plane */
+    int32_t     pw[2], ph[2];    /* coded plane size: luma, chroma */
+    int32_t     left, top, W, H; /* window, luma samples */
+    int32_t     cf, bd;          /* chroma_format_idc, bit depth */
+    int32_t     filter;          /* RGB images, 4:2:0 / 4:2:2: 0 point, 1 linear */
+    int32_t     nc;              /* interleaved RGB: 3 or 4 channels */
+    int32_t     k[13];           /* oh_import_coeffs: ry gy by ru gu bu rv gv bv yoff mid S D */
+};
+
 /* colour conversion (colour.hip): the geometry and the matrix of an RGB conversion (k: the coefficients for 16 bit), the
  * integers of oh_colour_tables' misc, and the three tables in device memory that the engine owns and fills on the stream in front of the
  * launches: A at int32 0, G at OH_COLT_G, B at OH_COLT_B, OH_COLT_N in all (each table padded to whole 16-byte granules). */
@@ -134,6 +149,8 @@ void ohk_resize(const OhResizeArgs *a, int n, int pad, hipStream_t st);
 void ohk_md5(const OhMd5Job *jobs, int n, void *digests, hipStream_t st);
 /* format / sample: OH_CONV_* (checked by the caller); n pictures of a.src */
 void ohk_convert(const OhConvArgs *a, int format, int sample, int n, hipStream_t st);
+/* format / sample: OH_CONV_* of the images (checked by the caller); n pictures of a.dst */
+void ohk_import(const OhImpArgs *a, int format, int sample, int n, hipStream_t st);
 /* format: an RGB format, sample: U8 .. F32 (checked by the caller); n pictures of a.c.src */
 void ohk_colour(const OhColArgs *a, int format, int sample, int n, hipStream_t st);
 /* n pictures of a.c.src into a.res[0 .. n) */

@@ -31,6 +31,7 @@ OH_E_HIP, OH_E_ARG, OH_E_NOMEM, OH_E_UNSUPPORTED = -1, -2, -3, -4
 CONV_FORMATS = {"planar": 0, "semiplanar": 1, "rgb_planar": 2, "rgb": 3, "rgba": 4}      # OH_CONV_PLANAR .. OH_CONV_RGBA
 CONV_NATIVE, CONV_U8, CONV_U16, CONV_F16, CONV_F32 = range(5)                           # OH_CONV_NATIVE .. OH_CONV_F32
 CONV_MAX_PICS, CONV_NCOEFFS = 64, 9
+IMPORT_NCOEFFS = 13                                                                     # OH_IMPORT_NCOEFFS
 
 
 class OhConvert(C.Structure):                                 # include/ohevc_hip.h
@@ -297,6 +298,17 @@ def convert_coeffs(cv, bit_depth):
     return tuple(out)
 
 
+def import_coeffs(cv, bit_depth):
+    """oh_import_coeffs (host only): (ry, gy, by, ru, gu, bu, rv, gv, bv, yoff, mid, S, D), the integers of an RGB import"""
+    out = (C.c_int32 * IMPORT_NCOEFFS)()
+    rc = lib().oh_import_coeffs(C.byref(cv), bit_depth, out, IMPORT_NCOEFFS)
+    if rc != 0:
+        err = EngineError(f"oh_import_coeffs failed ({rc})")
+        err.code = rc
+        raise err
+    return tuple(out)
+
+
 def lib_path():
     return os.path.join(F.PKG_DIR, "libohevc_hip.so")
 
@@ -345,6 +357,8 @@ def lib():
         L.oh_convert_image_bytes.argtypes = [C.POINTER(F.OhPicParams), C.POINTER(OhConvert)]
         L.oh_convert_image_bytes.restype = C.c_size_t
         L.oh_convert_coeffs.argtypes = [C.POINTER(OhConvert), I, C.POINTER(C.c_int32), I]
+        L.oh_pics_import.argtypes = [V, C.POINTER(C.c_int), I, C.POINTER(OhConvert), V, C.c_size_t, C.c_size_t]
+        L.oh_import_coeffs.argtypes = [C.POINTER(OhConvert), I, C.POINTER(C.c_int32), I]
         L.oh_pics_convert_colour.argtypes = [V, C.POINTER(C.c_int), I, C.POINTER(OhConvert), C.POINTER(OhColour), V, C.c_size_t, C.c_size_t]
         L.oh_colour_tables.argtypes = [C.POINTER(OhColour)] + [C.POINTER(C.c_int32)] * 4
         L.oh_pics_light_level.argtypes = [V, C.POINTER(C.c_int), I, C.POINTER(OhConvert), C.POINTER(OhLightSpec), C.POINTER(OhLightLevel)]
@@ -610,6 +624,96 @@ class Engine:
             # an event on the destroyed stream when the tensor is freed.
             cur.wait_stream(es)
         return out
+
+    def pics_import(self, images, fmt, *, out=None, bit_depth=None, chroma_format_idc=None, window=(0, 0, 0, 0), matrix=1, full_range=False,
+                    chroma="linear"):
+        """images on the engine's device -> finished engine pictures (oh_pics_import, the inverse of pics_convert): images is one
+        contiguous torch tensor in the shape and dtype pics_convert returns for fmt — "planar" / "semiplanar" (N, rows, W),
+        "rgb_planar" (N, 3, H, W), "rgb" / "rgba" (N, H, W, 3 | 4); uint8, uint16, float16 or float32 (YUV: uint8, or uint16 for the
+        stored samples of pictures above 8 bit).  out: the pictures to fill, window = (left, right, top, bottom) of them in luma
+        samples that the image fills (the image must have the window's size); the rest of their coded planes replicates the image's
+        edges.  Without out, pictures of bit_depth / chroma_format_idc are allocated with the image size rounded up to the minimum
+        coding block and the image at their top left.  matrix, full_range and chroma ("linear": the 1-2-1 filter of
+        chroma_sample_loc_type 0, "nearest": the co-sited pixel) say how RGB becomes YCbCr.  Returns (picture ids, window), the window
+        to pass to pics_convert / pic_download_window / pics_compare for the image.  Ordered with torch both ways: the engine stream
+        waits for torch's current stream before it reads, torch's current stream waits for the engine stream afterwards, so the tensor
+        may be freed or overwritten at once.  Does not wait on the host."""
+        import torch
+        if not _torch_first:
+            raise EngineError("Engine.pics_import: import torch before the first Engine is created (the engine must share torch's HIP "
+                              "runtime to read its tensors)")
+        fmt_i = conv_format(fmt)
+        yuv = fmt_i <= CONV_FORMATS["semiplanar"]
+        dev = torch.device("cuda", self.device)
+        if not isinstance(images, torch.Tensor) or images.device != dev or not images.is_contiguous():
+            raise ValueError(f"images: want a contiguous torch tensor on {dev}")
+        if images.dim() != (3 if yuv else 4) or images.shape[0] < 1:
+            raise ValueError(f"images: shape {tuple(images.shape)} is not what pics_convert gives for format {fmt!r}")
+        n = int(images.shape[0])
+        fresh = out is None
+        if fresh:
+            if bit_depth is None or chroma_format_idc is None:
+                raise ValueError("pics_import without out needs bit_depth and chroma_format_idc")
+            cf = int(chroma_format_idc)
+            if yuv:
+                W = int(images.shape[2])
+                rows = int(images.shape[1])
+                # planar / semi-planar rows of W samples: H luma rows and 2 (W >> hs) (H >> vs) chroma samples
+                num, den = {0: (1, 1), 1: (2, 3), 2: (1, 2), 3: (1, 3)}.get(cf, (0, 1))
+                H = rows * num // den
+            elif fmt_i == CONV_FORMATS["rgb_planar"]:
+                H, W = int(images.shape[2]), int(images.shape[3])
+            else:
+                H, W = int(images.shape[1]), int(images.shape[2])
+            if W < 1 or H < 1:
+                raise ValueError(f"images: shape {tuple(images.shape)} holds no picture of chroma format {cf}")
+            dp = F.pic_params(8, 8, bit_depth=int(bit_depth), chroma_format_idc=cf)
+            mcb = 1 << dp.log2_min_cb_size
+            dp.width, dp.height = -(-W // mcb) * mcb, -(-H // mcb) * mcb
+            window = (0, dp.width - W, 0, dp.height - H)
+            pids = [self.pic_alloc(dp) for _ in range(n)]
+        else:
+            pids = list(out)
+            if len(pids) != n:
+                raise ValueError(f"out: {len(pids)} pictures for {n} images")
+            window = tuple(int(v) for v in window)
+        try:
+            params = self._pic_params(pids[0])
+            # YUV + uint16: the stored samples of a picture above 8 bit; an 8-bit picture has no uint16 YUV form (OH_E_UNSUPPORTED below)
+            yuv16 = CONV_NATIVE if params.bit_depth > 8 else CONV_U16
+            samples = {torch.uint8: CONV_U8, torch.uint16: yuv16 if yuv else CONV_U16, torch.float16: CONV_F16, torch.float32: CONV_F32}
+            if images.dtype not in samples:
+                raise ValueError(f"images: dtype {images.dtype}: one of uint8, uint16, float16, float32")
+            sample = samples[images.dtype]
+            if yuv and sample == CONV_U8 and params.bit_depth == 8:
+                sample = CONV_NATIVE
+            cv = make_convert(fmt_i, sample, window, matrix, full_range, chroma)
+            esz = images.element_size()
+            ib = convert_image_bytes(params, cv)
+            ids = (C.c_int * n)(*pids)
+            if ib == 0:                                       # not a valid combination: the C call says why (and with which code)
+                self._chk(self.L.oh_pics_import(self.h, ids, n, C.byref(cv), None, 0, 0), "oh_pics_import")
+                raise EngineError("oh_pics_import: invalid import")
+            if images[0].numel() * esz != ib:
+                raise ValueError(f"images: {tuple(images.shape[1:])} {images.dtype} per image is {images[0].numel() * esz} bytes, the "
+                                 f"window {window} of the pictures takes {ib}")
+            cur = torch.cuda.current_stream(dev)
+            same = (self.stream() or 0) == cur.cuda_stream    # an engine created on torch's current stream: nothing to order
+            if not same:
+                if self._torch_stream is None:
+                    self._torch_stream = torch.cuda.ExternalStream(self.stream() or 0, device=dev)
+                es = self._torch_stream
+                es.wait_stream(cur)                           # the kernels that produce the images are queued on torch's stream
+            self._chk(self.L.oh_pics_import(self.h, ids, n, C.byref(cv), C.c_void_p(images.data_ptr()), ib, images.numel() * esz),
+                      "oh_pics_import")
+            if not same:
+                cur.wait_stream(es)                           # whatever torch does with the tensor later is ordered behind the read
+        except Exception:
+            if fresh:
+                for pid in pids:
+                    self.pic_free(pid)
+            raise
+        return pids, window
 
     def pics_light_level(self, pids, in_transfer, *, in_primaries=9, norm="maxrgb", src_peak=1000.0, window=(0, 0, 0, 0), matrix=9,
                          full_range=False, chroma="linear"):
