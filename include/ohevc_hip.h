@@ -357,8 +357,11 @@ int oh_upsample_blocks_defined(const OhUpsample *u, int w_bl, int h_bl, int w_el
  * execute enqueues passes 1-5 on the engine stream and may be called repeatedly on the same
  * device frame (the coefficient pool is never modified). */
 int oh_frame_upload(OhEngine *e, const OhFrame *f, OhDevFrame **out);
-/* n work lists at once: the host part and the copy per list, ONE set of preparation launches for all of them (what a batch of
- * independent pictures that will run as one oh_frames_execute should use).  All or nothing: on error no list stays uploaded. */
+/* n work lists at once (what a batch of independent pictures that will run as one oh_frames_execute should use): every chunk of up to
+ * 32 lists shares ONE device arena, is copied with a few large requests and prepared by ONE set of launches.  All or nothing: on
+ * error no list stays uploaded.  The lists are still executed, released and freed one by one and in any order, but the device
+ * memory of the lists of one chunk is returned TOGETHER, when the last of them is released or freed: a caller that keeps one list
+ * of a call for long keeps the memory of the whole chunk. */
 int oh_frames_upload(OhEngine *e, const OhFrame *const *fs, int n, OhDevFrame **out);
 int oh_frame_execute(OhEngine *e, OhDevFrame *df);
 /* n mutually independent pictures (none is a reference of another one; same OhPicParams): every pass
@@ -374,7 +377,7 @@ int oh_frame_release(OhEngine *e, OhDevFrame *df);
  * bytes: size of each destination, at most oh_bs_size() is copied */
 int oh_frame_download_bs(OhEngine *e, OhDevFrame *df, uint8_t *vbs, uint8_t *hbs, size_t bytes);
 int oh_frame_submit(OhEngine *e, const OhFrame *f);     /* upload + execute + release in stream order: nothing of the list stays behind */
-/* what the engine holds for work lists: out[0] device arenas alive (pooled or holding a list), [1] their bytes, [2] of them free in the pool,
+/* what the engine holds for work lists: out[0] device arenas alive (pooled or holding the lists of one upload call), [1] their bytes, [2] of them free in the pool,
  * [3] pinned staging buffers, [4] their bytes, [5] work lists waiting for a deferred free.  A decoder that submits and forgets one list
  * per picture sees all of them level off after a few pictures, however long the stream. */
 int oh_engine_memory(OhEngine *e, uint64_t out[6]);

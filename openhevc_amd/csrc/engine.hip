@@ -67,8 +67,11 @@ static int engine_create(OhEngine **out, int device, hipStream_t ext, bool use_e
     } else if (ok) {
         ok = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) == hipSuccess;
     }
+    /* default priority.  With the highest stream priority (hipStreamCreateWithPriority) the 4K Main 10 decode bench, four hardware
+     * queues, four alternating pairs of runs, gave 82.6-82.8 Gpixels/s against 79.3-87.9 (median 87.3) without, and arena_take's share
+     * of the host time rose from 0.0001 to 0.03 ms per picture (profiles/r10_chunk_handover.txt); at 12 queues it made no difference */
     if (ok)
-        ok = hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking) == hipSuccess;     /* (highest priority for this stream: measured, no difference) */
+        ok = hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking) == hipSuccess;
     if (!ok || ohk_init() != 0) {
         fprintf(stderr, "ohevc_hip: device %d initialisation failed\n", device);
         delete e;
@@ -358,15 +361,25 @@ OhEngine::Stage *stage_acquire(OhEngine *e, size_t bytes)
     }
     if (sg)
         return sg;
-    /* every buffer is busy: beyond OH_MAX_STAGES wait for one whose copy is furthest along instead of pinning more host memory
-     * (this is what throttles a host that hands pictures over faster than PCIe and the passes take them) */
-    if (e->stages.size() >= OH_MAX_STAGES) {
+    /* every buffer that fits is busy: beyond OH_STAGE_POOL_BYTES wait for the one whose copy is furthest along instead of pinning more
+     * host memory (this is what throttles a host that hands pictures over faster than PCIe and the passes take them) */
+    size_t alive = 0;
+    for (auto &c : e->stages) alive += c.bytes;
+    const size_t want = align_up(bytes, (size_t)4 << 20);
+    if (alive + want > OH_STAGE_POOL_BYTES) {
         for (auto &c : e->stages)
             if (c.busy && c.bytes >= bytes) {
                 if (hipEventSynchronize(c.done) != hipSuccess)
                     return nullptr;
                 c.busy = false;
                 return &c;
+            }
+        /* the pool holds smaller buffers only (lists that came alone before a chunk did): idle ones make room */
+        for (size_t i = e->stages.size(); i-- > 0 && alive + want > OH_STAGE_POOL_BYTES; )
+            if (!e->stages[i].busy) {
+                alive -= e->stages[i].bytes;
+                (void)hipEventDestroy(e->stages[i].done); (void)hipHostFree(e->stages[i].p);
+                e->stages.erase(e->stages.begin() + (long)i);
             }
     }
     OhEngine::Stage c;
@@ -398,7 +411,7 @@ static int read_summary(OhEngine *e, OhDevFrame *df, int index)
     if (df->summary_read)
         return df->prep_err ? OH_E_ARG : OH_OK;
     { HostTimer t(e, OH_HT_EXECUTE_WAIT_PREP);
-    HIPCHK(e, hipEventSynchronize(df->ready));
+    HIPCHK(e, hipEventSynchronize(df->chunk->ready));
     }
     const DevSummary *s = (const DevSummary *)df->sum_host;
     df->summary_read = true;
@@ -548,9 +561,9 @@ extern "C" int oh_frames_execute(OhEngine *e, OhDevFrame *const *dfs, int n)
         std::vector<Patch> patches;
         for (int i = 0; i < n; i++) {
             OhDevFrame *df = dfs[i];
-            if (!df->waited) {                              /* the list's copy runs on the copy stream */
-                HIPCHK(e, hipStreamWaitEvent(st, df->ready, 0));
-                df->waited = true;
+            if (!df->chunk->waited) {                       /* the chunk's copies run on the copy stream: one wait covers its lists */
+                HIPCHK(e, hipStreamWaitEvent(st, df->chunk->ready, 0));
+                df->chunk->waited = true;
             }
             Pic *c = get_pic(e, df->cur_pic);
             if (!c || c->gen != df->cur_gen)
@@ -678,8 +691,8 @@ extern "C" int oh_frame_free(OhEngine *e, OhDevFrame *df)
         return OH_E_ARG;
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (df->ready)
-        HIPCHK(e, hipEventSynchronize(df->ready));          /* never executed: its copy may still be running */
+    if (df->chunk && df->chunk->ready)
+        HIPCHK(e, hipEventSynchronize(df->chunk->ready));   /* never executed: its copy may still be running */
     free_dev_frame(e, df);
     return OH_OK;
 }
@@ -694,8 +707,10 @@ extern "C" int oh_frame_release(OhEngine *e, OhDevFrame *df)
         FAIL(e, OH_E_ARG, "oh_frame_release: work list of another engine");
     HostTimer t_all(e, OH_HT_RELEASE);
     HIPCHK(e, hipSetDevice(e->device));
-    if (!df->waited && df->ready)
-        HIPCHK(e, hipStreamWaitEvent(e->stream, df->ready, 0));      /* never executed: the release still has to stay behind its copy */
+    if (df->chunk && !df->chunk->waited && df->chunk->ready) {
+        HIPCHK(e, hipStreamWaitEvent(e->stream, df->chunk->ready, 0));      /* never executed: the release still has to stay behind its copy */
+        df->chunk->waited = true;
+    }
     free_dev_frame(e, df, true);
     return OH_OK;
 }
@@ -721,8 +736,8 @@ extern "C" int oh_frame_download_bs(OhEngine *e, OhDevFrame *df, uint8_t *vbs, u
     if (df->owner != e || !df->p.deblock_enabled)
         FAIL(e, OH_E_ARG, "oh_frame_download_bs: work list of another engine / without deblocking");
     HIPCHK(e, hipSetDevice(e->device));
-    if (df->ready)
-        HIPCHK(e, hipEventSynchronize(df->ready));          /* the list arrives on the copy stream */
+    if (df->chunk && df->chunk->ready)
+        HIPCHK(e, hipEventSynchronize(df->chunk->ready));   /* the list arrives on the copy stream */
     DevFrame hd;
     HIPCHK(e, hipMemcpyAsync(&hd, df->d, sizeof(hd), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));

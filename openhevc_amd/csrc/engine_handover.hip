@@ -1,8 +1,11 @@
 /*
- * engine_handover.hip — hand-over of work lists to the engine: host-side checks and counts, the device arena (laid out by
- * handover_layout.h, taken from the engine's pool), the header, the staging copy or the pull out of pinned memory, and the
- * preparation kernels behind it on the copy stream.  oh_frames_upload / oh_frame_upload of the C ABI (include/ohevc_hip.h).
+ * engine_handover.hip — hand-over of work lists to the engine, a chunk (the lists of one call, at most OH_MAX_BATCH) at a time:
+ * host-side checks and counts, ONE device arena for the chunk (laid out by handover_layout.h, taken from the engine's pool), the
+ * headers, the staging copies (one per group of OH_STAGE_GROUP lists) or the pull out of pinned memory, and the preparation kernels
+ * behind them on the copy stream.  oh_frames_upload / oh_frame_upload of the C ABI (include/ohevc_hip.h).
  */
+#include <memory>
+
 #include "engine_impl.h"
 
 hipEvent_t sync_event_get(OhEngine *e)
@@ -33,8 +36,8 @@ static void arena_delete(OhEngine *e, void *p, size_t bytes)
     if (e) { e->arenas_alive--; e->arena_bytes_alive -= bytes; }
 }
 
-/* an arena of at least `total` bytes for df: a pooled one that fits (within 2x), else a new one rounded up to 1 MiB */
-static int arena_take(OhEngine *e, size_t total, OhDevFrame *df)
+/* an arena of at least `total` bytes for a chunk: a pooled one that fits (within 2x), else a new one rounded up to 1 MiB */
+static int arena_take(OhEngine *e, size_t total, OhChunk *ck)
 {
     /* oldest first (the pool is in release order): an arena released long ago has no pass left that reads it, so the copy
      * need not wait for the engine stream; the most recently released one would stall the copy stream behind the passes
@@ -46,38 +49,37 @@ static int arena_take(OhEngine *e, size_t total, OhDevFrame *df)
     if (best >= 0 && e->arenas[best].free_ev && hipEventQuery(e->arenas[best].free_ev) != hipSuccess && e->arenas.size() < 512)
         best = -1;                                      /* even the oldest fit is still in flight: a new arena beats a stall */
     if (best >= 0) {
-        df->arena = e->arenas[best].p; df->arena_bytes = e->arenas[best].bytes;
-        if (e->arenas[best].free_ev) {                  /* released while passes were in flight: the copy must stay behind them */
+        ck->arena = e->arenas[best].p; ck->arena_bytes = e->arenas[best].bytes;
+        if (e->arenas[best].free_ev) {                  /* released while passes were in flight: the copies must stay behind them */
             (void)hipStreamWaitEvent(e->copy_stream, e->arenas[best].free_ev, 0);
             sync_event_put(e, e->arenas[best].free_ev);
         }
         e->arenas.erase(e->arenas.begin() + best);
         return OH_OK;
     }
-    df->arena_bytes = align_up(total, (size_t)1 << 20);
-    if ((df->arena = arena_new(e, df->arena_bytes)) == nullptr) {
+    ck->arena_bytes = align_up(total, (size_t)1 << 20);
+    if ((ck->arena = arena_new(e, ck->arena_bytes)) == nullptr) {
         (void)hipStreamSynchronize(e->stream);
         for (auto &a : e->arenas) { sync_event_put(e, a.free_ev); arena_delete(e, a.p, a.bytes); }      /* the pool may be what is in the way */
         e->arenas.clear();
-        if ((df->arena = arena_new(e, df->arena_bytes)) == nullptr)
-            FAIL(e, OH_E_NOMEM, "hipMalloc(%zu) for the work list failed", total);
+        if ((ck->arena = arena_new(e, ck->arena_bytes)) == nullptr)
+            FAIL(e, OH_E_NOMEM, "hipMalloc(%zu) for the work lists failed", total);
     }
     return OH_OK;
 }
 
-/* arenas go back to the engine's pool.  in_flight: kernels enqueued on the engine stream may still read the arena — an event
- * recorded there now tells the copy stream when the next work list may overwrite it. */
-void free_dev_frame(OhEngine *e, OhDevFrame *df, bool in_flight)
+/* the last list of a chunk is gone: event and summary block go back to their pools, the arena to the engine's.  in_flight: kernels
+ * enqueued on the engine stream may still read the arena — an event recorded there now (the stream is in order: it covers the lists
+ * released earlier as well) tells the copy stream when the next chunk may overwrite it. */
+static void chunk_free(OhEngine *e, OhChunk *ck, bool in_flight)
 {
-    if (!df)
-        return;
-    if (e && df->ready)
-        sync_event_put(e, df->ready);
-    if (df->sum_host) {
-        if (e && e->sum_pool.size() < 4096) e->sum_pool.push_back(df->sum_host);
-        else (void)hipHostFree(df->sum_host);
+    if (e && ck->ready)
+        sync_event_put(e, ck->ready);
+    if (ck->sum_host) {
+        if (e && e->sum_pool.size() < 4096) e->sum_pool.push_back(ck->sum_host);
+        else (void)hipHostFree(ck->sum_host);
     }
-    if (df->arena) {
+    if (ck->arena) {
         if (e && e->arenas.size() < 1024) {
             hipEvent_t fe = nullptr;
             if (in_flight && (fe = sync_event_get(e)) != nullptr && hipEventRecord(fe, e->stream) != hipSuccess) {
@@ -86,13 +88,28 @@ void free_dev_frame(OhEngine *e, OhDevFrame *df, bool in_flight)
             }
             if (in_flight && !fe)
                 (void)hipStreamSynchronize(e->stream);           /* no event to be had: wait instead */
-            e->arenas.push_back({ df->arena, df->arena_bytes, fe });
+            e->arenas.push_back({ ck->arena, ck->arena_bytes, fe });
         } else {
-            if (in_flight) (void)hipStreamSynchronize(e->stream);
-            arena_delete(e, df->arena, df->arena_bytes);
+            if (in_flight && e) (void)hipStreamSynchronize(e->stream);
+            arena_delete(e, ck->arena, ck->arena_bytes);
         }
     }
+    delete ck;
+}
+
+/* a list lets go of its chunk.  in_flight: passes of THIS list may still be running (oh_frame_release); remembered until the last
+ * list of the chunk goes, whichever way that one goes */
+void free_dev_frame(OhEngine *e, OhDevFrame *df, bool in_flight)
+{
+    if (!df)
+        return;
+    OhChunk *ck = df->chunk;
     delete df;
+    if (!ck)
+        return;
+    ck->in_flight = ck->in_flight || in_flight;
+    if (--ck->refs <= 0)
+        chunk_free(e, ck, ck->in_flight);
 }
 
 /* ---------------- work lists ---------------- */
@@ -110,7 +127,7 @@ static bool same_geometry(const OhPicParams &a, const OhPicParams &b)
  * `ready`.  Nothing of it touches samples, so it overlaps the passes of the pictures before.  A malformed list is
  * reported by the first oh_frame(s)_execute that includes it (OH_E_ARG, before any of its passes is launched).
  * ------------------------------------------------------------------------------------------------------------------- */
-static int check_host_side(OhEngine *e, const OhFrame *f, const Pic *cur, HostSide *h)
+static int check_host_side(OhEngine *e, const OhFrame *f, const Pic *cur, HostSide *h, std::vector<uint32_t> &pu_off)
 {
     const OhPicParams &p = f->p;
     h->ref_ok = 0; h->ref_used = 0; h->n_cross = 0; h->any_dense = false;
@@ -126,7 +143,6 @@ static int check_host_side(OhEngine *e, const OhFrame *f, const Pic *cur, HostSi
     const int hs = oh_hshift(&p, 1), vs = oh_vshift(&p, 1), two = p.chroma_format_idc ? 2 : 0;
     if ((uint64_t)f->n_pu * 2048 >= (1ull << 31))
         FAIL(e, OH_E_ARG, "PU list too long");
-    static thread_local std::vector<uint32_t> pu_off;
     pu_off.resize(2 * ((size_t)f->n_pu + 1));
     uint32_t *ol = pu_off.data(), *oc = ol + f->n_pu + 1;       /* running sums: where every PU's blocks start in the two lists */
     h->pu_off = ol;
@@ -188,16 +204,18 @@ static int check_host_side(OhEngine *e, const OhFrame *f, const Pic *cur, HostSi
     return OH_OK;
 }
 
-/* pinned block the summary of one work list lands in */
+/* pinned block the summaries of one chunk's work lists land in */
 static void *summary_block_get(OhEngine *e)
 {
     void *p = nullptr;
     if (!e->sum_pool.empty()) { p = e->sum_pool.back(); e->sum_pool.pop_back(); return p; }
-    return hipHostMalloc(&p, sizeof(DevSummary), hipHostMallocDefault) == hipSuccess ? p : nullptr;
+    return hipHostMalloc(&p, OH_MAX_BATCH * sizeof(DevSummary), hipHostMallocDefault) == hipSuccess ? p : nullptr;
 }
 
-/* everything of the header but summary_host: pictures, pointers into df's arena, counts; and which references df was uploaded with */
-static void fill_header(OhEngine *e, const OhFrame *f, const Pic *cur, const HostSide &h, const HandoverLayout &L, OhDevFrame *df, HandoverHeader *H)
+/* everything of the header but summary_host: pictures, pointers into the two parts of the list in its chunk's arena, counts; and which
+ * references df was uploaded with */
+static void fill_header(OhEngine *e, const OhFrame *f, const Pic *cur, const HostSide &h, const HandoverLayout &L, char *copied_base, char *rest_base,
+                        OhDevFrame *df, HandoverHeader *H)
 {
     DevFrame &hd = H->d;
     hd.pp = f->p;
@@ -213,7 +231,7 @@ static void fill_header(OhEngine *e, const OhFrame *f, const Pic *cur, const Hos
     }
     df->ref_used = h.ref_used;
     df->cur_gen = cur->gen;
-    handover_bind(L, (char *)df->arena, H);
+    handover_bind_split(L, copied_base, rest_base, H);
     hd.coeffs_present = f->coeffs != nullptr;
     hd.err_word = e->kerr; hd.cur_pic_id = f->cur_pic;
     hd.n_pu = f->n_pu; hd.n_mc_luma = h.cnt.n_mc_luma; hd.n_mc_chroma = h.cnt.n_mc_chroma; hd.n_tu = f->n_tu; hd.n_intra = f->n_intra;
@@ -231,7 +249,7 @@ static void fill_header(OhEngine *e, const OhFrame *f, const Pic *cur, const Hos
 enum { PULL_TABLE = 64 };
 static_assert(HL_N_SEGS <= PULL_TABLE, "a table entry per copied segment");
 static size_t pulled_stage_bytes(const HandoverLayout &L) { return L.own_bytes + PULL_TABLE * sizeof(OhPullSeg); }
-static hipError_t stage_pulled(OhEngine *e, const HandoverLayout &L, char *arena, OhEngine::Stage *sg)
+static hipError_t stage_pulled(OhEngine *e, const HandoverLayout &L, char *arena, OhEngine::Stage *sg)     /* arena: the list's copied part */
 {
     char *sp = (char *)sg->p;
     OhPullSeg *tab = (OhPullSeg *)(sp + L.own_bytes);
@@ -255,8 +273,9 @@ static hipError_t stage_pulled(OhEngine *e, const HandoverLayout &L, char *arena
     return hipGetLastError();
 }
 
-/* Any other list is staged: everything in one host buffer laid out like the arena -> one H2D copy */
-static hipError_t stage_copied(OhEngine *e, const HandoverLayout &L, char *arena, OhEngine::Stage *sg)
+/* Any other list is staged.  A group of consecutive lists goes into ONE pinned buffer, each laid out as in the arena (their copied
+ * parts are neighbours there), by ONE run of the copy helpers over the jobs of all of them -> ONE H2D copy of `bytes` */
+static hipError_t stage_copied(OhEngine *e, const HandoverLayout *L, const size_t *copied_off, int n, char *arena, size_t bytes, OhEngine::Stage *sg)
 {
     { HostTimer t(e, OH_HT_UPLOAD_MEMCPY);
     if (!e->copiers) {
@@ -264,12 +283,14 @@ static hipError_t stage_copied(OhEngine *e, const HandoverLayout &L, char *arena
         e->copiers = new CopyPool();
         e->copiers->start(cenv ? std::max(0, std::min(atoi(cenv), 8)) : 2);
     }
-    handover_copy_jobs(L, (char *)sg->p, e->copy_jobs);     /* dealt round-robin to the calling thread and the helpers */
-    e->copiers->run(e->copy_jobs);
+    e->copy_jobs.clear();
+    for (int i = 0; i < n; i++)
+        handover_copy_jobs_add(L[i], (char *)sg->p + (copied_off[i] - copied_off[0]), e->copy_jobs);
+    e->copiers->run(e->copy_jobs);                          /* dealt round-robin to the calling thread and the helpers */
     }
     /* asynchronous: the caller's arrays are already copied out; the pinned buffer stays busy until `done` */
     HostTimer t_enq(e, OH_HT_UPLOAD_ENQUEUE);
-    return hipMemcpyAsync(arena, sg->p, L.copy_bytes, hipMemcpyHostToDevice, e->copy_stream);
+    return hipMemcpyAsync(arena + copied_off[0], sg->p, bytes, hipMemcpyHostToDevice, e->copy_stream);
 }
 
 /* with bs_in, behind the copy: both grids from the maps — once per work list, the maps never change */
@@ -283,107 +304,129 @@ static hipError_t enqueue_bs_derive(const OhFrame *f, const HandoverHeader &H, h
     return hrc;
 }
 
-/* the host part of one hand-over and its H2D copy; finish_uploads() enqueues the preparation kernels behind it */
-static int upload_one(OhEngine *e, const OhFrame *f, OhDevFrame **out)
+/* what the hand-over of a chunk keeps per list between its steps (per host thread: engines of several threads hand over at once) */
+struct ChunkScratch {
+    HostSide h[OH_MAX_BATCH];
+    std::vector<uint32_t> pu_off[OH_MAX_BATCH];
+    HandoverHeader H[OH_MAX_BATCH];
+    HandoverLayout L[OH_MAX_BATCH];
+    Pic *cur[OH_MAX_BATCH];
+};
+
+/* The hand-over of one chunk, n <= OH_MAX_BATCH lists: every list checked and counted; ONE arena; the lists staged and copied in
+ * groups of OH_STAGE_GROUP (a pulled list is a group of its own); one set of preparation launches (the kernels pick the list with a
+ * grid dimension, like the passes); ONE `ready` event.  On the copy stream that is at most one wait, a copy and an event per group,
+ * the preparation launches and one event.  On an error out[] holds the lists made so far (or nulls): the caller frees them. */
+static int upload_chunk(OhEngine *e, const OhFrame *const *fs, int n, OhDevFrame **out)
 {
-    *out = nullptr;
-    int rc = check_params(e, &f->p);
-    if (rc)
-        return rc;
-    Pic *cur = get_pic(e, f->cur_pic);
-    if (!cur || !same_geometry(cur->p, f->p))
-        FAIL(e, OH_E_ARG, "cur_pic %d is not an allocated picture of this geometry", f->cur_pic);
+    static thread_local std::unique_ptr<ChunkScratch> scratch;
+    if (!scratch) scratch.reset(new ChunkScratch());
+    ChunkScratch &S = *scratch;
     HostTimer t_all(e, OH_HT_UPLOAD);
-    HostSide h;
-    { HostTimer t(e, OH_HT_UPLOAD_COUNT);
-    rc = check_host_side(e, f, cur, &h);
+    for (int i = 0; i < n; i++) {
+        const OhFrame *f = fs[i];
+        if (!f)
+            return OH_E_ARG;
+        int rc = check_params(e, &f->p);
+        if (rc)
+            return rc;
+        S.cur[i] = get_pic(e, f->cur_pic);
+        if (!S.cur[i] || !same_geometry(S.cur[i]->p, f->p))
+            FAIL(e, OH_E_ARG, "cur_pic %d is not an allocated picture of this geometry", f->cur_pic);
+        { HostTimer t(e, OH_HT_UPLOAD_COUNT);
+        rc = check_host_side(e, f, S.cur[i], &S.h[i], S.pu_off[i]);
+        }
+        if (rc)
+            return rc;
+        memset(&S.H[i], 0, sizeof(S.H[i]));
+        S.L[i] = handover_layout(f, S.h[i], &S.H[i].d);
     }
-    if (rc)
-        return rc;
     HIPCHK(e, hipSetDevice(e->device));
-    HandoverHeader H;
-    memset(&H, 0, sizeof(H));
-    const HandoverLayout L = handover_layout(f, h, &H.d);
-    OhDevFrame *df = new OhDevFrame();
+    const HandoverChunk C = handover_chunk_place(S.L, n);
+    OhChunk *ck = new OhChunk();
+    int rc;
     { HostTimer t(e, OH_HT_UPLOAD_ARENA);
-    rc = arena_take(e, L.total, df);
+    rc = arena_take(e, C.total, ck);
     }
     if (rc) {
-        delete df;
+        delete ck;
         return rc;
     }
-    fill_header(e, f, cur, h, L, df, &H);
-
-    /* byte grids still have to be packed on the way: such a list is staged even when it lies in pinned memory */
-    const bool pull = (f->flags & OH_FRAME_PINNED) != 0 && !L.packs;
-    OhEngine::Stage *sg;
-    { HostTimer t(e, OH_HT_UPLOAD_STAGE_WAIT);
-    sg = stage_acquire(e, pull ? pulled_stage_bytes(L) : L.copy_bytes);   /* a pinned buffer whose previous copy has completed */
+    if ((ck->sum_host = summary_block_get(e)) == nullptr) {
+        chunk_free(e, ck, false);
+        FAIL(e, OH_E_NOMEM, "hipHostMalloc(%zu) for the summaries failed", OH_MAX_BATCH * sizeof(DevSummary));
     }
-    df->sum_host = summary_block_get(e);
-    H.d.summary_host = df->sum_host;                       /* pinned, device-accessible: prep_finish stores the summary there */
-    if (!sg || !df->sum_host) {
-        free_dev_frame(e, df);
-        FAIL(e, OH_E_NOMEM, "hipHostMalloc(%zu) failed", L.copy_bytes);
-    }
-    hipStream_t cs = e->copy_stream;
-    hipError_t hrc = pull ? stage_pulled(e, L, (char *)df->arena, sg) : stage_copied(e, L, (char *)df->arena, sg);
-    HostTimer t_enq(e, OH_HT_UPLOAD_ENQUEUE);
-    if (hrc == hipSuccess && stage_in_use(e, sg, cs) != OH_OK)
-        hrc = hipGetLastError();
-    e->up_bytes += L.copy_bytes;
-    if (hrc == hipSuccess && H.mvf)
-        hrc = enqueue_bs_derive(f, H, cs);
-    if (hrc != hipSuccess) {
-        (void)hipStreamSynchronize(cs);
-        free_dev_frame(e, df);
-        FAIL(e, OH_E_HIP, "work-list upload failed: %s", hipGetErrorString(hrc));
-    }
-    df->sum_dev = H.d.summary;
-    df->cnt = h.cnt;
-    df->d = (DevFrame *)df->arena;
-    df->p = f->p;
-    for (int k = 0; k < 4; k++) df->tu_cnt[k] = h.tu_cnt[k];
-    df->n_cross = h.n_cross;
-    df->has_sao = f->p.sao_enabled && f->sao;
-    df->cur_pic = f->cur_pic;                  /* which half of cur_pic is final changes when the list is EXECUTED, not here */
-    df->owner = e;
-    *out = df;
-    return OH_OK;
-}
-
-/* preparation kernels of n freshly copied work lists (one set of launches per 32 of them: the kernels pick the list with a grid
- * dimension, like the passes), their summaries back to pinned memory, their `ready` events */
-static int finish_uploads(OhEngine *e, OhDevFrame *const *dfs, int n)
-{
-    HostTimer t_enq(e, OH_HT_UPLOAD_ENQUEUE);
-    hipStream_t cs = e->copy_stream;
-    for (int c0 = 0; c0 < n; c0 += OH_MAX_BATCH) {
-        const int nb = n - c0 < OH_MAX_BATCH ? n - c0 : OH_MAX_BATCH;
-        OhBatch B;
-        memset(&B, 0, sizeof(B));
-        OhPrepCounts mx;
-        memset(&mx, 0, sizeof(mx));
-        uint32_t max_cross = 0, max_runs = 0;
-        for (int i = 0; i < nb; i++) {
-            const OhDevFrame *df = dfs[c0 + i];
-            B.f[i] = df->d;
-            mx.n_pu = std::max(mx.n_pu, df->cnt.n_pu); mx.n_tu = std::max(mx.n_tu, df->cnt.n_tu);
-            mx.n_intra = std::max(mx.n_intra, df->cnt.n_intra); mx.n_sub = std::max(mx.n_sub, df->cnt.n_sub);
-            mx.n_ictu = std::max(mx.n_ictu, df->cnt.n_ictu);
-            max_runs = std::max(max_runs, ((df->cnt.n_mc_luma + 63) >> 6) + ((df->cnt.n_mc_chroma + 63) >> 6));
-            max_cross = std::max(max_cross, df->n_cross);
-        }
-        ohk_prepare(&B, nb, &mx, max_runs, max_cross, cs);
-        HIPCHK(e, hipGetLastError());
-    }
-    /* one point in the copy stream makes all of them ready: an event per list, recorded back to back */
+    char *arena = (char *)ck->arena;
+    ck->refs = n;
     for (int i = 0; i < n; i++) {
-        OhDevFrame *df = dfs[i];
-        if ((df->ready = sync_event_get(e)) == nullptr)
-            FAIL(e, OH_E_NOMEM, "no event for the work list");
-        HIPCHK(e, hipEventRecord(df->ready, cs));
+        const OhFrame *f = fs[i];
+        const HostSide &h = S.h[i];
+        OhDevFrame *df = new OhDevFrame();
+        df->chunk = ck;
+        fill_header(e, f, S.cur[i], h, S.L[i], arena + C.copied_off[i], arena + C.rest_off[i], df, &S.H[i]);
+        df->sum_host = (DevSummary *)ck->sum_host + i;
+        S.H[i].d.summary_host = df->sum_host;              /* pinned, device-accessible: prep_finish stores the summary there */
+        df->sum_dev = S.H[i].d.summary;
+        df->cnt = h.cnt;
+        df->d = (DevFrame *)(arena + C.copied_off[i]);
+        df->p = f->p;
+        for (int k = 0; k < 4; k++) df->tu_cnt[k] = h.tu_cnt[k];
+        df->n_cross = h.n_cross;
+        df->has_sao = f->p.sao_enabled && f->sao;
+        df->cur_pic = f->cur_pic;              /* which half of cur_pic is final changes when the list is EXECUTED, not here */
+        df->owner = e;
+        out[i] = df;
     }
+
+    hipStream_t cs = e->copy_stream;
+    /* byte grids still have to be packed on the way: such a list is staged even when it lies in pinned memory */
+    auto pulled = [&](int i) { return (fs[i]->flags & OH_FRAME_PINNED) != 0 && !S.L[i].packs; };
+    for (int g0 = 0, g1; g0 < n; g0 = g1) {
+        const bool pull = pulled(g0);
+        for (g1 = g0 + 1; !pull && g1 < n && g1 - g0 < OH_STAGE_GROUP && !pulled(g1); g1++)
+            ;
+        const size_t bytes = C.copied_off[g1] - C.copied_off[g0];
+        OhEngine::Stage *sg;
+        { HostTimer t(e, OH_HT_UPLOAD_STAGE_WAIT);
+        sg = stage_acquire(e, pull ? pulled_stage_bytes(S.L[g0]) : bytes);   /* a pinned buffer whose previous copy has completed */
+        }
+        if (!sg)
+            FAIL(e, OH_E_NOMEM, "hipHostMalloc(%zu) failed", bytes);
+        hipError_t hrc = pull ? stage_pulled(e, S.L[g0], arena + C.copied_off[g0], sg)
+                              : stage_copied(e, &S.L[g0], &C.copied_off[g0], g1 - g0, arena, bytes, sg);
+        HostTimer t_enq(e, OH_HT_UPLOAD_ENQUEUE);
+        if (hrc == hipSuccess && stage_in_use(e, sg, cs) != OH_OK)
+            hrc = hipGetLastError();
+        for (int i = g0; i < g1; i++) {
+            e->up_bytes += S.L[i].copy_bytes;
+            if (hrc == hipSuccess && S.H[i].mvf)
+                hrc = enqueue_bs_derive(fs[i], S.H[i], cs);
+        }
+        if (hrc != hipSuccess)
+            FAIL(e, OH_E_HIP, "work-list upload failed: %s", hipGetErrorString(hrc));
+    }
+
+    HostTimer t_enq(e, OH_HT_UPLOAD_ENQUEUE);
+    OhBatch B;
+    memset(&B, 0, sizeof(B));
+    OhPrepCounts mx;
+    memset(&mx, 0, sizeof(mx));
+    uint32_t max_cross = 0, max_runs = 0;
+    for (int i = 0; i < n; i++) {
+        const OhDevFrame *df = out[i];
+        B.f[i] = df->d;
+        mx.n_pu = std::max(mx.n_pu, df->cnt.n_pu); mx.n_tu = std::max(mx.n_tu, df->cnt.n_tu);
+        mx.n_intra = std::max(mx.n_intra, df->cnt.n_intra); mx.n_sub = std::max(mx.n_sub, df->cnt.n_sub);
+        mx.n_ictu = std::max(mx.n_ictu, df->cnt.n_ictu);
+        max_runs = std::max(max_runs, ((df->cnt.n_mc_luma + 63) >> 6) + ((df->cnt.n_mc_chroma + 63) >> 6));
+        max_cross = std::max(max_cross, df->n_cross);
+    }
+    ohk_prepare(&B, n, &mx, max_runs, max_cross, cs);
+    HIPCHK(e, hipGetLastError());
+    /* one point in the copy stream makes all of them ready */
+    if ((ck->ready = sync_event_get(e)) == nullptr)
+        FAIL(e, OH_E_NOMEM, "no event for the work lists");
+    HIPCHK(e, hipEventRecord(ck->ready, cs));
     return OH_OK;
 }
 
@@ -393,13 +436,12 @@ extern "C" int oh_frames_upload(OhEngine *e, const OhFrame *const *fs, int n, Oh
         return OH_E_ARG;
     for (int i = 0; i < n; i++) out[i] = nullptr;
     int rc = OH_OK;
-    int done = 0;
-    for (; done < n && rc == OH_OK; done++)
-        rc = fs[done] ? upload_one(e, fs[done], &out[done]) : OH_E_ARG;
-    if (rc == OH_OK)
-        rc = finish_uploads(e, out, n);
+    for (int c0 = 0; c0 < n && rc == OH_OK; c0 += OH_MAX_BATCH)
+        rc = upload_chunk(e, fs + c0, n - c0 < OH_MAX_BATCH ? n - c0 : OH_MAX_BATCH, out + c0);
     if (rc != OH_OK) {                                     /* all or nothing */
-        (void)hipStreamSynchronize(e->copy_stream);
+        bool any = false;
+        for (int i = 0; i < n; i++) any = any || out[i];
+        if (any) (void)hipStreamSynchronize(e->copy_stream);
         for (int i = 0; i < n; i++) { free_dev_frame(e, out[i]); out[i] = nullptr; }
     }
     return rc;

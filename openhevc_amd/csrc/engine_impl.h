@@ -40,10 +40,22 @@ struct Pic {
 
 struct EventSet { hipEvent_t ev[OH_N_PASSES + 1]; int n_frames = 1; };
 
-struct OhDevFrame {
+/* What the work lists handed over in one oh_frames_upload call (at most OH_MAX_BATCH of them) share: one device arena
+ * (handover_layout.h: handover_chunk_place), one `ready` event and one pinned block for their summaries.  A list uploaded alone is a
+ * chunk of one.  The lists are executed, released and freed one by one and in any order; the arena returns to the pool with the last. */
+struct OhChunk {
     void      *arena = nullptr;
     size_t     arena_bytes = 0;
-    DevFrame  *d = nullptr;
+    hipEvent_t ready = nullptr;   /* recorded on the copy stream behind the chunk's H2D copies, preparation kernels and summaries */
+    bool       waited = false;    /* the engine stream already waits for `ready` */
+    void      *sum_host = nullptr;/* pinned: OH_MAX_BATCH DevSummary, one per list */
+    int        refs = 0;          /* lists not yet released or freed */
+    bool       in_flight = false; /* some list was released while passes that read the arena could still be running */
+};
+
+struct OhDevFrame {
+    OhChunk   *chunk = nullptr;
+    DevFrame  *d = nullptr;       /* the start of the list's copied part in the chunk's arena */
     OhPicParams p{};
     uint32_t   tu_cnt[4] = { 0, 0, 0, 0 };
     uint32_t   n_cross = 0;
@@ -56,9 +68,7 @@ struct OhDevFrame {
     uint32_t   ref_gen[OH_MAX_REFS];
     uint8_t    ref_half[OH_MAX_REFS];
     uint16_t   ref_used = 0;      /* bit i: some PU predicts from slot i */
-    hipEvent_t ready = nullptr;   /* recorded on the copy stream behind the work list's H2D copy, preparation kernels and summary */
-    bool       waited = false;    /* the engine stream already waits for `ready` */
-    void      *sum_host = nullptr;/* pinned: the DevSummary the preparation kernels left */
+    void      *sum_host = nullptr;/* pinned, inside chunk->sum_host: the DevSummary the preparation kernels left */
     bool       summary_read = false;
     void      *sum_dev = nullptr; /* the summary in the arena */
     OhPrepCounts cnt{};           /* sizes of the preparation launches */
@@ -157,7 +167,7 @@ struct OhEngine {
     std::vector<Arena> arenas;               /* free device arenas */
     uint64_t    arenas_alive = 0, arena_bytes_alive = 0;      /* device arenas allocated and not freed (pooled or holding a work list): oh_engine_memory */
     std::vector<hipEvent_t> sync_events;     /* pool of timing-disabled events (ready / free_ev) */
-    std::vector<void *> sum_pool;            /* pinned blocks of sizeof(DevSummary) bytes */
+    std::vector<void *> sum_pool;            /* pinned blocks of OH_MAX_BATCH * sizeof(DevSummary) bytes: one per chunk */
     double      host_ms[OH_N_HOST_TIMES] = {};   /* where the host time of the hand-over path goes (oh_engine_host_times) */
     uint64_t    host_calls[OH_N_HOST_TIMES] = {};
     uint64_t    up_bytes = 0;                    /* bytes of work lists sent over PCIe since the last reset */
@@ -234,7 +244,16 @@ struct HostTimer {                       /* adds the scope's wall time to one sl
     HostTimer(OhEngine *e_, int slot_);
     ~HostTimer();
 };
-enum { OH_MAX_STAGES = 48 };             /* pinned staging buffers per engine before the host is made to wait */
+/* pinned staging memory per engine before the host is made to wait (48 buffers of 4 MiB when every list came alone; a group of
+ * OH_STAGE_GROUP lists is staged in one buffer: one chunk of 32 4K lists, 132 MB, at a time) */
+enum : size_t { OH_STAGE_POOL_BYTES = (size_t)48 * ((size_t)4 << 20) };
+/* lists staged into one pinned buffer and sent with ONE copy request: a chunk of OH_MAX_BATCH lists puts OH_MAX_BATCH / OH_STAGE_GROUP
+ * copies on the copy stream.  Smaller groups let the DMA start before the host has staged the whole chunk, larger ones put fewer
+ * commands on the stream, and that is what counts: 4K Main 10 decode, six runs each beside the parent's 63.5-65.8 Gpixels/s, gave
+ * 63.4-70.5 at 8, 65.7-69.0 at 16 and 82.1-87.8 at 32 (profiles/r10_chunk_handover.txt) */
+#ifndef OH_STAGE_GROUP
+#define OH_STAGE_GROUP 32
+#endif
 
 /* the planes of the half that holds the finished picture, and the bytes of one of its samples */
 static inline void *const *final_planes(const Pic *p) { return p->final_b ? p->b : p->a; }

@@ -2,7 +2,8 @@
  * handover_layout.h — the device arena of one work list as a value.  handover_layout() states every segment once (source, bytes,
  * presence, the DevFrame field it backs) and places them; handover_bind() turns the table into the header's pointers for an arena
  * base; handover_copy_jobs() cuts the copied range into the pieces of the staging copy.  Pure host code: no HIP runtime call, no
- * engine — tests/handover_layout_check.cpp runs all of it on the CPU.  The arena, in this order, every segment 256-byte aligned:
+ * engine — tests/handover_layout_check.cpp and tests/handover_chunk_check.cpp run all of it on the CPU.  handover_chunk_place() puts
+ * the lists of one call into one arena, copied parts first.  A list, in this order, every segment 256-byte aligned:
  *   [copied: header, raw lists, side arrays, coefficient pool] [cleared: cursor, summary, ctu_seen, tu_keep]
  *   [device only: prepared lists, scratch] [residual pool] [SAO stale buffer]
  */
@@ -183,27 +184,62 @@ static inline HandoverLayout handover_layout(const OhFrame *f, const HostSide &h
     return L;
 }
 
-/* the header's pointers for an arena at `base` */
-static inline void handover_bind(const HandoverLayout &L, char *base, HandoverHeader *H)
+/* where offset `off` of a list lies when its copied part [0, copy_bytes) stands at copied_base and the rest at rest_base */
+static inline char *hl_at(const HandoverLayout &L, char *copied_base, char *rest_base, size_t off)
+{
+    return off < L.copy_bytes ? copied_base + off : rest_base + (off - L.copy_bytes);
+}
+
+/* the header's pointers for a list in two parts (a chunk's arena: handover_chunk_place); no segment straddles copy_bytes */
+static inline void handover_bind_split(const HandoverLayout &L, char *copied_base, char *rest_base, HandoverHeader *H)
 {
     for (int i = 0; i < L.ns; i++)
         if (L.seg[i].field != HL_NO_FIELD) {
-            char *at = L.seg[i].null_field ? nullptr : base + L.seg[i].off;
+            char *at = L.seg[i].null_field ? nullptr : hl_at(L, copied_base, rest_base, L.seg[i].off);
             memcpy((char *)H + L.seg[i].field, &at, sizeof(at));
         }
     H->d.sub_small_w = (uint32_t *)H->d.sub_small;
-    H->d.res = (int16_t *)(base + L.res_off);
-    H->d.sao_stale = L.stale_bytes ? (uint16_t *)(base + L.stale_off) : nullptr;
-    H->d.zero_ptr = (uint32_t *)(base + L.zero_off); H->d.zero_words = (uint32_t)(L.zero_bytes / 4);
+    H->d.res = (int16_t *)hl_at(L, copied_base, rest_base, L.res_off);
+    H->d.sao_stale = L.stale_bytes ? (uint16_t *)hl_at(L, copied_base, rest_base, L.stale_off) : nullptr;
+    H->d.zero_ptr = (uint32_t *)hl_at(L, copied_base, rest_base, L.zero_off); H->d.zero_words = (uint32_t)(L.zero_bytes / 4);
+}
+
+/* the header's pointers for an arena at `base` that holds the list in one piece */
+static inline void handover_bind(const HandoverLayout &L, char *base, HandoverHeader *H)
+{
+    handover_bind_split(L, base, base + L.copy_bytes, H);
+}
+
+/* The arena of a chunk: the lists handed over in one call (at most OH_MAX_BATCH) share one arena,
+ *   [copied part of list 0 | ... | copied part of list n-1 | rest of list 0 | ... | rest of list n-1]
+ * every part 256-byte aligned, so that all the bytes that cross PCIe are one range, [0, copy_bytes), and any run of consecutive
+ * lists is copied with one request.  A list's copied part is [0, L.copy_bytes) of its own layout, its rest [L.copy_bytes, L.total). */
+struct HandoverChunk {
+    int    n;
+    size_t copied_off[OH_MAX_BATCH + 1];  /* where list i's copied part starts; [n] = copy_bytes */
+    size_t rest_off[OH_MAX_BATCH];        /* where its rest starts */
+    size_t copy_bytes, total;
+};
+static inline HandoverChunk handover_chunk_place(const HandoverLayout *L, int n)
+{
+    HandoverChunk C;
+    memset(&C, 0, sizeof(C));
+    C.n = n;
+    size_t at = 0;
+    for (int i = 0; i < n; i++) { C.copied_off[i] = at; at += align_up(L[i].copy_bytes, 256); }
+    C.copied_off[n] = C.copy_bytes = at;
+    for (int i = 0; i < n; i++) { C.rest_off[i] = at; at += align_up(L[i].total - L[i].copy_bytes, 256); }
+    C.total = at;
+    return C;
 }
 
 /* the one host copy of the hand-over (the work list into a pinned staging buffer laid out like the arena) as jobs for the copy helpers:
  * pieces of at most 128 KB; a byte grid is packed on the way, four source bytes per byte: pieces of 4 x 128 KB strengths */
 struct CopyJob { char *dst; const char *src; size_t n; bool pack; };
-static inline void handover_copy_jobs(const HandoverLayout &L, char *stage, std::vector<CopyJob> &jobs)
+/* adds the jobs of one list whose copied part is staged at `stage` (a group of lists is staged by ONE run over the jobs of all of them) */
+static inline void handover_copy_jobs_add(const HandoverLayout &L, char *stage, std::vector<CopyJob> &jobs)
 {
     const size_t piece = 128 * 1024;
-    jobs.clear();
     for (int i = 0; i < L.ns; i++) {
         const HandoverSeg &s = L.seg[i];
         if (!L.copied(s))
@@ -212,6 +248,11 @@ static inline void handover_copy_jobs(const HandoverLayout &L, char *stage, std:
         for (size_t o = 0; o < n; o += step)
             jobs.push_back({ stage + s.off + (s.pack_n ? o / 4 : o), (const char *)s.src + o, std::min(step, n - o), s.pack_n != 0 });
     }
+}
+static inline void handover_copy_jobs(const HandoverLayout &L, char *stage, std::vector<CopyJob> &jobs)
+{
+    jobs.clear();
+    handover_copy_jobs_add(L, stage, jobs);
 }
 
 #endif
