@@ -313,6 +313,56 @@ int64_t oh_compare_ssim_window(int bit_depth, uint32_t s1, uint32_t s2, uint64_t
 /* host only: 10 log10(M^2 samples / sse) in dB; +infinity for sse 0; NaN for samples 0 */
 double  oh_compare_psnr(uint64_t sse, uint64_t samples, int bit_depth);
 
+/* Composition of finished pictures (DESIGN.md §3h has the exact definition, which the tests check bit for bit against
+ * tests/compose_model.py): n destination pictures are composed IN PLACE, on their finished halves — an optional fill of the whole coded
+ * planes, then up to OH_COMPOSE_MAX_LAYERS layers in list order, each a rectangle of another finished picture placed at an offset,
+ * with an opacity and an optional 8-bit alpha plane in caller-owned DEVICE memory, source over destination in code values with
+ * straight alpha.  What a logo or burnt-in subtitles on every picture of a batch, picture-in-picture, a contact sheet and a letterbox
+ * are made of: oh_pics_import turns an RGBA overlay into a picture (and leaves its alpha channel where it is, for this call),
+ * oh_pics_resize scales it, this call puts it on.
+ * Per sample of plane c: w = alpha * opacity (0 .. 65280; alpha 255 without a plane) and oh_compose_blend(dst, src, alpha, opacity) =
+ * (src w + dst (65280 - w) + 32640) / 65280 in exact integers: w = 0 keeps dst, w = 65280 gives src.  Plane c of a layer is the rectangle,
+ * the position and the clip shifted by oh_hshift / oh_vshift; the alpha of a chroma sample is oh_compose_chroma_alpha of the luma
+ * alphas it covers (4:2:0 the rounded mean of 2 x 2, 4:2:2 of two, 4:4:4 the alpha itself). */
+enum { OH_COMPOSE_MAX_LAYERS = 16 };
+enum { OH_COMPOSE_FILL = 1 };                 /* flags */
+typedef struct OhLayer {
+    const int32_t *src_ids;       /* n finished pictures: the source of this layer for destination i (a logo: n times the same id) */
+    int32_t  sx, sy, w, h;        /* rectangle of the source, luma samples: inside the source's coded size */
+    int32_t  dx, dy;              /* where its top left goes in the destination, luma samples; may be negative or reach beyond: clipped */
+    int32_t  opacity;             /* 0 .. 256 */
+    const void *alpha;            /* NULL (255 everywhere) or DEVICE memory: one u8 per luma sample of the rectangle, straight (not premultiplied) */
+    int64_t  alpha_pixel_stride, alpha_row_stride, alpha_image_stride;   /* bytes; image stride 0: all destinations share one plane */
+} OhLayer;
+typedef struct OhCompose {
+    int32_t  flags;               /* 0 or OH_COMPOSE_FILL */
+    int32_t  fill[3];             /* OH_COMPOSE_FILL: the Y, Cb, Cr sample values every coded plane starts from (4:0:0: fill[1..2] are not read) */
+    int32_t  n_layers;            /* 0 .. OH_COMPOSE_MAX_LAYERS */
+    const OhLayer *layers;        /* host array, applied in order */
+} OhCompose;
+/* n destinations with identical OhPicParams; the n pictures of one layer with identical params among themselves, of any size, but of
+ * the destinations' bit depth and chroma format.  Reads each source's finished half and composes each destination's finished half (half
+ * 0 of a picture nothing has finished yet): the whole coded planes with OH_COMPOSE_FILL — the old content is not read —, else the
+ * bounding box of the layers clipped to the destination's coded size; which half is the finished one does not change.  A layer wholly
+ * outside the destination changes nothing.  The luma alpha of rectangle sample (x, y) of destination i is the byte at alpha + i *
+ * alpha_image_stride + y * alpha_row_stride + x * alpha_pixel_stride (pixel stride 4: the alpha channel of the RGBA image that went
+ * into oh_pics_import); clipping moves the origin with the rectangle.  Enqueued on the engine stream behind the work that finished the
+ * pictures, returns without waiting: the alpha planes must stay valid until the stream has passed the call.  n == 0: OH_OK.  More than
+ * OH_CONV_MAX_PICS destinations are split into several launches.
+ * OH_E_ARG, nothing written: a null e, cp or id array; n_layers outside 0 .. OH_COMPOSE_MAX_LAYERS, or null layers with n_layers > 0; an
+ * unknown picture; destinations whose params differ, or the pictures of one layer whose params differ; a destination listed twice, or a
+ * picture that is both a destination and a source; a source rectangle that is empty, not inside the source's coded size, or — like dx
+ * and dy — not a multiple of SubWidthC / SubHeightC; an opacity outside 0 .. 256; flag bits other than OH_COMPOSE_FILL; a fill value
+ * outside the bit depth; an alpha pointer that is not device memory of the engine's device, or whose allocation ends before the last
+ * byte the unclipped rectangle of the last image addresses; negative alpha strides.
+ * OH_E_UNSUPPORTED, nothing written: a layer whose pictures differ from the destinations in bit depth or chroma format. */
+int      oh_pics_compose(OhEngine *e, const int *dst_ids, int n, const OhCompose *cp);
+/* host only — the very functions the kernel evaluates (csrc/compose_common.h, shared by host and device like compare_common.h): the
+ * blend of one sample of at most 12 bits (alpha 0 .. 255, opacity 0 .. 256), and the alpha of a chroma sample from the luma alphas
+ * a00 a01 (upper luma row) and a10 a11 (lower) that it covers */
+uint32_t oh_compose_blend(uint32_t dst, uint32_t src, uint32_t alpha, uint32_t opacity);
+uint32_t oh_compose_chroma_alpha(int chroma_format_idc, uint32_t a00, uint32_t a01, uint32_t a10, uint32_t a11);
+
 /* SHVC inter-layer reference picture: resample the finished base-layer picture src_pic into
  * the enhancement-layer picture dst_pic, bit-exact with the reference's whole-picture slot
  * HEVCDSPContext.upsample_base_layer_frame (hevcdsp_template.c:2164-2438, call site hevc.c:3241).

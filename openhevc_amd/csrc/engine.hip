@@ -190,6 +190,7 @@ extern "C" void oh_engine_destroy(OhEngine *e)
     if (e->light_dev.p) (void)hipFree(e->light_dev.p);
     if (e->light_res.p) (void)hipFree(e->light_res.p);
     if (e->compare_res.p) (void)hipFree(e->compare_res.p);
+    if (e->compose_dev.p) (void)hipFree(e->compose_dev.p);
     for (auto &ev : e->batch_ev) if (ev) (void)hipEventDestroy(ev);
     if (e->dl_stream) { (void)hipStreamSynchronize(e->dl_stream); (void)hipStreamDestroy(e->dl_stream); }
     if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);

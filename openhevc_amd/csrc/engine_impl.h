@@ -2,7 +2,7 @@
  * engine_impl.h — what the engine's translation units share: the engine and picture structures, the error macros and the few
  * helpers more than one of them uses.  engine.hip: engine and picture lifecycle, staging buffers, passes, profiling;
  * engine_handover.hip: work-list hand-over and the arena pool; engine_pics.hip: plane transfers, hashes, conversion, import, measurement,
- * comparison and resizing of finished pictures; engine_shvc.hip: SHVC up-sampling.
+ * comparison, resizing and composition of finished pictures; engine_shvc.hip: SHVC up-sampling.
  * Internal: the C ABI is include/ohevc_hip.h.
  */
 #ifndef OHEVC_ENGINE_IMPL_H
@@ -217,6 +217,7 @@ struct OhEngine {
     std::vector<int32_t> light_tab;      /* OH_COLT_N as colour_build lays them out; OH_COLT_G of them go to the device */
     int32_t     light_misc[OH_COL_NMISC];
     Scratch     compare_res;             /* oh_pics_compare: the results of the call in HBM */
+    Scratch     compose_dev;             /* oh_pics_compose: the layer table of the call (OhCpsLayer, then OhCpsSrc per launch set) */
     uint32_t    spin_limit = 1u << 22;   /* polls (with s_sleep between them, ~1 s in all) before a waiting workgroup gives up; OHEVC_SPIN_LIMIT */
 };
 

@@ -1,13 +1,14 @@
 /*
  * engine_pics.hip — what the engine does with finished pictures beside the reconstruction path (host side; the kernels are md5.hip,
- * hash.hip, convert.hip, import.hip, colour.hip, light.hip, compare.hip and resize.hip): plane upload and download, the two-phase window fetch,
- * picture hashes, conversion to YUV / RGB images and back, with the colour tables of the HDR forms, light-level statistics, comparison of two
- * pictures, and resizing into engine pictures.
+ * hash.hip, convert.hip, import.hip, colour.hip, light.hip, compare.hip, resize.hip and compose.hip): plane upload and download, the two-phase
+ * window fetch, picture hashes, conversion to YUV / RGB images and back, with the colour tables of the HDR forms, light-level statistics,
+ * comparison of two pictures, resizing into engine pictures, and composition of pictures in place: fill, overlay, alpha blend.
  */
 #include <cmath>
 #include <limits>
 #include "engine_impl.h"
 #include "compare_common.h"
+#include "compose_common.h"
 
 /* at least `bytes` of device scratch, grow-only in 1 MiB steps.  Growing frees the old block: the caller has made sure that nothing
  * enqueued still uses it. */
@@ -1458,6 +1459,205 @@ extern "C" int oh_pics_resize(OhEngine *e, const int *src_ids, const int *dst_id
     { const int rc = stage_in_use(e, sg, e->stream); if (rc) return rc; }
     a.mid = (int16_t *)(d + pl.tab);
     return resize_launch(e, src_ids, dst_ids, n, per_set, rs->width < d0->p.width || rs->height < d0->p.height, &a);
+}
+
+/* ---------------- composition (compose.hip) ---------------- */
+extern "C" uint32_t oh_compose_blend(uint32_t dst, uint32_t src, uint32_t alpha, uint32_t opacity)
+{
+    return compose_blend(dst, src, alpha, opacity);
+}
+
+extern "C" uint32_t oh_compose_chroma_alpha(int chroma_format_idc, uint32_t a00, uint32_t a01, uint32_t a10, uint32_t a11)
+{
+    return compose_chroma_alpha(chroma_format_idc, a00, a01, a10, a11);
+}
+
+/* everything oh_pics_compose refuses, before anything is enqueued (dst_ids, cp not null; n > 0) */
+static int compose_check(OhEngine *e, const int *dst_ids, int n, const OhCompose *cp)
+{
+    const char *who = "oh_pics_compose";
+    if (cp->flags & ~OH_COMPOSE_FILL)
+        FAIL(e, OH_E_ARG, "%s: flags 0x%x (0 or OH_COMPOSE_FILL)", who, (unsigned)cp->flags);
+    if (cp->n_layers < 0 || cp->n_layers > OH_COMPOSE_MAX_LAYERS || (cp->n_layers && !cp->layers))
+        FAIL(e, OH_E_ARG, "%s: n_layers %d (0 .. %d), or no layers", who, cp->n_layers, OH_COMPOSE_MAX_LAYERS);
+    { const int rc = check_pics(e, dst_ids, n, who); if (rc) return rc; }
+    const int other = first_other_params(e, dst_ids, n);
+    if (other < n)
+        FAIL(e, OH_E_ARG, "%s: destination %d has other params than destination %d", who, dst_ids[other], dst_ids[0]);
+    std::vector<int> d(dst_ids, dst_ids + n);
+    std::sort(d.begin(), d.end());
+    if (std::adjacent_find(d.begin(), d.end()) != d.end())
+        FAIL(e, OH_E_ARG, "%s: a destination is listed twice", who);
+    const OhPicParams &dp = get_pic(e, dst_ids[0])->p;
+    const int cf = dp.chroma_format_idc, sw = 1 << oh_hshift(&dp, 1), sh = 1 << oh_vshift(&dp, 1);
+    if (cp->flags & OH_COMPOSE_FILL)
+        for (int c = 0; c < (cf ? 3 : 1); c++)
+            if (cp->fill[c] < 0 || cp->fill[c] >= 1 << dp.bit_depth)
+                FAIL(e, OH_E_ARG, "%s: fill[%d] = %d is not a sample of %d bits", who, c, cp->fill[c], dp.bit_depth);
+    for (int k = 0; k < cp->n_layers; k++) {
+        const OhLayer &l = cp->layers[k];
+        if (!l.src_ids)
+            FAIL(e, OH_E_ARG, "%s: layer %d has no src_ids", who, k);
+        for (int i = 0; i < n; i++) {
+            if (!get_pic(e, l.src_ids[i]))
+                FAIL(e, OH_E_ARG, "%s: layer %d: unknown picture %d", who, k, l.src_ids[i]);
+            if (std::binary_search(d.begin(), d.end(), l.src_ids[i]))
+                FAIL(e, OH_E_ARG, "%s: layer %d: picture %d is both source and destination", who, k, l.src_ids[i]);
+        }
+        const int so = first_other_params(e, l.src_ids, n);
+        if (so < n)
+            FAIL(e, OH_E_ARG, "%s: layer %d: picture %d has other params than picture %d", who, k, l.src_ids[so], l.src_ids[0]);
+        const OhPicParams &sp = get_pic(e, l.src_ids[0])->p;
+        if (l.opacity < 0 || l.opacity > 256)
+            FAIL(e, OH_E_ARG, "%s: layer %d: opacity %d (0 .. 256)", who, k, l.opacity);
+        if (sp.bit_depth != dp.bit_depth || sp.chroma_format_idc != cf)
+            FAIL(e, OH_E_UNSUPPORTED, "%s: layer %d: sources of %d bit, chroma format %d; destinations of %d bit, chroma format %d", who, k,
+                 sp.bit_depth, sp.chroma_format_idc, dp.bit_depth, cf);
+        if (l.w < 1 || l.h < 1 || l.sx < 0 || l.sy < 0 || l.sx > sp.width - l.w || l.sy > sp.height - l.h)
+            FAIL(e, OH_E_ARG, "%s: layer %d: rectangle %dx%d at (%d,%d) is empty or not inside the source's %dx%d", who, k, l.w, l.h, l.sx, l.sy,
+                 sp.width, sp.height);
+        if (l.sx % sw || l.w % sw || l.dx % sw || l.sy % sh || l.h % sh || l.dy % sh)
+            FAIL(e, OH_E_ARG, "%s: layer %d: rectangle %dx%d at (%d,%d) to (%d,%d): not multiples of %dx%d", who, k, l.w, l.h, l.sx, l.sy, l.dx,
+                 l.dy, sw, sh);
+        if (!l.alpha)
+            continue;
+        if (l.alpha_pixel_stride < 0 || l.alpha_row_stride < 0 || l.alpha_image_stride < 0)
+            FAIL(e, OH_E_ARG, "%s: layer %d: negative alpha strides (%lld, %lld, %lld)", who, k, (long long)l.alpha_pixel_stride,
+                 (long long)l.alpha_row_stride, (long long)l.alpha_image_stride);
+        /* the last byte the unclipped rectangle of the last image addresses, in 128 bits: the strides are the caller's */
+        const unsigned __int128 last = (unsigned __int128)(n - 1) * (uint64_t)l.alpha_image_stride +
+                                       (unsigned __int128)(l.h - 1) * (uint64_t)l.alpha_row_stride +
+                                       (unsigned __int128)(l.w - 1) * (uint64_t)l.alpha_pixel_stride;
+        HIPCHK(e, hipSetDevice(e->device));
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, l.alpha) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->device) {
+            (void)hipGetLastError();
+            FAIL(e, OH_E_ARG, "%s: layer %d: alpha is not device memory of device %d", who, k, e->device);
+        }
+        void *base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, const_cast<void *>(l.alpha)) != hipSuccess) {
+            (void)hipGetLastError();
+            continue;
+        }
+        const size_t room = (size_t)((const char *)base + size - (const char *)l.alpha);    /* bytes from alpha to the allocation's end */
+        if (last >= room)
+            FAIL(e, OH_E_ARG, "%s: layer %d: the alpha planes of %d rectangles of %dx%d (strides %lld, %lld, %lld) run past the %zu bytes left of "
+                 "their allocation", who, k, n, l.w, l.h, (long long)l.alpha_pixel_stride, (long long)l.alpha_row_stride,
+                 (long long)l.alpha_image_stride, room);
+    }
+    return OH_OK;
+}
+
+extern "C" int oh_pics_compose(OhEngine *e, const int *dst_ids, int n, const OhCompose *cp)
+{
+    if (!e || !cp || n < 0 || (n && !dst_ids))
+        return OH_E_ARG;
+    if (!n)
+        return OH_OK;
+    { const int rc = compose_check(e, dst_ids, n, cp); if (rc) return rc; }
+    const Pic *d0 = get_pic(e, dst_ids[0]);
+    const OhPicParams &dp = d0->p;
+    const int bpp = sample_bytes(dp.bit_depth), np = dp.chroma_format_idc ? 3 : 1, gs = 16 / bpp;
+    const bool fill = (cp->flags & OH_COMPOSE_FILL) != 0;
+    OhCpsArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int c = 0; c < np; c++) { a.pitch[c] = d0->stride[c] * bpp; a.fill_v[c] = fill ? cp->fill[c] : 0; }
+    a.np = np; a.bd = dp.bit_depth; a.cf = dp.chroma_format_idc; a.fill = fill;
+
+    /* the layers that are not wholly outside, with their geometry in both plane classes, and the area they touch */
+    std::vector<OhCpsLayer> lay;
+    std::vector<int> which;                                      /* their indices in cp->layers */
+    int box[2][4] = { { INT32_MAX, INT32_MAX, 0, 0 }, { INT32_MAX, INT32_MAX, 0, 0 } };      /* x0, y0, x1, y1 */
+    for (int k = 0; k < cp->n_layers; k++) {
+        const OhLayer &l = cp->layers[k];
+        const Pic *s0 = get_pic(e, l.src_ids[0]);
+        OhCpsLayer L;
+        memset(&L, 0, sizeof(L));
+        bool empty = false;
+        for (int q = 0; q < (np > 1 ? 2 : 1); q++) {
+            const int hs = oh_hshift(&dp, q), vs = oh_vshift(&dp, q);
+            const int dx = l.dx >> hs, dy = l.dy >> vs;         /* multiples of the sub-sampling: exact, also below zero */
+            /* the clip in 64 bits: dx and dy are any int32; a layer that is not wholly outside lies within a picture's extent of zero */
+            const int64_t x1 = std::min<int64_t>((int64_t)dx + (l.w >> hs), d0->w[q]), y1 = std::min<int64_t>((int64_t)dy + (l.h >> vs), d0->h[q]);
+            if (dx >= x1 || dy >= y1 || x1 <= 0 || y1 <= 0) {
+                empty = true;
+                break;
+            }
+            L.x0[q] = std::max(dx, 0); L.x1[q] = (int32_t)x1;
+            L.y0[q] = std::max(dy, 0); L.y1[q] = (int32_t)y1;
+            L.ox[q] = (l.sx >> hs) - dx; L.oy[q] = (l.sy >> vs) - dy;
+            L.dx[q] = dx; L.dy[q] = dy;
+            L.spitch[q] = s0->stride[q] * bpp;
+        }
+        if (empty)
+            continue;
+        L.opacity = l.opacity; L.has_alpha = l.alpha != nullptr;
+        L.a_ps = l.alpha_pixel_stride; L.a_rs = l.alpha_row_stride;
+        for (int q = 0; q < (np > 1 ? 2 : 1); q++) {
+            box[q][0] = std::min(box[q][0], L.x0[q]); box[q][1] = std::min(box[q][1], L.y0[q]);
+            box[q][2] = std::max(box[q][2], L.x1[q]); box[q][3] = std::max(box[q][3], L.y1[q]);
+        }
+        lay.push_back(L);
+        which.push_back(k);
+    }
+    for (int i = 0; i < n; i++)
+        get_pic(e, dst_ids[i])->done_seq = 0;                   /* not written by a reconstruction batch: a download stays behind the engine stream */
+    if (lay.empty() && !fill)
+        return OH_OK;                                           /* nothing reaches the destinations */
+    for (int q = 0; q < (np > 1 ? 2 : 1); q++) {
+        OhCpsClass &kc = a.k[q];
+        if (fill) { box[q][0] = box[q][1] = 0; box[q][2] = d0->w[q]; box[q][3] = d0->h[q]; }
+        kc.gx0 = box[q][0] / gs; kc.gx1 = (box[q][2] + gs - 1) / gs;     /* whole granules: a row's last one may end in its padding */
+        kc.y0 = box[q][1]; kc.y1 = box[q][3];
+        kc.tx = (kc.gx1 - kc.gx0 + OH_CPS_TW - 1) / OH_CPS_TW; kc.ty = (kc.y1 - kc.y0 + OH_CPS_TH - 1) / OH_CPS_TH;
+    }
+
+    /* the table: the layers, then per launch set [layer][destination of the set]; built in a pinned buffer of the pool and copied on the
+     * engine stream — behind the launches of an earlier call that read the device copy, in front of this call's */
+    const int nl = (int)lay.size();
+    const size_t lay_bytes = align_up((size_t)nl * sizeof(OhCpsLayer), 256);
+    const size_t need = lay_bytes + (size_t)nl * (size_t)n * sizeof(OhCpsSrc);
+    HIPCHK(e, hipSetDevice(e->device));
+    if (nl) {
+        if (need > e->compose_dev.bytes)
+            HIPCHK(e, hipStreamSynchronize(e->stream));          /* launches of earlier calls still read the old table */
+        { const int rc = scratch_reserve(e, &e->compose_dev, need); if (rc) return rc; }
+        OhEngine::Stage *sg = stage_acquire(e, need);
+        if (!sg)
+            FAIL(e, OH_E_NOMEM, "oh_pics_compose: no staging buffer for %zu bytes of layer table", need);
+        memset(sg->p, 0, lay_bytes);
+        memcpy(sg->p, lay.data(), (size_t)nl * sizeof(OhCpsLayer));
+        OhCpsSrc *hs = (OhCpsSrc *)((char *)sg->p + lay_bytes);
+        for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
+            const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+            for (int j = 0; j < nl; j++) {
+                const OhLayer &l = cp->layers[which[j]];
+                for (int i = 0; i < m; i++) {
+                    const Pic *s = get_pic(e, l.src_ids[i0 + i]);
+                    OhCpsSrc &t = hs[(size_t)nl * i0 + (size_t)j * m + i];
+                    for (int c = 0; c < 3; c++) t.p[c] = c < np ? final_planes(s)[c] : nullptr;
+                    t.alpha = l.alpha ? (const uint8_t *)l.alpha + (size_t)(i0 + i) * (size_t)l.alpha_image_stride : nullptr;
+                }
+            }
+        }
+        HIPCHK(e, hipMemcpyAsync(e->compose_dev.p, sg->p, need, hipMemcpyHostToDevice, e->stream));
+        { const int rc = stage_in_use(e, sg, e->stream); if (rc) return rc; }
+    }
+    a.n_layers = nl;
+    a.layers = (const OhCpsLayer *)e->compose_dev.p;
+    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
+        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+        for (int i = 0; i < m; i++) {
+            const Pic *q = get_pic(e, dst_ids[i0 + i]);
+            for (int c = 0; c < np; c++) a.dst[i][c] = final_planes(q)[c];
+        }
+        a.srcs = nl ? (const OhCpsSrc *)((const char *)e->compose_dev.p + lay_bytes) + (size_t)nl * i0 : nullptr;
+        a.n_pics = m;
+        ohk_compose(&a, m, e->stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    return OH_OK;
 }
 
 extern "C" int oh_pic_device_planes(OhEngine *e, int pic_id, void *planes[3], int32_t stride[3], int32_t width[3], int32_t height[3])

@@ -108,6 +108,41 @@ struct OhCmpArgs {
     int32_t     ssim;                /* 1: OH_CMP_SSIM */
 };
 
+/* picture composition (compose.hip): the finished halves of the destinations of one launch set by value in the kernel
+ * arguments, two plane classes (0 luma, 1 chroma) with the area the call touches and its tiling, and the layers in device memory that
+ * the engine owns and fills on the stream in front of the launches: the layers that are not wholly outside, in list order, with their
+ * geometry in both classes, then per layer and destination of the launch set the source's finished planes and the alpha plane. */
+enum { OH_CPS_TW = 64,               /* 16-byte granules of a destination row per workgroup tile: a wave takes one row of them */
+       OH_CPS_TH = 4 };              /* rows per tile */
+struct OhCpsLayer {                  /* [class] where a member has two entries */
+    int32_t x0[2], y0[2], x1[2], y1[2];  /* the rectangle clipped to the destination plane, plane samples: [x0, x1) x [y0, y1) */
+    int32_t ox[2], oy[2];            /* source sample = destination sample + (ox, oy) */
+    int32_t dx[2], dy[2];            /* where the unclipped rectangle starts in the destination plane: the origin of the alpha plane */
+    int32_t spitch[2];               /* bytes between rows of the source's planes */
+    int32_t opacity;                 /* 0 .. 256 */
+    int32_t has_alpha;
+    int64_t a_ps, a_rs;              /* bytes from one luma alpha to the next, from one row of them to the next */
+};
+struct OhCpsSrc {
+    const void    *p[3];             /* the source's finished planes */
+    const uint8_t *alpha;            /* the alpha of this destination's rectangle sample (0, 0); not read without has_alpha */
+};
+struct OhCpsClass {
+    int32_t gx0, gx1, y0, y1;        /* the touched area: granules [gx0, gx1) of rows [y0, y1) */
+    int32_t tx, ty;                  /* tiles across and down */
+};
+struct OhCpsArgs {
+    void             *dst[64][3];    /* OH_CONV_MAX_PICS destinations x planes: the finished halves */
+    const OhCpsLayer *layers;        /* [n_layers] */
+    const OhCpsSrc   *srcs;          /* [n_layers][n_pics] */
+    OhCpsClass        k[2];
+    int32_t           pitch[3];      /* bytes between rows of each destination plane */
+    int32_t           np, bd, cf;    /* planes: 1 or 3; bit depth; chroma_format_idc */
+    int32_t           n_layers, n_pics;
+    int32_t           fill;          /* 1: every sample starts as fill_v[plane] and the destination is not read */
+    int32_t           fill_v[3];
+};
+
 /* picture resizing (resize.hip): what one launch set needs, by value in the kernel arguments like OhConvArgs.  Two plane
  * classes (0 luma, 1 chroma), each with its own geometry and tap tables; the tables live in device memory that the engine owns and
  * fills (engine_pics.hip: oh_pics_resize) on the stream in front of the launches. */
@@ -157,6 +192,8 @@ void ohk_colour(const OhColArgs *a, int format, int sample, int n, hipStream_t s
 void ohk_light(const OhLightArgs *a, int n, hipStream_t st);
 /* n pairs of a.a / a.b into a.res[0 .. 3 n OH_CMP_SLOTS) */
 void ohk_compare(const OhCmpArgs *a, int n, hipStream_t st);
+/* n destinations of a.dst, composed in place: a.layers over what they hold, or over a.fill_v */
+void ohk_compose(const OhCpsArgs *a, int n, hipStream_t st);
 void ohk_hash(int kind, const OhMd5Job *jobs, const uint32_t *first, const uint32_t *task_map, int n_jobs, int n_tasks, uint32_t *partials,
               uint32_t *out, hipStream_t st);
 void ohk_inter(const OhBatch *B, int n, const OhPicParams *p, uint32_t max_luma, uint32_t max_chroma, hipStream_t st);

@@ -282,6 +282,42 @@ def resize_taps(src_extent, dst_extent, filter="bilinear", phase=2):
     return [(int(first[x]), [int(v) for v in k[x, :cnt[x]]]) for x in range(dst_extent)]
 
 
+COMPOSE_MAX_LAYERS, COMPOSE_FILL = 16, 1                                                # OH_COMPOSE_MAX_LAYERS, OH_COMPOSE_FILL
+CPS_TW, CPS_TH = 64, 4                                                                  # OH_CPS_TW, OH_CPS_TH (csrc/kernels.h): the kernel's tile, 16-byte granules x rows
+
+
+class OhLayer(C.Structure):                                   # include/ohevc_hip.h
+    _fields_ = [("src_ids", C.POINTER(C.c_int32)), ("sx", C.c_int32), ("sy", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
+                ("dx", C.c_int32), ("dy", C.c_int32), ("opacity", C.c_int32), ("alpha", C.c_void_p),
+                ("alpha_pixel_stride", C.c_int64), ("alpha_row_stride", C.c_int64), ("alpha_image_stride", C.c_int64)]
+
+
+class OhCompose(C.Structure):                                 # include/ohevc_hip.h
+    _fields_ = [("flags", C.c_int32), ("fill", C.c_int32 * 3), ("n_layers", C.c_int32), ("layers", C.POINTER(OhLayer))]
+
+
+class Layer:
+    """one layer of Engine.pics_compose: src, a finished picture's id for every destination or a list of one id per destination;
+    rect = (sx, sy, w, h) of the source in luma samples (None: its whole coded size); at = (dx, dy), where the rectangle's top left
+    goes in the destination (may be negative or reach beyond: clipped); opacity 0 .. 256; alpha, None or a torch uint8 tensor on the
+    engine's device of shape (h, w), shared by the destinations, or (n, h, w), with any non-negative strides (rgba[..., 3] of an
+    image works as it is): straight alpha, one value per luma sample of the rectangle"""
+    __slots__ = ("src", "rect", "at", "opacity", "alpha")
+
+    def __init__(self, src, rect=None, at=(0, 0), opacity=256, alpha=None):
+        self.src, self.rect, self.at, self.opacity, self.alpha = src, rect, at, opacity, alpha
+
+
+def compose_blend(dst, src, alpha, opacity):
+    """oh_compose_blend (host only): (src w + dst (65280 - w) + 32640) / 65280 with w = alpha opacity, by the function the kernel evaluates"""
+    return int(lib().oh_compose_blend(int(dst), int(src), int(alpha), int(opacity)))
+
+
+def compose_chroma_alpha(chroma_format_idc, a00, a01, a10, a11):
+    """oh_compose_chroma_alpha (host only): the alpha of a chroma sample from the luma alphas it covers"""
+    return int(lib().oh_compose_chroma_alpha(int(chroma_format_idc), int(a00), int(a01), int(a10), int(a11)))
+
+
 def convert_image_bytes(params, cv):
     """oh_convert_image_bytes (host only): bytes of one image, 0 when the combination is not valid"""
     return int(lib().oh_convert_image_bytes(C.byref(params), C.byref(cv)))
@@ -372,6 +408,11 @@ def lib():
         L.oh_compare_ssim_window.restype = C.c_int64
         L.oh_compare_psnr.argtypes = [C.c_uint64, C.c_uint64, I]
         L.oh_compare_psnr.restype = C.c_double
+        L.oh_pics_compose.argtypes = [V, C.POINTER(C.c_int), I, C.POINTER(OhCompose)]
+        L.oh_compose_blend.argtypes = [C.c_uint32] * 4
+        L.oh_compose_blend.restype = C.c_uint32
+        L.oh_compose_chroma_alpha.argtypes = [I] + [C.c_uint32] * 4
+        L.oh_compose_chroma_alpha.restype = C.c_uint32
         L.oh_pics_resize.argtypes = [V, C.POINTER(C.c_int), C.POINTER(C.c_int), I, C.POINTER(OhResize)]
         L.oh_resize_taps.argtypes = [I, I, I, I, C.POINTER(C.c_int32), C.POINTER(C.c_int16), I, C.POINTER(C.c_int)]
         L.oh_resize_max_taps.argtypes = [I, I, I]
@@ -778,6 +819,73 @@ class Engine:
         self._chk(rc, "oh_pics_resize")
         dp = self._pic_params(out[0])
         return out, (0, dp.width - width, 0, dp.height - height)
+
+    def pics_compose(self, dst, layers, *, fill=None):
+        """finished pictures composed in place on the GPU (oh_pics_compose): dst, the destination ids (identical params); layers, a
+        list of at most COMPOSE_MAX_LAYERS Layer applied in order, source over destination with straight alpha in code values; fill,
+        None or the (Y, Cb, Cr) sample values every coded plane starts from instead of what the destination holds (a 4:0:0 picture
+        reads the first only).  Without fill only the bounding box of the layers is touched.  Ordered with torch both ways like
+        pics_import: the engine stream waits for torch's current stream before it reads the alpha tensors, torch's current stream waits
+        for the engine stream afterwards, so they may be freed or overwritten at once.  Returns the destination ids; does not wait on
+        the host."""
+        dst = list(dst)
+        layers = list(layers)
+        n = len(dst)
+        keep = []                                             # what the C structures point at
+        ol = (OhLayer * max(len(layers), 1))()
+        torch = None
+        if any(l.alpha is not None for l in layers):
+            import torch
+            if not _torch_first:
+                raise EngineError("Engine.pics_compose: import torch before the first Engine is created (the engine must share torch's "
+                                  "HIP runtime to read its tensors)")
+        elif _torch_first:
+            import torch
+        dev = torch.device("cuda", self.device) if torch is not None else None
+        for k, l in enumerate(layers):
+            src = list(l.src) if isinstance(l.src, (list, tuple)) else [int(l.src)] * n
+            if len(src) != n:
+                raise ValueError(f"layer {k}: {len(src)} sources for {n} destinations")
+            ids = (C.c_int32 * max(n, 1))(*src)
+            keep.append(ids)
+            if l.rect is None:
+                sp = self._pic_params(src[0]) if n else None
+                rect = (0, 0, sp.width, sp.height) if n else (0, 0, 0, 0)
+            else:
+                rect = tuple(int(v) for v in l.rect)
+            o = ol[k]
+            o.src_ids = C.cast(ids, C.POINTER(C.c_int32))
+            o.sx, o.sy, o.w, o.h = rect
+            o.dx, o.dy = int(l.at[0]), int(l.at[1])
+            o.opacity = int(l.opacity)
+            if l.alpha is not None:
+                t = l.alpha
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.device != dev or t.dim() not in (2, 3):
+                    raise ValueError(f"layer {k}: alpha: want a torch uint8 tensor of shape (h, w) or (n, h, w) on {dev}")
+                if tuple(t.shape[-2:]) != (rect[3], rect[2]) or (t.dim() == 3 and t.shape[0] != n):
+                    raise ValueError(f"layer {k}: alpha of shape {tuple(t.shape)} for {n} rectangles of {rect[2]} x {rect[3]}")
+                st = t.stride()
+                if any(s < 0 for s in st):
+                    raise ValueError(f"layer {k}: alpha with negative strides {st}")
+                keep.append(t)
+                o.alpha = t.data_ptr()
+                o.alpha_pixel_stride, o.alpha_row_stride = st[-1], st[-2]
+                o.alpha_image_stride = st[0] if t.dim() == 3 else 0
+        cp = OhCompose(COMPOSE_FILL if fill is not None else 0, (C.c_int32 * 3)(*([int(v) for v in fill] + [0, 0])[:3] if fill is not None else (0, 0, 0)),
+                       len(layers), ol)
+        same = True
+        if torch is not None:
+            cur = torch.cuda.current_stream(dev)
+            same = (self.stream() or 0) == cur.cuda_stream    # an engine created on torch's current stream: nothing to order
+        if not same:
+            if self._torch_stream is None:
+                self._torch_stream = torch.cuda.ExternalStream(self.stream() or 0, device=dev)
+            es = self._torch_stream
+            es.wait_stream(cur)                               # the kernels that produce the alpha planes are queued on torch's stream
+        self._chk(self.L.oh_pics_compose(self.h, (C.c_int * max(n, 1))(*dst), n, C.byref(cp)), "oh_pics_compose")
+        if not same:
+            cur.wait_stream(es)                               # whatever torch does with the tensors later is ordered behind the read
+        return dst
 
     def _pic_params(self, pid):
         p = self._params.get(pid)
