@@ -10,7 +10,7 @@
  *   3. primaries      3 x 3 in Q20 with 64-bit sums, clipped to [0, 2^30]
  *   4. output         LINEAR: one int-to-float conversion and one f32 multiply; SRGB / GAMMA24: the code looked up in B
  * G and B are piecewise-logarithmic (64 segments per octave above 128, every integer below).  No floating-point library function and
- * no float expression the compiler could contract: the tables are built on the host (engine_pics.hip: oh_colour_tables).
+ * no float expression the compiler could contract: the tables are built on the host (pics_math.hip: oh_colour_tables).
  *
  * The three tables (29 KB) live in LDS beside the staging arrays.  A workgroup loads them once and converts OH_COL_ROWS image rows of
  * its segment, so the table loads (out of L2) stay a fraction of the pixel traffic.  Stages 2 and 3 are skipped (uniform branches)

@@ -1,6 +1,6 @@
 /*
  * compare_common.h — the SSIM window formula of DESIGN.md §3f, one function for the kernel (compare.hip) and for the host's
- * oh_compare_ssim_window (engine_pics.hip), so that the CPU tests pin what the GPU evaluates.
+ * oh_compare_ssim_window (pics_math.hip), so that the CPU tests pin what the GPU evaluates.
  */
 #ifndef OHEVC_COMPARE_COMMON_H
 #define OHEVC_COMPARE_COMMON_H

@@ -1,6 +1,6 @@
 /*
  * compose_common.h — the two integer formulas of DESIGN.md §3h, one definition for the kernel (compose.hip) and for the host's
- * oh_compose_blend / oh_compose_chroma_alpha (engine_pics.hip), so that the CPU tests pin what the GPU evaluates.
+ * oh_compose_blend / oh_compose_chroma_alpha (pics_math.hip), so that the CPU tests pin what the GPU evaluates.
  */
 #ifndef OHEVC_COMPOSE_COMMON_H
 #define OHEVC_COMPOSE_COMMON_H

@@ -1,8 +1,8 @@
 /*
  * engine.hip — host side of the MI355X engine: device-resident pictures (the DPB lives in HBM), staging buffers,
  * pass scheduling on one HIP stream, release of executed work lists, per-pass event timing.  Work lists are handed over
- * in engine_handover.hip; what runs on finished pictures beside that path is in engine_pics.hip and engine_shvc.hip;
- * engine_impl.h is what they share.
+ * in engine_handover.hip; what runs on finished pictures beside that path is in engine_pics.hip (its engine-free arithmetic in
+ * pics_math.hip) and engine_shvc.hip; engine_impl.h is what they share.
  * C ABI in include/ohevc_hip.h.  No CPU fallback exists: without a usable device every entry
  * point returns OH_E_HIP.
  */
@@ -184,13 +184,9 @@ extern "C" void oh_engine_destroy(OhEngine *e)
     for (auto *c : e->dl_stages) { (void)hipEventDestroy(c->done); (void)hipHostFree(c->p); delete c; }
     if (e->kerr) (void)hipHostFree(e->kerr);
     if (e->tickets) (void)hipFree(e->tickets);
-    if (e->hash_dev.p) (void)hipFree(e->hash_dev.p);
-    if (e->resize_dev.p) (void)hipFree(e->resize_dev.p);
-    if (e->colour_dev.p) (void)hipFree(e->colour_dev.p);
-    if (e->light_dev.p) (void)hipFree(e->light_dev.p);
-    if (e->light_res.p) (void)hipFree(e->light_res.p);
-    if (e->compare_res.p) (void)hipFree(e->compare_res.p);
-    if (e->compose_dev.p) (void)hipFree(e->compose_dev.p);
+    for (const OhEngine::Scratch *s : { &e->hash_dev, &e->resize_dev, &e->colour_tabs.dev, &e->light_tabs.dev, &e->light_res, &e->compare_res,
+                                        &e->compose_dev })
+        if (s->p) (void)hipFree(s->p);
     for (auto &ev : e->batch_ev) if (ev) (void)hipEventDestroy(ev);
     if (e->dl_stream) { (void)hipStreamSynchronize(e->dl_stream); (void)hipStreamDestroy(e->dl_stream); }
     if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);

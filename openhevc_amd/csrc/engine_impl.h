@@ -2,7 +2,8 @@
  * engine_impl.h — what the engine's translation units share: the engine and picture structures, the error macros and the few
  * helpers more than one of them uses.  engine.hip: engine and picture lifecycle, staging buffers, passes, profiling;
  * engine_handover.hip: work-list hand-over and the arena pool; engine_pics.hip: plane transfers, hashes, conversion, import, measurement,
- * comparison, resizing and composition of finished pictures; engine_shvc.hip: SHVC up-sampling.
+ * comparison, resizing and composition of finished pictures, with the helpers those services share; engine_shvc.hip: SHVC up-sampling.
+ * pics_math.hip, the services' host arithmetic, takes no engine and does not include this file (pics_math.h).
  * Internal: the C ABI is include/ohevc_hip.h.
  */
 #ifndef OHEVC_ENGINE_IMPL_H
@@ -202,20 +203,19 @@ struct OhEngine {
     struct Scratch { void *p = nullptr; size_t bytes = 0; };
     Scratch     hash_dev;                /* oh_pics_hash (CRC / checksum): the job table, its tasks and their values in HBM */
     Scratch     resize_dev;              /* oh_pics_resize: the tap tables of the call, then the int16 intermediate of one launch set */
-    Scratch     colour_dev;              /* oh_pics_convert_colour: the three tables of the call (OH_COLT_N int32) */
-    /* the tables of the last OhColour a call built (the host's work: a few thousand pow calls); colour_on_dev: the device copy holds
-     * them too, so a call with the same OhColour copies nothing */
-    OhColour    colour_last;
-    bool        colour_cached = false, colour_on_dev = false;
-    std::vector<int32_t> colour_tab;     /* OH_COLT_N, laid out as on the device */
-    int32_t     colour_misc[OH_COL_NMISC];
-    /* oh_pics_light_level: table A of its last source curve, host and device, apart from colour_* (neither call disturbs the tables
-     * the other has cached), and the results of the call in HBM */
-    Scratch     light_dev, light_res;
-    OhColour    light_last;
-    bool        light_cached = false, light_on_dev = false;
-    std::vector<int32_t> light_tab;      /* OH_COLT_N as colour_build lays them out; OH_COLT_G of them go to the device */
-    int32_t     light_misc[OH_COL_NMISC];
+    /* the tables of the last OhColour a service built (the host's work: a few thousand pow calls), host and device
+     * (engine_pics.hip: table_stage); on_dev: the device copy holds them too, so a call with the same OhColour copies nothing */
+    struct TableCache {
+        OhColour last;
+        bool     cached = false, on_dev = false;
+        std::vector<int32_t> tab;        /* OH_COLT_N as colour_build lays them out; the entries the service reads go to the device */
+        int32_t  misc[OH_COL_NMISC];
+        Scratch  dev;
+    };
+    TableCache  colour_tabs;             /* oh_pics_convert_colour: the three tables of the call (OH_COLT_N int32) */
+    TableCache  light_tabs;              /* oh_pics_light_level: table A of its last source curve (OH_COLT_G int32), apart from colour_tabs:
+                                          * neither call disturbs the tables the other has cached */
+    Scratch     light_res;               /* oh_pics_light_level: the results of the call in HBM */
     Scratch     compare_res;             /* oh_pics_compare: the results of the call in HBM */
     Scratch     compose_dev;             /* oh_pics_compose: the layer table of the call (OhCpsLayer, then OhCpsSrc per launch set) */
     uint32_t    spin_limit = 1u << 22;   /* polls (with s_sleep between them, ~1 s in all) before a waiting workgroup gives up; OHEVC_SPIN_LIMIT */

@@ -3,12 +3,11 @@
  * hash.hip, convert.hip, import.hip, colour.hip, light.hip, compare.hip, resize.hip and compose.hip): plane upload and download, the two-phase
  * window fetch, picture hashes, conversion to YUV / RGB images and back, with the colour tables of the HDR forms, light-level statistics,
  * comparison of two pictures, resizing into engine pictures, and composition of pictures in place: fill, overlay, alpha blend.
+ * Their arithmetic, which needs neither an engine nor a device, is pics_math.hip; the helpers at the top are what the services share.
  */
 #include <cmath>
-#include <limits>
 #include "engine_impl.h"
-#include "compare_common.h"
-#include "compose_common.h"
+#include "pics_math.h"
 
 /* at least `bytes` of device scratch, grow-only in 1 MiB steps.  Growing frees the old block: the caller has made sure that nothing
  * enqueued still uses it. */
@@ -24,24 +23,6 @@ static int scratch_reserve(OhEngine *e, OhEngine::Scratch *s, size_t bytes)
     return OH_OK;
 }
 
-/* a crop window of a picture: offsets not negative, something left and — aligned — the offsets multiples of the chroma sub-sampling.
- * false: *why says what is wrong. */
-static bool crop_window_ok(const OhPicParams *p, const OhWindow &w, bool aligned, std::string *why)
-{
-    const int cf = p->chroma_format_idc, sw = aligned && (cf == 1 || cf == 2) ? 2 : 1, sh = aligned && cf == 1 ? 2 : 1;
-    const int W = p->width - w.left - w.right, H = p->height - w.top - w.bottom;
-    if (w.left >= 0 && w.right >= 0 && w.top >= 0 && w.bottom >= 0 && W > 0 && H > 0 && !(w.left % sw) && !(w.right % sw) && !(w.top % sh) && !(w.bottom % sh))
-        return true;
-    char buf[256];
-    if (aligned)
-        snprintf(buf, sizeof(buf), "window (%d,%d,%d,%d) of %dx%d: empty, or offsets not multiples of %dx%d", w.left, w.right, w.top, w.bottom,
-                 p->width, p->height, sw, sh);
-    else
-        snprintf(buf, sizeof(buf), "window (%d,%d,%d,%d) leaves nothing of %dx%d", w.left, w.right, w.top, w.bottom, p->width, p->height);
-    *why = buf;
-    return false;
-}
-
 /* the first of n pictures (ids checked) whose params differ from those of the first; n: all are equal */
 static int first_other_params(OhEngine *e, const int *pic_ids, int n)
 {
@@ -49,6 +30,118 @@ static int first_other_params(OhEngine *e, const int *pic_ids, int n)
         if (memcmp(&get_pic(e, pic_ids[i])->p, &get_pic(e, pic_ids[0])->p, sizeof(OhPicParams)))
             return i;
     return n;
+}
+
+/* ---------------- what the services share ---------------- */
+/* the first of n pictures that are known and all have its params; nullptr: they are not (OH_E_ARG, the message set) */
+static const Pic *alike_pics(OhEngine *e, const char *who, const int *pic_ids, int n)
+{
+    if (check_pics(e, pic_ids, n, who))
+        return nullptr;
+    const int other = first_other_params(e, pic_ids, n);
+    if (other < n)
+        FAIL(e, nullptr, "%s: picture %d has other params than picture %d", who, pic_ids[other], pic_ids[0]);
+    return get_pic(e, pic_ids[0]);
+}
+
+/* the destinations of a call in rising order (what its search for a picture that is also a source takes); none may be listed twice */
+static int distinct_dsts(OhEngine *e, const char *who, const int *dst_ids, int n, std::vector<int> *sorted)
+{
+    *sorted = std::vector<int>(dst_ids, dst_ids + n);
+    std::sort(sorted->begin(), sorted->end());
+    if (std::adjacent_find(sorted->begin(), sorted->end()) != sorted->end())
+        FAIL(e, OH_E_ARG, "%s: a destination is listed twice", who);
+    return OH_OK;
+}
+
+/* the bytes from ptr to the end of its allocation; ROOM_NONE: ptr is not device memory of the engine's device (the current one);
+ * ROOM_UNKNOWN: it is, but the runtime cannot tell its extent — callers let such memory pass */
+enum : size_t { ROOM_NONE = 0, ROOM_UNKNOWN = ~(size_t)0 };
+static size_t device_room(OhEngine *e, const void *ptr)
+{
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, ptr) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->device) {
+        (void)hipGetLastError();
+        return ROOM_NONE;
+    }
+    void *base = nullptr; size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(ptr)) == hipSuccess)
+        return (size_t)((const char *)base + size - (const char *)ptr);
+    (void)hipGetLastError();
+    return ROOM_UNKNOWN;
+}
+
+/* the caller's images (`what`: "dst" or "src"): n of ib bytes, image_stride apart, of sb-byte samples, in `bytes` bytes of device memory at p */
+static int image_run_check(OhEngine *e, const char *who, const char *what, const void *p, int n, size_t ib, size_t sb, size_t image_stride, size_t bytes)
+{
+    if (image_stride < ib || image_stride % sb || (uintptr_t)p % sb)
+        FAIL(e, OH_E_ARG, "%s: image_stride %zu (an image takes %zu bytes) or %s not a multiple of the %zu-byte sample", who, image_stride, ib, what, sb);
+    if (!p || ib > bytes || (size_t)(n - 1) > (bytes - ib) / image_stride)
+        FAIL(e, OH_E_ARG, "%s: %d images of %zu bytes, %zu apart, do not fit %zu bytes", who, n, ib, image_stride, bytes);
+    const size_t total = (size_t)(n - 1) * image_stride + ib;
+    HIPCHK(e, hipSetDevice(e->device));
+    const size_t room = device_room(e, p);
+    if (room == ROOM_NONE)
+        FAIL(e, OH_E_ARG, "%s: %s is not device memory of device %d", who, what, e->device);
+    if (room != ROOM_UNKNOWN && total > room)
+        FAIL(e, OH_E_ARG, "%s: %zu bytes at %s run past the end of its allocation", who, total, what);
+    return OH_OK;
+}
+
+/* what a conversion kernel takes of the pictures' layout (all alike: p0) and of the OhConvert's window and chroma filter */
+static void conv_args(OhConvArgs *a, const Pic *p0, const OhConvert *cv)
+{
+    const OhPicParams &p = p0->p;
+    for (int c = 0; c < 3; c++) a->pitch[c] = p0->stride[c] * sample_bytes(p.bit_depth);
+    a->cw = p0->w[1]; a->ch = p0->h[1];
+    a->left = cv->win.left; a->top = cv->win.top;
+    a->W = p.width - cv->win.left - cv->win.right; a->H = p.height - cv->win.top - cv->win.bottom;
+    a->cf = p.chroma_format_idc; a->bd = p.bit_depth; a->filter = cv->chroma_filter;
+}
+
+/* the first n_entries table entries of col in tc's device copy, in front of the launches that follow: built on the host unless col is the
+ * cache's last, then staged in a pinned buffer and copied on the engine stream — behind earlier launches that read the device copy */
+static int table_stage(OhEngine *e, OhEngine::TableCache *tc, const OhColour *col, int n_entries, const char *who)
+{
+    if (!tc->cached || memcmp(&tc->last, col, sizeof(*col))) {
+        tc->cached = false;
+        tc->tab.resize((size_t)OH_COLT_N);
+        std::string why;
+        const int rc = colour_build(col, tc->tab.data(), tc->misc, &why);
+        if (rc) FAIL(e, rc, "%s: %s", who, why.c_str());
+        tc->last = *col; tc->cached = true; tc->on_dev = false;
+    }
+    const size_t bytes = (size_t)n_entries * sizeof(int32_t);
+    { const int rc = scratch_reserve(e, &tc->dev, bytes); if (rc) return rc; }           /* the first call's: a cache always asks for as much */
+    if (!tc->on_dev) {
+        OhEngine::Stage *sg = stage_acquire(e, bytes);
+        if (!sg)
+            FAIL(e, OH_E_NOMEM, "%s: no staging buffer for %zu bytes of table%s", who, bytes, n_entries == OH_COLT_N ? "s" : "");
+        memcpy(sg->p, tc->tab.data(), bytes);
+        HIPCHK(e, hipMemcpyAsync(tc->dev.p, sg->p, bytes, hipMemcpyHostToDevice, e->stream));
+        { const int rc = stage_in_use(e, sg, e->stream); if (rc) return rc; }
+        tc->on_dev = true;
+    }
+    return OH_OK;
+}
+
+/* the results of a call that ends with a wait.  begin: `bytes` of device scratch in s (the old buffer is idle), cleared on the engine stream
+ * in front of the launches, and a pinned buffer; fetch: the copy into it, the one stream wait, and what a kernel that gave up has latched */
+static int results_begin(OhEngine *e, const char *who, OhEngine::Scratch *s, size_t bytes, int n, OhEngine::Stage **sg)
+{
+    { const int rc = scratch_reserve(e, s, bytes); if (rc) return rc; }
+    *sg = stage_acquire(e, bytes);
+    if (!*sg)
+        FAIL(e, OH_E_NOMEM, "%s: no staging buffer for %d results", who, n);
+    HIPCHK(e, hipMemsetAsync(s->p, 0, bytes, e->stream));
+    return OH_OK;
+}
+
+static int results_fetch(OhEngine *e, const OhEngine::Scratch *s, size_t bytes, OhEngine::Stage *sg)
+{
+    HIPCHK(e, hipMemcpyAsync(sg->p, s->p, bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return kernel_error(e);
 }
 
 extern "C" int oh_pic_upload(OhEngine *e, int pic_id, const uint8_t *const planes[3], const ptrdiff_t strides[3])
@@ -349,105 +442,47 @@ extern "C" int oh_pics_hash(OhEngine *e, const int *pic_ids, int n, int hash_typ
 }
 
 /* ---------------- conversion to standard images (convert.hip) ---------------- */
-static int conv_sample_bytes(const OhConvert *cv, int bit_depth)
-{
-    switch (cv->sample) {
-    case OH_CONV_NATIVE: return sample_bytes(bit_depth);
-    case OH_CONV_U8:     return 1;
-    case OH_CONV_F32:    return 4;
-    default:             return 2;
-    }
-}
-
-/* what oh_pics_convert checks of the combination itself (not of pictures or memory); *bytes: one image */
-static int conv_check(const OhPicParams *p, const OhConvert *cv, size_t *bytes, std::string *why)
-{
-    char buf[256];
-    if (!p || !cv) { *why = "no params or no OhConvert"; return OH_E_ARG; }
-    const int cf = p->chroma_format_idc, bd = p->bit_depth;
-    if (p->width <= 0 || p->height <= 0 || cf < 0 || cf > 3 || (bd != 8 && bd != 9 && bd != 10 && bd != 12)) {
-        *why = "bad picture params"; return OH_E_ARG;
-    }
-    if (cv->format < OH_CONV_PLANAR || cv->format > OH_CONV_RGBA || cv->sample < OH_CONV_NATIVE || cv->sample > OH_CONV_F32) {
-        snprintf(buf, sizeof(buf), "format %d / sample %d unknown", cv->format, cv->sample); *why = buf; return OH_E_UNSUPPORTED;
-    }
-    const bool yuv = cv->format <= OH_CONV_SEMIPLANAR;
-    if (yuv ? cv->sample > OH_CONV_U8 : cv->sample == OH_CONV_NATIVE) {
-        snprintf(buf, sizeof(buf), "sample %d does not fit format %d (YUV: NATIVE or U8; RGB: U8, U16, F16, F32)", cv->sample, cv->format);
-        *why = buf; return OH_E_UNSUPPORTED;
-    }
-    if (!yuv && cv->matrix != 1 && cv->matrix != 5 && cv->matrix != 6 && cv->matrix != 9) {
-        snprintf(buf, sizeof(buf), "matrix_coefficients %d (1 BT.709, 5 / 6 BT.601, 9 BT.2020 NCL)", cv->matrix); *why = buf; return OH_E_UNSUPPORTED;
-    }
-    if (cv->format == OH_CONV_SEMIPLANAR && cf == 0) { *why = "a 4:0:0 picture has no semi-planar form"; return OH_E_UNSUPPORTED; }
-    if ((cv->full_range != 0 && cv->full_range != 1) || (cv->chroma_filter != 0 && cv->chroma_filter != 1)) {
-        *why = "full_range and chroma_filter are 0 or 1"; return OH_E_ARG;
-    }
-    if (!crop_window_ok(p, cv->win, true, why))
-        return OH_E_ARG;
-    const int sw = (cf == 1 || cf == 2) ? 2 : 1, sh = cf == 1 ? 2 : 1;
-    const int W = p->width - cv->win.left - cv->win.right, H = p->height - cv->win.top - cv->win.bottom;
-    size_t samples;
-    if (cv->format <= OH_CONV_SEMIPLANAR)
-        samples = (size_t)W * H + (cf ? 2 * (size_t)(W / sw) * (H / sh) : 0);
-    else
-        samples = (size_t)W * H * (cv->format == OH_CONV_RGBA ? 4 : 3);
-    *bytes = samples * (size_t)conv_sample_bytes(cv, bd);
-    return OH_OK;
-}
-
-extern "C" size_t oh_convert_image_bytes(const OhPicParams *p, const OhConvert *cv)
-{
-    size_t bytes = 0;
-    std::string why;
-    return conv_check(p, cv, &bytes, &why) == OH_OK ? bytes : 0;
-}
-
-/* the integers of an RGB conversion: R = clamp((cy (Y - yoff) + crv (Cr - mid) + 2^(S-1)) >> S, 0, 2^D - 1), G with cgu, cgv, B with
- * cbu; each coefficient round(2^S (2^D - 1) entry / scale) of the H.273 inverse matrix, S the largest shift that keeps every term and
- * every sum inside int32 for all samples of bit_depth bits */
-extern "C" int oh_convert_coeffs(const OhConvert *cv, int bit_depth, int32_t *out, int n)
-{
-    if (!cv || !out || n < OH_CONV_NCOEFFS || (bit_depth != 8 && bit_depth != 9 && bit_depth != 10 && bit_depth != 12))
-        return OH_E_ARG;
-    if (cv->format < OH_CONV_RGB_PLANAR || cv->format > OH_CONV_RGBA || cv->sample < OH_CONV_U8 || cv->sample > OH_CONV_F32)
-        return OH_E_UNSUPPORTED;
-    double kr, kb;
-    switch (cv->matrix) {
-    case 1:  kr = 0.2126; kb = 0.0722; break;
-    case 5:
-    case 6:  kr = 0.299;  kb = 0.114;  break;
-    case 9:  kr = 0.2627; kb = 0.0593; break;
-    default: return OH_E_UNSUPPORTED;
-    }
-    if (cv->full_range != 0 && cv->full_range != 1)
-        return OH_E_ARG;
-    const int B = bit_depth, D = cv->sample == OH_CONV_U8 ? 8 : 16;
-    const double kg = 1.0 - kr - kb, full = (double)((1 << B) - 1), unit = (double)(1 << (B - 8));
-    const double ys = cv->full_range ? full : 219.0 * unit, cs = cv->full_range ? full : 224.0 * unit;
-    const int yoff = cv->full_range ? 0 : 16 << (B - 8), mid = 1 << (B - 1);
-    const double ent[5] = { 1.0 / ys, 2.0 * (1.0 - kr) / cs, -2.0 * kb * (1.0 - kb) / (kg * cs), -2.0 * kr * (1.0 - kr) / (kg * cs),
-                            2.0 * (1.0 - kb) / cs };              /* cy, crv, cgu, cgv, cbu */
-    const int64_t dy = std::max(yoff, (1 << B) - 1 - yoff), dc = mid;   /* largest |Y - yoff|, |C - mid| */
-    const double scale = (double)((1 << D) - 1);
-    for (int S = 30; S >= 1; S--) {
-        int64_t c[5];
-        for (int i = 0; i < 5; i++) c[i] = llround(ldexp(scale * ent[i], S));
-        const int64_t r = (int64_t)1 << (S - 1), ty = std::llabs(c[0]) * dy;
-        const int64_t worst = std::max({ ty + std::llabs(c[1]) * dc + r, ty + (std::llabs(c[2]) + std::llabs(c[3])) * dc + r,
-                                         ty + std::llabs(c[4]) * dc + r });
-        if (worst > INT32_MAX)
-            continue;
-        for (int i = 0; i < 5; i++) out[i] = (int32_t)c[i];
-        out[5] = yoff; out[6] = mid; out[7] = S; out[8] = D;
-        return OH_OK;
-    }
-    return OH_E_UNSUPPORTED;
-}
-
 /* oh_pics_convert and oh_pics_convert_colour (col set: its tables are staged in front of the launches, which are colour.hip's) */
 static int pics_convert(OhEngine *e, const char *who, const int *pic_ids, int n, const OhConvert *cv, const OhColour *col, void *dst,
-                        size_t image_stride, size_t dst_bytes);
+                        size_t image_stride, size_t dst_bytes)
+{
+    const Pic *p0 = alike_pics(e, who, pic_ids, n);
+    if (!p0) return OH_E_ARG;
+    size_t ib = 0;
+    std::string why;
+    { const int rc = conv_check(&p0->p, cv, &ib, &why); if (rc) FAIL(e, rc, "%s: %s", who, why.c_str()); }
+    { const int rc = image_run_check(e, who, "dst", dst, n, ib, (size_t)conv_sample_bytes(cv, p0->p.bit_depth), image_stride, dst_bytes); if (rc) return rc; }
+    OhColArgs ca;
+    OhConvArgs &a = ca.c;
+    memset(&ca, 0, sizeof(ca));
+    conv_args(&a, p0, cv);
+    a.nc = cv->format == OH_CONV_RGBA ? 4 : 3;
+    a.image_stride = image_stride;
+    if (cv->format >= OH_CONV_RGB_PLANAR) {
+        OhConvert k16 = *cv;
+        if (col) k16.sample = OH_CONV_U16;                      /* the colour stages start from the 16-bit R'G'B' */
+        const int rc = oh_convert_coeffs(&k16, a.bd, a.k, OH_CONV_NCOEFFS);
+        if (rc) FAIL(e, rc, "%s: no coefficients for this conversion", who);
+    }
+    if (col) {
+        const int rc = table_stage(e, &e->colour_tabs, col, OH_COLT_N, who);
+        if (rc) return rc;
+        ca.tab = (const int32_t *)e->colour_tabs.dev.p;
+        memcpy(ca.misc, e->colour_tabs.misc, sizeof(ca.misc));
+    }
+    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
+        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+        for (int i = 0; i < m; i++) {
+            const Pic *q = get_pic(e, pic_ids[i0 + i]);
+            for (int c = 0; c < 3; c++) a.src[i][c] = a.cf || !c ? final_planes(q)[c] : nullptr;
+        }
+        a.dst = (char *)dst + (size_t)i0 * image_stride;
+        if (col) ohk_colour(&ca, cv->format, cv->sample, m, e->stream);
+        else     ohk_convert(&a, cv->format, cv->sample, m, e->stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    return OH_OK;
+}
 
 extern "C" int oh_pics_convert(OhEngine *e, const int *pic_ids, int n, const OhConvert *cv, void *dst, size_t image_stride, size_t dst_bytes)
 {
@@ -458,121 +493,7 @@ extern "C" int oh_pics_convert(OhEngine *e, const int *pic_ids, int n, const OhC
     return pics_convert(e, "oh_pics_convert", pic_ids, n, cv, nullptr, dst, image_stride, dst_bytes);
 }
 
-static int colour_stage(OhEngine *e, const OhColour *col, OhColArgs *ca);
-
-static int pics_convert(OhEngine *e, const char *who, const int *pic_ids, int n, const OhConvert *cv, const OhColour *col, void *dst,
-                        size_t image_stride, size_t dst_bytes)
-{
-    { const int rc = check_pics(e, pic_ids, n, who); if (rc) return rc; }
-    const Pic *p0 = get_pic(e, pic_ids[0]);
-    const int other = first_other_params(e, pic_ids, n);
-    if (other < n)
-        FAIL(e, OH_E_ARG, "%s: picture %d has other params than picture %d", who, pic_ids[other], pic_ids[0]);
-    size_t ib = 0;
-    std::string why;
-    { const int rc = conv_check(&p0->p, cv, &ib, &why); if (rc) FAIL(e, rc, "%s: %s", who, why.c_str()); }
-    const size_t ob = (size_t)conv_sample_bytes(cv, p0->p.bit_depth);
-    if (image_stride < ib || image_stride % ob || (uintptr_t)dst % ob)
-        FAIL(e, OH_E_ARG, "%s: image_stride %zu (an image takes %zu bytes) or dst not a multiple of the %zu-byte sample", who, image_stride, ib, ob);
-    if (!dst || ib > dst_bytes || (size_t)(n - 1) > (dst_bytes - ib) / image_stride)
-        FAIL(e, OH_E_ARG, "%s: %d images of %zu bytes, %zu apart, do not fit %zu bytes", who, n, ib, image_stride, dst_bytes);
-    const size_t total = (size_t)(n - 1) * image_stride + ib;
-    HIPCHK(e, hipSetDevice(e->device));
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, dst) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->device) {
-        (void)hipGetLastError();
-        FAIL(e, OH_E_ARG, "%s: dst is not device memory of device %d", who, e->device);
-    }
-    void *base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, dst) == hipSuccess) {
-        if ((char *)dst + total > (char *)base + size)
-            FAIL(e, OH_E_ARG, "%s: %zu bytes at dst run past the end of its allocation", who, total);
-    } else {
-        (void)hipGetLastError();
-    }
-    OhColArgs ca;
-    OhConvArgs &a = ca.c;
-    memset(&ca, 0, sizeof(ca));
-    const OhPicParams &p = p0->p;
-    const int bpp = sample_bytes(p.bit_depth);
-    for (int c = 0; c < 3; c++) a.pitch[c] = p0->stride[c] * bpp;
-    a.cw = p0->w[1]; a.ch = p0->h[1];
-    a.left = cv->win.left; a.top = cv->win.top;
-    a.W = p.width - cv->win.left - cv->win.right; a.H = p.height - cv->win.top - cv->win.bottom;
-    a.cf = p.chroma_format_idc; a.bd = p.bit_depth; a.filter = cv->chroma_filter;
-    a.nc = cv->format == OH_CONV_RGBA ? 4 : 3;
-    a.image_stride = image_stride;
-    if (cv->format >= OH_CONV_RGB_PLANAR) {
-        OhConvert k16 = *cv;
-        if (col) k16.sample = OH_CONV_U16;                      /* the colour stages start from the 16-bit R'G'B' */
-        const int rc = oh_convert_coeffs(&k16, p.bit_depth, a.k, OH_CONV_NCOEFFS);
-        if (rc) FAIL(e, rc, "%s: no coefficients for this conversion", who);
-    }
-    if (col) { const int rc = colour_stage(e, col, &ca); if (rc) return rc; }
-    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
-        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
-        for (int i = 0; i < m; i++) {
-            const Pic *q = get_pic(e, pic_ids[i0 + i]);
-            for (int c = 0; c < 3; c++) a.src[i][c] = p.chroma_format_idc || !c ? final_planes(q)[c] : nullptr;
-        }
-        a.dst = (char *)dst + (size_t)i0 * image_stride;
-        if (col) ohk_colour(&ca, cv->format, cv->sample, m, e->stream);
-        else     ohk_convert(&a, cv->format, cv->sample, m, e->stream);
-        HIPCHK(e, hipGetLastError());
-    }
-    return OH_OK;
-}
-
 /* ---------------- import of standard images (import.hip) ---------------- */
-/* the integers of an RGB import: Y = clamp((ry R + gy G + by B + (yoff << S) + 2^(S-1)) >> S, 0, 2^B - 1), Cb with the u row and mid,
- * Cr with the v row; each row sums to the exact scale (greys give mid, white gives peak luma); S the largest shift that keeps
- * (|c0| + |c1| + |c2|) (2^D - 1) + (offset << S) + 2^(S-1) of every row inside int32: every term and every partial sum, in whatever
- * order they are added */
-extern "C" int oh_import_coeffs(const OhConvert *cv, int bit_depth, int32_t *out, int n)
-{
-    if (!cv || !out || n < OH_IMPORT_NCOEFFS || (bit_depth != 8 && bit_depth != 9 && bit_depth != 10 && bit_depth != 12))
-        return OH_E_ARG;
-    if (cv->format < OH_CONV_RGB_PLANAR || cv->format > OH_CONV_RGBA || cv->sample < OH_CONV_U8 || cv->sample > OH_CONV_F32)
-        return OH_E_UNSUPPORTED;
-    double kr, kb;
-    switch (cv->matrix) {
-    case 1:  kr = 0.2126; kb = 0.0722; break;
-    case 5:
-    case 6:  kr = 0.299;  kb = 0.114;  break;
-    case 9:  kr = 0.2627; kb = 0.0593; break;
-    default: return OH_E_UNSUPPORTED;
-    }
-    if (cv->full_range != 0 && cv->full_range != 1)
-        return OH_E_ARG;
-    const int B = bit_depth, D = cv->sample == OH_CONV_U8 ? 8 : 16;
-    const double full = (double)((1 << B) - 1), unit = (double)(1 << (B - 8)), M = (double)((1 << D) - 1);
-    const double ys = cv->full_range ? full : 219.0 * unit, cs = cv->full_range ? full : 224.0 * unit;
-    const int64_t yoff = cv->full_range ? 0 : 16 << (B - 8), mid = 1 << (B - 1), Mi = ((int64_t)1 << D) - 1;
-    for (int S = 30; S >= 1; S--) {
-        int64_t c[9];
-        c[0] = llround(ldexp(ys * kr / M, S));
-        c[2] = llround(ldexp(ys * kb / M, S));
-        c[1] = llround(ldexp(ys / M, S)) - c[0] - c[2];
-        c[5] = c[6] = llround(ldexp(cs / (2.0 * M), S));
-        c[3] = llround(ldexp(-cs * kr / (2.0 * (1.0 - kb) * M), S));
-        c[4] = -c[3] - c[5];
-        c[8] = llround(ldexp(-cs * kb / (2.0 * (1.0 - kr) * M), S));
-        c[7] = -c[6] - c[8];
-        const int64_t r = (int64_t)1 << (S - 1);
-        int64_t worst = 0;
-        for (int row = 0; row < 3; row++)
-            worst = std::max<int64_t>(worst, (std::llabs(c[3 * row]) + std::llabs(c[3 * row + 1]) + std::llabs(c[3 * row + 2])) * Mi +
-                                                 ((row ? mid : yoff) << S) + r);
-        if (worst > INT32_MAX)
-            continue;
-        for (int i = 0; i < 9; i++) out[i] = (int32_t)c[i];
-        out[9] = (int32_t)yoff; out[10] = (int32_t)mid; out[11] = S; out[12] = D;
-        return OH_OK;
-    }
-    return OH_E_UNSUPPORTED;
-}
-
 extern "C" int oh_pics_import(OhEngine *e, const int *pic_ids, int n, const OhConvert *cv, const void *src, size_t image_stride, size_t src_bytes)
 {
     const char *who = "oh_pics_import";
@@ -580,40 +501,14 @@ extern "C" int oh_pics_import(OhEngine *e, const int *pic_ids, int n, const OhCo
         return OH_E_ARG;
     if (!n)
         return OH_OK;
-    { const int rc = check_pics(e, pic_ids, n, who); if (rc) return rc; }
-    const Pic *p0 = get_pic(e, pic_ids[0]);
-    const int other = first_other_params(e, pic_ids, n);
-    if (other < n)
-        FAIL(e, OH_E_ARG, "%s: picture %d has other params than picture %d", who, pic_ids[other], pic_ids[0]);
-    {
-        std::vector<int> d(pic_ids, pic_ids + n);
-        std::sort(d.begin(), d.end());
-        if (std::adjacent_find(d.begin(), d.end()) != d.end())
-            FAIL(e, OH_E_ARG, "%s: a destination is listed twice", who);
-    }
+    const Pic *p0 = alike_pics(e, who, pic_ids, n);
+    if (!p0) return OH_E_ARG;
+    std::vector<int> sorted;
+    { const int rc = distinct_dsts(e, who, pic_ids, n, &sorted); if (rc) return rc; }
     size_t ib = 0;
     std::string why;
     { const int rc = conv_check(&p0->p, cv, &ib, &why); if (rc) FAIL(e, rc, "%s: %s", who, why.c_str()); }
-    const size_t sb = (size_t)conv_sample_bytes(cv, p0->p.bit_depth);
-    if (image_stride < ib || image_stride % sb || (uintptr_t)src % sb)
-        FAIL(e, OH_E_ARG, "%s: image_stride %zu (an image takes %zu bytes) or src not a multiple of the %zu-byte sample", who, image_stride, ib, sb);
-    if (!src || ib > src_bytes || (size_t)(n - 1) > (src_bytes - ib) / image_stride)
-        FAIL(e, OH_E_ARG, "%s: %d images of %zu bytes, %zu apart, do not fit %zu bytes", who, n, ib, image_stride, src_bytes);
-    const size_t total = (size_t)(n - 1) * image_stride + ib;
-    HIPCHK(e, hipSetDevice(e->device));
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, src) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->device) {
-        (void)hipGetLastError();
-        FAIL(e, OH_E_ARG, "%s: src is not device memory of device %d", who, e->device);
-    }
-    void *base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(src)) == hipSuccess) {
-        if ((const char *)src + total > (const char *)base + size)
-            FAIL(e, OH_E_ARG, "%s: %zu bytes at src run past the end of its allocation", who, total);
-    } else {
-        (void)hipGetLastError();
-    }
+    { const int rc = image_run_check(e, who, "src", src, n, ib, (size_t)conv_sample_bytes(cv, p0->p.bit_depth), image_stride, src_bytes); if (rc) return rc; }
     OhImpArgs a;
     memset(&a, 0, sizeof(a));
     const OhPicParams &p = p0->p;
@@ -646,252 +541,6 @@ extern "C" int oh_pics_import(OhEngine *e, const int *pic_ids, int n, const OhCo
 }
 
 /* ---------------- colour conversion (colour.hip) ---------------- */
-namespace {
-const double PQ_M1 = 2610.0 / 16384.0, PQ_M2 = 2523.0 / 4096.0 * 128.0, PQ_C1 = 3424.0 / 4096.0, PQ_C2 = 2413.0 / 4096.0 * 32.0,
-             PQ_C3 = 2392.0 / 4096.0 * 32.0;
-/* ST 2084: signal -> luminance / 10000 and back */
-double pq_eotf(double x)
-{
-    const double xp = pow(std::max(x, 0.0), 1.0 / PQ_M2);
-    return pow(std::max(xp - PQ_C1, 0.0) / (PQ_C2 - PQ_C3 * xp), 1.0 / PQ_M1);
-}
-double pq_inv(double y)
-{
-    const double yp = pow(std::max(y, 0.0), PQ_M1);
-    return pow((PQ_C1 + PQ_C2 * yp) / (1.0 + PQ_C3 * yp), PQ_M2);
-}
-/* BT.2100 HLG inverse OETF: signal -> scene linear, 1 at signal 1 */
-double hlg_inv_oetf(double x)
-{
-    const double a = 0.17883277, b = 1.0 - 4.0 * a, c = 0.5 - a * log(4.0 * a);
-    return x <= 0.5 ? x * x / 3.0 : (exp((x - c) / a) + b) / 12.0;
-}
-double srgb_eotf(double x) { return x <= 0.04045 ? x / 12.92 : pow((x + 0.055) / 1.055, 2.4); }
-double srgb_inv(double l) { return l <= 0.0031308 ? 12.92 * l : 1.055 * pow(l, 1.0 / 2.4) - 0.055; }
-
-bool is_sdr_video(int t) { return t == 1 || t == 6 || t == 14 || t == 15; }
-
-/* BT.2390 EETF, black 0: nits -> nits.  Identity below the knee (exactly), the Hermite spline in the PQ domain above it, the target
- * peak from the source peak on (the spline ends there with slope 0) */
-struct Eetf {
-    double src_pq, mx, ks;
-    Eetf(double src_peak, double dst_peak) : src_pq(pq_inv(src_peak / 10000.0)), mx(pq_inv(dst_peak / 10000.0) / src_pq), ks(1.5 * mx - 0.5) {}
-    double gain(double nits) const
-    {
-        if (!(nits > 0))
-            return 1.0;
-        const double e1 = std::min(pq_inv(nits / 10000.0) / src_pq, 1.0);
-        if (e1 <= ks)
-            return 1.0;
-        const double t = (e1 - ks) / (1.0 - ks), t2 = t * t, t3 = t2 * t;
-        const double e2 = (2 * t3 - 3 * t2 + 1) * ks + (t3 - 2 * t2 + t) * (1.0 - ks) + (-2 * t3 + 3 * t2) * mx;
-        return 10000.0 * pq_eotf(e2 * src_pq) / nits;
-    }
-};
-
-void inv3(const double P[9], double inv[9])
-{
-    const double det = P[0] * (P[4] * P[8] - P[5] * P[7]) - P[1] * (P[3] * P[8] - P[5] * P[6]) + P[2] * (P[3] * P[7] - P[4] * P[6]);
-    inv[0] = (P[4] * P[8] - P[5] * P[7]) / det; inv[1] = (P[2] * P[7] - P[1] * P[8]) / det; inv[2] = (P[1] * P[5] - P[2] * P[4]) / det;
-    inv[3] = (P[5] * P[6] - P[3] * P[8]) / det; inv[4] = (P[0] * P[8] - P[2] * P[6]) / det; inv[5] = (P[2] * P[3] - P[0] * P[5]) / det;
-    inv[6] = (P[3] * P[7] - P[4] * P[6]) / det; inv[7] = (P[1] * P[6] - P[0] * P[7]) / det; inv[8] = (P[0] * P[4] - P[1] * P[3]) / det;
-}
-
-/* linear RGB -> XYZ of a set of primaries with the D65 white, row-major; false: a code outside the list */
-bool rgb_to_xyz(int prim, double m[9])
-{
-    double xy[6];
-    switch (prim) {
-    case 1:  { const double v[6] = { 0.640, 0.330, 0.300, 0.600, 0.150, 0.060 }; memcpy(xy, v, sizeof(v)); break; }
-    case 9:  { const double v[6] = { 0.708, 0.292, 0.170, 0.797, 0.131, 0.046 }; memcpy(xy, v, sizeof(v)); break; }
-    case 12: { const double v[6] = { 0.680, 0.320, 0.265, 0.690, 0.150, 0.060 }; memcpy(xy, v, sizeof(v)); break; }
-    default: return false;
-    }
-    const double xw = 0.3127, yw = 0.3290, W[3] = { xw / yw, 1.0, (1.0 - xw - yw) / yw };
-    double P[9];
-    for (int i = 0; i < 3; i++) {
-        const double x = xy[2 * i], y = xy[2 * i + 1];
-        P[i] = x / y; P[3 + i] = 1.0; P[6 + i] = (1.0 - x - y) / y;
-    }
-    double inv[9];
-    inv3(P, inv);
-    for (int i = 0; i < 3; i++) {
-        const double S = inv[3 * i] * W[0] + inv[3 * i + 1] * W[1] + inv[3 * i + 2] * W[2];
-        for (int r = 0; r < 3; r++) m[3 * r + i] = P[3 * r + i] * S;
-    }
-    return true;
-}
-
-/* a row of fractions that sum to 1 with q fraction bits, the largest entry corrected so that the integers sum to exactly 2^q */
-void q_row(const double r[3], int q, int32_t out[3])
-{
-    int best = 0, sum = 0;
-    for (int j = 0; j < 3; j++) {
-        out[j] = (int32_t)llround(ldexp(r[j], q));
-        sum += out[j];
-        if (out[j] > out[best]) best = j;
-    }
-    out[best] += (1 << q) - sum;
-}
-
-/* the node of entry k of a piecewise-logarithmic table, in units of 2^-30 of the full scale */
-double node_of(int k) { return k < 128 ? (double)k : ldexp((double)(64 + (k & 63)), (k >> 6) - 1); }
-
-/* rounded values into a table; false: a value, or a step between neighbours from entry `from` on (the entries the kernel interpolates
- * between), that its interpolation does not hold: max_step or more, or — rising — downwards */
-bool narrow(const std::vector<double> &v, int32_t *out, int64_t max_step, size_t from, bool rising)
-{
-    int64_t prev = 0;
-    for (size_t i = 0; i < v.size(); i++) {
-        if (!std::isfinite(v[i]) || fabs(v[i]) > 2e9)
-            return false;
-        const int64_t r = llround(v[i]);
-        if (i > from && (std::llabs(r - prev) >= max_step || (rising && r < prev)))
-            return false;
-        out[i] = (int32_t)r;
-        prev = r;
-    }
-    return true;
-}
-}
-
-/* what is wrong with an OhColour, by itself: OH_E_ARG, OH_E_UNSUPPORTED or OH_OK */
-static int colour_check(const OhColour *col, std::string *why)
-{
-    char buf[256];
-    if (col->out_transfer < OH_COL_LINEAR || col->out_transfer > OH_COL_GAMMA24 || col->tone < OH_TONE_NONE || col->tone > OH_TONE_BT2390 ||
-        col->norm < OH_NORM_MAXRGB || col->norm > OH_NORM_LUMA) {
-        snprintf(buf, sizeof(buf), "out_transfer %d, tone %d or norm %d outside its list", col->out_transfer, col->tone, col->norm);
-        *why = buf; return OH_E_ARG;
-    }
-    const float pk[3] = { col->src_peak, col->dst_peak, col->white };
-    for (int i = 0; i < 3; i++)
-        if (!std::isfinite(pk[i]) || !(pk[i] > 0)) { *why = "src_peak, dst_peak and white are finite and positive"; return OH_E_ARG; }
-    const int t = col->in_transfer;
-    if (t != 16 && t != 18 && t != 13 && !is_sdr_video(t)) {
-        snprintf(buf, sizeof(buf), "transfer_characteristics %d (16 PQ, 18 HLG, 13 sRGB, 1 / 6 / 14 / 15 SDR video)", t); *why = buf; return OH_E_UNSUPPORTED;
-    }
-    double m[9];
-    if (!rgb_to_xyz(col->in_primaries, m) || !rgb_to_xyz(col->out_primaries, m)) {
-        snprintf(buf, sizeof(buf), "colour_primaries %d -> %d (1 BT.709, 9 BT.2020, 12 P3-D65)", col->in_primaries, col->out_primaries);
-        *why = buf; return OH_E_UNSUPPORTED;
-    }
-    if (t == 18 && col->norm == OH_NORM_MAXRGB) { *why = "HLG takes OH_NORM_LUMA: its OOTF is defined on luminance"; return OH_E_UNSUPPORTED; }
-    if (t == 18 && !(col->src_peak >= 400.0f && col->src_peak <= 10000.0f)) { *why = "HLG with a nominal peak outside [400, 10000] nits"; return OH_E_UNSUPPORTED; }
-    if (col->tone == OH_TONE_BT2390) {
-        if (col->dst_peak >= col->src_peak) { *why = "OH_TONE_BT2390 with dst_peak >= src_peak"; return OH_E_UNSUPPORTED; }
-        if (Eetf(col->src_peak, col->dst_peak).ks <= 0) { *why = "OH_TONE_BT2390 with a knee at or below black"; return OH_E_UNSUPPORTED; }
-    }
-    return OH_OK;
-}
-
-/* the tables in the layout of the device copy (tab: OH_COLT_N int32, zero-padded) and misc */
-static int colour_build(const OhColour *col, int32_t *tab, int32_t *misc, std::string *why)
-{
-    { const int rc = colour_check(col, why); if (rc) return rc; }
-    const int t = col->in_transfer;
-    const bool pq = t == 16, hlg = t == 18;
-    const double Lfs = pq ? 10000.0 : (double)col->src_peak, src = col->src_peak, dstp = col->dst_peak;
-    memset(tab, 0, (size_t)OH_COLT_N * sizeof(int32_t));
-    memset(misc, 0, (size_t)OH_COL_NMISC * sizeof(int32_t));
-    std::vector<double> v((size_t)OH_COL_NA);
-    for (int i = 0; i < OH_COL_NA; i++) {
-        const double x = 16.0 * i / 65535.0;
-        v[i] = ldexp(pq ? pq_eotf(x) : hlg ? hlg_inv_oetf(x) : t == 13 ? srgb_eotf(x) : pow(x, 2.4), 30);
-    }
-    if (!narrow(v, tab, (int64_t)1 << 24, 0, true)) { *why = "the source curve's table falls or steps by 2^24 or more"; return OH_E_UNSUPPORTED; }
-    const bool tone = col->tone == OH_TONE_BT2390;
-    const double gamma = hlg ? 1.2 + 0.42 * log10(src / 1000.0) : 1.0;
-    const Eetf tm(src, dstp);
-    v.resize((size_t)OH_COL_NP);
-    for (int k = 0; k < OH_COL_NP; k++) {
-        const double x = ldexp(node_of(k), -30);
-        double g = 1.0;
-        if (hlg) g = x > 0 ? pow(x, gamma - 1.0) : 0.0;
-        if (tone) g *= tm.gain(hlg ? src * pow(x, gamma) : Lfs * x);
-        v[k] = ldexp(std::min(g, 1.0), 20);
-    }
-    if (!narrow(v, tab + OH_COLT_G, (int64_t)1 << 19, 128, false)) { *why = "the gain table steps by 2^19 or more"; return OH_E_UNSUPPORTED; }
-    if (col->out_transfer != OH_COL_LINEAR) {
-        for (int k = 0; k < OH_COL_NP; k++) {
-            const double x = ldexp(node_of(k), -30) * Lfs / dstp;
-            v[k] = 65535.0 * (col->out_transfer == OH_COL_SRGB ? srgb_inv(x) : pow(x, 1.0 / 2.4));
-        }
-        if (!narrow(v, tab + OH_COLT_B, (int64_t)1 << 19, 128, false)) { *why = "the output curve's table steps by 2^19 or more"; return OH_E_UNSUPPORTED; }
-    }
-    double si[9], so[9], soi[9];
-    rgb_to_xyz(col->in_primaries, si);
-    rgb_to_xyz(col->out_primaries, so);
-    inv3(so, soi);
-    for (int r = 0; r < 3; r++) {
-        double row[3];
-        for (int j = 0; j < 3; j++) row[j] = soi[3 * r] * si[j] + soi[3 * r + 1] * si[3 + j] + soi[3 * r + 2] * si[6 + j];
-        q_row(row, 20, misc + 3 * r);
-        if (col->in_primaries == col->out_primaries)
-            for (int j = 0; j < 3; j++) misc[3 * r + j] = r == j ? 1 << 20 : 0;
-    }
-    q_row(si + 3, 14, misc + 9);
-    misc[12] = col->norm;
-    misc[13] = col->out_transfer != OH_COL_LINEAR;
-    const float K = (float)(Lfs / ((double)col->white * 1073741824.0));
-    if (!std::isfinite(K) || !(K > 0)) { *why = "white is out of the f32 range of the output scale"; return OH_E_UNSUPPORTED; }
-    memcpy(&misc[14], &K, 4);
-    misc[15] = hlg || tone;
-    misc[16] = col->in_primaries != col->out_primaries;
-    return OH_OK;
-}
-
-extern "C" int oh_colour_tables(const OhColour *col, int32_t *A, int32_t *G, int32_t *B, int32_t *misc)
-{
-    if (!col || !A || !G || !B || !misc)
-        return OH_E_ARG;
-    std::vector<int32_t> tab((size_t)OH_COLT_N);
-    int32_t m[OH_COL_NMISC];
-    std::string why;
-    const int rc = colour_build(col, tab.data(), m, &why);
-    if (rc) return rc;
-    memcpy(A, tab.data(), (size_t)OH_COL_NA * 4);
-    memcpy(G, tab.data() + OH_COLT_G, (size_t)OH_COL_NP * 4);
-    memcpy(B, tab.data() + OH_COLT_B, (size_t)OH_COL_NP * 4);
-    memcpy(misc, m, sizeof(m));
-    return OH_OK;
-}
-
-/* the tables of col in the engine's device copy, in front of the launches that follow on the engine stream: built on the host unless
- * col is the last call's, staged in a pinned buffer of the pool and copied on the engine stream — behind the launches of an earlier
- * call that read the device copy — unless the device copy holds them already */
-static int colour_stage(OhEngine *e, const OhColour *col, OhColArgs *ca)
-{
-    if (!e->colour_cached || memcmp(&e->colour_last, col, sizeof(*col))) {
-        e->colour_cached = false;
-        e->colour_tab.resize((size_t)OH_COLT_N);
-        std::string why;
-        const int rc = colour_build(col, e->colour_tab.data(), e->colour_misc, &why);
-        if (rc) FAIL(e, rc, "oh_pics_convert_colour: %s", why.c_str());
-        e->colour_last = *col;
-        e->colour_cached = true;
-        e->colour_on_dev = false;
-    }
-    const size_t bytes = (size_t)OH_COLT_N * sizeof(int32_t);
-    if (!e->colour_dev.p) {
-        const int rc = scratch_reserve(e, &e->colour_dev, bytes);
-        if (rc) return rc;
-        e->colour_on_dev = false;
-    }
-    if (!e->colour_on_dev) {
-        OhEngine::Stage *sg = stage_acquire(e, bytes);
-        if (!sg)
-            FAIL(e, OH_E_NOMEM, "oh_pics_convert_colour: no staging buffer for %zu bytes of tables", bytes);
-        memcpy(sg->p, e->colour_tab.data(), bytes);
-        HIPCHK(e, hipMemcpyAsync(e->colour_dev.p, sg->p, bytes, hipMemcpyHostToDevice, e->stream));
-        { const int rc = stage_in_use(e, sg, e->stream); if (rc) return rc; }
-        e->colour_on_dev = true;
-    }
-    ca->tab = (const int32_t *)e->colour_dev.p;
-    memcpy(ca->misc, e->colour_misc, sizeof(ca->misc));
-    return OH_OK;
-}
-
 extern "C" int oh_pics_convert_colour(OhEngine *e, const int *pic_ids, int n, const OhConvert *cv, const OhColour *col, void *dst,
                                       size_t image_stride, size_t dst_bytes)
 {
@@ -909,49 +558,6 @@ extern "C" int oh_pics_convert_colour(OhEngine *e, const int *pic_ids, int n, co
 }
 
 /* ---------------- light-level statistics (light.hip) ---------------- */
-extern "C" int oh_light_bin(uint32_t v)
-{
-    v = std::min(v, (uint32_t)1 << 30);
-    if (v < (1u << 14))
-        return 0;
-    const int e = 31 - __builtin_clz(v);
-    return 1 + 16 * (e - 14) + (int)((v >> (e - 4)) & 15);
-}
-
-extern "C" uint32_t oh_light_bin_upper(int bin)
-{
-    if (bin <= 0)
-        return bin < 0 ? 0 : (1u << 14) - 1;
-    if (bin >= OH_LL_NBINS)
-        return 1u << 30;
-    const int e = 14 + (bin - 1) / 16, j = (bin - 1) % 16;
-    return (uint32_t)std::min<uint64_t>(((uint64_t)(17 + j) << (e - 4)) - 1, (uint64_t)1 << 30);
-}
-
-extern "C" int oh_light_percentile(const OhLightLevel *ll, int n, uint32_t ppm, uint32_t *value)
-{
-    if (!ll || !value || n < 1 || ppm > 1000000u)
-        return OH_E_ARG;
-    uint64_t total = 0;
-    uint32_t top = 0;
-    for (int i = 0; i < n; i++) {
-        total += ll[i].pixels;
-        top = std::max(top, ll[i].max);
-    }
-    if (!total)
-        return OH_E_ARG;
-    const uint64_t need = (uint64_t)ppm * total;
-    uint64_t cum = 0;
-    int b = 0;
-    for (; b < OH_LL_NBINS - 1; b++) {                          /* histograms that hold fewer than `pixels` end in the last bin */
-        for (int i = 0; i < n; i++) cum += ll[i].hist[b];
-        if (cum * 1000000u >= need)
-            break;
-    }
-    *value = std::min(oh_light_bin_upper(b), top);
-    return OH_OK;
-}
-
 /* the OhColour whose table A and luminance weights the light-level pass uses.  Neither depends on src_peak; HLG is built with 1000
  * nits so that a peak outside what oh_pics_convert_colour takes for its OOTF passes colour_check */
 static OhColour light_colour(const OhLightSpec *sp)
@@ -964,40 +570,6 @@ static OhColour light_colour(const OhLightSpec *sp)
     c.src_peak = c.white = sp->in_transfer == 18 ? 1000.0f : sp->src_peak;
     c.dst_peak = 100.0f;
     return c;
-}
-
-/* table A of col in the engine's device copy for this call, as colour_stage does for the three tables of oh_pics_convert_colour, with
- * a cache and a device buffer of its own.  Every light-level call ends with a wait: no launch reads the device copy while it changes. */
-static int light_stage(OhEngine *e, const OhColour *col, OhLightArgs *la)
-{
-    if (!e->light_cached || memcmp(&e->light_last, col, sizeof(*col))) {
-        e->light_cached = false;
-        e->light_tab.resize((size_t)OH_COLT_N);
-        std::string why;
-        const int rc = colour_build(col, e->light_tab.data(), e->light_misc, &why);
-        if (rc) FAIL(e, rc == OH_E_ARG ? OH_E_UNSUPPORTED : rc, "oh_pics_light_level: %s", why.c_str());
-        e->light_last = *col;
-        e->light_cached = true;
-        e->light_on_dev = false;
-    }
-    const size_t bytes = (size_t)OH_COLT_G * sizeof(int32_t);
-    if (!e->light_dev.p) {
-        const int rc = scratch_reserve(e, &e->light_dev, bytes);
-        if (rc) return rc;
-        e->light_on_dev = false;
-    }
-    if (!e->light_on_dev) {
-        OhEngine::Stage *sg = stage_acquire(e, bytes);
-        if (!sg)
-            FAIL(e, OH_E_NOMEM, "oh_pics_light_level: no staging buffer for %zu bytes of table", bytes);
-        memcpy(sg->p, e->light_tab.data(), bytes);
-        HIPCHK(e, hipMemcpyAsync(e->light_dev.p, sg->p, bytes, hipMemcpyHostToDevice, e->stream));
-        { const int rc = stage_in_use(e, sg, e->stream); if (rc) return rc; }
-        e->light_on_dev = true;
-    }
-    la->tab = (const int32_t *)e->light_dev.p;
-    for (int j = 0; j < 3; j++) la->w[j] = e->light_misc[9 + j];
-    return OH_OK;
 }
 
 extern "C" int oh_pics_light_level(OhEngine *e, const int *pic_ids, int n, const OhConvert *cv, const OhLightSpec *sp, OhLightLevel *out)
@@ -1014,11 +586,8 @@ extern "C" int oh_pics_light_level(OhEngine *e, const int *pic_ids, int n, const
     { const int rc = colour_check(&col, &why); if (rc) FAIL(e, OH_E_UNSUPPORTED, "%s: %s", who, why.c_str()); }
     if (!n)
         return OH_OK;
-    { const int rc = check_pics(e, pic_ids, n, who); if (rc) return rc; }
-    const Pic *p0 = get_pic(e, pic_ids[0]);
-    const int other = first_other_params(e, pic_ids, n);
-    if (other < n)
-        FAIL(e, OH_E_ARG, "%s: picture %d has other params than picture %d", who, pic_ids[other], pic_ids[0]);
+    const Pic *p0 = alike_pics(e, who, pic_ids, n);
+    if (!p0) return OH_E_ARG;
     OhConvert k16 = *cv;                                        /* format and sample are not the caller's to set: the 16-bit R'G'B' */
     k16.format = OH_CONV_RGB; k16.sample = OH_CONV_U16;
     size_t ib = 0;
@@ -1027,35 +596,27 @@ extern "C" int oh_pics_light_level(OhEngine *e, const int *pic_ids, int n, const
     OhLightArgs la;
     OhConvArgs &a = la.c;
     memset(&la, 0, sizeof(la));
-    const OhPicParams &p = p0->p;
-    const int bpp = sample_bytes(p.bit_depth);
-    for (int c = 0; c < 3; c++) a.pitch[c] = p0->stride[c] * bpp;
-    a.cw = p0->w[1]; a.ch = p0->h[1];
-    a.left = cv->win.left; a.top = cv->win.top;
-    a.W = p.width - cv->win.left - cv->win.right; a.H = p.height - cv->win.top - cv->win.bottom;
-    a.cf = p.chroma_format_idc; a.bd = p.bit_depth; a.filter = cv->chroma_filter;
-    { const int rc = oh_convert_coeffs(&k16, p.bit_depth, a.k, OH_CONV_NCOEFFS); if (rc) FAIL(e, rc, "%s: no coefficients for this conversion", who); }
+    conv_args(&a, p0, cv);
+    { const int rc = oh_convert_coeffs(&k16, a.bd, a.k, OH_CONV_NCOEFFS); if (rc) FAIL(e, rc, "%s: no coefficients for this conversion", who); }
     la.luma = sp->norm == OH_NORM_LUMA;
-    { const int rc = light_stage(e, &col, &la); if (rc) return rc; }
+    /* table A alone, in a cache of its own; the call ends with a wait, so no launch reads the device copy while it changes */
+    { const int rc = table_stage(e, &e->light_tabs, &col, OH_COLT_G, who); if (rc) return rc == OH_E_ARG ? OH_E_UNSUPPORTED : rc; }
+    la.tab = (const int32_t *)e->light_tabs.dev.p;
+    for (int j = 0; j < 3; j++) la.w[j] = e->light_tabs.misc[9 + j];
     const size_t bytes = (size_t)n * sizeof(OhLightDev);
-    { const int rc = scratch_reserve(e, &e->light_res, bytes); if (rc) return rc; }       /* every call ends with a wait: the old buffer is idle */
-    OhEngine::Stage *sg = stage_acquire(e, bytes);
-    if (!sg)
-        FAIL(e, OH_E_NOMEM, "%s: no staging buffer for %d results", who, n);
-    HIPCHK(e, hipMemsetAsync(e->light_res.p, 0, bytes, e->stream));
+    OhEngine::Stage *sg = nullptr;
+    { const int rc = results_begin(e, who, &e->light_res, bytes, n, &sg); if (rc) return rc; }
     for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
         const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
         for (int i = 0; i < m; i++) {
             const Pic *q = get_pic(e, pic_ids[i0 + i]);
-            for (int c = 0; c < 3; c++) a.src[i][c] = p.chroma_format_idc || !c ? final_planes(q)[c] : nullptr;
+            for (int c = 0; c < 3; c++) a.src[i][c] = a.cf || !c ? final_planes(q)[c] : nullptr;
         }
         la.res = (OhLightDev *)e->light_res.p + i0;
         ohk_light(&la, m, e->stream);
         HIPCHK(e, hipGetLastError());
     }
-    HIPCHK(e, hipMemcpyAsync(sg->p, e->light_res.p, bytes, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    { const int ke = kernel_error(e); if (ke) return ke; }     /* a kernel that gave up: these samples are not the picture */
+    { const int rc = results_fetch(e, &e->light_res, bytes, sg); if (rc) return rc; }
     const OhLightDev *r = (const OhLightDev *)sg->p;
     for (int i = 0; i < n; i++) {
         out[i].pixels = (uint64_t)a.W * (uint64_t)a.H;
@@ -1067,35 +628,6 @@ extern "C" int oh_pics_light_level(OhEngine *e, const int *pic_ids, int n, const
 }
 
 /* ---------------- comparison of two pictures (compare.hip) ---------------- */
-static bool compare_depth_ok(int bit_depth) { return bit_depth == 8 || bit_depth == 9 || bit_depth == 10 || bit_depth == 12; }
-
-extern "C" int oh_compare_ssim_consts(int bit_depth, int64_t *c1, int64_t *c2)
-{
-    if (!c1 || !c2 || !compare_depth_ok(bit_depth))
-        return OH_E_ARG;
-    compare_ssim_consts(bit_depth, c1, c2);
-    return OH_OK;
-}
-
-extern "C" int64_t oh_compare_ssim_window(int bit_depth, uint32_t s1, uint32_t s2, uint64_t ss, uint64_t s12)
-{
-    if (!compare_depth_ok(bit_depth))
-        return 0;
-    int64_t c1, c2;
-    compare_ssim_consts(bit_depth, &c1, &c2);
-    return compare_ssim_window(c1, c2, s1, s2, ss, s12);
-}
-
-extern "C" double oh_compare_psnr(uint64_t sse, uint64_t samples, int bit_depth)
-{
-    if (!samples)
-        return std::numeric_limits<double>::quiet_NaN();
-    if (!sse)
-        return std::numeric_limits<double>::infinity();
-    const double M = (double)((1u << bit_depth) - 1);
-    return 10.0 * std::log10(M * M * (double)samples / (double)sse);
-}
-
 extern "C" int oh_pics_compare(OhEngine *e, const int *a_ids, const int *b_ids, int n, const OhCompareSpec *sp, OhCompare *out)
 {
     const char *who = "oh_pics_compare";
@@ -1105,14 +637,10 @@ extern "C" int oh_pics_compare(OhEngine *e, const int *a_ids, const int *b_ids, 
         FAIL(e, OH_E_ARG, "%s: flags %#x: OH_CMP_SSIM is the only one", who, (unsigned)sp->flags);
     if (!n)
         return OH_OK;
-    { const int rc = check_pics(e, a_ids, n, who); if (rc) return rc; }
-    { const int rc = check_pics(e, b_ids, n, who); if (rc) return rc; }
     std::vector<int> all(a_ids, a_ids + n);
     all.insert(all.end(), b_ids, b_ids + n);
-    const int other = first_other_params(e, all.data(), 2 * n);
-    if (other < 2 * n)
-        FAIL(e, OH_E_ARG, "%s: picture %d has other params than picture %d", who, all[other], all[0]);
-    const Pic *p0 = get_pic(e, a_ids[0]);
+    const Pic *p0 = alike_pics(e, who, all.data(), 2 * n);
+    if (!p0) return OH_E_ARG;
     const OhPicParams &p = p0->p;
     std::string why;
     if (!crop_window_ok(&p, sp->win, true, &why))
@@ -1133,11 +661,8 @@ extern "C" int oh_pics_compare(OhEngine *e, const int *a_ids, const int *b_ids, 
     }
     a.np = np; a.bd = p.bit_depth; a.ssim = (sp->flags & OH_CMP_SSIM) != 0;
     const size_t bytes = (size_t)n * 3 * OH_CMP_SLOTS * sizeof(OhCmpDev);
-    { const int rc = scratch_reserve(e, &e->compare_res, bytes); if (rc) return rc; }     /* every call ends with a wait: the old buffer is idle */
-    OhEngine::Stage *sg = stage_acquire(e, bytes);
-    if (!sg)
-        FAIL(e, OH_E_NOMEM, "%s: no staging buffer for %d results", who, n);
-    HIPCHK(e, hipMemsetAsync(e->compare_res.p, 0, bytes, e->stream));
+    OhEngine::Stage *sg = nullptr;
+    { const int rc = results_begin(e, who, &e->compare_res, bytes, n, &sg); if (rc) return rc; }
     for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
         const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
         for (int i = 0; i < m; i++) {
@@ -1151,9 +676,7 @@ extern "C" int oh_pics_compare(OhEngine *e, const int *a_ids, const int *b_ids, 
         ohk_compare(&a, m, e->stream);
         HIPCHK(e, hipGetLastError());
     }
-    HIPCHK(e, hipMemcpyAsync(sg->p, e->compare_res.p, bytes, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    { const int ke = kernel_error(e); if (ke) return ke; }     /* a kernel that gave up: these samples are not the pictures */
+    { const int rc = results_fetch(e, &e->compare_res, bytes, sg); if (rc) return rc; }
     const OhCmpDev *r = (const OhCmpDev *)sg->p;
     for (int i = 0; i < n; i++) {
         memset(&out[i], 0, sizeof(out[i]));
@@ -1185,65 +708,6 @@ extern "C" int oh_pics_compare(OhEngine *e, const int *a_ids, const int *b_ids, 
 }
 
 /* ---------------- resizing into engine pictures (resize.hip) ---------------- */
-typedef __int128 i128;
-static i128 floor_div(i128 a, i128 b) { const i128 q = a / b; return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q; }   /* b > 0 */
-
-static bool resize_axis_ok(int S, int T, int filter, int phase)
-{
-    return S >= 1 && T >= 1 && S <= 16384 && T <= 16384 && (filter == OH_RESIZE_BILINEAR || filter == OH_RESIZE_BICUBIC) && (phase == 1 || phase == 2);
-}
-
-extern "C" int oh_resize_max_taps(int src_extent, int dst_extent, int filter)
-{
-    if (!resize_axis_ok(src_extent, dst_extent, filter, 2))
-        return OH_E_ARG;
-    const int64_t S = src_extent, T = dst_extent, D = 4 * std::max(S, T), R = filter == OH_RESIZE_BICUBIC ? 2 : 1;
-    return (int)std::min<int64_t>(S, (2 * R * D - 2) / (4 * T) + 1);          /* source samples strictly inside a span of 2RD */
-}
-
-/* the taps of one axis, all positions in units of 1/(4T) source samples */
-extern "C" int oh_resize_taps(int src_extent, int dst_extent, int filter, int phase, int32_t *first, int16_t *coeffs, int max_taps, int *n_taps)
-{
-    if (!first || !coeffs || !n_taps || !resize_axis_ok(src_extent, dst_extent, filter, phase) ||
-        max_taps < oh_resize_max_taps(src_extent, dst_extent, filter))
-        return OH_E_ARG;
-    const int64_t S = src_extent, T = dst_extent, p = phase, D = 4 * std::max(S, T), R = filter == OH_RESIZE_BICUBIC ? 2 : 1;
-    std::vector<i128> w;
-    std::vector<int64_t> k;
-    for (int64_t x = 0; x < T; x++) {
-        const int64_t c = (4 * x + p) * S;
-        int64_t lo = -(int64_t)floor_div(-(c - R * D - p * T + 1), 4 * T), hi = (int64_t)floor_div(c + R * D - p * T - 1, 4 * T);
-        lo = std::max<int64_t>(lo, 0); hi = std::min(hi, S - 1);
-        const int n = (int)(hi - lo + 1);
-        if (n < 1 || n > max_taps)
-            return OH_E_ARG;
-        w.assign((size_t)n, 0); k.assign((size_t)n, 0);
-        i128 sum = 0;
-        for (int j = 0; j < n; j++) {
-            const i128 v = std::llabs((4 * (lo + j) + p) * T - c), d = D;
-            w[j] = R == 1 ? d - v : v <= d ? 3 * v * v * v - 5 * v * v * d + 2 * d * d * d : -(v * v * v - 5 * v * v * d + 8 * v * d * d - 4 * d * d * d);
-            sum += w[j];
-        }
-        if (sum <= 0)
-            return OH_E_UNSUPPORTED;
-        int64_t ks = 0, ka = 0;
-        int best = 0;
-        for (int j = 0; j < n; j++) {
-            k[j] = (int64_t)floor_div(2 * w[j] * (1 << 14) + sum, 2 * sum);
-            ks += k[j];
-            if (k[j] > k[best]) best = j;
-        }
-        k[best] += (1 << 14) - ks;
-        for (int j = 0; j < n; j++) ka += std::llabs(k[j]);
-        if (ka >= 1 << 15)
-            return OH_E_UNSUPPORTED;
-        first[x] = (int32_t)lo; n_taps[x] = n;
-        int16_t *row = coeffs + (size_t)x * max_taps;
-        for (int j = 0; j < max_taps; j++) row[j] = j < n ? (int16_t)k[j] : 0;
-    }
-    return OH_OK;
-}
-
 namespace {
 struct ResizeAxis { std::vector<int32_t> first, cnt; std::vector<int16_t> k; int mt = 0; };
 /* what a call works out per plane class (0 luma, 1 chroma) beside its OhResizeClass: the taps of both axes, the quads of the horizontal
@@ -1273,10 +737,9 @@ static int resize_check(OhEngine *e, const int *src_ids, const int *dst_ids, int
     if (other < n)
         FAIL(e, OH_E_ARG, "oh_pics_resize: pictures %d -> %d have other params than pictures %d -> %d", src_ids[other], dst_ids[other], src_ids[0], dst_ids[0]);
     {
-        std::vector<int> d(dst_ids, dst_ids + n), s(src_ids, src_ids + n);
-        std::sort(d.begin(), d.end()); std::sort(s.begin(), s.end());
-        if (std::adjacent_find(d.begin(), d.end()) != d.end())
-            FAIL(e, OH_E_ARG, "oh_pics_resize: a destination is listed twice");
+        std::vector<int> d, s(src_ids, src_ids + n);
+        { const int rc = distinct_dsts(e, "oh_pics_resize", dst_ids, n, &d); if (rc) return rc; }
+        std::sort(s.begin(), s.end());
         for (int i = 0; i < n; i++)
             if (std::binary_search(s.begin(), s.end(), d[i]))
                 FAIL(e, OH_E_ARG, "oh_pics_resize: picture %d is both source and destination", d[i]);
@@ -1462,16 +925,6 @@ extern "C" int oh_pics_resize(OhEngine *e, const int *src_ids, const int *dst_id
 }
 
 /* ---------------- composition (compose.hip) ---------------- */
-extern "C" uint32_t oh_compose_blend(uint32_t dst, uint32_t src, uint32_t alpha, uint32_t opacity)
-{
-    return compose_blend(dst, src, alpha, opacity);
-}
-
-extern "C" uint32_t oh_compose_chroma_alpha(int chroma_format_idc, uint32_t a00, uint32_t a01, uint32_t a10, uint32_t a11)
-{
-    return compose_chroma_alpha(chroma_format_idc, a00, a01, a10, a11);
-}
-
 /* everything oh_pics_compose refuses, before anything is enqueued (dst_ids, cp not null; n > 0) */
 static int compose_check(OhEngine *e, const int *dst_ids, int n, const OhCompose *cp)
 {
@@ -1480,15 +933,11 @@ static int compose_check(OhEngine *e, const int *dst_ids, int n, const OhCompose
         FAIL(e, OH_E_ARG, "%s: flags 0x%x (0 or OH_COMPOSE_FILL)", who, (unsigned)cp->flags);
     if (cp->n_layers < 0 || cp->n_layers > OH_COMPOSE_MAX_LAYERS || (cp->n_layers && !cp->layers))
         FAIL(e, OH_E_ARG, "%s: n_layers %d (0 .. %d), or no layers", who, cp->n_layers, OH_COMPOSE_MAX_LAYERS);
-    { const int rc = check_pics(e, dst_ids, n, who); if (rc) return rc; }
-    const int other = first_other_params(e, dst_ids, n);
-    if (other < n)
-        FAIL(e, OH_E_ARG, "%s: destination %d has other params than destination %d", who, dst_ids[other], dst_ids[0]);
-    std::vector<int> d(dst_ids, dst_ids + n);
-    std::sort(d.begin(), d.end());
-    if (std::adjacent_find(d.begin(), d.end()) != d.end())
-        FAIL(e, OH_E_ARG, "%s: a destination is listed twice", who);
-    const OhPicParams &dp = get_pic(e, dst_ids[0])->p;
+    const Pic *d0 = alike_pics(e, who, dst_ids, n);
+    if (!d0) return OH_E_ARG;
+    std::vector<int> d;
+    { const int rc = distinct_dsts(e, who, dst_ids, n, &d); if (rc) return rc; }
+    const OhPicParams &dp = d0->p;
     const int cf = dp.chroma_format_idc, sw = 1 << oh_hshift(&dp, 1), sh = 1 << oh_vshift(&dp, 1);
     if (cp->flags & OH_COMPOSE_FILL)
         for (int c = 0; c < (cf ? 3 : 1); c++)
@@ -1529,19 +978,10 @@ static int compose_check(OhEngine *e, const int *dst_ids, int n, const OhCompose
                                        (unsigned __int128)(l.h - 1) * (uint64_t)l.alpha_row_stride +
                                        (unsigned __int128)(l.w - 1) * (uint64_t)l.alpha_pixel_stride;
         HIPCHK(e, hipSetDevice(e->device));
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, l.alpha) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->device) {
-            (void)hipGetLastError();
+        const size_t room = device_room(e, l.alpha);                                       /* bytes from alpha to the allocation's end */
+        if (room == ROOM_NONE)
             FAIL(e, OH_E_ARG, "%s: layer %d: alpha is not device memory of device %d", who, k, e->device);
-        }
-        void *base = nullptr;
-        size_t size = 0;
-        if (hipMemGetAddressRange(&base, &size, const_cast<void *>(l.alpha)) != hipSuccess) {
-            (void)hipGetLastError();
-            continue;
-        }
-        const size_t room = (size_t)((const char *)base + size - (const char *)l.alpha);    /* bytes from alpha to the allocation's end */
-        if (last >= room)
+        if (room != ROOM_UNKNOWN && last >= room)
             FAIL(e, OH_E_ARG, "%s: layer %d: the alpha planes of %d rectangles of %dx%d (strides %lld, %lld, %lld) run past the %zu bytes left of "
                  "their allocation", who, k, n, l.w, l.h, (long long)l.alpha_pixel_stride, (long long)l.alpha_row_stride,
                  (long long)l.alpha_image_stride, room);

@@ -145,7 +145,7 @@ struct OhCpsArgs {
 
 /* picture resizing (resize.hip): what one launch set needs, by value in the kernel arguments like OhConvArgs.  Two plane
  * classes (0 luma, 1 chroma), each with its own geometry and tap tables; the tables live in device memory that the engine owns and
- * fills (engine_pics.hip: oh_pics_resize) on the stream in front of the launches. */
+ * fills (engine_pics.hip: oh_pics_resize, from pics_math.hip: oh_resize_taps) on the stream in front of the launches. */
 enum { OH_RESIZE_VROWS = 8,          /* image rows per workgroup of the vertical pass */
        OH_RESIZE_LDS = 32 << 10,     /* bytes of staged source rows per workgroup of the horizontal pass */
        OH_RESIZE_SPAN = 4096,        /* most source samples of one staged row */

@@ -1,0 +1,19 @@
+/* pics_math.h — what engine_pics.hip uses of the host arithmetic in pics_math.hip beside the library's own entry points
+ * (include/ohevc_hip.h: oh_convert_coeffs, oh_resize_taps, ...).  Internal. */
+#ifndef OHEVC_PICS_MATH_H
+#define OHEVC_PICS_MATH_H
+
+#include <string>
+#include "../../include/ohevc_hip.h"
+
+#ifndef OH_INTERNAL
+#define OH_INTERNAL __attribute__((visibility("hidden")))    /* shared between the library's files, not part of its ABI */
+#endif
+
+OH_INTERNAL bool crop_window_ok(const OhPicParams *p, const OhWindow &w, bool aligned, std::string *why);
+OH_INTERNAL int conv_sample_bytes(const OhConvert *cv, int bit_depth);
+OH_INTERNAL int conv_check(const OhPicParams *p, const OhConvert *cv, size_t *bytes, std::string *why);
+OH_INTERNAL int colour_check(const OhColour *col, std::string *why);
+OH_INTERNAL int colour_build(const OhColour *col, int32_t *tab, int32_t *misc, std::string *why);
+
+#endif

@@ -13,6 +13,7 @@ import torch                                                                # no
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import colour_model as M                                                    # noqa: E402
+import device_room as DR                                                    # noqa: E402
 from openhevc_amd import engine as E                                        # noqa: E402
 from openhevc_amd import frame as F                                         # noqa: E402
 
@@ -260,9 +261,17 @@ def test_argument_errors_write_nothing():
     assert call([pids[0], 999], cv, ok, dst, ib, 2 * ib) == arg             # unknown id
     assert call(pids, E.make_convert("rgb", E.CONV_U8, (1, 0, 0, 0), matrix=9), ok, dst, ib, 2 * ib) == arg
     assert call([], cv, ok, dst, ib, 0) == 0                                # n == 0: nothing to do
+    cv16 = E.make_convert("rgb", E.CONV_U16, matrix=9)
+    assert call(pids[:1], cv16, ok, dst, 2 * ib + 1, 2 * ib + 1) == arg     # stride, dst: multiples of the sample size
+    assert call(pids[:1], cv16, ok, dst + 1, 2 * ib, 2 * ib) == arg
+    # two 16 x 16 pictures into memory whose allocation ends one byte before the second image does
+    small, _ = upload(eng, params(16, 16, 8, 1), ("random", "random"), np.random.default_rng(4))
+    sb = E.convert_image_bytes(params(16, 16, 8, 1), cv)
+    short, stride, claim = DR.one_byte_short(L, 2, sb)
+    assert call(small, cv, ok, short.data_ptr(), stride, claim) == arg
     eng.sync()
     torch.cuda.synchronize()
-    assert bool((buf == 0xA5).all()), "a refused call wrote into the destination"
+    assert bool((buf == 0xA5).all()) and bool((short == 0xA5).all()), "a refused call wrote into the destination"
     # the same buffer taken exactly: the guards around it stay untouched
     assert call(pids, cv, ok, dst, ib, 2 * ib) == 0
     eng.sync()

@@ -13,6 +13,7 @@ import torch                                                                # no
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import convert_model as M                                                   # noqa: E402
+import device_room as DR                                                    # noqa: E402
 import picture_hash as PH                                                   # noqa: E402
 from openhevc_amd import engine as E                                        # noqa: E402
 from openhevc_amd import frame as F                                         # noqa: E402
@@ -336,9 +337,18 @@ def test_argument_errors_write_nothing():
     assert call(pids, E.make_convert("rgb", E.CONV_NATIVE), dst, ib, 2 * ib) == uns
     assert call(pids, E.make_convert("rgb", E.CONV_U8, matrix=4), dst, ib, 2 * ib) == uns
     assert call([], cv, dst, ib, 0) == 0                                    # n == 0: nothing to do
+    cv16 = E.make_convert("rgb", E.CONV_U16)
+    ib16 = E.convert_image_bytes(p, cv16)
+    assert call(pids[:1], cv16, dst, ib16 + 1, ib16 + 1) == arg             # stride, dst: multiples of the sample size
+    assert call(pids[:1], cv16, dst + 1, ib16, ib16) == arg
+    # two 16 x 16 pictures into memory whose allocation ends one byte before the second image does
+    small, _ = upload(eng, params(16, 16, 8, 1), 2, np.random.default_rng(4))
+    sb = E.convert_image_bytes(params(16, 16, 8, 1), cv)
+    short, stride, claim = DR.one_byte_short(L, 2, sb)
+    assert call(small, cv, short.data_ptr(), stride, claim) == arg
     eng.sync()
     torch.cuda.synchronize()
-    assert bool((buf == 0xA5).all()), "a refused call wrote into the destination"
+    assert bool((buf == 0xA5).all()) and bool((short == 0xA5).all()), "a refused call wrote into the destination"
     # the same buffer taken exactly: the guards around it stay untouched
     assert call(pids, cv, dst, ib, 2 * ib) == 0
     eng.sync()

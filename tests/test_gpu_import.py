@@ -14,6 +14,7 @@ import torch                                                                # no
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import convert_model as CM                                                  # noqa: E402
+import device_room as DR                                                    # noqa: E402
 import import_model as IM                                                   # noqa: E402
 import picture_hash as PH                                                   # noqa: E402
 import resize_model as RM                                                   # noqa: E402
@@ -431,7 +432,13 @@ def test_argument_errors_write_nothing():
     assert call(pids, E.make_convert("rgb", E.CONV_U8, matrix=4), src, ib, 2 * ib) == uns
     assert call(pids, E.make_convert("rgb", E.CONV_U8, matrix=0), src, ib, 2 * ib) == uns
     assert call([], cv, src, ib, 0) == 0                                    # n == 0: nothing to do
+    # two 16 x 16 pictures from memory whose allocation ends one byte before the second image does
+    small, _ = upload(eng, params(16, 16, 8, 1), 2, np.random.default_rng(4))
+    before_small = [eng.pics_hash([pid], 0) for pid in small]
+    gone, stride, claim = DR.one_byte_short(eng.L, 2, E.convert_image_bytes(params(16, 16, 8, 1), cv))
+    assert call(small, cv, gone.data_ptr(), stride, claim) == arg
     eng.sync()
+    assert [eng.pics_hash([pid], 0) for pid in small] == before_small
     assert [eng.pics_hash([pid], 0) for pid in everything] == before, "a refused call wrote into a destination"
     # every refusal has the code oh_pics_convert gives for the same combination
     for bad in (E.make_convert("planar", E.CONV_F32), E.make_convert("rgb", E.CONV_NATIVE), E.make_convert("rgb", E.CONV_U8, matrix=4),
