@@ -363,6 +363,34 @@ int      oh_pics_compose(OhEngine *e, const int *dst_ids, int n, const OhCompose
 uint32_t oh_compose_blend(uint32_t dst, uint32_t src, uint32_t alpha, uint32_t opacity);
 uint32_t oh_compose_chroma_alpha(int chroma_format_idc, uint32_t a00, uint32_t a01, uint32_t a10, uint32_t a11);
 
+/* Reformatting of finished pictures (DESIGN.md §3j has the exact definition, which the tests check bit for bit against
+ * tests/reformat_model.py): n finished pictures become n finished pictures of another bit depth (8 / 9 / 10 / 12) and / or another
+ * chroma format (0 .. 3) and the same size — the call to make before oh_pics_resize, oh_pics_compose or oh_pics_compare when their
+ * pictures are not of one kind.  Every destination sample is a weighted sum of source samples of its plane whose weights total 2^f
+ * (f = 0: the sample itself), quantised ONCE by s = f + source depth - destination depth bits: oh_reformat_quantise.  Chroma that is
+ * sub-sampled further takes the co-sited source sample (OH_RF_POINT) or the 1-2-1 filter across and the two rows down of
+ * chroma_sample_loc_type 0 (OH_RF_LINEAR, the filter of oh_pics_import); chroma that is sub-sampled less takes the nearest source sample
+ * (OH_RF_POINT) or the linear filter of oh_pics_convert (OH_RF_LINEAR).  A 4:0:0 destination gets no chroma; from a 4:0:0 source every
+ * chroma sample is 2^(depth - 1).  The whole coded planes are converted, filter taps clamped at the edges of the coded source plane. */
+enum { OH_RF_ROUND = 0, OH_RF_DITHER };          /* depth: round to nearest, or the ordered 4 x 4 dither */
+enum { OH_RF_POINT = 0, OH_RF_LINEAR };          /* chroma_down, chroma_up (0 = point / nearest, 1 = linear, chroma_sample_loc_type 0) */
+typedef struct OhReformat { int32_t depth, chroma_down, chroma_up; } OhReformat;
+/* The n sources with identical OhPicParams, the n destinations with identical params, both of one width and height; bit depth and
+ * chroma format may differ, the other fields are not compared.  Reads each source's finished half, writes half 0 of each destination and
+ * marks it finished, like oh_pics_resize (pictures of oh_pic_wrap like allocated ones).  Enqueued on the engine stream behind the work
+ * that finished the sources, returns without waiting.  The filter that matters is chosen by the direction of the change; the other
+ * field is still checked.  Same depth and same format is a copy of the coded planes.  n == 0: OH_OK.  More than OH_CONV_MAX_PICS
+ * pictures are split into several launches.
+ * OH_E_ARG, nothing written: a null e, rf or id array; an unknown picture; sources (or destinations) whose params differ among
+ * themselves; a width or height that differs between sources and destinations; a picture that is both source and destination, or a
+ * destination listed twice; an enum value outside its list.  No combination gives OH_E_UNSUPPORTED. */
+int     oh_pics_reformat(OhEngine *e, const int *src_ids, const int *dst_ids, int n, const OhReformat *rf);
+/* host only: the very function the kernel evaluates (csrc/reformat_common.h).  s <= 0: min(sum << -s, 2^bd - 1); s > 0:
+ * min((sum + r) >> s, 2^bd - 1) with r = 2^(s - 1) (OH_RF_ROUND) or ((2 t + 1) << s) >> 5 (OH_RF_DITHER), t = B4[y & 3][x & 3],
+ * B4 = {{0,8,2,10},{12,4,14,6},{3,11,1,9},{15,7,13,5}}; (x, y): the sample's place in its destination plane.  sum 0 .. 8 * 4095,
+ * s -4 .. 7. */
+int32_t oh_reformat_quantise(int32_t sum, int s, int depth_mode, int x, int y, int dst_bit_depth);
+
 /* SHVC inter-layer reference picture: resample the finished base-layer picture src_pic into
  * the enhancement-layer picture dst_pic, bit-exact with the reference's whole-picture slot
  * HEVCDSPContext.upsample_base_layer_frame (hevcdsp_template.c:2164-2438, call site hevc.c:3241).

@@ -1,8 +1,9 @@
 /*
  * engine_pics.hip — what the engine does with finished pictures beside the reconstruction path (host side; the kernels are md5.hip,
- * hash.hip, convert.hip, import.hip, colour.hip, light.hip, compare.hip, resize.hip and compose.hip): plane upload and download, the two-phase
- * window fetch, picture hashes, conversion to YUV / RGB images and back, with the colour tables of the HDR forms, light-level statistics,
- * comparison of two pictures, resizing into engine pictures, and composition of pictures in place: fill, overlay, alpha blend.
+ * hash.hip, convert.hip, import.hip, colour.hip, light.hip, compare.hip, resize.hip, reformat.hip and compose.hip): plane upload and download,
+ * the two-phase window fetch, picture hashes, conversion to YUV / RGB images and back, with the colour tables of the HDR forms, light-level
+ * statistics, comparison of two pictures, resizing into engine pictures, reformatting into pictures of another bit depth or chroma format,
+ * and composition of pictures in place: fill, overlay, alpha blend.
  * Their arithmetic, which needs neither an engine nor a device, is pics_math.hip; the helpers at the top are what the services share.
  */
 #include <cmath>
@@ -922,6 +923,63 @@ extern "C" int oh_pics_resize(OhEngine *e, const int *src_ids, const int *dst_id
     { const int rc = stage_in_use(e, sg, e->stream); if (rc) return rc; }
     a.mid = (int16_t *)(d + pl.tab);
     return resize_launch(e, src_ids, dst_ids, n, per_set, rs->width < d0->p.width || rs->height < d0->p.height, &a);
+}
+
+/* ---------------- reformatting: bit depth and chroma format (reformat.hip) ---------------- */
+extern "C" int oh_pics_reformat(OhEngine *e, const int *src_ids, const int *dst_ids, int n, const OhReformat *rf)
+{
+    const char *who = "oh_pics_reformat";
+    if (!e || n < 0 || !rf || (n && (!src_ids || !dst_ids)))
+        return OH_E_ARG;
+    if (rf->depth < OH_RF_ROUND || rf->depth > OH_RF_DITHER)
+        FAIL(e, OH_E_ARG, "%s: depth %d (0 round, 1 dither)", who, rf->depth);
+    if (rf->chroma_down < OH_RF_POINT || rf->chroma_down > OH_RF_LINEAR || rf->chroma_up < OH_RF_POINT || rf->chroma_up > OH_RF_LINEAR)
+        FAIL(e, OH_E_ARG, "%s: chroma_down %d, chroma_up %d (0 point, 1 linear)", who, rf->chroma_down, rf->chroma_up);
+    if (!n)
+        return OH_OK;
+    const Pic *s0 = alike_pics(e, who, src_ids, n);
+    if (!s0) return OH_E_ARG;
+    const Pic *d0 = alike_pics(e, who, dst_ids, n);
+    if (!d0) return OH_E_ARG;
+    {
+        std::vector<int> d;
+        { const int rc = distinct_dsts(e, who, dst_ids, n, &d); if (rc) return rc; }
+        for (int i = 0; i < n; i++)
+            if (std::binary_search(d.begin(), d.end(), src_ids[i]))
+                FAIL(e, OH_E_ARG, "%s: picture %d is both source and destination", who, src_ids[i]);
+    }
+    const OhPicParams &sp = s0->p, &dp = d0->p;
+    if (sp.width != dp.width || sp.height != dp.height)
+        FAIL(e, OH_E_ARG, "%s: sources of %dx%d, destinations of %dx%d", who, sp.width, sp.height, dp.width, dp.height);
+    HIPCHK(e, hipSetDevice(e->device));
+    OhRfArgs a;
+    memset(&a, 0, sizeof(a));
+    const int snp = sp.chroma_format_idc ? 3 : 1, dnp = dp.chroma_format_idc ? 3 : 1;
+    for (int c = 0; c < snp; c++) a.spitch[c] = s0->stride[c] * sample_bytes(sp.bit_depth);
+    for (int c = 0; c < dnp; c++) a.dpitch[c] = d0->stride[c] * sample_bytes(dp.bit_depth);
+    for (int q = 0; q < 2; q++) {
+        a.sw[q] = q < snp ? s0->w[q] : 0; a.sh[q] = q < snp ? s0->h[q] : 0;
+        a.dw[q] = q < dnp ? d0->w[q] : 0; a.dh[q] = q < dnp ? d0->h[q] : 0;
+    }
+    a.scf = sp.chroma_format_idc; a.dcf = dp.chroma_format_idc;
+    a.sbd = sp.bit_depth; a.dbd = dp.bit_depth;
+    a.depth = rf->depth; a.down = rf->chroma_down; a.up = rf->chroma_up;
+    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
+        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+        for (int i = 0; i < m; i++) {
+            const Pic *s = get_pic(e, src_ids[i0 + i]);
+            Pic *q = get_pic(e, dst_ids[i0 + i]);
+            for (int c = 0; c < 3; c++) {
+                a.src[i][c] = c < snp ? final_planes(s)[c] : nullptr;
+                a.dst[i][c] = c < dnp ? q->a[c] : nullptr;
+            }
+            q->final_b = false;                                  /* the image is a finished picture in half 0 */
+            q->done_seq = 0;
+        }
+        ohk_reformat(&a, m, e->stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    return OH_OK;
 }
 
 /* ---------------- composition (compose.hip) ---------------- */

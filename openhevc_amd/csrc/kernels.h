@@ -143,6 +143,21 @@ struct OhCpsArgs {
     int32_t           fill_v[3];
 };
 
+/* picture reformatting (reformat.hip): the finished planes of the sources and half 0 of the destinations of one launch
+ * by value in the kernel arguments; every picture of a launch has the same geometry.  Two plane classes (0 luma, 1 chroma). */
+enum { OH_RF_SEG = 4096 };           /* plane samples per workgroup segment: of the destination row, or of the source row where chroma is
+                                        sub-sampled horizontally on the way (then OH_RF_SEG / 2 destination samples) */
+struct OhRfArgs {
+    const void *src[64][3];          /* OH_CONV_MAX_PICS pictures x planes: the finished halves */
+    void       *dst[64][3];          /* half 0 of the destinations */
+    int32_t     spitch[3], dpitch[3];/* bytes between rows of each plane */
+    int32_t     sw[2], sh[2];        /* coded size of the source planes (sw[1] = 0: 4:0:0) */
+    int32_t     dw[2], dh[2];        /* coded size of the destination planes (dw[1] = 0: 4:0:0) */
+    int32_t     scf, dcf;            /* chroma_format_idc of sources and destinations */
+    int32_t     sbd, dbd;            /* bit depths */
+    int32_t     depth, down, up;     /* OhReformat */
+};
+
 /* picture resizing (resize.hip): what one launch set needs, by value in the kernel arguments like OhConvArgs.  Two plane
  * classes (0 luma, 1 chroma), each with its own geometry and tap tables; the tables live in device memory that the engine owns and
  * fills (engine_pics.hip: oh_pics_resize, from pics_math.hip: oh_resize_taps) on the stream in front of the launches. */
@@ -194,6 +209,8 @@ void ohk_light(const OhLightArgs *a, int n, hipStream_t st);
 void ohk_compare(const OhCmpArgs *a, int n, hipStream_t st);
 /* n destinations of a.dst, composed in place: a.layers over what they hold, or over a.fill_v */
 void ohk_compose(const OhCpsArgs *a, int n, hipStream_t st);
+/* n sources of a.src into the n destinations of a.dst */
+void ohk_reformat(const OhRfArgs *a, int n, hipStream_t st);
 void ohk_hash(int kind, const OhMd5Job *jobs, const uint32_t *first, const uint32_t *task_map, int n_jobs, int n_tasks, uint32_t *partials,
               uint32_t *out, hipStream_t st);
 void ohk_inter(const OhBatch *B, int n, const OhPicParams *p, uint32_t max_luma, uint32_t max_chroma, hipStream_t st);

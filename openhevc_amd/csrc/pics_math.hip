@@ -1,7 +1,7 @@
 /*
  * pics_math.hip — the host arithmetic of the picture services (engine_pics.hip), with neither an engine nor a device: image sizes and
  * crop windows, the integers of the RGB conversions, the colour tables of the HDR forms, light-level bins and percentiles, the SSIM window
- * and PSNR, the resize taps, the compose formulas.  No kernel, no HIP runtime call: tests/pics_math_check.cpp runs it under sanitizers.
+ * and PSNR, the resize taps, the compose formulas, the reformat quantisation.  No kernel, no HIP runtime call: tests/pics_math_check.cpp runs it under sanitizers.
  */
 #include <stdio.h>
 #include <string.h>
@@ -13,6 +13,7 @@
 #include "kernels.h"
 #include "compare_common.h"
 #include "compose_common.h"
+#include "reformat_common.h"
 
 static bool depth_ok(int bit_depth) { return bit_depth == 8 || bit_depth == 9 || bit_depth == 10 || bit_depth == 12; }
 
@@ -535,4 +536,10 @@ extern "C" uint32_t oh_compose_blend(uint32_t dst, uint32_t src, uint32_t alpha,
 extern "C" uint32_t oh_compose_chroma_alpha(int chroma_format_idc, uint32_t a00, uint32_t a01, uint32_t a10, uint32_t a11)
 {
     return compose_chroma_alpha(chroma_format_idc, a00, a01, a10, a11);
+}
+
+/* ---------------- reformatting (reformat.hip) ---------------- */
+extern "C" int32_t oh_reformat_quantise(int32_t sum, int s, int depth_mode, int x, int y, int dst_bit_depth)
+{
+    return reformat_quantise(sum, s, depth_mode, x, y, dst_bit_depth);
 }

@@ -318,6 +318,30 @@ def compose_chroma_alpha(chroma_format_idc, a00, a01, a10, a11):
     return int(lib().oh_compose_chroma_alpha(int(chroma_format_idc), int(a00), int(a01), int(a10), int(a11)))
 
 
+class OhReformat(C.Structure):                                # include/ohevc_hip.h
+    _fields_ = [("depth", C.c_int32), ("chroma_down", C.c_int32), ("chroma_up", C.c_int32)]
+
+
+RF_DEPTH = {"round": 0, "dither": 1}                                                    # OH_RF_ROUND, OH_RF_DITHER
+RF_FILTERS = {"point": 0, "nearest": 0, "linear": 1}                                    # OH_RF_POINT, OH_RF_LINEAR
+RF_SEG = 4096                                                                          # OH_RF_SEG (csrc/kernels.h): plane samples per workgroup segment
+
+
+def _rf_enum(table, what, v):
+    """a name of table or its OH_RF_* number -> the number"""
+    if isinstance(v, str):
+        if v not in table:
+            raise ValueError(f"unknown {what} {v!r}: one of {sorted(table)}")
+        return table[v]
+    return int(v)
+
+
+def reformat_quantise(sum, s, mode, x, y, bit_depth):
+    """oh_reformat_quantise (host only): a weighted sum of source samples -> the destination sample of bit_depth bits, shifted down by s
+    bits with one rounding (mode "round" or "dither", or its number) at place (x, y) of its plane, by the function the kernel evaluates"""
+    return int(lib().oh_reformat_quantise(int(sum), int(s), _rf_enum(RF_DEPTH, "depth mode", mode), int(x), int(y), int(bit_depth)))
+
+
 def convert_image_bytes(params, cv):
     """oh_convert_image_bytes (host only): bytes of one image, 0 when the combination is not valid"""
     return int(lib().oh_convert_image_bytes(C.byref(params), C.byref(cv)))
@@ -413,6 +437,9 @@ def lib():
         L.oh_compose_blend.restype = C.c_uint32
         L.oh_compose_chroma_alpha.argtypes = [I] + [C.c_uint32] * 4
         L.oh_compose_chroma_alpha.restype = C.c_uint32
+        L.oh_pics_reformat.argtypes = [V, C.POINTER(C.c_int), C.POINTER(C.c_int), I, C.POINTER(OhReformat)]
+        L.oh_reformat_quantise.argtypes = [C.c_int32, I, I, I, I, I]
+        L.oh_reformat_quantise.restype = C.c_int32
         L.oh_pics_resize.argtypes = [V, C.POINTER(C.c_int), C.POINTER(C.c_int), I, C.POINTER(OhResize)]
         L.oh_resize_taps.argtypes = [I, I, I, I, C.POINTER(C.c_int32), C.POINTER(C.c_int16), I, C.POINTER(C.c_int)]
         L.oh_resize_max_taps.argtypes = [I, I, I]
@@ -819,6 +846,43 @@ class Engine:
         self._chk(rc, "oh_pics_resize")
         dp = self._pic_params(out[0])
         return out, (0, dp.width - width, 0, dp.height - height)
+
+    def pics_reformat(self, pids, *, bit_depth=None, chroma_format_idc=None, depth="round", down="linear", up="linear", out=None):
+        """finished pictures -> finished pictures of another bit depth and / or chroma format and the same size (oh_pics_reformat):
+        depth "round" or "dither" (the ordered 4 x 4 dither) where bits go; down "point" or "linear" where chroma is sub-sampled
+        further (the 1-2-1 filter of chroma_sample_loc_type 0), up "nearest" or "linear" where it is sub-sampled less.  out: destination
+        pictures to reuse, of any depth and format; None allocates pictures with the sources' params, bit_depth / chroma_format_idc
+        replaced where given.  Returns the destination ids.  Enqueued on the engine stream; does not wait."""
+        pids = list(pids)
+        n = len(pids)
+        rf = OhReformat(_rf_enum(RF_DEPTH, "depth mode", depth), _rf_enum(RF_FILTERS, "down filter", down), _rf_enum(RF_FILTERS, "up filter", up))
+        fresh = out is None
+        if fresh:
+            if n == 0:
+                return []
+            dp = F.OhPicParams.from_buffer_copy(self._pic_params(pids[0]))
+            if bit_depth is not None:
+                dp.bit_depth = int(bit_depth)
+            if chroma_format_idc is not None:
+                dp.chroma_format_idc = int(chroma_format_idc)
+            out = []
+            try:
+                for _ in range(n):
+                    out.append(self.pic_alloc(dp))
+            except Exception:
+                for pid in out:
+                    self.pic_free(pid)
+                raise
+        else:
+            out = list(out)
+            if len(out) != n:
+                raise ValueError(f"out: {len(out)} pictures for {n} sources")
+        rc = self.L.oh_pics_reformat(self.h, (C.c_int * max(n, 1))(*pids), (C.c_int * max(n, 1))(*out), n, C.byref(rf))
+        if rc != 0 and fresh:
+            for pid in out:
+                self.pic_free(pid)
+        self._chk(rc, "oh_pics_reformat")
+        return out
 
     def pics_compose(self, dst, layers, *, fill=None):
         """finished pictures composed in place on the GPU (oh_pics_compose): dst, the destination ids (identical params); layers, a
