@@ -77,6 +77,23 @@ typedef struct OhHdrSei {
  * than its fields. */
 int oh_sei_hdr(const uint8_t *nal, size_t size, OhHdrSei *out);
 
+/* The display orientation message of H.265 Annex D (payload type 47), which the reference passes over like the HDR messages: how the
+ * decoded picture is meant to be flipped and turned for display.  Bits, MSB first: display_orientation_cancel_flag u(1); unless
+ * cancelled hor_flip u(1), ver_flip u(1), anticlockwise_rotation u(16), display_orientation_persistence_flag u(1) — 20 bits, a payload
+ * of 3 bytes with its alignment bits; a cancelled message takes 1 byte.  oh_orient_from_sei (ohevc_hip.h) turns the fields into an
+ * orientation of oh_pics_orient. */
+typedef struct OhDisplayOrientation {
+    int32_t  present;                 /* a message was found */
+    int32_t  cancel;                  /* display_orientation_cancel_flag; the fields below are 0 then */
+    int32_t  hor_flip, ver_flip;
+    uint32_t anticlockwise_rotation;  /* u(16), units of 360 / 65536 degrees */
+    int32_t  persistence;
+} OhDisplayOrientation;
+/* nal[0 .. size): one (escaped) SEI NAL unit, header first.  The same message walk as oh_sei_hdr.  The message counts in a prefix SEI
+ * only; in a suffix SEI it is passed over; of several in one unit the last counts.  Returns 1 found, 0 none (*out is zero), or -1: not
+ * an SEI NAL unit, a message that runs past the unit, or a display orientation with a payload shorter than its fields. */
+int oh_sei_display_orientation(const uint8_t *nal, size_t size, OhDisplayOrientation *out);
+
 #ifdef __cplusplus
 }
 #endif

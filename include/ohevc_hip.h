@@ -391,6 +391,50 @@ int     oh_pics_reformat(OhEngine *e, const int *src_ids, const int *dst_ids, in
  * s -4 .. 7. */
 int32_t oh_reformat_quantise(int32_t sum, int s, int depth_mode, int x, int y, int dst_bit_depth);
 
+/* Orientation of finished pictures (DESIGN.md §3k has the exact definition, which the tests check bit for bit against
+ * tests/orient_model.py): n finished pictures become n finished pictures that hold a window of them cropped, mirrored, turned by
+ * quarter turns or transposed — what a display-orientation SEI (oh_sei_display_orientation, ohevc_annexb.h), the mirrored view of a
+ * frame-packed pair or a portrait rendition asks for, without leaving YUV.  A permutation of stored samples.  Per plane c, S is the
+ * plane's window: win shifted by oh_hshift / oh_vshift, Ws x Hs samples.
+ *   1. OH_ORIENT_TRANSPOSE first:  T[y][x] = S[x][y] (Wt = Hs, Ht = Ws); without it T = S;
+ *   2. OH_ORIENT_HFLIP next:       U[y][x] = T[y][Wt - 1 - x]; without it U = T;
+ *   3. OH_ORIENT_VFLIP last:       I[y][x] = U[Ht - 1 - y][x]; without it I = U.
+ * So 3 is a half turn, 5 (TRANSPOSE | HFLIP) a quarter turn clockwise, 6 (TRANSPOSE | VFLIP) a quarter turn anticlockwise and 7 the
+ * anti-transpose.  The image I takes the top left of the destination plane; the rest of the destination's coded plane replicates I's
+ * last column and last row, D[y][x] = I[min(y, Hi - 1)][min(x, Wi - 1)], as oh_pics_resize does, so the whole picture is defined and
+ * hashes.  Samples are copied as stored: chroma is not re-filtered, so a mirrored 4:2:0 or 4:2:2 picture keeps its chroma samples and
+ * their nominal siting moves by half a luma sample. */
+enum { OH_ORIENT_HFLIP = 1, OH_ORIENT_VFLIP = 2, OH_ORIENT_TRANSPOSE = 4 };   /* orientation: any OR of these, 0 .. 7 */
+typedef struct OhOrient {
+    int32_t  orientation;   /* 0 .. 7 */
+    OhWindow win;           /* source window, luma samples, rules as for oh_pics_convert */
+} OhOrient;
+/* The n sources with identical OhPicParams, the n destinations with identical params, of the sources' bit depth and chroma format and
+ * of any size that holds the image.  Reads each source's finished half, writes half 0 of each destination and marks it finished, like
+ * oh_pics_resize (pictures of oh_pic_wrap like allocated ones).  Enqueued on the engine stream behind the work that finished the
+ * sources, returns without waiting.  n == 0: OH_OK.  More than OH_CONV_MAX_PICS pictures are split into several launches.
+ * OH_E_ARG, nothing written: a null e, o or id array, or a negative n; an unknown picture; sources (or destinations) whose params
+ * differ among themselves; a picture that is both source and destination, or a destination listed twice; an orientation outside
+ * 0 .. 7; an empty window or one whose offsets are not multiples of SubWidthC / SubHeightC; an image (the window, its sides swapped
+ * under OH_ORIENT_TRANSPOSE) wider or taller than the destination's coded size.
+ * OH_E_UNSUPPORTED, nothing written: destinations of another bit depth or chroma format than the sources (oh_pics_reformat first);
+ * OH_ORIENT_TRANSPOSE on 4:2:2 pictures, whose result would be 4:4:0 (reformat to 4:2:0 or 4:4:4 first).  Orientations 0 .. 3 are
+ * fine on 4:2:2. */
+int oh_pics_orient(OhEngine *e, const int *src_ids, const int *dst_ids, int n, const OhOrient *o);
+/* host only: the one orientation equal to applying `first`, then `second` (to the image of `first`); -1 outside 0 .. 7 */
+int oh_orient_then(int first, int second);
+/* host only: the orientation that undoes `orientation`: oh_orient_then(o, oh_orient_inverse(o)) == 0; -1 outside 0 .. 7 */
+int oh_orient_inverse(int orientation);
+/* host only: the size of the image of a w x h window: swapped under OH_ORIENT_TRANSPOSE.  OH_E_ARG: an orientation outside 0 .. 7, a
+ * size below 1, a null pointer. */
+int oh_orient_size(int orientation, int w, int h, int *ow, int *oh);
+/* host only: the orientation that a display orientation SEI message recommends.  This comment is the contract: the message's flips
+ * come first, then the anticlockwise rotation of the flipped picture, so the result is oh_orient_then((hor_flip ? 1 : 0) |
+ * (ver_flip ? 2 : 0), R^k) with R = 6, a quarter turn anticlockwise, applied k = anticlockwise_rotation >> 14 times (the field counts
+ * in units of 360 / 2^16 degrees).  OH_E_UNSUPPORTED: anticlockwise_rotation & 0x3FFF is not 0 — an angle that is no quarter turn
+ * needs a resampler.  OH_E_ARG: a null pointer, a flag outside 0 / 1, a rotation of 2^16 or more. */
+int oh_orient_from_sei(int hor_flip, int ver_flip, uint32_t anticlockwise_rotation, int *orientation);
+
 /* SHVC inter-layer reference picture: resample the finished base-layer picture src_pic into
  * the enhancement-layer picture dst_pic, bit-exact with the reference's whole-picture slot
  * HEVCDSPContext.upsample_base_layer_frame (hevcdsp_template.c:2164-2438, call site hevc.c:3241).

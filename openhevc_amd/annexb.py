@@ -1,4 +1,4 @@
-"""ctypes view of include/ohevc_annexb.h (libohevc_host.so): access-unit splitter, NAL scan, NAL unescape, picture-hash SEI, HDR SEIs."""
+"""ctypes view of include/ohevc_annexb.h (libohevc_host.so): access-unit splitter, NAL scan, NAL unescape, picture-hash SEI, HDR SEIs, display-orientation SEI."""
 import ctypes as C
 import os
 
@@ -25,6 +25,11 @@ class OhHdrSei(C.Structure):
                 ("has_alt_transfer", C.c_int32), ("preferred_transfer", C.c_int32)]
 
 
+class OhDisplayOrientation(C.Structure):
+    _fields_ = [("present", C.c_int32), ("cancel", C.c_int32), ("hor_flip", C.c_int32), ("ver_flip", C.c_int32),
+                ("anticlockwise_rotation", C.c_uint32), ("persistence", C.c_int32)]
+
+
 _lib = None
 
 
@@ -49,6 +54,8 @@ def lib():
         L.oh_sei_picture_hash.restype = C.c_int
         L.oh_sei_hdr.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(OhHdrSei)]
         L.oh_sei_hdr.restype = C.c_int
+        L.oh_sei_display_orientation.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(OhDisplayOrientation)]
+        L.oh_sei_display_orientation.restype = C.c_int
         _lib = L
     return _lib
 
@@ -124,3 +131,18 @@ def hdr_sei(nal):
     if h.has_alt_transfer:
         d["preferred_transfer"] = int(h.preferred_transfer)
     return d
+
+
+def display_orientation(nal):
+    """None, or a dict of the display-orientation message (payload type 47) of one prefix SEI NAL unit (oh_sei_display_orientation):
+    "cancel", "hor_flip", "ver_flip" (bool), "anticlockwise_rotation" (0 .. 65535, units of 360 / 65536 degrees), "persistence"; the
+    fields behind "cancel" are False / 0 in a cancelled message.  engine.orientation_from_sei turns the flips and the rotation into
+    an orientation of Engine.pics_orient."""
+    d = OhDisplayOrientation()
+    r = lib().oh_sei_display_orientation(nal, len(nal), C.byref(d))
+    if r < 0:
+        raise ValueError("malformed SEI NAL unit")
+    if not r:
+        return None
+    return dict(cancel=bool(d.cancel), hor_flip=bool(d.hor_flip), ver_flip=bool(d.ver_flip),
+                anticlockwise_rotation=int(d.anticlockwise_rotation), persistence=bool(d.persistence))

@@ -250,3 +250,35 @@ int oh_sei_hdr(const uint8_t *nal, size_t size, OhHdrSei *out)
     }
     return out->has_mastering + out->has_cll + out->has_alt_transfer;
 }
+
+static int disp_msg(void *ctx, int nut, unsigned type, const uint8_t *q, unsigned len)
+{
+    OhDisplayOrientation *out = (OhDisplayOrientation *)ctx;
+    if (nut != NAL_SEI_PREFIX || type != 47)                  /* D.2.17 display_orientation */
+        return 0;
+    if (len < 1)
+        return -1;
+    memset(out, 0, sizeof(*out));                             /* the last message of the unit counts */
+    out->present = 1;
+    out->cancel = q[0] >> 7;
+    if (out->cancel)
+        return 0;
+    if (len < 3)                                              /* cancel, two flips, u(16), persistence: 20 bits */
+        return -1;
+    const uint32_t bits = ((uint32_t)q[0] << 16) | ((uint32_t)q[1] << 8) | q[2];
+    out->hor_flip = (bits >> 22) & 1;
+    out->ver_flip = (bits >> 21) & 1;
+    out->anticlockwise_rotation = (bits >> 5) & 0xFFFF;
+    out->persistence = (bits >> 4) & 1;
+    return 0;
+}
+
+int oh_sei_display_orientation(const uint8_t *nal, size_t size, OhDisplayOrientation *out)
+{
+    memset(out, 0, sizeof(*out));
+    if (sei_walk(nal, size, disp_msg, out) < 0) {
+        memset(out, 0, sizeof(*out));
+        return -1;
+    }
+    return out->present;
+}

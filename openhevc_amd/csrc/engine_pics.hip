@@ -1,8 +1,8 @@
 /*
  * engine_pics.hip — what the engine does with finished pictures beside the reconstruction path (host side; the kernels are md5.hip,
- * hash.hip, convert.hip, import.hip, colour.hip, light.hip, compare.hip, resize.hip, reformat.hip and compose.hip): plane upload and download,
+ * hash.hip, convert.hip, import.hip, colour.hip, light.hip, compare.hip, resize.hip, reformat.hip, orient.hip and compose.hip): plane upload and download,
  * the two-phase window fetch, picture hashes, conversion to YUV / RGB images and back, with the colour tables of the HDR forms, light-level
- * statistics, comparison of two pictures, resizing into engine pictures, reformatting into pictures of another bit depth or chroma format,
+ * statistics, comparison of two pictures, resizing into engine pictures, reformatting into pictures of another bit depth or chroma format, orientation (crop, flip, quarter turns, transpose),
  * and composition of pictures in place: fill, overlay, alpha blend.
  * Their arithmetic, which needs neither an engine nor a device, is pics_math.hip; the helpers at the top are what the services share.
  */
@@ -977,6 +977,72 @@ extern "C" int oh_pics_reformat(OhEngine *e, const int *src_ids, const int *dst_
             q->done_seq = 0;
         }
         ohk_reformat(&a, m, e->stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    return OH_OK;
+}
+
+/* ---------------- orientation: crop, flip, rotate, transpose (orient.hip) ---------------- */
+extern "C" int oh_pics_orient(OhEngine *e, const int *src_ids, const int *dst_ids, int n, const OhOrient *o)
+{
+    const char *who = "oh_pics_orient";
+    if (!e || n < 0 || !o || (n && (!src_ids || !dst_ids)))
+        return OH_E_ARG;
+    if (o->orientation < 0 || o->orientation > 7)
+        FAIL(e, OH_E_ARG, "%s: orientation %d (0 .. 7: any OR of HFLIP 1, VFLIP 2, TRANSPOSE 4)", who, o->orientation);
+    if (!n)
+        return OH_OK;
+    const Pic *s0 = alike_pics(e, who, src_ids, n);
+    if (!s0) return OH_E_ARG;
+    const Pic *d0 = alike_pics(e, who, dst_ids, n);
+    if (!d0) return OH_E_ARG;
+    {
+        std::vector<int> d;
+        { const int rc = distinct_dsts(e, who, dst_ids, n, &d); if (rc) return rc; }
+        for (int i = 0; i < n; i++)
+            if (std::binary_search(d.begin(), d.end(), src_ids[i]))
+                FAIL(e, OH_E_ARG, "%s: picture %d is both source and destination", who, src_ids[i]);
+    }
+    const OhPicParams &sp = s0->p, &dp = d0->p;
+    const OhWindow &w = o->win;
+    std::string why;
+    if (!crop_window_ok(&sp, w, true, &why))
+        FAIL(e, OH_E_ARG, "%s: %s", who, why.c_str());
+    const int cf = sp.chroma_format_idc, hs = cf == 1 || cf == 2, vs = cf == 1, bpp = sample_bytes(sp.bit_depth);
+    if (dp.bit_depth != sp.bit_depth || dp.chroma_format_idc != cf)
+        FAIL(e, OH_E_UNSUPPORTED, "%s: destinations of %d bit, chroma format %d; sources of %d bit, chroma format %d (oh_pics_reformat first)", who,
+             dp.bit_depth, dp.chroma_format_idc, sp.bit_depth, cf);
+    const bool tr = o->orientation & OH_ORIENT_TRANSPOSE;
+    if (tr && cf == 2)
+        FAIL(e, OH_E_UNSUPPORTED, "%s: orientation %d transposes 4:2:2 pictures into 4:4:0 (reformat to 4:2:0 or 4:4:4 first)", who, o->orientation);
+    const int W = sp.width - w.left - w.right, H = sp.height - w.top - w.bottom;
+    int iw = 0, ih = 0;
+    (void)oh_orient_size(o->orientation, W, H, &iw, &ih);
+    if (iw > dp.width || ih > dp.height)
+        FAIL(e, OH_E_ARG, "%s: the image of %dx%d does not fit the destinations' %dx%d", who, iw, ih, dp.width, dp.height);
+    HIPCHK(e, hipSetDevice(e->device));
+    OhOrArgs a;
+    memset(&a, 0, sizeof(a));
+    a.np = cf ? 3 : 1; a.bd = sp.bit_depth; a.orientation = o->orientation;
+    for (int c = 0; c < a.np; c++) { a.spitch[c] = s0->stride[c] * bpp; a.dpitch[c] = d0->stride[c] * bpp; }
+    for (int q = 0; q < (cf ? 2 : 1); q++) {
+        a.x0[q] = w.left >> (q ? hs : 0); a.y0[q] = w.top >> (q ? vs : 0);
+        a.ws[q] = W >> (q ? hs : 0); a.hs[q] = H >> (q ? vs : 0);
+        a.dw[q] = d0->w[q]; a.dh[q] = d0->h[q];
+    }
+    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
+        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+        for (int i = 0; i < m; i++) {
+            const Pic *s = get_pic(e, src_ids[i0 + i]);
+            Pic *q = get_pic(e, dst_ids[i0 + i]);
+            for (int c = 0; c < 3; c++) {
+                a.src[i][c] = c < a.np ? final_planes(s)[c] : nullptr;
+                a.dst[i][c] = c < a.np ? q->a[c] : nullptr;
+            }
+            q->final_b = false;                                  /* the image is a finished picture in half 0 */
+            q->done_seq = 0;
+        }
+        ohk_orient(&a, m, e->stream);
         HIPCHK(e, hipGetLastError());
     }
     return OH_OK;

@@ -158,6 +158,21 @@ struct OhRfArgs {
     int32_t     depth, down, up;     /* OhReformat */
 };
 
+/* picture orientation (orient.hip): the finished planes of the sources and half 0 of the destinations of one launch by
+ * value in the kernel arguments; every picture of a launch has the same geometry.  Two plane classes (0 luma, 1 chroma). */
+enum { OH_OR_TILE = 64,              /* edge of the square tile of destination samples that one workgroup of the transposing kernel makes */
+       OH_OR_SEG = 4096 };           /* destination samples of one row per workgroup of the row kernel (orientations 0 .. 3) */
+struct OhOrArgs {
+    const void *src[64][3];          /* OH_CONV_MAX_PICS pictures x planes: the finished halves */
+    void       *dst[64][3];          /* half 0 of the destinations */
+    int32_t     spitch[3], dpitch[3];/* bytes between rows of each plane */
+    int32_t     x0[2], y0[2];        /* origin of the plane's window S in the source plane */
+    int32_t     ws[2], hs[2];        /* size of S, plane samples */
+    int32_t     dw[2], dh[2];        /* coded size of the destination planes */
+    int32_t     np, bd;              /* planes: 1 or 3; bit depth */
+    int32_t     orientation;         /* OH_ORIENT_* bits */
+};
+
 /* picture resizing (resize.hip): what one launch set needs, by value in the kernel arguments like OhConvArgs.  Two plane
  * classes (0 luma, 1 chroma), each with its own geometry and tap tables; the tables live in device memory that the engine owns and
  * fills (engine_pics.hip: oh_pics_resize, from pics_math.hip: oh_resize_taps) on the stream in front of the launches. */
@@ -211,6 +226,8 @@ void ohk_compare(const OhCmpArgs *a, int n, hipStream_t st);
 void ohk_compose(const OhCpsArgs *a, int n, hipStream_t st);
 /* n sources of a.src into the n destinations of a.dst */
 void ohk_reformat(const OhRfArgs *a, int n, hipStream_t st);
+/* n sources of a.src, oriented, into the n destinations of a.dst */
+void ohk_orient(const OhOrArgs *a, int n, hipStream_t st);
 void ohk_hash(int kind, const OhMd5Job *jobs, const uint32_t *first, const uint32_t *task_map, int n_jobs, int n_tasks, uint32_t *partials,
               uint32_t *out, hipStream_t st);
 void ohk_inter(const OhBatch *B, int n, const OhPicParams *p, uint32_t max_luma, uint32_t max_chroma, hipStream_t st);

@@ -1,7 +1,7 @@
 /*
  * pics_math.hip — the host arithmetic of the picture services (engine_pics.hip), with neither an engine nor a device: image sizes and
  * crop windows, the integers of the RGB conversions, the colour tables of the HDR forms, light-level bins and percentiles, the SSIM window
- * and PSNR, the resize taps, the compose formulas, the reformat quantisation.  No kernel, no HIP runtime call: tests/pics_math_check.cpp runs it under sanitizers.
+ * and PSNR, the resize taps, the compose formulas, the reformat quantisation, the orientations' group.  No kernel, no HIP runtime call: tests/pics_math_check.cpp runs it under sanitizers.
  */
 #include <stdio.h>
 #include <string.h>
@@ -542,4 +542,65 @@ extern "C" uint32_t oh_compose_chroma_alpha(int chroma_format_idc, uint32_t a00,
 extern "C" int32_t oh_reformat_quantise(int32_t sum, int s, int depth_mode, int x, int y, int dst_bit_depth)
 {
     return reformat_quantise(sum, s, depth_mode, x, y, dst_bit_depth);
+}
+
+/* ---------------- orientation (orient.hip) ---------------- */
+/* the definition on a small array whose samples all differ: transpose, then the horizontal flip, then the vertical one */
+namespace {
+struct Grid { int w, h, v[6]; };
+const Grid GRID0 = { 3, 2, { 0, 1, 2, 3, 4, 5 } };
+Grid grid_orient(const Grid &s, int o)
+{
+    Grid d = s;
+    if (o & OH_ORIENT_TRANSPOSE) { d.w = s.h; d.h = s.w; }
+    for (int y = 0; y < d.h; y++)
+        for (int x = 0; x < d.w; x++) {
+            const int ty = (o & OH_ORIENT_VFLIP) ? d.h - 1 - y : y, tx = (o & OH_ORIENT_HFLIP) ? d.w - 1 - x : x;
+            d.v[y * d.w + x] = (o & OH_ORIENT_TRANSPOSE) ? s.v[tx * s.w + ty] : s.v[ty * s.w + tx];
+        }
+    return d;
+}
+}
+
+extern "C" int oh_orient_then(int first, int second)
+{
+    if (first < 0 || first > 7 || second < 0 || second > 7)
+        return -1;
+    const Grid want = grid_orient(grid_orient(GRID0, first), second);
+    for (int o = 0; o < 8; o++) {
+        const Grid g = grid_orient(GRID0, o);
+        if (g.w == want.w && g.h == want.h && !memcmp(g.v, want.v, sizeof(g.v)))
+            return o;
+    }
+    return -1;
+}
+
+extern "C" int oh_orient_inverse(int orientation)
+{
+    for (int o = 0; o < 8; o++)
+        if (oh_orient_then(orientation, o) == 0)
+            return o;
+    return -1;
+}
+
+extern "C" int oh_orient_size(int orientation, int w, int h, int *ow, int *oh)
+{
+    if (orientation < 0 || orientation > 7 || w < 1 || h < 1 || !ow || !oh)
+        return OH_E_ARG;
+    const bool t = orientation & OH_ORIENT_TRANSPOSE;
+    *ow = t ? h : w; *oh = t ? w : h;
+    return OH_OK;
+}
+
+extern "C" int oh_orient_from_sei(int hor_flip, int ver_flip, uint32_t anticlockwise_rotation, int *orientation)
+{
+    if (!orientation || hor_flip < 0 || hor_flip > 1 || ver_flip < 0 || ver_flip > 1 || anticlockwise_rotation > 0xFFFFu)
+        return OH_E_ARG;
+    if (anticlockwise_rotation & 0x3FFF)
+        return OH_E_UNSUPPORTED;
+    int o = (hor_flip ? OH_ORIENT_HFLIP : 0) | (ver_flip ? OH_ORIENT_VFLIP : 0);
+    for (uint32_t k = anticlockwise_rotation >> 14; k; k--)
+        o = oh_orient_then(o, OH_ORIENT_TRANSPOSE | OH_ORIENT_VFLIP);
+    *orientation = o;
+    return OH_OK;
 }

@@ -342,6 +342,61 @@ def reformat_quantise(sum, s, mode, x, y, bit_depth):
     return int(lib().oh_reformat_quantise(int(sum), int(s), _rf_enum(RF_DEPTH, "depth mode", mode), int(x), int(y), int(bit_depth)))
 
 
+class OhOrient(C.Structure):                                  # include/ohevc_hip.h
+    _fields_ = [("orientation", C.c_int32), ("win", OhWindow)]
+
+
+ORIENT_HFLIP, ORIENT_VFLIP, ORIENT_TRANSPOSE = 1, 2, 4                                  # OH_ORIENT_*: an orientation is any OR of these
+ORIENTATIONS = {"identity": 0, "hflip": 1, "vflip": 2, "rot180": 3, "transpose": 4, "rot90": 5, "rot270": 6, "antitranspose": 7}
+ORIENT_TILE = 64                                                                        # OH_OR_TILE (csrc/kernels.h): edge of the transposing kernel's tile
+
+
+def orient_code(v):
+    """a name of ORIENTATIONS ("rot90" is clockwise) or an int 0 .. 7 -> the int"""
+    if isinstance(v, str):
+        if v not in ORIENTATIONS:
+            raise ValueError(f"unknown orientation {v!r}: one of {sorted(ORIENTATIONS)}")
+        return ORIENTATIONS[v]
+    v = int(v)
+    if not 0 <= v <= 7:
+        raise ValueError(f"orientation {v}: 0 .. 7")
+    return v
+
+
+def orient_then(first, second):
+    """oh_orient_then (host only): the one orientation equal to applying first, then second"""
+    return int(lib().oh_orient_then(orient_code(first), orient_code(second)))
+
+
+def orient_inverse(o):
+    """oh_orient_inverse (host only): the orientation that undoes o"""
+    return int(lib().oh_orient_inverse(orient_code(o)))
+
+
+def orient_size(o, width, height):
+    """oh_orient_size (host only): (width, height) of the image of a width x height window: swapped under TRANSPOSE"""
+    ow, oh = C.c_int(), C.c_int()
+    rc = lib().oh_orient_size(orient_code(o), int(width), int(height), C.byref(ow), C.byref(oh))
+    if rc != 0:
+        err = EngineError(f"oh_orient_size failed ({rc})")
+        err.code = rc
+        raise err
+    return ow.value, oh.value
+
+
+def orientation_from_sei(hor_flip, ver_flip, anticlockwise_rotation):
+    """oh_orient_from_sei (host only): the orientation a display-orientation SEI message recommends (annexb.display_orientation has
+    its fields): the flips, then the anticlockwise rotation of the flipped picture, in units of 360 / 65536 degrees.  EngineError with
+    code OH_E_UNSUPPORTED for an angle that is no quarter turn."""
+    o = C.c_int()
+    rc = lib().oh_orient_from_sei(int(hor_flip), int(ver_flip), int(anticlockwise_rotation), C.byref(o))
+    if rc != 0:
+        err = EngineError(f"oh_orient_from_sei({hor_flip}, {ver_flip}, {anticlockwise_rotation:#x}) failed ({rc})")
+        err.code = rc
+        raise err
+    return o.value
+
+
 def convert_image_bytes(params, cv):
     """oh_convert_image_bytes (host only): bytes of one image, 0 when the combination is not valid"""
     return int(lib().oh_convert_image_bytes(C.byref(params), C.byref(cv)))
@@ -440,6 +495,11 @@ def lib():
         L.oh_pics_reformat.argtypes = [V, C.POINTER(C.c_int), C.POINTER(C.c_int), I, C.POINTER(OhReformat)]
         L.oh_reformat_quantise.argtypes = [C.c_int32, I, I, I, I, I]
         L.oh_reformat_quantise.restype = C.c_int32
+        L.oh_pics_orient.argtypes = [V, C.POINTER(C.c_int), C.POINTER(C.c_int), I, C.POINTER(OhOrient)]
+        L.oh_orient_then.argtypes = [I, I]
+        L.oh_orient_inverse.argtypes = [I]
+        L.oh_orient_size.argtypes = [I, I, I, C.POINTER(I), C.POINTER(I)]
+        L.oh_orient_from_sei.argtypes = [I, I, C.c_uint32, C.POINTER(I)]
         L.oh_pics_resize.argtypes = [V, C.POINTER(C.c_int), C.POINTER(C.c_int), I, C.POINTER(OhResize)]
         L.oh_resize_taps.argtypes = [I, I, I, I, C.POINTER(C.c_int32), C.POINTER(C.c_int16), I, C.POINTER(C.c_int)]
         L.oh_resize_max_taps.argtypes = [I, I, I]
@@ -883,6 +943,51 @@ class Engine:
                 self.pic_free(pid)
         self._chk(rc, "oh_pics_reformat")
         return out
+
+    def pics_orient(self, pids, orientation, *, window=(0, 0, 0, 0), out=None):
+        """finished pictures -> finished pictures that hold a window of them mirrored, turned or transposed (oh_pics_orient):
+        orientation an int 0 .. 7 (any OR of ORIENT_HFLIP, ORIENT_VFLIP, ORIENT_TRANSPOSE; the transposition is applied first, then the
+        horizontal, then the vertical flip) or "identity", "hflip", "vflip", "rot180", "transpose", "rot90" (clockwise), "rot270",
+        "antitranspose"; window = (left, right, top, bottom) of the sources in luma samples.  out: destination pictures to reuse; None
+        allocates pictures with the sources' params and the oriented size rounded up to the minimum coding block.  Returns
+        (destination ids, dst_window) like pics_resize: the image is the top-left of each destination, the rest replicates its last
+        column and row.  Enqueued on the engine stream; does not wait."""
+        pids = list(pids)
+        n = len(pids)
+        if n == 0:
+            raise ValueError("pics_orient needs at least one picture (the destinations follow the pictures' params)")
+        code = orient_code(orientation)
+        od = OhOrient(code, OhWindow(*window))
+        sp = self._pic_params(pids[0])
+        width, height = sp.width - od.win.left - od.win.right, sp.height - od.win.top - od.win.bottom
+        if code & ORIENT_TRANSPOSE:
+            width, height = height, width
+        fresh = out is None
+        if fresh:
+            if width < 1 or height < 1:
+                raise ValueError(f"window {tuple(window)} leaves nothing of {sp.width}x{sp.height}")
+            dp = F.OhPicParams.from_buffer_copy(sp)
+            mcb = 1 << sp.log2_min_cb_size
+            dp.width, dp.height = -(-width // mcb) * mcb, -(-height // mcb) * mcb
+            out = []
+            try:
+                for _ in range(n):
+                    out.append(self.pic_alloc(dp))
+            except Exception:
+                for pid in out:
+                    self.pic_free(pid)
+                raise
+        else:
+            out = list(out)
+            if len(out) != n:
+                raise ValueError(f"out: {len(out)} pictures for {n} sources")
+        rc = self.L.oh_pics_orient(self.h, (C.c_int * n)(*pids), (C.c_int * n)(*out), n, C.byref(od))
+        if rc != 0 and fresh:
+            for pid in out:
+                self.pic_free(pid)
+        self._chk(rc, "oh_pics_orient")
+        dp = self._pic_params(out[0])
+        return out, (0, dp.width - width, 0, dp.height - height)
 
     def pics_compose(self, dst, layers, *, fill=None):
         """finished pictures composed in place on the GPU (oh_pics_compose): dst, the destination ids (identical params); layers, a
