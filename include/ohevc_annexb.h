@@ -94,6 +94,22 @@ typedef struct OhDisplayOrientation {
  * an SEI NAL unit, a message that runs past the unit, or a display orientation with a payload shorter than its fields. */
 int oh_sei_display_orientation(const uint8_t *nal, size_t size, OhDisplayOrientation *out);
 
+/* The picture timing message of H.265 Annex D (payload type 1), of which the reference keeps pic_struct (hevc_sei.c:85-101) to tag its
+ * frames interlaced_frame / top_field_first.  With frame_field_info_present_flag set the payload starts, MSB first, with pic_struct
+ * u(4), source_scan_type u(2), duplicate_flag u(1); the HRD fields that may follow are not read.  The flag is a VUI field of the SPS:
+ * the caller passes it.  Without it the message holds none of the three, and they are -1, the reference's "unknown".
+ * oh_field_info (ohevc_hip.h) says what a pic_struct means. */
+typedef struct OhPicTiming {
+    int32_t present;                  /* a message was found */
+    int32_t pic_struct;               /* 0 .. 15 as coded (13 .. 15 are reserved); -1 unknown */
+    int32_t source_scan_type;         /* 0 interlaced, 1 progressive, 2 unknown, 3 reserved; -1 unknown */
+    int32_t duplicate_flag;           /* -1 unknown */
+} OhPicTiming;
+/* nal[0 .. size): one (escaped) SEI NAL unit, header first.  The same message walk as oh_sei_display_orientation.  The message counts
+ * in a prefix SEI only; in a suffix SEI it is passed over; of several in one unit the last counts.  Returns 1 found, 0 none (*out is
+ * zero), or -1: not an SEI NAL unit, a message that runs past the unit, or frame_field_info_present set and an empty payload. */
+int oh_sei_pic_timing(const uint8_t *nal, size_t size, int frame_field_info_present, OhPicTiming *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -435,6 +435,85 @@ int oh_orient_size(int orientation, int w, int h, int *ow, int *oh);
  * needs a resampler.  OH_E_ARG: a null pointer, a flag outside 0 / 1, a rotation of 2^16 or more. */
 int oh_orient_from_sei(int hor_flip, int ver_flip, uint32_t anticlockwise_rotation, int *orientation);
 
+/* Fields and frames (DESIGN.md §3l has the exact definitions, which the tests check bit for bit against tests/deinterlace_model.py).
+ * The reference reads field_seq_flag and the pic_struct of the picture timing SEI (oh_sei_pic_timing, ohevc_annexb.h) and tags its
+ * frames interlaced_frame / top_field_first; these calls act on it without a host copy.
+ *
+ * host only: what a pic_struct says (H.265 Table D.2).  This comment is the contract.
+ *   kind          0 frame (pic_struct 0 and 3 .. 8), 1 top field (1, 9, 11), 2 bottom field (2, 10, 12);
+ *   pair          -1 (9, 10): the field pairs with the previous picture in output order; +1 (11, 12): with the next; else 0;
+ *   top_first     1 (3, 5), 0 (4, 6), -1 otherwise: which field of a frame is displayed first, where the message says so;
+ *   repeat_first  1 (5, 6): the first field is shown again after the second; else 0;
+ *   frames        2 (7, frame doubling), 3 (8, frame tripling), else 1.
+ * OH_E_ARG: a null pointer, a pic_struct outside 0 .. 12. */
+typedef struct OhFieldInfo { int32_t kind, pair, top_first, repeat_first, frames; } OhFieldInfo;
+int oh_field_info(int pic_struct, OhFieldInfo *out);
+
+/* n pairs of fields become n frames (weave), n frames become their fields (separate).  Per plane, over the whole coded planes:
+ * D[2y][x] = T[y][x] and D[2y + 1][x] = B[y][x]; separate is the exact inverse.  Chroma planes follow the same row rule: an interlaced
+ * 4:2:0 frame alternates its chroma rows by field too.  The 2n fields have identical OhPicParams; the n frames have identical params,
+ * the fields' width, bit depth and chroma format and exactly twice their height; the other fields of the params are not compared
+ * between fields and frames.  In oh_pics_separate one of top_ids / bottom_ids may be null: that field is not made.
+ * Reads each source's finished half, writes half 0 of each destination and marks it finished, like oh_pics_orient (pictures of
+ * oh_pic_wrap like allocated ones).  Enqueued on the engine stream behind the work that finished the sources, returns without waiting.
+ * n == 0: OH_OK.  More than OH_CONV_MAX_PICS frames are split into several launches.
+ * OH_E_ARG, nothing written: a null e or id array (but for the one of oh_pics_separate), or a negative n; both destination lists of
+ * oh_pics_separate null; an unknown picture; fields (or frames) whose params differ among themselves; a width that differs between
+ * fields and frames; a frame height that is not twice the field height; a picture that is both source and destination; a destination
+ * listed twice, across both destination lists of oh_pics_separate.
+ * OH_E_UNSUPPORTED, nothing written: a bit depth or chroma format that differs between fields and frames (oh_pics_reformat first);
+ * this is looked at before the sizes. */
+int oh_pics_weave(OhEngine *e, const int *top_ids, const int *bottom_ids, const int *dst_ids, int n);
+int oh_pics_separate(OhEngine *e, const int *src_ids, const int *top_ids, const int *bottom_ids, int n);
+
+/* Deinterlacing: n finished pictures (frames whose rows alternate between two fields) become n finished pictures of the same params.
+ * The whole coded planes, every plane alike, no window (oh_pics_orient crops).  H x W is a plane's coded size (H is even), M =
+ * 2^bit_depth - 1.  Rows with y % 2 == parity are the KEPT field, the others are MISSING.  Two row rules: clamped, r(k) = min(max(k, 0),
+ * H - 1); mirrored, which always lands on a kept row: up = y - 1 >= 0 ? y - 1 : y + 1, dn = y + 1 <= H - 1 ? y + 1 : y - 1.  Columns
+ * clamp: cx(k) = min(max(k, 0), W - 1).  C is the plane of cur.
+ *   OH_DEINT_BOB       kept rows are copied; a missing row is (C[up][x] + C[dn][x] + 1) >> 1.  Reads nothing of the other field: called
+ *                      twice, with parity 0 and 1, it gives field rate.
+ *   OH_DEINT_BLEND     every row, kept or not: (C[r(y-1)][x] + 2 C[y][x] + C[r(y+1)][x] + 2) >> 2.  parity is checked, not used.
+ *   OH_DEINT_LOWPASS5  kept rows are copied; a missing row is clip((-C[r(y-2)][x] + 4 C[r(y-1)][x] + 2 C[y][x] + 4 C[r(y+1)][x]
+ *                      - C[r(y+2)][x] + 4) >> 3, 0, M), an arithmetic shift of the signed sum.  At 8 bit with parity 0 this is the
+ *                      reference's deinterlace_bottom_field (imgconvert.c:299-379), whose edge rows are this clamping.
+ *   OH_DEINT_ADAPTIVE  kept rows are copied; a missing row is motion-adaptive with an edge-directed spatial predictor.  P / C / N are
+ *                      the planes of prev / cur / next; (A, B) = (P, C) when kept_first is 1 — the kept field is the earlier one of
+ *                      its frame, so the other field's rows lie before it in prev and after it in cur — and (C, N) when it is 0.
+ *                      All values signed 32 bit:
+ *                          c = C[up][x]; e = C[dn][x]
+ *                          t    = (A[y][x] + B[y][x]) >> 1
+ *                          d0   = |A[y][x] - B[y][x]|
+ *                          d1   = (|P[up][x] - c| + |P[dn][x] - e|) >> 1
+ *                          d2   = (|N[up][x] - c| + |N[dn][x] - e|) >> 1
+ *                          diff = max(d0 >> 1, d1, d2)
+ *                          score(j) = sum over k in {-1, 0, 1} of |C[up][cx(x+k+j)] - C[dn][cx(x+k-j)]|
+ *                          best = score(0) - 1; j* = 0
+ *                          for s in (-1, +1), in this order:
+ *                              if score(s) < best:   best = score(s); j* = s
+ *                                  if score(2s) < best:   best = score(2s); j* = 2s      (tried only when s itself won)
+ *                          sp  = (C[up][cx(x+j*)] + C[dn][cx(x-j*)]) >> 1
+ *                          out = min(max(sp, t - diff), t + diff)
+ *                      No clip is needed: sp and t lie in [0, M] and out lies between them.  With prev == cur == next the output is cur
+ *                      exactly (diff == 0, t == C[y][x]): a still scene passes through untouched.
+ * prev_ids / next_ids are read by OH_DEINT_ADAPTIVE only and not even checked by the other modes; a null array, or an entry of -1,
+ * stands for the cur picture of that index (stream start and end).
+ * All pictures involved have identical OhPicParams.  Reads finished halves, writes half 0 of each destination and marks it finished,
+ * like oh_pics_orient; enqueued on the engine stream, returns without waiting.  n == 0: OH_OK.  More than OH_CONV_MAX_PICS pictures
+ * are split into several launches.
+ * OH_E_ARG, nothing written: a null e, d, cur_ids or dst_ids, or a negative n; an unknown picture, or an id below -1 in prev / next;
+ * params that differ anywhere among cur, dst and (ADAPTIVE) prev / next — a bit depth or chroma format that differs is such a
+ * difference, as in oh_pics_compare; a destination that is also any source of the call, or a destination listed twice; a mode outside
+ * 0 .. 3; a parity or kept_first outside 0 / 1.  No combination gives OH_E_UNSUPPORTED. */
+enum { OH_DEINT_BOB = 0, OH_DEINT_BLEND, OH_DEINT_LOWPASS5, OH_DEINT_ADAPTIVE };
+typedef struct OhDeinterlace { int32_t mode, parity, kept_first; } OhDeinterlace;
+int oh_pics_deinterlace(OhEngine *e, const int *prev_ids, const int *cur_ids, const int *next_ids,
+                        const int *dst_ids, int n, const OhDeinterlace *d);
+/* host only: the ADAPTIVE formula above on a window (the function the kernel evaluates, csrc/deinterlace_common.h): up[i] / dn[i] are
+ * C[up][cx(x-3+i)] / C[dn][cx(x-3+i)]; a, b are A[y][x], B[y][x]; pu, pd, nu, nd are P[up][x], P[dn][x], N[up][x], N[dn][x]. */
+int32_t oh_deint_adaptive(const int32_t up[7], const int32_t dn[7], int32_t a, int32_t b,
+                          int32_t pu, int32_t pd, int32_t nu, int32_t nd);
+
 /* SHVC inter-layer reference picture: resample the finished base-layer picture src_pic into
  * the enhancement-layer picture dst_pic, bit-exact with the reference's whole-picture slot
  * HEVCDSPContext.upsample_base_layer_frame (hevcdsp_template.c:2164-2438, call site hevc.c:3241).

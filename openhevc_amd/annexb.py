@@ -1,4 +1,4 @@
-"""ctypes view of include/ohevc_annexb.h (libohevc_host.so): access-unit splitter, NAL scan, NAL unescape, picture-hash SEI, HDR SEIs, display-orientation SEI."""
+"""ctypes view of include/ohevc_annexb.h (libohevc_host.so): access-unit splitter, NAL scan, NAL unescape, picture-hash SEI, HDR SEIs, display-orientation SEI, picture timing SEI."""
 import ctypes as C
 import os
 
@@ -30,6 +30,10 @@ class OhDisplayOrientation(C.Structure):
                 ("anticlockwise_rotation", C.c_uint32), ("persistence", C.c_int32)]
 
 
+class OhPicTiming(C.Structure):
+    _fields_ = [("present", C.c_int32), ("pic_struct", C.c_int32), ("source_scan_type", C.c_int32), ("duplicate_flag", C.c_int32)]
+
+
 _lib = None
 
 
@@ -56,6 +60,8 @@ def lib():
         L.oh_sei_hdr.restype = C.c_int
         L.oh_sei_display_orientation.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(OhDisplayOrientation)]
         L.oh_sei_display_orientation.restype = C.c_int
+        L.oh_sei_pic_timing.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(OhPicTiming)]
+        L.oh_sei_pic_timing.restype = C.c_int
         _lib = L
     return _lib
 
@@ -146,3 +152,16 @@ def display_orientation(nal):
         return None
     return dict(cancel=bool(d.cancel), hor_flip=bool(d.hor_flip), ver_flip=bool(d.ver_flip),
                 anticlockwise_rotation=int(d.anticlockwise_rotation), persistence=bool(d.persistence))
+
+
+def pic_timing(nal, frame_field_info_present=True):
+    """None, or a dict of the picture timing message (payload type 1) of one prefix SEI NAL unit (oh_sei_pic_timing): "pic_struct",
+    "source_scan_type", "duplicate_flag" as ints.  frame_field_info_present is the VUI flag of the stream's SPS, which the caller
+    knows; without it the message holds none of the three and they are -1.  engine.field_info says what a pic_struct means."""
+    d = OhPicTiming()
+    r = lib().oh_sei_pic_timing(nal, len(nal), int(bool(frame_field_info_present)), C.byref(d))
+    if r < 0:
+        raise ValueError("malformed SEI NAL unit")
+    if not r:
+        return None
+    return dict(pic_struct=int(d.pic_struct), source_scan_type=int(d.source_scan_type), duplicate_flag=int(d.duplicate_flag))

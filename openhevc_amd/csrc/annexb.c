@@ -282,3 +282,35 @@ int oh_sei_display_orientation(const uint8_t *nal, size_t size, OhDisplayOrienta
     }
     return out->present;
 }
+
+struct timing_ctx { OhPicTiming *out; int info_present; };
+
+static int timing_msg(void *ctx, int nut, unsigned type, const uint8_t *q, unsigned len)
+{
+    struct timing_ctx *t = (struct timing_ctx *)ctx;
+    OhPicTiming *out = t->out;
+    if (nut != NAL_SEI_PREFIX || type != 1)                   /* D.2.3 pic_timing */
+        return 0;
+    memset(out, 0, sizeof(*out));                             /* the last message of the unit counts */
+    out->present = 1;
+    out->pic_struct = out->source_scan_type = out->duplicate_flag = -1;     /* unknown without frame_field_info_present_flag */
+    if (!t->info_present)
+        return 0;
+    if (len < 1)                                              /* pic_struct u(4), source_scan_type u(2), duplicate_flag u(1) */
+        return -1;
+    out->pic_struct = q[0] >> 4;
+    out->source_scan_type = (q[0] >> 2) & 3;
+    out->duplicate_flag = (q[0] >> 1) & 1;
+    return 0;
+}
+
+int oh_sei_pic_timing(const uint8_t *nal, size_t size, int frame_field_info_present, OhPicTiming *out)
+{
+    struct timing_ctx t = { out, frame_field_info_present != 0 };
+    memset(out, 0, sizeof(*out));
+    if (sei_walk(nal, size, timing_msg, &t) < 0) {
+        memset(out, 0, sizeof(*out));
+        return -1;
+    }
+    return out->present;
+}

@@ -1,9 +1,9 @@
 /*
  * engine_pics.hip — what the engine does with finished pictures beside the reconstruction path (host side; the kernels are md5.hip,
- * hash.hip, convert.hip, import.hip, colour.hip, light.hip, compare.hip, resize.hip, reformat.hip, orient.hip and compose.hip): plane upload and download,
+ * hash.hip, convert.hip, import.hip, colour.hip, light.hip, compare.hip, resize.hip, reformat.hip, orient.hip, deinterlace.hip and compose.hip): plane upload and download,
  * the two-phase window fetch, picture hashes, conversion to YUV / RGB images and back, with the colour tables of the HDR forms, light-level
  * statistics, comparison of two pictures, resizing into engine pictures, reformatting into pictures of another bit depth or chroma format, orientation (crop, flip, quarter turns, transpose),
- * and composition of pictures in place: fill, overlay, alpha blend.
+ * fields (weave, separate, deinterlace) and composition of pictures in place: fill, overlay, alpha blend.
  * Their arithmetic, which needs neither an engine nor a device, is pics_math.hip; the helpers at the top are what the services share.
  */
 #include <cmath>
@@ -1043,6 +1043,168 @@ extern "C" int oh_pics_orient(OhEngine *e, const int *src_ids, const int *dst_id
             q->done_seq = 0;
         }
         ohk_orient(&a, m, e->stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    return OH_OK;
+}
+
+/* ---------------- fields and deinterlacing (deinterlace.hip) ---------------- */
+/* no destination is listed twice and none is among the sources */
+static int dsts_apart(OhEngine *e, const char *who, const std::vector<int> &dsts, const std::vector<int> &srcs)
+{
+    std::vector<int> d;
+    { const int rc = distinct_dsts(e, who, dsts.data(), (int)dsts.size(), &d); if (rc) return rc; }
+    for (int s : srcs)
+        if (std::binary_search(d.begin(), d.end(), s))
+            FAIL(e, OH_E_ARG, "%s: picture %d is both source and destination", who, s);
+    return OH_OK;
+}
+
+/* what weave and separate ask of their fields (f0) and frames (F0) */
+static int fields_check(OhEngine *e, const char *who, const Pic *f0, const Pic *F0)
+{
+    const OhPicParams &fp = f0->p, &Fp = F0->p;
+    if (fp.bit_depth != Fp.bit_depth || fp.chroma_format_idc != Fp.chroma_format_idc)
+        FAIL(e, OH_E_UNSUPPORTED, "%s: fields of %d bit, chroma format %d; frames of %d bit, chroma format %d (oh_pics_reformat first)", who,
+             fp.bit_depth, fp.chroma_format_idc, Fp.bit_depth, Fp.chroma_format_idc);
+    if (fp.width != Fp.width || Fp.height != 2 * fp.height)
+        FAIL(e, OH_E_ARG, "%s: fields of %dx%d, frames of %dx%d (the same width, twice the height)", who, fp.width, fp.height, Fp.width, Fp.height);
+    return OH_OK;
+}
+
+/* the launches of weave and separate: role[k] (null: not in this call) holds the ids of a.pic[k]; wr: the roles that are written */
+static int fields_launch(OhEngine *e, const Pic *f0, const Pic *F0, const int *const role[4], unsigned wr, int op, int sides, int n)
+{
+    HIPCHK(e, hipSetDevice(e->device));
+    OhDiArgs a;
+    memset(&a, 0, sizeof(a));
+    const OhPicParams &Fp = F0->p;
+    const int bpp = sample_bytes(Fp.bit_depth);
+    a.np = Fp.chroma_format_idc ? 3 : 1; a.bd = Fp.bit_depth; a.op = op; a.sides = sides;
+    for (int c = 0; c < a.np; c++) { a.pitch[c] = F0->stride[c] * bpp; a.fpitch[c] = f0->stride[c] * bpp; }
+    for (int q = 0; q < (a.np > 1 ? 2 : 1); q++) { a.w[q] = F0->w[q]; a.h[q] = F0->h[q]; }
+    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
+        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+        for (int k = 0; k < 4; k++) {
+            if (!role[k])
+                continue;
+            for (int i = 0; i < m; i++) {
+                Pic *q = get_pic(e, role[k][i0 + i]);
+                const bool w = wr >> k & 1;
+                for (int c = 0; c < 3; c++)
+                    a.pic[k][i][c] = c < a.np ? (w ? q->a[c] : final_planes(q)[c]) : nullptr;
+                if (w) {
+                    q->final_b = false;                          /* the image is a finished picture in half 0 */
+                    q->done_seq = 0;
+                }
+            }
+        }
+        ohk_fields(&a, m, e->stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    return OH_OK;
+}
+
+extern "C" int oh_pics_weave(OhEngine *e, const int *top_ids, const int *bottom_ids, const int *dst_ids, int n)
+{
+    const char *who = "oh_pics_weave";
+    if (!e || n < 0 || (n && (!top_ids || !bottom_ids || !dst_ids)))
+        return OH_E_ARG;
+    if (!n)
+        return OH_OK;
+    std::vector<int> fields(top_ids, top_ids + n);
+    fields.insert(fields.end(), bottom_ids, bottom_ids + n);
+    const Pic *f0 = alike_pics(e, who, fields.data(), 2 * n);
+    if (!f0) return OH_E_ARG;
+    const Pic *F0 = alike_pics(e, who, dst_ids, n);
+    if (!F0) return OH_E_ARG;
+    { const int rc = dsts_apart(e, who, std::vector<int>(dst_ids, dst_ids + n), fields); if (rc) return rc; }
+    { const int rc = fields_check(e, who, f0, F0); if (rc) return rc; }
+    const int *const role[4] = { top_ids, bottom_ids, nullptr, dst_ids };
+    return fields_launch(e, f0, F0, role, 1u << 3, OH_DI_WEAVE, 3, n);
+}
+
+extern "C" int oh_pics_separate(OhEngine *e, const int *src_ids, const int *top_ids, const int *bottom_ids, int n)
+{
+    const char *who = "oh_pics_separate";
+    if (!e || n < 0 || (n && !src_ids) || (!top_ids && !bottom_ids))
+        return OH_E_ARG;
+    if (!n)
+        return OH_OK;
+    std::vector<int> fields;
+    if (top_ids) fields.insert(fields.end(), top_ids, top_ids + n);
+    if (bottom_ids) fields.insert(fields.end(), bottom_ids, bottom_ids + n);
+    const Pic *F0 = alike_pics(e, who, src_ids, n);
+    if (!F0) return OH_E_ARG;
+    const Pic *f0 = alike_pics(e, who, fields.data(), (int)fields.size());
+    if (!f0) return OH_E_ARG;
+    { const int rc = dsts_apart(e, who, fields, std::vector<int>(src_ids, src_ids + n)); if (rc) return rc; }
+    { const int rc = fields_check(e, who, f0, F0); if (rc) return rc; }
+    const int *const role[4] = { src_ids, nullptr, top_ids, bottom_ids };
+    return fields_launch(e, f0, F0, role, 3u << 2, OH_DI_SEPARATE, (top_ids ? 1 : 0) | (bottom_ids ? 2 : 0), n);
+}
+
+extern "C" int oh_pics_deinterlace(OhEngine *e, const int *prev_ids, const int *cur_ids, const int *next_ids, const int *dst_ids, int n,
+                                   const OhDeinterlace *d)
+{
+    const char *who = "oh_pics_deinterlace";
+    if (!e || n < 0 || !d || (n && (!cur_ids || !dst_ids)))
+        return OH_E_ARG;
+    if (d->mode < OH_DEINT_BOB || d->mode > OH_DEINT_ADAPTIVE)
+        FAIL(e, OH_E_ARG, "%s: mode %d (0 bob, 1 blend, 2 lowpass5, 3 adaptive)", who, d->mode);
+    if (d->parity < 0 || d->parity > 1 || d->kept_first < 0 || d->kept_first > 1)
+        FAIL(e, OH_E_ARG, "%s: parity %d, kept_first %d (0 or 1)", who, d->parity, d->kept_first);
+    if (!n)
+        return OH_OK;
+    /* the pictures of index i: prev, cur, next; a null array or an entry of -1 stands for cur; read by ADAPTIVE only */
+    const bool adaptive = d->mode == OH_DEINT_ADAPTIVE;
+    std::vector<int> around[2];
+    std::vector<int> srcs(cur_ids, cur_ids + n);
+    for (int k = 0; k < 2; k++) {
+        const int *ids = k ? next_ids : prev_ids;
+        around[k] = std::vector<int>(cur_ids, cur_ids + n);
+        if (!adaptive || !ids)
+            continue;
+        for (int i = 0; i < n; i++) {
+            if (ids[i] < -1)
+                FAIL(e, OH_E_ARG, "%s: %s picture %d (-1 stands for the cur picture)", who, k ? "next" : "prev", ids[i]);
+            if (ids[i] >= 0)
+                around[k][i] = ids[i];
+        }
+        srcs.insert(srcs.end(), around[k].begin(), around[k].end());
+    }
+    std::vector<int> all(srcs);
+    all.insert(all.end(), dst_ids, dst_ids + n);
+    const Pic *p0 = alike_pics(e, who, all.data(), (int)all.size());
+    if (!p0) return OH_E_ARG;
+    { const int rc = dsts_apart(e, who, std::vector<int>(dst_ids, dst_ids + n), srcs); if (rc) return rc; }
+    const OhPicParams &p = p0->p;
+    HIPCHK(e, hipSetDevice(e->device));
+    OhDiArgs a;
+    memset(&a, 0, sizeof(a));
+    const int bpp = sample_bytes(p.bit_depth);
+    a.np = p.chroma_format_idc ? 3 : 1; a.bd = p.bit_depth;
+    a.mode = d->mode; a.parity = d->parity; a.kept_first = d->kept_first;
+    for (int c = 0; c < a.np; c++) a.pitch[c] = p0->stride[c] * bpp;
+    for (int q = 0; q < (a.np > 1 ? 2 : 1); q++) {
+        a.w[q] = p0->w[q]; a.h[q] = p0->h[q];
+        if (a.h[q] < 2 || (a.h[q] & 1))
+            FAIL(e, OH_E_ARG, "%s: planes of %d rows (an even number, 2 at least)", who, a.h[q]);
+    }
+    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
+        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+        for (int i = 0; i < m; i++) {
+            const Pic *s[3] = { get_pic(e, around[0][i0 + i]), get_pic(e, cur_ids[i0 + i]), get_pic(e, around[1][i0 + i]) };
+            Pic *q = get_pic(e, dst_ids[i0 + i]);
+            for (int c = 0; c < 3; c++) {
+                for (int k = 0; k < 3; k++)
+                    a.pic[k][i][c] = c < a.np ? final_planes(s[k])[c] : nullptr;
+                a.pic[3][i][c] = c < a.np ? q->a[c] : nullptr;
+            }
+            q->final_b = false;                                  /* the image is a finished picture in half 0 */
+            q->done_seq = 0;
+        }
+        ohk_deinterlace(&a, m, e->stream);
         HIPCHK(e, hipGetLastError());
     }
     return OH_OK;

@@ -173,6 +173,25 @@ struct OhOrArgs {
     int32_t     orientation;         /* OH_ORIENT_* bits */
 };
 
+/* fields and deinterlacing (deinterlace.hip): the planes of the pictures of one launch by value in the kernel arguments;
+ * every frame of a launch has one geometry, every field another.  Two plane classes (0 luma, 1 chroma).  What the four pictures of
+ * index i are depends on the call:
+ *   ohk_deinterlace          pic[0] prev, pic[1] cur, pic[2] next (finished halves; prev and next are read by OH_DEINT_ADAPTIVE only),
+ *                            pic[3] half 0 of the destination;
+ *   ohk_fields, weave        pic[0] top field, pic[1] bottom field (finished halves), pic[3] half 0 of the frame;
+ *   ohk_fields, separate     pic[0] the frame (finished half), pic[2] / pic[3] half 0 of the top / bottom field (sides: which are made). */
+enum { OH_DI_SEG = 4096 };           /* destination samples of one row per workgroup */
+enum { OH_DI_WEAVE = 0, OH_DI_SEPARATE };
+struct OhDiArgs {
+    void       *pic[4][64][3];       /* role x OH_CONV_MAX_PICS pictures x planes */
+    int32_t     pitch[3];            /* bytes between rows of each plane: of the frames (ohk_fields), of every picture (ohk_deinterlace) */
+    int32_t     fpitch[3];           /* ohk_fields: bytes between rows of each plane of the fields */
+    int32_t     w[2], h[2];          /* coded size of the planes: of the frames (ohk_fields), of every picture (ohk_deinterlace) */
+    int32_t     np, bd;              /* planes: 1 or 3; bit depth */
+    int32_t     op, sides;           /* ohk_fields: OH_DI_WEAVE / OH_DI_SEPARATE; separate: bit 0 top, bit 1 bottom */
+    int32_t     mode, parity, kept_first;    /* ohk_deinterlace: OhDeinterlace */
+};
+
 /* picture resizing (resize.hip): what one launch set needs, by value in the kernel arguments like OhConvArgs.  Two plane
  * classes (0 luma, 1 chroma), each with its own geometry and tap tables; the tables live in device memory that the engine owns and
  * fills (engine_pics.hip: oh_pics_resize, from pics_math.hip: oh_resize_taps) on the stream in front of the launches. */
@@ -228,6 +247,10 @@ void ohk_compose(const OhCpsArgs *a, int n, hipStream_t st);
 void ohk_reformat(const OhRfArgs *a, int n, hipStream_t st);
 /* n sources of a.src, oriented, into the n destinations of a.dst */
 void ohk_orient(const OhOrArgs *a, int n, hipStream_t st);
+/* n pictures of a.pic[1] (with a.pic[0] and a.pic[2] around them in time) deinterlaced into the n destinations of a.pic[3] */
+void ohk_deinterlace(const OhDiArgs *a, int n, hipStream_t st);
+/* n pairs of fields woven into n frames, or n frames separated into one or two fields each */
+void ohk_fields(const OhDiArgs *a, int n, hipStream_t st);
 void ohk_hash(int kind, const OhMd5Job *jobs, const uint32_t *first, const uint32_t *task_map, int n_jobs, int n_tasks, uint32_t *partials,
               uint32_t *out, hipStream_t st);
 void ohk_inter(const OhBatch *B, int n, const OhPicParams *p, uint32_t max_luma, uint32_t max_chroma, hipStream_t st);

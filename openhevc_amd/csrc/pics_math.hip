@@ -1,7 +1,7 @@
 /*
  * pics_math.hip — the host arithmetic of the picture services (engine_pics.hip), with neither an engine nor a device: image sizes and
  * crop windows, the integers of the RGB conversions, the colour tables of the HDR forms, light-level bins and percentiles, the SSIM window
- * and PSNR, the resize taps, the compose formulas, the reformat quantisation, the orientations' group.  No kernel, no HIP runtime call: tests/pics_math_check.cpp runs it under sanitizers.
+ * and PSNR, the resize taps, the compose formulas, the reformat quantisation, the orientations' group, the pic_struct table and the adaptive deinterlacer's sample.  No kernel, no HIP runtime call: tests/pics_math_check.cpp runs it under sanitizers.
  */
 #include <stdio.h>
 #include <string.h>
@@ -14,6 +14,7 @@
 #include "compare_common.h"
 #include "compose_common.h"
 #include "reformat_common.h"
+#include "deinterlace_common.h"
 
 static bool depth_ok(int bit_depth) { return bit_depth == 8 || bit_depth == 9 || bit_depth == 10 || bit_depth == 12; }
 
@@ -603,4 +604,25 @@ extern "C" int oh_orient_from_sei(int hor_flip, int ver_flip, uint32_t anticlock
         o = oh_orient_then(o, OH_ORIENT_TRANSPOSE | OH_ORIENT_VFLIP);
     *orientation = o;
     return OH_OK;
+}
+
+/* ---------------- fields and deinterlacing (deinterlace.hip) ---------------- */
+extern "C" int oh_field_info(int pic_struct, OhFieldInfo *out)
+{
+    if (!out || pic_struct < 0 || pic_struct > 12)
+        return OH_E_ARG;
+    /* H.265 Table D.2: 0 frame, 1 top, 2 bottom, 3 top-bottom, 4 bottom-top, 5 top-bottom-top, 6 bottom-top-bottom, 7 doubling,
+     * 8 tripling, 9 top with previous bottom, 10 bottom with previous top, 11 top with next bottom, 12 bottom with next top */
+    const int s = pic_struct;
+    out->kind = s == 1 || s == 9 || s == 11 ? 1 : s == 2 || s == 10 || s == 12 ? 2 : 0;
+    out->pair = s == 9 || s == 10 ? -1 : s == 11 || s == 12 ? 1 : 0;
+    out->top_first = s == 3 || s == 5 ? 1 : s == 4 || s == 6 ? 0 : -1;
+    out->repeat_first = s == 5 || s == 6;
+    out->frames = s == 7 ? 2 : s == 8 ? 3 : 1;
+    return OH_OK;
+}
+
+extern "C" int32_t oh_deint_adaptive(const int32_t up[7], const int32_t dn[7], int32_t a, int32_t b, int32_t pu, int32_t pd, int32_t nu, int32_t nd)
+{
+    return deint_adaptive(up, dn, a, b, pu, pd, nu, nd);
 }

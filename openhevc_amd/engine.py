@@ -2,6 +2,7 @@
 
 There is no CPU fallback: creating an Engine without the built library or without a GPU raises.
 """
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -397,6 +398,57 @@ def orientation_from_sei(hor_flip, ver_flip, anticlockwise_rotation):
     return o.value
 
 
+class OhFieldInfo(C.Structure):                               # include/ohevc_hip.h
+    _fields_ = [("kind", C.c_int32), ("pair", C.c_int32), ("top_first", C.c_int32), ("repeat_first", C.c_int32), ("frames", C.c_int32)]
+
+
+class OhDeinterlace(C.Structure):                             # include/ohevc_hip.h
+    _fields_ = [("mode", C.c_int32), ("parity", C.c_int32), ("kept_first", C.c_int32)]
+
+
+FieldInfo = collections.namedtuple("FieldInfo", "kind pair top_first repeat_first frames")
+FIELD_FRAME, FIELD_TOP, FIELD_BOTTOM = 0, 1, 2                                          # FieldInfo.kind
+DEINT_BOB, DEINT_BLEND, DEINT_LOWPASS5, DEINT_ADAPTIVE = 0, 1, 2, 3                     # OH_DEINT_*
+DEINT_MODES = {"bob": DEINT_BOB, "blend": DEINT_BLEND, "lowpass5": DEINT_LOWPASS5, "adaptive": DEINT_ADAPTIVE}
+DEINT_SEG = 4096                                                                        # OH_DI_SEG (csrc/kernels.h): samples of a row per workgroup
+
+
+def field_info(pic_struct):
+    """oh_field_info (host only): what a pic_struct of the picture timing SEI (annexb.pic_timing) says, H.265 Table D.2, as a
+    FieldInfo: kind 0 frame / 1 top field / 2 bottom field; pair -1 / +1 where the field pairs with the previous / next picture in
+    output order, else 0; top_first 1 / 0 where the message says which field of a frame is first, else -1; repeat_first; frames, how
+    often a frame is shown (2 doubling, 3 tripling).  EngineError with code OH_E_ARG outside 0 .. 12."""
+    fi = OhFieldInfo()
+    rc = lib().oh_field_info(int(pic_struct), C.byref(fi))
+    if rc != 0:
+        err = EngineError(f"oh_field_info({pic_struct}) failed ({rc})")
+        err.code = rc
+        raise err
+    return FieldInfo(fi.kind, fi.pair, fi.top_first, fi.repeat_first, fi.frames)
+
+
+def deint_mode(v):
+    """a name of DEINT_MODES or an int 0 .. 3 -> the int"""
+    if isinstance(v, str):
+        if v not in DEINT_MODES:
+            raise ValueError(f"unknown deinterlacing mode {v!r}: one of {sorted(DEINT_MODES)}")
+        return DEINT_MODES[v]
+    v = int(v)
+    if not 0 <= v <= 3:
+        raise ValueError(f"deinterlacing mode {v}: 0 .. 3")
+    return v
+
+
+def deint_adaptive(up, dn, a, b, pu, pd, nu, nd):
+    """oh_deint_adaptive (host only): one missing sample of the adaptive mode from its window: up / dn seven kept samples of cur
+    above and below (columns x - 3 .. x + 3), a / b the two samples at its own place before and after, pu / pd / nu / nd the samples
+    above and below it in prev and next"""
+    up, dn = [int(v) for v in up], [int(v) for v in dn]
+    if len(up) != 7 or len(dn) != 7:
+        raise ValueError("up and dn hold seven samples each")
+    return int(lib().oh_deint_adaptive((C.c_int32 * 7)(*up), (C.c_int32 * 7)(*dn), int(a), int(b), int(pu), int(pd), int(nu), int(nd)))
+
+
 def convert_image_bytes(params, cv):
     """oh_convert_image_bytes (host only): bytes of one image, 0 when the combination is not valid"""
     return int(lib().oh_convert_image_bytes(C.byref(params), C.byref(cv)))
@@ -500,6 +552,13 @@ def lib():
         L.oh_orient_inverse.argtypes = [I]
         L.oh_orient_size.argtypes = [I, I, I, C.POINTER(I), C.POINTER(I)]
         L.oh_orient_from_sei.argtypes = [I, I, C.c_uint32, C.POINTER(I)]
+        IP = C.POINTER(C.c_int)
+        L.oh_field_info.argtypes = [I, C.POINTER(OhFieldInfo)]
+        L.oh_pics_weave.argtypes = [V, IP, IP, IP, I]
+        L.oh_pics_separate.argtypes = [V, IP, IP, IP, I]
+        L.oh_pics_deinterlace.argtypes = [V, IP, IP, IP, IP, I, C.POINTER(OhDeinterlace)]
+        L.oh_deint_adaptive.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32)] + [C.c_int32] * 6
+        L.oh_deint_adaptive.restype = C.c_int32
         L.oh_pics_resize.argtypes = [V, C.POINTER(C.c_int), C.POINTER(C.c_int), I, C.POINTER(OhResize)]
         L.oh_resize_taps.argtypes = [I, I, I, I, C.POINTER(C.c_int32), C.POINTER(C.c_int16), I, C.POINTER(C.c_int)]
         L.oh_resize_max_taps.argtypes = [I, I, I]
@@ -988,6 +1047,123 @@ class Engine:
         self._chk(rc, "oh_pics_orient")
         dp = self._pic_params(out[0])
         return out, (0, dp.width - width, 0, dp.height - height)
+
+    def _alloc_like(self, pid, height, n):
+        """n fresh pictures with the params of picture pid and another height; ValueError where oh_pic_alloc would refuse the height"""
+        dp = F.OhPicParams.from_buffer_copy(self._pic_params(pid))
+        mcb = 1 << dp.log2_min_cb_size
+        if height < mcb or height % mcb:
+            raise ValueError(f"a height of {height} is no multiple of the minimum coding block ({mcb}): no picture can hold it")
+        dp.height = height
+        out = []
+        try:
+            for _ in range(n):
+                out.append(self.pic_alloc(dp))
+        except Exception:
+            for made in out:
+                self.pic_free(made)
+            raise
+        return out
+
+    def pics_weave(self, top_pids, bottom_pids, *, out=None):
+        """n pairs of finished fields -> n finished frames (oh_pics_weave): frame row 2y is row y of the top field, row 2y + 1 row y of
+        the bottom field, in every plane.  out: destination pictures to reuse; None allocates pictures with the fields' params and
+        twice their height.  Returns the destination ids.  Enqueued on the engine stream; does not wait."""
+        top, bottom = list(top_pids), list(bottom_pids)
+        n = len(top)
+        if n == 0:
+            raise ValueError("pics_weave needs at least one pair of fields (the destinations follow the fields' params)")
+        if len(bottom) != n:
+            raise ValueError(f"{n} top fields, {len(bottom)} bottom fields")
+        fresh = out is None
+        if fresh:
+            out = self._alloc_like(top[0], 2 * self._pic_params(top[0]).height, n)
+        else:
+            out = list(out)
+            if len(out) != n:
+                raise ValueError(f"out: {len(out)} pictures for {n} pairs of fields")
+        IA = C.c_int * n
+        rc = self.L.oh_pics_weave(self.h, IA(*top), IA(*bottom), IA(*out), n)
+        if rc != 0 and fresh:
+            for pid in out:
+                self.pic_free(pid)
+        self._chk(rc, "oh_pics_weave")
+        return out
+
+    def pics_separate(self, pids, *, top=True, bottom=True, out=None):
+        """n finished frames -> their fields (oh_pics_separate), the inverse of pics_weave: row y of the top field is frame row 2y, of
+        the bottom field frame row 2y + 1.  top / bottom: which fields to make.  out: (top ids or None, bottom ids or None) to reuse;
+        None allocates pictures with the frames' params and half their height (ValueError where no picture can have that height).
+        Returns (top ids, bottom ids), None for a side that was not asked for.  Enqueued on the engine stream; does not wait."""
+        pids = list(pids)
+        n = len(pids)
+        if n == 0:
+            raise ValueError("pics_separate needs at least one picture (the destinations follow the pictures' params)")
+        if not top and not bottom:
+            raise ValueError("pics_separate: neither field asked for")
+        fresh = out is None
+        if fresh:
+            height = self._pic_params(pids[0]).height
+            if height % 2:
+                raise ValueError(f"a frame of {height} rows has no two fields of one height")
+            both = self._alloc_like(pids[0], height // 2, n * (bool(top) + bool(bottom)))
+            sides = [both[:n] if top else None, both[-n:] if bottom else None]
+        else:
+            sides = [None if s is None else list(s) for s in out]
+            if len(sides) != 2 or (sides[0] is None) != (not top) or (sides[1] is None) != (not bottom):
+                raise ValueError("out: a pair (top ids, bottom ids) with None for the side that is not asked for")
+            for s in sides:
+                if s is not None and len(s) != n:
+                    raise ValueError(f"out: {len(s)} pictures for {n} sources")
+        IA = C.c_int * n
+        rc = self.L.oh_pics_separate(self.h, IA(*pids), IA(*sides[0]) if top else None, IA(*sides[1]) if bottom else None, n)
+        if rc != 0 and fresh:
+            for pid in both:
+                self.pic_free(pid)
+        self._chk(rc, "oh_pics_separate")
+        return sides[0], sides[1]
+
+    def pics_deinterlace(self, pids, mode="adaptive", *, keep="top", kept_first=True, prev=None, next=None, out=None):
+        """finished pictures whose rows alternate between two fields -> finished progressive pictures (oh_pics_deinterlace; the exact
+        definitions are in include/ohevc_hip.h).  mode: "bob", "blend", "lowpass5", "adaptive" or DEINT_*; keep: "top" (rows 0, 2, ...
+        are kept, parity 0) or "bottom" (parity 1), or the parity itself; kept_first: the kept field is the earlier one of its frame
+        (adaptive only); prev / next: the pictures before and after each one in time (adaptive only), lists that may hold None, which
+        like prev=None / next=None stands for the picture itself.  out: destination pictures to reuse; None allocates pictures with
+        the sources' params.  Returns the destination ids.  Enqueued on the engine stream; does not wait."""
+        pids = list(pids)
+        n = len(pids)
+        if n == 0:
+            raise ValueError("pics_deinterlace needs at least one picture (the destinations follow the pictures' params)")
+        if keep in ("top", "bottom"):
+            parity = int(keep == "bottom")
+        elif keep in (0, 1):
+            parity = int(keep)
+        else:
+            raise ValueError(f"keep {keep!r}: 'top' (0) or 'bottom' (1)")
+        dd = OhDeinterlace(deint_mode(mode), parity, int(bool(kept_first)))
+        IA = C.c_int * n
+        around = []
+        for name, ids in (("prev", prev), ("next", next)):
+            if ids is None:
+                around.append(None)
+                continue
+            ids = [-1 if v is None else int(v) for v in ids]
+            if len(ids) != n:
+                raise ValueError(f"{name}: {len(ids)} entries for {n} sources")
+            around.append(IA(*ids))
+        fresh = out is None
+        if fresh:
+            out = self._alloc_like(pids[0], self._pic_params(pids[0]).height, n)
+        else:
+            out = list(out)
+            if len(out) != n:
+                raise ValueError(f"out: {len(out)} pictures for {n} sources")
+        rc = self.L.oh_pics_deinterlace(self.h, around[0], IA(*pids), around[1], IA(*out), n, C.byref(dd))
+        if rc != 0 and fresh:
+            for pid in out:
+                self.pic_free(pid)
+        self._chk(rc, "oh_pics_deinterlace")
+        return out
 
     def pics_compose(self, dst, layers, *, fill=None):
         """finished pictures composed in place on the GPU (oh_pics_compose): dst, the destination ids (identical params); layers, a
