@@ -514,6 +514,63 @@ int oh_pics_deinterlace(OhEngine *e, const int *prev_ids, const int *cur_ids, co
 int32_t oh_deint_adaptive(const int32_t up[7], const int32_t dn[7], int32_t a, int32_t b,
                           int32_t pu, int32_t pd, int32_t nu, int32_t nd);
 
+/* Filters: n finished pictures become n finished pictures of the same params (the tests check every plane bit for bit
+ * against tests/filter_model.py).  The whole coded planes, no window.  This comment is the contract.  H x W is a plane's coded size,
+ * M = 2^bit_depth - 1; rows clamp, r(k) = min(max(k, 0), H - 1), and so do columns, cx(k) = min(max(k, 0), W - 1); S is the source
+ * plane; q is 0 for luma and 1 for chroma; all arithmetic is signed 32 bit and >> is an arithmetic shift.
+ * A tap set is LEGAL when nh and nv are odd and lie in 1 .. 15, the h and the v taps each sum to 256, and the sums of |h| and of |v|
+ * are at most 512 each.  Then |tmp| <= 512 * 4095 and |acc| <= 512 * 512 * 4095 < 2^31 - 2^15: int32 never overflows at 12 bit.
+ *   OH_FILTER_CONVOLVE  tmp[y][x] = sum over k of h[k] S[y][cx(x + k - nh / 2)], not rounded;
+ *                       acc = sum over k of v[k] tmp[r(y + k - nv / 2)][x];
+ *                       out = min(max((acc + 32768) >> 16, 0), M): one rounding per sample.  Taps {256} on both axes give a copy.
+ *   OH_FILTER_UNSHARP   B is the CONVOLVE output of the plane with its class's taps, d = S - B; out = S where |d| <= threshold[q],
+ *                       else min(max(S + ((amount[q] d + 32) >> 6), 0), M).  An amount of 64 adds the whole detail once, a negative
+ *                       one softens, 0 is a copy.
+ *   OH_FILTER_MEDIAN    the fifth smallest of the nine samples S[r(y + j)][cx(x + i)], i, j in {-1, 0, 1}.
+ *   OH_FILTER_TEMPORAL  P / C / N are the planes of prev / src / next; mp = sum over i, j in {-1, 0, 1} of |P[r(y + j)][cx(x + i)] -
+ *                       C[r(y + j)][cx(x + i)]|, mn the same with N; p' = mp <= threshold[q] ? P[y][x] : C[y][x], n' the same with
+ *                       mn and N; out = (p' + 2 C[y][x] + n' + 2) >> 2.  With prev == src == next the output is src exactly; no clip
+ *                       is needed.
+ * planes: bit c set, plane c is filtered; clear, it is copied; bits of planes the format lacks are ignored.  taps[0] are luma's,
+ * taps[1] those of both chroma planes; amount and threshold likewise.
+ * prev_ids / next_ids are read by OH_FILTER_TEMPORAL only and not even checked by the other modes; a null array, or an entry of -1,
+ * stands for the src picture of that index, as in oh_pics_deinterlace.
+ * The fields a mode does not read are not checked: CONVOLVE ignores amount and threshold, MEDIAN and TEMPORAL ignore taps and amount
+ * (MEDIAN the threshold too).  The fields it reads are checked for both classes, whatever `planes` says.
+ * All pictures involved have identical OhPicParams.  Reads finished halves, writes half 0 of each destination and marks it finished,
+ * like oh_pics_deinterlace; enqueued on the engine stream, returns without waiting.  n == 0: OH_OK (the OhFilter is checked all the
+ * same, its thresholds against the M of 12 bit, there being no picture to take a depth from).  More than OH_CONV_MAX_PICS pictures are
+ * split into several launches.
+ * OH_E_ARG, nothing written: a null e, f, src_ids or dst_ids, or a negative n; an unknown picture, or an id below -1 in prev / next;
+ * params that differ anywhere among src, dst and (TEMPORAL) prev / next; a destination that is also any source of the call, or a
+ * destination listed twice; a mode outside 0 .. 3; planes outside 0 .. 7; illegal taps; an amount outside -64 .. 512; a threshold
+ * outside 0 .. M (UNSHARP) or 0 .. 9 M (TEMPORAL).  No combination gives OH_E_UNSUPPORTED. */
+enum { OH_FILTER_CONVOLVE = 0, OH_FILTER_UNSHARP, OH_FILTER_MEDIAN, OH_FILTER_TEMPORAL };
+enum { OH_FILTER_MAX_TAPS = 15 };
+typedef struct OhFilterTaps { int32_t nh, nv; int16_t h[OH_FILTER_MAX_TAPS], v[OH_FILTER_MAX_TAPS]; } OhFilterTaps;
+typedef struct OhFilter {
+    int32_t      mode;          /* OH_FILTER_* */
+    int32_t      planes;        /* bit c set: plane c is filtered; clear: plane c is copied.  0 .. 7; bits of planes the format lacks are ignored */
+    OhFilterTaps taps[2];       /* [0] luma, [1] both chroma planes: CONVOLVE, UNSHARP */
+    int32_t      amount[2];     /* UNSHARP, in 1/64: -64 .. 512 */
+    int32_t      threshold[2];  /* UNSHARP: 0 .. M;  TEMPORAL: 0 .. 9 * M */
+} OhFilter;
+int oh_pics_filter(OhEngine *e, const int *prev_ids, const int *src_ids, const int *next_ids,
+                   const int *dst_ids, int n, const OhFilter *f);
+/* host only: OH_OK for a legal tap set (above), else OH_E_ARG (a null pointer too) */
+int oh_filter_taps_check(const OhFilterTaps *t);
+/* host only: row n - 1 of Pascal's triangle scaled to sum 256, n in {1, 3, 5, 7, 9}: {256}, {64,128,64}, {16,64,96,64,16},
+ * {4,24,60,80,60,24,4}, {1,8,28,56,70,56,28,8,1}; any other n, or a null pointer: OH_E_ARG */
+int oh_filter_binomial(int n, int16_t *out);
+/* host only: n equal taps, n odd in 1 .. 15: each 256 / n in integer division, the middle one the remainder more; else OH_E_ARG */
+int oh_filter_box(int n, int16_t *out);
+/* host only: the sample formulas above (the functions the kernel evaluates, csrc/filter_common.h).  oh_filter_unsharp: s the source
+ * sample, b the CONVOLVE output; oh_filter_median9: the fifth smallest of nine values in any order; oh_filter_temporal: c / p / n the
+ * samples of src / prev / next at one place, mp / mn the two window sums */
+int32_t oh_filter_unsharp(int32_t s, int32_t b, int32_t amount, int32_t threshold, int32_t M);
+int32_t oh_filter_median9(const int32_t v[9]);
+int32_t oh_filter_temporal(int32_t c, int32_t p, int32_t n, int32_t mp, int32_t mn, int32_t threshold);
+
 /* SHVC inter-layer reference picture: resample the finished base-layer picture src_pic into
  * the enhancement-layer picture dst_pic, bit-exact with the reference's whole-picture slot
  * HEVCDSPContext.upsample_base_layer_frame (hevcdsp_template.c:2164-2438, call site hevc.c:3241).

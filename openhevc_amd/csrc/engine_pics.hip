@@ -1,9 +1,9 @@
 /*
  * engine_pics.hip — what the engine does with finished pictures beside the reconstruction path (host side; the kernels are md5.hip,
- * hash.hip, convert.hip, import.hip, colour.hip, light.hip, compare.hip, resize.hip, reformat.hip, orient.hip, deinterlace.hip and compose.hip): plane upload and download,
+ * hash.hip, convert.hip, import.hip, colour.hip, light.hip, compare.hip, resize.hip, reformat.hip, orient.hip, deinterlace.hip, filter.hip and compose.hip): plane upload and download,
  * the two-phase window fetch, picture hashes, conversion to YUV / RGB images and back, with the colour tables of the HDR forms, light-level
  * statistics, comparison of two pictures, resizing into engine pictures, reformatting into pictures of another bit depth or chroma format, orientation (crop, flip, quarter turns, transpose),
- * fields (weave, separate, deinterlace) and composition of pictures in place: fill, overlay, alpha blend.
+ * fields (weave, separate, deinterlace), filters (blur, sharpen, median, temporal denoise) and composition of pictures in place: fill, overlay, alpha blend.
  * Their arithmetic, which needs neither an engine nor a device, is pics_math.hip; the helpers at the top are what the services share.
  */
 #include <cmath>
@@ -1205,6 +1205,85 @@ extern "C" int oh_pics_deinterlace(OhEngine *e, const int *prev_ids, const int *
             q->done_seq = 0;
         }
         ohk_deinterlace(&a, m, e->stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    return OH_OK;
+}
+
+/* ---------------- filters (filter.hip) ---------------- */
+extern "C" int oh_pics_filter(OhEngine *e, const int *prev_ids, const int *src_ids, const int *next_ids, const int *dst_ids, int n,
+                              const OhFilter *f)
+{
+    const char *who = "oh_pics_filter";
+    if (!e || n < 0 || !f || (n && (!src_ids || !dst_ids)))
+        return OH_E_ARG;
+    if (f->mode < OH_FILTER_CONVOLVE || f->mode > OH_FILTER_TEMPORAL)
+        FAIL(e, OH_E_ARG, "%s: mode %d (0 convolve, 1 unsharp, 2 median, 3 temporal)", who, f->mode);
+    if (!n) {                                                   /* no picture, no bit depth: what does not depend on one */
+        std::string why;
+        const int rc = filter_check(f, 12, &why);
+        if (rc) FAIL(e, rc, "%s: %s", who, why.c_str());
+        return OH_OK;
+    }
+    /* the pictures of index i: prev, src, next; a null array or an entry of -1 stands for src; read by TEMPORAL only */
+    const bool temporal = f->mode == OH_FILTER_TEMPORAL;
+    std::vector<int> around[2];
+    std::vector<int> srcs(src_ids, src_ids + n);
+    for (int k = 0; k < 2; k++) {
+        const int *ids = k ? next_ids : prev_ids;
+        around[k] = std::vector<int>(src_ids, src_ids + n);
+        if (!temporal || !ids)
+            continue;
+        for (int i = 0; i < n; i++) {
+            if (ids[i] < -1)
+                FAIL(e, OH_E_ARG, "%s: %s picture %d (-1 stands for the src picture)", who, k ? "next" : "prev", ids[i]);
+            if (ids[i] >= 0)
+                around[k][i] = ids[i];
+        }
+        srcs.insert(srcs.end(), around[k].begin(), around[k].end());
+    }
+    std::vector<int> all(srcs);
+    all.insert(all.end(), dst_ids, dst_ids + n);
+    const Pic *p0 = alike_pics(e, who, all.data(), (int)all.size());
+    if (!p0) return OH_E_ARG;
+    { const int rc = dsts_apart(e, who, std::vector<int>(dst_ids, dst_ids + n), srcs); if (rc) return rc; }
+    const OhPicParams &p = p0->p;
+    {
+        std::string why;
+        const int rc = filter_check(f, p.bit_depth, &why);
+        if (rc) FAIL(e, rc, "%s: %s", who, why.c_str());
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    OhFilterArgs a;
+    memset(&a, 0, sizeof(a));
+    const int bpp = sample_bytes(p.bit_depth);
+    a.np = p.chroma_format_idc ? 3 : 1; a.bd = p.bit_depth;
+    a.mode = f->mode; a.planes = f->planes;
+    for (int c = 0; c < a.np; c++) a.pitch[c] = p0->stride[c] * bpp;
+    for (int q = 0; q < 2; q++) {
+        if (q < (a.np > 1 ? 2 : 1)) { a.w[q] = p0->w[q]; a.h[q] = p0->h[q]; }
+        a.amount[q] = f->amount[q]; a.threshold[q] = f->threshold[q];
+        if (f->mode > OH_FILTER_UNSHARP)
+            continue;
+        const OhFilterTaps &t = f->taps[q];
+        for (int k = 0; k < t.nh; k++) a.taps_h[q][OH_FILTER_MAX_TAPS / 2 - t.nh / 2 + k] = t.h[k];
+        for (int k = 0; k < t.nv; k++) a.taps_v[q][OH_FILTER_MAX_TAPS / 2 - t.nv / 2 + k] = t.v[k];
+        a.radius = std::max(a.radius, std::max(t.nh, t.nv) / 2);
+    }
+    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
+        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+        for (int i = 0; i < m; i++) {
+            const Pic *s[3] = { get_pic(e, around[0][i0 + i]), get_pic(e, src_ids[i0 + i]), get_pic(e, around[1][i0 + i]) };
+            Pic *d = get_pic(e, dst_ids[i0 + i]);
+            for (int c = 0; c < 3; c++) {
+                for (int k = 0; k < 3; k++)
+                    a.src[k][i][c] = c < a.np ? final_planes(s[k])[c] : nullptr;
+                a.dst[i][c] = c < a.np ? d->a[c] : nullptr;
+            }
+            d->final_b = false;                                  /* the image is a finished picture in half 0 */
+            d->done_seq = 0;
+        }
+        ohk_filter(&a, m, e->stream);
         HIPCHK(e, hipGetLastError());
     }
     return OH_OK;

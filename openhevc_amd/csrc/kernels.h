@@ -192,6 +192,23 @@ struct OhDiArgs {
     int32_t     mode, parity, kept_first;    /* ohk_deinterlace: OhDeinterlace */
 };
 
+/* picture filters (filter.hip): the planes of the pictures of one launch by value in the kernel arguments, and the taps
+ * with them; every picture of a launch has the same geometry.  Two plane classes (0 luma, 1 chroma). */
+enum { OH_FLT_TW = 128,              /* destination samples across one workgroup's tile: the horizontal unit */
+       OH_FLT_TH = 32 };             /* destination rows of a tile: the vertical unit */
+struct OhFilterArgs {
+    const void *src[3][64][3];       /* prev, src, next (finished halves; prev and next are read by OH_FILTER_TEMPORAL only) x
+                                        OH_CONV_MAX_PICS pictures x planes */
+    void       *dst[64][3];          /* half 0 of the destinations */
+    int32_t     pitch[3];            /* bytes between rows of each plane */
+    int32_t     w[2], h[2];          /* coded size of the planes */
+    int32_t     np, bd;              /* planes: 1 or 3; bit depth */
+    int32_t     mode, planes;        /* OhFilter */
+    int32_t     radius;              /* CONVOLVE, UNSHARP: the largest nh / 2, nv / 2 of both classes */
+    int32_t     taps_h[2][15], taps_v[2][15];   /* the taps of each class, centred: entry OH_FILTER_MAX_TAPS / 2 is the middle tap, zeros around */
+    int32_t     amount[2], threshold[2];
+};
+
 /* picture resizing (resize.hip): what one launch set needs, by value in the kernel arguments like OhConvArgs.  Two plane
  * classes (0 luma, 1 chroma), each with its own geometry and tap tables; the tables live in device memory that the engine owns and
  * fills (engine_pics.hip: oh_pics_resize, from pics_math.hip: oh_resize_taps) on the stream in front of the launches. */
@@ -251,6 +268,8 @@ void ohk_orient(const OhOrArgs *a, int n, hipStream_t st);
 void ohk_deinterlace(const OhDiArgs *a, int n, hipStream_t st);
 /* n pairs of fields woven into n frames, or n frames separated into one or two fields each */
 void ohk_fields(const OhDiArgs *a, int n, hipStream_t st);
+/* n pictures of a.src[1] (with a.src[0] and a.src[2] around them in time) filtered into the n destinations of a.dst */
+void ohk_filter(const OhFilterArgs *a, int n, hipStream_t st);
 void ohk_hash(int kind, const OhMd5Job *jobs, const uint32_t *first, const uint32_t *task_map, int n_jobs, int n_tasks, uint32_t *partials,
               uint32_t *out, hipStream_t st);
 void ohk_inter(const OhBatch *B, int n, const OhPicParams *p, uint32_t max_luma, uint32_t max_chroma, hipStream_t st);

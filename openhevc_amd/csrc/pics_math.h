@@ -15,5 +15,6 @@ OH_INTERNAL int conv_sample_bytes(const OhConvert *cv, int bit_depth);
 OH_INTERNAL int conv_check(const OhPicParams *p, const OhConvert *cv, size_t *bytes, std::string *why);
 OH_INTERNAL int colour_check(const OhColour *col, std::string *why);
 OH_INTERNAL int colour_build(const OhColour *col, int32_t *tab, int32_t *misc, std::string *why);
+OH_INTERNAL int filter_check(const OhFilter *f, int bit_depth, std::string *why);
 
 #endif

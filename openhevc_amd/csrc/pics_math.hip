@@ -1,7 +1,7 @@
 /*
  * pics_math.hip — the host arithmetic of the picture services (engine_pics.hip), with neither an engine nor a device: image sizes and
  * crop windows, the integers of the RGB conversions, the colour tables of the HDR forms, light-level bins and percentiles, the SSIM window
- * and PSNR, the resize taps, the compose formulas, the reformat quantisation, the orientations' group, the pic_struct table and the adaptive deinterlacer's sample.  No kernel, no HIP runtime call: tests/pics_math_check.cpp runs it under sanitizers.
+ * and PSNR, the resize taps, the compose formulas, the reformat quantisation, the orientations' group, the pic_struct table, the adaptive deinterlacer's sample and the filters' taps and samples.  No kernel, no HIP runtime call: tests/pics_math_check.cpp runs it under sanitizers.
  */
 #include <stdio.h>
 #include <string.h>
@@ -15,6 +15,7 @@
 #include "compose_common.h"
 #include "reformat_common.h"
 #include "deinterlace_common.h"
+#include "filter_common.h"
 
 static bool depth_ok(int bit_depth) { return bit_depth == 8 || bit_depth == 9 || bit_depth == 10 || bit_depth == 12; }
 
@@ -625,4 +626,77 @@ extern "C" int oh_field_info(int pic_struct, OhFieldInfo *out)
 extern "C" int32_t oh_deint_adaptive(const int32_t up[7], const int32_t dn[7], int32_t a, int32_t b, int32_t pu, int32_t pd, int32_t nu, int32_t nd)
 {
     return deint_adaptive(up, dn, a, b, pu, pd, nu, nd);
+}
+
+/* ---------------- filters (filter.hip) ---------------- */
+extern "C" int oh_filter_taps_check(const OhFilterTaps *t)
+{
+    if (!t || t->nh < 1 || t->nh > OH_FILTER_MAX_TAPS || !(t->nh & 1) || t->nv < 1 || t->nv > OH_FILTER_MAX_TAPS || !(t->nv & 1))
+        return OH_E_ARG;
+    for (int axis = 0; axis < 2; axis++) {
+        const int16_t *k = axis ? t->v : t->h;
+        int sum = 0, mag = 0;
+        for (int i = 0; i < (axis ? t->nv : t->nh); i++) { sum += k[i]; mag += std::abs((int)k[i]); }
+        if (sum != 256 || mag > 512)
+            return OH_E_ARG;
+    }
+    return OH_OK;
+}
+
+extern "C" int oh_filter_binomial(int n, int16_t *out)
+{
+    if (!out || n < 1 || n > 9 || !(n & 1))
+        return OH_E_ARG;
+    int row[9] = { 1 };
+    for (int i = 1; i < n; i++)                                 /* row n - 1 of Pascal's triangle: its sum 2^(n - 1) divides 256 */
+        for (int j = i; j > 0; j--) row[j] += row[j - 1];
+    for (int j = 0; j < n; j++) out[j] = (int16_t)(row[j] * (256 >> (n - 1)));
+    return OH_OK;
+}
+
+extern "C" int oh_filter_box(int n, int16_t *out)
+{
+    if (!out || n < 1 || n > OH_FILTER_MAX_TAPS || !(n & 1))
+        return OH_E_ARG;
+    for (int j = 0; j < n; j++) out[j] = (int16_t)(256 / n);
+    out[n / 2] += (int16_t)(256 % n);
+    return OH_OK;
+}
+
+extern "C" int32_t oh_filter_unsharp(int32_t s, int32_t b, int32_t amount, int32_t threshold, int32_t M)
+{
+    return filter_unsharp(s, b, amount, threshold, M);
+}
+
+extern "C" int32_t oh_filter_median9(const int32_t v[9]) { return filter_median9(v); }
+
+extern "C" int32_t oh_filter_temporal(int32_t c, int32_t p, int32_t n, int32_t mp, int32_t mn, int32_t threshold)
+{
+    return filter_temporal(c, p, n, mp, mn, threshold);
+}
+
+/* what oh_pics_filter checks of the OhFilter itself, for pictures of bit_depth bits: the fields its mode reads, for both classes */
+int filter_check(const OhFilter *f, int bit_depth, std::string *why)
+{
+    char buf[256];
+    const int M = (1 << bit_depth) - 1;
+    if (f->mode < OH_FILTER_CONVOLVE || f->mode > OH_FILTER_TEMPORAL) {
+        snprintf(buf, sizeof(buf), "mode %d (0 convolve, 1 unsharp, 2 median, 3 temporal)", f->mode); *why = buf; return OH_E_ARG;
+    }
+    if (f->planes < 0 || f->planes > 7) { snprintf(buf, sizeof(buf), "planes %d (0 .. 7)", f->planes); *why = buf; return OH_E_ARG; }
+    for (int q = 0; q < 2; q++) {
+        if (f->mode <= OH_FILTER_UNSHARP && oh_filter_taps_check(&f->taps[q])) {
+            snprintf(buf, sizeof(buf), "taps[%d]: %d x %d taps; each axis an odd number of 1 .. %d that sum to 256, their magnitudes to 512 at most",
+                     q, f->taps[q].nh, f->taps[q].nv, (int)OH_FILTER_MAX_TAPS);
+            *why = buf; return OH_E_ARG;
+        }
+        if (f->mode == OH_FILTER_UNSHARP && (f->amount[q] < -64 || f->amount[q] > 512)) {
+            snprintf(buf, sizeof(buf), "amount[%d] %d (-64 .. 512)", q, f->amount[q]); *why = buf; return OH_E_ARG;
+        }
+        const int64_t top = f->mode == OH_FILTER_TEMPORAL ? 9 * (int64_t)M : M;
+        if ((f->mode == OH_FILTER_UNSHARP || f->mode == OH_FILTER_TEMPORAL) && (f->threshold[q] < 0 || f->threshold[q] > top)) {
+            snprintf(buf, sizeof(buf), "threshold[%d] %d (0 .. %lld)", q, f->threshold[q], (long long)top); *why = buf; return OH_E_ARG;
+        }
+    }
+    return OH_OK;
 }

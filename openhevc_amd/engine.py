@@ -449,6 +449,72 @@ def deint_adaptive(up, dn, a, b, pu, pd, nu, nd):
     return int(lib().oh_deint_adaptive((C.c_int32 * 7)(*up), (C.c_int32 * 7)(*dn), int(a), int(b), int(pu), int(pd), int(nu), int(nd)))
 
 
+FILTER_MAX_TAPS = 15                                                                    # OH_FILTER_MAX_TAPS
+
+
+class OhFilterTaps(C.Structure):                              # include/ohevc_hip.h
+    _fields_ = [("nh", C.c_int32), ("nv", C.c_int32), ("h", C.c_int16 * FILTER_MAX_TAPS), ("v", C.c_int16 * FILTER_MAX_TAPS)]
+
+
+class OhFilter(C.Structure):                                  # include/ohevc_hip.h
+    _fields_ = [("mode", C.c_int32), ("planes", C.c_int32), ("taps", OhFilterTaps * 2), ("amount", C.c_int32 * 2),
+                ("threshold", C.c_int32 * 2)]
+
+
+FILTER_CONVOLVE, FILTER_UNSHARP, FILTER_MEDIAN, FILTER_TEMPORAL = 0, 1, 2, 3             # OH_FILTER_*
+FILTER_MODES = {"convolve": FILTER_CONVOLVE, "unsharp": FILTER_UNSHARP, "median": FILTER_MEDIAN, "temporal": FILTER_TEMPORAL}
+FILTER_TW, FILTER_TH = 128, 32                                                          # OH_FLT_TW, OH_FLT_TH (csrc/kernels.h): a workgroup's tile
+
+
+def filter_mode(v):
+    """a name of FILTER_MODES or an int 0 .. 3 -> the int"""
+    if isinstance(v, str):
+        if v not in FILTER_MODES:
+            raise ValueError(f"unknown filter mode {v!r}: one of {sorted(FILTER_MODES)}")
+        return FILTER_MODES[v]
+    v = int(v)
+    if not 0 <= v <= 3:
+        raise ValueError(f"filter mode {v}: 0 .. 3")
+    return v
+
+
+def _filter_row(name, n):
+    out = (C.c_int16 * FILTER_MAX_TAPS)()
+    rc = getattr(lib(), name)(int(n), out)
+    if rc != 0:
+        err = EngineError(f"{name}({n}) failed ({rc})")
+        err.code = rc
+        raise err
+    return [int(v) for v in out[:n]]
+
+
+def filter_binomial(n):
+    """oh_filter_binomial (host only): row n - 1 of Pascal's triangle scaled to sum 256, n in {1, 3, 5, 7, 9}"""
+    return _filter_row("oh_filter_binomial", n)
+
+
+def filter_box(n):
+    """oh_filter_box (host only): n equal taps of sum 256, n odd in 1 .. 15, the middle one taking the remainder of 256 / n"""
+    return _filter_row("oh_filter_box", n)
+
+
+def filter_taps(h, v):
+    """an OhFilterTaps of the horizontal taps h and the vertical taps v; EngineError with code OH_E_ARG unless it is legal
+    (oh_filter_taps_check: each axis an odd number of 1 .. 15 taps that sum to 256, their magnitudes to 512 at most)"""
+    h, v = [int(k) for k in h], [int(k) for k in v]
+    if not 1 <= len(h) <= FILTER_MAX_TAPS or not 1 <= len(v) <= FILTER_MAX_TAPS or any(not -32768 <= k <= 32767 for k in h + v):
+        raise ValueError(f"{len(h)} x {len(v)} taps: 1 .. {FILTER_MAX_TAPS} int16 values on either axis")
+    t = OhFilterTaps(len(h), len(v))
+    t.h[:len(h)] = h
+    t.v[:len(v)] = v
+    rc = lib().oh_filter_taps_check(C.byref(t))
+    if rc != 0:
+        err = EngineError(f"taps {h} x {v} are not legal ({rc})")
+        err.code = rc
+        raise err
+    return t
+
+
 def convert_image_bytes(params, cv):
     """oh_convert_image_bytes (host only): bytes of one image, 0 when the combination is not valid"""
     return int(lib().oh_convert_image_bytes(C.byref(params), C.byref(cv)))
@@ -559,6 +625,16 @@ def lib():
         L.oh_pics_deinterlace.argtypes = [V, IP, IP, IP, IP, I, C.POINTER(OhDeinterlace)]
         L.oh_deint_adaptive.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32)] + [C.c_int32] * 6
         L.oh_deint_adaptive.restype = C.c_int32
+        L.oh_pics_filter.argtypes = [V, IP, IP, IP, IP, I, C.POINTER(OhFilter)]
+        L.oh_filter_taps_check.argtypes = [C.POINTER(OhFilterTaps)]
+        L.oh_filter_binomial.argtypes = [I, C.POINTER(C.c_int16)]
+        L.oh_filter_box.argtypes = [I, C.POINTER(C.c_int16)]
+        L.oh_filter_unsharp.argtypes = [C.c_int32] * 5
+        L.oh_filter_unsharp.restype = C.c_int32
+        L.oh_filter_median9.argtypes = [C.POINTER(C.c_int32)]
+        L.oh_filter_median9.restype = C.c_int32
+        L.oh_filter_temporal.argtypes = [C.c_int32] * 6
+        L.oh_filter_temporal.restype = C.c_int32
         L.oh_pics_resize.argtypes = [V, C.POINTER(C.c_int), C.POINTER(C.c_int), I, C.POINTER(OhResize)]
         L.oh_resize_taps.argtypes = [I, I, I, I, C.POINTER(C.c_int32), C.POINTER(C.c_int16), I, C.POINTER(C.c_int)]
         L.oh_resize_max_taps.argtypes = [I, I, I]
@@ -1163,6 +1239,51 @@ class Engine:
             for pid in out:
                 self.pic_free(pid)
         self._chk(rc, "oh_pics_deinterlace")
+        return out
+
+    def pics_filter(self, pids, mode, *, luma=None, chroma=None, amount=64, threshold=0, planes=7, prev=None, next=None, out=None):
+        """finished pictures -> finished filtered pictures of the same params (oh_pics_filter; the exact definitions are in
+        include/ohevc_hip.h).  mode: "convolve", "unsharp", "median", "temporal" or FILTER_*; luma / chroma: (h, v) tap lists of the
+        luma plane and of both chroma planes (convolve, unsharp), None the binomial 3 x 3; amount (unsharp, in 1/64) and threshold
+        (unsharp, temporal): an int for both classes or a pair (luma, chroma); planes: bit c set filters plane c, clear copies it;
+        prev / next: the pictures before and after each one in time (temporal only), lists that may hold None, which like prev=None /
+        next=None stands for the picture itself.  out: destination pictures to reuse; None allocates pictures with the sources'
+        params.  Returns the destination ids.  Enqueued on the engine stream; does not wait."""
+        pids = list(pids)
+        n = len(pids)
+        if n == 0:
+            raise ValueError("pics_filter needs at least one picture (the destinations follow the pictures' params)")
+        ff = OhFilter(filter_mode(mode), int(planes))
+        for q, taps in enumerate((luma, chroma)):
+            h, v = (filter_binomial(3), filter_binomial(3)) if taps is None else taps
+            ff.taps[q] = filter_taps(h, v)
+        for name, val, arr in (("amount", amount, ff.amount), ("threshold", threshold, ff.threshold)):
+            pair = tuple(val) if hasattr(val, "__len__") else (val, val)
+            if len(pair) != 2:
+                raise ValueError(f"{name}: an int or a pair (luma, chroma)")
+            arr[0], arr[1] = int(pair[0]), int(pair[1])
+        IA = C.c_int * n
+        around = []
+        for name, ids in (("prev", prev), ("next", next)):
+            if ids is None:
+                around.append(None)
+                continue
+            ids = [-1 if v is None else int(v) for v in ids]
+            if len(ids) != n:
+                raise ValueError(f"{name}: {len(ids)} entries for {n} sources")
+            around.append(IA(*ids))
+        fresh = out is None
+        if fresh:
+            out = self._alloc_like(pids[0], self._pic_params(pids[0]).height, n)
+        else:
+            out = list(out)
+            if len(out) != n:
+                raise ValueError(f"out: {len(out)} pictures for {n} sources")
+        rc = self.L.oh_pics_filter(self.h, around[0], IA(*pids), around[1], IA(*out), n, C.byref(ff))
+        if rc != 0 and fresh:
+            for pid in out:
+                self.pic_free(pid)
+        self._chk(rc, "oh_pics_filter")
         return out
 
     def pics_compose(self, dst, layers, *, fill=None):
