@@ -1,9 +1,6 @@
 /*
- * engine_pics.hip — what the engine does with finished pictures beside the reconstruction path (host side; the kernels are md5.hip,
- * hash.hip, convert.hip, import.hip, colour.hip, light.hip, compare.hip, resize.hip, reformat.hip, orient.hip, deinterlace.hip, filter.hip and compose.hip): plane upload and download,
- * the two-phase window fetch, picture hashes, conversion to YUV / RGB images and back, with the colour tables of the HDR forms, light-level
- * statistics, comparison of two pictures, resizing into engine pictures, reformatting into pictures of another bit depth or chroma format, orientation (crop, flip, quarter turns, transpose),
- * fields (weave, separate, deinterlace), filters (blur, sharpen, median, temporal denoise) and composition of pictures in place: fill, overlay, alpha blend.
+ * engine_pics.hip — the host side of what the engine does with finished pictures beside the reconstruction path: plane upload and
+ * download, the two-phase window fetch, and the picture services, one section each below with its kernel file and its part of DESIGN.md.
  * Their arithmetic, which needs neither an engine nor a device, is pics_math.hip; the helpers at the top are what the services share.
  */
 #include <cmath>
@@ -55,6 +52,71 @@ static int distinct_dsts(OhEngine *e, const char *who, const int *dst_ids, int n
     return OH_OK;
 }
 
+/* no destination is listed twice and none is among the sources */
+static int dsts_apart(OhEngine *e, const char *who, const int *dst_ids, int nd, const int *src_ids, int ns)
+{
+    int both = 0;
+    switch (ids_apart(dst_ids, nd, src_ids, ns, &both)) {
+    case 1: FAIL(e, OH_E_ARG, "%s: a destination is listed twice", who);
+    case 2: FAIL(e, OH_E_ARG, "%s: picture %d is both source and destination", who, both);
+    }
+    return OH_OK;
+}
+
+/* the pictures of index i in time: around[0][i] before and around[1][i] after own_ids[i] (`own`: what the call names it), where a null
+ * array or an entry of -1 stands for the picture itself; srcs: every source of the call.  used: the mode reads them at all */
+struct Neighbours { std::vector<int> around[2], srcs; };
+static int neighbours(OhEngine *e, const char *who, const char *own, const int *prev_ids, const int *own_ids, const int *next_ids, int n,
+                      bool used, Neighbours *nb)
+{
+    const int *const ids[2] = { prev_ids, next_ids };
+    int side = 0;
+    const int bad = neighbours_resolve(ids, own_ids, n, used, nb->around, &nb->srcs, &side);
+    if (bad >= 0)
+        FAIL(e, OH_E_ARG, "%s: %s picture %d (-1 stands for the %s picture)", who, side ? "next" : "prev", ids[side][bad], own);
+    return OH_OK;
+}
+
+/* sources and n destinations of one kind: all known and alike, the destinations apart.  The first source, or nullptr (OH_E_ARG) */
+static const Pic *alike_apart(OhEngine *e, const char *who, const std::vector<int> &srcs, const int *dst_ids, int n)
+{
+    std::vector<int> all(srcs);
+    all.insert(all.end(), dst_ids, dst_ids + n);
+    const Pic *p0 = alike_pics(e, who, all.data(), (int)all.size());
+    if (!p0 || dsts_apart(e, who, dst_ids, n, srcs.data(), (int)srcs.size()))
+        return nullptr;
+    return p0;
+}
+
+/* a picture's geometry as the kernels take it: planes (1 or 3), bytes between the rows of the first np planes, and the coded size of
+ * the plane classes (0 luma, 1 chroma) that np planes have.  What a helper does not set stays as the caller cleared it */
+static int n_planes(const OhPicParams &p) { return p.chroma_format_idc ? 3 : 1; }
+
+static void row_pitches(const Pic *p, int np, int32_t pitch[3])
+{
+    for (int c = 0; c < np; c++) pitch[c] = p->stride[c] * sample_bytes(p->p.bit_depth);
+}
+
+static void class_sizes(const Pic *p, int np, int32_t w[2], int32_t h[2])
+{
+    for (int q = 0; q < (np > 1 ? 2 : 1); q++) { w[q] = p->w[q]; h[q] = p->h[q]; }
+}
+
+/* the planes of a picture that a launch reads: its finished half, null from plane np on */
+template <typename P> static void read_planes(const Pic *p, int np, P planes[3])
+{
+    for (int c = 0; c < 3; c++) planes[c] = c < np ? final_planes(p)[c] : nullptr;
+}
+
+/* the planes of a picture that a launch writes: half 0, which holds the finished picture from here on, and no reconstruction batch
+ * made it: a download stays behind the engine stream.  Called per launch set, after every check of the call, in front of the launch */
+static void write_planes(Pic *p, int np, void *planes[3])
+{
+    for (int c = 0; c < 3; c++) planes[c] = c < np ? p->a[c] : nullptr;
+    p->final_b = false;
+    p->done_seq = 0;
+}
+
 /* the bytes from ptr to the end of its allocation; ROOM_NONE: ptr is not device memory of the engine's device (the current one);
  * ROOM_UNKNOWN: it is, but the runtime cannot tell its extent — callers let such memory pass */
 enum : size_t { ROOM_NONE = 0, ROOM_UNKNOWN = ~(size_t)0 };
@@ -93,10 +155,10 @@ static int image_run_check(OhEngine *e, const char *who, const char *what, const
 static void conv_args(OhConvArgs *a, const Pic *p0, const OhConvert *cv)
 {
     const OhPicParams &p = p0->p;
-    for (int c = 0; c < 3; c++) a->pitch[c] = p0->stride[c] * sample_bytes(p.bit_depth);
+    row_pitches(p0, 3, a->pitch);
     a->cw = p0->w[1]; a->ch = p0->h[1];
     a->left = cv->win.left; a->top = cv->win.top;
-    a->W = p.width - cv->win.left - cv->win.right; a->H = p.height - cv->win.top - cv->win.bottom;
+    window_size(&p, cv->win, &a->W, &a->H);
     a->cf = p.chroma_format_idc; a->bd = p.bit_depth; a->filter = cv->chroma_filter;
 }
 
@@ -209,11 +271,12 @@ extern "C" int oh_pic_download_start(OhEngine *e, int pic_id, const OhWindow *wi
     std::string why;
     if (!crop_window_ok(&p->p, *win, false, &why))
         FAIL(e, OH_E_ARG, "oh_pic_download_window: %s", why.c_str());
-    const int W = p->p.width - win->left - win->right, H = p->p.height - win->top - win->bottom;
+    int W, H;
+    window_size(&p->p, *win, &W, &H);
     HIPCHK(e, hipSetDevice(e->device));
     const size_t bpp = sample_bytes(p->p.bit_depth);
     OhDownload d;
-    d.np = p->p.chroma_format_idc ? 3 : 1;
+    d.np = n_planes(p->p);
     size_t total = 0;
     for (int c = 0; c < d.np; c++) {
         const int hs = oh_hshift(&p->p, c), vs = oh_vshift(&p->p, c);
@@ -473,10 +536,7 @@ static int pics_convert(OhEngine *e, const char *who, const int *pic_ids, int n,
     }
     for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
         const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
-        for (int i = 0; i < m; i++) {
-            const Pic *q = get_pic(e, pic_ids[i0 + i]);
-            for (int c = 0; c < 3; c++) a.src[i][c] = a.cf || !c ? final_planes(q)[c] : nullptr;
-        }
+        for (int i = 0; i < m; i++) read_planes(get_pic(e, pic_ids[i0 + i]), n_planes(p0->p), a.src[i]);
         a.dst = (char *)dst + (size_t)i0 * image_stride;
         if (col) ohk_colour(&ca, cv->format, cv->sample, m, e->stream);
         else     ohk_convert(&a, cv->format, cv->sample, m, e->stream);
@@ -504,8 +564,7 @@ extern "C" int oh_pics_import(OhEngine *e, const int *pic_ids, int n, const OhCo
         return OH_OK;
     const Pic *p0 = alike_pics(e, who, pic_ids, n);
     if (!p0) return OH_E_ARG;
-    std::vector<int> sorted;
-    { const int rc = distinct_dsts(e, who, pic_ids, n, &sorted); if (rc) return rc; }
+    { const int rc = dsts_apart(e, who, pic_ids, n, nullptr, 0); if (rc) return rc; }
     size_t ib = 0;
     std::string why;
     { const int rc = conv_check(&p0->p, cv, &ib, &why); if (rc) FAIL(e, rc, "%s: %s", who, why.c_str()); }
@@ -513,12 +572,11 @@ extern "C" int oh_pics_import(OhEngine *e, const int *pic_ids, int n, const OhCo
     OhImpArgs a;
     memset(&a, 0, sizeof(a));
     const OhPicParams &p = p0->p;
-    const int bpp = sample_bytes(p.bit_depth), np = p.chroma_format_idc ? 3 : 1;
-    for (int c = 0; c < np; c++) a.pitch[c] = p0->stride[c] * bpp;
-    a.pw[0] = p0->w[0]; a.ph[0] = p0->h[0];
-    a.pw[1] = np > 1 ? p0->w[1] : 0; a.ph[1] = np > 1 ? p0->h[1] : 0;
+    const int np = n_planes(p);
+    row_pitches(p0, np, a.pitch);
+    class_sizes(p0, np, a.pw, a.ph);
     a.left = cv->win.left; a.top = cv->win.top;
-    a.W = p.width - cv->win.left - cv->win.right; a.H = p.height - cv->win.top - cv->win.bottom;
+    window_size(&p, cv->win, &a.W, &a.H);
     a.cf = p.chroma_format_idc; a.bd = p.bit_depth; a.filter = cv->chroma_filter;
     a.nc = cv->format == OH_CONV_RGBA ? 4 : 3;
     a.image_stride = image_stride;
@@ -528,12 +586,7 @@ extern "C" int oh_pics_import(OhEngine *e, const int *pic_ids, int n, const OhCo
     }
     for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
         const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
-        for (int i = 0; i < m; i++) {
-            Pic *q = get_pic(e, pic_ids[i0 + i]);
-            for (int c = 0; c < np; c++) a.dst[i][c] = q->a[c];
-            q->final_b = false;                                  /* the image is a finished picture in half 0 */
-            q->done_seq = 0;
-        }
+        for (int i = 0; i < m; i++) write_planes(get_pic(e, pic_ids[i0 + i]), np, a.dst[i]);
         a.src = (const char *)src + (size_t)i0 * image_stride;
         ohk_import(&a, cv->format, cv->sample, m, e->stream);
         HIPCHK(e, hipGetLastError());
@@ -609,10 +662,7 @@ extern "C" int oh_pics_light_level(OhEngine *e, const int *pic_ids, int n, const
     { const int rc = results_begin(e, who, &e->light_res, bytes, n, &sg); if (rc) return rc; }
     for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
         const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
-        for (int i = 0; i < m; i++) {
-            const Pic *q = get_pic(e, pic_ids[i0 + i]);
-            for (int c = 0; c < 3; c++) a.src[i][c] = a.cf || !c ? final_planes(q)[c] : nullptr;
-        }
+        for (int i = 0; i < m; i++) read_planes(get_pic(e, pic_ids[i0 + i]), n_planes(p0->p), a.src[i]);
         la.res = (OhLightDev *)e->light_res.p + i0;
         ohk_light(&la, m, e->stream);
         HIPCHK(e, hipGetLastError());
@@ -649,9 +699,10 @@ extern "C" int oh_pics_compare(OhEngine *e, const int *a_ids, const int *b_ids, 
     HIPCHK(e, hipSetDevice(e->device));
     OhCmpArgs a;
     memset(&a, 0, sizeof(a));
-    const int np = p.chroma_format_idc ? 3 : 1, bpp = sample_bytes(p.bit_depth);
-    const int W = p.width - sp->win.left - sp->win.right, H = p.height - sp->win.top - sp->win.bottom;
-    for (int c = 0; c < np; c++) a.pitch[c] = p0->stride[c] * bpp;
+    const int np = n_planes(p);
+    int W, H;
+    window_size(&p, sp->win, &W, &H);
+    row_pitches(p0, np, a.pitch);
     for (int c = 0; c < (np > 1 ? 2 : 1); c++) {
         OhCmpClass &k = a.k[c];
         const int hs = oh_hshift(&p, c), vs = oh_vshift(&p, c);
@@ -667,11 +718,8 @@ extern "C" int oh_pics_compare(OhEngine *e, const int *a_ids, const int *b_ids, 
     for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
         const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
         for (int i = 0; i < m; i++) {
-            const Pic *qa = get_pic(e, a_ids[i0 + i]), *qb = get_pic(e, b_ids[i0 + i]);
-            for (int c = 0; c < 3; c++) {
-                a.a[i][c] = c < np ? final_planes(qa)[c] : nullptr;
-                a.b[i][c] = c < np ? final_planes(qb)[c] : nullptr;
-            }
+            read_planes(get_pic(e, a_ids[i0 + i]), np, a.a[i]);
+            read_planes(get_pic(e, b_ids[i0 + i]), np, a.b[i]);
         }
         a.res = (OhCmpDev *)e->compare_res.p + (size_t)i0 * 3 * OH_CMP_SLOTS;
         ohk_compare(&a, m, e->stream);
@@ -732,20 +780,12 @@ static int resize_axis(int S, int T, int filter, int phase, ResizeAxis *ax)
 /* what oh_pics_resize checks of its arguments (n > 0, the lists present) */
 static int resize_check(OhEngine *e, const int *src_ids, const int *dst_ids, int n, const OhResize *rs)
 {
-    { const int rc = check_pics(e, src_ids, n, "oh_pics_resize"); if (rc) return rc; }
-    { const int rc = check_pics(e, dst_ids, n, "oh_pics_resize"); if (rc) return rc; }
-    const int other = std::min(first_other_params(e, src_ids, n), first_other_params(e, dst_ids, n));
-    if (other < n)
-        FAIL(e, OH_E_ARG, "oh_pics_resize: pictures %d -> %d have other params than pictures %d -> %d", src_ids[other], dst_ids[other], src_ids[0], dst_ids[0]);
-    {
-        std::vector<int> d, s(src_ids, src_ids + n);
-        { const int rc = distinct_dsts(e, "oh_pics_resize", dst_ids, n, &d); if (rc) return rc; }
-        std::sort(s.begin(), s.end());
-        for (int i = 0; i < n; i++)
-            if (std::binary_search(s.begin(), s.end(), d[i]))
-                FAIL(e, OH_E_ARG, "oh_pics_resize: picture %d is both source and destination", d[i]);
-    }
-    const OhPicParams &sp = get_pic(e, src_ids[0])->p, &dp = get_pic(e, dst_ids[0])->p;
+    const Pic *s0 = alike_pics(e, "oh_pics_resize", src_ids, n);
+    if (!s0) return OH_E_ARG;
+    const Pic *d0 = alike_pics(e, "oh_pics_resize", dst_ids, n);
+    if (!d0) return OH_E_ARG;
+    { const int rc = dsts_apart(e, "oh_pics_resize", dst_ids, n, src_ids, n); if (rc) return rc; }
+    const OhPicParams &sp = s0->p, &dp = d0->p;
     if (rs->filter != OH_RESIZE_BILINEAR && rs->filter != OH_RESIZE_BICUBIC)
         FAIL(e, OH_E_ARG, "oh_pics_resize: filter %d (0 bilinear, 1 bicubic)", rs->filter);
     const int cf = sp.chroma_format_idc, hs = cf == 1 || cf == 2, vs = cf == 1, sw = 1 << hs, sv = 1 << vs;
@@ -759,7 +799,8 @@ static int resize_check(OhEngine *e, const int *src_ids, const int *dst_ids, int
     if (dp.bit_depth != sp.bit_depth || dp.chroma_format_idc != cf)
         FAIL(e, OH_E_UNSUPPORTED, "oh_pics_resize: destinations of %d bit, chroma format %d; sources of %d bit, chroma format %d", dp.bit_depth,
              dp.chroma_format_idc, sp.bit_depth, cf);
-    const int W = sp.width - rs->win.left - rs->win.right, H = sp.height - rs->win.top - rs->win.bottom;
+    int W, H;
+    window_size(&sp, rs->win, &W, &H);
     for (int c = 0; c < (cf ? 2 : 1); c++) {
         const int64_t ext[4] = { W >> (c ? hs : 0), rs->width >> (c ? hs : 0), H >> (c ? vs : 0), rs->height >> (c ? vs : 0) };
         for (int a = 0; a < 4; a += 2)
@@ -777,9 +818,10 @@ static int resize_plan(OhEngine *e, const Pic *s0, const Pic *d0, const OhResize
     const OhPicParams &sp = s0->p;
     const OhWindow &w = rs->win;
     const int cf = sp.chroma_format_idc, hs = cf == 1 || cf == 2, vs = cf == 1, bpp = sample_bytes(sp.bit_depth);
-    const int W = sp.width - w.left - w.right, H = sp.height - w.top - w.bottom;
+    int W, H;
+    window_size(&sp, w, &W, &H);
     memset(a, 0, sizeof(*a));
-    a->np = cf ? 3 : 1; a->bd = sp.bit_depth;
+    a->np = n_planes(sp); a->bd = sp.bit_depth;
     pl->ncls = cf ? 2 : 1;
     uint64_t mid_pic = 0;
     for (int c = 0; c < pl->ncls; c++) {
@@ -882,11 +924,8 @@ static int resize_launch(OhEngine *e, const int *src_ids, const int *dst_ids, in
     for (int i0 = 0; i0 < n; i0 += per_set) {
         const int m = std::min(n - i0, per_set);
         for (int i = 0; i < m; i++) {
-            const Pic *s = get_pic(e, src_ids[i0 + i]);
-            Pic *q = get_pic(e, dst_ids[i0 + i]);
-            for (int c = 0; c < a->np; c++) { a->src[i][c] = final_planes(s)[c]; a->dst[i][c] = q->a[c]; }
-            q->final_b = false;                                  /* the image is a finished picture in half 0 */
-            q->done_seq = 0;
+            read_planes(get_pic(e, src_ids[i0 + i]), a->np, a->src[i]);
+            write_planes(get_pic(e, dst_ids[i0 + i]), a->np, a->dst[i]);
         }
         ohk_resize(a, m, pad, e->stream);
         HIPCHK(e, hipGetLastError());
@@ -941,40 +980,24 @@ extern "C" int oh_pics_reformat(OhEngine *e, const int *src_ids, const int *dst_
     if (!s0) return OH_E_ARG;
     const Pic *d0 = alike_pics(e, who, dst_ids, n);
     if (!d0) return OH_E_ARG;
-    {
-        std::vector<int> d;
-        { const int rc = distinct_dsts(e, who, dst_ids, n, &d); if (rc) return rc; }
-        for (int i = 0; i < n; i++)
-            if (std::binary_search(d.begin(), d.end(), src_ids[i]))
-                FAIL(e, OH_E_ARG, "%s: picture %d is both source and destination", who, src_ids[i]);
-    }
+    { const int rc = dsts_apart(e, who, dst_ids, n, src_ids, n); if (rc) return rc; }
     const OhPicParams &sp = s0->p, &dp = d0->p;
     if (sp.width != dp.width || sp.height != dp.height)
         FAIL(e, OH_E_ARG, "%s: sources of %dx%d, destinations of %dx%d", who, sp.width, sp.height, dp.width, dp.height);
     HIPCHK(e, hipSetDevice(e->device));
     OhRfArgs a;
     memset(&a, 0, sizeof(a));
-    const int snp = sp.chroma_format_idc ? 3 : 1, dnp = dp.chroma_format_idc ? 3 : 1;
-    for (int c = 0; c < snp; c++) a.spitch[c] = s0->stride[c] * sample_bytes(sp.bit_depth);
-    for (int c = 0; c < dnp; c++) a.dpitch[c] = d0->stride[c] * sample_bytes(dp.bit_depth);
-    for (int q = 0; q < 2; q++) {
-        a.sw[q] = q < snp ? s0->w[q] : 0; a.sh[q] = q < snp ? s0->h[q] : 0;
-        a.dw[q] = q < dnp ? d0->w[q] : 0; a.dh[q] = q < dnp ? d0->h[q] : 0;
-    }
+    const int snp = n_planes(sp), dnp = n_planes(dp);            /* sources and destinations: each side its own plane count */
+    row_pitches(s0, snp, a.spitch); class_sizes(s0, snp, a.sw, a.sh);
+    row_pitches(d0, dnp, a.dpitch); class_sizes(d0, dnp, a.dw, a.dh);
     a.scf = sp.chroma_format_idc; a.dcf = dp.chroma_format_idc;
     a.sbd = sp.bit_depth; a.dbd = dp.bit_depth;
     a.depth = rf->depth; a.down = rf->chroma_down; a.up = rf->chroma_up;
     for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
         const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
         for (int i = 0; i < m; i++) {
-            const Pic *s = get_pic(e, src_ids[i0 + i]);
-            Pic *q = get_pic(e, dst_ids[i0 + i]);
-            for (int c = 0; c < 3; c++) {
-                a.src[i][c] = c < snp ? final_planes(s)[c] : nullptr;
-                a.dst[i][c] = c < dnp ? q->a[c] : nullptr;
-            }
-            q->final_b = false;                                  /* the image is a finished picture in half 0 */
-            q->done_seq = 0;
+            read_planes(get_pic(e, src_ids[i0 + i]), snp, a.src[i]);
+            write_planes(get_pic(e, dst_ids[i0 + i]), dnp, a.dst[i]);
         }
         ohk_reformat(&a, m, e->stream);
         HIPCHK(e, hipGetLastError());
@@ -996,51 +1019,40 @@ extern "C" int oh_pics_orient(OhEngine *e, const int *src_ids, const int *dst_id
     if (!s0) return OH_E_ARG;
     const Pic *d0 = alike_pics(e, who, dst_ids, n);
     if (!d0) return OH_E_ARG;
-    {
-        std::vector<int> d;
-        { const int rc = distinct_dsts(e, who, dst_ids, n, &d); if (rc) return rc; }
-        for (int i = 0; i < n; i++)
-            if (std::binary_search(d.begin(), d.end(), src_ids[i]))
-                FAIL(e, OH_E_ARG, "%s: picture %d is both source and destination", who, src_ids[i]);
-    }
+    { const int rc = dsts_apart(e, who, dst_ids, n, src_ids, n); if (rc) return rc; }
     const OhPicParams &sp = s0->p, &dp = d0->p;
     const OhWindow &w = o->win;
     std::string why;
     if (!crop_window_ok(&sp, w, true, &why))
         FAIL(e, OH_E_ARG, "%s: %s", who, why.c_str());
-    const int cf = sp.chroma_format_idc, hs = cf == 1 || cf == 2, vs = cf == 1, bpp = sample_bytes(sp.bit_depth);
+    const int cf = sp.chroma_format_idc, hs = cf == 1 || cf == 2, vs = cf == 1;
     if (dp.bit_depth != sp.bit_depth || dp.chroma_format_idc != cf)
         FAIL(e, OH_E_UNSUPPORTED, "%s: destinations of %d bit, chroma format %d; sources of %d bit, chroma format %d (oh_pics_reformat first)", who,
              dp.bit_depth, dp.chroma_format_idc, sp.bit_depth, cf);
     const bool tr = o->orientation & OH_ORIENT_TRANSPOSE;
     if (tr && cf == 2)
         FAIL(e, OH_E_UNSUPPORTED, "%s: orientation %d transposes 4:2:2 pictures into 4:4:0 (reformat to 4:2:0 or 4:4:4 first)", who, o->orientation);
-    const int W = sp.width - w.left - w.right, H = sp.height - w.top - w.bottom;
-    int iw = 0, ih = 0;
+    int W, H, iw = 0, ih = 0;
+    window_size(&sp, w, &W, &H);
     (void)oh_orient_size(o->orientation, W, H, &iw, &ih);
     if (iw > dp.width || ih > dp.height)
         FAIL(e, OH_E_ARG, "%s: the image of %dx%d does not fit the destinations' %dx%d", who, iw, ih, dp.width, dp.height);
     HIPCHK(e, hipSetDevice(e->device));
     OhOrArgs a;
     memset(&a, 0, sizeof(a));
-    a.np = cf ? 3 : 1; a.bd = sp.bit_depth; a.orientation = o->orientation;
-    for (int c = 0; c < a.np; c++) { a.spitch[c] = s0->stride[c] * bpp; a.dpitch[c] = d0->stride[c] * bpp; }
+    a.np = n_planes(sp); a.bd = sp.bit_depth; a.orientation = o->orientation;
+    row_pitches(s0, a.np, a.spitch);
+    row_pitches(d0, a.np, a.dpitch);
+    class_sizes(d0, a.np, a.dw, a.dh);
     for (int q = 0; q < (cf ? 2 : 1); q++) {
         a.x0[q] = w.left >> (q ? hs : 0); a.y0[q] = w.top >> (q ? vs : 0);
         a.ws[q] = W >> (q ? hs : 0); a.hs[q] = H >> (q ? vs : 0);
-        a.dw[q] = d0->w[q]; a.dh[q] = d0->h[q];
     }
     for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
         const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
         for (int i = 0; i < m; i++) {
-            const Pic *s = get_pic(e, src_ids[i0 + i]);
-            Pic *q = get_pic(e, dst_ids[i0 + i]);
-            for (int c = 0; c < 3; c++) {
-                a.src[i][c] = c < a.np ? final_planes(s)[c] : nullptr;
-                a.dst[i][c] = c < a.np ? q->a[c] : nullptr;
-            }
-            q->final_b = false;                                  /* the image is a finished picture in half 0 */
-            q->done_seq = 0;
+            read_planes(get_pic(e, src_ids[i0 + i]), a.np, a.src[i]);
+            write_planes(get_pic(e, dst_ids[i0 + i]), a.np, a.dst[i]);
         }
         ohk_orient(&a, m, e->stream);
         HIPCHK(e, hipGetLastError());
@@ -1049,17 +1061,6 @@ extern "C" int oh_pics_orient(OhEngine *e, const int *src_ids, const int *dst_id
 }
 
 /* ---------------- fields and deinterlacing (deinterlace.hip) ---------------- */
-/* no destination is listed twice and none is among the sources */
-static int dsts_apart(OhEngine *e, const char *who, const std::vector<int> &dsts, const std::vector<int> &srcs)
-{
-    std::vector<int> d;
-    { const int rc = distinct_dsts(e, who, dsts.data(), (int)dsts.size(), &d); if (rc) return rc; }
-    for (int s : srcs)
-        if (std::binary_search(d.begin(), d.end(), s))
-            FAIL(e, OH_E_ARG, "%s: picture %d is both source and destination", who, s);
-    return OH_OK;
-}
-
 /* what weave and separate ask of their fields (f0) and frames (F0) */
 static int fields_check(OhEngine *e, const char *who, const Pic *f0, const Pic *F0)
 {
@@ -1079,10 +1080,10 @@ static int fields_launch(OhEngine *e, const Pic *f0, const Pic *F0, const int *c
     OhDiArgs a;
     memset(&a, 0, sizeof(a));
     const OhPicParams &Fp = F0->p;
-    const int bpp = sample_bytes(Fp.bit_depth);
-    a.np = Fp.chroma_format_idc ? 3 : 1; a.bd = Fp.bit_depth; a.op = op; a.sides = sides;
-    for (int c = 0; c < a.np; c++) { a.pitch[c] = F0->stride[c] * bpp; a.fpitch[c] = f0->stride[c] * bpp; }
-    for (int q = 0; q < (a.np > 1 ? 2 : 1); q++) { a.w[q] = F0->w[q]; a.h[q] = F0->h[q]; }
+    a.np = n_planes(Fp); a.bd = Fp.bit_depth; a.op = op; a.sides = sides;
+    row_pitches(F0, a.np, a.pitch);
+    row_pitches(f0, a.np, a.fpitch);
+    class_sizes(F0, a.np, a.w, a.h);
     for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
         const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
         for (int k = 0; k < 4; k++) {
@@ -1090,13 +1091,8 @@ static int fields_launch(OhEngine *e, const Pic *f0, const Pic *F0, const int *c
                 continue;
             for (int i = 0; i < m; i++) {
                 Pic *q = get_pic(e, role[k][i0 + i]);
-                const bool w = wr >> k & 1;
-                for (int c = 0; c < 3; c++)
-                    a.pic[k][i][c] = c < a.np ? (w ? q->a[c] : final_planes(q)[c]) : nullptr;
-                if (w) {
-                    q->final_b = false;                          /* the image is a finished picture in half 0 */
-                    q->done_seq = 0;
-                }
+                if (wr >> k & 1) write_planes(q, a.np, a.pic[k][i]);
+                else             read_planes(q, a.np, a.pic[k][i]);
             }
         }
         ohk_fields(&a, m, e->stream);
@@ -1118,7 +1114,7 @@ extern "C" int oh_pics_weave(OhEngine *e, const int *top_ids, const int *bottom_
     if (!f0) return OH_E_ARG;
     const Pic *F0 = alike_pics(e, who, dst_ids, n);
     if (!F0) return OH_E_ARG;
-    { const int rc = dsts_apart(e, who, std::vector<int>(dst_ids, dst_ids + n), fields); if (rc) return rc; }
+    { const int rc = dsts_apart(e, who, dst_ids, n, fields.data(), 2 * n); if (rc) return rc; }
     { const int rc = fields_check(e, who, f0, F0); if (rc) return rc; }
     const int *const role[4] = { top_ids, bottom_ids, nullptr, dst_ids };
     return fields_launch(e, f0, F0, role, 1u << 3, OH_DI_WEAVE, 3, n);
@@ -1138,7 +1134,7 @@ extern "C" int oh_pics_separate(OhEngine *e, const int *src_ids, const int *top_
     if (!F0) return OH_E_ARG;
     const Pic *f0 = alike_pics(e, who, fields.data(), (int)fields.size());
     if (!f0) return OH_E_ARG;
-    { const int rc = dsts_apart(e, who, fields, std::vector<int>(src_ids, src_ids + n)); if (rc) return rc; }
+    { const int rc = dsts_apart(e, who, fields.data(), (int)fields.size(), src_ids, n); if (rc) return rc; }
     { const int rc = fields_check(e, who, f0, F0); if (rc) return rc; }
     const int *const role[4] = { src_ids, nullptr, top_ids, bottom_ids };
     return fields_launch(e, f0, F0, role, 3u << 2, OH_DI_SEPARATE, (top_ids ? 1 : 0) | (bottom_ids ? 2 : 0), n);
@@ -1156,53 +1152,28 @@ extern "C" int oh_pics_deinterlace(OhEngine *e, const int *prev_ids, const int *
         FAIL(e, OH_E_ARG, "%s: parity %d, kept_first %d (0 or 1)", who, d->parity, d->kept_first);
     if (!n)
         return OH_OK;
-    /* the pictures of index i: prev, cur, next; a null array or an entry of -1 stands for cur; read by ADAPTIVE only */
-    const bool adaptive = d->mode == OH_DEINT_ADAPTIVE;
-    std::vector<int> around[2];
-    std::vector<int> srcs(cur_ids, cur_ids + n);
-    for (int k = 0; k < 2; k++) {
-        const int *ids = k ? next_ids : prev_ids;
-        around[k] = std::vector<int>(cur_ids, cur_ids + n);
-        if (!adaptive || !ids)
-            continue;
-        for (int i = 0; i < n; i++) {
-            if (ids[i] < -1)
-                FAIL(e, OH_E_ARG, "%s: %s picture %d (-1 stands for the cur picture)", who, k ? "next" : "prev", ids[i]);
-            if (ids[i] >= 0)
-                around[k][i] = ids[i];
-        }
-        srcs.insert(srcs.end(), around[k].begin(), around[k].end());
-    }
-    std::vector<int> all(srcs);
-    all.insert(all.end(), dst_ids, dst_ids + n);
-    const Pic *p0 = alike_pics(e, who, all.data(), (int)all.size());
+    Neighbours nb;                                              /* prev and next: read by ADAPTIVE only */
+    { const int rc = neighbours(e, who, "cur", prev_ids, cur_ids, next_ids, n, d->mode == OH_DEINT_ADAPTIVE, &nb); if (rc) return rc; }
+    const Pic *p0 = alike_apart(e, who, nb.srcs, dst_ids, n);
     if (!p0) return OH_E_ARG;
-    { const int rc = dsts_apart(e, who, std::vector<int>(dst_ids, dst_ids + n), srcs); if (rc) return rc; }
     const OhPicParams &p = p0->p;
     HIPCHK(e, hipSetDevice(e->device));
     OhDiArgs a;
     memset(&a, 0, sizeof(a));
-    const int bpp = sample_bytes(p.bit_depth);
-    a.np = p.chroma_format_idc ? 3 : 1; a.bd = p.bit_depth;
+    a.np = n_planes(p); a.bd = p.bit_depth;
     a.mode = d->mode; a.parity = d->parity; a.kept_first = d->kept_first;
-    for (int c = 0; c < a.np; c++) a.pitch[c] = p0->stride[c] * bpp;
-    for (int q = 0; q < (a.np > 1 ? 2 : 1); q++) {
-        a.w[q] = p0->w[q]; a.h[q] = p0->h[q];
+    row_pitches(p0, a.np, a.pitch);
+    class_sizes(p0, a.np, a.w, a.h);
+    for (int q = 0; q < (a.np > 1 ? 2 : 1); q++)
         if (a.h[q] < 2 || (a.h[q] & 1))
             FAIL(e, OH_E_ARG, "%s: planes of %d rows (an even number, 2 at least)", who, a.h[q]);
-    }
     for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
         const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
         for (int i = 0; i < m; i++) {
-            const Pic *s[3] = { get_pic(e, around[0][i0 + i]), get_pic(e, cur_ids[i0 + i]), get_pic(e, around[1][i0 + i]) };
-            Pic *q = get_pic(e, dst_ids[i0 + i]);
-            for (int c = 0; c < 3; c++) {
-                for (int k = 0; k < 3; k++)
-                    a.pic[k][i][c] = c < a.np ? final_planes(s[k])[c] : nullptr;
-                a.pic[3][i][c] = c < a.np ? q->a[c] : nullptr;
-            }
-            q->final_b = false;                                  /* the image is a finished picture in half 0 */
-            q->done_seq = 0;
+            read_planes(get_pic(e, nb.around[0][i0 + i]), a.np, a.pic[0][i]);
+            read_planes(get_pic(e, cur_ids[i0 + i]), a.np, a.pic[1][i]);
+            read_planes(get_pic(e, nb.around[1][i0 + i]), a.np, a.pic[2][i]);
+            write_planes(get_pic(e, dst_ids[i0 + i]), a.np, a.pic[3][i]);
         }
         ohk_deinterlace(&a, m, e->stream);
         HIPCHK(e, hipGetLastError());
@@ -1225,28 +1196,10 @@ extern "C" int oh_pics_filter(OhEngine *e, const int *prev_ids, const int *src_i
         if (rc) FAIL(e, rc, "%s: %s", who, why.c_str());
         return OH_OK;
     }
-    /* the pictures of index i: prev, src, next; a null array or an entry of -1 stands for src; read by TEMPORAL only */
-    const bool temporal = f->mode == OH_FILTER_TEMPORAL;
-    std::vector<int> around[2];
-    std::vector<int> srcs(src_ids, src_ids + n);
-    for (int k = 0; k < 2; k++) {
-        const int *ids = k ? next_ids : prev_ids;
-        around[k] = std::vector<int>(src_ids, src_ids + n);
-        if (!temporal || !ids)
-            continue;
-        for (int i = 0; i < n; i++) {
-            if (ids[i] < -1)
-                FAIL(e, OH_E_ARG, "%s: %s picture %d (-1 stands for the src picture)", who, k ? "next" : "prev", ids[i]);
-            if (ids[i] >= 0)
-                around[k][i] = ids[i];
-        }
-        srcs.insert(srcs.end(), around[k].begin(), around[k].end());
-    }
-    std::vector<int> all(srcs);
-    all.insert(all.end(), dst_ids, dst_ids + n);
-    const Pic *p0 = alike_pics(e, who, all.data(), (int)all.size());
+    Neighbours nb;                                              /* prev and next: read by TEMPORAL only */
+    { const int rc = neighbours(e, who, "src", prev_ids, src_ids, next_ids, n, f->mode == OH_FILTER_TEMPORAL, &nb); if (rc) return rc; }
+    const Pic *p0 = alike_apart(e, who, nb.srcs, dst_ids, n);
     if (!p0) return OH_E_ARG;
-    { const int rc = dsts_apart(e, who, std::vector<int>(dst_ids, dst_ids + n), srcs); if (rc) return rc; }
     const OhPicParams &p = p0->p;
     {
         std::string why;
@@ -1256,12 +1209,11 @@ extern "C" int oh_pics_filter(OhEngine *e, const int *prev_ids, const int *src_i
     HIPCHK(e, hipSetDevice(e->device));
     OhFilterArgs a;
     memset(&a, 0, sizeof(a));
-    const int bpp = sample_bytes(p.bit_depth);
-    a.np = p.chroma_format_idc ? 3 : 1; a.bd = p.bit_depth;
+    a.np = n_planes(p); a.bd = p.bit_depth;
     a.mode = f->mode; a.planes = f->planes;
-    for (int c = 0; c < a.np; c++) a.pitch[c] = p0->stride[c] * bpp;
+    row_pitches(p0, a.np, a.pitch);
+    class_sizes(p0, a.np, a.w, a.h);
     for (int q = 0; q < 2; q++) {
-        if (q < (a.np > 1 ? 2 : 1)) { a.w[q] = p0->w[q]; a.h[q] = p0->h[q]; }
         a.amount[q] = f->amount[q]; a.threshold[q] = f->threshold[q];
         if (f->mode > OH_FILTER_UNSHARP)
             continue;
@@ -1273,15 +1225,10 @@ extern "C" int oh_pics_filter(OhEngine *e, const int *prev_ids, const int *src_i
     for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
         const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
         for (int i = 0; i < m; i++) {
-            const Pic *s[3] = { get_pic(e, around[0][i0 + i]), get_pic(e, src_ids[i0 + i]), get_pic(e, around[1][i0 + i]) };
-            Pic *d = get_pic(e, dst_ids[i0 + i]);
-            for (int c = 0; c < 3; c++) {
-                for (int k = 0; k < 3; k++)
-                    a.src[k][i][c] = c < a.np ? final_planes(s[k])[c] : nullptr;
-                a.dst[i][c] = c < a.np ? d->a[c] : nullptr;
-            }
-            d->final_b = false;                                  /* the image is a finished picture in half 0 */
-            d->done_seq = 0;
+            read_planes(get_pic(e, nb.around[0][i0 + i]), a.np, a.src[0][i]);
+            read_planes(get_pic(e, src_ids[i0 + i]), a.np, a.src[1][i]);
+            read_planes(get_pic(e, nb.around[1][i0 + i]), a.np, a.src[2][i]);
+            write_planes(get_pic(e, dst_ids[i0 + i]), a.np, a.dst[i]);
         }
         ohk_filter(&a, m, e->stream);
         HIPCHK(e, hipGetLastError());
@@ -1363,11 +1310,12 @@ extern "C" int oh_pics_compose(OhEngine *e, const int *dst_ids, int n, const OhC
     { const int rc = compose_check(e, dst_ids, n, cp); if (rc) return rc; }
     const Pic *d0 = get_pic(e, dst_ids[0]);
     const OhPicParams &dp = d0->p;
-    const int bpp = sample_bytes(dp.bit_depth), np = dp.chroma_format_idc ? 3 : 1, gs = 16 / bpp;
+    const int bpp = sample_bytes(dp.bit_depth), np = n_planes(dp), gs = 16 / bpp;
     const bool fill = (cp->flags & OH_COMPOSE_FILL) != 0;
     OhCpsArgs a;
     memset(&a, 0, sizeof(a));
-    for (int c = 0; c < np; c++) { a.pitch[c] = d0->stride[c] * bpp; a.fill_v[c] = fill ? cp->fill[c] : 0; }
+    row_pitches(d0, np, a.pitch);
+    for (int c = 0; c < np; c++) a.fill_v[c] = fill ? cp->fill[c] : 0;
     a.np = np; a.bd = dp.bit_depth; a.cf = dp.chroma_format_idc; a.fill = fill;
 
     /* the layers that are not wholly outside, with their geometry in both plane classes, and the area they touch */
@@ -1406,8 +1354,10 @@ extern "C" int oh_pics_compose(OhEngine *e, const int *dst_ids, int n, const OhC
         lay.push_back(L);
         which.push_back(k);
     }
+    /* compose writes in place into the finished half, whichever it is, so it does not go through write_planes: final_b stays, and only
+     * done_seq is cleared — not written by a reconstruction batch: a download stays behind the engine stream */
     for (int i = 0; i < n; i++)
-        get_pic(e, dst_ids[i])->done_seq = 0;                   /* not written by a reconstruction batch: a download stays behind the engine stream */
+        get_pic(e, dst_ids[i])->done_seq = 0;
     if (lay.empty() && !fill)
         return OH_OK;                                           /* nothing reaches the destinations */
     for (int q = 0; q < (np > 1 ? 2 : 1); q++) {
@@ -1441,7 +1391,7 @@ extern "C" int oh_pics_compose(OhEngine *e, const int *dst_ids, int n, const OhC
                 for (int i = 0; i < m; i++) {
                     const Pic *s = get_pic(e, l.src_ids[i0 + i]);
                     OhCpsSrc &t = hs[(size_t)nl * i0 + (size_t)j * m + i];
-                    for (int c = 0; c < 3; c++) t.p[c] = c < np ? final_planes(s)[c] : nullptr;
+                    read_planes(s, np, t.p);
                     t.alpha = l.alpha ? (const uint8_t *)l.alpha + (size_t)(i0 + i) * (size_t)l.alpha_image_stride : nullptr;
                 }
             }
@@ -1453,10 +1403,7 @@ extern "C" int oh_pics_compose(OhEngine *e, const int *dst_ids, int n, const OhC
     a.layers = (const OhCpsLayer *)e->compose_dev.p;
     for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
         const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
-        for (int i = 0; i < m; i++) {
-            const Pic *q = get_pic(e, dst_ids[i0 + i]);
-            for (int c = 0; c < np; c++) a.dst[i][c] = final_planes(q)[c];
-        }
+        for (int i = 0; i < m; i++) read_planes(get_pic(e, dst_ids[i0 + i]), np, a.dst[i]);      /* in place: the finished half */
         a.srcs = nl ? (const OhCpsSrc *)((const char *)e->compose_dev.p + lay_bytes) + (size_t)nl * i0 : nullptr;
         a.n_pics = m;
         ohk_compose(&a, m, e->stream);

@@ -4,13 +4,18 @@
 #define OHEVC_PICS_MATH_H
 
 #include <string>
+#include <vector>
 #include "../../include/ohevc_hip.h"
 
 #ifndef OH_INTERNAL
 #define OH_INTERNAL __attribute__((visibility("hidden")))    /* shared between the library's files, not part of its ABI */
 #endif
 
+OH_INTERNAL void window_size(const OhPicParams *p, const OhWindow &w, int *W, int *H);
 OH_INTERNAL bool crop_window_ok(const OhPicParams *p, const OhWindow &w, bool aligned, std::string *why);
+OH_INTERNAL int ids_apart(const int *dst_ids, int nd, const int *src_ids, int ns, int *both);
+OH_INTERNAL int neighbours_resolve(const int *const around_ids[2], const int *own_ids, int n, bool used, std::vector<int> around[2],
+                                   std::vector<int> *srcs, int *side);
 OH_INTERNAL int conv_sample_bytes(const OhConvert *cv, int bit_depth);
 OH_INTERNAL int conv_check(const OhPicParams *p, const OhConvert *cv, size_t *bytes, std::string *why);
 OH_INTERNAL int colour_check(const OhColour *col, std::string *why);

@@ -1,6 +1,6 @@
 /*
  * pics_math.hip — the host arithmetic of the picture services (engine_pics.hip), with neither an engine nor a device: image sizes and
- * crop windows, the integers of the RGB conversions, the colour tables of the HDR forms, light-level bins and percentiles, the SSIM window
+ * crop windows, the ids of a call (destinations apart from sources, neighbours in time), the integers of the RGB conversions, the colour tables of the HDR forms, light-level bins and percentiles, the SSIM window
  * and PSNR, the resize taps, the compose formulas, the reformat quantisation, the orientations' group, the pic_struct table, the adaptive deinterlacer's sample and the filters' taps and samples.  No kernel, no HIP runtime call: tests/pics_math_check.cpp runs it under sanitizers.
  */
 #include <stdio.h>
@@ -19,12 +19,20 @@
 
 static bool depth_ok(int bit_depth) { return bit_depth == 8 || bit_depth == 9 || bit_depth == 10 || bit_depth == 12; }
 
+/* what a window leaves of a picture, luma samples */
+void window_size(const OhPicParams *p, const OhWindow &w, int *W, int *H)
+{
+    *W = p->width - w.left - w.right;
+    *H = p->height - w.top - w.bottom;
+}
+
 /* a crop window of a picture: offsets not negative, something left and — aligned — the offsets multiples of the chroma sub-sampling.
  * false: *why says what is wrong. */
 bool crop_window_ok(const OhPicParams *p, const OhWindow &w, bool aligned, std::string *why)
 {
     const int cf = p->chroma_format_idc, sw = aligned && (cf == 1 || cf == 2) ? 2 : 1, sh = aligned && cf == 1 ? 2 : 1;
-    const int W = p->width - w.left - w.right, H = p->height - w.top - w.bottom;
+    int W, H;
+    window_size(p, w, &W, &H);
     if (w.left >= 0 && w.right >= 0 && w.top >= 0 && w.bottom >= 0 && W > 0 && H > 0 && !(w.left % sw) && !(w.right % sw) && !(w.top % sh) && !(w.bottom % sh))
         return true;
     char buf[256];
@@ -35,6 +43,48 @@ bool crop_window_ok(const OhPicParams *p, const OhWindow &w, bool aligned, std::
         snprintf(buf, sizeof(buf), "window (%d,%d,%d,%d) leaves nothing of %dx%d", w.left, w.right, w.top, w.bottom, p->width, p->height);
     *why = buf;
     return false;
+}
+
+/* the ids of a call that writes pictures.  0: no destination is listed twice and none is among the sources; 1: one is listed twice;
+ * 2: *both, the first such source, is also a destination */
+int ids_apart(const int *dst_ids, int nd, const int *src_ids, int ns, int *both)
+{
+    std::vector<int> d(dst_ids, dst_ids + nd);
+    std::sort(d.begin(), d.end());
+    if (std::adjacent_find(d.begin(), d.end()) != d.end())
+        return 1;
+    for (int i = 0; i < ns; i++)
+        if (std::binary_search(d.begin(), d.end(), src_ids[i])) {
+            *both = src_ids[i];
+            return 2;
+        }
+    return 0;
+}
+
+/* the pictures before (around[0]) and after (around[1]) each of the n pictures own_ids in time: around_ids[k][i], where a null array
+ * or an entry of -1 stands for the picture itself; *srcs: own_ids, then the lists that were given.  Not used (the mode does not read
+ * them): the arrays are not read and every picture stands for itself.  -1: done; else the index of the first entry below -1, in
+ * list *side */
+int neighbours_resolve(const int *const around_ids[2], const int *own_ids, int n, bool used, std::vector<int> around[2],
+                       std::vector<int> *srcs, int *side)
+{
+    srcs->assign(own_ids, own_ids + n);
+    for (int k = 0; k < 2; k++) {
+        const int *ids = around_ids[k];
+        around[k].assign(own_ids, own_ids + n);
+        if (!used || !ids)
+            continue;
+        for (int i = 0; i < n; i++) {
+            if (ids[i] < -1) {
+                *side = k;
+                return i;
+            }
+            if (ids[i] >= 0)
+                around[k][i] = ids[i];
+        }
+        srcs->insert(srcs->end(), around[k].begin(), around[k].end());
+    }
+    return -1;
 }
 
 /* ---------------- conversion to standard images (convert.hip) ---------------- */
@@ -75,7 +125,8 @@ int conv_check(const OhPicParams *p, const OhConvert *cv, size_t *bytes, std::st
     if (!crop_window_ok(p, cv->win, true, why))
         return OH_E_ARG;
     const int sw = (cf == 1 || cf == 2) ? 2 : 1, sh = cf == 1 ? 2 : 1;
-    const int W = p->width - cv->win.left - cv->win.right, H = p->height - cv->win.top - cv->win.bottom;
+    int W, H;
+    window_size(p, cv->win, &W, &H);
     size_t samples;
     if (cv->format <= OH_CONV_SEMIPLANAR)
         samples = (size_t)W * H + (cf ? 2 * (size_t)(W / sw) * (H / sh) : 0);

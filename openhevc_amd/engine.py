@@ -3,6 +3,7 @@
 There is no CPU fallback: creating an Engine without the built library or without a GPU raises.
 """
 import collections
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -819,6 +820,78 @@ class Engine:
             return [(0, [bytes(out[i].md5[c]) for c in range(3)]) for i in range(n)]
         return [(hash_type, list(out[i].crc if hash_type == 1 else out[i].checksum)) for i in range(n)]
 
+    # ---- what the wrappers of the picture services share ----
+    @staticmethod
+    def _sized(params, width, height):
+        """a copy of params with the size rounded up to the minimum coding block"""
+        dp = F.OhPicParams.from_buffer_copy(params)
+        mcb = 1 << dp.log2_min_cb_size
+        dp.width, dp.height = -(-width // mcb) * mcb, -(-height // mcb) * mcb
+        return dp
+
+    def _alloc_like(self, params, n):
+        """n fresh pictures of params; the ones already made are freed when an allocation fails"""
+        out = []
+        try:
+            for _ in range(n):
+                out.append(self.pic_alloc(params))
+        except Exception:
+            for made in out:
+                self.pic_free(made)
+            raise
+        return out
+
+    def _dsts(self, out, n, what, params):
+        """the destinations of a call, (ids, the ones made for it): out listed, one for each of the n `what`, or without out n fresh
+        pictures of params(), which raises where no picture can be made"""
+        if out is None:
+            out = self._alloc_like(params(), n)
+            return out, out
+        out = list(out)
+        if len(out) != n:
+            raise ValueError(f"out: {len(out)} pictures for {n} {what}")
+        return out, []
+
+    def _call(self, rc, what, made):
+        """the return code of a service: a refusal frees the pictures made for the call and raises through _chk"""
+        if rc != 0:
+            for pid in made:
+                self.pic_free(pid)
+        self._chk(rc, what)
+
+    @staticmethod
+    def _around(n, prev, next):
+        """the prev / next arrays of a call: None stays None (the library takes a null array), a None entry becomes -1"""
+        around = []
+        for name, ids in (("prev", prev), ("next", next)):
+            if ids is not None:
+                ids = [-1 if v is None else int(v) for v in ids]
+                if len(ids) != n:
+                    raise ValueError(f"{name}: {len(ids)} entries for {n} sources")
+                ids = (C.c_int * n)(*ids)
+            around.append(ids)
+        return around
+
+    @contextlib.contextmanager
+    def _torch_ordered(self, torch):
+        """a library call that reads or writes torch's memory, ordered with torch both ways (torch None: nothing to order)"""
+        dev = torch.device("cuda", self.device) if torch is not None else None
+        cur = torch.cuda.current_stream(dev) if torch is not None else None
+        if cur is None or (self.stream() or 0) == cur.cuda_stream:   # an engine created on torch's current stream: nothing to order
+            yield
+            return
+        if self._torch_stream is None:
+            self._torch_stream = torch.cuda.ExternalStream(self.stream() or 0, device=dev)
+        es = self._torch_stream
+        # the kernels that produce what the call reads are queued on torch's stream, and the allocator may hand out memory for what it
+        # writes that a queued kernel still uses
+        es.wait_stream(cur)
+        yield
+        # torch's stream waits for the call, so whatever torch does with the memory later (a free and a reuse included) is ordered
+        # behind it.  No record_stream on the engine stream: the image usually outlives the engine, and the allocator would record
+        # an event on the destroyed stream when the tensor is freed.
+        cur.wait_stream(es)
+
     def pics_convert(self, pids, fmt, *, dtype=None, window=(0, 0, 0, 0), matrix=1, full_range=False, chroma="linear", out=None,
                      colour=None):
         """finished pictures -> one torch tensor on the engine's device (oh_pics_convert): fmt "planar" / "semiplanar" (N, rows, W),
@@ -868,24 +941,13 @@ class Engine:
             out = torch.empty(shape, dtype=tdt, device=dev)
         elif tuple(out.shape) != shape or out.dtype != tdt or out.device != dev or not out.is_contiguous():
             raise ValueError(f"out: want a contiguous {tdt} tensor of shape {shape} on {dev}, got {out.dtype} {tuple(out.shape)} on {out.device}")
-        cur = torch.cuda.current_stream(dev)
-        same = (self.stream() or 0) == cur.cuda_stream        # an engine created on torch's current stream: nothing to order
-        if not same:
-            if self._torch_stream is None:
-                self._torch_stream = torch.cuda.ExternalStream(self.stream() or 0, device=dev)
-            es = self._torch_stream
-            es.wait_stream(cur)                               # the allocator may hand out memory a queued kernel still uses
-        if colour is None:
-            self._chk(self.L.oh_pics_convert(self.h, (C.c_int * n)(*pids), n, C.byref(cv), C.c_void_p(out.data_ptr()), ib,
-                                             out.numel() * esz), "oh_pics_convert")
-        else:
-            self._chk(self.L.oh_pics_convert_colour(self.h, (C.c_int * n)(*pids), n, C.byref(cv), C.byref(colour),
-                                                    C.c_void_p(out.data_ptr()), ib, out.numel() * esz), "oh_pics_convert_colour")
-        if not same:
-            # torch's stream waits for the write, so whatever torch does with the memory later (a free and a reuse included) is ordered
-            # behind it.  No record_stream on the engine stream: the image usually outlives the engine, and the allocator would record
-            # an event on the destroyed stream when the tensor is freed.
-            cur.wait_stream(es)
+        with self._torch_ordered(torch):
+            if colour is None:
+                self._chk(self.L.oh_pics_convert(self.h, (C.c_int * n)(*pids), n, C.byref(cv), C.c_void_p(out.data_ptr()), ib,
+                                                 out.numel() * esz), "oh_pics_convert")
+            else:
+                self._chk(self.L.oh_pics_convert_colour(self.h, (C.c_int * n)(*pids), n, C.byref(cv), C.byref(colour),
+                                                        C.c_void_p(out.data_ptr()), ib, out.numel() * esz), "oh_pics_convert_colour")
         return out
 
     def pics_import(self, images, fmt, *, out=None, bit_depth=None, chroma_format_idc=None, window=(0, 0, 0, 0), matrix=1, full_range=False,
@@ -913,8 +975,9 @@ class Engine:
         if images.dim() != (3 if yuv else 4) or images.shape[0] < 1:
             raise ValueError(f"images: shape {tuple(images.shape)} is not what pics_convert gives for format {fmt!r}")
         n = int(images.shape[0])
-        fresh = out is None
-        if fresh:
+
+        def fitting():                                        # params of fresh pictures with the image at their top left, and its window
+            nonlocal window
             if bit_depth is None or chroma_format_idc is None:
                 raise ValueError("pics_import without out needs bit_depth and chroma_format_idc")
             cf = int(chroma_format_idc)
@@ -930,15 +993,12 @@ class Engine:
                 H, W = int(images.shape[1]), int(images.shape[2])
             if W < 1 or H < 1:
                 raise ValueError(f"images: shape {tuple(images.shape)} holds no picture of chroma format {cf}")
-            dp = F.pic_params(8, 8, bit_depth=int(bit_depth), chroma_format_idc=cf)
-            mcb = 1 << dp.log2_min_cb_size
-            dp.width, dp.height = -(-W // mcb) * mcb, -(-H // mcb) * mcb
+            dp = self._sized(F.pic_params(8, 8, bit_depth=int(bit_depth), chroma_format_idc=cf), W, H)
             window = (0, dp.width - W, 0, dp.height - H)
-            pids = [self.pic_alloc(dp) for _ in range(n)]
-        else:
-            pids = list(out)
-            if len(pids) != n:
-                raise ValueError(f"out: {len(pids)} pictures for {n} images")
+            return dp
+
+        pids, made = self._dsts(out, n, "images", fitting)
+        if not made:
             window = tuple(int(v) for v in window)
         try:
             params = self._pic_params(pids[0])
@@ -960,21 +1020,12 @@ class Engine:
             if images[0].numel() * esz != ib:
                 raise ValueError(f"images: {tuple(images.shape[1:])} {images.dtype} per image is {images[0].numel() * esz} bytes, the "
                                  f"window {window} of the pictures takes {ib}")
-            cur = torch.cuda.current_stream(dev)
-            same = (self.stream() or 0) == cur.cuda_stream    # an engine created on torch's current stream: nothing to order
-            if not same:
-                if self._torch_stream is None:
-                    self._torch_stream = torch.cuda.ExternalStream(self.stream() or 0, device=dev)
-                es = self._torch_stream
-                es.wait_stream(cur)                           # the kernels that produce the images are queued on torch's stream
-            self._chk(self.L.oh_pics_import(self.h, ids, n, C.byref(cv), C.c_void_p(images.data_ptr()), ib, images.numel() * esz),
-                      "oh_pics_import")
-            if not same:
-                cur.wait_stream(es)                           # whatever torch does with the tensor later is ordered behind the read
+            with self._torch_ordered(torch):
+                self._chk(self.L.oh_pics_import(self.h, ids, n, C.byref(cv), C.c_void_p(images.data_ptr()), ib, images.numel() * esz),
+                          "oh_pics_import")
         except Exception:
-            if fresh:
-                for pid in pids:
-                    self.pic_free(pid)
+            for pid in made:
+                self.pic_free(pid)
             raise
         return pids, window
 
@@ -1021,24 +1072,15 @@ class Engine:
             raise ValueError("pics_resize needs at least one picture (the destinations follow the pictures' params)")
         width, height = int(size[0]), int(size[1])
         rs = OhResize(resize_filter(filter), OhWindow(*window), width, height)
-        fresh = out is None
-        if fresh:
+
+        def fitting():
             sp = self._pic_params(pids[0])
             if width < 1 or height < 1:
                 raise ValueError(f"size {size}: at least 1 x 1")
-            dp = F.OhPicParams.from_buffer_copy(sp)
-            mcb = 1 << sp.log2_min_cb_size
-            dp.width, dp.height = -(-width // mcb) * mcb, -(-height // mcb) * mcb
-            out = [self.pic_alloc(dp) for _ in range(n)]
-        else:
-            out = list(out)
-            if len(out) != n:
-                raise ValueError(f"out: {len(out)} pictures for {n} sources")
-        rc = self.L.oh_pics_resize(self.h, (C.c_int * n)(*pids), (C.c_int * n)(*out), n, C.byref(rs))
-        if rc != 0 and fresh:
-            for pid in out:
-                self.pic_free(pid)
-        self._chk(rc, "oh_pics_resize")
+            return self._sized(sp, width, height)
+
+        out, made = self._dsts(out, n, "sources", fitting)
+        self._call(self.L.oh_pics_resize(self.h, (C.c_int * n)(*pids), (C.c_int * n)(*out), n, C.byref(rs)), "oh_pics_resize", made)
         dp = self._pic_params(out[0])
         return out, (0, dp.width - width, 0, dp.height - height)
 
@@ -1051,32 +1093,20 @@ class Engine:
         pids = list(pids)
         n = len(pids)
         rf = OhReformat(_rf_enum(RF_DEPTH, "depth mode", depth), _rf_enum(RF_FILTERS, "down filter", down), _rf_enum(RF_FILTERS, "up filter", up))
-        fresh = out is None
-        if fresh:
-            if n == 0:
-                return []
+        if out is None and n == 0:
+            return []
+
+        def reformatted():
             dp = F.OhPicParams.from_buffer_copy(self._pic_params(pids[0]))
             if bit_depth is not None:
                 dp.bit_depth = int(bit_depth)
             if chroma_format_idc is not None:
                 dp.chroma_format_idc = int(chroma_format_idc)
-            out = []
-            try:
-                for _ in range(n):
-                    out.append(self.pic_alloc(dp))
-            except Exception:
-                for pid in out:
-                    self.pic_free(pid)
-                raise
-        else:
-            out = list(out)
-            if len(out) != n:
-                raise ValueError(f"out: {len(out)} pictures for {n} sources")
-        rc = self.L.oh_pics_reformat(self.h, (C.c_int * max(n, 1))(*pids), (C.c_int * max(n, 1))(*out), n, C.byref(rf))
-        if rc != 0 and fresh:
-            for pid in out:
-                self.pic_free(pid)
-        self._chk(rc, "oh_pics_reformat")
+            return dp
+
+        out, made = self._dsts(out, n, "sources", reformatted)
+        self._call(self.L.oh_pics_reformat(self.h, (C.c_int * max(n, 1))(*pids), (C.c_int * max(n, 1))(*out), n, C.byref(rf)),
+                   "oh_pics_reformat", made)
         return out
 
     def pics_orient(self, pids, orientation, *, window=(0, 0, 0, 0), out=None):
@@ -1097,49 +1127,25 @@ class Engine:
         width, height = sp.width - od.win.left - od.win.right, sp.height - od.win.top - od.win.bottom
         if code & ORIENT_TRANSPOSE:
             width, height = height, width
-        fresh = out is None
-        if fresh:
+
+        def fitting():
             if width < 1 or height < 1:
                 raise ValueError(f"window {tuple(window)} leaves nothing of {sp.width}x{sp.height}")
-            dp = F.OhPicParams.from_buffer_copy(sp)
-            mcb = 1 << sp.log2_min_cb_size
-            dp.width, dp.height = -(-width // mcb) * mcb, -(-height // mcb) * mcb
-            out = []
-            try:
-                for _ in range(n):
-                    out.append(self.pic_alloc(dp))
-            except Exception:
-                for pid in out:
-                    self.pic_free(pid)
-                raise
-        else:
-            out = list(out)
-            if len(out) != n:
-                raise ValueError(f"out: {len(out)} pictures for {n} sources")
-        rc = self.L.oh_pics_orient(self.h, (C.c_int * n)(*pids), (C.c_int * n)(*out), n, C.byref(od))
-        if rc != 0 and fresh:
-            for pid in out:
-                self.pic_free(pid)
-        self._chk(rc, "oh_pics_orient")
+            return self._sized(sp, width, height)
+
+        out, made = self._dsts(out, n, "sources", fitting)
+        self._call(self.L.oh_pics_orient(self.h, (C.c_int * n)(*pids), (C.c_int * n)(*out), n, C.byref(od)), "oh_pics_orient", made)
         dp = self._pic_params(out[0])
         return out, (0, dp.width - width, 0, dp.height - height)
 
-    def _alloc_like(self, pid, height, n):
-        """n fresh pictures with the params of picture pid and another height; ValueError where oh_pic_alloc would refuse the height"""
+    def _of_height(self, pid, height):
+        """the params of picture pid with another height; ValueError where oh_pic_alloc would refuse the height"""
         dp = F.OhPicParams.from_buffer_copy(self._pic_params(pid))
         mcb = 1 << dp.log2_min_cb_size
         if height < mcb or height % mcb:
             raise ValueError(f"a height of {height} is no multiple of the minimum coding block ({mcb}): no picture can hold it")
         dp.height = height
-        out = []
-        try:
-            for _ in range(n):
-                out.append(self.pic_alloc(dp))
-        except Exception:
-            for made in out:
-                self.pic_free(made)
-            raise
-        return out
+        return dp
 
     def pics_weave(self, top_pids, bottom_pids, *, out=None):
         """n pairs of finished fields -> n finished frames (oh_pics_weave): frame row 2y is row y of the top field, row 2y + 1 row y of
@@ -1151,19 +1157,9 @@ class Engine:
             raise ValueError("pics_weave needs at least one pair of fields (the destinations follow the fields' params)")
         if len(bottom) != n:
             raise ValueError(f"{n} top fields, {len(bottom)} bottom fields")
-        fresh = out is None
-        if fresh:
-            out = self._alloc_like(top[0], 2 * self._pic_params(top[0]).height, n)
-        else:
-            out = list(out)
-            if len(out) != n:
-                raise ValueError(f"out: {len(out)} pictures for {n} pairs of fields")
+        out, made = self._dsts(out, n, "pairs of fields", lambda: self._of_height(top[0], 2 * self._pic_params(top[0]).height))
         IA = C.c_int * n
-        rc = self.L.oh_pics_weave(self.h, IA(*top), IA(*bottom), IA(*out), n)
-        if rc != 0 and fresh:
-            for pid in out:
-                self.pic_free(pid)
-        self._chk(rc, "oh_pics_weave")
+        self._call(self.L.oh_pics_weave(self.h, IA(*top), IA(*bottom), IA(*out), n), "oh_pics_weave", made)
         return out
 
     def pics_separate(self, pids, *, top=True, bottom=True, out=None):
@@ -1177,26 +1173,21 @@ class Engine:
             raise ValueError("pics_separate needs at least one picture (the destinations follow the pictures' params)")
         if not top and not bottom:
             raise ValueError("pics_separate: neither field asked for")
-        fresh = out is None
-        if fresh:
+        made = []
+        if out is None:                                       # the fields of both sides in one run: made or freed together
             height = self._pic_params(pids[0]).height
             if height % 2:
                 raise ValueError(f"a frame of {height} rows has no two fields of one height")
-            both = self._alloc_like(pids[0], height // 2, n * (bool(top) + bool(bottom)))
-            sides = [both[:n] if top else None, both[-n:] if bottom else None]
+            made = self._alloc_like(self._of_height(pids[0], height // 2), n * (bool(top) + bool(bottom)))
+            sides = [made[:n] if top else None, made[-n:] if bottom else None]
         else:
-            sides = [None if s is None else list(s) for s in out]
+            sides = list(out)
             if len(sides) != 2 or (sides[0] is None) != (not top) or (sides[1] is None) != (not bottom):
                 raise ValueError("out: a pair (top ids, bottom ids) with None for the side that is not asked for")
-            for s in sides:
-                if s is not None and len(s) != n:
-                    raise ValueError(f"out: {len(s)} pictures for {n} sources")
+            sides = [None if s is None else self._dsts(s, n, "sources", None)[0] for s in sides]
         IA = C.c_int * n
-        rc = self.L.oh_pics_separate(self.h, IA(*pids), IA(*sides[0]) if top else None, IA(*sides[1]) if bottom else None, n)
-        if rc != 0 and fresh:
-            for pid in both:
-                self.pic_free(pid)
-        self._chk(rc, "oh_pics_separate")
+        self._call(self.L.oh_pics_separate(self.h, IA(*pids), IA(*sides[0]) if top else None, IA(*sides[1]) if bottom else None, n),
+                   "oh_pics_separate", made)
         return sides[0], sides[1]
 
     def pics_deinterlace(self, pids, mode="adaptive", *, keep="top", kept_first=True, prev=None, next=None, out=None):
@@ -1218,27 +1209,9 @@ class Engine:
             raise ValueError(f"keep {keep!r}: 'top' (0) or 'bottom' (1)")
         dd = OhDeinterlace(deint_mode(mode), parity, int(bool(kept_first)))
         IA = C.c_int * n
-        around = []
-        for name, ids in (("prev", prev), ("next", next)):
-            if ids is None:
-                around.append(None)
-                continue
-            ids = [-1 if v is None else int(v) for v in ids]
-            if len(ids) != n:
-                raise ValueError(f"{name}: {len(ids)} entries for {n} sources")
-            around.append(IA(*ids))
-        fresh = out is None
-        if fresh:
-            out = self._alloc_like(pids[0], self._pic_params(pids[0]).height, n)
-        else:
-            out = list(out)
-            if len(out) != n:
-                raise ValueError(f"out: {len(out)} pictures for {n} sources")
-        rc = self.L.oh_pics_deinterlace(self.h, around[0], IA(*pids), around[1], IA(*out), n, C.byref(dd))
-        if rc != 0 and fresh:
-            for pid in out:
-                self.pic_free(pid)
-        self._chk(rc, "oh_pics_deinterlace")
+        around = self._around(n, prev, next)
+        out, made = self._dsts(out, n, "sources", lambda: self._pic_params(pids[0]))
+        self._call(self.L.oh_pics_deinterlace(self.h, around[0], IA(*pids), around[1], IA(*out), n, C.byref(dd)), "oh_pics_deinterlace", made)
         return out
 
     def pics_filter(self, pids, mode, *, luma=None, chroma=None, amount=64, threshold=0, planes=7, prev=None, next=None, out=None):
@@ -1263,27 +1236,9 @@ class Engine:
                 raise ValueError(f"{name}: an int or a pair (luma, chroma)")
             arr[0], arr[1] = int(pair[0]), int(pair[1])
         IA = C.c_int * n
-        around = []
-        for name, ids in (("prev", prev), ("next", next)):
-            if ids is None:
-                around.append(None)
-                continue
-            ids = [-1 if v is None else int(v) for v in ids]
-            if len(ids) != n:
-                raise ValueError(f"{name}: {len(ids)} entries for {n} sources")
-            around.append(IA(*ids))
-        fresh = out is None
-        if fresh:
-            out = self._alloc_like(pids[0], self._pic_params(pids[0]).height, n)
-        else:
-            out = list(out)
-            if len(out) != n:
-                raise ValueError(f"out: {len(out)} pictures for {n} sources")
-        rc = self.L.oh_pics_filter(self.h, around[0], IA(*pids), around[1], IA(*out), n, C.byref(ff))
-        if rc != 0 and fresh:
-            for pid in out:
-                self.pic_free(pid)
-        self._chk(rc, "oh_pics_filter")
+        around = self._around(n, prev, next)
+        out, made = self._dsts(out, n, "sources", lambda: self._pic_params(pids[0]))
+        self._call(self.L.oh_pics_filter(self.h, around[0], IA(*pids), around[1], IA(*out), n, C.byref(ff)), "oh_pics_filter", made)
         return out
 
     def pics_compose(self, dst, layers, *, fill=None):
@@ -1339,18 +1294,8 @@ class Engine:
                 o.alpha_image_stride = st[0] if t.dim() == 3 else 0
         cp = OhCompose(COMPOSE_FILL if fill is not None else 0, (C.c_int32 * 3)(*([int(v) for v in fill] + [0, 0])[:3] if fill is not None else (0, 0, 0)),
                        len(layers), ol)
-        same = True
-        if torch is not None:
-            cur = torch.cuda.current_stream(dev)
-            same = (self.stream() or 0) == cur.cuda_stream    # an engine created on torch's current stream: nothing to order
-        if not same:
-            if self._torch_stream is None:
-                self._torch_stream = torch.cuda.ExternalStream(self.stream() or 0, device=dev)
-            es = self._torch_stream
-            es.wait_stream(cur)                               # the kernels that produce the alpha planes are queued on torch's stream
-        self._chk(self.L.oh_pics_compose(self.h, (C.c_int * max(n, 1))(*dst), n, C.byref(cp)), "oh_pics_compose")
-        if not same:
-            cur.wait_stream(es)                               # whatever torch does with the tensors later is ordered behind the read
+        with self._torch_ordered(torch):                      # the alpha planes are torch's
+            self._chk(self.L.oh_pics_compose(self.h, (C.c_int * max(n, 1))(*dst), n, C.byref(cp)), "oh_pics_compose")
         return dst
 
     def _pic_params(self, pid):

@@ -5,9 +5,13 @@
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
+#include <algorithm>
 #include <memory>
+#include <string>
+#include <vector>
 
 #include "../include/ohevc_hip.h"
+#include "../openhevc_amd/csrc/pics_math.h"
 
 static int failures;
 #define CHECK(cond, ...)                                                                   \
@@ -193,6 +197,68 @@ static int window_and_blend_group(void)
     return n;
 }
 
+/* the ids of a call that writes pictures (ids_apart, neighbours_resolve), every list a heap block of exactly n ints, and the window size */
+static int ids_group(void)
+{
+    int cases = 0;
+    const int sizes[2] = { 1, 65 };
+    for (int n : sizes) {
+        auto dst = heap<int>((size_t)n), src = heap<int>((size_t)n), nbr = heap<int>((size_t)n);
+        auto unread = heap<int>(0);                             /* a list that must not be read: any read is a sanitizer report */
+        for (int i = 0; i < n; i++) { dst[i] = 1000 - 7 * i; src[i] = 2000 + i; }      /* destinations not in order: 1000 the largest */
+        int both = -5;
+        CHECK(ids_apart(dst.get(), n, src.get(), n, &both) == 0 && both == -5, "n %d: apart", n);
+        CHECK(ids_apart(dst.get(), n, unread.get(), 0, &both) == 0 && ids_apart(dst.get(), n, nullptr, 0, &both) == 0, "n %d: no sources", n);
+        for (int at = 0; at < n; at += std::max(n - 1, 1)) {   /* a source equal to the largest (first) and the smallest (last) destination */
+            const int keep = src[n - 1 - at];
+            src[n - 1 - at] = dst[at];
+            CHECK(ids_apart(dst.get(), n, src.get(), n, &both) == 2 && both == dst[at], "n %d: source %d is destination %d: %d", n, n - 1 - at, at, both);
+            src[n - 1 - at] = keep;
+            cases++;
+        }
+        if (n > 1) {                                            /* a duplicate of the first and of the last entry */
+            for (int at = 0; at < n; at += n - 1) {
+                const int other = at ? n / 2 : n - 1, keep = dst[other];
+                dst[other] = dst[at];
+                src[0] = dst[at];                               /* listed twice comes first, as the services report it */
+                CHECK(ids_apart(dst.get(), n, src.get(), n, &both) == 1, "n %d: entry %d again at %d", n, at, other);
+                dst[other] = keep; src[0] = 2000;
+                cases++;
+            }
+        }
+        const int *const none[2] = { nullptr, nullptr };
+        const int *const dead[2] = { unread.get(), unread.get() };
+        const int *const given[2] = { nbr.get(), nullptr };
+        const int *const later[2] = { nullptr, nbr.get() };
+        std::vector<int> around[2], srcs;
+        int side = -5;
+        CHECK(neighbours_resolve(none, dst.get(), n, true, around, &srcs, &side) == -1 && (int)srcs.size() == n && around[0] == srcs && around[1] == srcs,
+              "n %d: null neighbour arrays", n);
+        CHECK(neighbours_resolve(dead, dst.get(), n, false, around, &srcs, &side) == -1 && (int)srcs.size() == n && around[0] == srcs && around[1] == srcs,
+              "n %d: neighbours that the mode does not use", n);
+        for (int i = 0; i < n; i++) nbr[i] = -1;
+        CHECK(neighbours_resolve(given, dst.get(), n, true, around, &srcs, &side) == -1 && (int)srcs.size() == 2 * n && around[0] == around[1] &&
+              std::equal(around[0].begin(), around[0].end(), dst.get()) && std::equal(around[0].begin(), around[0].end(), srcs.begin() + n), "n %d: all -1", n);
+        nbr[n - 1] = 77;
+        CHECK(neighbours_resolve(later, dst.get(), n, true, around, &srcs, &side) == -1 && around[1][n - 1] == 77 && srcs.back() == 77 && around[0][n - 1] == dst[n - 1] &&
+              around[1][0] == (n > 1 ? dst[0] : 77), "n %d: a next picture in the last slot", n);
+        nbr[n - 1] = -2;
+        CHECK(neighbours_resolve(later, dst.get(), n, true, around, &srcs, &side) == n - 1 && side == 1, "n %d: -2 in the last slot of next, side %d", n, side);
+        CHECK(neighbours_resolve(given, dst.get(), n, true, around, &srcs, &side) == n - 1 && side == 0, "n %d: -2 in the last slot of prev, side %d", n, side);
+        CHECK(neighbours_resolve(given, dst.get(), n, false, around, &srcs, &side) == -1 && (int)srcs.size() == n, "n %d: -2 where the mode does not use it", n);
+        cases += 7;
+    }
+    OhPicParams p;
+    memset(&p, 0, sizeof(p));
+    p.width = 416; p.height = 240; p.chroma_format_idc = 1;
+    const OhWindow w = { 200, 215, 100, 139 };
+    int W = 0, H = 0;
+    window_size(&p, w, &W, &H);
+    std::string why;
+    CHECK(W == 1 && H == 1 && crop_window_ok(&p, w, false, &why) && !crop_window_ok(&p, w, true, &why), "a window that leaves %d x %d", W, H);
+    return cases + 1;
+}
+
 int main()
 {
     printf("resize taps: %d axes\n", resize_group());
@@ -200,6 +266,7 @@ int main()
     printf("colour tables: %d OhColour\n", colour_group());
     printf("light bins and percentiles: %d values\n", light_group());
     printf("ssim window and blend: %d points\n", window_and_blend_group());
+    printf("ids apart, neighbours and the window size: %d cases\n", ids_group());
     if (failures) fprintf(stderr, "%d checks failed\n", failures);
     else printf("pics math ok\n");
     return failures ? 1 : 0;

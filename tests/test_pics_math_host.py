@@ -18,4 +18,4 @@ def test_pics_math_under_sanitizers(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.rstrip().endswith("pics math ok"), r.stdout + r.stderr
-    assert len(r.stdout.splitlines()) == 6                               # one line per group, then the verdict
+    assert len(r.stdout.splitlines()) == 7                               # one line per group, then the verdict

@@ -65,8 +65,8 @@ def run(a):
     for key, label, bd, what, reads in CASES:
         prv, cur, nxt = sets[bd]
         if bd not in dst:
-            dst[bd] = eng._alloc_like(cur[0], H, n)
-            copies[bd] = eng._alloc_like(cur[0], H, n)
+            dst[bd] = eng._alloc_like(eng._pic_params(cur[0]), n)
+            copies[bd] = eng._alloc_like(eng._pic_params(cur[0]), n)
         cp, d = copies[bd], dst[bd]
         mode, kw = how[what]
 
