@@ -3,6 +3,11 @@
  * host-side checks and counts, ONE device arena for the chunk (laid out by handover_layout.h, taken from the engine's pool), the
  * headers, the staging copies (one per group of OH_STAGE_GROUP lists) or the pull out of pinned memory, and the preparation kernels
  * behind them on the copy stream.  oh_frames_upload / oh_frame_upload of the C ABI (include/ohevc_hip.h).
+ * Order of events for a chunk: (1) parameters, current picture and usable references of every list, on the submitting thread;
+ * (2) the lists checked and counted list-parallel by the submitter and the engine's helper threads (handover_host.h), the failing list
+ * of lowest index reported; (3) layouts, arena, summary block, headers; (4) per group a staging buffer, the staging copy with its
+ * pieces claimed by the same threads, and ONE H2D copy; (5) the preparation launches and `ready`.  Nothing is taken from a pool or
+ * enqueued before (2) is through, and no helper touches the caller's arrays once oh_frames_upload has returned.
  */
 #include <memory>
 
@@ -126,82 +131,31 @@ static bool same_geometry(const OhPicParams &a, const OhPicParams &b)
  * boundary strengths from the motion field when the list carries bs_in (bs.hip)  ->  the summary back to pinned memory  ->
  * `ready`.  Nothing of it touches samples, so it overlaps the passes of the pictures before.  A malformed list is
  * reported by the first oh_frame(s)_execute that includes it (OH_E_ARG, before any of its passes is launched).
+ * The counting (handover_host.h: handover_check_list) and the staging copy are shared with the engine's helper threads, lists and
+ * pieces claimed from a cursor; what knows the engine — pictures, pools, streams, the error string, the timers — stays on the
+ * submitting thread.
  * ------------------------------------------------------------------------------------------------------------------- */
-static int check_host_side(OhEngine *e, const OhFrame *f, const Pic *cur, HostSide *h, std::vector<uint32_t> &pu_off)
+/* the engine's helper threads, started with the first hand-over and before anything of it that they share */
+static CopyPool *copiers_get(OhEngine *e)
 {
-    const OhPicParams &p = f->p;
-    h->ref_ok = 0; h->ref_used = 0; h->n_cross = 0; h->any_dense = false;
+    if (!e->copiers) {
+        static const char *cenv = getenv("OHEVC_COPY_THREADS");
+        e->copiers = new CopyPool();
+        e->copiers->start(cenv ? std::max(0, std::min(atoi(cenv), 8)) : 2);
+    }
+    return e->copiers;
+}
+
+/* bit i: slot i of the list's references holds a picture of its geometry that is not the picture being reconstructed */
+static uint32_t usable_refs(OhEngine *e, const OhFrame *f, const Pic *cur)
+{
+    uint32_t ok = 0;
     for (int i = 0; i < OH_MAX_REFS; i++) {
         Pic *r = get_pic(e, f->ref_pics[i]);
-        if (r && same_geometry(r->p, p) && r != cur)
-            h->ref_ok |= 1u << i;
+        if (r && same_geometry(r->p, f->p) && r != cur)
+            ok |= 1u << i;
     }
-    if ((f->n_pu && !f->pu) || (f->n_wp && !f->wp) || (f->n_tu && !f->tu) || (f->n_intra && !f->intra))
-        FAIL(e, OH_E_ARG, "a non-zero item count comes with a NULL array (pu / wp / tu / intra)");
-    /* blocks per PU: sizes the MC block lists (prep_pu_scan repeats the sums on the GPU and validates every PU) */
-    uint64_t nl = 0, nc = 0;
-    const int hs = oh_hshift(&p, 1), vs = oh_vshift(&p, 1), two = p.chroma_format_idc ? 2 : 0;
-    if ((uint64_t)f->n_pu * 2048 >= (1ull << 31))
-        FAIL(e, OH_E_ARG, "PU list too long");
-    pu_off.resize(2 * ((size_t)f->n_pu + 1));
-    uint32_t *ol = pu_off.data(), *oc = ol + f->n_pu + 1;       /* running sums: where every PU's blocks start in the two lists */
-    h->pu_off = ol;
-    for (uint32_t i = 0; i < f->n_pu; i++) {
-        const OhPu &pu = f->pu[i];
-        ol[i] = (uint32_t)nl; oc[i] = (uint32_t)nc;
-        nl += (uint64_t)(((pu.w + 7) >> 3) * ((pu.h + 7) >> 3));
-        nc += (uint64_t)(two * ((((pu.w >> hs) + 7) >> 3) * (((pu.h >> vs) + 7) >> 3)));
-        for (int l = 0; l < 2; l++)
-            if (pu.ref[l] < OH_MAX_REFS) h->ref_used |= (uint16_t)(1u << pu.ref[l]);
-    }
-    ol[f->n_pu] = (uint32_t)nl; oc[f->n_pu] = (uint32_t)nc;
-    for (uint32_t i = 0; i < f->n_wp; i++)
-        if (f->wp[i].log2_denom[0] > 7 || f->wp[i].log2_denom[1] > 7)
-            FAIL(e, OH_E_ARG, "weights %u: log2 denominator out of range", i);
-    h->tu_cnt[0] = h->tu_cnt[1] = h->tu_cnt[2] = h->tu_cnt[3] = 0;
-    for (uint32_t i = 0; i < f->n_tu; i++) {                  /* launch sizes of the residual pass; is any block dense? */
-        const OhTu &t = f->tu[i];
-        h->tu_cnt[(t.log2_size - 2) & 3]++;
-        h->n_cross += (t.flags & OH_TUF_CROSS) != 0;
-        h->any_dense = h->any_dense || !(t.flags & OH_TUF_SPARSE);
-    }
-    if (h->any_dense && f->n_coeff && !f->coeffs)
-        FAIL(e, OH_E_ARG, "dense transform blocks but coeffs[] is NULL");
-    if (h->n_cross && !f->tu_cross)
-        FAIL(e, OH_E_ARG, "cross-component blocks without tu_cross[]");
-    if (f->n_intra && p.constrained_intra_pred && !f->is_intra)
-        FAIL(e, OH_E_ARG, "constrained_intra_pred without the is_intra map");
-    if (f->n_intra) {
-        /* the level table is the contract behind the waits between CTUs (prep_intra_wait: a CTU waits only for lower levels), and
-         * prep_intra_ctu looks every entry's level up in it: checked here; everything below it on the GPU */
-        if (!f->level_start || !f->n_levels || !f->ictu || !f->n_ictu || !f->sub_start || !f->n_sub ||
-            f->level_start[0] != 0 || f->level_start[f->n_levels] != f->n_ictu)
-            FAIL(e, OH_E_ARG, "intra wavefront tables inconsistent");
-        for (uint32_t l = 0; l < f->n_levels; l++)
-            if (f->level_start[l] > f->level_start[l + 1])
-                FAIL(e, OH_E_ARG, "intra level table not monotonic");
-    }
-    if (p.deblock_enabled) {
-        const OhBsInputs *bi = f->bs_in;                      /* boundary strengths derived on the GPU instead of handed over */
-        if (bi && (!bi->mvf || !bi->cbf_luma || !bi->call_log2 || !bi->ctb_flags))
-            FAIL(e, OH_E_ARG, "bs_in: all four maps are required");
-        if (bi && (p.log2_min_pu_size < 2 || p.log2_min_tb_size < 2))
-            FAIL(e, OH_E_ARG, "bs_in: min PU / TB size below 4");
-        if (bi) {
-            const size_t n_cells = (size_t)(p.width >> p.log2_min_tb_size) * (p.height >> p.log2_min_tb_size);
-            for (size_t i = 0; i < n_cells; i++)
-                if (bi->call_log2[i] && (bi->call_log2[i] < p.log2_min_tb_size || bi->call_log2[i] > p.log2_ctb_size))
-                    FAIL(e, OH_E_ARG, "bs_in: call_log2[%zu] = %d is not a block size of this picture", i, bi->call_log2[i]);
-        }
-        if ((!bi && (!f->vertical_bs || !f->horizontal_bs || f->bs_size < oh_bs_size(&p))) || !f->qp_y_tab || !f->deblock)
-            FAIL(e, OH_E_ARG, "deblock side arrays missing or too small");
-    }
-    if ((p.pcm_loop_filter_disable || p.transquant_bypass_enable) && !f->is_pcm)
-        FAIL(e, OH_E_ARG, "is_pcm map required when pcm loop-filter disable / transquant bypass is on");
-    OhPrepCounts *cnt = &h->cnt;
-    cnt->n_pu = f->n_pu; cnt->n_mc_luma = (uint32_t)nl; cnt->n_mc_chroma = (uint32_t)nc; cnt->n_tu = f->n_tu;
-    cnt->n_intra = f->n_intra; cnt->n_sub = f->n_intra ? f->n_sub : 0; cnt->n_ictu = f->n_intra ? f->n_ictu : 0;
-    return OH_OK;
+    return ok;
 }
 
 /* pinned block the summaries of one chunk's work lists land in */
@@ -278,15 +232,10 @@ static hipError_t stage_pulled(OhEngine *e, const HandoverLayout &L, char *arena
 static hipError_t stage_copied(OhEngine *e, const HandoverLayout *L, const size_t *copied_off, int n, char *arena, size_t bytes, OhEngine::Stage *sg)
 {
     { HostTimer t(e, OH_HT_UPLOAD_MEMCPY);
-    if (!e->copiers) {
-        static const char *cenv = getenv("OHEVC_COPY_THREADS");
-        e->copiers = new CopyPool();
-        e->copiers->start(cenv ? std::max(0, std::min(atoi(cenv), 8)) : 2);
-    }
     e->copy_jobs.clear();
     for (int i = 0; i < n; i++)
         handover_copy_jobs_add(L[i], (char *)sg->p + (copied_off[i] - copied_off[0]), e->copy_jobs);
-    e->copiers->run(e->copy_jobs);                          /* dealt round-robin to the calling thread and the helpers */
+    copiers_get(e)->run(e->copy_jobs);                      /* claimed piece by piece by the calling thread and the helpers */
     }
     /* asynchronous: the caller's arrays are already copied out; the pinned buffer stays busy until `done` */
     HostTimer t_enq(e, OH_HT_UPLOAD_ENQUEUE);
@@ -311,6 +260,8 @@ struct ChunkScratch {
     HandoverHeader H[OH_MAX_BATCH];
     HandoverLayout L[OH_MAX_BATCH];
     Pic *cur[OH_MAX_BATCH];
+    uint32_t ref_ok[OH_MAX_BATCH];
+    HandoverCheck chk[OH_MAX_BATCH];  /* the error slot of every list: written by whichever thread checked it */
 };
 
 /* The hand-over of one chunk, n <= OH_MAX_BATCH lists: every list checked and counted; ONE arena; the lists staged and copied in
@@ -323,23 +274,39 @@ static int upload_chunk(OhEngine *e, const OhFrame *const *fs, int n, OhDevFrame
     if (!scratch) scratch.reset(new ChunkScratch());
     ChunkScratch &S = *scratch;
     HostTimer t_all(e, OH_HT_UPLOAD);
-    for (int i = 0; i < n; i++) {
+    CopyPool *pool = copiers_get(e);
+    /* what needs the engine, list by list on this thread: it stops at the first list it refuses (n_ok of them passed; the error
+     * stands in e->err), and that list is the one reported unless a list before it fails its own check below */
+    int n_ok = 0, rc_engine = OH_OK;
+    auto engine_side = [&](int i) -> int {
         const OhFrame *f = fs[i];
         if (!f)
             return OH_E_ARG;
-        int rc = check_params(e, &f->p);
-        if (rc)
+        if (const int rc = check_params(e, &f->p))
             return rc;
         S.cur[i] = get_pic(e, f->cur_pic);
         if (!S.cur[i] || !same_geometry(S.cur[i]->p, f->p))
             FAIL(e, OH_E_ARG, "cur_pic %d is not an allocated picture of this geometry", f->cur_pic);
-        { HostTimer t(e, OH_HT_UPLOAD_COUNT);
-        rc = check_host_side(e, f, S.cur[i], &S.h[i], S.pu_off[i]);
-        }
-        if (rc)
-            return rc;
+        S.ref_ok[i] = usable_refs(e, f, S.cur[i]);
+        return OH_OK;
+    };
+    while (n_ok < n && (rc_engine = engine_side(n_ok)) == OH_OK)
+        n_ok++;
+    /* check and count, list-parallel: every list is taken by one thread (this one or a helper) and all of them are through before
+     * anything is taken from a pool or enqueued, so a refused chunk leaves the engine as it was */
+    int bad;
+    { HostTimer t(e, OH_HT_UPLOAD_COUNT);
+    bad = handover_check_chunk(pool, fs, S.ref_ok, n_ok, S.h, S.pu_off, S.chk);
+    }
+    if (bad >= 0) {
+        e->err = S.chk[bad].msg;
+        return S.chk[bad].rc;
+    }
+    if (rc_engine != OH_OK)
+        return rc_engine;
+    for (int i = 0; i < n; i++) {
         memset(&S.H[i], 0, sizeof(S.H[i]));
-        S.L[i] = handover_layout(f, S.h[i], &S.H[i].d);
+        S.L[i] = handover_layout(fs[i], S.h[i], &S.H[i].d);
     }
     HIPCHK(e, hipSetDevice(e->device));
     const HandoverChunk C = handover_chunk_place(S.L, n);

@@ -1,7 +1,8 @@
 /*
  * engine_impl.h — what the engine's translation units share: the engine and picture structures, the error macros and the few
  * helpers more than one of them uses.  engine.hip: engine and picture lifecycle, staging buffers, passes, profiling;
- * engine_handover.hip: work-list hand-over and the arena pool; engine_pics.hip: plane transfers, hashes, conversion, import, measurement,
+ * engine_handover.hip: work-list hand-over and the arena pool (its host-only parts, which run on several threads, are handover_layout.h
+ * and handover_host.h: the layout, the check-and-count of a list and the thread pool, none of which knows the engine); engine_pics.hip: plane transfers, hashes, conversion, import, measurement,
  * comparison, resizing and composition of finished pictures, with the helpers those services share; engine_shvc.hip: SHVC up-sampling.
  * pics_math.hip, the services' host arithmetic, takes no engine and does not include this file (pics_math.h).
  * Internal: the C ABI is include/ohevc_hip.h.
@@ -23,6 +24,7 @@
 
 #include "../../include/ohevc_hip.h"
 #include "handover_layout.h"
+#include "handover_host.h"              /* CopyPool, handover_check_chunk: host-only, shared with the CPU checks */
 #include "kernels.h"
 
 #define OH_INTERNAL __attribute__((visibility("hidden")))    /* shared between the engine's files, not part of the library's ABI */
@@ -82,64 +84,6 @@ struct OhDevFrame {
     const struct OhEngine *owner = nullptr;   /* picture ids and arenas belong to one engine */
 };
 
-/* helper threads for the one host copy of the hand-over (the work list into a pinned staging buffer): the lists of a 4K picture are
- * ~4 MB, 0.22 ms for one thread — most of what the hand-over costs the decoder's thread.  The calling thread keeps a share. */
-struct CopyPool {
-    std::vector<std::thread> th;
-    std::mutex mu;
-    std::condition_variable cv, done_cv;
-    const std::vector<CopyJob> *jobs = nullptr;
-    int pending = 0;
-    uint64_t gen = 0;
-    bool stop = false;
-    static void run_share(const std::vector<CopyJob> &jobs, int share, int shares)
-    {
-        for (size_t i = (size_t)share; i < jobs.size(); i += (size_t)shares) {
-            const CopyJob &j = jobs[i];
-            if (j.pack) pack_bs((uint8_t *)j.dst, (const uint8_t *)j.src, j.n);
-            else memcpy(j.dst, j.src, j.n);
-        }
-    }
-    void worker(int k)
-    {
-        uint64_t seen = 0;
-        for (;;) {
-            const std::vector<CopyJob> *my;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return stop || gen != seen; });
-                if (stop) return;
-                seen = gen;
-                my = jobs;
-            }
-            run_share(*my, k + 1, (int)th.size() + 1);
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                if (--pending == 0) done_cv.notify_one();
-            }
-        }
-    }
-    void start(int n) { for (int k = 0; k < n; k++) th.emplace_back(&CopyPool::worker, this, k); }
-    void run(const std::vector<CopyJob> &j)                    /* returns when every job has been copied */
-    {
-        if (th.empty()) { run_share(j, 0, 1); return; }
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            jobs = &j; pending = (int)th.size(); gen++;
-        }
-        cv.notify_all();
-        run_share(j, 0, (int)th.size() + 1);
-        std::unique_lock<std::mutex> lk(mu);
-        done_cv.wait(lk, [&] { return pending == 0; });
-    }
-    ~CopyPool()
-    {
-        { std::lock_guard<std::mutex> lk(mu); stop = true; }
-        cv.notify_all();
-        for (auto &t : th) t.join();
-    }
-};
-
 struct OhEngine {
     int         device = 0;
     int         n_cu = 256;              /* compute units of the device */
@@ -188,7 +132,10 @@ struct OhEngine {
     enum { TICKET_RING = 128, TICKET_WORDS = 2 * OH_MAX_BATCH * 32 };      /* per batch: (direct, staged) x pictures, a cache line each (intra.hip: OH_TICKET_STRIDE) */
     uint32_t   *tickets = nullptr;
     uint64_t    ticket_seq = 0;
-    CopyPool   *copiers = nullptr;      /* created with the first hand-over (OHEVC_COPY_THREADS helpers, default 2) */
+    /* the hand-over's helper threads (handover_host.h; OHEVC_COPY_THREADS of them, default 2, 0: the submitter does everything alone
+     * on the same code path): started by the first hand-over BEFORE its check-and-count phase, which they share list by list, as they
+     * share the staging copy piece by piece.  They see lists and staging memory, never the engine */
+    CopyPool   *copiers = nullptr;
     /* output fetch (oh_pic_download_start / oh_download_finish): its own pinned buffers and copy helpers, usable while another thread
      * drives the engine */
     std::mutex  dl_mu, dl_copy_mu;

@@ -20,10 +20,23 @@
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 /* n boundary strengths (0..2, one per byte: hevc_filter.c's vertical_bs / horizontal_bs) -> (n + 3) / 4 bytes, entry i in bits
- * 2 (i & 3) of byte i >> 2 — the form the deblock pass reads.  Four bytes per multiply: the 2-bit fields land in the top byte. */
+ * 2 (i & 3) of byte i >> 2 — the form the deblock pass reads.  32 source bytes per step as eight 32-bit lanes (the compiler's vector
+ * extension, lowered to whatever the build's baseline has: shifts, ORs and a narrowing, no lane multiply), each lane folded into its low
+ * byte; then four bytes per multiply (the 2-bit fields land in the top byte), then the last one to three entries. */
 static inline void pack_bs(uint8_t *dst, const uint8_t *src, size_t n)
 {
+    typedef uint32_t pb_u32x8 __attribute__((vector_size(32)));
+    typedef uint8_t pb_u8x8 __attribute__((vector_size(8)));
     size_t i = 0;
+    for (; i + 32 <= n; i += 32) {
+        pb_u32x8 x;
+        memcpy(&x, src + i, 32);                               /* any alignment */
+        x &= 0x03030303u;
+        x |= x >> 6;                                           /* bytes 0 and 2 of a lane: entries 0|1 and 2|3 */
+        x = (x | (x >> 12)) & 0xffu;
+        const pb_u8x8 y = __builtin_convertvector(x, pb_u8x8);
+        memcpy(dst + (i >> 2), &y, 8);
+    }
     for (; i + 4 <= n; i += 4) {
         uint32_t x;
         memcpy(&x, src + i, 4);
@@ -36,7 +49,7 @@ static inline void pack_bs(uint8_t *dst, const uint8_t *src, size_t n)
     }
 }
 
-/* what the host counts and checks before the hand-over (engine_handover.hip: check_host_side) */
+/* what the host counts and checks before the hand-over (handover_host.h: handover_check_list) */
 struct HostSide {
     OhPrepCounts cnt;
     uint32_t tu_cnt[4], n_cross;      /* transform blocks per size: launch sizes of the residual pass */
