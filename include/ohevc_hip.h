@@ -571,6 +571,77 @@ int32_t oh_filter_unsharp(int32_t s, int32_t b, int32_t amount, int32_t threshol
 int32_t oh_filter_median9(const int32_t v[9]);
 int32_t oh_filter_temporal(int32_t c, int32_t p, int32_t n, int32_t mp, int32_t mn, int32_t threshold);
 
+/* Histograms: the code values of n finished pictures counted plane by plane (the tests check every field bit for bit
+ * against tests/levels_model.py).  The rules are those of oh_pics_compare: identical OhPicParams, win in luma samples with offsets that
+ * are multiples of SubWidthC / SubHeightC, plane c's window is win shifted by oh_hshift / oh_vshift.  Reads finished halves on the engine
+ * stream, waits for it and fills out on the host; every call starts from zero.  The GPU counts the bins; samples, sum, sum_sq, min and
+ * max are derived from them on the host in 64-bit integers, so every field is exact and independent of the order of the workgroups.  A
+ * stored sample above 2^bit_depth - 1, which no decoder and no service writes, counts in the top bin of its depth.  More than
+ * OH_CONV_MAX_PICS pictures are split into several launches.  n == 0: OH_OK.
+ * OH_E_ARG, out untouched: a null win, out or id array, a negative n, an unknown picture, pictures whose params differ, an empty window
+ * or one whose offsets are not multiples of SubWidthC / SubHeightC.  No combination gives OH_E_UNSUPPORTED. */
+enum { OH_HIST_BINS = 4096 };
+typedef struct OhPlaneHist {
+    uint64_t samples;              /* samples of the plane's window */
+    uint64_t sum, sum_sq;          /* sum v, sum v^2 */
+    uint32_t min, max;             /* of v; a plane the picture lacks: everything 0 */
+    uint32_t hist[OH_HIST_BINS];   /* hist[v] = samples equal to v; bins >= 2^bit_depth are 0 */
+} OhPlaneHist;
+typedef struct OhHistogram { OhPlaneHist plane[3]; } OhHistogram;
+int oh_pics_histogram(OhEngine *e, const int *pic_ids, int n, const OhWindow *win, OhHistogram *out);
+/* host only: the n plane histograms pooled, N their samples (the sum of their bins), cum(v) the pooled count of the values <= v:
+ * *value is the smallest v with cum(v) > 0 and cum(v) 10^6 >= ppm N, in 64-bit integers; ppm 0 gives the minimum, 10^6 the maximum.
+ * OH_E_ARG: a null pointer, n < 1, ppm > 10^6, no samples. */
+int oh_hist_percentile(const OhPlaneHist *h, int n, uint32_t ppm, uint32_t *value);
+/* host only: *sad = sum over v of |a.hist[v] - b.hist[v]|, the scene-cut measure.  OH_E_ARG: a null pointer. */
+int oh_hist_distance(const OhPlaneHist *a, const OhPlaneHist *b, uint64_t *sad);
+
+/* Look-up tables: n finished pictures become n finished pictures of the same size and chroma format, every sample of a selected plane
+ * c replaced by table[c][sample], over the whole coded planes (tests/levels_model.py).  The sources have identical
+ * params among themselves, the destinations among themselves; both sides share width, height and chroma format, the bit depth may
+ * differ.  A plane whose bit is clear is copied, which needs equal depths.  Bits of planes the format lacks are ignored, as are their
+ * table pointers.  Reads finished halves, writes half 0 of each destination and marks it finished, like oh_pics_reformat; enqueued on the
+ * engine stream, returns without waiting.  The tables are copied by the call (through a pinned buffer, onto the engine stream in front
+ * of the launch): the host arrays may be freed on return.  n == 0: OH_OK (planes is checked all the same; n_entries and the tables are
+ * not: there is no picture to take the depths from).  More than OH_CONV_MAX_PICS pictures are split into several launches.
+ * OH_E_ARG, nothing written: a null e, lut or id array, a negative n; an unknown picture; params that differ as above; a destination
+ * that is also a source, or listed twice; planes outside 0 .. 7; n_entries other than 2^(source bit depth); a null table of a selected
+ * plane the format has; a table entry above 2^(destination bit depth) - 1; depths that differ while a plane the format has is not
+ * selected.  No combination gives OH_E_UNSUPPORTED. */
+typedef struct OhLut {
+    int32_t planes;               /* bit c set: plane c goes through table[c]; clear: plane c is copied */
+    int32_t n_entries;            /* must be 1 << (source bit depth) */
+    const uint16_t *table[3];     /* HOST arrays of n_entries values, each 0 .. 2^(destination bit depth) - 1 */
+} OhLut;
+int oh_pics_lut(OhEngine *e, const int *src_ids, const int *dst_ids, int n, const OhLut *lut);
+/* host only: table builders, all in integers (division is the integer division of non-negative numbers, >> on a negative number an
+ * arithmetic shift).  bs / bd: source / destination bit depth, each in {8, 9, 10, 12}; Ms / Md = 2^bs - 1 / 2^bd - 1; ks = 2^(bs - 8),
+ * kd = 2^(bd - 8); out: 2^bs entries, v their index.  OH_E_ARG, out untouched: another depth, a null pointer, and what each one names.
+ *   oh_lut_identity   s = bs - bd; s <= 0: v << -s; s > 0: min((v + 2^(s - 1)) >> s, Md) — oh_reformat_quantise with OH_RF_ROUND, f = 0
+ *   oh_lut_range      to_full (non-zero: limited -> full, zero: full -> limited) of luma (chroma zero) or chroma (non-zero):
+ *                       to full, luma       c = min(max(v, 16 ks), 235 ks) - 16 ks;  out = (c Md + (219 ks >> 1)) / (219 ks)
+ *                       to full, chroma     d = min(max(v, 16 ks), 240 ks) - 128 ks;  m = (|d| Md + 112 ks) / (224 ks);
+ *                                           out = min(max(2^(bd - 1) + sign(d) m, 0), Md)
+ *                       to limited, luma    out = 16 kd + (v 219 kd + (Ms >> 1)) / Ms
+ *                       to limited, chroma  d = v - 2^(bs - 1);  m = (|d| 224 kd + (Ms >> 1)) / Ms;
+ *                                           out = min(max(128 kd + sign(d) m, 16 kd), 240 kd)
+ *   oh_lut_linear     min(max(((v - pivot_in) gain_q16 + pivot_out 65536 + 32768) >> 16, 0), Md) in int64; the pivots are any int32;
+ *                     gain -65536 with pivots 0 and Md inverts, 131072 doubles the contrast around the pivots
+ *   oh_lut_stretch    auto-levels at one depth bd: lo = oh_hist_percentile(h, n, lo_ppm), hi = oh_hist_percentile(h, n, 10^6 - hi_ppm);
+ *                     hi <= lo: the identity; else ((min(max(v, lo), hi) - lo) Md + ((hi - lo) >> 1)) / (hi - lo).
+ *                     OH_E_ARG also: n < 1, lo_ppm + hi_ppm >= 10^6, no samples
+ *   oh_lut_equalise   at one depth bd, the n histograms pooled: cum(v) the count of the values <= v, cmin = cum at the smallest value
+ *                     present, N all samples; N == cmin: the identity; else 0 where cum(v) < cmin and
+ *                     ((cum(v) - cmin) Md + ((N - cmin) >> 1)) / (N - cmin) elsewhere.  OH_E_ARG also: n < 1
+ *   oh_lut_then       out[v] = second[first[v]] for v < n1: two tables in one pass.  OH_E_ARG: a null pointer, n1 or n2 below 1, an
+ *                     entry of first that is >= n2 */
+int oh_lut_identity(int bs, int bd, uint16_t *out);
+int oh_lut_range(int bs, int bd, int to_full, int chroma, uint16_t *out);
+int oh_lut_linear(int bs, int bd, int32_t gain_q16, int32_t pivot_in, int32_t pivot_out, uint16_t *out);
+int oh_lut_stretch(const OhPlaneHist *h, int n, uint32_t lo_ppm, uint32_t hi_ppm, int bd, uint16_t *out);
+int oh_lut_equalise(const OhPlaneHist *h, int n, int bd, uint16_t *out);
+int oh_lut_then(const uint16_t *first, int n1, const uint16_t *second, int n2, uint16_t *out);
+
 /* SHVC inter-layer reference picture: resample the finished base-layer picture src_pic into
  * the enhancement-layer picture dst_pic, bit-exact with the reference's whole-picture slot
  * HEVCDSPContext.upsample_base_layer_frame (hevcdsp_template.c:2164-2438, call site hevc.c:3241).

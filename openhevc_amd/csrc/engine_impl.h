@@ -3,7 +3,7 @@
  * helpers more than one of them uses.  engine.hip: engine and picture lifecycle, staging buffers, passes, profiling;
  * engine_handover.hip: work-list hand-over and the arena pool (its host-only parts, which run on several threads, are handover_layout.h
  * and handover_host.h: the layout, the check-and-count of a list and the thread pool, none of which knows the engine); engine_pics.hip: plane transfers, hashes, conversion, import, measurement,
- * comparison, resizing and composition of finished pictures, with the helpers those services share; engine_shvc.hip: SHVC up-sampling.
+ * comparison, resizing, composition, histograms and look-up tables of finished pictures, with the helpers those services share; engine_shvc.hip: SHVC up-sampling.
  * pics_math.hip, the services' host arithmetic, takes no engine and does not include this file (pics_math.h).
  * Internal: the C ABI is include/ohevc_hip.h.
  */
@@ -164,7 +164,10 @@ struct OhEngine {
                                           * neither call disturbs the tables the other has cached */
     Scratch     light_res;               /* oh_pics_light_level: the results of the call in HBM */
     Scratch     compare_res;             /* oh_pics_compare: the results of the call in HBM */
-    Scratch     compose_dev;             /* oh_pics_compose: the layer table of the call (OhCpsLayer, then OhCpsSrc per launch set) */
+    Scratch     hist_res;                /* oh_pics_histogram: the bins of the call in HBM */
+    Scratch     lut_tabs;                /* oh_pics_lut: the three tables of the last call (3 x OH_LUT_MAX uint16), rewritten on the stream
+                                          * behind the launches that read them */
+    Scratch     compose_dev;           /* oh_pics_compose: the layer table of the call (OhCpsLayer, then OhCpsSrc per launch set) */
     uint32_t    spin_limit = 1u << 22;   /* polls (with s_sleep between them, ~1 s in all) before a waiting workgroup gives up; OHEVC_SPIN_LIMIT */
 };
 

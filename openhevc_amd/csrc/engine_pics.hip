@@ -1412,6 +1412,113 @@ extern "C" int oh_pics_compose(OhEngine *e, const int *dst_ids, int n, const OhC
     return OH_OK;
 }
 
+/* ---------------- histograms of the code values (histogram.hip) ---------------- */
+extern "C" int oh_pics_histogram(OhEngine *e, const int *pic_ids, int n, const OhWindow *win, OhHistogram *out)
+{
+    const char *who = "oh_pics_histogram";
+    if (!e || n < 0 || !win || !out || (n && !pic_ids))
+        return OH_E_ARG;
+    if (!n)
+        return OH_OK;
+    const Pic *p0 = alike_pics(e, who, pic_ids, n);
+    if (!p0) return OH_E_ARG;
+    const OhPicParams &p = p0->p;
+    std::string why;
+    if (!crop_window_ok(&p, *win, true, &why))
+        FAIL(e, OH_E_ARG, "%s: %s", who, why.c_str());
+    HIPCHK(e, hipSetDevice(e->device));
+    OhHistArgs a;
+    memset(&a, 0, sizeof(a));
+    const int np = n_planes(p), sb = sample_bytes(p.bit_depth);
+    int W, H;
+    window_size(&p, *win, &W, &H);
+    row_pitches(p0, np, a.pitch);
+    for (int c = 0; c < (np > 1 ? 2 : 1); c++) {
+        OhHistClass &k = a.k[c];
+        const int hs = oh_hshift(&p, c), vs = oh_vshift(&p, c);
+        k.x0 = win->left >> hs; k.y0 = win->top >> vs;
+        k.w = W >> hs; k.h = H >> vs;
+        k.g0 = k.x0 * sb / 16;                                  /* the granules of a row that hold a sample of the window */
+        k.ng = ((k.x0 + k.w) * sb + 15) / 16 - k.g0;
+        k.tiles = (k.h + OH_HG_ROWS - 1) / OH_HG_ROWS;
+    }
+    a.np = np; a.bd = p.bit_depth;
+    const size_t per_pic = (size_t)3 * OH_HG_BINS, bytes = (size_t)n * per_pic * sizeof(uint32_t);
+    OhEngine::Stage *sg = nullptr;
+    { const int rc = results_begin(e, who, &e->hist_res, bytes, n, &sg); if (rc) return rc; }
+    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
+        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+        for (int i = 0; i < m; i++) read_planes(get_pic(e, pic_ids[i0 + i]), np, a.src[i]);
+        a.res = (uint32_t *)e->hist_res.p + (size_t)i0 * per_pic;
+        ohk_histogram(&a, m, e->stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    { const int rc = results_fetch(e, &e->hist_res, bytes, sg); if (rc) return rc; }
+    const uint32_t *r = (const uint32_t *)sg->p;
+    for (int i = 0; i < n; i++) {
+        memset(&out[i], 0, sizeof(out[i]));
+        for (int c = 0; c < np; c++)
+            hist_derive(r + (size_t)i * per_pic + (size_t)c * OH_HG_BINS, &out[i].plane[c]);
+    }
+    return OH_OK;
+}
+
+/* ---------------- look-up tables (lut.hip) ---------------- */
+extern "C" int oh_pics_lut(OhEngine *e, const int *src_ids, const int *dst_ids, int n, const OhLut *lut)
+{
+    const char *who = "oh_pics_lut";
+    if (!e || n < 0 || !lut || (n && (!src_ids || !dst_ids)))
+        return OH_E_ARG;
+    if (lut->planes < 0 || lut->planes > 7)
+        FAIL(e, OH_E_ARG, "%s: planes %d outside 0 .. 7", who, lut->planes);
+    if (!n)
+        return OH_OK;
+    const Pic *s0 = alike_pics(e, who, src_ids, n);
+    if (!s0) return OH_E_ARG;
+    const Pic *d0 = alike_pics(e, who, dst_ids, n);
+    if (!d0) return OH_E_ARG;
+    { const int rc = dsts_apart(e, who, dst_ids, n, src_ids, n); if (rc) return rc; }
+    const OhPicParams &sp = s0->p, &dp = d0->p;
+    if (sp.width != dp.width || sp.height != dp.height || sp.chroma_format_idc != dp.chroma_format_idc)
+        FAIL(e, OH_E_ARG, "%s: sources of %dx%d, chroma format %d, destinations of %dx%d, chroma format %d", who, sp.width, sp.height,
+             sp.chroma_format_idc, dp.width, dp.height, dp.chroma_format_idc);
+    std::string why;
+    if (lut_check(lut, sp.bit_depth, dp.bit_depth, n_planes(sp), &why))
+        FAIL(e, OH_E_ARG, "%s: %s", who, why.c_str());
+    HIPCHK(e, hipSetDevice(e->device));
+    const int np = n_planes(sp);
+    /* the tables of the call: staged in a pinned buffer of the pool and copied on the engine stream — behind the launches of an earlier
+     * call that read the device copy, in front of this call's.  The device copy has its full size from the first call on. */
+    const size_t tab_bytes = (size_t)3 * OH_LUT_MAX * sizeof(uint16_t);
+    { const int rc = scratch_reserve(e, &e->lut_tabs, tab_bytes); if (rc) return rc; }
+    OhEngine::Stage *sg = stage_acquire(e, tab_bytes);
+    if (!sg)
+        FAIL(e, OH_E_NOMEM, "%s: no staging buffer for %zu bytes of tables", who, tab_bytes);
+    memset(sg->p, 0, tab_bytes);
+    for (int c = 0; c < np; c++)
+        if (lut->planes >> c & 1)
+            memcpy((uint16_t *)sg->p + (size_t)c * OH_LUT_MAX, lut->table[c], (size_t)lut->n_entries * sizeof(uint16_t));
+    HIPCHK(e, hipMemcpyAsync(e->lut_tabs.p, sg->p, tab_bytes, hipMemcpyHostToDevice, e->stream));
+    { const int rc = stage_in_use(e, sg, e->stream); if (rc) return rc; }
+    OhLutArgs a;
+    memset(&a, 0, sizeof(a));
+    row_pitches(s0, np, a.spitch); row_pitches(d0, np, a.dpitch);
+    class_sizes(s0, np, a.w, a.h);
+    a.np = np; a.sbd = sp.bit_depth; a.dbd = dp.bit_depth;
+    a.planes = lut->planes;
+    a.tab = (const uint16_t *)e->lut_tabs.p;
+    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
+        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+        for (int i = 0; i < m; i++) {
+            read_planes(get_pic(e, src_ids[i0 + i]), np, a.src[i]);
+            write_planes(get_pic(e, dst_ids[i0 + i]), np, a.dst[i]);
+        }
+        ohk_lut(&a, m, e->stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    return OH_OK;
+}
+
 extern "C" int oh_pic_device_planes(OhEngine *e, int pic_id, void *planes[3], int32_t stride[3], int32_t width[3], int32_t height[3])
 {
     if (!e)

@@ -209,6 +209,40 @@ struct OhFilterArgs {
     int32_t     amount[2], threshold[2];
 };
 
+/* histograms of the code values (histogram.hip): the finished planes of the pictures of one launch by value in the kernel
+ * arguments, two plane classes (0 luma, 1 chroma) with the plane's window and the 16-byte granules of a row that cover it, and the bins
+ * of the launch's first picture in device memory that the engine owns and clears on the stream in front of the launch. */
+enum { OH_HG_ROWS = 8,               /* window rows per workgroup: all the granules of each */
+       OH_HG_BINS = 4096 };          /* OH_HIST_BINS: uint32 per plane of a picture in res */
+struct OhHistClass {
+    int32_t x0, y0, w, h;            /* the plane's window: origin in the plane, size */
+    int32_t g0, ng;                  /* the first granule of a plane row that holds a sample of the window, and how many do */
+    int32_t tiles;                   /* workgroups per plane: ceil(h / OH_HG_ROWS) */
+};
+struct OhHistArgs {
+    const void *src[64][3];          /* OH_CONV_MAX_PICS pictures x planes: the finished halves */
+    uint32_t   *res;                 /* [picture][3][OH_HG_BINS] */
+    OhHistClass k[2];
+    int32_t     pitch[3];            /* bytes between rows of each plane */
+    int32_t     np, bd;              /* planes: 1 or 3; bit depth */
+};
+
+/* look-up tables (lut.hip): the finished planes of the sources and half 0 of the destinations of one launch by value in
+ * the kernel arguments; every picture of a launch has the same geometry.  Two plane classes (0 luma, 1 chroma).  tab: three tables of
+ * OH_LUT_MAX uint16 each in device memory that the engine owns and fills on the stream in front of the launch. */
+enum { OH_LUT_ROWS = 16,             /* plane rows per workgroup: it loads its plane's table once for all of them */
+       OH_LUT_UNIT = 16,             /* samples a lane takes at a time: whole 16-byte granules of either sample type */
+       OH_LUT_MAX = 4096 };          /* entries of a table at 12 bit */
+struct OhLutArgs {
+    const void     *src[64][3];      /* OH_CONV_MAX_PICS pictures x planes: the finished halves */
+    void           *dst[64][3];      /* half 0 of the destinations */
+    const uint16_t *tab;             /* [3][OH_LUT_MAX] */
+    int32_t         spitch[3], dpitch[3];   /* bytes between rows of each plane */
+    int32_t         w[2], h[2];      /* coded size of the planes */
+    int32_t         np, sbd, dbd;    /* planes: 1 or 3; bit depths */
+    int32_t         planes;          /* bit c set: plane c goes through its table; clear: it is copied (sbd == dbd) */
+};
+
 /* picture resizing (resize.hip): what one launch set needs, by value in the kernel arguments like OhConvArgs.  Two plane
  * classes (0 luma, 1 chroma), each with its own geometry and tap tables; the tables live in device memory that the engine owns and
  * fills (engine_pics.hip: oh_pics_resize, from pics_math.hip: oh_resize_taps) on the stream in front of the launches. */
@@ -270,7 +304,11 @@ void ohk_deinterlace(const OhDiArgs *a, int n, hipStream_t st);
 void ohk_fields(const OhDiArgs *a, int n, hipStream_t st);
 /* n pictures of a.src[1] (with a.src[0] and a.src[2] around them in time) filtered into the n destinations of a.dst */
 void ohk_filter(const OhFilterArgs *a, int n, hipStream_t st);
-void ohk_hash(int kind, const OhMd5Job *jobs, const uint32_t *first, const uint32_t *task_map, int n_jobs, int n_tasks, uint32_t *partials,
+/* the bins of n pictures of a.src into a.res[0 .. 3 n OH_HG_BINS) */
+void ohk_histogram(const OhHistArgs *a, int n, hipStream_t st);
+/* n sources of a.src through a.tab into the n destinations of a.dst */
+void ohk_lut(const OhLutArgs *a, int n, hipStream_t st);
+void ohk_hash(int kind,const OhMd5Job *jobs, const uint32_t *first, const uint32_t *task_map, int n_jobs, int n_tasks, uint32_t *partials,
               uint32_t *out, hipStream_t st);
 void ohk_inter(const OhBatch *B, int n, const OhPicParams *p, uint32_t max_luma, uint32_t max_chroma, hipStream_t st);
 void ohk_residual(const OhBatch *B, int n, const OhPicParams *p, const uint32_t max_cnt[4], hipStream_t st);

@@ -1,7 +1,7 @@
 /*
  * pics_math.hip — the host arithmetic of the picture services (engine_pics.hip), with neither an engine nor a device: image sizes and
  * crop windows, the ids of a call (destinations apart from sources, neighbours in time), the integers of the RGB conversions, the colour tables of the HDR forms, light-level bins and percentiles, the SSIM window
- * and PSNR, the resize taps, the compose formulas, the reformat quantisation, the orientations' group, the pic_struct table, the adaptive deinterlacer's sample and the filters' taps and samples.  No kernel, no HIP runtime call: tests/pics_math_check.cpp runs it under sanitizers.
+ * and PSNR, the resize taps, the compose formulas, the reformat quantisation, the orientations' group, the pic_struct table, the adaptive deinterlacer's sample, the filters' taps and samples, and what follows from a histogram's bins with the table builders.  No kernel, no HIP runtime call: tests/pics_math_check.cpp runs it under sanitizers.
  */
 #include <stdio.h>
 #include <string.h>
@@ -748,6 +748,181 @@ int filter_check(const OhFilter *f, int bit_depth, std::string *why)
         if ((f->mode == OH_FILTER_UNSHARP || f->mode == OH_FILTER_TEMPORAL) && (f->threshold[q] < 0 || f->threshold[q] > top)) {
             snprintf(buf, sizeof(buf), "threshold[%d] %d (0 .. %lld)", q, f->threshold[q], (long long)top); *why = buf; return OH_E_ARG;
         }
+    }
+    return OH_OK;
+}
+
+/* ---------------- histograms and look-up tables (histogram.hip, lut.hip) ---------------- */
+/* the fields of a plane's histogram that follow from its bins (the kernel makes nothing else), in 64-bit integers */
+void hist_derive(const uint32_t *bins, OhPlaneHist *out)
+{
+    memset(out, 0, sizeof(*out));
+    bool any = false;
+    for (uint32_t v = 0; v < OH_HIST_BINS; v++) {
+        const uint64_t c = bins[v];
+        out->hist[v] = bins[v];
+        if (!c)
+            continue;
+        out->samples += c;
+        out->sum += c * v;
+        out->sum_sq += c * v * v;
+        if (!any) out->min = v;
+        out->max = v;
+        any = true;
+    }
+}
+
+/* the pooled count of bin v of n histograms */
+static uint64_t pooled(const OhPlaneHist *h, int n, int v)
+{
+    uint64_t c = 0;
+    for (int i = 0; i < n; i++) c += h[i].hist[v];
+    return c;
+}
+
+static uint64_t pooled_total(const OhPlaneHist *h, int n)
+{
+    uint64_t N = 0;
+    for (int v = 0; v < OH_HIST_BINS; v++) N += pooled(h, n, v);
+    return N;
+}
+
+extern "C" int oh_hist_percentile(const OhPlaneHist *h, int n, uint32_t ppm, uint32_t *value)
+{
+    if (!h || !value || n < 1 || ppm > 1000000u)
+        return OH_E_ARG;
+    const uint64_t N = pooled_total(h, n);
+    if (!N)
+        return OH_E_ARG;
+    const uint64_t need = (uint64_t)ppm * N;
+    uint64_t cum = 0;
+    for (int v = 0; v < OH_HIST_BINS; v++) {
+        cum += pooled(h, n, v);
+        if (cum && cum * 1000000u >= need) {
+            *value = (uint32_t)v;
+            return OH_OK;
+        }
+    }
+    return OH_E_ARG;                                            /* not reached: cum ends at N */
+}
+
+extern "C" int oh_hist_distance(const OhPlaneHist *a, const OhPlaneHist *b, uint64_t *sad)
+{
+    if (!a || !b || !sad)
+        return OH_E_ARG;
+    uint64_t s = 0;
+    for (int v = 0; v < OH_HIST_BINS; v++)
+        s += a->hist[v] > b->hist[v] ? a->hist[v] - b->hist[v] : b->hist[v] - a->hist[v];
+    *sad = s;
+    return OH_OK;
+}
+
+extern "C" int oh_lut_identity(int bs, int bd, uint16_t *out)
+{
+    if (!depth_ok(bs) || !depth_ok(bd) || !out)
+        return OH_E_ARG;
+    for (int v = 0; v < (1 << bs); v++)
+        out[v] = (uint16_t)reformat_quantise(v, bs - bd, OH_RF_ROUND, 0, 0, bd);
+    return OH_OK;
+}
+
+extern "C" int oh_lut_range(int bs, int bd, int to_full, int chroma, uint16_t *out)
+{
+    if (!depth_ok(bs) || !depth_ok(bd) || !out)
+        return OH_E_ARG;
+    const int64_t Ms = (1 << bs) - 1, Md = (1 << bd) - 1, ks = 1 << (bs - 8), kd = 1 << (bd - 8);
+    for (int64_t v = 0; v <= Ms; v++) {
+        int64_t o;
+        if (to_full && !chroma) {
+            const int64_t c = std::min(std::max(v, 16 * ks), 235 * ks) - 16 * ks;
+            o = (c * Md + (219 * ks >> 1)) / (219 * ks);
+        } else if (to_full) {
+            const int64_t d = std::min(std::max(v, 16 * ks), 240 * ks) - 128 * ks;
+            const int64_t m = ((d < 0 ? -d : d) * Md + 112 * ks) / (224 * ks);
+            o = std::min(std::max(((int64_t)1 << (bd - 1)) + (d < 0 ? -m : m), (int64_t)0), Md);
+        } else if (!chroma) {
+            o = 16 * kd + (v * 219 * kd + (Ms >> 1)) / Ms;
+        } else {
+            const int64_t d = v - ((int64_t)1 << (bs - 1));
+            const int64_t m = ((d < 0 ? -d : d) * 224 * kd + (Ms >> 1)) / Ms;
+            o = std::min(std::max(128 * kd + (d < 0 ? -m : m), 16 * kd), 240 * kd);
+        }
+        out[v] = (uint16_t)o;
+    }
+    return OH_OK;
+}
+
+extern "C" int oh_lut_linear(int bs, int bd, int32_t gain_q16, int32_t pivot_in, int32_t pivot_out, uint16_t *out)
+{
+    if (!depth_ok(bs) || !depth_ok(bd) || !out)
+        return OH_E_ARG;
+    const int64_t Md = (1 << bd) - 1;
+    for (int64_t v = 0; v < (1 << bs); v++) {                   /* |v - pivot_in| <= 2^31 + 4095 and |gain| <= 2^31: the sum stays below 2^63 */
+        const int64_t y = ((v - pivot_in) * gain_q16 + (int64_t)pivot_out * 65536 + 32768) >> 16;
+        out[v] = (uint16_t)std::min(std::max(y, (int64_t)0), Md);
+    }
+    return OH_OK;
+}
+
+extern "C" int oh_lut_stretch(const OhPlaneHist *h, int n, uint32_t lo_ppm, uint32_t hi_ppm, int bd, uint16_t *out)
+{
+    if (!h || n < 1 || !depth_ok(bd) || !out || (uint64_t)lo_ppm + hi_ppm >= 1000000u)
+        return OH_E_ARG;
+    uint32_t lo32 = 0, hi32 = 0;
+    if (oh_hist_percentile(h, n, lo_ppm, &lo32) || oh_hist_percentile(h, n, 1000000u - hi_ppm, &hi32))
+        return OH_E_ARG;
+    const int64_t lo = lo32, hi = hi32, M = (1 << bd) - 1;
+    for (int64_t v = 0; v <= M; v++)
+        out[v] = (uint16_t)(hi <= lo ? v : ((std::min(std::max(v, lo), hi) - lo) * M + ((hi - lo) >> 1)) / (hi - lo));
+    return OH_OK;
+}
+
+extern "C" int oh_lut_equalise(const OhPlaneHist *h, int n, int bd, uint16_t *out)
+{
+    if (!h || n < 1 || !depth_ok(bd) || !out)
+        return OH_E_ARG;
+    const uint64_t N = pooled_total(h, n), M = (1u << bd) - 1;
+    uint64_t cmin = 0;
+    for (int v = 0; v < OH_HIST_BINS && !cmin; v++) cmin = pooled(h, n, v);
+    uint64_t cum = 0;
+    for (uint64_t v = 0; v <= M; v++) {
+        cum += pooled(h, n, (int)v);
+        out[v] = (uint16_t)(N == cmin ? v : cum < cmin ? 0 : ((cum - cmin) * M + ((N - cmin) >> 1)) / (N - cmin));
+    }
+    return OH_OK;
+}
+
+extern "C" int oh_lut_then(const uint16_t *first, int n1, const uint16_t *second, int n2, uint16_t *out)
+{
+    if (!first || !second || !out || n1 < 1 || n2 < 1)
+        return OH_E_ARG;
+    for (int v = 0; v < n1; v++)
+        if (first[v] >= n2)
+            return OH_E_ARG;
+    for (int v = 0; v < n1; v++)
+        out[v] = second[first[v]];
+    return OH_OK;
+}
+
+/* what oh_pics_lut checks of the OhLut itself (planes is in 0 .. 7), for sources of sbd and destinations of dbd bits with np planes */
+int lut_check(const OhLut *lut, int sbd, int dbd, int np, std::string *why)
+{
+    char buf[256];
+    if (lut->n_entries != 1 << sbd) {
+        snprintf(buf, sizeof(buf), "n_entries %d for sources of %d bits (%d)", lut->n_entries, sbd, 1 << sbd); *why = buf; return OH_E_ARG;
+    }
+    for (int c = 0; c < np; c++) {
+        if (!(lut->planes >> c & 1)) {
+            if (sbd != dbd) {
+                snprintf(buf, sizeof(buf), "plane %d is copied, from %d to %d bits", c, sbd, dbd); *why = buf; return OH_E_ARG;
+            }
+            continue;
+        }
+        if (!lut->table[c]) { snprintf(buf, sizeof(buf), "no table for plane %d", c); *why = buf; return OH_E_ARG; }
+        for (int v = 0; v < lut->n_entries; v++)
+            if (lut->table[c][v] >> dbd) {
+                snprintf(buf, sizeof(buf), "table[%d][%d] = %d does not fit %d bits", c, v, lut->table[c][v], dbd); *why = buf; return OH_E_ARG;
+            }
     }
     return OH_OK;
 }

@@ -516,6 +516,141 @@ def filter_taps(h, v):
     return t
 
 
+HIST_BINS = 4096                                                                        # OH_HIST_BINS
+LUT_DEPTHS = (8, 9, 10, 12)
+LUT_ROWS, LUT_UNIT, HG_ROWS = 16, 16, 8                                                 # OH_LUT_ROWS, OH_LUT_UNIT, OH_HG_ROWS (csrc/kernels.h)
+
+
+class OhPlaneHist(C.Structure):                               # include/ohevc_hip.h
+    _fields_ = [("samples", C.c_uint64), ("sum", C.c_uint64), ("sum_sq", C.c_uint64), ("min", C.c_uint32), ("max", C.c_uint32),
+                ("hist", C.c_uint32 * HIST_BINS)]
+
+
+class OhHistogram(C.Structure):                               # include/ohevc_hip.h
+    _fields_ = [("plane", OhPlaneHist * 3)]
+
+
+class OhLut(C.Structure):                                     # include/ohevc_hip.h
+    _fields_ = [("planes", C.c_int32), ("n_entries", C.c_int32), ("table", C.POINTER(C.c_uint16) * 3)]
+
+
+class PlaneHist:
+    """the code values of one plane of a picture (OhPlaneHist): samples, sum, sum_sq, min, max and hist, a numpy uint32 array of
+    2^bit_depth counts; mean and variance derive from the integers and are None for a plane the picture lacks"""
+    __slots__ = ("samples", "sum", "sum_sq", "min", "max", "hist")
+
+    def __init__(self, samples, sum, sum_sq, min, max, hist):
+        self.samples, self.sum, self.sum_sq, self.min, self.max = int(samples), int(sum), int(sum_sq), int(min), int(max)
+        self.hist = np.ascontiguousarray(hist, dtype=np.uint32)
+        if self.hist.ndim != 1 or self.hist.size > HIST_BINS:
+            raise ValueError(f"hist: at most {HIST_BINS} counts in one dimension, not {self.hist.shape}")
+
+    def __repr__(self):
+        return f"PlaneHist(samples={self.samples}, sum={self.sum}, sum_sq={self.sum_sq}, min={self.min}, max={self.max})"
+
+    @property
+    def mean(self):
+        return self.sum / self.samples if self.samples else None
+
+    @property
+    def variance(self):
+        """the population variance, from the integers: (samples sum_sq - sum^2) / samples^2"""
+        return (self.samples * self.sum_sq - self.sum * self.sum) / (self.samples * self.samples) if self.samples else None
+
+    def as_struct(self):
+        h = OhPlaneHist(self.samples, self.sum, self.sum_sq, self.min, self.max)
+        C.memmove(h.hist, self.hist.ctypes.data, 4 * self.hist.size)
+        return h
+
+
+class Histogram:
+    """the code values of one picture (OhHistogram): plane, three PlaneHist (those a 4:0:0 picture lacks are all zero)"""
+    __slots__ = ("plane",)
+
+    def __init__(self, o, bit_depth):
+        self.plane = [PlaneHist(p.samples, p.sum, p.sum_sq, p.min, p.max, np.frombuffer(p.hist, dtype=np.uint32)[:1 << bit_depth].copy())
+                      for p in o.plane]
+
+    def __repr__(self):
+        return f"Histogram({self.plane})"
+
+
+def _levels_chk(rc, what):
+    if rc != 0:
+        err = EngineError(f"{what} failed ({rc})")
+        err.code = rc
+        raise err
+
+
+def _hist_array(hists):
+    """PlaneHist objects (or one) -> (a ctypes array of OhPlaneHist, their number)"""
+    hists = [hists] if isinstance(hists, PlaneHist) else list(hists)
+    return (OhPlaneHist * max(len(hists), 1))(*[h.as_struct() for h in hists]), len(hists)
+
+
+def hist_percentile(hists, ppm):
+    """oh_hist_percentile (host only): the PlaneHist of hists pooled -> the smallest value at or below which ppm millionths of the
+    samples lie; 0 gives the minimum, 1000000 the maximum"""
+    arr, n = _hist_array(hists)
+    v = C.c_uint32()
+    _levels_chk(lib().oh_hist_percentile(arr, n, int(ppm), C.byref(v)), "oh_hist_percentile")
+    return v.value
+
+
+def hist_distance(a, b):
+    """oh_hist_distance (host only): the sum over all values of |a.hist - b.hist| of two PlaneHist, the scene-cut measure"""
+    sad = C.c_uint64()
+    _levels_chk(lib().oh_hist_distance(C.byref(a.as_struct()), C.byref(b.as_struct()), C.byref(sad)), "oh_hist_distance")
+    return sad.value
+
+
+def _lut_built(name, n_entries, *args):
+    """a table builder of the library -> a numpy uint16 array of n_entries values"""
+    out = np.zeros(max(int(n_entries), 1), dtype=np.uint16)
+    _levels_chk(getattr(lib(), name)(*args, out.ctypes.data_as(C.POINTER(C.c_uint16))), name)
+    return out
+
+
+def _lut_entries(bit_depth):
+    """the entries of a table indexed by samples of bit_depth bits; a depth no builder takes makes one entry, and the builder refuses"""
+    return 1 << int(bit_depth) if int(bit_depth) in LUT_DEPTHS else 1
+
+
+def lut_identity(bs, bd):
+    """oh_lut_identity (host only): the table of a plain depth change from bs to bd bits, rounding to nearest"""
+    return _lut_built("oh_lut_identity", _lut_entries(bs), int(bs), int(bd))
+
+
+def lut_range(bs, bd, to_full, chroma=False):
+    """oh_lut_range (host only): limited -> full range (to_full) or full -> limited, of luma or of chroma, from bs to bd bits"""
+    return _lut_built("oh_lut_range", _lut_entries(bs), int(bs), int(bd), int(bool(to_full)), int(bool(chroma)))
+
+
+def lut_linear(bs, bd, gain_q16, pivot_in=0, pivot_out=0):
+    """oh_lut_linear (host only): (v - pivot_in) gain_q16 / 65536 + pivot_out, rounded and clamped to bd bits; 65536 is a gain of 1"""
+    return _lut_built("oh_lut_linear", _lut_entries(bs), int(bs), int(bd), int(gain_q16), int(pivot_in), int(pivot_out))
+
+
+def lut_stretch(hists, bit_depth, lo_ppm=0, hi_ppm=0):
+    """oh_lut_stretch (host only): auto-levels from the pooled PlaneHist of hists: the lo_ppm percentile goes to 0, the value hi_ppm
+    below the top to the maximum"""
+    arr, n = _hist_array(hists)
+    return _lut_built("oh_lut_stretch", _lut_entries(bit_depth), arr, n, int(lo_ppm), int(hi_ppm), int(bit_depth))
+
+
+def lut_equalise(hists, bit_depth):
+    """oh_lut_equalise (host only): the table that equalises the pooled PlaneHist of hists"""
+    arr, n = _hist_array(hists)
+    return _lut_built("oh_lut_equalise", _lut_entries(bit_depth), arr, n, int(bit_depth))
+
+
+def lut_then(first, second):
+    """oh_lut_then (host only): second[first[v]], two tables as one"""
+    first, second = np.ascontiguousarray(first, dtype=np.uint16), np.ascontiguousarray(second, dtype=np.uint16)
+    P = C.POINTER(C.c_uint16)
+    return _lut_built("oh_lut_then", first.size, first.ctypes.data_as(P), first.size, second.ctypes.data_as(P), second.size)
+
+
 def convert_image_bytes(params, cv):
     """oh_convert_image_bytes (host only): bytes of one image, 0 when the combination is not valid"""
     return int(lib().oh_convert_image_bytes(C.byref(params), C.byref(cv)))
@@ -636,6 +771,17 @@ def lib():
         L.oh_filter_median9.restype = C.c_int32
         L.oh_filter_temporal.argtypes = [C.c_int32] * 6
         L.oh_filter_temporal.restype = C.c_int32
+        U16P, HP = C.POINTER(C.c_uint16), C.POINTER(OhPlaneHist)
+        L.oh_pics_histogram.argtypes = [V, IP, I, C.POINTER(OhWindow), C.POINTER(OhHistogram)]
+        L.oh_hist_percentile.argtypes = [HP, I, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.oh_hist_distance.argtypes = [HP, HP, C.POINTER(C.c_uint64)]
+        L.oh_pics_lut.argtypes = [V, IP, IP, I, C.POINTER(OhLut)]
+        L.oh_lut_identity.argtypes = [I, I, U16P]
+        L.oh_lut_range.argtypes = [I, I, I, I, U16P]
+        L.oh_lut_linear.argtypes = [I, I, C.c_int32, C.c_int32, C.c_int32, U16P]
+        L.oh_lut_stretch.argtypes = [HP, I, C.c_uint32, C.c_uint32, I, U16P]
+        L.oh_lut_equalise.argtypes = [HP, I, I, U16P]
+        L.oh_lut_then.argtypes = [U16P, I, U16P, I, U16P]
         L.oh_pics_resize.argtypes = [V, C.POINTER(C.c_int), C.POINTER(C.c_int), I, C.POINTER(OhResize)]
         L.oh_resize_taps.argtypes = [I, I, I, I, C.POINTER(C.c_int32), C.POINTER(C.c_int16), I, C.POINTER(C.c_int)]
         L.oh_resize_max_taps.argtypes = [I, I, I]
@@ -1239,6 +1385,55 @@ class Engine:
         around = self._around(n, prev, next)
         out, made = self._dsts(out, n, "sources", lambda: self._pic_params(pids[0]))
         self._call(self.L.oh_pics_filter(self.h, around[0], IA(*pids), around[1], IA(*out), n, C.byref(ff)), "oh_pics_filter", made)
+        return out
+
+    def pics_histogram(self, pids, *, window=(0, 0, 0, 0)):
+        """the code values of finished pictures counted on the GPU (oh_pics_histogram): a Histogram per picture with a PlaneHist per
+        plane — samples, sum, sum_sq, min, max, mean, variance and hist, the uint32 counts of the 2^bit_depth values; window = (left,
+        right, top, bottom), luma samples.  Waits for the engine stream."""
+        pids = list(pids)
+        n = len(pids)
+        win = OhWindow(*window)
+        out = (OhHistogram * max(n, 1))()
+        self._chk(self.L.oh_pics_histogram(self.h, (C.c_int * max(n, 1))(*pids), n, C.byref(win), out), "oh_pics_histogram")
+        return [Histogram(out[i], self._pic_params(pids[i]).bit_depth) for i in range(n)]
+
+    def pics_lut(self, pids, tables, *, planes=None, bit_depth=None, out=None):
+        """finished pictures -> finished pictures of the same size and chroma format whose samples went through a table
+        (oh_pics_lut): dst = table[src].  tables: one array of 2^(source bit depth) values, which goes to every selected plane, or a
+        sequence of up to three, one per plane, where None means that the plane is copied; planes: bit c set sends plane c through its
+        table (None: every plane that has one).  out: destination pictures to reuse, of any bit depth that holds the tables' values;
+        None allocates pictures with the sources' params, bit_depth replaced where given.  Returns the destination ids.  Enqueued on
+        the engine stream; does not wait; the tables may be changed at once."""
+        pids = list(pids)
+        n = len(pids)
+        one = not isinstance(tables, (list, tuple)) or len(tables) > 3 or any(t is not None and not hasattr(t, "__len__") for t in tables)
+        per_plane = [tables] * 3 if one else (list(tables) + [None] * 3)[:3]
+        per_plane = [None if t is None else np.asarray(t) for t in per_plane]
+        if any(t is not None and (t.ndim != 1 or (t.size and (t.min() < 0 or t.max() > 0xFFFF))) for t in per_plane):
+            raise ValueError("pics_lut: a table has one dimension and values of 16 bits")
+        per_plane = [None if t is None else np.ascontiguousarray(t, dtype=np.uint16) for t in per_plane]
+        sizes = {t.size for t in per_plane if t is not None}
+        if len(sizes) > 1:
+            raise ValueError(f"pics_lut: tables of {sorted(sizes)} entries in one call")
+        if planes is None:
+            planes = sum(1 << c for c, t in enumerate(per_plane) if t is not None)
+        # without any table (every plane copied) the entries are those of the sources' depth, which the library asks for all the same
+        lut = OhLut(int(planes), sizes.pop() if sizes else 1 << self._pic_params(pids[0]).bit_depth if n else 0)
+        for c, t in enumerate(per_plane):
+            if t is not None:
+                lut.table[c] = t.ctypes.data_as(C.POINTER(C.c_uint16))
+        if out is None and n == 0:
+            return []
+
+        def with_depth():
+            dp = F.OhPicParams.from_buffer_copy(self._pic_params(pids[0]))
+            if bit_depth is not None:
+                dp.bit_depth = int(bit_depth)
+            return dp
+
+        out, made = self._dsts(out, n, "sources", with_depth)
+        self._call(self.L.oh_pics_lut(self.h, (C.c_int * max(n, 1))(*pids), (C.c_int * max(n, 1))(*out), n, C.byref(lut)), "oh_pics_lut", made)
         return out
 
     def pics_compose(self, dst, layers, *, fill=None):
