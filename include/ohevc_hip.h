@@ -642,6 +642,73 @@ int oh_lut_stretch(const OhPlaneHist *h, int n, uint32_t lo_ppm, uint32_t hi_ppm
 int oh_lut_equalise(const OhPlaneHist *h, int n, int bd, uint16_t *out);
 int oh_lut_then(const uint16_t *first, int n1, const uint16_t *second, int n2, uint16_t *out);
 
+/* Motion: a block-matching search between two finished pictures and the motion-compensated prediction that such a field describes, in
+ * HEVC's quarter-sample units with HEVC's interpolation filters, so that a vector means what it means to an HEVC decoder (DESIGN.md
+ * §3o; the tests check every field and every plane bit for bit against tests/motion_model.py, which is held against the oracle's
+ * uni-prediction at every fraction).
+ * Definitions.  W x H the coded luma plane, M = 2^bit_depth - 1.  Rows and columns of the reference clamp to the plane (HEVC's
+ * padding), so every vector is defined.  Block (bx, by) of size B is the luma rectangle at (bx B, by B) of B x B samples cut at the
+ * plane's edge (sizes are multiples of 8, so B = 16 leaves blocks 8 wide or high).  P(mv) is the luma prediction of that rectangle
+ * from ref with the vector mv, the uni-predicted samples of H.265 8.5.3.3.3: xInt = x + (mvx >> 2), xFrac = mvx & 3, likewise y; the
+ * 8-tap filters {-1,4,-10,58,17,-5,1,0}, {-1,4,-11,40,40,-11,4,-1}, {0,1,-5,17,58,-10,4,-1} over the columns xInt - 3 .. xInt + 4;
+ * the first stage shifted right by bit_depth - 8; with both fractions non-zero a second stage over eight rows of first-stage values,
+ * shifted right by 6; without any fraction the sample << (14 - bit_depth); that 14-bit value v becomes
+ * min(max((v + 2^(13 - bit_depth)) >> (14 - bit_depth), 0), M).  SAD(mv) = sum |cur - P(mv)| over the rectangle.  With the block's
+ * centre c = (cx, cy) in integer samples and d(mv) = |mvx - 4 cx| + |mvy - 4 cy|: cost(mv) = SAD(mv) + ((lambda d(mv)) >> 2).
+ * Candidates are ordered by the key (cost, d, mvy, mvx), ascending and lexicographic: a total order, so the winner does not depend on
+ * the order of evaluation.
+ *
+ * oh_pics_motion: per pair (cur_ids[i], ref_ids[i]) and block, stage 0 tries the (2 range_x + 1)(2 range_y + 1) integer vectors
+ * 4 (c + (i, j)), |i| <= range_x, |j| <= range_y, and takes the smallest key; with subpel >= 1 stage 1 tries the stage-0 winner +
+ * {-2, 0, 2}^2; with subpel == 2 stage 2 tries the stage-1 winner + {-1, 0, 1}^2.  out[(i bh + by) bw + bx] (bw, bh:
+ * oh_motion_blocks) receives the winner, its SAD and SAD(4 c).  Only luma is searched.  All pictures have identical params; a picture
+ * may appear in many pairs and as both members of one.  Nothing is written to pictures.  centres: per pair and block (cx, cy), int16,
+ * in the order of out; copied by the call through a pinned buffer onto the engine stream.  Reads finished halves on the engine stream,
+ * waits for it and fills out on the host.  More than OH_CONV_MAX_PICS pairs are split into several launches.  n == 0: OH_OK (ms is
+ * checked all the same, but for the centres, of which there are none).
+ * OH_E_ARG, out untouched: a null e, ms, out or id array, a negative n; an unknown picture; params that differ; block other than 8 or
+ * 16; a range outside 0 .. OH_MOTION_MAX_RANGE; subpel outside 0 .. 2; lambda outside 0 .. OH_MOTION_MAX_LAMBDA; a centre component
+ * beyond +-OH_MOTION_MAX_CENTRE.  No combination gives OH_E_UNSUPPORTED.
+ *
+ * oh_pics_motion_compensate: n finished ref pictures become n finished dst pictures of identical params.  field: n bw bh vectors in
+ * the order of out above, of which only x and y are read; any int16 value is legal.  Luma of block (bx, by) of dst is P(its vector).
+ * Each chroma plane of the block is the rectangle divided by SubWidthC / SubHeightC, predicted by H.265 8.5.3.3.3 chroma (hs / vs =
+ * oh_hshift / oh_vshift): xIntC = xC + (mvx >> (2 + hs)), the eighth-sample fraction (mvx & ((4 << hs) - 1)) << (1 - hs), likewise y
+ * with vs; the 4-tap filters {-2,58,10,-2}, {-4,54,16,-2}, {-6,46,28,-4}, {-4,36,36,-4} and their mirror images over the columns
+ * xIntC - 1 .. xIntC + 2, the stages, shifts and rounding of luma.  A 4:0:0 picture has no chroma.  Writes half 0 of each destination
+ * and marks it finished; enqueued on the engine stream, returns without waiting, like oh_pics_filter.  The field is copied by the
+ * call.  A zero field gives a copy of ref.  n == 0: OH_OK (block is checked all the same).
+ * OH_E_ARG, nothing written: a null e, field or id array, a negative n; an unknown picture; params that differ; a destination that is
+ * also a source, or listed twice; block other than 8 or 16. */
+enum { OH_MOTION_MAX_RANGE = 32, OH_MOTION_MAX_CENTRE = 4096, OH_MOTION_MAX_LAMBDA = 4096 };
+typedef struct OhMotionVector { int16_t x, y;        /* quarter luma samples, HEVC's mvLX */
+                                uint32_t sad;        /* SAD of the winner */
+                                uint32_t sad_centre; /* SAD at the block's search centre (integer vector) */ } OhMotionVector;
+typedef struct OhMotionSearch {
+    int32_t block;            /* 8 or 16 */
+    int32_t range_x, range_y; /* 0 .. OH_MOTION_MAX_RANGE, integer samples either side of the centre */
+    int32_t subpel;           /* 0 integer, 1 half, 2 quarter */
+    int32_t lambda;           /* 0 .. OH_MOTION_MAX_LAMBDA */
+    const int16_t *centres;   /* NULL (all zero) or HOST array: per pair, per block, (cx, cy) in integer samples, |c| <= OH_MOTION_MAX_CENTRE */
+} OhMotionSearch;
+int oh_motion_blocks(int width, int height, int block, int *bw, int *bh);       /* host only: ceil(W / block), ceil(H / block) */
+int oh_pics_motion(OhEngine *e, const int *cur_ids, const int *ref_ids, int n, const OhMotionSearch *ms, OhMotionVector *out);
+int oh_pics_motion_compensate(OhEngine *e, const int *ref_ids, const int *dst_ids, int n, int block, const OhMotionVector *field);
+/* host only, coarse to fine: a field searched with blocks of block_c on pictures reduced by the integer factor s in {1, 2, 4, 8}
+ * (bwc x bhc blocks) becomes the search centres of a grid of bw x bh blocks of block_f on the full pictures.  Fine block (bx, by)
+ * takes the coarse block (min(bx block_f / (s block_c), bwc - 1), min(by block_f / (s block_c), bhc - 1)); its centre is
+ * (s mv + 2) >> 2 per component (an arithmetic shift), clamped to +-OH_MOTION_MAX_CENTRE; centres: 2 bw bh int16, (cx, cy) per block.
+ * OH_E_ARG, centres untouched: a null pointer, a size below 1, another s, a block size other than 8 or 16. */
+int oh_motion_scale(const OhMotionVector *coarse, int bwc, int bhc, int block_c, int s, int bw, int bh, int block_f, int16_t *centres);
+/* host only: the formulas above as the kernels evaluate them (csrc/motion_common.h).  oh_motion_qpel: win the 8 x 8 reference
+ * samples of rows yInt - 3 .. yInt + 4 and columns xInt - 3 .. xInt + 4, row by row; fx, fy in 0 .. 3.  oh_motion_epel: win the 4 x 4
+ * samples of rows yIntC - 1 .. yIntC + 2 and columns xIntC - 1 .. xIntC + 2; fx, fy in 0 .. 7.  Both return the predicted sample, or
+ * -1 for a null window, a fraction outside its range or a bit depth other than 8, 9, 10, 12.  oh_motion_cost: sad + ((lambda d) >> 2)
+ * of the vector (mvx, mvy) around the centre (cx, cy), in 64 bits so that it is defined for every argument. */
+int32_t oh_motion_qpel(const uint16_t win[64], int fx, int fy, int bit_depth);
+int32_t oh_motion_epel(const uint16_t win[16], int fx, int fy, int bit_depth);
+uint64_t oh_motion_cost(uint32_t sad, int mvx, int mvy, int cx, int cy, int lambda);
+
 /* SHVC inter-layer reference picture: resample the finished base-layer picture src_pic into
  * the enhancement-layer picture dst_pic, bit-exact with the reference's whole-picture slot
  * HEVCDSPContext.upsample_base_layer_frame (hevcdsp_template.c:2164-2438, call site hevc.c:3241).

@@ -167,6 +167,9 @@ struct OhEngine {
     Scratch     hist_res;                /* oh_pics_histogram: the bins of the call in HBM */
     Scratch     lut_tabs;                /* oh_pics_lut: the three tables of the last call (3 x OH_LUT_MAX uint16), rewritten on the stream
                                           * behind the launches that read them */
+    Scratch     motion_res;              /* oh_pics_motion: the vectors of the call in HBM */
+    Scratch     motion_centres;          /* oh_pics_motion: the centres of the call, rewritten on the stream behind the launches that read them */
+    Scratch     motion_field;            /* oh_pics_motion_compensate: the vectors of the call, likewise */
     Scratch     compose_dev;           /* oh_pics_compose: the layer table of the call (OhCpsLayer, then OhCpsSrc per launch set) */
     uint32_t    spin_limit = 1u << 22;   /* polls (with s_sleep between them, ~1 s in all) before a waiting workgroup gives up; OHEVC_SPIN_LIMIT */
 };

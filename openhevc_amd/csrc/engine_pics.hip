@@ -1519,6 +1519,112 @@ extern "C" int oh_pics_lut(OhEngine *e, const int *src_ids, const int *dst_ids, 
     return OH_OK;
 }
 
+/* ---------------- motion search and compensation (motion.hip) ---------------- */
+/* a host list of the call in device scratch s, in front of the launches that follow: staged in a pinned buffer of the pool and copied on
+ * the engine stream, behind the launches of an earlier call that read the device copy.  Growing the scratch frees the old block, which
+ * waits for the device */
+static int list_to_device(OhEngine *e, const char *who, OhEngine::Scratch *s, const void *list, size_t bytes)
+{
+    { const int rc = scratch_reserve(e, s, bytes); if (rc) return rc; }
+    OhEngine::Stage *sg = stage_list(e, list, bytes);
+    if (!sg)
+        FAIL(e, OH_E_NOMEM, "%s: no staging buffer for %zu bytes of vectors", who, bytes);
+    HIPCHK(e, hipMemcpyAsync(s->p, sg->p, bytes, hipMemcpyHostToDevice, e->stream));
+    return stage_in_use(e, sg, e->stream);
+}
+
+extern "C" int oh_pics_motion(OhEngine *e, const int *cur_ids, const int *ref_ids, int n, const OhMotionSearch *ms, OhMotionVector *out)
+{
+    const char *who = "oh_pics_motion";
+    if (!e || n < 0 || !ms || !out || (n && (!cur_ids || !ref_ids)))
+        return OH_E_ARG;
+    std::string why;
+    if (motion_check(ms, 0, &why))
+        FAIL(e, OH_E_ARG, "%s: %s", who, why.c_str());
+    if (!n)
+        return OH_OK;
+    std::vector<int> all(cur_ids, cur_ids + n);
+    all.insert(all.end(), ref_ids, ref_ids + n);
+    const Pic *p0 = alike_pics(e, who, all.data(), 2 * n);
+    if (!p0) return OH_E_ARG;
+    const OhPicParams &p = p0->p;
+    OhMoSearchArgs a;
+    memset(&a, 0, sizeof(a));
+    a.w = p0->w[0]; a.h = p0->h[0]; a.bd = p.bit_depth;
+    a.block = ms->block;
+    (void)oh_motion_blocks(a.w, a.h, a.block, &a.bw, &a.bh);
+    const size_t per_pair = (size_t)a.bw * a.bh;
+    if (motion_check(ms, (size_t)n * per_pair, &why))
+        FAIL(e, OH_E_ARG, "%s: %s", who, why.c_str());
+    HIPCHK(e, hipSetDevice(e->device));
+    int32_t pitch[3];
+    row_pitches(p0, 1, pitch);
+    a.pitch = pitch[0];
+    a.rx = ms->range_x; a.ry = ms->range_y; a.subpel = ms->subpel; a.lambda = ms->lambda;
+    if (ms->centres) {
+        const int rc = list_to_device(e, who, &e->motion_centres, ms->centres, (size_t)n * per_pair * sizeof(OhMoVec));
+        if (rc) return rc;
+    }
+    const size_t bytes = (size_t)n * per_pair * sizeof(OhMoDev);
+    OhEngine::Stage *sg = nullptr;
+    { const int rc = results_begin(e, who, &e->motion_res, bytes, n, &sg); if (rc) return rc; }
+    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
+        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+        for (int i = 0; i < m; i++) {
+            a.cur[i] = final_planes(get_pic(e, cur_ids[i0 + i]))[0];
+            a.ref[i] = final_planes(get_pic(e, ref_ids[i0 + i]))[0];
+        }
+        a.centres = ms->centres ? (const OhMoVec *)e->motion_centres.p + (size_t)i0 * per_pair : nullptr;
+        a.res = (OhMoDev *)e->motion_res.p + (size_t)i0 * per_pair;
+        ohk_motion_search(&a, m, e->stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    { const int rc = results_fetch(e, &e->motion_res, bytes, sg); if (rc) return rc; }
+    memcpy(out, sg->p, bytes);
+    return OH_OK;
+}
+
+extern "C" int oh_pics_motion_compensate(OhEngine *e, const int *ref_ids, const int *dst_ids, int n, int block, const OhMotionVector *field)
+{
+    const char *who = "oh_pics_motion_compensate";
+    if (!e || n < 0 || !field || (n && (!ref_ids || !dst_ids)))
+        return OH_E_ARG;
+    if (block != 8 && block != 16)
+        FAIL(e, OH_E_ARG, "%s: block %d (8 or 16)", who, block);
+    if (!n)
+        return OH_OK;
+    const Pic *p0 = alike_apart(e, who, std::vector<int>(ref_ids, ref_ids + n), dst_ids, n);
+    if (!p0) return OH_E_ARG;
+    const OhPicParams &p = p0->p;
+    HIPCHK(e, hipSetDevice(e->device));
+    OhMoCompArgs a;
+    memset(&a, 0, sizeof(a));
+    a.np = n_planes(p); a.bd = p.bit_depth;
+    a.hs = oh_hshift(&p, 1); a.vs = oh_vshift(&p, 1);
+    row_pitches(p0, a.np, a.pitch);
+    class_sizes(p0, a.np, a.w, a.h);
+    a.block = block;
+    (void)oh_motion_blocks(a.w[0], a.h[0], block, &a.bw, &a.bh);
+    const size_t per_pic = (size_t)a.bw * a.bh;
+    {   /* the x and y of the field: what the kernel reads */
+        std::vector<OhMoVec> xy((size_t)n * per_pic);
+        for (size_t i = 0; i < xy.size(); i++) { xy[i].x = field[i].x; xy[i].y = field[i].y; }
+        const int rc = list_to_device(e, who, &e->motion_field, xy.data(), xy.size() * sizeof(OhMoVec));
+        if (rc) return rc;
+    }
+    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
+        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+        for (int i = 0; i < m; i++) {
+            read_planes(get_pic(e, ref_ids[i0 + i]), a.np, a.ref[i]);
+            write_planes(get_pic(e, dst_ids[i0 + i]), a.np, a.dst[i]);
+        }
+        a.field = (const OhMoVec *)e->motion_field.p + (size_t)i0 * per_pic;
+        ohk_motion_compensate(&a, m, e->stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    return OH_OK;
+}
+
 extern "C" int oh_pic_device_planes(OhEngine *e, int pic_id, void *planes[3], int32_t stride[3], int32_t width[3], int32_t height[3])
 {
     if (!e)

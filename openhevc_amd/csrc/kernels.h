@@ -243,6 +243,33 @@ struct OhLutArgs {
     int32_t         planes;          /* bit c set: plane c goes through its table; clear: it is copied (sbd == dbd) */
 };
 
+/* motion search and compensation (motion.hip): the finished planes of the pictures of one launch by value in the kernel
+ * arguments; every picture of a launch has the same geometry.  The centres, the field and the results of the launch's first picture lie
+ * in device memory that the engine owns and fills or clears on the stream in front of the launch. */
+enum { OH_MO_REACH = 4 };            /* reference samples beyond the integer range on either side that the sub-sample stages may read:
+                                        three quarters further, and the 8-tap filter's three before and four behind */
+struct OhMoVec { int16_t x, y; };    /* a vector (quarter samples) of a field, or a centre (integer samples) */
+struct OhMoDev { int16_t x, y; uint32_t sad, sad_centre; };  /* OhMotionVector */
+struct OhMoSearchArgs {
+    const void    *cur[64], *ref[64];/* OH_CONV_MAX_PICS pairs: the finished luma planes */
+    const OhMoVec *centres;          /* [pair][bh][bw], or null: all zero */
+    OhMoDev       *res;              /* [pair][bh][bw] */
+    int32_t        pitch;            /* bytes between luma rows */
+    int32_t        w, h, bd;         /* coded luma size, bit depth */
+    int32_t        block, bw, bh;    /* 8 or 16; blocks across and down */
+    int32_t        rx, ry, subpel, lambda;
+};
+struct OhMoCompArgs {
+    const void    *ref[64][3];       /* OH_CONV_MAX_PICS pictures x planes: the finished halves */
+    void          *dst[64][3];       /* half 0 of the destinations */
+    const OhMoVec *field;            /* [picture][bh][bw] */
+    int32_t        pitch[3];         /* bytes between rows of each plane */
+    int32_t        w[2], h[2];       /* coded size of the planes */
+    int32_t        hs, vs;           /* oh_hshift / oh_vshift of the chroma planes */
+    int32_t        np, bd;           /* planes: 1 or 3; bit depth */
+    int32_t        block, bw, bh;
+};
+
 /* picture resizing (resize.hip): what one launch set needs, by value in the kernel arguments like OhConvArgs.  Two plane
  * classes (0 luma, 1 chroma), each with its own geometry and tap tables; the tables live in device memory that the engine owns and
  * fills (engine_pics.hip: oh_pics_resize, from pics_math.hip: oh_resize_taps) on the stream in front of the launches. */
@@ -308,6 +335,10 @@ void ohk_filter(const OhFilterArgs *a, int n, hipStream_t st);
 void ohk_histogram(const OhHistArgs *a, int n, hipStream_t st);
 /* n sources of a.src through a.tab into the n destinations of a.dst */
 void ohk_lut(const OhLutArgs *a, int n, hipStream_t st);
+/* the blocks of n pairs of a.cur / a.ref searched into a.res[0 .. n bw bh) */
+void ohk_motion_search(const OhMoSearchArgs *a, int n, hipStream_t st);
+/* n pictures of a.ref compensated by a.field[0 .. n bw bh) into the n destinations of a.dst */
+void ohk_motion_compensate(const OhMoCompArgs *a, int n, hipStream_t st);
 void ohk_hash(int kind,const OhMd5Job *jobs, const uint32_t *first, const uint32_t *task_map, int n_jobs, int n_tasks, uint32_t *partials,
               uint32_t *out, hipStream_t st);
 void ohk_inter(const OhBatch *B, int n, const OhPicParams *p, uint32_t max_luma, uint32_t max_chroma, hipStream_t st);

@@ -16,6 +16,7 @@
 #include "reformat_common.h"
 #include "deinterlace_common.h"
 #include "filter_common.h"
+#include "motion_common.h"
 
 static bool depth_ok(int bit_depth) { return bit_depth == 8 || bit_depth == 9 || bit_depth == 10 || bit_depth == 12; }
 
@@ -924,5 +925,76 @@ int lut_check(const OhLut *lut, int sbd, int dbd, int np, std::string *why)
                 snprintf(buf, sizeof(buf), "table[%d][%d] = %d does not fit %d bits", c, v, lut->table[c][v], dbd); *why = buf; return OH_E_ARG;
             }
     }
+    return OH_OK;
+}
+
+/* ---------------- motion: the host-only helpers and what oh_pics_motion checks ---------------- */
+static bool block_ok(int block) { return block == 8 || block == 16; }
+
+extern "C" int oh_motion_blocks(int width, int height, int block, int *bw, int *bh)
+{
+    if (width < 1 || height < 1 || !block_ok(block) || !bw || !bh)
+        return OH_E_ARG;
+    *bw = (width + block - 1) / block; *bh = (height + block - 1) / block;
+    return OH_OK;
+}
+
+extern "C" int oh_motion_scale(const OhMotionVector *coarse, int bwc, int bhc, int block_c, int s, int bw, int bh, int block_f, int16_t *centres)
+{
+    if (!coarse || !centres || bwc < 1 || bhc < 1 || bw < 1 || bh < 1 || !block_ok(block_c) || !block_ok(block_f) ||
+        (s != 1 && s != 2 && s != 4 && s != 8))
+        return OH_E_ARG;
+    for (int by = 0; by < bh; by++)
+        for (int bx = 0; bx < bw; bx++) {
+            const int64_t span = (int64_t)s * block_c;
+            const int64_t qx = std::min<int64_t>((int64_t)bx * block_f / span, bwc - 1), qy = std::min<int64_t>((int64_t)by * block_f / span, bhc - 1);
+            const OhMotionVector &v = coarse[qy * bwc + qx];
+            const int comp[2] = { v.x, v.y };
+            for (int k = 0; k < 2; k++)
+                centres[2 * ((size_t)by * bw + bx) + k] =
+                    (int16_t)std::min(std::max((s * comp[k] + 2) >> 2, -(int)OH_MOTION_MAX_CENTRE), (int)OH_MOTION_MAX_CENTRE);
+        }
+    return OH_OK;
+}
+
+extern "C" int32_t oh_motion_qpel(const uint16_t win[64], int fx, int fy, int bit_depth)
+{
+    if (!win || fx < 0 || fx > 3 || fy < 0 || fy > 3 || !depth_ok(bit_depth))
+        return -1;
+    return motion_sample<8>(win, 8, fx, fy, bit_depth);
+}
+
+extern "C" int32_t oh_motion_epel(const uint16_t win[16], int fx, int fy, int bit_depth)
+{
+    if (!win || fx < 0 || fx > 7 || fy < 0 || fy > 7 || !depth_ok(bit_depth))
+        return -1;
+    return motion_sample<4>(win, 4, fx, fy, bit_depth);
+}
+
+extern "C" uint64_t oh_motion_cost(uint32_t sad, int mvx, int mvy, int cx, int cy, int lambda)
+{
+    const int64_t dx = (int64_t)mvx - 4 * (int64_t)cx, dy = (int64_t)mvy - 4 * (int64_t)cy;
+    const int64_t d = (dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy);
+    return (uint64_t)((int64_t)sad + (((int64_t)lambda * d) >> 2));
+}
+
+/* what oh_pics_motion checks of the OhMotionSearch itself; n_centres: the (cx, cy) pairs the call reads of ms->centres, if it has any */
+int motion_check(const OhMotionSearch *ms, size_t n_centres, std::string *why)
+{
+    char buf[256];
+    if (!block_ok(ms->block)) { snprintf(buf, sizeof(buf), "block %d (8 or 16)", ms->block); *why = buf; return OH_E_ARG; }
+    if (ms->range_x < 0 || ms->range_x > OH_MOTION_MAX_RANGE || ms->range_y < 0 || ms->range_y > OH_MOTION_MAX_RANGE) {
+        snprintf(buf, sizeof(buf), "range %d x %d outside 0 .. %d", ms->range_x, ms->range_y, OH_MOTION_MAX_RANGE); *why = buf; return OH_E_ARG;
+    }
+    if (ms->subpel < 0 || ms->subpel > 2) { snprintf(buf, sizeof(buf), "subpel %d (0 integer, 1 half, 2 quarter)", ms->subpel); *why = buf; return OH_E_ARG; }
+    if (ms->lambda < 0 || ms->lambda > OH_MOTION_MAX_LAMBDA) {
+        snprintf(buf, sizeof(buf), "lambda %d outside 0 .. %d", ms->lambda, OH_MOTION_MAX_LAMBDA); *why = buf; return OH_E_ARG;
+    }
+    if (ms->centres)
+        for (size_t i = 0; i < 2 * n_centres; i++)
+            if (ms->centres[i] < -OH_MOTION_MAX_CENTRE || ms->centres[i] > OH_MOTION_MAX_CENTRE) {
+                snprintf(buf, sizeof(buf), "centre %zu is (%d, %d): beyond %d", i / 2, ms->centres[i & ~(size_t)1], ms->centres[i | 1], OH_MOTION_MAX_CENTRE);
+                *why = buf; return OH_E_ARG;
+            }
     return OH_OK;
 }

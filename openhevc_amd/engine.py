@@ -516,6 +516,64 @@ def filter_taps(h, v):
     return t
 
 
+MOTION_MAX_RANGE, MOTION_MAX_CENTRE, MOTION_MAX_LAMBDA = 32, 4096, 4096                  # OH_MOTION_MAX_*
+
+
+class OhMotionVector(C.Structure):                            # include/ohevc_hip.h
+    _fields_ = [("x", C.c_int16), ("y", C.c_int16), ("sad", C.c_uint32), ("sad_centre", C.c_uint32)]
+
+
+class OhMotionSearch(C.Structure):                            # include/ohevc_hip.h
+    _fields_ = [("block", C.c_int32), ("range_x", C.c_int32), ("range_y", C.c_int32), ("subpel", C.c_int32), ("lam", C.c_int32),
+                ("centres", C.POINTER(C.c_int16))]
+
+
+MOTION_DTYPE = np.dtype([("x", np.int16), ("y", np.int16), ("sad", np.uint32), ("sad_centre", np.uint32)])     # OhMotionVector
+
+
+def _motion_chk(rc, what):
+    if rc != 0:
+        err = EngineError(f"{what} failed ({rc})")
+        err.code = rc
+        raise err
+
+
+def motion_blocks(width, height, block=16):
+    """oh_motion_blocks (host only): (bw, bh), the blocks of `block` samples across and down a coded luma plane of width x height"""
+    bw, bh = C.c_int(0), C.c_int(0)
+    _motion_chk(lib().oh_motion_blocks(int(width), int(height), int(block), C.byref(bw), C.byref(bh)), f"oh_motion_blocks({width}, {height}, {block})")
+    return bw.value, bh.value
+
+
+def motion_field(field):
+    """a field of vectors as a C-contiguous array of MOTION_DTYPE: a structured array as pics_motion returns it, or an integer array whose
+    last axis holds (x, y)"""
+    f = np.asarray(field)
+    if f.dtype == MOTION_DTYPE:
+        return np.ascontiguousarray(f)
+    if f.dtype.names is not None or f.ndim < 1 or f.shape[-1] != 2 or f.dtype.kind not in "iu":
+        raise ValueError("a field is an array of MOTION_DTYPE or an integer array of (x, y) pairs")
+    if f.size and (f.min() < -32768 or f.max() > 32767):
+        raise ValueError("a vector component is an int16")
+    out = np.zeros(f.shape[:-1], dtype=MOTION_DTYPE)
+    out["x"], out["y"] = f[..., 0], f[..., 1]
+    return out
+
+
+def motion_scale(coarse, block_c, s, grid, block_f):
+    """oh_motion_scale (host only), coarse to fine: coarse, the (bhc, bwc) field of one pair searched with blocks of block_c on pictures
+    reduced by the integer factor s (1, 2, 4, 8), becomes the int16 search centres (bh, bw, 2) of the grid = (bw, bh) of blocks of
+    block_f on the full pictures: fine block (bx, by) takes the coarse block under it, its centre is (s mv + 2) >> 2 per component"""
+    coarse = motion_field(coarse)
+    if coarse.ndim != 2:
+        raise ValueError(f"motion_scale: the field of one pair has the shape (bh, bw), not {coarse.shape}")
+    bw, bh = int(grid[0]), int(grid[1])
+    out = np.zeros((max(bh, 0), max(bw, 0), 2), dtype=np.int16)
+    _motion_chk(lib().oh_motion_scale(coarse.ctypes.data_as(C.POINTER(OhMotionVector)), coarse.shape[1], coarse.shape[0], int(block_c), int(s), bw, bh,
+                                      int(block_f), out.ctypes.data_as(C.POINTER(C.c_int16))), "oh_motion_scale")
+    return out
+
+
 HIST_BINS = 4096                                                                        # OH_HIST_BINS
 LUT_DEPTHS = (8, 9, 10, 12)
 LUT_ROWS, LUT_UNIT, HG_ROWS = 16, 16, 8                                                 # OH_LUT_ROWS, OH_LUT_UNIT, OH_HG_ROWS (csrc/kernels.h)
@@ -782,6 +840,17 @@ def lib():
         L.oh_lut_stretch.argtypes = [HP, I, C.c_uint32, C.c_uint32, I, U16P]
         L.oh_lut_equalise.argtypes = [HP, I, I, U16P]
         L.oh_lut_then.argtypes = [U16P, I, U16P, I, U16P]
+        MVP = C.POINTER(OhMotionVector)
+        L.oh_motion_blocks.argtypes = [I, I, I, IP, IP]
+        L.oh_pics_motion.argtypes = [V, IP, IP, I, C.POINTER(OhMotionSearch), MVP]
+        L.oh_pics_motion_compensate.argtypes = [V, IP, IP, I, I, MVP]
+        L.oh_motion_scale.argtypes = [MVP, I, I, I, I, I, I, I, C.POINTER(C.c_int16)]
+        L.oh_motion_qpel.argtypes = [U16P, I, I, I]
+        L.oh_motion_qpel.restype = C.c_int32
+        L.oh_motion_epel.argtypes = [U16P, I, I, I]
+        L.oh_motion_epel.restype = C.c_int32
+        L.oh_motion_cost.argtypes = [C.c_uint32, I, I, I, I, I]
+        L.oh_motion_cost.restype = C.c_uint64
         L.oh_pics_resize.argtypes = [V, C.POINTER(C.c_int), C.POINTER(C.c_int), I, C.POINTER(OhResize)]
         L.oh_resize_taps.argtypes = [I, I, I, I, C.POINTER(C.c_int32), C.POINTER(C.c_int16), I, C.POINTER(C.c_int)]
         L.oh_resize_max_taps.argtypes = [I, I, I]
@@ -1385,6 +1454,61 @@ class Engine:
         around = self._around(n, prev, next)
         out, made = self._dsts(out, n, "sources", lambda: self._pic_params(pids[0]))
         self._call(self.L.oh_pics_filter(self.h, around[0], IA(*pids), around[1], IA(*out), n, C.byref(ff)), "oh_pics_filter", made)
+        return out
+
+    def pics_motion(self, cur, ref, block=16, range=(8, 8), subpel=2, lam=0, centres=None):
+        """block-matching motion search between finished pictures on the GPU (oh_pics_motion; the exact definition is in
+        include/ohevc_hip.h): per pair (cur[i], ref[i]) and luma block of `block` samples the vector, in HEVC's quarter samples, that
+        predicts the block of cur from ref with the smallest (cost, d, y, x), cost = SAD + ((lam d) >> 2).  range = (x, y) integer
+        samples either side of the centre, subpel 0 integer / 1 half / 2 quarter, centres: None or the int16 (cx, cy) per pair and block,
+        shape (n, bh, bw, 2).  Returns a numpy structured array of shape (n, bh, bw) with the fields x, y, sad, sad_centre.  Waits for
+        the engine stream."""
+        cur, ref = list(cur), list(ref)
+        n = len(cur)
+        if len(ref) != n:
+            raise ValueError(f"pics_motion: {n} pictures against {len(ref)}")
+        ms = OhMotionSearch(int(block), int(range[0]), int(range[1]), int(subpel), int(lam))
+        bw = bh = 0
+        if n and cur[0] in self._params and int(block) in (8, 16):
+            p = self._pic_params(cur[0])
+            bw, bh = motion_blocks(p.width, p.height, block)
+        if centres is not None:
+            c = np.asarray(centres)
+            if c.shape != (n, bh, bw, 2) or c.dtype.kind not in "iu":
+                raise ValueError(f"pics_motion: centres of shape {c.shape}, not {(n, bh, bw, 2)} integers")
+            if c.size and (c.min() < -32768 or c.max() > 32767):
+                raise ValueError("pics_motion: a centre component is an int16")
+            c = np.ascontiguousarray(c, dtype=np.int16)
+            # without pairs there is nothing to read, but a non-null pointer all the same
+            ms.centres = (c if c.size else np.zeros(2, np.int16)).ctypes.data_as(C.POINTER(C.c_int16))
+        out = np.zeros((n, bh, bw), dtype=MOTION_DTYPE)
+        buf = out if out.size else np.zeros(1, dtype=MOTION_DTYPE)
+        IA = C.c_int * max(n, 1)
+        self._chk(self.L.oh_pics_motion(self.h, IA(*cur), IA(*ref), n, C.byref(ms), buf.ctypes.data_as(C.POINTER(OhMotionVector))), "oh_pics_motion")
+        return out
+
+    def pics_motion_compensate(self, ref, field, block=16, out=None):
+        """finished pictures -> their motion-compensated predictions, finished pictures of the same params (oh_pics_motion_compensate;
+        the exact definition is in include/ohevc_hip.h): luma block (bx, by) of destination i is ref[i] displaced by field[i, by, bx]
+        with HEVC's luma interpolation, its chroma by the same vector with the chroma interpolation.  field: what pics_motion returned,
+        or an integer array (n, bh, bw, 2) of (x, y) in quarter luma samples.  out: destination pictures to reuse; None allocates
+        pictures with the sources' params.  Returns the destination ids.  Enqueued on the engine stream; does not wait; the field may
+        be changed at once."""
+        ref = list(ref)
+        n = len(ref)
+        if n == 0:
+            raise ValueError("pics_motion_compensate needs at least one picture (the destinations follow the pictures' params)")
+        f = motion_field(field)
+        if int(block) in (8, 16):
+            p = self._pic_params(ref[0])
+            bw, bh = motion_blocks(p.width, p.height, block)
+            if f.shape != (n, bh, bw):
+                raise ValueError(f"pics_motion_compensate: a field of shape {f.shape}, not {(n, bh, bw)}")
+        IA = C.c_int * n
+        out, made = self._dsts(out, n, "sources", lambda: self._pic_params(ref[0]))
+        buf = f if f.size else np.zeros(1, dtype=MOTION_DTYPE)
+        self._call(self.L.oh_pics_motion_compensate(self.h, IA(*ref), IA(*out), n, int(block), buf.ctypes.data_as(C.POINTER(OhMotionVector))),
+                   "oh_pics_motion_compensate", made)
         return out
 
     def pics_histogram(self, pids, *, window=(0, 0, 0, 0)):
