@@ -435,6 +435,97 @@ int oh_orient_size(int orientation, int w, int h, int *ow, int *oh);
  * needs a resampler.  OH_E_ARG: a null pointer, a flag outside 0 / 1, a rotation of 2^16 or more. */
 int oh_orient_from_sei(int hor_flip, int ver_flip, uint32_t anticlockwise_rotation, int *orientation);
 
+/* Warping of finished pictures (DESIGN.md §3p has the exact definition, which the tests check bit for bit against
+ * tests/warp_model.py): n finished pictures become n finished pictures resampled through one affine or perspective coordinate map —
+ * rotation by any angle, shear, keystone correction, a stabilising shift, rotate-and-scale augmentation, the display-orientation SEI
+ * at any angle — without leaving YUV.  Every sample is an exact integer.
+ *
+ * m is the INVERSE map, destination -> source, in luma samples: integer coordinates are sample positions, the top-left luma sample of
+ * the source window is (0, 0) and so is the image's.
+ *   m[0] m[1] m[3] m[4]   Q16, |.| <= 2^22          x_src = (m0 x + m1 y + m2) / W      W = 1 (affine)
+ *   m[2] m[5]             Q16, |.| <= 2^36          y_src = (m3 x + m4 y + m5) / W      W = (m6 x + m7 y + m8) / 2^30 (perspective)
+ *   m[6] m[7]             Q30 per sample, |.| <= 2^26
+ *   m[8]                  Q30, 0 < m[8] <= 2^36; 2^30 when the map is affine
+ * OH_WARP_AFFINE ignores m[6 .. 8].  Sample (x, y) of plane c of the image (shifts hs, vs; h = vs) has the luma position X = x << hs,
+ * Y = y << vs and half a luma row more where vs = 1 (chroma_sample_loc_type 0, as in oh_pics_resize); in int64_t, >> flooring:
+ *   Nx = m0 X + m1 Y + m2 + h (m1 >> 1),  Ny = m3 X + m4 Y + m5 + h (m4 >> 1),  D = m6 X + m7 Y + m8 + h (m7 >> 1)
+ *   affine Lx = Nx; perspective Lx = floor(Nx 2^22 / (D >> 8)); Ly likewise; both clamped to [-2^30, 2^31 - 1]
+ *   Px = Lx >> hs, Py = (Ly - vs 2^15) >> vs                                            the position in the plane's window, Q16
+ *   NEAREST: ix = (Px + 2^15) >> 16;  else Qx = (Px + 512) >> 10, ix = Qx >> 6, fx = Qx & 63 (1/64 sample); y likewise.
+ * A tap at plane index (i, j) of the plane's window of Wc x Hc samples: OH_WARP_REPLICATE clamps i to 0 .. Wc - 1 and j to
+ * 0 .. Hc - 1; OH_WARP_CONSTANT gives fill[c] where i or j is outside.  Nothing outside the window is ever read.
+ *   NEAREST   s(ix, iy)
+ *   BILINEAR  t_j = (64 - fx) s(ix, j) + fx s(ix + 1, j), j = iy, iy + 1;  v = ((64 - fy) t_iy + fy t_(iy+1) + 2^11) >> 12
+ *   BICUBIC   Keys, a = -1/2, 64 phases, taps c[f][0 .. 3] that sum to 1024 (oh_warp_cubic), at ix - 1 .. ix + 2, iy - 1 .. iy + 2:
+ *             t_j = (sum_k c[fx][k] s(ix - 1 + k, j) + 8) >> 4;  v = clip((sum_j c[fy][j] t_j + 2^15) >> 16, 0, 2^bd - 1)
+ * No anti-aliasing: a map that shrinks is point-sampled; oh_pics_resize is the call for scaling down.  The image takes the top left
+ * width x height of each destination; the rest of the destination's coded planes replicates its last column and row. */
+enum { OH_WARP_AFFINE = 0, OH_WARP_PERSPECTIVE };
+enum { OH_WARP_NEAREST = 0, OH_WARP_BILINEAR, OH_WARP_BICUBIC };
+enum { OH_WARP_REPLICATE = 0, OH_WARP_CONSTANT };
+typedef struct OhWarp {
+    int32_t  mode, filter, border;
+    uint16_t fill[3];        /* code values per plane, OH_WARP_CONSTANT only */
+    OhWindow win;            /* source window, luma samples, rules as for oh_pics_convert; nothing outside it is ever read */
+    int32_t  width, height;  /* image size inside the destinations, luma samples */
+    int64_t  m[9];           /* INVERSE map, destination -> source */
+} OhWarp;
+/* The n sources with identical OhPicParams, the n destinations with identical params, of the sources' bit depth and chroma format.
+ * Reads each source's finished half, writes half 0 of each destination and marks it finished, like oh_pics_orient.  Enqueued on the
+ * engine stream behind the work that finished the sources, returns without waiting.  n == 0: OH_OK after the OhWarp itself was
+ * checked.  More than OH_CONV_MAX_PICS pictures are split into several launches.
+ * OH_E_ARG, nothing written: a null e, w or id array, or a negative n; an unknown picture; sources (or destinations) whose params
+ * differ among themselves; a picture that is both source and destination, or a destination listed twice; an empty window or one whose
+ * offsets are not multiples of SubWidthC / SubHeightC; width or height below 1, above the destination's coded size or no multiple of
+ * SubWidthC / SubHeightC; a mode, filter or border outside its list; with OH_WARP_CONSTANT a fill above the largest code value; a
+ * coefficient outside the bounds above; OH_WARP_PERSPECTIVE with a denominator m6 x + m7 y + m8 below 2^20 at one of the four corner
+ * samples of the image (it is linear, so the corners bound it).
+ * OH_E_UNSUPPORTED, nothing written: destinations of another bit depth or chroma format than the sources (oh_pics_reformat first). */
+int oh_pics_warp(OhEngine *e, const int *src_ids, const int *dst_ids, int n, const OhWarp *w);
+/* host only, exact integers, the very functions the kernel evaluates (csrc/warp_common.h).
+ * oh_warp_position: the position (Q16, in the window of a plane with shifts hs, vs) that sample (x, y) of that plane of the image
+ * reads; of w only mode and m are read.  OH_E_ARG: a null pointer, shifts outside 0 / 1, x or y negative or (x << hs, y << vs) above
+ * 16384, a mode outside its list, a coefficient outside its bounds, a perspective denominator below 2^20 at the sample.
+ * oh_warp_cubic: the four taps of phase f (0 .. 63); OH_E_ARG otherwise.
+ * oh_warp_interp: one sample from its 4 x 4 neighbourhood, taps[4 j + i] = s(ix - 1 + i, iy - 1 + j) (NEAREST reads taps[5], BILINEAR
+ * taps[5], [6], [9], [10]); -1: a null pointer, a fraction outside 0 .. 63, a filter outside its list, a depth that is not 8, 9, 10
+ * or 12. */
+int     oh_warp_position(const OhWarp *w, int hs, int vs, int x, int y, int32_t *px_q16, int32_t *py_q16);
+int     oh_warp_cubic(int f, int16_t c[4]);
+int32_t oh_warp_interp(const uint16_t taps[16], int fx, int fy, int filter, int bit_depth);
+/* host only: how many workgroup tiles of a call with this OhWarp (mode, filter, width, height, m) into destinations of dst_width x
+ * dst_height at this depth and chroma format stage their taps in LDS (*staged) and how many gather them from global memory
+ * (*gathered): the kernel's own predicate, so that a test knows which paths it ran.  OH_E_ARG: what oh_pics_warp refuses of these. */
+int     oh_warp_paths(const OhWarp *w, int bit_depth, int chroma_format_idc, int dst_width, int dst_height, int64_t *staged, int64_t *gathered);
+/* host only, builders: each fills the whole OhWarp — OH_WARP_AFFINE, OH_WARP_BILINEAR, OH_WARP_REPLICATE, fill 0, the whole picture
+ * as window, width = height = 0 (oh_warp_from_sei: the image size) — and the map.  OH_E_ARG: a null pointer, or as said.
+ * oh_warp_translation: destination (x, y) reads source (x + dx_q2 / 4, y + dy_q2 / 4), the convention of OhMotionVector, so a global
+ * vector of a motion field can be applied.
+ * oh_warp_then: the one map equal to warping by `first`, then warping its image by `second` (affine maps only; m[6 .. 8] are not
+ * read): A = A_first A_second with every product (a b + 2^15) >> 16; the result keeps first's filter, border, fill and window and
+ * second's width and height.  OH_E_ARG also: a mode other than OH_WARP_AFFINE, a coefficient of an argument or of the result outside
+ * its bounds.
+ * oh_warp_invert: fwd as a source -> destination map becomes the destination -> source map (affine only), every term a quotient of
+ * exact integers rounded to nearest (halves up) in __int128; the other fields are copied.  OH_E_ARG also: a singular map, a
+ * coefficient of the argument or of the result outside its bounds.
+ * oh_warp_rotation: an anticlockwise turn of the picture by `anticlockwise` (units of 360 / 2^16 degrees, below 2^16) that carries
+ * the source position (cx_src, cy_src) to the destination position (cx_dst, cy_dst) (Q16, |.| <= 2^36): in y-down coordinates
+ * x = x' cos - y' sin, y = x' sin + y' cos about the centres, times scale_q16 (1 .. 2^22: source samples per destination sample).
+ * m0 = m4 = llrint(scale cos), m3 = -m1 = llrint(scale sin) with libm's cos / sin of a double — the only floating point of the
+ * service — and exactly 0 / +-scale at multiples of a quarter turn; m2 = cx_src - ((m0 cx_dst + m1 cy_dst + 2^15) >> 16), m5 =
+ * cy_src - ((m3 cx_dst + m4 cy_dst + 2^15) >> 16).  OH_E_ARG also: a result outside the bounds.
+ * oh_warp_from_sei: the display-orientation SEI message at any angle for a picture of w x h luma samples (1 .. 16384): the flips come
+ * first, then the anticlockwise rotation about the picture's centre, the order oh_orient_from_sei states.  The image is the rotated
+ * bounding box, *ow = (|m0| w + |m1| h + 65535) >> 16 and *oh = (|m3| w + |m4| h + 65535) >> 16 of the rotation's terms, each rounded
+ * up to a multiple of 2; the centres are (size - 1) << 15.  OH_E_ARG also: a flag outside 0 / 1, a rotation of 2^16 or more. */
+int oh_warp_identity(OhWarp *out);
+int oh_warp_translation(int32_t dx_q2, int32_t dy_q2, OhWarp *out);
+int oh_warp_then(const OhWarp *first, const OhWarp *second, OhWarp *out);
+int oh_warp_invert(const OhWarp *fwd, OhWarp *out);
+int oh_warp_rotation(uint32_t anticlockwise, int64_t cx_src_q16, int64_t cy_src_q16, int64_t cx_dst_q16, int64_t cy_dst_q16, int32_t scale_q16,
+                     OhWarp *out);
+int oh_warp_from_sei(int hor_flip, int ver_flip, uint32_t anticlockwise_rotation, int w, int h, OhWarp *out, int *ow, int *oh);
+
 /* Fields and frames (DESIGN.md §3l has the exact definitions, which the tests check bit for bit against tests/deinterlace_model.py).
  * The reference reads field_seq_flag and the pic_struct of the picture timing SEI (oh_sei_pic_timing, ohevc_annexb.h) and tags its
  * frames interlaced_frame / top_field_first; these calls act on it without a host copy.

@@ -143,7 +143,8 @@ def display_orientation(nal):
     """None, or a dict of the display-orientation message (payload type 47) of one prefix SEI NAL unit (oh_sei_display_orientation):
     "cancel", "hor_flip", "ver_flip" (bool), "anticlockwise_rotation" (0 .. 65535, units of 360 / 65536 degrees), "persistence"; the
     fields behind "cancel" are False / 0 in a cancelled message.  engine.orientation_from_sei turns the flips and the rotation into
-    an orientation of Engine.pics_orient."""
+    an orientation of Engine.pics_orient where the rotation is a multiple of a quarter turn; engine.warp_from_sei turns them into the
+    map and the image size of Engine.pics_warp at any angle."""
     d = OhDisplayOrientation()
     r = lib().oh_sei_display_orientation(nal, len(nal), C.byref(d))
     if r < 0:

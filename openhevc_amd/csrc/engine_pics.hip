@@ -1060,6 +1060,63 @@ extern "C" int oh_pics_orient(OhEngine *e, const int *src_ids, const int *dst_id
     return OH_OK;
 }
 
+/* ---------------- warping: affine and perspective resampling (warp.hip) ---------------- */
+extern "C" int oh_pics_warp(OhEngine *e, const int *src_ids, const int *dst_ids, int n, const OhWarp *w)
+{
+    const char *who = "oh_pics_warp";
+    if (!e || n < 0 || !w || (n && (!src_ids || !dst_ids)))
+        return OH_E_ARG;
+    std::string why;
+    if (warp_check(w, 16, &why) || warp_image_check(w, &why))           /* the fill against the depth: below, with the pictures */
+        FAIL(e, OH_E_ARG, "%s: %s", who, why.c_str());
+    if (!n)
+        return OH_OK;
+    const Pic *s0 = alike_pics(e, who, src_ids, n);
+    if (!s0) return OH_E_ARG;
+    const Pic *d0 = alike_pics(e, who, dst_ids, n);
+    if (!d0) return OH_E_ARG;
+    { const int rc = dsts_apart(e, who, dst_ids, n, src_ids, n); if (rc) return rc; }
+    const OhPicParams &sp = s0->p, &dp = d0->p;
+    if (!crop_window_ok(&sp, w->win, true, &why))
+        FAIL(e, OH_E_ARG, "%s: %s", who, why.c_str());
+    const int cf = sp.chroma_format_idc, hs = cf == 1 || cf == 2, vs = cf == 1;
+    if (dp.bit_depth != sp.bit_depth || dp.chroma_format_idc != cf)
+        FAIL(e, OH_E_UNSUPPORTED, "%s: destinations of %d bit, chroma format %d; sources of %d bit, chroma format %d (oh_pics_reformat first)", who,
+             dp.bit_depth, dp.chroma_format_idc, sp.bit_depth, cf);
+    if (w->width > dp.width || w->height > dp.height || w->width % (1 << hs) || w->height % (1 << vs))
+        FAIL(e, OH_E_ARG, "%s: image %dx%d: above the destination's %dx%d, or not multiples of %dx%d", who, w->width, w->height, dp.width, dp.height,
+             1 << hs, 1 << vs);
+    if (warp_check(w, sp.bit_depth, &why))
+        FAIL(e, OH_E_ARG, "%s: %s", who, why.c_str());
+    int W, H;
+    window_size(&sp, w->win, &W, &H);
+    HIPCHK(e, hipSetDevice(e->device));
+    OhWarpArgs a;
+    memset(&a, 0, sizeof(a));
+    a.np = n_planes(sp); a.bd = sp.bit_depth; a.sx = hs; a.sy = vs;
+    a.mode = w->mode; a.filter = w->filter; a.border = w->border;
+    for (int c = 0; c < 3; c++) a.fill[c] = w->fill[c];
+    for (int k = 0; k < 9; k++) a.m[k] = w->m[k];
+    row_pitches(s0, a.np, a.spitch);
+    row_pitches(d0, a.np, a.dpitch);
+    class_sizes(d0, a.np, a.dw, a.dh);
+    for (int q = 0; q < (cf ? 2 : 1); q++) {
+        a.x0[q] = w->win.left >> (q ? hs : 0); a.y0[q] = w->win.top >> (q ? vs : 0);
+        a.ws[q] = W >> (q ? hs : 0); a.hs[q] = H >> (q ? vs : 0);
+        a.iw[q] = w->width >> (q ? hs : 0); a.ih[q] = w->height >> (q ? vs : 0);
+    }
+    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
+        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+        for (int i = 0; i < m; i++) {
+            read_planes(get_pic(e, src_ids[i0 + i]), a.np, a.src[i]);
+            write_planes(get_pic(e, dst_ids[i0 + i]), a.np, a.dst[i]);
+        }
+        ohk_warp(&a, m, e->stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    return OH_OK;
+}
+
 /* ---------------- fields and deinterlacing (deinterlace.hip) ---------------- */
 /* what weave and separate ask of their fields (f0) and frames (F0) */
 static int fields_check(OhEngine *e, const char *who, const Pic *f0, const Pic *F0)

@@ -173,6 +173,24 @@ struct OhOrArgs {
     int32_t     orientation;         /* OH_ORIENT_* bits */
 };
 
+/* picture warping (warp.hip): the finished planes of the sources and half 0 of the destinations of one launch by value
+ * in the kernel arguments; every picture of a launch has the same geometry.  Two plane classes (0 luma, 1 chroma).  The tile of one
+ * workgroup and its LDS budget are WARP_TW, WARP_TH and WARP_LDS of warp_common.h, which the host's oh_warp_paths shares. */
+struct OhWarpArgs {
+    const void *src[64][3];          /* OH_CONV_MAX_PICS pictures x planes: the finished halves */
+    void       *dst[64][3];          /* half 0 of the destinations */
+    int64_t     m[9];                /* OhWarp.m */
+    int32_t     spitch[3], dpitch[3];/* bytes between rows of each plane */
+    int32_t     x0[2], y0[2];        /* origin of the plane's window in the source plane */
+    int32_t     ws[2], hs[2];        /* size of the plane's window */
+    int32_t     iw[2], ih[2];        /* size of the image in the destination planes */
+    int32_t     dw[2], dh[2];        /* coded size of the destination planes */
+    int32_t     sx, sy;              /* oh_hshift / oh_vshift of the chroma planes */
+    int32_t     np, bd;              /* planes: 1 or 3; bit depth */
+    int32_t     mode, filter, border;/* OhWarp */
+    int32_t     fill[3];
+};
+
 /* fields and deinterlacing (deinterlace.hip): the planes of the pictures of one launch by value in the kernel arguments;
  * every frame of a launch has one geometry, every field another.  Two plane classes (0 luma, 1 chroma).  What the four pictures of
  * index i are depends on the call:
@@ -325,6 +343,8 @@ void ohk_compose(const OhCpsArgs *a, int n, hipStream_t st);
 void ohk_reformat(const OhRfArgs *a, int n, hipStream_t st);
 /* n sources of a.src, oriented, into the n destinations of a.dst */
 void ohk_orient(const OhOrArgs *a, int n, hipStream_t st);
+/* n sources of a.src, warped, into the n destinations of a.dst */
+void ohk_warp(const OhWarpArgs *a, int n, hipStream_t st);
 /* n pictures of a.pic[1] (with a.pic[0] and a.pic[2] around them in time) deinterlaced into the n destinations of a.pic[3] */
 void ohk_deinterlace(const OhDiArgs *a, int n, hipStream_t st);
 /* n pairs of fields woven into n frames, or n frames separated into one or two fields each */

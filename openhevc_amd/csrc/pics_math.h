@@ -23,6 +23,9 @@ OH_INTERNAL int colour_build(const OhColour *col, int32_t *tab, int32_t *misc, s
 OH_INTERNAL int filter_check(const OhFilter *f, int bit_depth, std::string *why);
 OH_INTERNAL void hist_derive(const uint32_t *bins, OhPlaneHist *out);
 OH_INTERNAL int motion_check(const OhMotionSearch *ms, size_t n_centres, std::string *why);
+OH_INTERNAL int warp_map_check(const OhWarp *w, std::string *why);
+OH_INTERNAL int warp_check(const OhWarp *w, int bit_depth, std::string *why);
+OH_INTERNAL int warp_image_check(const OhWarp *w, std::string *why);
 OH_INTERNAL int lut_check(const OhLut *lut, int sbd, int dbd, int np, std::string *why);
 
 #endif

@@ -1,7 +1,7 @@
 /*
  * pics_math.hip — the host arithmetic of the picture services (engine_pics.hip), with neither an engine nor a device: image sizes and
  * crop windows, the ids of a call (destinations apart from sources, neighbours in time), the integers of the RGB conversions, the colour tables of the HDR forms, light-level bins and percentiles, the SSIM window
- * and PSNR, the resize taps, the compose formulas, the reformat quantisation, the orientations' group, the pic_struct table, the adaptive deinterlacer's sample, the filters' taps and samples, and what follows from a histogram's bins with the table builders.  No kernel, no HIP runtime call: tests/pics_math_check.cpp runs it under sanitizers.
+ * and PSNR, the resize taps, the compose formulas, the reformat quantisation, the orientations' group, the pic_struct table, the adaptive deinterlacer's sample, the filters' taps and samples, and what follows from a histogram's bins with the table builders, the motion helpers, and the warp's positions, taps and map builders.  No kernel, no HIP runtime call: tests/pics_math_check.cpp runs it under sanitizers.
  */
 #include <stdio.h>
 #include <string.h>
@@ -17,6 +17,7 @@
 #include "deinterlace_common.h"
 #include "filter_common.h"
 #include "motion_common.h"
+#include "warp_common.h"
 
 static bool depth_ok(int bit_depth) { return bit_depth == 8 || bit_depth == 9 || bit_depth == 10 || bit_depth == 12; }
 
@@ -996,5 +997,246 @@ int motion_check(const OhMotionSearch *ms, size_t n_centres, std::string *why)
                 snprintf(buf, sizeof(buf), "centre %zu is (%d, %d): beyond %d", i / 2, ms->centres[i & ~(size_t)1], ms->centres[i | 1], OH_MOTION_MAX_CENTRE);
                 *why = buf; return OH_E_ARG;
             }
+    return OH_OK;
+}
+
+/* ---------------- warping: the host-only helpers and what oh_pics_warp checks ---------------- */
+static bool within(int64_t v, int bits) { return v >= -((int64_t)1 << bits) && v <= ((int64_t)1 << bits); }
+
+/* the mode and the coefficients it reads */
+int warp_map_check(const OhWarp *w, std::string *why)
+{
+    char buf[256];
+    if (w->mode < OH_WARP_AFFINE || w->mode > OH_WARP_PERSPECTIVE) {
+        snprintf(buf, sizeof(buf), "mode %d (0 affine, 1 perspective)", w->mode); *why = buf; return OH_E_ARG;
+    }
+    const int64_t *m = w->m;
+    if (!within(m[0], 22) || !within(m[1], 22) || !within(m[3], 22) || !within(m[4], 22) || !within(m[2], 36) || !within(m[5], 36)) {
+        *why = "m[0], m[1], m[3], m[4] beyond 2^22 or m[2], m[5] beyond 2^36 (Q16)"; return OH_E_ARG;
+    }
+    if (w->mode == OH_WARP_PERSPECTIVE && (!within(m[6], 26) || !within(m[7], 26) || m[8] <= 0 || m[8] > (int64_t)1 << 36)) {
+        *why = "m[6], m[7] beyond 2^26 or m[8] outside 1 .. 2^36 (Q30)"; return OH_E_ARG;
+    }
+    return OH_OK;
+}
+
+/* the perspective denominator at luma sample (X, Y), at least 2^20 */
+static bool warp_denominator_ok(const OhWarp *w, int64_t X, int64_t Y)
+{
+    return w->mode != OH_WARP_PERSPECTIVE || w->m[6] * X + w->m[7] * Y + w->m[8] >= (int64_t)1 << 20;
+}
+
+/* what oh_pics_warp checks of the OhWarp itself, without pictures; the image is checked where width is not 0 */
+int warp_check(const OhWarp *w, int bit_depth, std::string *why)
+{
+    char buf[256];
+    { const int rc = warp_map_check(w, why); if (rc) return rc; }
+    if (w->filter < OH_WARP_NEAREST || w->filter > OH_WARP_BICUBIC) {
+        snprintf(buf, sizeof(buf), "filter %d (0 nearest, 1 bilinear, 2 bicubic)", w->filter); *why = buf; return OH_E_ARG;
+    }
+    if (w->border < OH_WARP_REPLICATE || w->border > OH_WARP_CONSTANT) {
+        snprintf(buf, sizeof(buf), "border %d (0 replicate, 1 constant)", w->border); *why = buf; return OH_E_ARG;
+    }
+    if (w->border == OH_WARP_CONSTANT)
+        for (int c = 0; c < 3; c++)
+            if (w->fill[c] >> bit_depth) {
+                snprintf(buf, sizeof(buf), "fill[%d] = %d does not fit %d bits", c, w->fill[c], bit_depth); *why = buf; return OH_E_ARG;
+            }
+    return OH_OK;
+}
+
+/* the image of a call: inside 1 .. 16384, and the denominator at its four corner samples */
+int warp_image_check(const OhWarp *w, std::string *why)
+{
+    char buf[256];
+    if (w->width < 1 || w->height < 1 || w->width > 16384 || w->height > 16384) {
+        snprintf(buf, sizeof(buf), "image %dx%d: outside 1 .. 16384", w->width, w->height); *why = buf; return OH_E_ARG;
+    }
+    for (int k = 0; k < 4; k++)
+        if (!warp_denominator_ok(w, k & 1 ? w->width - 1 : 0, k & 2 ? w->height - 1 : 0)) {
+            snprintf(buf, sizeof(buf), "the perspective denominator is below 2^20 at corner (%d, %d) of the image", k & 1 ? w->width - 1 : 0,
+                     k & 2 ? w->height - 1 : 0);
+            *why = buf; return OH_E_ARG;
+        }
+    return OH_OK;
+}
+
+extern "C" int oh_warp_position(const OhWarp *w, int hs, int vs, int x, int y, int32_t *px_q16, int32_t *py_q16)
+{
+    std::string why;
+    if (!w || !px_q16 || !py_q16 || hs < 0 || hs > 1 || vs < 0 || vs > 1 || x < 0 || y < 0 || x > 16384 >> hs || y > 16384 >> vs || warp_map_check(w, &why))
+        return OH_E_ARG;
+    if (w->mode == OH_WARP_PERSPECTIVE) {
+        if (w->m[6] * ((int64_t)x << hs) + w->m[7] * ((int64_t)y << vs) + w->m[8] + vs * (w->m[7] >> 1) < (int64_t)1 << 20)
+            return OH_E_ARG;
+        warp_position<true>(w->m, hs, vs, x, y, px_q16, py_q16);
+    } else
+        warp_position<false>(w->m, hs, vs, x, y, px_q16, py_q16);
+    return OH_OK;
+}
+
+extern "C" int oh_warp_cubic(int f, int16_t c[4])
+{
+    if (f < 0 || f > 63 || !c)
+        return OH_E_ARG;
+    int32_t k[4];
+    warp_cubic(f, k);
+    for (int i = 0; i < 4; i++) c[i] = (int16_t)k[i];
+    return OH_OK;
+}
+
+extern "C" int32_t oh_warp_interp(const uint16_t taps[16], int fx, int fy, int filter, int bit_depth)
+{
+    if (!taps || fx < 0 || fx > 63 || fy < 0 || fy > 63 || filter < OH_WARP_NEAREST || filter > OH_WARP_BICUBIC || !depth_ok(bit_depth))
+        return -1;
+    return warp_interp(filter, [=](int i, int j) { return (int32_t)taps[4 * j + i]; }, 1, 1, fx, fy, (1 << bit_depth) - 1);
+}
+
+extern "C" int oh_warp_paths(const OhWarp *w, int bit_depth, int chroma_format_idc, int dst_width, int dst_height, int64_t *staged, int64_t *gathered)
+{
+    std::string why;
+    const int cf = chroma_format_idc, hs = cf == 1 || cf == 2, vs = cf == 1;
+    if (!w || !staged || !gathered || !depth_ok(bit_depth) || cf < 0 || cf > 3 || warp_check(w, bit_depth, &why) || warp_image_check(w, &why) ||
+        w->width > dst_width || w->height > dst_height || dst_width > 16384 || dst_height > 16384 || w->width % (1 << hs) || w->height % (1 << vs) ||
+        dst_width % (1 << hs) || dst_height % (1 << vs))
+        return OH_E_ARG;
+    *staged = *gathered = 0;
+    for (int q = 0; q < (cf ? 2 : 1); q++) {
+        const int sx = q ? hs : 0, sy = q ? vs : 0, dw = dst_width >> sx, dh = dst_height >> sy, iw = w->width >> sx, ih = w->height >> sy;
+        for (int ty = 0; ty * WARP_TH < dh; ty++)
+            for (int tx = 0; tx * WARP_TW < dw; tx++) {
+                int xa, ya, xb, yb;
+                warp_tile_corners(tx, ty, dw, dh, iw, ih, &xa, &ya, &xb, &yb);
+                const WarpBox b = w->mode == OH_WARP_PERSPECTIVE ? warp_tile_box<true>(w->m, sx, sy, w->filter, xa, ya, xb, yb)
+                                                                 : warp_tile_box<false>(w->m, sx, sy, w->filter, xa, ya, xb, yb);
+                *(warp_box_staged(b, bit_depth > 8 ? 2 : 1) ? staged : gathered) += q ? 2 : 1;
+            }
+    }
+    return OH_OK;
+}
+
+extern "C" int oh_warp_identity(OhWarp *out)
+{
+    if (!out)
+        return OH_E_ARG;
+    memset(out, 0, sizeof(*out));
+    out->mode = OH_WARP_AFFINE; out->filter = OH_WARP_BILINEAR; out->border = OH_WARP_REPLICATE;
+    out->m[0] = out->m[4] = 65536;
+    out->m[8] = (int64_t)1 << 30;
+    return OH_OK;
+}
+
+extern "C" int oh_warp_translation(int32_t dx_q2, int32_t dy_q2, OhWarp *out)
+{
+    if (oh_warp_identity(out))
+        return OH_E_ARG;
+    out->m[2] = (int64_t)dx_q2 * 16384;
+    out->m[5] = (int64_t)dy_q2 * 16384;
+    return OH_OK;
+}
+
+static bool warp_affine_ok(const OhWarp *w)
+{
+    std::string why;
+    return w && w->mode == OH_WARP_AFFINE && !warp_map_check(w, &why);
+}
+
+extern "C" int oh_warp_then(const OhWarp *first, const OhWarp *second, OhWarp *out)
+{
+    if (!out || !warp_affine_ok(first) || !warp_affine_ok(second))
+        return OH_E_ARG;
+    const int64_t *a = first->m, *b = second->m;
+    auto P = [](int64_t x, int64_t y) { return (x * y + 32768) >> 16; };
+    OhWarp r = *first;
+    r.width = second->width; r.height = second->height;
+    r.m[0] = P(a[0], b[0]) + P(a[1], b[3]);
+    r.m[1] = P(a[0], b[1]) + P(a[1], b[4]);
+    r.m[2] = P(a[0], b[2]) + P(a[1], b[5]) + a[2];
+    r.m[3] = P(a[3], b[0]) + P(a[4], b[3]);
+    r.m[4] = P(a[3], b[1]) + P(a[4], b[4]);
+    r.m[5] = P(a[3], b[2]) + P(a[4], b[5]) + a[5];
+    r.m[6] = r.m[7] = 0; r.m[8] = (int64_t)1 << 30;
+    if (!warp_affine_ok(&r))
+        return OH_E_ARG;
+    *out = r;
+    return OH_OK;
+}
+
+/* n / d rounded to nearest, halves up; d != 0.  false: the quotient leaves 63 bits */
+static bool rounded_div(__int128 n, __int128 d, int64_t *q)
+{
+    if (d < 0) { n = -n; d = -d; }
+    const __int128 t = 2 * n + d, dd = 2 * d;
+    __int128 r = t / dd;
+    if (t % dd < 0) r--;
+    if (r > ((__int128)1 << 62) || r < -((__int128)1 << 62))
+        return false;
+    *q = (int64_t)r;
+    return true;
+}
+
+extern "C" int oh_warp_invert(const OhWarp *fwd, OhWarp *out)
+{
+    if (!out || !warp_affine_ok(fwd))
+        return OH_E_ARG;
+    const __int128 a = fwd->m[0], b = fwd->m[1], tx = fwd->m[2], c = fwd->m[3], d = fwd->m[4], ty = fwd->m[5];
+    const __int128 det = a * d - b * c, one = (__int128)1 << 32, q16 = 65536;
+    if (det == 0)
+        return OH_E_ARG;
+    OhWarp r = *fwd;
+    if (!rounded_div(d * one, det, &r.m[0]) || !rounded_div(-b * one, det, &r.m[1]) || !rounded_div((b * ty - d * tx) * q16, det, &r.m[2]) ||
+        !rounded_div(-c * one, det, &r.m[3]) || !rounded_div(a * one, det, &r.m[4]) || !rounded_div((c * tx - a * ty) * q16, det, &r.m[5]))
+        return OH_E_ARG;
+    r.m[6] = r.m[7] = 0; r.m[8] = (int64_t)1 << 30;
+    if (!warp_affine_ok(&r))
+        return OH_E_ARG;
+    *out = r;
+    return OH_OK;
+}
+
+extern "C" int oh_warp_rotation(uint32_t anticlockwise, int64_t cx_src_q16, int64_t cy_src_q16, int64_t cx_dst_q16, int64_t cy_dst_q16,
+                                int32_t scale_q16, OhWarp *out)
+{
+    if (!out || anticlockwise >= 65536u || scale_q16 < 1 || scale_q16 > 1 << 22 || !within(cx_src_q16, 36) || !within(cy_src_q16, 36) ||
+        !within(cx_dst_q16, 36) || !within(cy_dst_q16, 36))
+        return OH_E_ARG;
+    int64_t co, si;
+    if (!(anticlockwise & 0x3FFF)) {
+        const int k = (int)(anticlockwise >> 14);
+        co = k == 0 ? scale_q16 : k == 2 ? -(int64_t)scale_q16 : 0;
+        si = k == 1 ? scale_q16 : k == 3 ? -(int64_t)scale_q16 : 0;
+    } else {
+        const double t = (double)anticlockwise * (6.283185307179586476925286766559 / 65536.0);
+        co = llrint((double)scale_q16 * cos(t));
+        si = llrint((double)scale_q16 * sin(t));
+    }
+    OhWarp r;
+    (void)oh_warp_identity(&r);
+    r.m[0] = co; r.m[1] = -si; r.m[3] = si; r.m[4] = co;
+    r.m[2] = cx_src_q16 - ((r.m[0] * cx_dst_q16 + r.m[1] * cy_dst_q16 + 32768) >> 16);
+    r.m[5] = cy_src_q16 - ((r.m[3] * cx_dst_q16 + r.m[4] * cy_dst_q16 + 32768) >> 16);
+    if (!warp_affine_ok(&r))
+        return OH_E_ARG;
+    *out = r;
+    return OH_OK;
+}
+
+extern "C" int oh_warp_from_sei(int hor_flip, int ver_flip, uint32_t anticlockwise_rotation, int w, int h, OhWarp *out, int *ow, int *oh)
+{
+    if (!out || !ow || !oh || hor_flip < 0 || hor_flip > 1 || ver_flip < 0 || ver_flip > 1 || anticlockwise_rotation >= 65536u || w < 1 || h < 1 ||
+        w > 16384 || h > 16384)
+        return OH_E_ARG;
+    OhWarp r;
+    if (oh_warp_rotation(anticlockwise_rotation, 0, 0, 0, 0, 65536, &r))
+        return OH_E_ARG;
+    auto mag = [](int64_t v) { return v < 0 ? -v : v; };
+    const int iw = (int)(((mag(r.m[0]) * w + mag(r.m[1]) * h + 65535) >> 16) + 1) & ~1, ih = (int)(((mag(r.m[3]) * w + mag(r.m[4]) * h + 65535) >> 16) + 1) & ~1;
+    if (oh_warp_rotation(anticlockwise_rotation, (int64_t)(w - 1) << 15, (int64_t)(h - 1) << 15, (int64_t)(iw - 1) << 15, (int64_t)(ih - 1) << 15, 65536, &r))
+        return OH_E_ARG;
+    if (hor_flip) { r.m[0] = -r.m[0]; r.m[1] = -r.m[1]; r.m[2] = ((int64_t)(w - 1) << 16) - r.m[2]; }
+    if (ver_flip) { r.m[3] = -r.m[3]; r.m[4] = -r.m[4]; r.m[5] = ((int64_t)(h - 1) << 16) - r.m[5]; }
+    r.width = iw; r.height = ih;
+    *out = r;
+    *ow = iw; *oh = ih;
     return OH_OK;
 }

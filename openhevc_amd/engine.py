@@ -399,6 +399,126 @@ def orientation_from_sei(hor_flip, ver_flip, anticlockwise_rotation):
     return o.value
 
 
+class OhWarp(C.Structure):                                    # include/ohevc_hip.h
+    _fields_ = [("mode", C.c_int32), ("filter", C.c_int32), ("border", C.c_int32), ("fill", C.c_uint16 * 3), ("win", OhWindow),
+                ("width", C.c_int32), ("height", C.c_int32), ("m", C.c_int64 * 9)]
+
+
+WARP_MODES = {"affine": 0, "perspective": 1}                                            # OH_WARP_AFFINE, OH_WARP_PERSPECTIVE
+WARP_FILTERS = {"nearest": 0, "bilinear": 1, "bicubic": 2}                              # OH_WARP_NEAREST .. OH_WARP_BICUBIC
+WARP_BORDERS = {"replicate": 0, "constant": 1}                                          # OH_WARP_REPLICATE, OH_WARP_CONSTANT
+WARP_TILE = (64, 16)                                                                    # WARP_TW, WARP_TH (csrc/warp_common.h): a workgroup's tile
+
+
+def _warp_enum(table, what, v):
+    """a name of the table or one of its ints -> the int"""
+    if isinstance(v, str):
+        if v not in table:
+            raise ValueError(f"unknown {what} {v!r}: one of {sorted(table)}")
+        return table[v]
+    if int(v) not in table.values():
+        raise ValueError(f"{what} {v}: one of {sorted(table.values())}")
+    return int(v)
+
+
+def _warp_built(name, *args):
+    """one of the C builders, which fill a whole OhWarp"""
+    w = OhWarp()
+    rc = getattr(lib(), name)(*args, C.byref(w))
+    if rc != 0:
+        err = EngineError(f"{name} failed ({rc})")
+        err.code = rc
+        raise err
+    return w
+
+
+def warp_matrix(matrix, mode=None):
+    """(mode, the nine int64 of OhWarp.m) from any form Engine.pics_warp takes: an OhWarp; 6 or 9 integers in the fixed-point layout
+    of OhWarp.m (6: affine, m[6 .. 8] = 0, 0, 2^30); a float 2 x 3 or 3 x 3 numpy array, the inverse map (destination -> source) in luma
+    samples.  A float array is rounded here and nowhere else: a 3 x 3 array is first divided by its [2][2] entry (which must not be
+    0), then m[0 .. 5] = rint(65536 a) and m[6], m[7] = rint(2^30 a), m[8] = 2^30; rint is numpy's, halves to even, in float64.  mode
+    None: affine for 6 numbers or 2 x 3, perspective for 9 or 3 x 3."""
+    if isinstance(matrix, OhWarp):
+        return (matrix.mode if mode is None else _warp_enum(WARP_MODES, "mode", mode)), [int(v) for v in matrix.m]
+    a = np.asarray(matrix)
+    if a.dtype.kind == "f":
+        if a.shape not in ((2, 3), (3, 3)):
+            raise ValueError(f"a float matrix of shape {a.shape}: 2 x 3 or 3 x 3")
+        a = a.astype(np.float64)
+        if not np.isfinite(a).all():
+            raise ValueError("a matrix with an entry that is not finite")
+        if a.shape == (3, 3):
+            if a[2, 2] == 0:
+                raise ValueError("a 3 x 3 matrix whose [2][2] entry is 0")
+            a = a / a[2, 2]
+        m = [int(v) for v in np.rint(a[:2].reshape(-1) * 65536.0)]
+        m += [int(np.rint(a[2, 0] * 2.0 ** 30)), int(np.rint(a[2, 1] * 2.0 ** 30)), 1 << 30] if a.shape == (3, 3) else [0, 0, 1 << 30]
+        inferred = 1 if a.shape == (3, 3) else 0
+    else:
+        if a.dtype.kind not in "iu" or a.size not in (6, 9):
+            raise ValueError("a matrix is an OhWarp, 6 or 9 integers, or a float 2 x 3 / 3 x 3 array")
+        m = [int(v) for v in a.reshape(-1)]
+        inferred = 1 if len(m) == 9 else 0
+        m += [0, 0, 1 << 30] if len(m) == 6 else []
+    if any(not -(1 << 63) <= v < 1 << 63 for v in m):
+        raise ValueError("a coefficient does not fit int64")
+    return (inferred if mode is None else _warp_enum(WARP_MODES, "mode", mode)), m
+
+
+def warp_identity():
+    """oh_warp_identity (host only): the OhWarp of the identity map — affine, bilinear, replicate; width and height 0"""
+    return _warp_built("oh_warp_identity")
+
+
+def warp_translation(dx_q2, dy_q2):
+    """oh_warp_translation (host only): destination (x, y) reads source (x + dx_q2 / 4, y + dy_q2 / 4): quarter samples, the
+    convention of OhMotionVector"""
+    return _warp_built("oh_warp_translation", int(dx_q2), int(dy_q2))
+
+
+def warp_rotation(anticlockwise, centre_src, centre_dst, scale_q16=65536):
+    """oh_warp_rotation (host only): an anticlockwise turn by `anticlockwise` units of 360 / 65536 degrees that carries the source
+    position centre_src = (x, y) to the destination position centre_dst, both Q16 luma samples; scale_q16: source samples per
+    destination sample"""
+    return _warp_built("oh_warp_rotation", int(anticlockwise), int(centre_src[0]), int(centre_src[1]), int(centre_dst[0]), int(centre_dst[1]),
+                       int(scale_q16))
+
+
+def warp_then(first, second):
+    """oh_warp_then (host only, affine maps): the one map equal to warping by first, then warping its image by second"""
+    return _warp_built("oh_warp_then", C.byref(first), C.byref(second))
+
+
+def warp_invert(fwd):
+    """oh_warp_invert (host only, affine maps): a source -> destination map becomes the destination -> source map the service takes"""
+    return _warp_built("oh_warp_invert", C.byref(fwd))
+
+
+def warp_from_sei(hor_flip, ver_flip, anticlockwise_rotation, width, height):
+    """oh_warp_from_sei (host only): (OhWarp, (image width, image height)) of a display-orientation SEI message at any angle
+    (annexb.display_orientation has its fields) for pictures of width x height luma samples: the flips, then the anticlockwise
+    rotation about the centre, into the rotated bounding box rounded up to even sizes.  The result is affine, bilinear, replicate."""
+    w, ow, oh = OhWarp(), C.c_int(), C.c_int()
+    rc = lib().oh_warp_from_sei(int(hor_flip), int(ver_flip), int(anticlockwise_rotation), int(width), int(height), C.byref(w), C.byref(ow), C.byref(oh))
+    if rc != 0:
+        err = EngineError(f"oh_warp_from_sei({hor_flip}, {ver_flip}, {anticlockwise_rotation:#x}, {width}, {height}) failed ({rc})")
+        err.code = rc
+        raise err
+    return w, (ow.value, oh.value)
+
+
+def warp_paths(warp, bit_depth, chroma_format_idc, dst_width, dst_height):
+    """oh_warp_paths (host only): (tiles that stage their taps in LDS, tiles that gather them from global memory) of a call with
+    this OhWarp into destinations of dst_width x dst_height: the kernel's own predicate"""
+    s, g = C.c_int64(), C.c_int64()
+    rc = lib().oh_warp_paths(C.byref(warp), int(bit_depth), int(chroma_format_idc), int(dst_width), int(dst_height), C.byref(s), C.byref(g))
+    if rc != 0:
+        err = EngineError(f"oh_warp_paths failed ({rc})")
+        err.code = rc
+        raise err
+    return s.value, g.value
+
+
 class OhFieldInfo(C.Structure):                               # include/ohevc_hip.h
     _fields_ = [("kind", C.c_int32), ("pair", C.c_int32), ("top_first", C.c_int32), ("repeat_first", C.c_int32), ("frames", C.c_int32)]
 
@@ -813,6 +933,19 @@ def lib():
         L.oh_orient_size.argtypes = [I, I, I, C.POINTER(I), C.POINTER(I)]
         L.oh_orient_from_sei.argtypes = [I, I, C.c_uint32, C.POINTER(I)]
         IP = C.POINTER(C.c_int)
+        WP, I64 = C.POINTER(OhWarp), C.c_int64
+        L.oh_pics_warp.argtypes = [V, IP, IP, I, WP]
+        L.oh_warp_position.argtypes = [WP, I, I, I, I, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.oh_warp_cubic.argtypes = [I, C.POINTER(C.c_int16)]
+        L.oh_warp_interp.argtypes = [C.POINTER(C.c_uint16), I, I, I, I]
+        L.oh_warp_interp.restype = C.c_int32
+        L.oh_warp_paths.argtypes = [WP, I, I, I, I, C.POINTER(I64), C.POINTER(I64)]
+        L.oh_warp_identity.argtypes = [WP]
+        L.oh_warp_translation.argtypes = [C.c_int32, C.c_int32, WP]
+        L.oh_warp_then.argtypes = [WP, WP, WP]
+        L.oh_warp_invert.argtypes = [WP, WP]
+        L.oh_warp_rotation.argtypes = [C.c_uint32, I64, I64, I64, I64, C.c_int32, WP]
+        L.oh_warp_from_sei.argtypes = [I, I, C.c_uint32, I, I, WP, IP, IP]
         L.oh_field_info.argtypes = [I, C.POINTER(OhFieldInfo)]
         L.oh_pics_weave.argtypes = [V, IP, IP, IP, I]
         L.oh_pics_separate.argtypes = [V, IP, IP, IP, I]
@@ -1350,6 +1483,40 @@ class Engine:
 
         out, made = self._dsts(out, n, "sources", fitting)
         self._call(self.L.oh_pics_orient(self.h, (C.c_int * n)(*pids), (C.c_int * n)(*out), n, C.byref(od)), "oh_pics_orient", made)
+        dp = self._pic_params(out[0])
+        return out, (0, dp.width - width, 0, dp.height - height)
+
+    def pics_warp(self, pids, matrix, size, *, mode=None, filter="bilinear", border="replicate", fill=(0, 0, 0), window=(0, 0, 0, 0), out=None):
+        """finished pictures -> finished pictures resampled through an affine or perspective map (oh_pics_warp): matrix is the INVERSE
+        map, destination -> source, in luma samples with (0, 0) the top-left sample of the window and of the image — an OhWarp (of
+        which the map and, with mode None, the mode are taken: warp_rotation, warp_translation, warp_from_sei, ... build them), 6 or 9
+        integers in the fixed-point layout of OhWarp.m, or a float 2 x 3 / 3 x 3 numpy array, which warp_matrix rounds to that layout
+        (its docstring has the rounding).  size = (width, height) of the image in luma samples; mode "affine" / "perspective" or None
+        (by the matrix's form); filter "nearest", "bilinear" or "bicubic" (no anti-aliasing: pics_resize scales down); border
+        "replicate" or "constant" with fill = the code values per plane; window = (left, right, top, bottom) of the sources, outside
+        of which nothing is read.  out: destination pictures to reuse; None allocates pictures with the sources' params and the size
+        rounded up to the minimum coding block.  Returns (destination ids, dst_window) like pics_resize.  Enqueued on the engine
+        stream; does not wait."""
+        pids = list(pids)
+        n = len(pids)
+        if n == 0:
+            raise ValueError("pics_warp needs at least one picture (the destinations follow the pictures' params)")
+        width, height = int(size[0]), int(size[1])
+        code, m = warp_matrix(matrix, mode)
+        fill = [int(v) for v in fill]
+        if len(fill) != 3 or any(not 0 <= v <= 0xFFFF for v in fill):
+            raise ValueError(f"fill {tuple(fill)}: three code values")
+        wp = OhWarp(code, _warp_enum(WARP_FILTERS, "filter", filter), _warp_enum(WARP_BORDERS, "border", border), (C.c_uint16 * 3)(*fill),
+                    OhWindow(*window), width, height, (C.c_int64 * 9)(*m))
+
+        def fitting():
+            sp = self._pic_params(pids[0])
+            if width < 1 or height < 1:
+                raise ValueError(f"size {size}: at least 1 x 1")
+            return self._sized(sp, width, height)
+
+        out, made = self._dsts(out, n, "sources", fitting)
+        self._call(self.L.oh_pics_warp(self.h, (C.c_int * n)(*pids), (C.c_int * n)(*out), n, C.byref(wp)), "oh_pics_warp", made)
         dp = self._pic_params(out[0])
         return out, (0, dp.width - width, 0, dp.height - height)
 
