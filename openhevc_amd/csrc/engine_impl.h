@@ -193,6 +193,13 @@ struct OhEngine {
         return (code);                                                                            \
     } while (0)
 
+/* a step that sets the message itself: its code, where it is not OH_OK, is the caller's */
+#define OH_TRY(expr)                                                                              \
+    do {                                                                                          \
+        const int try_rc_ = (expr);                                                               \
+        if (try_rc_) return try_rc_;                                                              \
+    } while (0)
+
 struct HostTimer {                       /* adds the scope's wall time to one slot of OhEngine::host_ms */
     OhEngine *e; int slot; std::chrono::steady_clock::time_point t0;
     HostTimer(OhEngine *e_, int slot_);

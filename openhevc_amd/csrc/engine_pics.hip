@@ -31,6 +31,44 @@ static int first_other_params(OhEngine *e, const int *pic_ids, int n)
 }
 
 /* ---------------- what the services share ---------------- */
+/* a check of pics_math.hip that said `why`: rc, OH_OK included, with the message set where it is a refusal */
+static int refuse(OhEngine *e, int rc, const char *who, const char *why)
+{
+    if (rc)
+        FAIL(e, rc, "%s: %s", who, why);
+    return OH_OK;
+}
+static int refuse(OhEngine *e, int rc, const char *who, const std::string &why) { return refuse(e, rc, who, why.c_str()); }
+
+/* the n pictures of a call in launch sets of at most per_set: set(i0, m) fills in the m pictures from i0 on and launches */
+template <typename Set> static int launch_sets(OhEngine *e, int n, Set set, int per_set = OH_CONV_MAX_PICS)
+{
+    for (int i0 = 0; i0 < n; i0 += per_set) {
+        set(i0, std::min(n - i0, per_set));
+        HIPCHK(e, hipGetLastError());
+    }
+    return OH_OK;
+}
+
+/* `bytes` that fill(pinned block) writes, in device scratch s in front of the launches that follow: staged in a pinned buffer of the pool
+ * and copied on the engine stream, behind the launches of an earlier call that read the device copy.  Growing the scratch frees the old
+ * block: a caller whose earlier launches may still use it has waited for them.  what: the block, for the refusal */
+template <typename Fill> static int upload(OhEngine *e, const char *who, const char *what, OhEngine::Scratch *s, size_t bytes, Fill fill)
+{
+    OH_TRY(scratch_reserve(e, s, bytes));
+    OhEngine::Stage *sg = stage_acquire(e, bytes);
+    if (!sg)
+        FAIL(e, OH_E_NOMEM, "%s: no staging buffer for %zu bytes of %s", who, bytes, what);
+    fill(sg->p);
+    HIPCHK(e, hipMemcpyAsync(s->p, sg->p, bytes, hipMemcpyHostToDevice, e->stream));
+    return stage_in_use(e, sg, e->stream);
+}
+
+static int upload_copy(OhEngine *e, const char *who, const char *what, OhEngine::Scratch *s, size_t bytes, const void *block)
+{
+    return upload(e, who, what, s, bytes, [=](void *h) { memcpy(h, block, bytes); });
+}
+
 /* the first of n pictures that are known and all have its params; nullptr: they are not (OH_E_ARG, the message set) */
 static const Pic *alike_pics(OhEngine *e, const char *who, const int *pic_ids, int n)
 {
@@ -86,6 +124,26 @@ static const Pic *alike_apart(OhEngine *e, const char *who, const std::vector<in
     if (!p0 || dsts_apart(e, who, dst_ids, n, srcs.data(), (int)srcs.size()))
         return nullptr;
     return p0;
+}
+
+/* ns sources and nd destinations whose params may differ: the sources known and alike, then the destinations, then the destinations
+ * apart.  *s0, *d0: the first of each side.  The engine's device is the current one from here on */
+static int srcs_dsts(OhEngine *e, const char *who, const int *src_ids, int ns, const int *dst_ids, int nd, const Pic **s0, const Pic **d0)
+{
+    if (!(*s0 = alike_pics(e, who, src_ids, ns)) || !(*d0 = alike_pics(e, who, dst_ids, nd)))
+        return OH_E_ARG;
+    OH_TRY(dsts_apart(e, who, dst_ids, nd, src_ids, ns));
+    HIPCHK(e, hipSetDevice(e->device));
+    return OH_OK;
+}
+
+/* pictures `as` of params a and `bs` of params b (the nouns of the refusal) that a call takes only in one bit depth and chroma format */
+static int same_format(OhEngine *e, const char *who, const char *as, const OhPicParams &a, const char *bs, const OhPicParams &b)
+{
+    if (a.bit_depth != b.bit_depth || a.chroma_format_idc != b.chroma_format_idc)
+        FAIL(e, OH_E_UNSUPPORTED, "%s: %s of %d bit, chroma format %d; %s of %d bit, chroma format %d (oh_pics_reformat first)", who, as,
+             a.bit_depth, a.chroma_format_idc, bs, b.bit_depth, b.chroma_format_idc);
+    return OH_OK;
 }
 
 /* a picture's geometry as the kernels take it: planes (1 or 3), bytes between the rows of the first np planes, and the coded size of
@@ -170,21 +228,12 @@ static int table_stage(OhEngine *e, OhEngine::TableCache *tc, const OhColour *co
         tc->cached = false;
         tc->tab.resize((size_t)OH_COLT_N);
         std::string why;
-        const int rc = colour_build(col, tc->tab.data(), tc->misc, &why);
-        if (rc) FAIL(e, rc, "%s: %s", who, why.c_str());
+        OH_TRY(refuse(e, colour_build(col, tc->tab.data(), tc->misc, &why), who, why));
         tc->last = *col; tc->cached = true; tc->on_dev = false;
     }
-    const size_t bytes = (size_t)n_entries * sizeof(int32_t);
-    { const int rc = scratch_reserve(e, &tc->dev, bytes); if (rc) return rc; }           /* the first call's: a cache always asks for as much */
-    if (!tc->on_dev) {
-        OhEngine::Stage *sg = stage_acquire(e, bytes);
-        if (!sg)
-            FAIL(e, OH_E_NOMEM, "%s: no staging buffer for %zu bytes of table%s", who, bytes, n_entries == OH_COLT_N ? "s" : "");
-        memcpy(sg->p, tc->tab.data(), bytes);
-        HIPCHK(e, hipMemcpyAsync(tc->dev.p, sg->p, bytes, hipMemcpyHostToDevice, e->stream));
-        { const int rc = stage_in_use(e, sg, e->stream); if (rc) return rc; }
-        tc->on_dev = true;
-    }
+    if (!tc->on_dev)                                            /* a cache always asks for as many entries: the device copy never grows */
+        OH_TRY(upload_copy(e, who, n_entries == OH_COLT_N ? "tables" : "table", &tc->dev, (size_t)n_entries * sizeof(int32_t), tc->tab.data()));
+    tc->on_dev = true;
     return OH_OK;
 }
 
@@ -192,7 +241,7 @@ static int table_stage(OhEngine *e, OhEngine::TableCache *tc, const OhColour *co
  * in front of the launches, and a pinned buffer; fetch: the copy into it, the one stream wait, and what a kernel that gave up has latched */
 static int results_begin(OhEngine *e, const char *who, OhEngine::Scratch *s, size_t bytes, int n, OhEngine::Stage **sg)
 {
-    { const int rc = scratch_reserve(e, s, bytes); if (rc) return rc; }
+    OH_TRY(scratch_reserve(e, s, bytes));
     *sg = stage_acquire(e, bytes);
     if (!*sg)
         FAIL(e, OH_E_NOMEM, "%s: no staging buffer for %d results", who, n);
@@ -238,7 +287,7 @@ extern "C" int oh_pic_download(OhEngine *e, int pic_id, uint8_t *const planes[3]
         HIPCHK(e, hipMemcpy2DAsync(planes[c], (size_t)strides[c], final_planes(p)[c], (size_t)p->stride[c] * bpp,
                                    (size_t)p->w[c] * bpp, (size_t)p->h[c], hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    { const int ke = kernel_error(e); if (ke) return ke; }     /* a kernel that gave up: these samples are not the picture */
+    OH_TRY(kernel_error(e));     /* a kernel that gave up: these samples are not the picture */
     return OH_OK;
 }
 
@@ -426,7 +475,7 @@ static int pics_md5(OhEngine *e, const int *pic_ids, int n, uint8_t *digests)
     ohk_md5(jobs, nj, out, e->stream);                        /* pinned host memory is mapped: the kernel reads the jobs and writes the digests there */
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    { const int ke = kernel_error(e); if (ke) return ke; }     /* a kernel that gave up: these samples are not the picture */
+    OH_TRY(kernel_error(e));     /* a kernel that gave up: these samples are not the picture */
     for (size_t k = 0; k < slot.size(); k++) {
         if (slot[k] >= 0) memcpy(digests + k * 16, out + (size_t)slot[k] * 16, 16);
         else memset(digests + k * 16, 0, 16);
@@ -440,7 +489,7 @@ extern "C" int oh_pics_md5(OhEngine *e, const int *pic_ids, int n, uint8_t *dige
         return OH_E_ARG;
     if (!n)
         return OH_OK;
-    { const int rc = check_pics(e, pic_ids, n, "oh_pics_md5"); if (rc) return rc; }
+    OH_TRY(check_pics(e, pic_ids, n, "oh_pics_md5"));
     return pics_md5(e, pic_ids, n, digests);
 }
 
@@ -461,7 +510,7 @@ static int pics_crc_checksum(OhEngine *e, const int *pic_ids, int n, int kind, u
     const uint32_t nt = first[nj];
     const size_t o_first = align_up((size_t)nj * sizeof(OhMd5Job), 256), o_map = o_first + align_up(((size_t)nj + 1) * 4, 256),
                  o_part = o_map + align_up((size_t)nt * 8, 256), dev_bytes = o_part + align_up((size_t)nt * 4, 256);
-    { const int rc = scratch_reserve(e, &e->hash_dev, dev_bytes); if (rc) return rc; }    /* every call ends with a wait: the old buffer is idle */
+    OH_TRY(scratch_reserve(e, &e->hash_dev, dev_bytes));    /* every call ends with a wait: the old buffer is idle */
     OhEngine::Stage *sg = stage_acquire(e, o_part + (size_t)nj * 4);
     if (!sg)
         FAIL(e, OH_E_NOMEM, "hipHostMalloc for %d picture hashes failed", n);
@@ -477,7 +526,7 @@ static int pics_crc_checksum(OhEngine *e, const int *pic_ids, int n, int kind, u
              e->stream);
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    { const int ke = kernel_error(e); if (ke) return ke; }
+    OH_TRY(kernel_error(e));
     for (size_t k = 0; k < slot.size(); k++)
         vals[k] = slot[k] >= 0 ? out[slot[k]] : 0;
     return OH_OK;
@@ -491,11 +540,10 @@ extern "C" int oh_pics_hash(OhEngine *e, const int *pic_ids, int n, int hash_typ
         FAIL(e, OH_E_ARG, "oh_pics_hash: hash_type %d (0 MD5, 1 CRC, 2 checksum)", hash_type);
     if (!n)
         return OH_OK;
-    { const int rc = check_pics(e, pic_ids, n, "oh_pics_hash"); if (rc) return rc; }
+    OH_TRY(check_pics(e, pic_ids, n, "oh_pics_hash"));
     std::vector<uint32_t> v((size_t)n * 12);                  /* per picture: MD5 three 16-byte digests, else three values */
     uint8_t *dg = (uint8_t *)v.data();
-    const int rc = hash_type == 0 ? pics_md5(e, pic_ids, n, dg) : pics_crc_checksum(e, pic_ids, n, hash_type, v.data());
-    if (rc) return rc;
+    OH_TRY(hash_type == 0 ? pics_md5(e, pic_ids, n, dg) : pics_crc_checksum(e, pic_ids, n, hash_type, v.data()));
     for (int i = 0; i < n; i++) {
         memset(&out[i], 0, sizeof(out[i]));
         out[i].present = 1; out[i].hash_type = hash_type;
@@ -514,8 +562,8 @@ static int pics_convert(OhEngine *e, const char *who, const int *pic_ids, int n,
     if (!p0) return OH_E_ARG;
     size_t ib = 0;
     std::string why;
-    { const int rc = conv_check(&p0->p, cv, &ib, &why); if (rc) FAIL(e, rc, "%s: %s", who, why.c_str()); }
-    { const int rc = image_run_check(e, who, "dst", dst, n, ib, (size_t)conv_sample_bytes(cv, p0->p.bit_depth), image_stride, dst_bytes); if (rc) return rc; }
+    OH_TRY(refuse(e, conv_check(&p0->p, cv, &ib, &why), who, why));
+    OH_TRY(image_run_check(e, who, "dst", dst, n, ib, (size_t)conv_sample_bytes(cv, p0->p.bit_depth), image_stride, dst_bytes));
     OhColArgs ca;
     OhConvArgs &a = ca.c;
     memset(&ca, 0, sizeof(ca));
@@ -525,24 +573,19 @@ static int pics_convert(OhEngine *e, const char *who, const int *pic_ids, int n,
     if (cv->format >= OH_CONV_RGB_PLANAR) {
         OhConvert k16 = *cv;
         if (col) k16.sample = OH_CONV_U16;                      /* the colour stages start from the 16-bit R'G'B' */
-        const int rc = oh_convert_coeffs(&k16, a.bd, a.k, OH_CONV_NCOEFFS);
-        if (rc) FAIL(e, rc, "%s: no coefficients for this conversion", who);
+        OH_TRY(refuse(e, oh_convert_coeffs(&k16, a.bd, a.k, OH_CONV_NCOEFFS), who, "no coefficients for this conversion"));
     }
     if (col) {
-        const int rc = table_stage(e, &e->colour_tabs, col, OH_COLT_N, who);
-        if (rc) return rc;
+        OH_TRY(table_stage(e, &e->colour_tabs, col, OH_COLT_N, who));
         ca.tab = (const int32_t *)e->colour_tabs.dev.p;
         memcpy(ca.misc, e->colour_tabs.misc, sizeof(ca.misc));
     }
-    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
-        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+    return launch_sets(e, n, [&](int i0, int m) {
         for (int i = 0; i < m; i++) read_planes(get_pic(e, pic_ids[i0 + i]), n_planes(p0->p), a.src[i]);
         a.dst = (char *)dst + (size_t)i0 * image_stride;
         if (col) ohk_colour(&ca, cv->format, cv->sample, m, e->stream);
         else     ohk_convert(&a, cv->format, cv->sample, m, e->stream);
-        HIPCHK(e, hipGetLastError());
-    }
-    return OH_OK;
+    });
 }
 
 extern "C" int oh_pics_convert(OhEngine *e, const int *pic_ids, int n, const OhConvert *cv, void *dst, size_t image_stride, size_t dst_bytes)
@@ -564,11 +607,11 @@ extern "C" int oh_pics_import(OhEngine *e, const int *pic_ids, int n, const OhCo
         return OH_OK;
     const Pic *p0 = alike_pics(e, who, pic_ids, n);
     if (!p0) return OH_E_ARG;
-    { const int rc = dsts_apart(e, who, pic_ids, n, nullptr, 0); if (rc) return rc; }
+    OH_TRY(dsts_apart(e, who, pic_ids, n, nullptr, 0));
     size_t ib = 0;
     std::string why;
-    { const int rc = conv_check(&p0->p, cv, &ib, &why); if (rc) FAIL(e, rc, "%s: %s", who, why.c_str()); }
-    { const int rc = image_run_check(e, who, "src", src, n, ib, (size_t)conv_sample_bytes(cv, p0->p.bit_depth), image_stride, src_bytes); if (rc) return rc; }
+    OH_TRY(refuse(e, conv_check(&p0->p, cv, &ib, &why), who, why));
+    OH_TRY(image_run_check(e, who, "src", src, n, ib, (size_t)conv_sample_bytes(cv, p0->p.bit_depth), image_stride, src_bytes));
     OhImpArgs a;
     memset(&a, 0, sizeof(a));
     const OhPicParams &p = p0->p;
@@ -580,18 +623,13 @@ extern "C" int oh_pics_import(OhEngine *e, const int *pic_ids, int n, const OhCo
     a.cf = p.chroma_format_idc; a.bd = p.bit_depth; a.filter = cv->chroma_filter;
     a.nc = cv->format == OH_CONV_RGBA ? 4 : 3;
     a.image_stride = image_stride;
-    if (cv->format >= OH_CONV_RGB_PLANAR) {
-        const int rc = oh_import_coeffs(cv, p.bit_depth, a.k, OH_IMPORT_NCOEFFS);
-        if (rc) FAIL(e, rc, "%s: no coefficients for this conversion", who);
-    }
-    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
-        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+    if (cv->format >= OH_CONV_RGB_PLANAR)
+        OH_TRY(refuse(e, oh_import_coeffs(cv, p.bit_depth, a.k, OH_IMPORT_NCOEFFS), who, "no coefficients for this conversion"));
+    return launch_sets(e, n, [&](int i0, int m) {
         for (int i = 0; i < m; i++) write_planes(get_pic(e, pic_ids[i0 + i]), np, a.dst[i]);
         a.src = (const char *)src + (size_t)i0 * image_stride;
         ohk_import(&a, cv->format, cv->sample, m, e->stream);
-        HIPCHK(e, hipGetLastError());
-    }
-    return OH_OK;
+    });
 }
 
 /* ---------------- colour conversion (colour.hip) ---------------- */
@@ -601,7 +639,7 @@ extern "C" int oh_pics_convert_colour(OhEngine *e, const int *pic_ids, int n, co
     if (!e || n < 0 || !cv || !col || (n && !pic_ids))
         return OH_E_ARG;
     std::string why;
-    { const int rc = colour_check(col, &why); if (rc) FAIL(e, rc, "oh_pics_convert_colour: %s", why.c_str()); }
+    OH_TRY(refuse(e, colour_check(col, &why), "oh_pics_convert_colour", why));
     if (cv->format >= OH_CONV_PLANAR && cv->format <= OH_CONV_SEMIPLANAR)
         FAIL(e, OH_E_UNSUPPORTED, "oh_pics_convert_colour: format %d is a YUV format", cv->format);
     if (col->out_transfer == OH_COL_LINEAR && (cv->sample == OH_CONV_U8 || cv->sample == OH_CONV_U16))
@@ -637,7 +675,7 @@ extern "C" int oh_pics_light_level(OhEngine *e, const int *pic_ids, int n, const
         FAIL(e, OH_E_ARG, "%s: src_peak is finite and positive", who);
     const OhColour col = light_colour(sp);
     std::string why;
-    { const int rc = colour_check(&col, &why); if (rc) FAIL(e, OH_E_UNSUPPORTED, "%s: %s", who, why.c_str()); }
+    OH_TRY(refuse(e, colour_check(&col, &why) ? OH_E_UNSUPPORTED : OH_OK, who, why));
     if (!n)
         return OH_OK;
     const Pic *p0 = alike_pics(e, who, pic_ids, n);
@@ -645,13 +683,13 @@ extern "C" int oh_pics_light_level(OhEngine *e, const int *pic_ids, int n, const
     OhConvert k16 = *cv;                                        /* format and sample are not the caller's to set: the 16-bit R'G'B' */
     k16.format = OH_CONV_RGB; k16.sample = OH_CONV_U16;
     size_t ib = 0;
-    { const int rc = conv_check(&p0->p, &k16, &ib, &why); if (rc) FAIL(e, rc, "%s: %s", who, why.c_str()); }
+    OH_TRY(refuse(e, conv_check(&p0->p, &k16, &ib, &why), who, why));
     HIPCHK(e, hipSetDevice(e->device));
     OhLightArgs la;
     OhConvArgs &a = la.c;
     memset(&la, 0, sizeof(la));
     conv_args(&a, p0, cv);
-    { const int rc = oh_convert_coeffs(&k16, a.bd, a.k, OH_CONV_NCOEFFS); if (rc) FAIL(e, rc, "%s: no coefficients for this conversion", who); }
+    OH_TRY(refuse(e, oh_convert_coeffs(&k16, a.bd, a.k, OH_CONV_NCOEFFS), who, "no coefficients for this conversion"));
     la.luma = sp->norm == OH_NORM_LUMA;
     /* table A alone, in a cache of its own; the call ends with a wait, so no launch reads the device copy while it changes */
     { const int rc = table_stage(e, &e->light_tabs, &col, OH_COLT_G, who); if (rc) return rc == OH_E_ARG ? OH_E_UNSUPPORTED : rc; }
@@ -659,15 +697,13 @@ extern "C" int oh_pics_light_level(OhEngine *e, const int *pic_ids, int n, const
     for (int j = 0; j < 3; j++) la.w[j] = e->light_tabs.misc[9 + j];
     const size_t bytes = (size_t)n * sizeof(OhLightDev);
     OhEngine::Stage *sg = nullptr;
-    { const int rc = results_begin(e, who, &e->light_res, bytes, n, &sg); if (rc) return rc; }
-    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
-        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+    OH_TRY(results_begin(e, who, &e->light_res, bytes, n, &sg));
+    OH_TRY(launch_sets(e, n, [&](int i0, int m) {
         for (int i = 0; i < m; i++) read_planes(get_pic(e, pic_ids[i0 + i]), n_planes(p0->p), a.src[i]);
         la.res = (OhLightDev *)e->light_res.p + i0;
         ohk_light(&la, m, e->stream);
-        HIPCHK(e, hipGetLastError());
-    }
-    { const int rc = results_fetch(e, &e->light_res, bytes, sg); if (rc) return rc; }
+    }));
+    OH_TRY(results_fetch(e, &e->light_res, bytes, sg));
     const OhLightDev *r = (const OhLightDev *)sg->p;
     for (int i = 0; i < n; i++) {
         out[i].pixels = (uint64_t)a.W * (uint64_t)a.H;
@@ -695,37 +731,31 @@ extern "C" int oh_pics_compare(OhEngine *e, const int *a_ids, const int *b_ids, 
     const OhPicParams &p = p0->p;
     std::string why;
     if (!crop_window_ok(&p, sp->win, true, &why))
-        FAIL(e, OH_E_ARG, "%s: %s", who, why.c_str());
+        return refuse(e, OH_E_ARG, who, why);
     HIPCHK(e, hipSetDevice(e->device));
     OhCmpArgs a;
     memset(&a, 0, sizeof(a));
     const int np = n_planes(p);
-    int W, H;
-    window_size(&p, sp->win, &W, &H);
     row_pitches(p0, np, a.pitch);
     for (int c = 0; c < (np > 1 ? 2 : 1); c++) {
         OhCmpClass &k = a.k[c];
-        const int hs = oh_hshift(&p, c), vs = oh_vshift(&p, c);
-        k.x0 = sp->win.left >> hs; k.y0 = sp->win.top >> vs;
-        k.w = W >> hs; k.h = H >> vs;
+        class_window(&p, sp->win, c, &k.x0, &k.y0, &k.w, &k.h);
         k.tx = std::max(1, ((k.w >> 2) + OH_CMP_TW / 4 - 1) / (OH_CMP_TW / 4));
         k.ty = std::max(1, ((k.h >> 2) + OH_CMP_TH / 4 - 1) / (OH_CMP_TH / 4));
     }
     a.np = np; a.bd = p.bit_depth; a.ssim = (sp->flags & OH_CMP_SSIM) != 0;
     const size_t bytes = (size_t)n * 3 * OH_CMP_SLOTS * sizeof(OhCmpDev);
     OhEngine::Stage *sg = nullptr;
-    { const int rc = results_begin(e, who, &e->compare_res, bytes, n, &sg); if (rc) return rc; }
-    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
-        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+    OH_TRY(results_begin(e, who, &e->compare_res, bytes, n, &sg));
+    OH_TRY(launch_sets(e, n, [&](int i0, int m) {
         for (int i = 0; i < m; i++) {
             read_planes(get_pic(e, a_ids[i0 + i]), np, a.a[i]);
             read_planes(get_pic(e, b_ids[i0 + i]), np, a.b[i]);
         }
         a.res = (OhCmpDev *)e->compare_res.p + (size_t)i0 * 3 * OH_CMP_SLOTS;
         ohk_compare(&a, m, e->stream);
-        HIPCHK(e, hipGetLastError());
-    }
-    { const int rc = results_fetch(e, &e->compare_res, bytes, sg); if (rc) return rc; }
+    }));
+    OH_TRY(results_fetch(e, &e->compare_res, bytes, sg));
     const OhCmpDev *r = (const OhCmpDev *)sg->p;
     for (int i = 0; i < n; i++) {
         memset(&out[i], 0, sizeof(out[i]));
@@ -777,21 +807,17 @@ static int resize_axis(int S, int T, int filter, int phase, ResizeAxis *ax)
     return oh_resize_taps(S, T, filter, phase, ax->first.data(), ax->k.data(), ax->mt, ax->cnt.data());
 }
 
-/* what oh_pics_resize checks of its arguments (n > 0, the lists present) */
-static int resize_check(OhEngine *e, const int *src_ids, const int *dst_ids, int n, const OhResize *rs)
+/* what oh_pics_resize checks of its arguments (n > 0, the lists present); *s0, *d0: the first source and destination */
+static int resize_check(OhEngine *e, const int *src_ids, const int *dst_ids, int n, const OhResize *rs, const Pic **s0, const Pic **d0)
 {
-    const Pic *s0 = alike_pics(e, "oh_pics_resize", src_ids, n);
-    if (!s0) return OH_E_ARG;
-    const Pic *d0 = alike_pics(e, "oh_pics_resize", dst_ids, n);
-    if (!d0) return OH_E_ARG;
-    { const int rc = dsts_apart(e, "oh_pics_resize", dst_ids, n, src_ids, n); if (rc) return rc; }
-    const OhPicParams &sp = s0->p, &dp = d0->p;
+    OH_TRY(srcs_dsts(e, "oh_pics_resize", src_ids, n, dst_ids, n, s0, d0));
+    const OhPicParams &sp = (*s0)->p, &dp = (*d0)->p;
     if (rs->filter != OH_RESIZE_BILINEAR && rs->filter != OH_RESIZE_BICUBIC)
         FAIL(e, OH_E_ARG, "oh_pics_resize: filter %d (0 bilinear, 1 bicubic)", rs->filter);
     const int cf = sp.chroma_format_idc, hs = cf == 1 || cf == 2, vs = cf == 1, sw = 1 << hs, sv = 1 << vs;
     std::string why;
     if (!crop_window_ok(&sp, rs->win, true, &why))
-        FAIL(e, OH_E_ARG, "oh_pics_resize: %s", why.c_str());
+        return refuse(e, OH_E_ARG, "oh_pics_resize", why);
     /* the size rules read the SOURCES' chroma format: a destination of another format is refused below */
     if (rs->width < 1 || rs->height < 1 || rs->width > dp.width || rs->height > dp.height || rs->width % sw || rs->height % sv)
         FAIL(e, OH_E_ARG, "oh_pics_resize: image %dx%d: below 1, above the destination's %dx%d, or not multiples of %dx%d", rs->width, rs->height,
@@ -817,19 +843,19 @@ static int resize_plan(OhEngine *e, const Pic *s0, const Pic *d0, const OhResize
 {
     const OhPicParams &sp = s0->p;
     const OhWindow &w = rs->win;
-    const int cf = sp.chroma_format_idc, hs = cf == 1 || cf == 2, vs = cf == 1, bpp = sample_bytes(sp.bit_depth);
-    int W, H;
-    window_size(&sp, w, &W, &H);
+    const int bpp = sample_bytes(sp.bit_depth);
     memset(a, 0, sizeof(*a));
     a->np = n_planes(sp); a->bd = sp.bit_depth;
-    pl->ncls = cf ? 2 : 1;
+    pl->ncls = a->np > 1 ? 2 : 1;
     uint64_t mid_pic = 0;
     for (int c = 0; c < pl->ncls; c++) {
         OhResizeClass &k = a->k[c];
         const ResizeAxis &hx = pl->hx[c], &vx = pl->vx[c];
-        const int Sw = W >> (c ? hs : 0), Sh = H >> (c ? vs : 0);
-        k.x0 = w.left >> (c ? hs : 0); k.y0 = w.top >> (c ? vs : 0); k.sh = Sh;
-        k.tw = rs->width >> (c ? hs : 0); k.th = rs->height >> (c ? vs : 0);
+        const int hs = oh_hshift(&sp, c), vs = oh_vshift(&sp, c);
+        int32_t Sw, Sh;
+        class_window(&sp, w, c, &k.x0, &k.y0, &Sw, &Sh);
+        k.sh = Sh;
+        k.tw = rs->width >> hs; k.th = rs->height >> vs;
         k.cw = d0->w[c]; k.ch = d0->h[c];
         k.src_pitch = s0->stride[c] * bpp; k.dst_pitch = d0->stride[c] * bpp;
         k.mid_stride = (int32_t)align_up((size_t)k.tw + 1, 64);
@@ -921,16 +947,13 @@ static void resize_fill(const ResizePlan &pl, OhResizeArgs *a, char *h, const ch
 /* the pictures of the call in sets of at most per_set (what the intermediate has room for), one launch set each */
 static int resize_launch(OhEngine *e, const int *src_ids, const int *dst_ids, int n, int per_set, int pad, OhResizeArgs *a)
 {
-    for (int i0 = 0; i0 < n; i0 += per_set) {
-        const int m = std::min(n - i0, per_set);
+    return launch_sets(e, n, [&](int i0, int m) {
         for (int i = 0; i < m; i++) {
             read_planes(get_pic(e, src_ids[i0 + i]), a->np, a->src[i]);
             write_planes(get_pic(e, dst_ids[i0 + i]), a->np, a->dst[i]);
         }
         ohk_resize(a, m, pad, e->stream);
-        HIPCHK(e, hipGetLastError());
-    }
-    return OH_OK;
+    }, per_set);
 }
 
 extern "C" int oh_pics_resize(OhEngine *e, const int *src_ids, const int *dst_ids, int n, const OhResize *rs)
@@ -939,27 +962,19 @@ extern "C" int oh_pics_resize(OhEngine *e, const int *src_ids, const int *dst_id
         return OH_E_ARG;
     if (!n)
         return OH_OK;
-    { const int rc = resize_check(e, src_ids, dst_ids, n, rs); if (rc) return rc; }
-    const Pic *s0 = get_pic(e, src_ids[0]), *d0 = get_pic(e, dst_ids[0]);
+    const Pic *s0, *d0;
+    OH_TRY(resize_check(e, src_ids, dst_ids, n, rs, &s0, &d0));
     OhResizeArgs a;
     ResizePlan pl;
-    { const int rc = resize_plan(e, s0, d0, rs, &a, &pl); if (rc) return rc; }
+    OH_TRY(resize_plan(e, s0, d0, rs, &a, &pl));
     const size_t mid_bytes = (size_t)a.mid_pic * 2;
     const int per_set = (int)std::max<size_t>(1, std::min<size_t>(OH_RESIZE_MAX_PICS, ((size_t)512 << 20) / mid_bytes));
     const size_t need = pl.tab + (size_t)std::min(n, per_set) * mid_bytes;
-    HIPCHK(e, hipSetDevice(e->device));
     if (need > e->resize_dev.bytes)
         HIPCHK(e, hipStreamSynchronize(e->stream));              /* launches of earlier calls still use the old buffer */
-    { const int rc = scratch_reserve(e, &e->resize_dev, need); if (rc) return rc; }
-    /* the tables: built in a pinned buffer of the pool, copied on the engine stream — behind the launches of an earlier call that
-     * read the device copy, in front of this call's */
-    OhEngine::Stage *sg = stage_acquire(e, pl.tab);
-    if (!sg)
-        FAIL(e, OH_E_NOMEM, "oh_pics_resize: no staging buffer for %zu bytes of tap tables", pl.tab);
+    OH_TRY(scratch_reserve(e, &e->resize_dev, need));            /* the tables, then the intermediate of a launch set */
     char *d = (char *)e->resize_dev.p;
-    resize_fill(pl, &a, (char *)sg->p, d);
-    HIPCHK(e, hipMemcpyAsync(d, sg->p, pl.tab, hipMemcpyHostToDevice, e->stream));
-    { const int rc = stage_in_use(e, sg, e->stream); if (rc) return rc; }
+    OH_TRY(upload(e, "oh_pics_resize", "tap tables", &e->resize_dev, pl.tab, [&](void *h) { resize_fill(pl, &a, (char *)h, d); }));
     a.mid = (int16_t *)(d + pl.tab);
     return resize_launch(e, src_ids, dst_ids, n, per_set, rs->width < d0->p.width || rs->height < d0->p.height, &a);
 }
@@ -976,15 +991,11 @@ extern "C" int oh_pics_reformat(OhEngine *e, const int *src_ids, const int *dst_
         FAIL(e, OH_E_ARG, "%s: chroma_down %d, chroma_up %d (0 point, 1 linear)", who, rf->chroma_down, rf->chroma_up);
     if (!n)
         return OH_OK;
-    const Pic *s0 = alike_pics(e, who, src_ids, n);
-    if (!s0) return OH_E_ARG;
-    const Pic *d0 = alike_pics(e, who, dst_ids, n);
-    if (!d0) return OH_E_ARG;
-    { const int rc = dsts_apart(e, who, dst_ids, n, src_ids, n); if (rc) return rc; }
+    const Pic *s0, *d0;
+    OH_TRY(srcs_dsts(e, who, src_ids, n, dst_ids, n, &s0, &d0));
     const OhPicParams &sp = s0->p, &dp = d0->p;
     if (sp.width != dp.width || sp.height != dp.height)
         FAIL(e, OH_E_ARG, "%s: sources of %dx%d, destinations of %dx%d", who, sp.width, sp.height, dp.width, dp.height);
-    HIPCHK(e, hipSetDevice(e->device));
     OhRfArgs a;
     memset(&a, 0, sizeof(a));
     const int snp = n_planes(sp), dnp = n_planes(dp);            /* sources and destinations: each side its own plane count */
@@ -993,16 +1004,13 @@ extern "C" int oh_pics_reformat(OhEngine *e, const int *src_ids, const int *dst_
     a.scf = sp.chroma_format_idc; a.dcf = dp.chroma_format_idc;
     a.sbd = sp.bit_depth; a.dbd = dp.bit_depth;
     a.depth = rf->depth; a.down = rf->chroma_down; a.up = rf->chroma_up;
-    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
-        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+    return launch_sets(e, n, [&](int i0, int m) {
         for (int i = 0; i < m; i++) {
             read_planes(get_pic(e, src_ids[i0 + i]), snp, a.src[i]);
             write_planes(get_pic(e, dst_ids[i0 + i]), dnp, a.dst[i]);
         }
         ohk_reformat(&a, m, e->stream);
-        HIPCHK(e, hipGetLastError());
-    }
-    return OH_OK;
+    });
 }
 
 /* ---------------- orientation: crop, flip, rotate, transpose (orient.hip) ---------------- */
@@ -1015,49 +1023,36 @@ extern "C" int oh_pics_orient(OhEngine *e, const int *src_ids, const int *dst_id
         FAIL(e, OH_E_ARG, "%s: orientation %d (0 .. 7: any OR of HFLIP 1, VFLIP 2, TRANSPOSE 4)", who, o->orientation);
     if (!n)
         return OH_OK;
-    const Pic *s0 = alike_pics(e, who, src_ids, n);
-    if (!s0) return OH_E_ARG;
-    const Pic *d0 = alike_pics(e, who, dst_ids, n);
-    if (!d0) return OH_E_ARG;
-    { const int rc = dsts_apart(e, who, dst_ids, n, src_ids, n); if (rc) return rc; }
+    const Pic *s0, *d0;
+    OH_TRY(srcs_dsts(e, who, src_ids, n, dst_ids, n, &s0, &d0));
     const OhPicParams &sp = s0->p, &dp = d0->p;
     const OhWindow &w = o->win;
     std::string why;
     if (!crop_window_ok(&sp, w, true, &why))
-        FAIL(e, OH_E_ARG, "%s: %s", who, why.c_str());
-    const int cf = sp.chroma_format_idc, hs = cf == 1 || cf == 2, vs = cf == 1;
-    if (dp.bit_depth != sp.bit_depth || dp.chroma_format_idc != cf)
-        FAIL(e, OH_E_UNSUPPORTED, "%s: destinations of %d bit, chroma format %d; sources of %d bit, chroma format %d (oh_pics_reformat first)", who,
-             dp.bit_depth, dp.chroma_format_idc, sp.bit_depth, cf);
-    const bool tr = o->orientation & OH_ORIENT_TRANSPOSE;
-    if (tr && cf == 2)
+        return refuse(e, OH_E_ARG, who, why);
+    OH_TRY(same_format(e, who, "destinations", dp, "sources", sp));
+    if ((o->orientation & OH_ORIENT_TRANSPOSE) && sp.chroma_format_idc == 2)
         FAIL(e, OH_E_UNSUPPORTED, "%s: orientation %d transposes 4:2:2 pictures into 4:4:0 (reformat to 4:2:0 or 4:4:4 first)", who, o->orientation);
     int W, H, iw = 0, ih = 0;
     window_size(&sp, w, &W, &H);
     (void)oh_orient_size(o->orientation, W, H, &iw, &ih);
     if (iw > dp.width || ih > dp.height)
         FAIL(e, OH_E_ARG, "%s: the image of %dx%d does not fit the destinations' %dx%d", who, iw, ih, dp.width, dp.height);
-    HIPCHK(e, hipSetDevice(e->device));
     OhOrArgs a;
     memset(&a, 0, sizeof(a));
     a.np = n_planes(sp); a.bd = sp.bit_depth; a.orientation = o->orientation;
     row_pitches(s0, a.np, a.spitch);
     row_pitches(d0, a.np, a.dpitch);
     class_sizes(d0, a.np, a.dw, a.dh);
-    for (int q = 0; q < (cf ? 2 : 1); q++) {
-        a.x0[q] = w.left >> (q ? hs : 0); a.y0[q] = w.top >> (q ? vs : 0);
-        a.ws[q] = W >> (q ? hs : 0); a.hs[q] = H >> (q ? vs : 0);
-    }
-    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
-        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+    for (int q = 0; q < (a.np > 1 ? 2 : 1); q++)
+        class_window(&sp, w, q, &a.x0[q], &a.y0[q], &a.ws[q], &a.hs[q]);
+    return launch_sets(e, n, [&](int i0, int m) {
         for (int i = 0; i < m; i++) {
             read_planes(get_pic(e, src_ids[i0 + i]), a.np, a.src[i]);
             write_planes(get_pic(e, dst_ids[i0 + i]), a.np, a.dst[i]);
         }
         ohk_orient(&a, m, e->stream);
-        HIPCHK(e, hipGetLastError());
-    }
-    return OH_OK;
+    });
 }
 
 /* ---------------- warping: affine and perspective resampling (warp.hip) ---------------- */
@@ -1068,29 +1063,21 @@ extern "C" int oh_pics_warp(OhEngine *e, const int *src_ids, const int *dst_ids,
         return OH_E_ARG;
     std::string why;
     if (warp_check(w, 16, &why) || warp_image_check(w, &why))           /* the fill against the depth: below, with the pictures */
-        FAIL(e, OH_E_ARG, "%s: %s", who, why.c_str());
+        return refuse(e, OH_E_ARG, who, why);
     if (!n)
         return OH_OK;
-    const Pic *s0 = alike_pics(e, who, src_ids, n);
-    if (!s0) return OH_E_ARG;
-    const Pic *d0 = alike_pics(e, who, dst_ids, n);
-    if (!d0) return OH_E_ARG;
-    { const int rc = dsts_apart(e, who, dst_ids, n, src_ids, n); if (rc) return rc; }
+    const Pic *s0, *d0;
+    OH_TRY(srcs_dsts(e, who, src_ids, n, dst_ids, n, &s0, &d0));
     const OhPicParams &sp = s0->p, &dp = d0->p;
     if (!crop_window_ok(&sp, w->win, true, &why))
-        FAIL(e, OH_E_ARG, "%s: %s", who, why.c_str());
-    const int cf = sp.chroma_format_idc, hs = cf == 1 || cf == 2, vs = cf == 1;
-    if (dp.bit_depth != sp.bit_depth || dp.chroma_format_idc != cf)
-        FAIL(e, OH_E_UNSUPPORTED, "%s: destinations of %d bit, chroma format %d; sources of %d bit, chroma format %d (oh_pics_reformat first)", who,
-             dp.bit_depth, dp.chroma_format_idc, sp.bit_depth, cf);
+        return refuse(e, OH_E_ARG, who, why);
+    const int hs = oh_hshift(&sp, 1), vs = oh_vshift(&sp, 1);
+    OH_TRY(same_format(e, who, "destinations", dp, "sources", sp));
     if (w->width > dp.width || w->height > dp.height || w->width % (1 << hs) || w->height % (1 << vs))
         FAIL(e, OH_E_ARG, "%s: image %dx%d: above the destination's %dx%d, or not multiples of %dx%d", who, w->width, w->height, dp.width, dp.height,
              1 << hs, 1 << vs);
     if (warp_check(w, sp.bit_depth, &why))
-        FAIL(e, OH_E_ARG, "%s: %s", who, why.c_str());
-    int W, H;
-    window_size(&sp, w->win, &W, &H);
-    HIPCHK(e, hipSetDevice(e->device));
+        return refuse(e, OH_E_ARG, who, why);
     OhWarpArgs a;
     memset(&a, 0, sizeof(a));
     a.np = n_planes(sp); a.bd = sp.bit_depth; a.sx = hs; a.sy = vs;
@@ -1100,21 +1087,17 @@ extern "C" int oh_pics_warp(OhEngine *e, const int *src_ids, const int *dst_ids,
     row_pitches(s0, a.np, a.spitch);
     row_pitches(d0, a.np, a.dpitch);
     class_sizes(d0, a.np, a.dw, a.dh);
-    for (int q = 0; q < (cf ? 2 : 1); q++) {
-        a.x0[q] = w->win.left >> (q ? hs : 0); a.y0[q] = w->win.top >> (q ? vs : 0);
-        a.ws[q] = W >> (q ? hs : 0); a.hs[q] = H >> (q ? vs : 0);
-        a.iw[q] = w->width >> (q ? hs : 0); a.ih[q] = w->height >> (q ? vs : 0);
+    for (int q = 0; q < (a.np > 1 ? 2 : 1); q++) {
+        class_window(&sp, w->win, q, &a.x0[q], &a.y0[q], &a.ws[q], &a.hs[q]);
+        a.iw[q] = w->width >> oh_hshift(&sp, q); a.ih[q] = w->height >> oh_vshift(&sp, q);
     }
-    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
-        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+    return launch_sets(e, n, [&](int i0, int m) {
         for (int i = 0; i < m; i++) {
             read_planes(get_pic(e, src_ids[i0 + i]), a.np, a.src[i]);
             write_planes(get_pic(e, dst_ids[i0 + i]), a.np, a.dst[i]);
         }
         ohk_warp(&a, m, e->stream);
-        HIPCHK(e, hipGetLastError());
-    }
-    return OH_OK;
+    });
 }
 
 /* ---------------- fields and deinterlacing (deinterlace.hip) ---------------- */
@@ -1122,9 +1105,7 @@ extern "C" int oh_pics_warp(OhEngine *e, const int *src_ids, const int *dst_ids,
 static int fields_check(OhEngine *e, const char *who, const Pic *f0, const Pic *F0)
 {
     const OhPicParams &fp = f0->p, &Fp = F0->p;
-    if (fp.bit_depth != Fp.bit_depth || fp.chroma_format_idc != Fp.chroma_format_idc)
-        FAIL(e, OH_E_UNSUPPORTED, "%s: fields of %d bit, chroma format %d; frames of %d bit, chroma format %d (oh_pics_reformat first)", who,
-             fp.bit_depth, fp.chroma_format_idc, Fp.bit_depth, Fp.chroma_format_idc);
+    OH_TRY(same_format(e, who, "fields", fp, "frames", Fp));
     if (fp.width != Fp.width || Fp.height != 2 * fp.height)
         FAIL(e, OH_E_ARG, "%s: fields of %dx%d, frames of %dx%d (the same width, twice the height)", who, fp.width, fp.height, Fp.width, Fp.height);
     return OH_OK;
@@ -1133,7 +1114,6 @@ static int fields_check(OhEngine *e, const char *who, const Pic *f0, const Pic *
 /* the launches of weave and separate: role[k] (null: not in this call) holds the ids of a.pic[k]; wr: the roles that are written */
 static int fields_launch(OhEngine *e, const Pic *f0, const Pic *F0, const int *const role[4], unsigned wr, int op, int sides, int n)
 {
-    HIPCHK(e, hipSetDevice(e->device));
     OhDiArgs a;
     memset(&a, 0, sizeof(a));
     const OhPicParams &Fp = F0->p;
@@ -1141,8 +1121,7 @@ static int fields_launch(OhEngine *e, const Pic *f0, const Pic *F0, const int *c
     row_pitches(F0, a.np, a.pitch);
     row_pitches(f0, a.np, a.fpitch);
     class_sizes(F0, a.np, a.w, a.h);
-    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
-        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+    return launch_sets(e, n, [&](int i0, int m) {
         for (int k = 0; k < 4; k++) {
             if (!role[k])
                 continue;
@@ -1153,9 +1132,7 @@ static int fields_launch(OhEngine *e, const Pic *f0, const Pic *F0, const int *c
             }
         }
         ohk_fields(&a, m, e->stream);
-        HIPCHK(e, hipGetLastError());
-    }
-    return OH_OK;
+    });
 }
 
 extern "C" int oh_pics_weave(OhEngine *e, const int *top_ids, const int *bottom_ids, const int *dst_ids, int n)
@@ -1167,12 +1144,9 @@ extern "C" int oh_pics_weave(OhEngine *e, const int *top_ids, const int *bottom_
         return OH_OK;
     std::vector<int> fields(top_ids, top_ids + n);
     fields.insert(fields.end(), bottom_ids, bottom_ids + n);
-    const Pic *f0 = alike_pics(e, who, fields.data(), 2 * n);
-    if (!f0) return OH_E_ARG;
-    const Pic *F0 = alike_pics(e, who, dst_ids, n);
-    if (!F0) return OH_E_ARG;
-    { const int rc = dsts_apart(e, who, dst_ids, n, fields.data(), 2 * n); if (rc) return rc; }
-    { const int rc = fields_check(e, who, f0, F0); if (rc) return rc; }
+    const Pic *f0, *F0;
+    OH_TRY(srcs_dsts(e, who, fields.data(), 2 * n, dst_ids, n, &f0, &F0));
+    OH_TRY(fields_check(e, who, f0, F0));
     const int *const role[4] = { top_ids, bottom_ids, nullptr, dst_ids };
     return fields_launch(e, f0, F0, role, 1u << 3, OH_DI_WEAVE, 3, n);
 }
@@ -1187,12 +1161,9 @@ extern "C" int oh_pics_separate(OhEngine *e, const int *src_ids, const int *top_
     std::vector<int> fields;
     if (top_ids) fields.insert(fields.end(), top_ids, top_ids + n);
     if (bottom_ids) fields.insert(fields.end(), bottom_ids, bottom_ids + n);
-    const Pic *F0 = alike_pics(e, who, src_ids, n);
-    if (!F0) return OH_E_ARG;
-    const Pic *f0 = alike_pics(e, who, fields.data(), (int)fields.size());
-    if (!f0) return OH_E_ARG;
-    { const int rc = dsts_apart(e, who, fields.data(), (int)fields.size(), src_ids, n); if (rc) return rc; }
-    { const int rc = fields_check(e, who, f0, F0); if (rc) return rc; }
+    const Pic *F0, *f0;
+    OH_TRY(srcs_dsts(e, who, src_ids, n, fields.data(), (int)fields.size(), &F0, &f0));
+    OH_TRY(fields_check(e, who, f0, F0));
     const int *const role[4] = { src_ids, nullptr, top_ids, bottom_ids };
     return fields_launch(e, f0, F0, role, 3u << 2, OH_DI_SEPARATE, (top_ids ? 1 : 0) | (bottom_ids ? 2 : 0), n);
 }
@@ -1210,7 +1181,7 @@ extern "C" int oh_pics_deinterlace(OhEngine *e, const int *prev_ids, const int *
     if (!n)
         return OH_OK;
     Neighbours nb;                                              /* prev and next: read by ADAPTIVE only */
-    { const int rc = neighbours(e, who, "cur", prev_ids, cur_ids, next_ids, n, d->mode == OH_DEINT_ADAPTIVE, &nb); if (rc) return rc; }
+    OH_TRY(neighbours(e, who, "cur", prev_ids, cur_ids, next_ids, n, d->mode == OH_DEINT_ADAPTIVE, &nb));
     const Pic *p0 = alike_apart(e, who, nb.srcs, dst_ids, n);
     if (!p0) return OH_E_ARG;
     const OhPicParams &p = p0->p;
@@ -1224,8 +1195,7 @@ extern "C" int oh_pics_deinterlace(OhEngine *e, const int *prev_ids, const int *
     for (int q = 0; q < (a.np > 1 ? 2 : 1); q++)
         if (a.h[q] < 2 || (a.h[q] & 1))
             FAIL(e, OH_E_ARG, "%s: planes of %d rows (an even number, 2 at least)", who, a.h[q]);
-    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
-        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+    return launch_sets(e, n, [&](int i0, int m) {
         for (int i = 0; i < m; i++) {
             read_planes(get_pic(e, nb.around[0][i0 + i]), a.np, a.pic[0][i]);
             read_planes(get_pic(e, cur_ids[i0 + i]), a.np, a.pic[1][i]);
@@ -1233,9 +1203,7 @@ extern "C" int oh_pics_deinterlace(OhEngine *e, const int *prev_ids, const int *
             write_planes(get_pic(e, dst_ids[i0 + i]), a.np, a.pic[3][i]);
         }
         ohk_deinterlace(&a, m, e->stream);
-        HIPCHK(e, hipGetLastError());
-    }
-    return OH_OK;
+    });
 }
 
 /* ---------------- filters (filter.hip) ---------------- */
@@ -1249,20 +1217,15 @@ extern "C" int oh_pics_filter(OhEngine *e, const int *prev_ids, const int *src_i
         FAIL(e, OH_E_ARG, "%s: mode %d (0 convolve, 1 unsharp, 2 median, 3 temporal)", who, f->mode);
     if (!n) {                                                   /* no picture, no bit depth: what does not depend on one */
         std::string why;
-        const int rc = filter_check(f, 12, &why);
-        if (rc) FAIL(e, rc, "%s: %s", who, why.c_str());
-        return OH_OK;
+        return refuse(e, filter_check(f, 12, &why), who, why);
     }
     Neighbours nb;                                              /* prev and next: read by TEMPORAL only */
-    { const int rc = neighbours(e, who, "src", prev_ids, src_ids, next_ids, n, f->mode == OH_FILTER_TEMPORAL, &nb); if (rc) return rc; }
+    OH_TRY(neighbours(e, who, "src", prev_ids, src_ids, next_ids, n, f->mode == OH_FILTER_TEMPORAL, &nb));
     const Pic *p0 = alike_apart(e, who, nb.srcs, dst_ids, n);
     if (!p0) return OH_E_ARG;
     const OhPicParams &p = p0->p;
-    {
-        std::string why;
-        const int rc = filter_check(f, p.bit_depth, &why);
-        if (rc) FAIL(e, rc, "%s: %s", who, why.c_str());
-    }
+    std::string why;
+    OH_TRY(refuse(e, filter_check(f, p.bit_depth, &why), who, why));
     HIPCHK(e, hipSetDevice(e->device));
     OhFilterArgs a;
     memset(&a, 0, sizeof(a));
@@ -1279,8 +1242,7 @@ extern "C" int oh_pics_filter(OhEngine *e, const int *prev_ids, const int *src_i
         for (int k = 0; k < t.nv; k++) a.taps_v[q][OH_FILTER_MAX_TAPS / 2 - t.nv / 2 + k] = t.v[k];
         a.radius = std::max(a.radius, std::max(t.nh, t.nv) / 2);
     }
-    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
-        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+    return launch_sets(e, n, [&](int i0, int m) {
         for (int i = 0; i < m; i++) {
             read_planes(get_pic(e, nb.around[0][i0 + i]), a.np, a.src[0][i]);
             read_planes(get_pic(e, src_ids[i0 + i]), a.np, a.src[1][i]);
@@ -1288,9 +1250,7 @@ extern "C" int oh_pics_filter(OhEngine *e, const int *prev_ids, const int *src_i
             write_planes(get_pic(e, dst_ids[i0 + i]), a.np, a.dst[i]);
         }
         ohk_filter(&a, m, e->stream);
-        HIPCHK(e, hipGetLastError());
-    }
-    return OH_OK;
+    });
 }
 
 /* ---------------- composition (compose.hip) ---------------- */
@@ -1305,7 +1265,7 @@ static int compose_check(OhEngine *e, const int *dst_ids, int n, const OhCompose
     const Pic *d0 = alike_pics(e, who, dst_ids, n);
     if (!d0) return OH_E_ARG;
     std::vector<int> d;
-    { const int rc = distinct_dsts(e, who, dst_ids, n, &d); if (rc) return rc; }
+    OH_TRY(distinct_dsts(e, who, dst_ids, n, &d));
     const OhPicParams &dp = d0->p;
     const int cf = dp.chroma_format_idc, sw = 1 << oh_hshift(&dp, 1), sh = 1 << oh_vshift(&dp, 1);
     if (cp->flags & OH_COMPOSE_FILL)
@@ -1364,7 +1324,7 @@ extern "C" int oh_pics_compose(OhEngine *e, const int *dst_ids, int n, const OhC
         return OH_E_ARG;
     if (!n)
         return OH_OK;
-    { const int rc = compose_check(e, dst_ids, n, cp); if (rc) return rc; }
+    OH_TRY(compose_check(e, dst_ids, n, cp));
     const Pic *d0 = get_pic(e, dst_ids[0]);
     const OhPicParams &dp = d0->p;
     const int bpp = sample_bytes(dp.bit_depth), np = n_planes(dp), gs = 16 / bpp;
@@ -1434,39 +1394,29 @@ extern "C" int oh_pics_compose(OhEngine *e, const int *dst_ids, int n, const OhC
     if (nl) {
         if (need > e->compose_dev.bytes)
             HIPCHK(e, hipStreamSynchronize(e->stream));          /* launches of earlier calls still read the old table */
-        { const int rc = scratch_reserve(e, &e->compose_dev, need); if (rc) return rc; }
-        OhEngine::Stage *sg = stage_acquire(e, need);
-        if (!sg)
-            FAIL(e, OH_E_NOMEM, "oh_pics_compose: no staging buffer for %zu bytes of layer table", need);
-        memset(sg->p, 0, lay_bytes);
-        memcpy(sg->p, lay.data(), (size_t)nl * sizeof(OhCpsLayer));
-        OhCpsSrc *hs = (OhCpsSrc *)((char *)sg->p + lay_bytes);
-        for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
-            const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+        OH_TRY(upload(e, "oh_pics_compose", "layer table", &e->compose_dev, need, [&](void *h) {
+            memset(h, 0, lay_bytes);
+            memcpy(h, lay.data(), (size_t)nl * sizeof(OhCpsLayer));
+            OhCpsSrc *hs = (OhCpsSrc *)((char *)h + lay_bytes);
             for (int j = 0; j < nl; j++) {
                 const OhLayer &l = cp->layers[which[j]];
-                for (int i = 0; i < m; i++) {
-                    const Pic *s = get_pic(e, l.src_ids[i0 + i]);
-                    OhCpsSrc &t = hs[(size_t)nl * i0 + (size_t)j * m + i];
-                    read_planes(s, np, t.p);
-                    t.alpha = l.alpha ? (const uint8_t *)l.alpha + (size_t)(i0 + i) * (size_t)l.alpha_image_stride : nullptr;
+                for (int i = 0; i < n; i++) {                   /* picture i of the call: number i - i0 of the m in its launch set */
+                    const int i0 = i - i % OH_CONV_MAX_PICS, m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+                    OhCpsSrc &t = hs[(size_t)nl * i0 + (size_t)j * m + (i - i0)];
+                    read_planes(get_pic(e, l.src_ids[i]), np, t.p);
+                    t.alpha = l.alpha ? (const uint8_t *)l.alpha + (size_t)i * (size_t)l.alpha_image_stride : nullptr;
                 }
             }
-        }
-        HIPCHK(e, hipMemcpyAsync(e->compose_dev.p, sg->p, need, hipMemcpyHostToDevice, e->stream));
-        { const int rc = stage_in_use(e, sg, e->stream); if (rc) return rc; }
+        }));
     }
     a.n_layers = nl;
     a.layers = (const OhCpsLayer *)e->compose_dev.p;
-    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
-        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+    return launch_sets(e, n, [&](int i0, int m) {
         for (int i = 0; i < m; i++) read_planes(get_pic(e, dst_ids[i0 + i]), np, a.dst[i]);      /* in place: the finished half */
         a.srcs = nl ? (const OhCpsSrc *)((const char *)e->compose_dev.p + lay_bytes) + (size_t)nl * i0 : nullptr;
         a.n_pics = m;
         ohk_compose(&a, m, e->stream);
-        HIPCHK(e, hipGetLastError());
-    }
-    return OH_OK;
+    });
 }
 
 /* ---------------- histograms of the code values (histogram.hip) ---------------- */
@@ -1482,19 +1432,15 @@ extern "C" int oh_pics_histogram(OhEngine *e, const int *pic_ids, int n, const O
     const OhPicParams &p = p0->p;
     std::string why;
     if (!crop_window_ok(&p, *win, true, &why))
-        FAIL(e, OH_E_ARG, "%s: %s", who, why.c_str());
+        return refuse(e, OH_E_ARG, who, why);
     HIPCHK(e, hipSetDevice(e->device));
     OhHistArgs a;
     memset(&a, 0, sizeof(a));
     const int np = n_planes(p), sb = sample_bytes(p.bit_depth);
-    int W, H;
-    window_size(&p, *win, &W, &H);
     row_pitches(p0, np, a.pitch);
     for (int c = 0; c < (np > 1 ? 2 : 1); c++) {
         OhHistClass &k = a.k[c];
-        const int hs = oh_hshift(&p, c), vs = oh_vshift(&p, c);
-        k.x0 = win->left >> hs; k.y0 = win->top >> vs;
-        k.w = W >> hs; k.h = H >> vs;
+        class_window(&p, *win, c, &k.x0, &k.y0, &k.w, &k.h);
         k.g0 = k.x0 * sb / 16;                                  /* the granules of a row that hold a sample of the window */
         k.ng = ((k.x0 + k.w) * sb + 15) / 16 - k.g0;
         k.tiles = (k.h + OH_HG_ROWS - 1) / OH_HG_ROWS;
@@ -1502,15 +1448,13 @@ extern "C" int oh_pics_histogram(OhEngine *e, const int *pic_ids, int n, const O
     a.np = np; a.bd = p.bit_depth;
     const size_t per_pic = (size_t)3 * OH_HG_BINS, bytes = (size_t)n * per_pic * sizeof(uint32_t);
     OhEngine::Stage *sg = nullptr;
-    { const int rc = results_begin(e, who, &e->hist_res, bytes, n, &sg); if (rc) return rc; }
-    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
-        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+    OH_TRY(results_begin(e, who, &e->hist_res, bytes, n, &sg));
+    OH_TRY(launch_sets(e, n, [&](int i0, int m) {
         for (int i = 0; i < m; i++) read_planes(get_pic(e, pic_ids[i0 + i]), np, a.src[i]);
         a.res = (uint32_t *)e->hist_res.p + (size_t)i0 * per_pic;
         ohk_histogram(&a, m, e->stream);
-        HIPCHK(e, hipGetLastError());
-    }
-    { const int rc = results_fetch(e, &e->hist_res, bytes, sg); if (rc) return rc; }
+    }));
+    OH_TRY(results_fetch(e, &e->hist_res, bytes, sg));
     const uint32_t *r = (const uint32_t *)sg->p;
     for (int i = 0; i < n; i++) {
         memset(&out[i], 0, sizeof(out[i]));
@@ -1530,33 +1474,24 @@ extern "C" int oh_pics_lut(OhEngine *e, const int *src_ids, const int *dst_ids, 
         FAIL(e, OH_E_ARG, "%s: planes %d outside 0 .. 7", who, lut->planes);
     if (!n)
         return OH_OK;
-    const Pic *s0 = alike_pics(e, who, src_ids, n);
-    if (!s0) return OH_E_ARG;
-    const Pic *d0 = alike_pics(e, who, dst_ids, n);
-    if (!d0) return OH_E_ARG;
-    { const int rc = dsts_apart(e, who, dst_ids, n, src_ids, n); if (rc) return rc; }
+    const Pic *s0, *d0;
+    OH_TRY(srcs_dsts(e, who, src_ids, n, dst_ids, n, &s0, &d0));
     const OhPicParams &sp = s0->p, &dp = d0->p;
     if (sp.width != dp.width || sp.height != dp.height || sp.chroma_format_idc != dp.chroma_format_idc)
         FAIL(e, OH_E_ARG, "%s: sources of %dx%d, chroma format %d, destinations of %dx%d, chroma format %d", who, sp.width, sp.height,
              sp.chroma_format_idc, dp.width, dp.height, dp.chroma_format_idc);
     std::string why;
     if (lut_check(lut, sp.bit_depth, dp.bit_depth, n_planes(sp), &why))
-        FAIL(e, OH_E_ARG, "%s: %s", who, why.c_str());
-    HIPCHK(e, hipSetDevice(e->device));
+        return refuse(e, OH_E_ARG, who, why);
     const int np = n_planes(sp);
-    /* the tables of the call: staged in a pinned buffer of the pool and copied on the engine stream — behind the launches of an earlier
-     * call that read the device copy, in front of this call's.  The device copy has its full size from the first call on. */
+    /* the tables of the call; the device copy has its full size from the first call on */
     const size_t tab_bytes = (size_t)3 * OH_LUT_MAX * sizeof(uint16_t);
-    { const int rc = scratch_reserve(e, &e->lut_tabs, tab_bytes); if (rc) return rc; }
-    OhEngine::Stage *sg = stage_acquire(e, tab_bytes);
-    if (!sg)
-        FAIL(e, OH_E_NOMEM, "%s: no staging buffer for %zu bytes of tables", who, tab_bytes);
-    memset(sg->p, 0, tab_bytes);
-    for (int c = 0; c < np; c++)
-        if (lut->planes >> c & 1)
-            memcpy((uint16_t *)sg->p + (size_t)c * OH_LUT_MAX, lut->table[c], (size_t)lut->n_entries * sizeof(uint16_t));
-    HIPCHK(e, hipMemcpyAsync(e->lut_tabs.p, sg->p, tab_bytes, hipMemcpyHostToDevice, e->stream));
-    { const int rc = stage_in_use(e, sg, e->stream); if (rc) return rc; }
+    OH_TRY(upload(e, who, "tables", &e->lut_tabs, tab_bytes, [&](void *h) {
+        memset(h, 0, tab_bytes);
+        for (int c = 0; c < np; c++)
+            if (lut->planes >> c & 1)
+                memcpy((uint16_t *)h + (size_t)c * OH_LUT_MAX, lut->table[c], (size_t)lut->n_entries * sizeof(uint16_t));
+    }));
     OhLutArgs a;
     memset(&a, 0, sizeof(a));
     row_pitches(s0, np, a.spitch); row_pitches(d0, np, a.dpitch);
@@ -1564,32 +1499,16 @@ extern "C" int oh_pics_lut(OhEngine *e, const int *src_ids, const int *dst_ids, 
     a.np = np; a.sbd = sp.bit_depth; a.dbd = dp.bit_depth;
     a.planes = lut->planes;
     a.tab = (const uint16_t *)e->lut_tabs.p;
-    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
-        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+    return launch_sets(e, n, [&](int i0, int m) {
         for (int i = 0; i < m; i++) {
             read_planes(get_pic(e, src_ids[i0 + i]), np, a.src[i]);
             write_planes(get_pic(e, dst_ids[i0 + i]), np, a.dst[i]);
         }
         ohk_lut(&a, m, e->stream);
-        HIPCHK(e, hipGetLastError());
-    }
-    return OH_OK;
+    });
 }
 
 /* ---------------- motion search and compensation (motion.hip) ---------------- */
-/* a host list of the call in device scratch s, in front of the launches that follow: staged in a pinned buffer of the pool and copied on
- * the engine stream, behind the launches of an earlier call that read the device copy.  Growing the scratch frees the old block, which
- * waits for the device */
-static int list_to_device(OhEngine *e, const char *who, OhEngine::Scratch *s, const void *list, size_t bytes)
-{
-    { const int rc = scratch_reserve(e, s, bytes); if (rc) return rc; }
-    OhEngine::Stage *sg = stage_list(e, list, bytes);
-    if (!sg)
-        FAIL(e, OH_E_NOMEM, "%s: no staging buffer for %zu bytes of vectors", who, bytes);
-    HIPCHK(e, hipMemcpyAsync(s->p, sg->p, bytes, hipMemcpyHostToDevice, e->stream));
-    return stage_in_use(e, sg, e->stream);
-}
-
 extern "C" int oh_pics_motion(OhEngine *e, const int *cur_ids, const int *ref_ids, int n, const OhMotionSearch *ms, OhMotionVector *out)
 {
     const char *who = "oh_pics_motion";
@@ -1597,7 +1516,7 @@ extern "C" int oh_pics_motion(OhEngine *e, const int *cur_ids, const int *ref_id
         return OH_E_ARG;
     std::string why;
     if (motion_check(ms, 0, &why))
-        FAIL(e, OH_E_ARG, "%s: %s", who, why.c_str());
+        return refuse(e, OH_E_ARG, who, why);
     if (!n)
         return OH_OK;
     std::vector<int> all(cur_ids, cur_ids + n);
@@ -1612,21 +1531,18 @@ extern "C" int oh_pics_motion(OhEngine *e, const int *cur_ids, const int *ref_id
     (void)oh_motion_blocks(a.w, a.h, a.block, &a.bw, &a.bh);
     const size_t per_pair = (size_t)a.bw * a.bh;
     if (motion_check(ms, (size_t)n * per_pair, &why))
-        FAIL(e, OH_E_ARG, "%s: %s", who, why.c_str());
+        return refuse(e, OH_E_ARG, who, why);
     HIPCHK(e, hipSetDevice(e->device));
     int32_t pitch[3];
     row_pitches(p0, 1, pitch);
     a.pitch = pitch[0];
     a.rx = ms->range_x; a.ry = ms->range_y; a.subpel = ms->subpel; a.lambda = ms->lambda;
-    if (ms->centres) {
-        const int rc = list_to_device(e, who, &e->motion_centres, ms->centres, (size_t)n * per_pair * sizeof(OhMoVec));
-        if (rc) return rc;
-    }
+    if (ms->centres)                                            /* growing the scratch frees the old block, which waits for the device */
+        OH_TRY(upload_copy(e, who, "vectors", &e->motion_centres, (size_t)n * per_pair * sizeof(OhMoVec), ms->centres));
     const size_t bytes = (size_t)n * per_pair * sizeof(OhMoDev);
     OhEngine::Stage *sg = nullptr;
-    { const int rc = results_begin(e, who, &e->motion_res, bytes, n, &sg); if (rc) return rc; }
-    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
-        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+    OH_TRY(results_begin(e, who, &e->motion_res, bytes, n, &sg));
+    OH_TRY(launch_sets(e, n, [&](int i0, int m) {
         for (int i = 0; i < m; i++) {
             a.cur[i] = final_planes(get_pic(e, cur_ids[i0 + i]))[0];
             a.ref[i] = final_planes(get_pic(e, ref_ids[i0 + i]))[0];
@@ -1634,9 +1550,8 @@ extern "C" int oh_pics_motion(OhEngine *e, const int *cur_ids, const int *ref_id
         a.centres = ms->centres ? (const OhMoVec *)e->motion_centres.p + (size_t)i0 * per_pair : nullptr;
         a.res = (OhMoDev *)e->motion_res.p + (size_t)i0 * per_pair;
         ohk_motion_search(&a, m, e->stream);
-        HIPCHK(e, hipGetLastError());
-    }
-    { const int rc = results_fetch(e, &e->motion_res, bytes, sg); if (rc) return rc; }
+    }));
+    OH_TRY(results_fetch(e, &e->motion_res, bytes, sg));
     memcpy(out, sg->p, bytes);
     return OH_OK;
 }
@@ -1663,23 +1578,19 @@ extern "C" int oh_pics_motion_compensate(OhEngine *e, const int *ref_ids, const 
     a.block = block;
     (void)oh_motion_blocks(a.w[0], a.h[0], block, &a.bw, &a.bh);
     const size_t per_pic = (size_t)a.bw * a.bh;
-    {   /* the x and y of the field: what the kernel reads */
-        std::vector<OhMoVec> xy((size_t)n * per_pic);
-        for (size_t i = 0; i < xy.size(); i++) { xy[i].x = field[i].x; xy[i].y = field[i].y; }
-        const int rc = list_to_device(e, who, &e->motion_field, xy.data(), xy.size() * sizeof(OhMoVec));
-        if (rc) return rc;
-    }
-    for (int i0 = 0; i0 < n; i0 += OH_CONV_MAX_PICS) {
-        const int m = std::min(n - i0, (int)OH_CONV_MAX_PICS);
+    const size_t n_vec = (size_t)n * per_pic;
+    OH_TRY(upload(e, who, "vectors", &e->motion_field, n_vec * sizeof(OhMoVec), [&](void *h) {
+        OhMoVec *xy = (OhMoVec *)h;                              /* the x and y of the field: what the kernel reads */
+        for (size_t i = 0; i < n_vec; i++) { xy[i].x = field[i].x; xy[i].y = field[i].y; }
+    }));
+    return launch_sets(e, n, [&](int i0, int m) {
         for (int i = 0; i < m; i++) {
             read_planes(get_pic(e, ref_ids[i0 + i]), a.np, a.ref[i]);
             write_planes(get_pic(e, dst_ids[i0 + i]), a.np, a.dst[i]);
         }
         a.field = (const OhMoVec *)e->motion_field.p + (size_t)i0 * per_pic;
         ohk_motion_compensate(&a, m, e->stream);
-        HIPCHK(e, hipGetLastError());
-    }
-    return OH_OK;
+    });
 }
 
 extern "C" int oh_pic_device_planes(OhEngine *e, int pic_id, void *planes[3], int32_t stride[3], int32_t width[3], int32_t height[3])

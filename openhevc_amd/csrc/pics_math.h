@@ -12,6 +12,7 @@
 #endif
 
 OH_INTERNAL void window_size(const OhPicParams *p, const OhWindow &w, int *W, int *H);
+OH_INTERNAL void class_window(const OhPicParams *p, const OhWindow &w, int q, int32_t *x0, int32_t *y0, int32_t *ws, int32_t *hs);
 OH_INTERNAL bool crop_window_ok(const OhPicParams *p, const OhWindow &w, bool aligned, std::string *why);
 OH_INTERNAL int ids_apart(const int *dst_ids, int nd, const int *src_ids, int ns, int *both);
 OH_INTERNAL int neighbours_resolve(const int *const around_ids[2], const int *own_ids, int n, bool used, std::vector<int> around[2],

@@ -28,6 +28,16 @@ void window_size(const OhPicParams *p, const OhWindow &w, int *W, int *H)
     *H = p->height - w.top - w.bottom;
 }
 
+/* the window in the planes of class q (0 luma, 1 chroma): its origin in the plane and what it leaves, plane samples */
+void class_window(const OhPicParams *p, const OhWindow &w, int q, int32_t *x0, int32_t *y0, int32_t *ws, int32_t *hs)
+{
+    const int sx = oh_hshift(p, q), sy = oh_vshift(p, q);
+    int W, H;
+    window_size(p, w, &W, &H);
+    *x0 = w.left >> sx; *y0 = w.top >> sy;
+    *ws = W >> sx; *hs = H >> sy;
+}
+
 /* a crop window of a picture: offsets not negative, something left and — aligned — the offsets multiples of the chroma sub-sampling.
  * false: *why says what is wrong. */
 bool crop_window_ok(const OhPicParams *p, const OhWindow &w, bool aligned, std::string *why)

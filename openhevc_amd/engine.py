@@ -25,6 +25,32 @@ class EngineError(RuntimeError):
     code = None                                               # the OH_E_* code of the failed call, where one is known
 
 
+def _check(rc, what, failed=None, text="{what} failed ({rc})"):
+    """the return code of the library call `what`: where it failed (default: where it is not 0), EngineError(text) with .code set"""
+    if rc != 0 if failed is None else failed:
+        err = EngineError(text.format(what=what, rc=rc))
+        err.code = rc
+        raise err
+
+
+def _enum(table, what, v, ints=None):
+    """a name of table or its number -> the number.  ints None: any number passes as int(v); a range or a collection: the ints that
+    do, which the ValueError of any other names as "lo .. hi" or as the sorted list"""
+    if isinstance(v, str):
+        if v not in table:
+            raise ValueError(f"unknown {what} {v!r}: one of {sorted(table)}")
+        return table[v]
+    i = int(v)
+    if ints is not None and i not in ints:
+        raise ValueError(f"{what} {i}: {ints[0]} .. {ints[-1]}" if isinstance(ints, range) else f"{what} {v}: one of {sorted(ints)}")
+    return i
+
+
+def _ids(ids):
+    """picture ids as a ctypes int array: as many entries as there are, one at least (the library takes no array without an address)"""
+    return (C.c_int * max(len(ids), 1))(*ids)
+
+
 class OhWindow(C.Structure):                                  # include/ohevc_hip.h
     _fields_ = [("left", C.c_int32), ("right", C.c_int32), ("top", C.c_int32), ("bottom", C.c_int32)]
 
@@ -43,11 +69,7 @@ class OhConvert(C.Structure):                                 # include/ohevc_hi
 
 def conv_format(fmt):
     """a format name of CONV_FORMATS or its OH_CONV_* number -> the number"""
-    if isinstance(fmt, str):
-        if fmt not in CONV_FORMATS:
-            raise ValueError(f"unknown format {fmt!r}: one of {sorted(CONV_FORMATS)}")
-        return CONV_FORMATS[fmt]
-    return int(fmt)
+    return _enum(CONV_FORMATS, "format", fmt)
 
 
 def make_convert(fmt, sample, window=(0, 0, 0, 0), matrix=1, full_range=False, chroma="linear"):
@@ -84,10 +106,7 @@ def colour_tables(col):
     A, G, B, misc = np.zeros(COL_NA, np.int32), np.zeros(COL_NP, np.int32), np.zeros(COL_NP, np.int32), np.zeros(COL_NMISC, np.int32)
     P = C.POINTER(C.c_int32)
     rc = lib().oh_colour_tables(C.byref(col), A.ctypes.data_as(P), G.ctypes.data_as(P), B.ctypes.data_as(P), misc.ctypes.data_as(P))
-    if rc != 0:
-        err = EngineError(f"oh_colour_tables failed ({rc})")
-        err.code = rc
-        raise err
+    _check(rc, "oh_colour_tables")
     return A, G, B, misc
 
 
@@ -140,10 +159,7 @@ def light_percentile(lls, ppm=999900):
     arr = (OhLightLevel * max(len(lls), 1))(*[ll.as_struct() for ll in lls])
     v = C.c_uint32()
     rc = lib().oh_light_percentile(arr, len(lls), int(ppm), C.byref(v))
-    if rc != 0:
-        err = EngineError(f"oh_light_percentile failed ({rc})")
-        err.code = rc
-        raise err
+    _check(rc, "oh_light_percentile")
     return v.value
 
 
@@ -195,11 +211,7 @@ def compare_psnr(sse, samples, bit_depth):
 def compare_ssim_consts(bit_depth):
     """oh_compare_ssim_consts (host only): (c1, c2) of the SSIM windows at that bit depth"""
     c1, c2 = C.c_int64(), C.c_int64()
-    rc = lib().oh_compare_ssim_consts(int(bit_depth), C.byref(c1), C.byref(c2))
-    if rc != 0:
-        err = EngineError(f"oh_compare_ssim_consts failed ({rc})")
-        err.code = rc
-        raise err
+    _check(lib().oh_compare_ssim_consts(int(bit_depth), C.byref(c1), C.byref(c2)), "oh_compare_ssim_consts")
     return c1.value, c2.value
 
 
@@ -257,11 +269,7 @@ RESIZE_MAX_PICS, RESIZE_MAX_DOWN, RESIZE_MAX_UP = 64, 128, 16
 
 def resize_filter(filt):
     """a filter name of RESIZE_FILTERS or its OH_RESIZE_* number -> the number"""
-    if isinstance(filt, str):
-        if filt not in RESIZE_FILTERS:
-            raise ValueError(f"unknown filter {filt!r}: one of {sorted(RESIZE_FILTERS)}")
-        return RESIZE_FILTERS[filt]
-    return int(filt)
+    return _enum(RESIZE_FILTERS, "filter", filt)
 
 
 def resize_taps(src_extent, dst_extent, filter="bilinear", phase=2):
@@ -269,18 +277,12 @@ def resize_taps(src_extent, dst_extent, filter="bilinear", phase=2):
     the integers the kernels receive; phase 2: centred samples, 1: the co-sited chroma columns of 4:2:0 / 4:2:2"""
     f = resize_filter(filter)
     mt = lib().oh_resize_max_taps(src_extent, dst_extent, f)
-    if mt < 1:
-        err = EngineError(f"oh_resize_max_taps({src_extent}, {dst_extent}, {f}) failed ({mt})")
-        err.code = mt
-        raise err
+    _check(mt, f"oh_resize_max_taps({src_extent}, {dst_extent}, {f})", mt < 1)
     n = max(dst_extent, 1)
     first, cnt, k = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, mt), np.int16)
     rc = lib().oh_resize_taps(src_extent, dst_extent, f, phase, first.ctypes.data_as(C.POINTER(C.c_int32)),
                               k.ctypes.data_as(C.POINTER(C.c_int16)), mt, cnt.ctypes.data_as(C.POINTER(C.c_int)))
-    if rc != 0:
-        err = EngineError(f"oh_resize_taps failed ({rc})")
-        err.code = rc
-        raise err
+    _check(rc, "oh_resize_taps")
     return [(int(first[x]), [int(v) for v in k[x, :cnt[x]]]) for x in range(dst_extent)]
 
 
@@ -329,19 +331,10 @@ RF_FILTERS = {"point": 0, "nearest": 0, "linear": 1}                            
 RF_SEG = 4096                                                                          # OH_RF_SEG (csrc/kernels.h): plane samples per workgroup segment
 
 
-def _rf_enum(table, what, v):
-    """a name of table or its OH_RF_* number -> the number"""
-    if isinstance(v, str):
-        if v not in table:
-            raise ValueError(f"unknown {what} {v!r}: one of {sorted(table)}")
-        return table[v]
-    return int(v)
-
-
 def reformat_quantise(sum, s, mode, x, y, bit_depth):
     """oh_reformat_quantise (host only): a weighted sum of source samples -> the destination sample of bit_depth bits, shifted down by s
     bits with one rounding (mode "round" or "dither", or its number) at place (x, y) of its plane, by the function the kernel evaluates"""
-    return int(lib().oh_reformat_quantise(int(sum), int(s), _rf_enum(RF_DEPTH, "depth mode", mode), int(x), int(y), int(bit_depth)))
+    return int(lib().oh_reformat_quantise(int(sum), int(s), _enum(RF_DEPTH, "depth mode", mode), int(x), int(y), int(bit_depth)))
 
 
 class OhOrient(C.Structure):                                  # include/ohevc_hip.h
@@ -355,14 +348,7 @@ ORIENT_TILE = 64                                                                
 
 def orient_code(v):
     """a name of ORIENTATIONS ("rot90" is clockwise) or an int 0 .. 7 -> the int"""
-    if isinstance(v, str):
-        if v not in ORIENTATIONS:
-            raise ValueError(f"unknown orientation {v!r}: one of {sorted(ORIENTATIONS)}")
-        return ORIENTATIONS[v]
-    v = int(v)
-    if not 0 <= v <= 7:
-        raise ValueError(f"orientation {v}: 0 .. 7")
-    return v
+    return _enum(ORIENTATIONS, "orientation", v, range(8))
 
 
 def orient_then(first, second):
@@ -378,11 +364,7 @@ def orient_inverse(o):
 def orient_size(o, width, height):
     """oh_orient_size (host only): (width, height) of the image of a width x height window: swapped under TRANSPOSE"""
     ow, oh = C.c_int(), C.c_int()
-    rc = lib().oh_orient_size(orient_code(o), int(width), int(height), C.byref(ow), C.byref(oh))
-    if rc != 0:
-        err = EngineError(f"oh_orient_size failed ({rc})")
-        err.code = rc
-        raise err
+    _check(lib().oh_orient_size(orient_code(o), int(width), int(height), C.byref(ow), C.byref(oh)), "oh_orient_size")
     return ow.value, oh.value
 
 
@@ -392,10 +374,7 @@ def orientation_from_sei(hor_flip, ver_flip, anticlockwise_rotation):
     code OH_E_UNSUPPORTED for an angle that is no quarter turn."""
     o = C.c_int()
     rc = lib().oh_orient_from_sei(int(hor_flip), int(ver_flip), int(anticlockwise_rotation), C.byref(o))
-    if rc != 0:
-        err = EngineError(f"oh_orient_from_sei({hor_flip}, {ver_flip}, {anticlockwise_rotation:#x}) failed ({rc})")
-        err.code = rc
-        raise err
+    _check(rc, f"oh_orient_from_sei({hor_flip}, {ver_flip}, {anticlockwise_rotation:#x})")
     return o.value
 
 
@@ -410,25 +389,10 @@ WARP_BORDERS = {"replicate": 0, "constant": 1}                                  
 WARP_TILE = (64, 16)                                                                    # WARP_TW, WARP_TH (csrc/warp_common.h): a workgroup's tile
 
 
-def _warp_enum(table, what, v):
-    """a name of the table or one of its ints -> the int"""
-    if isinstance(v, str):
-        if v not in table:
-            raise ValueError(f"unknown {what} {v!r}: one of {sorted(table)}")
-        return table[v]
-    if int(v) not in table.values():
-        raise ValueError(f"{what} {v}: one of {sorted(table.values())}")
-    return int(v)
-
-
 def _warp_built(name, *args):
     """one of the C builders, which fill a whole OhWarp"""
     w = OhWarp()
-    rc = getattr(lib(), name)(*args, C.byref(w))
-    if rc != 0:
-        err = EngineError(f"{name} failed ({rc})")
-        err.code = rc
-        raise err
+    _check(getattr(lib(), name)(*args, C.byref(w)), name)
     return w
 
 
@@ -439,7 +403,7 @@ def warp_matrix(matrix, mode=None):
     0), then m[0 .. 5] = rint(65536 a) and m[6], m[7] = rint(2^30 a), m[8] = 2^30; rint is numpy's, halves to even, in float64.  mode
     None: affine for 6 numbers or 2 x 3, perspective for 9 or 3 x 3."""
     if isinstance(matrix, OhWarp):
-        return (matrix.mode if mode is None else _warp_enum(WARP_MODES, "mode", mode)), [int(v) for v in matrix.m]
+        return (matrix.mode if mode is None else _enum(WARP_MODES, "mode", mode, WARP_MODES.values())), [int(v) for v in matrix.m]
     a = np.asarray(matrix)
     if a.dtype.kind == "f":
         if a.shape not in ((2, 3), (3, 3)):
@@ -462,7 +426,7 @@ def warp_matrix(matrix, mode=None):
         m += [0, 0, 1 << 30] if len(m) == 6 else []
     if any(not -(1 << 63) <= v < 1 << 63 for v in m):
         raise ValueError("a coefficient does not fit int64")
-    return (inferred if mode is None else _warp_enum(WARP_MODES, "mode", mode)), m
+    return (inferred if mode is None else _enum(WARP_MODES, "mode", mode, WARP_MODES.values())), m
 
 
 def warp_identity():
@@ -500,10 +464,7 @@ def warp_from_sei(hor_flip, ver_flip, anticlockwise_rotation, width, height):
     rotation about the centre, into the rotated bounding box rounded up to even sizes.  The result is affine, bilinear, replicate."""
     w, ow, oh = OhWarp(), C.c_int(), C.c_int()
     rc = lib().oh_warp_from_sei(int(hor_flip), int(ver_flip), int(anticlockwise_rotation), int(width), int(height), C.byref(w), C.byref(ow), C.byref(oh))
-    if rc != 0:
-        err = EngineError(f"oh_warp_from_sei({hor_flip}, {ver_flip}, {anticlockwise_rotation:#x}, {width}, {height}) failed ({rc})")
-        err.code = rc
-        raise err
+    _check(rc, f"oh_warp_from_sei({hor_flip}, {ver_flip}, {anticlockwise_rotation:#x}, {width}, {height})")
     return w, (ow.value, oh.value)
 
 
@@ -512,10 +473,7 @@ def warp_paths(warp, bit_depth, chroma_format_idc, dst_width, dst_height):
     this OhWarp into destinations of dst_width x dst_height: the kernel's own predicate"""
     s, g = C.c_int64(), C.c_int64()
     rc = lib().oh_warp_paths(C.byref(warp), int(bit_depth), int(chroma_format_idc), int(dst_width), int(dst_height), C.byref(s), C.byref(g))
-    if rc != 0:
-        err = EngineError(f"oh_warp_paths failed ({rc})")
-        err.code = rc
-        raise err
+    _check(rc, "oh_warp_paths")
     return s.value, g.value
 
 
@@ -540,24 +498,13 @@ def field_info(pic_struct):
     output order, else 0; top_first 1 / 0 where the message says which field of a frame is first, else -1; repeat_first; frames, how
     often a frame is shown (2 doubling, 3 tripling).  EngineError with code OH_E_ARG outside 0 .. 12."""
     fi = OhFieldInfo()
-    rc = lib().oh_field_info(int(pic_struct), C.byref(fi))
-    if rc != 0:
-        err = EngineError(f"oh_field_info({pic_struct}) failed ({rc})")
-        err.code = rc
-        raise err
+    _check(lib().oh_field_info(int(pic_struct), C.byref(fi)), f"oh_field_info({pic_struct})")
     return FieldInfo(fi.kind, fi.pair, fi.top_first, fi.repeat_first, fi.frames)
 
 
 def deint_mode(v):
     """a name of DEINT_MODES or an int 0 .. 3 -> the int"""
-    if isinstance(v, str):
-        if v not in DEINT_MODES:
-            raise ValueError(f"unknown deinterlacing mode {v!r}: one of {sorted(DEINT_MODES)}")
-        return DEINT_MODES[v]
-    v = int(v)
-    if not 0 <= v <= 3:
-        raise ValueError(f"deinterlacing mode {v}: 0 .. 3")
-    return v
+    return _enum(DEINT_MODES, "deinterlacing mode", v, range(4))
 
 
 def deint_adaptive(up, dn, a, b, pu, pd, nu, nd):
@@ -589,23 +536,12 @@ FILTER_TW, FILTER_TH = 128, 32                                                  
 
 def filter_mode(v):
     """a name of FILTER_MODES or an int 0 .. 3 -> the int"""
-    if isinstance(v, str):
-        if v not in FILTER_MODES:
-            raise ValueError(f"unknown filter mode {v!r}: one of {sorted(FILTER_MODES)}")
-        return FILTER_MODES[v]
-    v = int(v)
-    if not 0 <= v <= 3:
-        raise ValueError(f"filter mode {v}: 0 .. 3")
-    return v
+    return _enum(FILTER_MODES, "filter mode", v, range(4))
 
 
 def _filter_row(name, n):
     out = (C.c_int16 * FILTER_MAX_TAPS)()
-    rc = getattr(lib(), name)(int(n), out)
-    if rc != 0:
-        err = EngineError(f"{name}({n}) failed ({rc})")
-        err.code = rc
-        raise err
+    _check(getattr(lib(), name)(int(n), out), f"{name}({n})")
     return [int(v) for v in out[:n]]
 
 
@@ -628,11 +564,7 @@ def filter_taps(h, v):
     t = OhFilterTaps(len(h), len(v))
     t.h[:len(h)] = h
     t.v[:len(v)] = v
-    rc = lib().oh_filter_taps_check(C.byref(t))
-    if rc != 0:
-        err = EngineError(f"taps {h} x {v} are not legal ({rc})")
-        err.code = rc
-        raise err
+    _check(lib().oh_filter_taps_check(C.byref(t)), f"taps {h} x {v}", text="{what} are not legal ({rc})")
     return t
 
 
@@ -651,17 +583,10 @@ class OhMotionSearch(C.Structure):                            # include/ohevc_hi
 MOTION_DTYPE = np.dtype([("x", np.int16), ("y", np.int16), ("sad", np.uint32), ("sad_centre", np.uint32)])     # OhMotionVector
 
 
-def _motion_chk(rc, what):
-    if rc != 0:
-        err = EngineError(f"{what} failed ({rc})")
-        err.code = rc
-        raise err
-
-
 def motion_blocks(width, height, block=16):
     """oh_motion_blocks (host only): (bw, bh), the blocks of `block` samples across and down a coded luma plane of width x height"""
     bw, bh = C.c_int(0), C.c_int(0)
-    _motion_chk(lib().oh_motion_blocks(int(width), int(height), int(block), C.byref(bw), C.byref(bh)), f"oh_motion_blocks({width}, {height}, {block})")
+    _check(lib().oh_motion_blocks(int(width), int(height), int(block), C.byref(bw), C.byref(bh)), f"oh_motion_blocks({width}, {height}, {block})")
     return bw.value, bh.value
 
 
@@ -689,7 +614,7 @@ def motion_scale(coarse, block_c, s, grid, block_f):
         raise ValueError(f"motion_scale: the field of one pair has the shape (bh, bw), not {coarse.shape}")
     bw, bh = int(grid[0]), int(grid[1])
     out = np.zeros((max(bh, 0), max(bw, 0), 2), dtype=np.int16)
-    _motion_chk(lib().oh_motion_scale(coarse.ctypes.data_as(C.POINTER(OhMotionVector)), coarse.shape[1], coarse.shape[0], int(block_c), int(s), bw, bh,
+    _check(lib().oh_motion_scale(coarse.ctypes.data_as(C.POINTER(OhMotionVector)), coarse.shape[1], coarse.shape[0], int(block_c), int(s), bw, bh,
                                       int(block_f), out.ctypes.data_as(C.POINTER(C.c_int16))), "oh_motion_scale")
     return out
 
@@ -753,13 +678,6 @@ class Histogram:
         return f"Histogram({self.plane})"
 
 
-def _levels_chk(rc, what):
-    if rc != 0:
-        err = EngineError(f"{what} failed ({rc})")
-        err.code = rc
-        raise err
-
-
 def _hist_array(hists):
     """PlaneHist objects (or one) -> (a ctypes array of OhPlaneHist, their number)"""
     hists = [hists] if isinstance(hists, PlaneHist) else list(hists)
@@ -771,21 +689,21 @@ def hist_percentile(hists, ppm):
     samples lie; 0 gives the minimum, 1000000 the maximum"""
     arr, n = _hist_array(hists)
     v = C.c_uint32()
-    _levels_chk(lib().oh_hist_percentile(arr, n, int(ppm), C.byref(v)), "oh_hist_percentile")
+    _check(lib().oh_hist_percentile(arr, n, int(ppm), C.byref(v)), "oh_hist_percentile")
     return v.value
 
 
 def hist_distance(a, b):
     """oh_hist_distance (host only): the sum over all values of |a.hist - b.hist| of two PlaneHist, the scene-cut measure"""
     sad = C.c_uint64()
-    _levels_chk(lib().oh_hist_distance(C.byref(a.as_struct()), C.byref(b.as_struct()), C.byref(sad)), "oh_hist_distance")
+    _check(lib().oh_hist_distance(C.byref(a.as_struct()), C.byref(b.as_struct()), C.byref(sad)), "oh_hist_distance")
     return sad.value
 
 
 def _lut_built(name, n_entries, *args):
     """a table builder of the library -> a numpy uint16 array of n_entries values"""
     out = np.zeros(max(int(n_entries), 1), dtype=np.uint16)
-    _levels_chk(getattr(lib(), name)(*args, out.ctypes.data_as(C.POINTER(C.c_uint16))), name)
+    _check(getattr(lib(), name)(*args, out.ctypes.data_as(C.POINTER(C.c_uint16))), name)
     return out
 
 
@@ -837,22 +755,14 @@ def convert_image_bytes(params, cv):
 def convert_coeffs(cv, bit_depth):
     """oh_convert_coeffs (host only): (cy, crv, cgu, cgv, cbu, yoff, mid, S, D), the integers of an RGB conversion"""
     out = (C.c_int32 * CONV_NCOEFFS)()
-    rc = lib().oh_convert_coeffs(C.byref(cv), bit_depth, out, CONV_NCOEFFS)
-    if rc != 0:
-        err = EngineError(f"oh_convert_coeffs failed ({rc})")
-        err.code = rc
-        raise err
+    _check(lib().oh_convert_coeffs(C.byref(cv), bit_depth, out, CONV_NCOEFFS), "oh_convert_coeffs")
     return tuple(out)
 
 
 def import_coeffs(cv, bit_depth):
     """oh_import_coeffs (host only): (ry, gy, by, ru, gu, bu, rv, gv, bv, yoff, mid, S, D), the integers of an RGB import"""
     out = (C.c_int32 * IMPORT_NCOEFFS)()
-    rc = lib().oh_import_coeffs(C.byref(cv), bit_depth, out, IMPORT_NCOEFFS)
-    if rc != 0:
-        err = EngineError(f"oh_import_coeffs failed ({rc})")
-        err.code = rc
-        raise err
+    _check(lib().oh_import_coeffs(C.byref(cv), bit_depth, out, IMPORT_NCOEFFS), "oh_import_coeffs")
     return tuple(out)
 
 
@@ -874,8 +784,9 @@ def lib():
         # brings a second HIP runtime that sees no GPU.  Loaded before it, both share torch's (what Engine.pics_convert needs).
         _torch_first = "torch" in sys.modules
         L = C.CDLL(lib_path())
-        V, I = C.c_void_p, C.c_int
-        PP = C.POINTER(C.c_void_p)
+        V, I, I64 = C.c_void_p, C.c_int, C.c_int64
+        PP, IP, U16P = C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_uint16)
+        WP, HP, MVP = C.POINTER(OhWarp), C.POINTER(OhPlaneHist), C.POINTER(OhMotionVector)
         L.oh_engine_create.argtypes = [PP, I]
         L.oh_engine_create_on_stream.argtypes = [PP, I, V]
         L.oh_pic_bytes.argtypes = [C.POINTER(F.OhPicParams)]
@@ -932,8 +843,6 @@ def lib():
         L.oh_orient_inverse.argtypes = [I]
         L.oh_orient_size.argtypes = [I, I, I, C.POINTER(I), C.POINTER(I)]
         L.oh_orient_from_sei.argtypes = [I, I, C.c_uint32, C.POINTER(I)]
-        IP = C.POINTER(C.c_int)
-        WP, I64 = C.POINTER(OhWarp), C.c_int64
         L.oh_pics_warp.argtypes = [V, IP, IP, I, WP]
         L.oh_warp_position.argtypes = [WP, I, I, I, I, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.oh_warp_cubic.argtypes = [I, C.POINTER(C.c_int16)]
@@ -962,7 +871,6 @@ def lib():
         L.oh_filter_median9.restype = C.c_int32
         L.oh_filter_temporal.argtypes = [C.c_int32] * 6
         L.oh_filter_temporal.restype = C.c_int32
-        U16P, HP = C.POINTER(C.c_uint16), C.POINTER(OhPlaneHist)
         L.oh_pics_histogram.argtypes = [V, IP, I, C.POINTER(OhWindow), C.POINTER(OhHistogram)]
         L.oh_hist_percentile.argtypes = [HP, I, C.c_uint32, C.POINTER(C.c_uint32)]
         L.oh_hist_distance.argtypes = [HP, HP, C.POINTER(C.c_uint64)]
@@ -973,7 +881,6 @@ def lib():
         L.oh_lut_stretch.argtypes = [HP, I, C.c_uint32, C.c_uint32, I, U16P]
         L.oh_lut_equalise.argtypes = [HP, I, I, U16P]
         L.oh_lut_then.argtypes = [U16P, I, U16P, I, U16P]
-        MVP = C.POINTER(OhMotionVector)
         L.oh_motion_blocks.argtypes = [I, I, I, IP, IP]
         L.oh_pics_motion.argtypes = [V, IP, IP, I, C.POINTER(OhMotionSearch), MVP]
         L.oh_pics_motion_compensate.argtypes = [V, IP, IP, I, I, MVP]
@@ -1042,9 +949,7 @@ class Engine:
 
     def _chk(self, rc, what):
         if rc != 0:
-            err = EngineError(f"{what} failed ({rc}): {self.L.oh_engine_last_error(self.h).decode()}")
-            err.code = rc
-            raise err
+            _check(rc, f"{what} failed ({rc}): {self.L.oh_engine_last_error(self.h).decode()}", text="{what}")
 
     def close(self):
         if getattr(self, "h", None):
@@ -1089,19 +994,29 @@ class Engine:
         self._params.pop(pid, None)
 
     @staticmethod
-    def _plane_args(hp):
-        n = len(hp.planes)
-        d = (C.c_void_p * 3)(*[pl.ctypes.data for pl in hp.planes] + [None] * (3 - n))
-        s = (C.c_ssize_t * 3)(*[pl.strides[0] for pl in hp.planes] + [0] * (3 - n))
-        return d, s
+    def _plane_args(planes, params=None, window=(0, 0, 0, 0), pad=0):
+        """(planes, their pointers, their row strides) as the plane calls take them: planes, a list of numpy planes, or with None
+        zeroed planes that hold the window = (left, right, top, bottom) of a picture of params, their rows pad bytes longer"""
+        if planes is None:
+            dt = np.uint8 if params.bit_depth <= 8 else np.uint16
+            W, H = params.width - window[0] - window[1], params.height - window[2] - window[3]
+            planes = []
+            for c in range(F.n_planes(params)):
+                hs = 1 if c and params.chroma_format_idc in (1, 2) else 0
+                vs = 1 if c and params.chroma_format_idc == 1 else 0
+                planes.append(np.zeros((H >> vs, (W >> hs) + pad // dt().itemsize), dt))
+        n = len(planes)
+        d = (C.c_void_p * 3)(*[pl.ctypes.data for pl in planes] + [None] * (3 - n))
+        s = (C.c_ssize_t * 3)(*[pl.strides[0] for pl in planes] + [0] * (3 - n))
+        return planes, d, s
 
     def pic_upload(self, pid, hp):
-        d, s = self._plane_args(hp)
+        _, d, s = self._plane_args(hp.planes)
         self._chk(self.L.oh_pic_upload(self.h, pid, d, s), "oh_pic_upload")
 
     def pic_download(self, pid, params):
         hp = F.HostPic(params)
-        d, s = self._plane_args(hp)
+        _, d, s = self._plane_args(hp.planes)
         self._chk(self.L.oh_pic_download(self.h, pid, d, s), "oh_pic_download")
         return hp
 
@@ -1116,42 +1031,24 @@ class Engine:
     def download_finish(self, handle, params, left=0, right=0, top=0, bottom=0, planes=True):
         """second half (oh_download_finish): waits for the copies, returns the packed planes; planes=False: hands no destination over
         (the call must return OH_E_ARG and still release the staging buffer) and returns the error code"""
-        dt = np.uint8 if params.bit_depth <= 8 else np.uint16
-        W, H = params.width - left - right, params.height - top - bottom
         if not planes:
             return self.L.oh_download_finish(self.h, handle, None, None)
-        out = []
-        for c in range(F.n_planes(params)):
-            hs = 1 if c and params.chroma_format_idc in (1, 2) else 0
-            vs = 1 if c and params.chroma_format_idc == 1 else 0
-            out.append(np.zeros((H >> vs, W >> hs), dt))
-        n = len(out)
-        d = (C.c_void_p * 3)(*[pl.ctypes.data for pl in out] + [None] * (3 - n))
-        s = (C.c_ssize_t * 3)(*[pl.strides[0] for pl in out] + [0] * (3 - n))
+        out, d, s = self._plane_args(None, params, (left, right, top, bottom))
         self._chk(self.L.oh_download_finish(self.h, handle, d, s), "oh_download_finish")
         return out
 
     def pic_download_window(self, pid, params, left=0, right=0, top=0, bottom=0, pad=0):
         """the picture inside its conformance window as packed numpy planes (pad: extra bytes per destination row, to
         exercise pitches larger than the row)"""
-        dt = np.uint8 if params.bit_depth <= 8 else np.uint16
-        W, H = params.width - left - right, params.height - top - bottom
-        planes = []
-        for c in range(F.n_planes(params)):
-            hs = 1 if c and params.chroma_format_idc in (1, 2) else 0
-            vs = 1 if c and params.chroma_format_idc == 1 else 0
-            planes.append(np.zeros((H >> vs, (W >> hs) + pad // dt().itemsize), dt))
-        n = len(planes)
-        d = (C.c_void_p * 3)(*[pl.ctypes.data for pl in planes] + [None] * (3 - n))
-        s = (C.c_ssize_t * 3)(*[pl.strides[0] for pl in planes] + [0] * (3 - n))
+        planes, d, s = self._plane_args(None, params, (left, right, top, bottom), pad)
         win = OhWindow(left, right, top, bottom)
         self._chk(self.L.oh_pic_download_window(self.h, pid, C.byref(win), d, s), "oh_pic_download_window")
-        return [pl[:, :pl.shape[1] - pad // dt().itemsize] if pad else pl for pl in planes]
+        return [pl[:, :pl.shape[1] - pad // pl.itemsize] if pad else pl for pl in planes]
 
     def pics_md5(self, pids):
         """[[16-byte MD5 of plane 0, 1, 2]] of finished pictures, computed on the GPU (oh_pics_md5)"""
         n = len(pids)
-        ids = (C.c_int * max(n, 1))(*pids)
+        ids = _ids(pids)
         out = (C.c_uint8 * (48 * max(n, 1)))()
         self._chk(self.L.oh_pics_md5(self.h, ids, n, out), "oh_pics_md5")
         raw = bytes(out)
@@ -1161,7 +1058,7 @@ class Engine:
         """[(hash_type, [plane 0, 1, 2])] of finished pictures, computed on the GPU (oh_pics_hash): hash_type 0 MD5 (16-byte values),
         1 CRC, 2 checksum (ints) — the shape annexb.picture_hash gives for a decoded-picture-hash SEI"""
         n = len(pids)
-        ids = (C.c_int * max(n, 1))(*pids)
+        ids = _ids(pids)
         out = (OhPictureHash * max(n, 1))()
         self._chk(self.L.oh_pics_hash(self.h, ids, n, hash_type, out), "oh_pics_hash")
         if hash_type == 0:
@@ -1207,6 +1104,21 @@ class Engine:
                 self.pic_free(pid)
         self._chk(rc, what)
 
+    def _image_call(self, call, what, pids, out, width, height, nothing):
+        """a service that puts an image of width x height luma samples at the top left of its destinations: out, or fresh pictures of
+        the sources' params with that size rounded up to the minimum coding block (nothing: the ValueError where none can be made).
+        call(source ids, destination ids) is the library call `what`.  Returns (destination ids, dst_window), the window of the image"""
+        def fitting():
+            sp = self._pic_params(pids[0])
+            if width < 1 or height < 1:
+                raise ValueError(nothing)
+            return self._sized(sp, width, height)
+
+        out, made = self._dsts(out, len(pids), "sources", fitting)
+        self._call(call(_ids(pids), _ids(out)), what, made)
+        dp = self._pic_params(out[0])
+        return out, (0, dp.width - width, 0, dp.height - height)
+
     @staticmethod
     def _around(n, prev, next):
         """the prev / next arrays of a call: None stays None (the library takes a null array), a None entry becomes -1"""
@@ -1216,7 +1128,7 @@ class Engine:
                 ids = [-1 if v is None else int(v) for v in ids]
                 if len(ids) != n:
                     raise ValueError(f"{name}: {len(ids)} entries for {n} sources")
-                ids = (C.c_int * n)(*ids)
+                ids = _ids(ids)
             around.append(ids)
         return around
 
@@ -1272,7 +1184,7 @@ class Engine:
         cv = make_convert(fmt_i, sample, window, matrix, full_range, chroma)
         ib = convert_image_bytes(params, cv)
         if ib == 0:                                           # not a valid combination: the C call says why (and with which code)
-            self._chk(self.L.oh_pics_convert(self.h, (C.c_int * n)(*pids), n, C.byref(cv), None, 0, 0), "oh_pics_convert")
+            self._chk(self.L.oh_pics_convert(self.h, _ids(pids), n, C.byref(cv), None, 0, 0), "oh_pics_convert")
             raise EngineError("oh_pics_convert: invalid conversion")
         left, right, top, bottom = window
         W, H = params.width - left - right, params.height - top - bottom
@@ -1291,10 +1203,10 @@ class Engine:
             raise ValueError(f"out: want a contiguous {tdt} tensor of shape {shape} on {dev}, got {out.dtype} {tuple(out.shape)} on {out.device}")
         with self._torch_ordered(torch):
             if colour is None:
-                self._chk(self.L.oh_pics_convert(self.h, (C.c_int * n)(*pids), n, C.byref(cv), C.c_void_p(out.data_ptr()), ib,
+                self._chk(self.L.oh_pics_convert(self.h, _ids(pids), n, C.byref(cv), C.c_void_p(out.data_ptr()), ib,
                                                  out.numel() * esz), "oh_pics_convert")
             else:
-                self._chk(self.L.oh_pics_convert_colour(self.h, (C.c_int * n)(*pids), n, C.byref(cv), C.byref(colour),
+                self._chk(self.L.oh_pics_convert_colour(self.h, _ids(pids), n, C.byref(cv), C.byref(colour),
                                                         C.c_void_p(out.data_ptr()), ib, out.numel() * esz), "oh_pics_convert_colour")
         return out
 
@@ -1361,7 +1273,7 @@ class Engine:
             cv = make_convert(fmt_i, sample, window, matrix, full_range, chroma)
             esz = images.element_size()
             ib = convert_image_bytes(params, cv)
-            ids = (C.c_int * n)(*pids)
+            ids = _ids(pids)
             if ib == 0:                                       # not a valid combination: the C call says why (and with which code)
                 self._chk(self.L.oh_pics_import(self.h, ids, n, C.byref(cv), None, 0, 0), "oh_pics_import")
                 raise EngineError("oh_pics_import: invalid import")
@@ -1390,7 +1302,7 @@ class Engine:
         cv = make_convert("rgb", CONV_U16, window, matrix, full_range, chroma)
         sp = OhLightSpec(int(in_transfer), int(in_primaries), COL_NORM[norm], float(src_peak))
         out = (OhLightLevel * max(n, 1))()
-        self._chk(self.L.oh_pics_light_level(self.h, (C.c_int * max(n, 1))(*pids), n, C.byref(cv), C.byref(sp), out), "oh_pics_light_level")
+        self._chk(self.L.oh_pics_light_level(self.h, _ids(pids), n, C.byref(cv), C.byref(sp), out), "oh_pics_light_level")
         fs = 10000.0 if int(in_transfer) == 16 else float(src_peak)
         return [LightLevel(o.pixels, o.sum, o.max, o.min, np.frombuffer(o.hist, dtype=np.uint32).copy(), fs) for o in out[:n]]
 
@@ -1404,7 +1316,7 @@ class Engine:
             raise ValueError(f"pics_compare: {n} pictures against {len(b_pids)}")
         sp = OhCompareSpec(OhWindow(*window), CMP_SSIM if ssim else 0)
         out = (OhCompare * max(n, 1))()
-        self._chk(self.L.oh_pics_compare(self.h, (C.c_int * max(n, 1))(*a_pids), (C.c_int * max(n, 1))(*b_pids), n, C.byref(sp), out),
+        self._chk(self.L.oh_pics_compare(self.h, _ids(a_pids), _ids(b_pids), n, C.byref(sp), out),
                   "oh_pics_compare")
         return [Compare(out[i], self._pic_params(a_pids[i]).bit_depth) for i in range(n)]
 
@@ -1420,17 +1332,8 @@ class Engine:
             raise ValueError("pics_resize needs at least one picture (the destinations follow the pictures' params)")
         width, height = int(size[0]), int(size[1])
         rs = OhResize(resize_filter(filter), OhWindow(*window), width, height)
-
-        def fitting():
-            sp = self._pic_params(pids[0])
-            if width < 1 or height < 1:
-                raise ValueError(f"size {size}: at least 1 x 1")
-            return self._sized(sp, width, height)
-
-        out, made = self._dsts(out, n, "sources", fitting)
-        self._call(self.L.oh_pics_resize(self.h, (C.c_int * n)(*pids), (C.c_int * n)(*out), n, C.byref(rs)), "oh_pics_resize", made)
-        dp = self._pic_params(out[0])
-        return out, (0, dp.width - width, 0, dp.height - height)
+        return self._image_call(lambda src, dst: self.L.oh_pics_resize(self.h, src, dst, n, C.byref(rs)), "oh_pics_resize", pids, out, width, height,
+                                f"size {size}: at least 1 x 1")
 
     def pics_reformat(self, pids, *, bit_depth=None, chroma_format_idc=None, depth="round", down="linear", up="linear", out=None):
         """finished pictures -> finished pictures of another bit depth and / or chroma format and the same size (oh_pics_reformat):
@@ -1440,7 +1343,7 @@ class Engine:
         replaced where given.  Returns the destination ids.  Enqueued on the engine stream; does not wait."""
         pids = list(pids)
         n = len(pids)
-        rf = OhReformat(_rf_enum(RF_DEPTH, "depth mode", depth), _rf_enum(RF_FILTERS, "down filter", down), _rf_enum(RF_FILTERS, "up filter", up))
+        rf = OhReformat(_enum(RF_DEPTH, "depth mode", depth), _enum(RF_FILTERS, "down filter", down), _enum(RF_FILTERS, "up filter", up))
         if out is None and n == 0:
             return []
 
@@ -1453,7 +1356,7 @@ class Engine:
             return dp
 
         out, made = self._dsts(out, n, "sources", reformatted)
-        self._call(self.L.oh_pics_reformat(self.h, (C.c_int * max(n, 1))(*pids), (C.c_int * max(n, 1))(*out), n, C.byref(rf)),
+        self._call(self.L.oh_pics_reformat(self.h, _ids(pids), _ids(out), n, C.byref(rf)),
                    "oh_pics_reformat", made)
         return out
 
@@ -1475,16 +1378,8 @@ class Engine:
         width, height = sp.width - od.win.left - od.win.right, sp.height - od.win.top - od.win.bottom
         if code & ORIENT_TRANSPOSE:
             width, height = height, width
-
-        def fitting():
-            if width < 1 or height < 1:
-                raise ValueError(f"window {tuple(window)} leaves nothing of {sp.width}x{sp.height}")
-            return self._sized(sp, width, height)
-
-        out, made = self._dsts(out, n, "sources", fitting)
-        self._call(self.L.oh_pics_orient(self.h, (C.c_int * n)(*pids), (C.c_int * n)(*out), n, C.byref(od)), "oh_pics_orient", made)
-        dp = self._pic_params(out[0])
-        return out, (0, dp.width - width, 0, dp.height - height)
+        return self._image_call(lambda src, dst: self.L.oh_pics_orient(self.h, src, dst, n, C.byref(od)), "oh_pics_orient", pids, out, width, height,
+                                f"window {tuple(window)} leaves nothing of {sp.width}x{sp.height}")
 
     def pics_warp(self, pids, matrix, size, *, mode=None, filter="bilinear", border="replicate", fill=(0, 0, 0), window=(0, 0, 0, 0), out=None):
         """finished pictures -> finished pictures resampled through an affine or perspective map (oh_pics_warp): matrix is the INVERSE
@@ -1506,19 +1401,10 @@ class Engine:
         fill = [int(v) for v in fill]
         if len(fill) != 3 or any(not 0 <= v <= 0xFFFF for v in fill):
             raise ValueError(f"fill {tuple(fill)}: three code values")
-        wp = OhWarp(code, _warp_enum(WARP_FILTERS, "filter", filter), _warp_enum(WARP_BORDERS, "border", border), (C.c_uint16 * 3)(*fill),
+        wp = OhWarp(code, _enum(WARP_FILTERS, "filter", filter, WARP_FILTERS.values()), _enum(WARP_BORDERS, "border", border, WARP_BORDERS.values()), (C.c_uint16 * 3)(*fill),
                     OhWindow(*window), width, height, (C.c_int64 * 9)(*m))
-
-        def fitting():
-            sp = self._pic_params(pids[0])
-            if width < 1 or height < 1:
-                raise ValueError(f"size {size}: at least 1 x 1")
-            return self._sized(sp, width, height)
-
-        out, made = self._dsts(out, n, "sources", fitting)
-        self._call(self.L.oh_pics_warp(self.h, (C.c_int * n)(*pids), (C.c_int * n)(*out), n, C.byref(wp)), "oh_pics_warp", made)
-        dp = self._pic_params(out[0])
-        return out, (0, dp.width - width, 0, dp.height - height)
+        return self._image_call(lambda src, dst: self.L.oh_pics_warp(self.h, src, dst, n, C.byref(wp)), "oh_pics_warp", pids, out, width, height,
+                                f"size {size}: at least 1 x 1")
 
     def _of_height(self, pid, height):
         """the params of picture pid with another height; ValueError where oh_pic_alloc would refuse the height"""
@@ -1540,8 +1426,7 @@ class Engine:
         if len(bottom) != n:
             raise ValueError(f"{n} top fields, {len(bottom)} bottom fields")
         out, made = self._dsts(out, n, "pairs of fields", lambda: self._of_height(top[0], 2 * self._pic_params(top[0]).height))
-        IA = C.c_int * n
-        self._call(self.L.oh_pics_weave(self.h, IA(*top), IA(*bottom), IA(*out), n), "oh_pics_weave", made)
+        self._call(self.L.oh_pics_weave(self.h, _ids(top), _ids(bottom), _ids(out), n), "oh_pics_weave", made)
         return out
 
     def pics_separate(self, pids, *, top=True, bottom=True, out=None):
@@ -1567,8 +1452,7 @@ class Engine:
             if len(sides) != 2 or (sides[0] is None) != (not top) or (sides[1] is None) != (not bottom):
                 raise ValueError("out: a pair (top ids, bottom ids) with None for the side that is not asked for")
             sides = [None if s is None else self._dsts(s, n, "sources", None)[0] for s in sides]
-        IA = C.c_int * n
-        self._call(self.L.oh_pics_separate(self.h, IA(*pids), IA(*sides[0]) if top else None, IA(*sides[1]) if bottom else None, n),
+        self._call(self.L.oh_pics_separate(self.h, _ids(pids), _ids(sides[0]) if top else None, _ids(sides[1]) if bottom else None, n),
                    "oh_pics_separate", made)
         return sides[0], sides[1]
 
@@ -1590,10 +1474,9 @@ class Engine:
         else:
             raise ValueError(f"keep {keep!r}: 'top' (0) or 'bottom' (1)")
         dd = OhDeinterlace(deint_mode(mode), parity, int(bool(kept_first)))
-        IA = C.c_int * n
         around = self._around(n, prev, next)
         out, made = self._dsts(out, n, "sources", lambda: self._pic_params(pids[0]))
-        self._call(self.L.oh_pics_deinterlace(self.h, around[0], IA(*pids), around[1], IA(*out), n, C.byref(dd)), "oh_pics_deinterlace", made)
+        self._call(self.L.oh_pics_deinterlace(self.h, around[0], _ids(pids), around[1], _ids(out), n, C.byref(dd)), "oh_pics_deinterlace", made)
         return out
 
     def pics_filter(self, pids, mode, *, luma=None, chroma=None, amount=64, threshold=0, planes=7, prev=None, next=None, out=None):
@@ -1617,10 +1500,9 @@ class Engine:
             if len(pair) != 2:
                 raise ValueError(f"{name}: an int or a pair (luma, chroma)")
             arr[0], arr[1] = int(pair[0]), int(pair[1])
-        IA = C.c_int * n
         around = self._around(n, prev, next)
         out, made = self._dsts(out, n, "sources", lambda: self._pic_params(pids[0]))
-        self._call(self.L.oh_pics_filter(self.h, around[0], IA(*pids), around[1], IA(*out), n, C.byref(ff)), "oh_pics_filter", made)
+        self._call(self.L.oh_pics_filter(self.h, around[0], _ids(pids), around[1], _ids(out), n, C.byref(ff)), "oh_pics_filter", made)
         return out
 
     def pics_motion(self, cur, ref, block=16, range=(8, 8), subpel=2, lam=0, centres=None):
@@ -1650,8 +1532,7 @@ class Engine:
             ms.centres = (c if c.size else np.zeros(2, np.int16)).ctypes.data_as(C.POINTER(C.c_int16))
         out = np.zeros((n, bh, bw), dtype=MOTION_DTYPE)
         buf = out if out.size else np.zeros(1, dtype=MOTION_DTYPE)
-        IA = C.c_int * max(n, 1)
-        self._chk(self.L.oh_pics_motion(self.h, IA(*cur), IA(*ref), n, C.byref(ms), buf.ctypes.data_as(C.POINTER(OhMotionVector))), "oh_pics_motion")
+        self._chk(self.L.oh_pics_motion(self.h, _ids(cur), _ids(ref), n, C.byref(ms), buf.ctypes.data_as(C.POINTER(OhMotionVector))), "oh_pics_motion")
         return out
 
     def pics_motion_compensate(self, ref, field, block=16, out=None):
@@ -1671,10 +1552,9 @@ class Engine:
             bw, bh = motion_blocks(p.width, p.height, block)
             if f.shape != (n, bh, bw):
                 raise ValueError(f"pics_motion_compensate: a field of shape {f.shape}, not {(n, bh, bw)}")
-        IA = C.c_int * n
         out, made = self._dsts(out, n, "sources", lambda: self._pic_params(ref[0]))
         buf = f if f.size else np.zeros(1, dtype=MOTION_DTYPE)
-        self._call(self.L.oh_pics_motion_compensate(self.h, IA(*ref), IA(*out), n, int(block), buf.ctypes.data_as(C.POINTER(OhMotionVector))),
+        self._call(self.L.oh_pics_motion_compensate(self.h, _ids(ref), _ids(out), n, int(block), buf.ctypes.data_as(C.POINTER(OhMotionVector))),
                    "oh_pics_motion_compensate", made)
         return out
 
@@ -1686,7 +1566,7 @@ class Engine:
         n = len(pids)
         win = OhWindow(*window)
         out = (OhHistogram * max(n, 1))()
-        self._chk(self.L.oh_pics_histogram(self.h, (C.c_int * max(n, 1))(*pids), n, C.byref(win), out), "oh_pics_histogram")
+        self._chk(self.L.oh_pics_histogram(self.h, _ids(pids), n, C.byref(win), out), "oh_pics_histogram")
         return [Histogram(out[i], self._pic_params(pids[i]).bit_depth) for i in range(n)]
 
     def pics_lut(self, pids, tables, *, planes=None, bit_depth=None, out=None):
@@ -1724,7 +1604,7 @@ class Engine:
             return dp
 
         out, made = self._dsts(out, n, "sources", with_depth)
-        self._call(self.L.oh_pics_lut(self.h, (C.c_int * max(n, 1))(*pids), (C.c_int * max(n, 1))(*out), n, C.byref(lut)), "oh_pics_lut", made)
+        self._call(self.L.oh_pics_lut(self.h, _ids(pids), _ids(out), n, C.byref(lut)), "oh_pics_lut", made)
         return out
 
     def pics_compose(self, dst, layers, *, fill=None):
@@ -1753,7 +1633,7 @@ class Engine:
             src = list(l.src) if isinstance(l.src, (list, tuple)) else [int(l.src)] * n
             if len(src) != n:
                 raise ValueError(f"layer {k}: {len(src)} sources for {n} destinations")
-            ids = (C.c_int32 * max(n, 1))(*src)
+            ids = _ids(src)
             keep.append(ids)
             if l.rect is None:
                 sp = self._pic_params(src[0]) if n else None
@@ -1781,7 +1661,7 @@ class Engine:
         cp = OhCompose(COMPOSE_FILL if fill is not None else 0, (C.c_int32 * 3)(*([int(v) for v in fill] + [0, 0])[:3] if fill is not None else (0, 0, 0)),
                        len(layers), ol)
         with self._torch_ordered(torch):                      # the alpha planes are torch's
-            self._chk(self.L.oh_pics_compose(self.h, (C.c_int * max(n, 1))(*dst), n, C.byref(cp)), "oh_pics_compose")
+            self._chk(self.L.oh_pics_compose(self.h, _ids(dst), n, C.byref(cp)), "oh_pics_compose")
         return dst
 
     def _pic_params(self, pid):

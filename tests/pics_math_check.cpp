@@ -259,6 +259,33 @@ static int ids_group(void)
     return cases + 1;
 }
 
+/* the window in a plane class (class_window) against plain shifts, every output a heap block of one int32_t */
+static int class_window_group(void)
+{
+    int cases = 0;
+    const int sizes[2][2] = { { 16, 8 }, { 24, 16 } }, offs[3] = { 0, 2, 6 };
+    for (int cf = 0; cf <= 3; cf++)
+        for (const auto &size : sizes)
+            for (int l : offs) for (int r : offs) for (int t : offs) for (int b : offs) {
+                OhPicParams p;
+                memset(&p, 0, sizeof(p));
+                p.width = size[0]; p.height = size[1]; p.chroma_format_idc = cf;
+                const OhWindow w = { l, r, t, b };
+                const int W = p.width - l - r, H = p.height - t - b;
+                if (W < 2 || H < 2)
+                    continue;
+                for (int q = 0; q <= 1; q++, cases++) {
+                    const int sx = q && (cf == 1 || cf == 2), sy = q && cf == 1;
+                    auto x0 = heap<int32_t>(1), y0 = heap<int32_t>(1), ws = heap<int32_t>(1), hs = heap<int32_t>(1);
+                    class_window(&p, w, q, x0.get(), y0.get(), ws.get(), hs.get());
+                    CHECK(x0[0] == l >> sx && y0[0] == t >> sy && ws[0] == W >> sx && hs[0] == H >> sy,
+                          "chroma format %d, %dx%d, window (%d,%d,%d,%d), class %d: %dx%d at (%d,%d)", cf, p.width, p.height, l, r, t, b, q,
+                          ws[0], hs[0], x0[0], y0[0]);
+                }
+            }
+    return cases;
+}
+
 int main()
 {
     printf("resize taps: %d axes\n", resize_group());
@@ -267,6 +294,7 @@ int main()
     printf("light bins and percentiles: %d values\n", light_group());
     printf("ssim window and blend: %d points\n", window_and_blend_group());
     printf("ids apart, neighbours and the window size: %d cases\n", ids_group());
+    printf("the window in a plane class: %d cases\n", class_window_group());
     if (failures) fprintf(stderr, "%d checks failed\n", failures);
     else printf("pics math ok\n");
     return failures ? 1 : 0;

@@ -3,6 +3,7 @@ pictures made for it that are freed again when an allocation fails or the librar
 call; its pic_alloc, pic_free and the one library function a wrapper calls are stand-ins that record ids — no GPU, nothing preloaded."""
 import types
 
+import numpy as np
 import pytest
 
 from openhevc_amd import frame as F
@@ -56,6 +57,10 @@ SERVICES = {
     "separate_top": ("oh_pics_separate", lambda e, out: e.pics_separate(SRC, bottom=False, out=out), lambda k: (_given(k), None)),
     "deinterlace": ("oh_pics_deinterlace", lambda e, out: e.pics_deinterlace(SRC, "adaptive", prev=[None, 1, 2], out=out), _given),
     "filter": ("oh_pics_filter", lambda e, out: e.pics_filter(SRC, "temporal", next=[2, 3, None], out=out), _given),
+    "lut": ("oh_pics_lut", lambda e, out: e.pics_lut(SRC, np.arange(256, dtype=np.uint16), out=out), _given),
+    "motion_compensate": ("oh_pics_motion_compensate", lambda e, out: e.pics_motion_compensate(SRC, np.zeros((N, 1, 1, 2), np.int16), out=out),
+                          _given),
+    "warp": ("oh_pics_warp", lambda e, out: e.pics_warp(SRC, [65536, 0, 0, 0, 65536, 0], (8, 8), out=out), _given),
 }
 ALL = pytest.mark.parametrize("service", sorted(SERVICES))
 
@@ -84,7 +89,7 @@ def test_fresh_pictures_are_returned(service):
     name, call, _ = SERVICES[service]
     rig = Rig(name)
     got = call(rig.e, None)
-    ids = got[0] if service in ("resize", "orient") else got
+    ids = got[0] if service in ("resize", "orient", "warp") else got
     if service.startswith("separate"):
         ids = ids[0] + (ids[1] or [])
     assert ids == rig.made and rig.freed == [] and rig.calls == 1

@@ -1,5 +1,5 @@
 """The host arithmetic of the picture services (openhevc_amd/csrc/pics_math.hip: coefficients, colour tables, light-level bins, the SSIM
-window, resize taps, the blend) writes caller-sized arrays from shift, __int128 and llround arithmetic: tests/pics_math_check.cpp runs it
+window, resize taps, the blend, the window in a plane class) writes caller-sized arrays from shift, __int128 and llround arithmetic: tests/pics_math_check.cpp runs it
 at the extremes of its domain over heap blocks of exactly the documented sizes, as a stand-alone program built with AddressSanitizer
 and UBSan — no GPU, nothing loaded into Python."""
 import os
@@ -18,4 +18,4 @@ def test_pics_math_under_sanitizers(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.rstrip().endswith("pics math ok"), r.stdout + r.stderr
-    assert len(r.stdout.splitlines()) == 7                               # one line per group, then the verdict
+    assert len(r.stdout.splitlines()) == 8                               # one line per group, then the verdict
