@@ -110,6 +110,37 @@ typedef struct OhPicTiming {
  * zero), or -1: not an SEI NAL unit, a message that runs past the unit, or frame_field_info_present set and an empty payload. */
 int oh_sei_pic_timing(const uint8_t *nal, size_t size, int frame_field_info_present, OhPicTiming *out);
 
+/* The film grain characteristics message of H.265 Annex D (payload type 19), which the reference does not parse: the grain that the
+ * encoder removed and the decoder is to synthesise again on the displayed picture.  Bits, MSB first, of the unescaped payload:
+ * film_grain_characteristics_cancel_flag u(1); unless cancelled film_grain_model_id u(2), separate_colour_description_present_flag
+ * u(1); with the description film_grain_bit_depth_luma_minus8 u(3), film_grain_bit_depth_chroma_minus8 u(3), film_grain_full_range_flag
+ * u(1), film_grain_colour_primaries u(8), film_grain_transfer_characteristics u(8), film_grain_matrix_coeffs u(8); then
+ * blending_mode_id u(2), log2_scale_factor u(4), comp_model_present_flag[c] u(1) for c = 0 .. 2; per present c
+ * num_intensity_intervals_minus1 u(8), num_model_values_minus1 u(3) and per interval intensity_interval_lower_bound u(8),
+ * intensity_interval_upper_bound u(8) and per model value comp_model_value se(v); at the end
+ * film_grain_characteristics_persistence_flag u(1).  Every field is kept as coded; what lies behind a cancel flag, an absent
+ * description or an absent component is 0.  oh_grain_from_sei (ohevc_hip.h) turns the message into the tables of oh_pics_grain. */
+enum { OH_FG_MAX_INTERVALS = 256, OH_FG_MAX_VALUES = 6 };
+typedef struct OhFilmGrainSei {
+    int32_t present;                  /* a message was found */
+    int32_t cancel;                   /* film_grain_characteristics_cancel_flag */
+    int32_t model_id;
+    int32_t separate_colour_description;
+    int32_t bit_depth_luma_minus8, bit_depth_chroma_minus8, full_range;
+    int32_t colour_primaries, transfer_characteristics, matrix_coeffs;
+    int32_t blending_mode_id, log2_scale_factor;
+    int32_t comp_model_present[3];
+    int32_t num_intensity_intervals_minus1[3], num_model_values_minus1[3];
+    int32_t persistence;
+    uint8_t lower[3][OH_FG_MAX_INTERVALS], upper[3][OH_FG_MAX_INTERVALS];
+    int32_t value[3][OH_FG_MAX_INTERVALS][OH_FG_MAX_VALUES];
+} OhFilmGrainSei;
+/* nal[0 .. size): one (escaped) SEI NAL unit, header first.  The same message walk as oh_sei_display_orientation.  The message counts
+ * in a prefix SEI only; in a suffix SEI it is passed over; of several in one unit the last counts.  Returns 1 found, 0 none (*out is
+ * zero), or -1 (*out is zero): not an SEI NAL unit, a message that runs past the unit, a field that lies past the end of the payload,
+ * num_model_values_minus1 above 5, an se(v) code of more than 32 leading zeros or one whose value does not fit an int32_t. */
+int oh_sei_film_grain(const uint8_t *nal, size_t size, OhFilmGrainSei *out);
+
 #ifdef __cplusplus
 }
 #endif

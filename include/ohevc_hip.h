@@ -733,6 +733,78 @@ int oh_lut_stretch(const OhPlaneHist *h, int n, uint32_t lo_ppm, uint32_t hi_ppm
 int oh_lut_equalise(const OhPlaneHist *h, int n, int bd, uint16_t *out);
 int oh_lut_then(const uint16_t *first, int n1, const uint16_t *second, int n2, uint16_t *out);
 
+/* Film grain: n finished pictures become n finished pictures of identical params with synthesised grain added, as the film grain
+ * characteristics SEI (ohevc_annexb.h: oh_sei_film_grain) asks of a decoder after its output process (the tests check
+ * every coded plane bit for bit against tests/grain_model.py).  The profile of the message is SMPTE RDD 5's — model 0 (frequency
+ * filtering), up to three model values (sigma, horizontal and vertical cut-off in sixteenths of the band, 2 .. 14), 8 x 8 blocks chosen
+ * by their mean intensity, smoothing across block edges — but the synthesis is this project's own and NOT bit-exact with RDD 5, whose
+ * Gaussian and seed tables it does not use: every sample is defined in integers below.
+ * Definitions.  fmix(h): h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16 in uint32.
+ * H(a, b, c, d) = fmix(a ^ fmix(b ^ fmix(c ^ fmix(d ^ 0x9e3779b9)))).  gauss(h) = the sum of the four bytes of h, minus 510.
+ * Pattern P[fh][fv], fh and fv in 2 .. 14, 32 x 32 int8: coefficients C[v][u] (int16, row v the vertical frequency) =
+ * 8 gauss(H(1, 16 fh + fv, u, v)) where u < 2 fh, v < 2 fv and (u, v) != (0, 0), else 0; raw = HEVC's inverse 32 x 32 transform of C
+ * at bit depth 8 (H.265 8.6.4.2: stage shifts 7 and 12, 16-bit clip between the stages); r = isqrt(sum raw^2 / 1024) (integer division,
+ * floor square root); P = clip(-127, 127, floor((64 raw + r) / (2 r))).
+ * A table per plane of 256 uint32_t, indexed by a block's 8-bit mean: entry = sigma | fh << 8 | fv << 12; sigma 0: no grain.
+ * Block (bx, by) of plane c covers the samples x in 8 bx .. 8 bx + 7, y in 8 by .. 8 by + 7 that the coded plane has (n = 64, 32 or 16
+ * of them: plane sizes are multiples of 4): a8 = ((sum of the samples + n / 2) / n) >> (bd - 8), entry = table[c][a8],
+ * h = H(2, seed, c, 65536 by + bx), ox = ((h & 0xFFFF) 25) >> 16, oy = (((h >> 16) & 0x7FFF) 25) >> 15, negate = h >> 31.
+ * Sample (x, y): p = +-P[fh][fv][oy + (y & 7)][ox + (x & 7)], g = (sigma p 2^(bd - 8) + 2^(4 + log2_scale)) >> (5 + log2_scale)
+ * (arithmetic shift).  At x = 7 mod 8 with x + 1 < W and at x = 0 mod 8 with x > 0, g' = (g(x - 1) + 2 g(x) + g(x + 1) + 2) >> 2 from
+ * the unsmoothed values of both blocks, elsewhere g' = g.  blending 0 (additive): out = clip(0, 2^bd - 1, s + g'); blending 1
+ * (multiplicative, this project's definition): out = clip(0, 2^bd - 1, s + ((s g' + 2^(bd - 1)) >> bd)).  A plane whose bit in planes
+ * is clear is copied.  seeds: one per picture — a caller passes the POC, so that a picture looks the same however often it is shown.
+ * Bits of planes the format lacks are ignored, as are their table pointers.  Reads finished halves, writes half 0 of each destination
+ * and marks it finished, like oh_pics_lut; enqueued on the engine stream, returns without waiting.  Tables and seeds are copied by the
+ * call: the host arrays may be freed on return.  The 169 patterns (173 KB) are built on the first call of an engine and stay in device
+ * memory.  n == 0: OH_OK (planes, blending and log2_scale are checked all the same).  More than OH_CONV_MAX_PICS pictures are split
+ * into several launches.
+ * OH_E_ARG, nothing written: a null e, g, seeds or id array, a negative n; an unknown picture; params that differ anywhere among the
+ * 2n pictures; a destination that is also a source, or listed twice; planes outside 0 .. 7; blending outside 0 .. 1; log2_scale
+ * outside 0 .. 15; a null table of a selected plane that the format has; an entry of such a table above 0xFFFF, or with a non-zero
+ * sigma and a cut-off outside 2 .. 14.  No combination gives OH_E_UNSUPPORTED. */
+enum { OH_GRAIN_ADDITIVE = 0, OH_GRAIN_MULTIPLICATIVE = 1 };
+enum { OH_GRAIN_ENTRIES = 256 };
+typedef struct OhGrain {
+    int32_t planes;               /* bit c set: plane c gets grain by table[c]; clear: plane c is copied */
+    int32_t blending;             /* OH_GRAIN_* */
+    int32_t log2_scale;           /* 0 .. 15 */
+    const uint32_t *table[3];     /* HOST tables of OH_GRAIN_ENTRIES entries */
+} OhGrain;
+int oh_pics_grain(OhEngine *e, const int *src_ids, const int *dst_ids, int n, const OhGrain *g, const uint32_t *seeds);
+/* host only: the pieces of the definition above, which the kernel shares (csrc/grain_common.h).
+ *   oh_grain_hash      H(a, b, c, d);   oh_grain_gauss   gauss(h)
+ *   oh_grain_pattern   pattern (fh, fv): coeffs and raw 1024 int16, pattern 1024 int8, row-major; any of the three may be null.
+ *                      OH_E_ARG: a cut-off outside 2 .. 14
+ *   oh_grain_uniform   all 256 entries of out = sigma | fh << 8 | fv << 12.  OH_E_ARG: a null out, sigma outside 0 .. 255, a cut-off
+ *                      outside 2 .. 14
+ *   oh_grain_from_sei  the tables of a message: per present component and interval, sigma = value 0, fh = value 1 (8 where the message
+ *                      has one value), fv = value 2 (fh where it has fewer than three) over lower .. upper; intensities in no interval
+ *                      and components without a model get entry 0.  out->planes from comp_model_present_flag, blending from
+ *                      blending_mode_id, log2_scale from log2_scale_factor, table[c] = tables[c].  The separate colour description is
+ *                      ignored: the grain is added to the decoded samples as they are.  OH_E_ARG: a null pointer, a message that is
+ *                      absent (present 0) or cancelled.  OH_E_UNSUPPORTED: model_id other than 0, blending_mode_id above 1, more than
+ *                      3 model values, a sigma outside 0 .. 255, a cut-off outside 2 .. 14, lower above upper, overlapping intervals
+ *                      of one component; tables and out are untouched then
+ *   oh_grain_block     ox, oy, negate of block (bx, by), each 0 .. 65535, of plane c (0 .. 2).  OH_E_ARG: outside those, a null pointer
+ *   oh_grain_mean      a8 of a block of n (64, 32 or 16) samples of bd bits (8, 9, 10, 12) that sum to sum; -1: other n or bd
+ *   oh_grain_value     g of a pattern value p (-127 .. 127, signed by negate), sigma 0 .. 255, log2_scale 0 .. 15 at bd bits (8, 9, 10,
+ *                      12): |g| <= 16193, far inside OH_GRAIN_MAX.  0 outside these domains
+ *   oh_grain_smooth    g' of a sample at a block edge: (left + 2 g + right + 2) >> 2.  0 unless all three lie in +-OH_GRAIN_MAX
+ *   oh_grain_blend     out of a sample s (0 .. 2^bd - 1) and its g' (+-OH_GRAIN_MAX), blending 0 or 1.  0 outside these domains */
+enum { OH_GRAIN_MAX = 1 << 18 };
+uint32_t oh_grain_hash(uint32_t a, uint32_t b, uint32_t c, uint32_t d);
+int32_t oh_grain_gauss(uint32_t h);
+int oh_grain_pattern(int fh, int fv, int16_t *coeffs, int16_t *raw, int8_t *pattern);
+int oh_grain_uniform(int sigma, int fh, int fv, uint32_t *out);
+struct OhFilmGrainSei;
+int oh_grain_from_sei(const struct OhFilmGrainSei *sei, uint32_t tables[3][256], OhGrain *out);
+int oh_grain_block(uint32_t seed, int c, int bx, int by, int *ox, int *oy, int *negate);
+int32_t oh_grain_mean(uint32_t sum, int n, int bit_depth);
+int32_t oh_grain_value(int32_t sigma, int32_t p, int bit_depth, int log2_scale);
+int32_t oh_grain_smooth(int32_t left, int32_t g, int32_t right);
+int32_t oh_grain_blend(int32_t s, int32_t g, int bit_depth, int blending);
+
 /* Motion: a block-matching search between two finished pictures and the motion-compensated prediction that such a field describes, in
  * HEVC's quarter-sample units with HEVC's interpolation filters, so that a vector means what it means to an HEVC decoder (DESIGN.md
  * §3o; the tests check every field and every plane bit for bit against tests/motion_model.py, which is held against the oracle's

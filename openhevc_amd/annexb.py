@@ -1,4 +1,4 @@
-"""ctypes view of include/ohevc_annexb.h (libohevc_host.so): access-unit splitter, NAL scan, NAL unescape, picture-hash SEI, HDR SEIs, display-orientation SEI, picture timing SEI."""
+"""ctypes view of include/ohevc_annexb.h (libohevc_host.so): access-unit splitter, NAL scan, NAL unescape, picture-hash SEI, HDR SEIs, display-orientation SEI, picture timing SEI, film grain SEI."""
 import ctypes as C
 import os
 
@@ -34,6 +34,19 @@ class OhPicTiming(C.Structure):
     _fields_ = [("present", C.c_int32), ("pic_struct", C.c_int32), ("source_scan_type", C.c_int32), ("duplicate_flag", C.c_int32)]
 
 
+FG_MAX_INTERVALS, FG_MAX_VALUES = 256, 6                       # OH_FG_MAX_INTERVALS, OH_FG_MAX_VALUES
+
+
+class OhFilmGrainSei(C.Structure):
+    _fields_ = [("present", C.c_int32), ("cancel", C.c_int32), ("model_id", C.c_int32), ("separate_colour_description", C.c_int32),
+                ("bit_depth_luma_minus8", C.c_int32), ("bit_depth_chroma_minus8", C.c_int32), ("full_range", C.c_int32),
+                ("colour_primaries", C.c_int32), ("transfer_characteristics", C.c_int32), ("matrix_coeffs", C.c_int32),
+                ("blending_mode_id", C.c_int32), ("log2_scale_factor", C.c_int32), ("comp_model_present", C.c_int32 * 3),
+                ("num_intensity_intervals_minus1", C.c_int32 * 3), ("num_model_values_minus1", C.c_int32 * 3), ("persistence", C.c_int32),
+                ("lower", (C.c_uint8 * FG_MAX_INTERVALS) * 3), ("upper", (C.c_uint8 * FG_MAX_INTERVALS) * 3),
+                ("value", ((C.c_int32 * FG_MAX_VALUES) * FG_MAX_INTERVALS) * 3)]
+
+
 _lib = None
 
 
@@ -62,6 +75,8 @@ def lib():
         L.oh_sei_display_orientation.restype = C.c_int
         L.oh_sei_pic_timing.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(OhPicTiming)]
         L.oh_sei_pic_timing.restype = C.c_int
+        L.oh_sei_film_grain.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(OhFilmGrainSei)]
+        L.oh_sei_film_grain.restype = C.c_int
         _lib = L
     return _lib
 
@@ -166,3 +181,81 @@ def pic_timing(nal, frame_field_info_present=True):
     if not r:
         return None
     return dict(pic_struct=int(d.pic_struct), source_scan_type=int(d.source_scan_type), duplicate_flag=int(d.duplicate_flag))
+
+
+def film_grain_struct(nal):
+    """None, or the OhFilmGrainSei of the film grain characteristics message (payload type 19) of one prefix SEI NAL unit"""
+    g = OhFilmGrainSei()
+    r = lib().oh_sei_film_grain(nal, len(nal), C.byref(g))
+    if r < 0:
+        raise ValueError("malformed SEI NAL unit")
+    return g if r else None
+
+
+def film_grain(nal):
+    """None, or a dict of the film grain characteristics message (payload type 19) of one prefix SEI NAL unit (oh_sei_film_grain),
+    every field as coded: "cancel" (bool; a cancelled message holds nothing else), "model_id", "colour" (None, or a dict of
+    "bit_depth_luma", "bit_depth_chroma", "full_range", "colour_primaries", "transfer_characteristics", "matrix_coeffs" where the
+    separate colour description is present), "blending_mode_id", "log2_scale_factor", "persistence" (bool) and "components": three
+    entries, None for a component without a model, else a list of (lower, upper, [model values]) per intensity interval.
+    engine.grain_from_sei turns the dict into what Engine.pics_grain takes."""
+    g = film_grain_struct(nal)
+    if g is None:
+        return None
+    if g.cancel:
+        return dict(cancel=True)
+    colour = None
+    if g.separate_colour_description:
+        colour = dict(bit_depth_luma=8 + g.bit_depth_luma_minus8, bit_depth_chroma=8 + g.bit_depth_chroma_minus8,
+                      full_range=bool(g.full_range), colour_primaries=int(g.colour_primaries),
+                      transfer_characteristics=int(g.transfer_characteristics), matrix_coeffs=int(g.matrix_coeffs))
+    comps = []
+    for c in range(3):
+        if not g.comp_model_present[c]:
+            comps.append(None)
+            continue
+        nv = g.num_model_values_minus1[c] + 1
+        comps.append([(int(g.lower[c][i]), int(g.upper[c][i]), [int(g.value[c][i][j]) for j in range(nv)])
+                      for i in range(g.num_intensity_intervals_minus1[c] + 1)])
+    return dict(cancel=False, model_id=int(g.model_id), colour=colour, blending_mode_id=int(g.blending_mode_id),
+                log2_scale_factor=int(g.log2_scale_factor), components=comps, persistence=bool(g.persistence))
+
+
+def film_grain_to_struct(d):
+    """the OhFilmGrainSei that film_grain would have read the dict d from"""
+    g = OhFilmGrainSei()
+    g.present = 1
+    if d.get("cancel"):
+        g.cancel = 1
+        return g
+    g.model_id = int(d.get("model_id", 0))
+    colour = d.get("colour")
+    if colour:
+        g.separate_colour_description = 1
+        g.bit_depth_luma_minus8, g.bit_depth_chroma_minus8 = int(colour["bit_depth_luma"]) - 8, int(colour["bit_depth_chroma"]) - 8
+        g.full_range = int(bool(colour["full_range"]))
+        g.colour_primaries, g.transfer_characteristics = int(colour["colour_primaries"]), int(colour["transfer_characteristics"])
+        g.matrix_coeffs = int(colour["matrix_coeffs"])
+    g.blending_mode_id, g.log2_scale_factor = int(d.get("blending_mode_id", 0)), int(d.get("log2_scale_factor", 0))
+    g.persistence = int(bool(d.get("persistence", False)))
+    comps = list(d.get("components", ()))
+    if len(comps) > 3:
+        raise ValueError("film grain: at most three components")
+    for c, iv in enumerate(comps):
+        if iv is None:
+            continue
+        iv = list(iv)
+        if not 1 <= len(iv) <= FG_MAX_INTERVALS:
+            raise ValueError(f"film grain: component {c} has {len(iv)} intervals (1 .. {FG_MAX_INTERVALS})")
+        nv = {len(v) for _, _, v in iv}
+        if len(nv) != 1 or not 1 <= min(nv) <= FG_MAX_VALUES:
+            raise ValueError(f"film grain: the intervals of component {c} have one number of model values, 1 .. {FG_MAX_VALUES}")
+        g.comp_model_present[c] = 1
+        g.num_intensity_intervals_minus1[c], g.num_model_values_minus1[c] = len(iv) - 1, nv.pop() - 1
+        for i, (lo, hi, vals) in enumerate(iv):
+            if not (0 <= int(lo) <= 255 and 0 <= int(hi) <= 255):
+                raise ValueError("film grain: the bounds of an interval are 0 .. 255")
+            g.lower[c][i], g.upper[c][i] = int(lo), int(hi)
+            for j, v in enumerate(vals):
+                g.value[c][i][j] = int(v)
+    return g

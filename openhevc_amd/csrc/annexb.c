@@ -1,5 +1,5 @@
 /*
- * annexb.c — Annex-B byte stream: access-unit splitter, NAL scan, NAL unescape, picture-hash SEI, HDR SEIs.  See include/ohevc_annexb.h for the
+ * annexb.c — Annex-B byte stream: access-unit splitter, NAL scan, NAL unescape, picture-hash SEI, HDR SEIs, display-orientation, picture timing and film grain SEIs.  See include/ohevc_annexb.h for the
  * reference lines each entry point follows.  Plain C, no dependencies.
  */
 #include "../../include/ohevc_annexb.h"
@@ -309,6 +309,95 @@ int oh_sei_pic_timing(const uint8_t *nal, size_t size, int frame_field_info_pres
     struct timing_ctx t = { out, frame_field_info_present != 0 };
     memset(out, 0, sizeof(*out));
     if (sei_walk(nal, size, timing_msg, &t) < 0) {
+        memset(out, 0, sizeof(*out));
+        return -1;
+    }
+    return out->present;
+}
+
+/* bits of a payload, MSB first; a read past the end sets bad and gives 0 */
+struct bit_reader { const uint8_t *p; size_t bits, at; int bad; };
+
+static uint32_t get_bits(struct bit_reader *b, int n)       /* n in 0 .. 32 */
+{
+    uint32_t v = 0;
+    if (b->bad || (size_t)n > b->bits - b->at) {
+        b->bad = 1;
+        return 0;
+    }
+    for (int i = 0; i < n; i++, b->at++)
+        v = (v << 1) | ((b->p[b->at >> 3] >> (7 - (b->at & 7))) & 1);
+    return v;
+}
+
+/* se(v) of H.265 9.2: codeNum k = 2^z - 1 + the z bits behind the z leading zeros and the one; the value is (k + 1) / 2 for an odd k
+ * and -k / 2 for an even one */
+static int32_t get_se(struct bit_reader *b)
+{
+    int z = 0;
+    while (!b->bad && !get_bits(b, 1))
+        if (++z > 32)
+            b->bad = 1;
+    if (b->bad)
+        return 0;
+    const uint64_t k = (((uint64_t)1 << z) - 1) + get_bits(b, z);
+    const int64_t v = (k & 1) ? (int64_t)((k + 1) >> 1) : -(int64_t)(k >> 1);
+    if (b->bad || v > INT32_MAX || v < INT32_MIN) {
+        b->bad = 1;
+        return 0;
+    }
+    return (int32_t)v;
+}
+
+static int grain_msg(void *ctx, int nut, unsigned type, const uint8_t *q, unsigned len)
+{
+    OhFilmGrainSei *out = (OhFilmGrainSei *)ctx;
+    if (nut != NAL_SEI_PREFIX || type != 19)                  /* D.2.21 film_grain_characteristics */
+        return 0;
+    struct bit_reader b = { q, (size_t)len * 8, 0, 0 };
+    memset(out, 0, sizeof(*out));                             /* the last message of the unit counts */
+    out->present = 1;
+    out->cancel = (int32_t)get_bits(&b, 1);
+    if (b.bad)
+        return -1;
+    if (out->cancel)
+        return 0;
+    out->model_id = (int32_t)get_bits(&b, 2);
+    out->separate_colour_description = (int32_t)get_bits(&b, 1);
+    if (out->separate_colour_description) {
+        out->bit_depth_luma_minus8 = (int32_t)get_bits(&b, 3);
+        out->bit_depth_chroma_minus8 = (int32_t)get_bits(&b, 3);
+        out->full_range = (int32_t)get_bits(&b, 1);
+        out->colour_primaries = (int32_t)get_bits(&b, 8);
+        out->transfer_characteristics = (int32_t)get_bits(&b, 8);
+        out->matrix_coeffs = (int32_t)get_bits(&b, 8);
+    }
+    out->blending_mode_id = (int32_t)get_bits(&b, 2);
+    out->log2_scale_factor = (int32_t)get_bits(&b, 4);
+    for (int c = 0; c < 3; c++)
+        out->comp_model_present[c] = (int32_t)get_bits(&b, 1);
+    for (int c = 0; c < 3 && !b.bad; c++) {
+        if (!out->comp_model_present[c])
+            continue;
+        out->num_intensity_intervals_minus1[c] = (int32_t)get_bits(&b, 8);
+        out->num_model_values_minus1[c] = (int32_t)get_bits(&b, 3);
+        if (b.bad || out->num_model_values_minus1[c] >= OH_FG_MAX_VALUES)
+            return -1;
+        for (int i = 0; i <= out->num_intensity_intervals_minus1[c] && !b.bad; i++) {
+            out->lower[c][i] = (uint8_t)get_bits(&b, 8);
+            out->upper[c][i] = (uint8_t)get_bits(&b, 8);
+            for (int j = 0; j <= out->num_model_values_minus1[c]; j++)
+                out->value[c][i][j] = get_se(&b);
+        }
+    }
+    out->persistence = (int32_t)get_bits(&b, 1);
+    return b.bad ? -1 : 0;
+}
+
+int oh_sei_film_grain(const uint8_t *nal, size_t size, OhFilmGrainSei *out)
+{
+    memset(out, 0, sizeof(*out));
+    if (sei_walk(nal, size, grain_msg, out) < 0) {
         memset(out, 0, sizeof(*out));
         return -1;
     }

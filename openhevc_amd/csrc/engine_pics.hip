@@ -6,6 +6,7 @@
 #include <cmath>
 #include "engine_impl.h"
 #include "pics_math.h"
+#include "grain_common.h"
 
 /* at least `bytes` of device scratch, grow-only in 1 MiB steps.  Growing frees the old block: the caller has made sure that nothing
  * enqueued still uses it. */
@@ -1505,6 +1506,67 @@ extern "C" int oh_pics_lut(OhEngine *e, const int *src_ids, const int *dst_ids, 
             write_planes(get_pic(e, dst_ids[i0 + i]), np, a.dst[i]);
         }
         ohk_lut(&a, m, e->stream);
+    });
+}
+
+/* ---------------- film grain (grain.hip) ---------------- */
+extern "C" int oh_pics_grain(OhEngine *e, const int *src_ids, const int *dst_ids, int n, const OhGrain *g, const uint32_t *seeds)
+{
+    const char *who = "oh_pics_grain";
+    if (!e || n < 0 || !g || !seeds || (n && (!src_ids || !dst_ids)))
+        return OH_E_ARG;
+    std::string why;
+    if (grain_check(g, 0, &why))                                /* planes, blending, log2_scale: also of a call without pictures */
+        return refuse(e, OH_E_ARG, who, why);
+    if (!n)
+        return OH_OK;
+    const Pic *s0, *d0;
+    OH_TRY(srcs_dsts(e, who, src_ids, n, dst_ids, n, &s0, &d0));
+    if (memcmp(&s0->p, &d0->p, sizeof(OhPicParams)))
+        FAIL(e, OH_E_ARG, "%s: destination %d has other params than source %d", who, dst_ids[0], src_ids[0]);
+    const OhPicParams &p = s0->p;
+    const int np = n_planes(p);
+    if (grain_check(g, np, &why))
+        return refuse(e, OH_E_ARG, who, why);
+    /* the patterns: once per engine */
+    if (!e->grain_patterns_ready) {
+        OH_TRY(upload(e, who, "patterns", &e->grain_patterns, (size_t)GRAIN_CUTS * GRAIN_CUTS * GRAIN_PAT * GRAIN_PAT, [&](void *h) {
+            for (int fh = GRAIN_CUT_MIN; fh <= GRAIN_CUT_MAX; fh++)
+                for (int fv = GRAIN_CUT_MIN; fv <= GRAIN_CUT_MAX; fv++)
+                    (void)oh_grain_pattern(fh, fv, nullptr, nullptr, (int8_t *)h + (size_t)grain_pattern_index(fh, fv) * GRAIN_PAT * GRAIN_PAT);
+        }));
+        e->grain_patterns_ready = true;
+    }
+    /* the tables and the seeds of the call */
+    const size_t tab_bytes = (size_t)3 * OH_GRAIN_ENTRIES * sizeof(uint32_t), need = tab_bytes + (size_t)n * sizeof(uint32_t);
+    if (need > e->grain_tabs.bytes)
+        HIPCHK(e, hipStreamSynchronize(e->stream));              /* launches of earlier calls still read the old block */
+    OH_TRY(upload(e, who, "tables and seeds", &e->grain_tabs, need, [&](void *h) {
+        memset(h, 0, tab_bytes);
+        for (int c = 0; c < np; c++)
+            if (g->planes >> c & 1)
+                memcpy((uint32_t *)h + (size_t)c * OH_GRAIN_ENTRIES, g->table[c], OH_GRAIN_ENTRIES * sizeof(uint32_t));
+        memcpy((char *)h + tab_bytes, seeds, (size_t)n * sizeof(uint32_t));
+    }));
+    OhGrainArgs a;
+    memset(&a, 0, sizeof(a));
+    row_pitches(s0, np, a.pitch);
+    class_sizes(s0, np, a.w, a.h);
+    for (int q = 0; q < (np > 1 ? 2 : 1); q++) {
+        a.tx[q] = (a.w[q] + GRAIN_TW * GRAIN_BLOCK - 1) / (GRAIN_TW * GRAIN_BLOCK);
+        a.ty[q] = (a.h[q] + GRAIN_BLOCK - 1) / GRAIN_BLOCK;
+    }
+    a.np = np; a.bd = p.bit_depth;
+    a.planes = g->planes; a.blending = g->blending; a.log2_scale = g->log2_scale;
+    a.tab = (const uint32_t *)e->grain_tabs.p;
+    a.patterns = (const int8_t *)e->grain_patterns.p;
+    return launch_sets(e, n, [&](int i0, int m) {
+        for (int i = 0; i < m; i++) {
+            read_planes(get_pic(e, src_ids[i0 + i]), np, a.src[i]);
+            write_planes(get_pic(e, dst_ids[i0 + i]), np, a.dst[i]);
+        }
+        a.seeds = (const uint32_t *)((const char *)e->grain_tabs.p + tab_bytes) + i0;
+        ohk_grain(&a, m, e->stream);
     });
 }
 

@@ -261,6 +261,23 @@ struct OhLutArgs {
     int32_t         planes;          /* bit c set: plane c goes through its table; clear: it is copied (sbd == dbd) */
 };
 
+/* film grain (grain.hip): the finished planes of the sources and half 0 of the destinations of one launch by value in
+ * the kernel arguments; every picture of a launch has the same geometry.  Two plane classes (0 luma, 1 chroma).  tab, seeds and patterns
+ * lie in device memory that the engine owns: the tables and seeds of the call, filled on the stream in front of the launches, and the
+ * 169 patterns, filled once. */
+struct OhGrainArgs {
+    const void     *src[64][3];      /* OH_CONV_MAX_PICS pictures x planes: the finished halves */
+    void           *dst[64][3];      /* half 0 of the destinations */
+    const uint32_t *tab;             /* [3][OH_GRAIN_ENTRIES] */
+    const uint32_t *seeds;           /* of the launch's first picture on */
+    const int8_t   *patterns;        /* [13][13][32][32]: grain_pattern_index of grain_common.h */
+    int32_t         pitch[3];        /* bytes between rows of each plane */
+    int32_t         w[2], h[2];      /* coded size of the planes */
+    int32_t         tx[2], ty[2];    /* workgroups across (GRAIN_TW blocks each) and down (a row of blocks each) a plane */
+    int32_t         np, bd;          /* planes: 1 or 3; bit depth */
+    int32_t         planes, blending, log2_scale;   /* OhGrain */
+};
+
 /* motion search and compensation (motion.hip): the finished planes of the pictures of one launch by value in the kernel
  * arguments; every picture of a launch has the same geometry.  The centres, the field and the results of the launch's first picture lie
  * in device memory that the engine owns and fills or clears on the stream in front of the launch. */
@@ -355,6 +372,8 @@ void ohk_filter(const OhFilterArgs *a, int n, hipStream_t st);
 void ohk_histogram(const OhHistArgs *a, int n, hipStream_t st);
 /* n sources of a.src through a.tab into the n destinations of a.dst */
 void ohk_lut(const OhLutArgs *a, int n, hipStream_t st);
+/* n sources of a.src with grain added into the n destinations of a.dst */
+void ohk_grain(const OhGrainArgs *a, int n, hipStream_t st);
 /* the blocks of n pairs of a.cur / a.ref searched into a.res[0 .. n bw bh) */
 void ohk_motion_search(const OhMoSearchArgs *a, int n, hipStream_t st);
 /* n pictures of a.ref compensated by a.field[0 .. n bw bh) into the n destinations of a.dst */

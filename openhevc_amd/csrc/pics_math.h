@@ -28,5 +28,6 @@ OH_INTERNAL int warp_map_check(const OhWarp *w, std::string *why);
 OH_INTERNAL int warp_check(const OhWarp *w, int bit_depth, std::string *why);
 OH_INTERNAL int warp_image_check(const OhWarp *w, std::string *why);
 OH_INTERNAL int lut_check(const OhLut *lut, int sbd, int dbd, int np, std::string *why);
+OH_INTERNAL int grain_check(const OhGrain *g, int np, std::string *why);
 
 #endif

@@ -1,7 +1,7 @@
 /*
  * pics_math.hip — the host arithmetic of the picture services (engine_pics.hip), with neither an engine nor a device: image sizes and
  * crop windows, the ids of a call (destinations apart from sources, neighbours in time), the integers of the RGB conversions, the colour tables of the HDR forms, light-level bins and percentiles, the SSIM window
- * and PSNR, the resize taps, the compose formulas, the reformat quantisation, the orientations' group, the pic_struct table, the adaptive deinterlacer's sample, the filters' taps and samples, and what follows from a histogram's bins with the table builders, the motion helpers, and the warp's positions, taps and map builders.  No kernel, no HIP runtime call: tests/pics_math_check.cpp runs it under sanitizers.
+ * and PSNR, the resize taps, the compose formulas, the reformat quantisation, the orientations' group, the pic_struct table, the adaptive deinterlacer's sample, the filters' taps and samples, and what follows from a histogram's bins with the table builders, the motion helpers, the warp's positions, taps and map builders, and the film grain's hash, patterns, tables and samples.  No kernel, no HIP runtime call: tests/pics_math_check.cpp runs it under sanitizers.
  */
 #include <stdio.h>
 #include <string.h>
@@ -18,6 +18,8 @@
 #include "filter_common.h"
 #include "motion_common.h"
 #include "warp_common.h"
+#include "grain_common.h"
+#include "../../include/ohevc_annexb.h"
 
 static bool depth_ok(int bit_depth) { return bit_depth == 8 || bit_depth == 9 || bit_depth == 10 || bit_depth == 12; }
 
@@ -1248,5 +1250,176 @@ extern "C" int oh_warp_from_sei(int hor_flip, int ver_flip, uint32_t anticlockwi
     r.width = iw; r.height = ih;
     *out = r;
     *ow = iw; *oh = ih;
+    return OH_OK;
+}
+
+/* ---------------- film grain (grain.hip): the host-only helpers and what oh_pics_grain checks ---------------- */
+static bool cut_ok(int f) { return f >= GRAIN_CUT_MIN && f <= GRAIN_CUT_MAX; }
+
+extern "C" uint32_t oh_grain_hash(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return grain_hash(a, b, c, d); }
+extern "C" int32_t oh_grain_gauss(uint32_t h) { return grain_gauss(h); }
+
+/* one stage of HEVC's inverse 32-point transform over all 32 lines of c: down the columns (pass 0) or along the rows (pass 1) */
+static void grain_inverse_stage(int16_t *c, int pass, int shift)
+{
+    static const int8_t cosv[32] = { 64, 90, 90, 90, 89, 88, 87, 85, 83, 82, 80, 78, 75, 73, 70, 67,
+                                     64, 61, 57, 54, 50, 46, 43, 38, 36, 31, 25, 22, 18, 13, 9, 4 };
+    int m[32][32];                                              /* row k: the basis function of frequency k */
+    for (int k = 0; k < 32; k++)
+        for (int n = 0; n < 32; n++) {
+            int a = (k * (2 * n + 1)) & 127;
+            if (a > 64) a = 128 - a;
+            m[k][n] = k == 0 ? 64 : a == 32 ? 0 : a < 32 ? cosv[a] : -cosv[64 - a];
+        }
+    const int step = pass ? 1 : 32, line_step = pass ? 32 : 1;
+    for (int line = 0; line < 32; line++) {
+        int16_t *p = c + line * line_step;
+        int32_t out[32];
+        for (int i = 0; i < 32; i++) {
+            int32_t acc = 0;
+            for (int k = 0; k < 32; k++)
+                acc += m[k][i] * p[k * step];
+            acc = (acc + (1 << (shift - 1))) >> shift;
+            out[i] = std::min(std::max(acc, -32768), 32767);
+        }
+        for (int i = 0; i < 32; i++)
+            p[i * step] = (int16_t)out[i];
+    }
+}
+
+extern "C" int oh_grain_pattern(int fh, int fv, int16_t *coeffs, int16_t *raw, int8_t *pattern)
+{
+    if (!cut_ok(fh) || !cut_ok(fv))
+        return OH_E_ARG;
+    int16_t c[GRAIN_PAT * GRAIN_PAT];
+    for (int v = 0; v < GRAIN_PAT; v++)
+        for (int u = 0; u < GRAIN_PAT; u++)
+            c[v * GRAIN_PAT + u] = (u < 2 * fh && v < 2 * fv && (u || v))
+                                       ? (int16_t)(8 * grain_gauss(grain_hash(1, (uint32_t)(fh * 16 + fv), (uint32_t)u, (uint32_t)v))) : (int16_t)0;
+    if (coeffs) memcpy(coeffs, c, sizeof(c));
+    grain_inverse_stage(c, 0, 7);
+    grain_inverse_stage(c, 1, 12);                              /* 20 - bit depth, at 8 bit */
+    if (raw) memcpy(raw, c, sizeof(c));
+    if (!pattern)
+        return OH_OK;
+    int64_t ss = 0;
+    for (int i = 0; i < GRAIN_PAT * GRAIN_PAT; i++)
+        ss += (int64_t)c[i] * c[i];
+    ss /= GRAIN_PAT * GRAIN_PAT;
+    int64_t r = 0;
+    while ((r + 1) * (r + 1) <= ss) r++;                        /* at most 32767 steps */
+    for (int i = 0; i < GRAIN_PAT * GRAIN_PAT; i++) {
+        int64_t v = 0;
+        if (r) {
+            const int64_t num = 64 * (int64_t)c[i] + r, den = 2 * r;
+            v = num / den - (num % den < 0);                    /* floor */
+        }
+        pattern[i] = (int8_t)std::min<int64_t>(std::max<int64_t>(v, -127), 127);
+    }
+    return OH_OK;
+}
+
+extern "C" int oh_grain_uniform(int sigma, int fh, int fv, uint32_t *out)
+{
+    if (!out || sigma < 0 || sigma > 255 || !cut_ok(fh) || !cut_ok(fv))
+        return OH_E_ARG;
+    for (int a = 0; a < OH_GRAIN_ENTRIES; a++)
+        out[a] = (uint32_t)sigma | (uint32_t)fh << 8 | (uint32_t)fv << 12;
+    return OH_OK;
+}
+
+extern "C" int oh_grain_from_sei(const OhFilmGrainSei *sei, uint32_t tables[3][256], OhGrain *out)
+{
+    if (!sei || !tables || !out || !sei->present || sei->cancel)
+        return OH_E_ARG;
+    if (sei->model_id != 0 || sei->blending_mode_id < 0 || sei->blending_mode_id > 1 || sei->log2_scale_factor < 0 || sei->log2_scale_factor > 15)
+        return OH_E_UNSUPPORTED;
+    std::vector<uint32_t> t((size_t)3 * OH_GRAIN_ENTRIES, 0);
+    int planes = 0;
+    for (int c = 0; c < 3; c++) {
+        if (!sei->comp_model_present[c])
+            continue;
+        planes |= 1 << c;
+        const int ni = sei->num_intensity_intervals_minus1[c] + 1, nv = sei->num_model_values_minus1[c] + 1;
+        if (ni < 1 || ni > OH_FG_MAX_INTERVALS || nv < 1 || nv > 3)
+            return OH_E_UNSUPPORTED;
+        bool covered[OH_GRAIN_ENTRIES] = {};
+        for (int i = 0; i < ni; i++) {
+            const int32_t *v = sei->value[c][i];
+            const int32_t sigma = v[0], fh = nv > 1 ? v[1] : 8, fv = nv > 2 ? v[2] : fh;
+            if (sigma < 0 || sigma > 255 || !cut_ok(fh) || !cut_ok(fv) || sei->lower[c][i] > sei->upper[c][i])
+                return OH_E_UNSUPPORTED;
+            for (int a = sei->lower[c][i]; a <= sei->upper[c][i]; a++) {
+                if (covered[a])
+                    return OH_E_UNSUPPORTED;
+                covered[a] = true;
+                t[(size_t)c * OH_GRAIN_ENTRIES + a] = (uint32_t)sigma | (uint32_t)fh << 8 | (uint32_t)fv << 12;
+            }
+        }
+    }
+    memcpy(tables, t.data(), t.size() * sizeof(uint32_t));
+    out->planes = planes; out->blending = sei->blending_mode_id; out->log2_scale = sei->log2_scale_factor;
+    for (int c = 0; c < 3; c++)
+        out->table[c] = tables[c];
+    return OH_OK;
+}
+
+extern "C" int oh_grain_block(uint32_t seed, int c, int bx, int by, int *ox, int *oy, int *negate)
+{
+    if (!ox || !oy || !negate || c < 0 || c > 2 || bx < 0 || bx > 65535 || by < 0 || by > 65535)
+        return OH_E_ARG;
+    grain_block(seed, c, bx, by, ox, oy, negate);
+    return OH_OK;
+}
+
+extern "C" int32_t oh_grain_mean(uint32_t sum, int n, int bit_depth)
+{
+    if ((n != 64 && n != 32 && n != 16) || !depth_ok(bit_depth))
+        return -1;
+    return grain_mean(sum, n, bit_depth);
+}
+
+/* the three below answer 0 outside their domains: nothing is shifted by an amount, and no product formed, that the kernel never sees */
+static bool grain_in(int32_t g) { return g >= -OH_GRAIN_MAX && g <= OH_GRAIN_MAX; }
+
+extern "C" int32_t oh_grain_value(int32_t sigma, int32_t p, int bit_depth, int log2_scale)
+{
+    if (sigma < 0 || sigma > 255 || p < -127 || p > 127 || !depth_ok(bit_depth) || log2_scale < 0 || log2_scale > 15)
+        return 0;
+    return grain_value(sigma, p, bit_depth, log2_scale);
+}
+
+extern "C" int32_t oh_grain_smooth(int32_t left, int32_t g, int32_t right)
+{
+    if (!grain_in(left) || !grain_in(g) || !grain_in(right))
+        return 0;
+    return grain_smooth(left, g, right);
+}
+
+extern "C" int32_t oh_grain_blend(int32_t s, int32_t g, int bit_depth, int blending)
+{
+    if (!depth_ok(bit_depth) || blending < 0 || blending > 1 || s < 0 || s >= 1 << bit_depth || !grain_in(g))
+        return 0;
+    return grain_blend(s, g, bit_depth, blending);
+}
+
+/* what oh_pics_grain checks of the OhGrain itself, for pictures of np planes */
+int grain_check(const OhGrain *g, int np, std::string *why)
+{
+    char buf[256];
+    if (g->planes < 0 || g->planes > 7) { snprintf(buf, sizeof(buf), "planes %d outside 0 .. 7", g->planes); *why = buf; return OH_E_ARG; }
+    if (g->blending < 0 || g->blending > 1) { snprintf(buf, sizeof(buf), "blending %d outside 0 .. 1", g->blending); *why = buf; return OH_E_ARG; }
+    if (g->log2_scale < 0 || g->log2_scale > 15) { snprintf(buf, sizeof(buf), "log2_scale %d outside 0 .. 15", g->log2_scale); *why = buf; return OH_E_ARG; }
+    for (int c = 0; c < np; c++) {
+        if (!(g->planes >> c & 1))
+            continue;
+        if (!g->table[c]) { snprintf(buf, sizeof(buf), "no table for plane %d", c); *why = buf; return OH_E_ARG; }
+        for (int a = 0; a < OH_GRAIN_ENTRIES; a++) {
+            const uint32_t t = g->table[c][a];
+            if (t >> 16 || ((t & 255) && (!cut_ok((int)(t >> 8 & 15)) || !cut_ok((int)(t >> 12 & 15))))) {
+                snprintf(buf, sizeof(buf), "table[%d][%d] = 0x%x: sigma | fh << 8 | fv << 12 with cut-offs 2 .. 14", c, a, t); *why = buf; return OH_E_ARG;
+            }
+        }
+    }
     return OH_OK;
 }

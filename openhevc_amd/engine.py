@@ -747,6 +747,94 @@ def lut_then(first, second):
     return _lut_built("oh_lut_then", first.size, first.ctypes.data_as(P), first.size, second.ctypes.data_as(P), second.size)
 
 
+class OhGrain(C.Structure):                                   # include/ohevc_hip.h
+    _fields_ = [("planes", C.c_int32), ("blending", C.c_int32), ("log2_scale", C.c_int32), ("table", C.POINTER(C.c_uint32) * 3)]
+
+
+GRAIN_BLENDINGS = {"additive": 0, "multiplicative": 1}                                  # OH_GRAIN_ADDITIVE, OH_GRAIN_MULTIPLICATIVE
+GRAIN_ENTRIES = 256                                                                     # OH_GRAIN_ENTRIES
+GRAIN_TILE = (256, 8)                                                                   # GRAIN_TW blocks of GRAIN_BLOCK: a workgroup's tile
+
+
+class Grain:
+    """what Engine.pics_grain adds (OhGrain): tables, a numpy uint32 array (3, 256) of sigma | fh << 8 | fv << 12 per plane and 8-bit
+    block mean; planes, bit c set: plane c gets grain; blending, 0 additive or 1 multiplicative; log2_scale, 0 .. 15"""
+    __slots__ = ("tables", "planes", "blending", "log2_scale")
+
+    def __init__(self, tables, planes=7, blending=0, log2_scale=0):
+        t = np.asarray(tables)
+        if t.shape != (3, GRAIN_ENTRIES) or t.dtype.kind not in "iu" or (t.size and (t.min() < 0 or t.max() > 0xFFFFFFFF)):
+            raise ValueError(f"grain: tables of shape {t.shape}, not (3, {GRAIN_ENTRIES}) entries of 32 bits")
+        self.tables = np.ascontiguousarray(t, dtype=np.uint32)
+        self.planes, self.blending, self.log2_scale = int(planes), _enum(GRAIN_BLENDINGS, "blending", blending), int(log2_scale)
+
+    def __repr__(self):
+        return f"Grain(planes={self.planes}, blending={self.blending}, log2_scale={self.log2_scale})"
+
+    def as_struct(self, planes=None):
+        """the OhGrain; it points into self.tables, which must outlive the call it is passed to"""
+        g = OhGrain(self.planes if planes is None else int(planes), self.blending, self.log2_scale)
+        for c in range(3):
+            g.table[c] = self.tables[c].ctypes.data_as(C.POINTER(C.c_uint32))
+        return g
+
+
+def grain_hash(a, b, c, d):
+    """oh_grain_hash (host only): H(a, b, c, d) of the film grain definition, four uint32 -> uint32"""
+    return int(lib().oh_grain_hash(a & 0xFFFFFFFF, b & 0xFFFFFFFF, c & 0xFFFFFFFF, d & 0xFFFFFFFF))
+
+
+def grain_pattern(fh, fv, parts=False):
+    """oh_grain_pattern (host only): pattern (fh, fv), cut-offs 2 .. 14 in sixteenths of the band: a numpy int8 array (32, 32); parts:
+    (coefficients int16, raw int16, pattern int8) instead"""
+    c, r, p = np.zeros((32, 32), np.int16), np.zeros((32, 32), np.int16), np.zeros((32, 32), np.int8)
+    I16 = C.POINTER(C.c_int16)
+    _check(lib().oh_grain_pattern(int(fh), int(fv), c.ctypes.data_as(I16), r.ctypes.data_as(I16), p.ctypes.data_as(C.POINTER(C.c_int8))),
+           "oh_grain_pattern")
+    return (c, r, p) if parts else p
+
+
+def make_grain(sigma, fh=8, fv=None, *, log2_scale=0, blending="additive", planes=7):
+    """one entry for every intensity of every plane (oh_grain_uniform): sigma 0 .. 255, the horizontal and vertical cut-off fh, fv
+    (2 .. 14; fv None: fh).  The standard deviation of the grain is about sigma / 2^log2_scale code values of an 8-bit picture."""
+    t = np.zeros((3, GRAIN_ENTRIES), dtype=np.uint32)
+    _check(lib().oh_grain_uniform(int(sigma), int(fh), int(fh if fv is None else fv), t[0].ctypes.data_as(C.POINTER(C.c_uint32))),
+           "oh_grain_uniform")
+    t[1:] = t[0]
+    return Grain(t, planes, blending, log2_scale)
+
+
+def grain_from_sei(sei):
+    """oh_grain_from_sei (host only): the dict of annexb.film_grain (or an annexb.OhFilmGrainSei) -> the Grain of its tables, planes,
+    blending and scale.  EngineError with code OH_E_UNSUPPORTED for a message outside the profile (model 0, up to three model values,
+    cut-offs 2 .. 14, intervals that do not overlap), OH_E_ARG for a cancelled one.  The separate colour description is ignored."""
+    from . import annexb as A
+    if sei is None:
+        raise ValueError("grain_from_sei: no message")
+    s = sei if isinstance(sei, A.OhFilmGrainSei) else A.film_grain_to_struct(sei)
+    t = np.zeros((3, GRAIN_ENTRIES), dtype=np.uint32)
+    g = OhGrain()
+    _check(lib().oh_grain_from_sei(C.byref(s), t.ctypes.data_as(C.c_void_p), C.byref(g)), "oh_grain_from_sei")
+    return Grain(t, g.planes, g.blending, g.log2_scale)
+
+
+def grain_block(seed, c, bx, by):
+    """oh_grain_block (host only): (ox, oy, negate) of block (bx, by) of plane c of a picture with that seed"""
+    ox, oy, neg = C.c_int(), C.c_int(), C.c_int()
+    _check(lib().oh_grain_block(int(seed) & 0xFFFFFFFF, int(c), int(bx), int(by), C.byref(ox), C.byref(oy), C.byref(neg)), "oh_grain_block")
+    return ox.value, oy.value, neg.value
+
+
+def grain_seeds(seeds, n):
+    """the seeds of n pictures as a numpy uint32 array: a sequence of n ints, or one int b, which stands for b + i (a run of POCs);
+    every seed is taken modulo 2^32"""
+    if hasattr(seeds, "__len__"):
+        if len(seeds) != n:
+            raise ValueError(f"seeds: {len(seeds)} for {n} pictures")
+        return np.array([int(s) & 0xFFFFFFFF for s in seeds], dtype=np.uint32)
+    return np.array([(int(seeds) + i) & 0xFFFFFFFF for i in range(n)], dtype=np.uint32)
+
+
 def convert_image_bytes(params, cv):
     """oh_convert_image_bytes (host only): bytes of one image, 0 when the combination is not valid"""
     return int(lib().oh_convert_image_bytes(C.byref(params), C.byref(cv)))
@@ -881,6 +969,24 @@ def lib():
         L.oh_lut_stretch.argtypes = [HP, I, C.c_uint32, C.c_uint32, I, U16P]
         L.oh_lut_equalise.argtypes = [HP, I, I, U16P]
         L.oh_lut_then.argtypes = [U16P, I, U16P, I, U16P]
+        U32, I32, U32P = C.c_uint32, C.c_int32, C.POINTER(C.c_uint32)
+        L.oh_pics_grain.argtypes = [V, IP, IP, I, C.POINTER(OhGrain), U32P]
+        L.oh_grain_hash.argtypes = [U32] * 4
+        L.oh_grain_hash.restype = U32
+        L.oh_grain_gauss.argtypes = [U32]
+        L.oh_grain_gauss.restype = I32
+        L.oh_grain_pattern.argtypes = [I, I, C.POINTER(C.c_int16), C.POINTER(C.c_int16), C.POINTER(C.c_int8)]
+        L.oh_grain_uniform.argtypes = [I, I, I, U32P]
+        L.oh_grain_from_sei.argtypes = [V, V, C.POINTER(OhGrain)]
+        L.oh_grain_block.argtypes = [U32, I, I, I, IP, IP, IP]
+        L.oh_grain_mean.argtypes = [U32, I, I]
+        L.oh_grain_mean.restype = I32
+        L.oh_grain_value.argtypes = [I32, I32, I, I]
+        L.oh_grain_value.restype = I32
+        L.oh_grain_smooth.argtypes = [I32] * 3
+        L.oh_grain_smooth.restype = I32
+        L.oh_grain_blend.argtypes = [I32, I32, I, I]
+        L.oh_grain_blend.restype = I32
         L.oh_motion_blocks.argtypes = [I, I, I, IP, IP]
         L.oh_pics_motion.argtypes = [V, IP, IP, I, C.POINTER(OhMotionSearch), MVP]
         L.oh_pics_motion_compensate.argtypes = [V, IP, IP, I, I, MVP]
@@ -1605,6 +1711,27 @@ class Engine:
 
         out, made = self._dsts(out, n, "sources", with_depth)
         self._call(self.L.oh_pics_lut(self.h, _ids(pids), _ids(out), n, C.byref(lut)), "oh_pics_lut", made)
+        return out
+
+    def pics_grain(self, pids, grain, seeds, *, planes=None, out=None):
+        """finished pictures -> finished pictures of the same params with synthesised film grain added (oh_pics_grain; the exact
+        definition is in include/ohevc_hip.h).  grain: what grain_from_sei or make_grain returned; seeds: one int per picture, or one
+        int b for b, b + 1, ... — the pictures' POCs, so that a picture gets the same grain however often it is shown; planes: bit c
+        set adds grain to plane c, clear copies it (None: the grain's own planes).  out: destination pictures to reuse; None allocates
+        pictures with the sources' params.  Returns the destination ids.  Enqueued on the engine stream; does not wait; the grain and
+        the seeds may be changed at once."""
+        pids = list(pids)
+        n = len(pids)
+        if not isinstance(grain, Grain):
+            raise ValueError("pics_grain: grain is what grain_from_sei or make_grain returns")
+        sd = grain_seeds(seeds, n)
+        g = grain.as_struct(planes)
+        if out is None and n == 0:
+            return []
+        out, made = self._dsts(out, n, "sources", lambda: self._pic_params(pids[0]))
+        buf = sd if sd.size else np.zeros(1, dtype=np.uint32)   # without pictures there is nothing to read, but a non-null pointer all the same
+        self._call(self.L.oh_pics_grain(self.h, _ids(pids), _ids(out), n, C.byref(g), buf.ctypes.data_as(C.POINTER(C.c_uint32))),
+                   "oh_pics_grain", made)
         return out
 
     def pics_compose(self, dst, layers, *, fill=None):
