@@ -141,6 +141,41 @@ typedef struct OhFilmGrainSei {
  * num_model_values_minus1 above 5, an se(v) code of more than 32 leading zeros or one whose value does not fit an int32_t. */
 int oh_sei_film_grain(const uint8_t *nal, size_t size, OhFilmGrainSei *out);
 
+/* The colour remapping information message of H.265 Annex D (payload type 142), which the reference does not parse: how a display is
+ * to turn the decoded pictures into the rendition that the content owner graded — a piecewise-linear table per component, a 3 x 3
+ * matrix, a second table per component.  Bits, MSB first, of the unescaped payload: colour_remap_id ue(v), colour_remap_cancel_flag
+ * u(1); unless cancelled colour_remap_persistence_flag u(1), colour_remap_video_signal_info_present_flag u(1); with the signal info
+ * colour_remap_full_range_flag u(1), colour_remap_primaries u(8), colour_remap_transfer_function u(8),
+ * colour_remap_matrix_coefficients u(8); then colour_remap_input_bit_depth u(8), colour_remap_output_bit_depth u(8); for c = 0 .. 2
+ * pre_lut_num_val_minus1[c] u(8) and, where that is above 0, for i = 0 .. pre_lut_num_val_minus1[c] pre_lut_coded_value[c][i] u(vi),
+ * pre_lut_target_value[c][i] u(vo); colour_remap_matrix_present_flag u(1); with the matrix log2_matrix_denom u(4) and
+ * colour_remap_coeffs[c][i] se(v) for c, i = 0 .. 2; for c = 0 .. 2 post_lut_num_val_minus1[c] u(8) and, where that is above 0, per i
+ * post_lut_coded_value[c][i] u(vo), post_lut_target_value[c][i] u(vo).  The widths: vi = ((input_bit_depth + 7) >> 3) << 3, vo the
+ * same of output_bit_depth.  Every field is kept as coded; what lies behind a cancel flag or an absent flag is 0.  oh_remap_from_sei
+ * (ohevc_hip.h) turns the message into what oh_pics_colour_remap takes. */
+enum { OH_CRI_MAX_PIVOTS = 33 };
+typedef struct OhColourRemapSei {
+    int32_t present;                  /* a message was found */
+    int32_t cancel;                   /* colour_remap_cancel_flag */
+    uint32_t id;                      /* colour_remap_id */
+    int32_t persistence;
+    int32_t video_signal_info_present, full_range, primaries, transfer_function, matrix_coefficients;
+    int32_t input_bit_depth, output_bit_depth;
+    int32_t pre_lut_num_val_minus1[3];
+    uint16_t pre_lut_coded_value[3][OH_CRI_MAX_PIVOTS], pre_lut_target_value[3][OH_CRI_MAX_PIVOTS];
+    int32_t matrix_present, log2_matrix_denom;
+    int32_t coeffs[3][3];
+    int32_t post_lut_num_val_minus1[3];
+    uint16_t post_lut_coded_value[3][OH_CRI_MAX_PIVOTS], post_lut_target_value[3][OH_CRI_MAX_PIVOTS];
+} OhColourRemapSei;
+/* nal[0 .. size): one (escaped) SEI NAL unit, header first.  The same message walk as oh_sei_film_grain.  The message counts in a
+ * prefix SEI only; in a suffix SEI it is passed over.  id -1: the last message of the unit counts; otherwise the last one whose
+ * colour_remap_id equals id (a stream may carry one message per target display).  Returns 1 found, 0 none (*out is zero), or -1 (*out
+ * is zero): not an SEI NAL unit, a message that runs past the unit, a field that lies past the end of the payload, a bit depth outside
+ * 8 .. 16 (the widths of the fields behind it are defined only there), a num_val_minus1 above 32, a ue(v) / se(v) code of more than 32
+ * leading zeros or one whose value does not fit its type — in any colour remapping message of the unit, selected or not. */
+int oh_sei_colour_remap(const uint8_t *nal, size_t size, int64_t id, OhColourRemapSei *out);
+
 #ifdef __cplusplus
 }
 #endif

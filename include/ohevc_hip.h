@@ -805,6 +805,52 @@ int32_t oh_grain_value(int32_t sigma, int32_t p, int bit_depth, int log2_scale);
 int32_t oh_grain_smooth(int32_t left, int32_t g, int32_t right);
 int32_t oh_grain_blend(int32_t s, int32_t g, int bit_depth, int blending);
 
+/* Colour remapping: n finished 4:4:4 pictures become n finished 4:4:4 pictures of the same size, every output sample made from all
+ * three components of the source sample, as the colour remapping information SEI (ohevc_annexb.h: oh_sei_colour_remap) prescribes: a
+ * table per component, a 3 x 3 matrix, a second table per component (the tests check every coded plane bit for bit
+ * against tests/remap_model.py).  Everything is in integers.  bi / bo: the input / output bit depth, each 8, 9, 10 or 12;
+ * Mi = 2^bi - 1, Mo = 2^bo - 1.  Sample (s0, s1, s2): p_i = pre[i][s_i]; m_c = clip(0, Mo, (sum_i coeff[c][i] p_i + r) >> d) with
+ * d = log2_denom, r = 2^(d - 1) for d > 0 and 0 for d = 0, the shift arithmetic; out_c = post[c][m_c].  A source sample above Mi, which
+ * no decoder and no service writes, is looked up by its low bits.  Sources are of in_bit_depth, destinations of out_bit_depth, over the
+ * whole coded planes.  Reads finished halves, writes half 0 of each destination and marks it finished, like oh_pics_lut; enqueued on the
+ * engine stream, returns without waiting.  The tables are copied by the call: the host arrays may be freed on return.  n == 0: OH_OK
+ * after the checks that need no picture (the struct's).  More than OH_CONV_MAX_PICS pictures are split into several launches.
+ * OH_E_ARG, nothing written: a null e, r or id array, a negative n; an unknown picture; params that differ among the sources or among
+ * the destinations; a destination that is also a source, or listed twice; sizes that differ; a picture depth other than the struct's; a
+ * struct depth outside 8, 9, 10, 12; a null table; a table entry above Mo; a coefficient outside -32768 .. 32767; log2_denom outside
+ * 0 .. 15.  OH_E_UNSUPPORTED: a chroma format other than 4:4:4 on either side (oh_pics_reformat first, or oh_remap_luts with oh_pics_lut
+ * where the matrix is diagonal). */
+typedef struct OhRemap {
+    int32_t in_bit_depth, out_bit_depth;
+    const uint16_t *pre[3];       /* HOST, 2^in entries, values 0 .. Mo  */
+    int32_t coeff[3][3], log2_denom;
+    const uint16_t *post[3];      /* HOST, 2^out entries, values 0 .. Mo */
+} OhRemap;
+int oh_pics_colour_remap(OhEngine *e, const int *src_ids, const int *dst_ids, int n, const OhRemap *r);
+/* host only: the pieces of the definition above, which the kernel shares (csrc/remap_common.h).
+ *   oh_remap_curve     the piecewise-linear table of 2^bi_ entries from bi_ to bo_ bits (each 8, 9, 10 or 12, passed independently: a
+ *                      post curve is bo -> bo) through n pivots (coded[k], target[k]).  n = 0: the points (0, 0), (Mi_, Mo_).  Otherwise
+ *                      the n given points (n <= 33), a point (0, 0) in front where coded[0] > 0 and a point (Mi_, Mo_) behind where the
+ *                      last coded value is below Mi_.  For v in x_k .. x_k+1, dx = x_k+1 - x_k, t = v - x_k:
+ *                      out[v] = (y_k (dx - t) + y_k+1 t + (dx >> 1)) / dx.  Targets need not be monotonic.  OH_E_ARG, out untouched: a
+ *                      null pointer (coded and target may be null where n is 0), another depth, n outside 0 .. 33, coded values not
+ *                      strictly increasing, a coded value above Mi_, a target above Mo_
+ *   oh_remap_sample    out[3] of the sample s[3]; 1, or 0 for a null pointer or an OhRemap that oh_pics_colour_remap would refuse
+ *   oh_remap_from_sei  the six curves of a message in tables (0 .. 2 pre, 3 .. 5 post; num_val_minus1 of 0 is a curve without pivots),
+ *                      its matrix (absent: the identity with log2_denom 0), out pointing into tables.  The signal info describes the
+ *                      result and changes no sample: it is passed over.  OH_E_ARG: a null pointer, a message that is absent (present 0)
+ *                      or cancelled, what oh_remap_curve refuses.  OH_E_UNSUPPORTED: a depth outside 8, 9, 10, 12.  tables and out are
+ *                      untouched then
+ *   oh_remap_luts      where every off-diagonal coefficient is 0 the remap is a function of each plane alone:
+ *                      out[c][v] = post[c][clip(0, Mo, (coeff[c][c] pre[c][v] + r) >> d)] for v < 2^bi, tables for oh_pics_lut, which
+ *                      works at any chroma format.  OH_E_ARG: a null pointer or an OhRemap that oh_pics_colour_remap would refuse;
+ *                      OH_E_UNSUPPORTED: any other matrix; out is untouched then */
+int oh_remap_curve(int in_bit_depth, int out_bit_depth, int n, const uint16_t *coded, const uint16_t *target, uint16_t *out);
+int oh_remap_sample(const OhRemap *r, const uint16_t s[3], uint16_t out[3]);
+struct OhColourRemapSei;
+int oh_remap_from_sei(const struct OhColourRemapSei *sei, uint16_t tables[6][4096], OhRemap *out);
+int oh_remap_luts(const OhRemap *r, uint16_t out[3][4096]);
+
 /* Motion: a block-matching search between two finished pictures and the motion-compensated prediction that such a field describes, in
  * HEVC's quarter-sample units with HEVC's interpolation filters, so that a vector means what it means to an HEVC decoder (DESIGN.md
  * §3o; the tests check every field and every plane bit for bit against tests/motion_model.py, which is held against the oracle's

@@ -1,4 +1,4 @@
-"""ctypes view of include/ohevc_annexb.h (libohevc_host.so): access-unit splitter, NAL scan, NAL unescape, picture-hash SEI, HDR SEIs, display-orientation SEI, picture timing SEI, film grain SEI."""
+"""ctypes view of include/ohevc_annexb.h (libohevc_host.so): access-unit splitter, NAL scan, NAL unescape, picture-hash SEI, HDR SEIs, display-orientation SEI, picture timing SEI, film grain SEI, colour remapping SEI."""
 import ctypes as C
 import os
 
@@ -47,6 +47,20 @@ class OhFilmGrainSei(C.Structure):
                 ("value", ((C.c_int32 * FG_MAX_VALUES) * FG_MAX_INTERVALS) * 3)]
 
 
+CRI_MAX_PIVOTS = 33                                            # OH_CRI_MAX_PIVOTS
+
+
+class OhColourRemapSei(C.Structure):
+    _fields_ = [("present", C.c_int32), ("cancel", C.c_int32), ("id", C.c_uint32), ("persistence", C.c_int32),
+                ("video_signal_info_present", C.c_int32), ("full_range", C.c_int32), ("primaries", C.c_int32),
+                ("transfer_function", C.c_int32), ("matrix_coefficients", C.c_int32),
+                ("input_bit_depth", C.c_int32), ("output_bit_depth", C.c_int32), ("pre_lut_num_val_minus1", C.c_int32 * 3),
+                ("pre_lut_coded_value", (C.c_uint16 * CRI_MAX_PIVOTS) * 3), ("pre_lut_target_value", (C.c_uint16 * CRI_MAX_PIVOTS) * 3),
+                ("matrix_present", C.c_int32), ("log2_matrix_denom", C.c_int32), ("coeffs", (C.c_int32 * 3) * 3),
+                ("post_lut_num_val_minus1", C.c_int32 * 3),
+                ("post_lut_coded_value", (C.c_uint16 * CRI_MAX_PIVOTS) * 3), ("post_lut_target_value", (C.c_uint16 * CRI_MAX_PIVOTS) * 3)]
+
+
 _lib = None
 
 
@@ -77,6 +91,8 @@ def lib():
         L.oh_sei_pic_timing.restype = C.c_int
         L.oh_sei_film_grain.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(OhFilmGrainSei)]
         L.oh_sei_film_grain.restype = C.c_int
+        L.oh_sei_colour_remap.argtypes = [C.c_char_p, C.c_size_t, C.c_int64, C.POINTER(OhColourRemapSei)]
+        L.oh_sei_colour_remap.restype = C.c_int
         _lib = L
     return _lib
 
@@ -259,3 +275,78 @@ def film_grain_to_struct(d):
             for j, v in enumerate(vals):
                 g.value[c][i][j] = int(v)
     return g
+
+
+def colour_remap_struct(nal, id=None):
+    """None, or the OhColourRemapSei of the colour remapping information message (payload type 142) of one prefix SEI NAL unit: the
+    last one of the unit, or with id the last one whose colour_remap_id is id"""
+    r = OhColourRemapSei()
+    rc = lib().oh_sei_colour_remap(nal, len(nal), -1 if id is None else int(id), C.byref(r))
+    if rc < 0:
+        raise ValueError("malformed SEI NAL unit")
+    return r if rc else None
+
+
+def colour_remap(nal, id=None):
+    """None, or a dict of the colour remapping information message (payload type 142) of one prefix SEI NAL unit
+    (oh_sei_colour_remap), every field as coded: "id", "cancel" (bool; a cancelled message holds nothing else), "persistence" (bool),
+    "signal" (None, or a dict of "full_range", "primaries", "transfer_function", "matrix_coefficients"), "input_bit_depth",
+    "output_bit_depth", "pre" and "post": three lists of (coded, target) pivots, empty where num_val_minus1 is 0, and "matrix": None, or
+    (log2_matrix_denom, three rows of three coefficients).  id: None takes the last message of the unit, a number the last one with that
+    colour_remap_id.  engine.remap_from_sei turns the dict into what Engine.pics_colour_remap takes."""
+    r = colour_remap_struct(nal, id)
+    if r is None:
+        return None
+    if r.cancel:
+        return dict(id=int(r.id), cancel=True)
+    signal = None
+    if r.video_signal_info_present:
+        signal = dict(full_range=bool(r.full_range), primaries=int(r.primaries), transfer_function=int(r.transfer_function),
+                      matrix_coefficients=int(r.matrix_coefficients))
+
+    def pivots(nm1, coded, target):
+        return [[(int(coded[c][i]), int(target[c][i])) for i in range(nm1[c] + 1 if nm1[c] else 0)] for c in range(3)]
+
+    matrix = (int(r.log2_matrix_denom), [[int(r.coeffs[c][i]) for i in range(3)] for c in range(3)]) if r.matrix_present else None
+    return dict(id=int(r.id), cancel=False, persistence=bool(r.persistence), signal=signal, input_bit_depth=int(r.input_bit_depth),
+                output_bit_depth=int(r.output_bit_depth), pre=pivots(r.pre_lut_num_val_minus1, r.pre_lut_coded_value, r.pre_lut_target_value),
+                matrix=matrix, post=pivots(r.post_lut_num_val_minus1, r.post_lut_coded_value, r.post_lut_target_value))
+
+
+def colour_remap_to_struct(d):
+    """the OhColourRemapSei that colour_remap would have read the dict d from"""
+    r = OhColourRemapSei()
+    r.present, r.id = 1, int(d.get("id", 0))
+    if d.get("cancel"):
+        r.cancel = 1
+        return r
+    r.persistence = int(bool(d.get("persistence", False)))
+    signal = d.get("signal")
+    if signal:
+        r.video_signal_info_present = 1
+        r.full_range = int(bool(signal["full_range"]))
+        r.primaries, r.transfer_function = int(signal["primaries"]), int(signal["transfer_function"])
+        r.matrix_coefficients = int(signal["matrix_coefficients"])
+    r.input_bit_depth, r.output_bit_depth = int(d["input_bit_depth"]), int(d["output_bit_depth"])
+    for key, nm1, coded, target in (("pre", r.pre_lut_num_val_minus1, r.pre_lut_coded_value, r.pre_lut_target_value),
+                                    ("post", r.post_lut_num_val_minus1, r.post_lut_coded_value, r.post_lut_target_value)):
+        curves = list(d.get(key) or ((), (), ()))
+        if len(curves) != 3:
+            raise ValueError(f"colour remap: {key} has three curves")
+        for c, pv in enumerate(curves):
+            pv = list(pv)
+            if len(pv) == 1 or len(pv) > CRI_MAX_PIVOTS:
+                raise ValueError(f"colour remap: {key}[{c}] has {len(pv)} pivots (none, or 2 .. {CRI_MAX_PIVOTS}: num_val_minus1 of 0 codes none)")
+            nm1[c] = max(len(pv) - 1, 0)
+            for i, (x, y) in enumerate(pv):
+                if not (0 <= int(x) <= 0xFFFF and 0 <= int(y) <= 0xFFFF):
+                    raise ValueError("colour remap: a pivot is two values of 16 bits")
+                coded[c][i], target[c][i] = int(x), int(y)
+    matrix = d.get("matrix")
+    if matrix is not None:
+        r.matrix_present = 1
+        r.log2_matrix_denom = int(matrix[0])
+        for c in range(3):
+            for i in range(3):
+                r.coeffs[c][i] = int(matrix[1][c][i])
+    return r

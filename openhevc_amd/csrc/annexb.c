@@ -1,5 +1,5 @@
 /*
- * annexb.c — Annex-B byte stream: access-unit splitter, NAL scan, NAL unescape, picture-hash SEI, HDR SEIs, display-orientation, picture timing and film grain SEIs.  See include/ohevc_annexb.h for the
+ * annexb.c — Annex-B byte stream: access-unit splitter, NAL scan, NAL unescape, picture-hash SEI, HDR SEIs, display-orientation, picture timing, film grain and colour remapping SEIs.  See include/ohevc_annexb.h for the
  * reference lines each entry point follows.  Plain C, no dependencies.
  */
 #include "../../include/ohevc_annexb.h"
@@ -398,6 +398,98 @@ int oh_sei_film_grain(const uint8_t *nal, size_t size, OhFilmGrainSei *out)
 {
     memset(out, 0, sizeof(*out));
     if (sei_walk(nal, size, grain_msg, out) < 0) {
+        memset(out, 0, sizeof(*out));
+        return -1;
+    }
+    return out->present;
+}
+
+/* ue(v) of H.265 9.2: codeNum 2^z - 1 + the z bits behind the z leading zeros and the one */
+static uint32_t get_ue(struct bit_reader *b)
+{
+    int z = 0;
+    while (!b->bad && !get_bits(b, 1))
+        if (++z > 32)
+            b->bad = 1;
+    if (b->bad)
+        return 0;
+    const uint64_t k = (((uint64_t)1 << z) - 1) + get_bits(b, z);
+    if (b->bad || k > UINT32_MAX) {
+        b->bad = 1;
+        return 0;
+    }
+    return (uint32_t)k;
+}
+
+/* num_val_minus1 and, where it is above 0, the pivots of one curve of the colour remapping message: coded values of vc bits, target
+ * values of vt bits */
+static void remap_curve_fields(struct bit_reader *b, int vc, int vt, int32_t *num_val_minus1, uint16_t *coded, uint16_t *target)
+{
+    *num_val_minus1 = (int32_t)get_bits(b, 8);
+    if (*num_val_minus1 >= OH_CRI_MAX_PIVOTS) {
+        b->bad = 1;
+        return;
+    }
+    if (*num_val_minus1 > 0)
+        for (int i = 0; i <= *num_val_minus1 && !b->bad; i++) {
+            coded[i] = (uint16_t)get_bits(b, vc);
+            target[i] = (uint16_t)get_bits(b, vt);
+        }
+}
+
+struct remap_ctx { OhColourRemapSei *out; int64_t id; };
+
+static int remap_msg(void *ctx, int nut, unsigned type, const uint8_t *q, unsigned len)
+{
+    struct remap_ctx *r = (struct remap_ctx *)ctx;
+    if (nut != NAL_SEI_PREFIX || type != 142)                 /* D.2.33 colour_remapping_info */
+        return 0;
+    struct bit_reader b = { q, (size_t)len * 8, 0, 0 };
+    OhColourRemapSei m;
+    memset(&m, 0, sizeof(m));
+    m.present = 1;
+    m.id = get_ue(&b);
+    m.cancel = (int32_t)get_bits(&b, 1);
+    if (b.bad)
+        return -1;
+    if (!m.cancel) {
+        m.persistence = (int32_t)get_bits(&b, 1);
+        m.video_signal_info_present = (int32_t)get_bits(&b, 1);
+        if (m.video_signal_info_present) {
+            m.full_range = (int32_t)get_bits(&b, 1);
+            m.primaries = (int32_t)get_bits(&b, 8);
+            m.transfer_function = (int32_t)get_bits(&b, 8);
+            m.matrix_coefficients = (int32_t)get_bits(&b, 8);
+        }
+        m.input_bit_depth = (int32_t)get_bits(&b, 8);
+        m.output_bit_depth = (int32_t)get_bits(&b, 8);
+        if (b.bad || m.input_bit_depth < 8 || m.input_bit_depth > 16 || m.output_bit_depth < 8 || m.output_bit_depth > 16)
+            return -1;
+        const int vi = ((m.input_bit_depth + 7) >> 3) << 3, vo = ((m.output_bit_depth + 7) >> 3) << 3;
+        for (int c = 0; c < 3 && !b.bad; c++)
+            remap_curve_fields(&b, vi, vo, &m.pre_lut_num_val_minus1[c], m.pre_lut_coded_value[c], m.pre_lut_target_value[c]);
+        m.matrix_present = (int32_t)get_bits(&b, 1);
+        if (m.matrix_present) {
+            m.log2_matrix_denom = (int32_t)get_bits(&b, 4);
+            for (int c = 0; c < 3; c++)
+                for (int i = 0; i < 3; i++)
+                    m.coeffs[c][i] = get_se(&b);
+        }
+        for (int c = 0; c < 3 && !b.bad; c++)
+            remap_curve_fields(&b, vo, vo, &m.post_lut_num_val_minus1[c], m.post_lut_coded_value[c], m.post_lut_target_value[c]);
+        if (b.bad)
+            return -1;
+    }
+    if (r->id < 0 || (int64_t)m.id == r->id)                  /* the last one that is asked for counts */
+        *r->out = m;
+    return 0;
+}
+
+int oh_sei_colour_remap(const uint8_t *nal, size_t size, int64_t id, OhColourRemapSei *out)
+{
+    struct remap_ctx r = { out, id };
+    memset(out, 0, sizeof(*out));
+    if (sei_walk(nal, size, remap_msg, &r) < 0) {
         memset(out, 0, sizeof(*out));
         return -1;
     }

@@ -185,7 +185,7 @@ extern "C" void oh_engine_destroy(OhEngine *e)
     if (e->kerr) (void)hipHostFree(e->kerr);
     if (e->tickets) (void)hipFree(e->tickets);
     for (const OhEngine::Scratch *s : { &e->hash_dev, &e->resize_dev, &e->colour_tabs.dev, &e->light_tabs.dev, &e->light_res, &e->compare_res,
-                                        &e->compose_dev, &e->hist_res, &e->lut_tabs, &e->grain_tabs, &e->grain_patterns, &e->motion_res, &e->motion_centres, &e->motion_field })
+                                        &e->compose_dev, &e->hist_res, &e->lut_tabs, &e->grain_tabs, &e->grain_patterns, &e->remap_tabs, &e->motion_res, &e->motion_centres, &e->motion_field })
         if (s->p) (void)hipFree(s->p);
     for (auto &ev : e->batch_ev) if (ev) (void)hipEventDestroy(ev);
     if (e->dl_stream) { (void)hipStreamSynchronize(e->dl_stream); (void)hipStreamDestroy(e->dl_stream); }

@@ -170,6 +170,8 @@ struct OhEngine {
     Scratch     grain_tabs;              /* oh_pics_grain: the three tables (3 x OH_GRAIN_ENTRIES uint32) and the seeds of the last call, likewise */
     Scratch     grain_patterns;          /* oh_pics_grain: the 169 patterns, built and copied by the engine's first call, then only read */
     bool        grain_patterns_ready = false;
+    Scratch     remap_tabs;              /* oh_pics_colour_remap: the six tables of the last call (6 x OH_LUT_MAX uint16), rewritten on the
+                                          * stream behind the launches that read them */
     Scratch     motion_res;              /* oh_pics_motion: the vectors of the call in HBM */
     Scratch     motion_centres;          /* oh_pics_motion: the centres of the call, rewritten on the stream behind the launches that read them */
     Scratch     motion_field;            /* oh_pics_motion_compensate: the vectors of the call, likewise */

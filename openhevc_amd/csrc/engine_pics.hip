@@ -1570,6 +1570,56 @@ extern "C" int oh_pics_grain(OhEngine *e, const int *src_ids, const int *dst_ids
     });
 }
 
+/* ---------------- colour remapping (remap.hip) ---------------- */
+extern "C" int oh_pics_colour_remap(OhEngine *e, const int *src_ids, const int *dst_ids, int n, const OhRemap *r)
+{
+    const char *who = "oh_pics_colour_remap";
+    if (!e || n < 0 || !r || (n && (!src_ids || !dst_ids)))
+        return OH_E_ARG;
+    std::string why;
+    if (remap_check(r, &why))                                   /* depths, matrix and tables: also of a call without pictures */
+        return refuse(e, OH_E_ARG, who, why);
+    if (!n)
+        return OH_OK;
+    const Pic *s0, *d0;
+    OH_TRY(srcs_dsts(e, who, src_ids, n, dst_ids, n, &s0, &d0));
+    const OhPicParams &sp = s0->p, &dp = d0->p;
+    if (sp.width != dp.width || sp.height != dp.height)
+        FAIL(e, OH_E_ARG, "%s: sources of %dx%d, destinations of %dx%d", who, sp.width, sp.height, dp.width, dp.height);
+    if (sp.bit_depth != r->in_bit_depth || dp.bit_depth != r->out_bit_depth)
+        FAIL(e, OH_E_ARG, "%s: sources of %d bit, destinations of %d bit; the remap is from %d to %d bit", who, sp.bit_depth, dp.bit_depth,
+             r->in_bit_depth, r->out_bit_depth);
+    if (sp.chroma_format_idc != 3 || dp.chroma_format_idc != 3)
+        FAIL(e, OH_E_UNSUPPORTED, "%s: sources of chroma format %d, destinations of chroma format %d; only 4:4:4 "
+             "(oh_pics_reformat first, or oh_remap_luts with oh_pics_lut where the matrix is diagonal)", who, sp.chroma_format_idc, dp.chroma_format_idc);
+    /* the tables of the call; the device copy has its full size from the first call on */
+    const size_t tab_bytes = (size_t)6 * OH_LUT_MAX * sizeof(uint16_t);
+    OH_TRY(upload(e, who, "tables", &e->remap_tabs, tab_bytes, [&](void *h) {
+        memset(h, 0, tab_bytes);
+        for (int c = 0; c < 3; c++) {
+            memcpy((uint16_t *)h + (size_t)c * OH_LUT_MAX, r->pre[c], sizeof(uint16_t) << r->in_bit_depth);
+            memcpy((uint16_t *)h + (size_t)(3 + c) * OH_LUT_MAX, r->post[c], sizeof(uint16_t) << r->out_bit_depth);
+        }
+    }));
+    OhRemapArgs a;
+    memset(&a, 0, sizeof(a));
+    row_pitches(s0, 3, a.spitch); row_pitches(d0, 3, a.dpitch);
+    a.w = s0->w[0]; a.h = s0->h[0];
+    a.sbd = sp.bit_depth; a.dbd = dp.bit_depth;
+    memcpy(a.coeff, r->coeff, sizeof(a.coeff));
+    a.log2_denom = r->log2_denom;
+    a.identity = remap_is_identity(r);
+    a.rows = OH_REMAP_ROWS;
+    a.tab = (const uint16_t *)e->remap_tabs.p;
+    return launch_sets(e, n, [&](int i0, int m) {
+        for (int i = 0; i < m; i++) {
+            read_planes(get_pic(e, src_ids[i0 + i]), 3, a.src[i]);
+            write_planes(get_pic(e, dst_ids[i0 + i]), 3, a.dst[i]);
+        }
+        ohk_remap(&a, m, e->stream);
+    });
+}
+
 /* ---------------- motion search and compensation (motion.hip) ---------------- */
 extern "C" int oh_pics_motion(OhEngine *e, const int *cur_ids, const int *ref_ids, int n, const OhMotionSearch *ms, OhMotionVector *out)
 {

@@ -278,6 +278,23 @@ struct OhGrainArgs {
     int32_t         planes, blending, log2_scale;   /* OhGrain */
 };
 
+/* colour remapping (remap.hip): the finished planes of the sources and half 0 of the destinations of one launch by value
+ * in the kernel arguments; every picture is 4:4:4, the sources alike and the destinations alike.  The six tables (pre 0 .. 2, post
+ * 0 .. 2) are OH_LUT_MAX uint16 each in device memory that the engine owns and fills on the stream in front of the launch. */
+enum { OH_REMAP_ROWS = 8 };          /* picture rows per workgroup: it loads the six tables once for all of them.  Coded heights are
+                                      * multiples of the minimum coding block of 8, so no band is ever cut; measured against 4, 16, 32, 64 */
+struct OhRemapArgs {
+    const void     *src[64][3];      /* OH_CONV_MAX_PICS pictures x planes: the finished halves */
+    void           *dst[64][3];      /* half 0 of the destinations */
+    const uint16_t *tab;             /* [6][OH_LUT_MAX] */
+    int32_t         spitch[3], dpitch[3];   /* bytes between rows of each plane */
+    int32_t         w, h;            /* coded size of every plane */
+    int32_t         sbd, dbd;        /* bit depth of sources and destinations */
+    int32_t         coeff[9], log2_denom;   /* OhRemap: the matrix, row-major */
+    int32_t         identity;        /* the matrix leaves the pre-table values as they are */
+    int32_t         rows;            /* picture rows per workgroup */
+};
+
 /* motion search and compensation (motion.hip): the finished planes of the pictures of one launch by value in the kernel
  * arguments; every picture of a launch has the same geometry.  The centres, the field and the results of the launch's first picture lie
  * in device memory that the engine owns and fills or clears on the stream in front of the launch. */
@@ -374,6 +391,8 @@ void ohk_histogram(const OhHistArgs *a, int n, hipStream_t st);
 void ohk_lut(const OhLutArgs *a, int n, hipStream_t st);
 /* n sources of a.src with grain added into the n destinations of a.dst */
 void ohk_grain(const OhGrainArgs *a, int n, hipStream_t st);
+/* n sources of a.src remapped into the n destinations of a.dst */
+void ohk_remap(const OhRemapArgs *a, int n, hipStream_t st);
 /* the blocks of n pairs of a.cur / a.ref searched into a.res[0 .. n bw bh) */
 void ohk_motion_search(const OhMoSearchArgs *a, int n, hipStream_t st);
 /* n pictures of a.ref compensated by a.field[0 .. n bw bh) into the n destinations of a.dst */

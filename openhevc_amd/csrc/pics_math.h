@@ -29,5 +29,7 @@ OH_INTERNAL int warp_check(const OhWarp *w, int bit_depth, std::string *why);
 OH_INTERNAL int warp_image_check(const OhWarp *w, std::string *why);
 OH_INTERNAL int lut_check(const OhLut *lut, int sbd, int dbd, int np, std::string *why);
 OH_INTERNAL int grain_check(const OhGrain *g, int np, std::string *why);
+OH_INTERNAL int remap_check(const OhRemap *r, std::string *why);
+OH_INTERNAL bool remap_is_identity(const OhRemap *r);
 
 #endif

@@ -1,7 +1,7 @@
 /*
  * pics_math.hip — the host arithmetic of the picture services (engine_pics.hip), with neither an engine nor a device: image sizes and
  * crop windows, the ids of a call (destinations apart from sources, neighbours in time), the integers of the RGB conversions, the colour tables of the HDR forms, light-level bins and percentiles, the SSIM window
- * and PSNR, the resize taps, the compose formulas, the reformat quantisation, the orientations' group, the pic_struct table, the adaptive deinterlacer's sample, the filters' taps and samples, and what follows from a histogram's bins with the table builders, the motion helpers, the warp's positions, taps and map builders, and the film grain's hash, patterns, tables and samples.  No kernel, no HIP runtime call: tests/pics_math_check.cpp runs it under sanitizers.
+ * and PSNR, the resize taps, the compose formulas, the reformat quantisation, the orientations' group, the pic_struct table, the adaptive deinterlacer's sample, the filters' taps and samples, and what follows from a histogram's bins with the table builders, the motion helpers, the warp's positions, taps and map builders, the film grain's hash, patterns, tables and samples, and the colour remapping's curves, samples and per-plane tables.  No kernel, no HIP runtime call: tests/pics_math_check.cpp runs it under sanitizers.
  */
 #include <stdio.h>
 #include <string.h>
@@ -19,6 +19,7 @@
 #include "motion_common.h"
 #include "warp_common.h"
 #include "grain_common.h"
+#include "remap_common.h"
 #include "../../include/ohevc_annexb.h"
 
 static bool depth_ok(int bit_depth) { return bit_depth == 8 || bit_depth == 9 || bit_depth == 10 || bit_depth == 12; }
@@ -1419,6 +1420,133 @@ int grain_check(const OhGrain *g, int np, std::string *why)
             if (t >> 16 || ((t & 255) && (!cut_ok((int)(t >> 8 & 15)) || !cut_ok((int)(t >> 12 & 15))))) {
                 snprintf(buf, sizeof(buf), "table[%d][%d] = 0x%x: sigma | fh << 8 | fv << 12 with cut-offs 2 .. 14", c, a, t); *why = buf; return OH_E_ARG;
             }
+        }
+    }
+    return OH_OK;
+}
+
+/* ---------------- colour remapping (remap.hip): the host-only helpers and what oh_pics_colour_remap checks ---------------- */
+extern "C" int oh_remap_curve(int in_bit_depth, int out_bit_depth, int n, const uint16_t *coded, const uint16_t *target, uint16_t *out)
+{
+    if (!out || !depth_ok(in_bit_depth) || !depth_ok(out_bit_depth) || n < 0 || n > 33 || (n && (!coded || !target)))
+        return OH_E_ARG;
+    const int32_t Mi = (1 << in_bit_depth) - 1, Mo = (1 << out_bit_depth) - 1;
+    int32_t x[35], y[35];
+    int np = 0;
+    if (!n || coded[0] > 0) { x[np] = 0; y[np++] = 0; }
+    for (int k = 0; k < n; k++) {
+        if (coded[k] > Mi || target[k] > Mo || (k && coded[k] <= coded[k - 1]))
+            return OH_E_ARG;
+        x[np] = coded[k]; y[np++] = target[k];
+    }
+    if (x[np - 1] < Mi) { x[np] = Mi; y[np++] = Mo; }
+    out[x[0]] = (uint16_t)y[0];
+    for (int k = 0; k + 1 < np; k++) {
+        const int32_t dx = x[k + 1] - x[k];                     /* y (dx - t) + y' t + dx / 2 <= 4095 * 4095 + 2047 */
+        for (int32_t t = 1; t <= dx; t++)
+            out[x[k] + t] = (uint16_t)((y[k] * (dx - t) + y[k + 1] * t + (dx >> 1)) / dx);
+    }
+    return OH_OK;
+}
+
+/* what oh_pics_colour_remap checks of the OhRemap itself */
+int remap_check(const OhRemap *r, std::string *why)
+{
+    char buf[256];
+    if (!depth_ok(r->in_bit_depth) || !depth_ok(r->out_bit_depth)) {
+        snprintf(buf, sizeof(buf), "bit depths %d -> %d: each 8, 9, 10 or 12", r->in_bit_depth, r->out_bit_depth); *why = buf; return OH_E_ARG;
+    }
+    if (r->log2_denom < 0 || r->log2_denom > REMAP_DENOM_MAX) {
+        snprintf(buf, sizeof(buf), "log2_denom %d outside 0 .. %d", r->log2_denom, REMAP_DENOM_MAX); *why = buf; return OH_E_ARG;
+    }
+    for (int c = 0; c < 3; c++)
+        for (int i = 0; i < 3; i++)
+            if (r->coeff[c][i] < REMAP_COEFF_MIN || r->coeff[c][i] > REMAP_COEFF_MAX) {
+                snprintf(buf, sizeof(buf), "coeff[%d][%d] = %d outside %d .. %d", c, i, r->coeff[c][i], REMAP_COEFF_MIN, REMAP_COEFF_MAX);
+                *why = buf; return OH_E_ARG;
+            }
+    for (int k = 0; k < 6; k++) {
+        const uint16_t *t = k < 3 ? r->pre[k] : r->post[k - 3];
+        const int entries = 1 << (k < 3 ? r->in_bit_depth : r->out_bit_depth);
+        if (!t) { snprintf(buf, sizeof(buf), "no %s table for component %d", k < 3 ? "pre" : "post", k % 3); *why = buf; return OH_E_ARG; }
+        uint32_t top = 0;
+        for (int v = 0; v < entries; v++)
+            top = std::max<uint32_t>(top, t[v]);
+        if (top >> r->out_bit_depth) {
+            snprintf(buf, sizeof(buf), "%s[%d] holds %u, which does not fit %d bits", k < 3 ? "pre" : "post", k % 3, top, r->out_bit_depth);
+            *why = buf; return OH_E_ARG;
+        }
+    }
+    return OH_OK;
+}
+
+/* the matrix leaves the pre-table values as they are */
+bool remap_is_identity(const OhRemap *r)
+{
+    for (int c = 0; c < 3; c++)
+        for (int i = 0; i < 3; i++)
+            if (r->coeff[c][i] != (c == i ? 1 << r->log2_denom : 0))
+                return false;
+    return true;
+}
+
+extern "C" int oh_remap_sample(const OhRemap *r, const uint16_t s[3], uint16_t out[3])
+{
+    std::string why;
+    if (!r || !s || !out || remap_check(r, &why))
+        return 0;
+    const uint32_t in[3] = { s[0], s[1], s[2] };
+    uint32_t o[3];
+    remap_sample<false>(r->pre[0], r->pre[1], r->pre[2], r->post[0], r->post[1], r->post[2], &r->coeff[0][0], r->log2_denom,
+                        (1u << r->in_bit_depth) - 1, (1 << r->out_bit_depth) - 1, in, o);
+    for (int c = 0; c < 3; c++)
+        out[c] = (uint16_t)o[c];
+    return 1;
+}
+
+extern "C" int oh_remap_from_sei(const OhColourRemapSei *sei, uint16_t tables[6][4096], OhRemap *out)
+{
+    if (!sei || !tables || !out || !sei->present || sei->cancel)
+        return OH_E_ARG;
+    const int bi = sei->input_bit_depth, bo = sei->output_bit_depth;
+    if (!depth_ok(bi) || !depth_ok(bo))
+        return OH_E_UNSUPPORTED;
+    std::vector<uint16_t> t((size_t)6 * 4096, 0);
+    for (int c = 0; c < 3; c++) {
+        const int npre = sei->pre_lut_num_val_minus1[c], npost = sei->post_lut_num_val_minus1[c];
+        if (npre < 0 || npre >= OH_CRI_MAX_PIVOTS || npost < 0 || npost >= OH_CRI_MAX_PIVOTS)
+            return OH_E_ARG;
+        if (oh_remap_curve(bi, bo, npre ? npre + 1 : 0, sei->pre_lut_coded_value[c], sei->pre_lut_target_value[c], &t[(size_t)c * 4096]) ||
+            oh_remap_curve(bo, bo, npost ? npost + 1 : 0, sei->post_lut_coded_value[c], sei->post_lut_target_value[c], &t[(size_t)(3 + c) * 4096]))
+            return OH_E_ARG;
+    }
+    memcpy(tables, t.data(), t.size() * sizeof(uint16_t));
+    out->in_bit_depth = bi; out->out_bit_depth = bo;
+    out->log2_denom = sei->matrix_present ? sei->log2_matrix_denom : 0;
+    for (int c = 0; c < 3; c++) {
+        for (int i = 0; i < 3; i++)
+            out->coeff[c][i] = sei->matrix_present ? sei->coeffs[c][i] : c == i;
+        out->pre[c] = tables[c]; out->post[c] = tables[3 + c];
+    }
+    return OH_OK;
+}
+
+extern "C" int oh_remap_luts(const OhRemap *r, uint16_t out[3][4096])
+{
+    std::string why;
+    if (!r || !out || remap_check(r, &why))
+        return OH_E_ARG;
+    for (int c = 0; c < 3; c++)
+        for (int i = 0; i < 3; i++)
+            if (c != i && r->coeff[c][i])
+                return OH_E_UNSUPPORTED;
+    const int32_t Mo = (1 << r->out_bit_depth) - 1;
+    for (int c = 0; c < 3; c++) {
+        int32_t k[3] = { 0, 0, 0 };
+        k[c] = r->coeff[c][c];
+        for (int v = 0; v < 1 << r->in_bit_depth; v++) {
+            const int32_t p = r->pre[c][v];
+            out[c][v] = r->post[c][remap_row(k, p, p, p, r->log2_denom, Mo)];
         }
     }
     return OH_OK;

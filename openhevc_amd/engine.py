@@ -835,6 +835,120 @@ def grain_seeds(seeds, n):
     return np.array([(int(seeds) + i) & 0xFFFFFFFF for i in range(n)], dtype=np.uint32)
 
 
+class OhRemap(C.Structure):                                   # include/ohevc_hip.h
+    _fields_ = [("in_bit_depth", C.c_int32), ("out_bit_depth", C.c_int32), ("pre", C.POINTER(C.c_uint16) * 3),
+                ("coeff", (C.c_int32 * 3) * 3), ("log2_denom", C.c_int32), ("post", C.POINTER(C.c_uint16) * 3)]
+
+
+REMAP_MAX_PIVOTS = 33                                                                   # OH_CRI_MAX_PIVOTS
+REMAP_ROWS = 8                                                                          # OH_REMAP_ROWS: a workgroup's band of rows
+
+
+def _remap_tables(what, tables, bit_depth):
+    t = np.asarray(tables)
+    entries = 1 << bit_depth if 0 <= bit_depth <= 16 else -1
+    if t.shape != (3, entries) or t.dtype.kind not in "iu" or (t.size and (t.min() < 0 or t.max() > 0xFFFF)):
+        raise ValueError(f"remap: {what} tables of shape {t.shape}, not (3, {entries}) entries of 16 bits")
+    return np.ascontiguousarray(t, dtype=np.uint16)
+
+
+class Remap:
+    """what Engine.pics_colour_remap applies (OhRemap): pre, a numpy uint16 array (3, 2^in_bit_depth) of values 0 .. 2^out_bit_depth - 1;
+    coeff, a numpy int32 array (3, 3) with log2_denom, its denominator's logarithm; post, a numpy uint16 array (3, 2^out_bit_depth)"""
+    __slots__ = ("pre", "coeff", "log2_denom", "post", "in_bit_depth", "out_bit_depth")
+
+    def __init__(self, pre, coeff, log2_denom, post, in_bit_depth, out_bit_depth=None):
+        self.in_bit_depth = int(in_bit_depth)
+        self.out_bit_depth = self.in_bit_depth if out_bit_depth is None else int(out_bit_depth)
+        self.pre = _remap_tables("pre", pre, self.in_bit_depth)
+        self.post = _remap_tables("post", post, self.out_bit_depth)
+        k = np.asarray(coeff)
+        if k.shape != (3, 3) or k.dtype.kind not in "iu" or abs(k).max() > 0x7FFFFFFF:
+            raise ValueError(f"remap: coeff of shape {k.shape}, not (3, 3) integers of 32 bits")
+        self.coeff = np.ascontiguousarray(k, dtype=np.int32)
+        self.log2_denom = int(log2_denom)
+
+    def __repr__(self):
+        return f"Remap({self.in_bit_depth} -> {self.out_bit_depth} bit, coeff={self.coeff.tolist()}, log2_denom={self.log2_denom})"
+
+    def as_struct(self):
+        """the OhRemap; it points into self.pre and self.post, which must outlive the call it is passed to"""
+        r = OhRemap(self.in_bit_depth, self.out_bit_depth)
+        r.log2_denom = self.log2_denom
+        for c in range(3):
+            r.pre[c] = self.pre[c].ctypes.data_as(C.POINTER(C.c_uint16))
+            r.post[c] = self.post[c].ctypes.data_as(C.POINTER(C.c_uint16))
+            for i in range(3):
+                r.coeff[c][i] = int(self.coeff[c, i])
+        return r
+
+    def luts(self):
+        """oh_remap_luts (host only): where the matrix is diagonal, the three tables of 2^in_bit_depth entries that do the same plane by
+        plane — for Engine.pics_lut(pids, list(remap.luts()), bit_depth=remap.out_bit_depth), at any chroma format.  EngineError with
+        code OH_E_UNSUPPORTED for any other matrix"""
+        out = np.zeros((3, 4096), dtype=np.uint16)
+        r = self.as_struct()
+        _check(lib().oh_remap_luts(C.byref(r), out.ctypes.data_as(C.c_void_p)), "oh_remap_luts")
+        return out[:, :1 << self.in_bit_depth].copy()
+
+    def sample(self, s):
+        """oh_remap_sample (host only): the three output components of the source sample s"""
+        r = self.as_struct()
+        o = (C.c_uint16 * 3)()
+        rc = lib().oh_remap_sample(C.byref(r), (C.c_uint16 * 3)(*[int(v) for v in s]), o)
+        _check(rc, "oh_remap_sample", failed=rc != 1, text="{what} refused the remap")
+        return tuple(o)
+
+
+def remap_curve(in_bit_depth, out_bit_depth, pivots=()):
+    """oh_remap_curve (host only): the piecewise-linear table of 2^in_bit_depth entries through pivots, up to 33 pairs (coded, target)
+    with strictly increasing coded values; (0, 0) and (2^in - 1, 2^out - 1) are added where the pivots do not reach the ends"""
+    pv = [(int(x), int(y)) for x, y in pivots]
+    if any(not (0 <= x <= 0xFFFF and 0 <= y <= 0xFFFF) for x, y in pv):
+        raise ValueError("remap_curve: a pivot is two values of 16 bits")
+    n = len(pv)
+    coded, target = (C.c_uint16 * max(n, 1))(*[x for x, _ in pv]), (C.c_uint16 * max(n, 1))(*[y for _, y in pv])
+    out = np.zeros(1 << in_bit_depth if 0 <= in_bit_depth <= 12 else 1, dtype=np.uint16)
+    _check(lib().oh_remap_curve(int(in_bit_depth), int(out_bit_depth), n, coded, target, out.ctypes.data_as(C.POINTER(C.c_uint16))),
+           "oh_remap_curve")
+    return out
+
+
+def make_remap(pre, coeff, log2_denom, post, in_bit_depth, out_bit_depth=None):
+    """a Remap from its parts.  pre / post: None (the curve without pivots: a rescaling from depth to depth), one table or list of
+    pivots for all three components, or a sequence of three of these; a list of pivots goes through remap_curve.  coeff: None for the
+    identity (2^log2_denom on the diagonal, so log2_denom up to 14: 2^15 is no coefficient), or three rows of three integers"""
+    bi = int(in_bit_depth)
+    bo = bi if out_bit_depth is None else int(out_bit_depth)
+
+    def one(t, b):
+        t = np.zeros(0) if t is None else np.asarray(t)
+        return remap_curve(b, bo, t) if t.size == 0 or (t.ndim == 2 and t.shape[1] == 2) else t
+
+    def three(t, b):
+        # three of them: None, pivot lists (two dimensions) or tables (one dimension, and not the two entries of one pivot)
+        apart = t is not None and len(t) == 3 and all(x is None or np.ndim(x) == 2 or (np.ndim(x) == 1 and len(x) != 2) for x in t)
+        return np.stack([one(x, b) for x in (t if apart else [t] * 3)])
+
+    k = np.eye(3, dtype=np.int64) << int(log2_denom) if coeff is None else coeff
+    return Remap(three(pre, bi), k, log2_denom, three(post, bo), bi, bo)
+
+
+def remap_from_sei(sei):
+    """oh_remap_from_sei (host only): the dict of annexb.colour_remap (or an annexb.OhColourRemapSei) -> the Remap of its six curves and
+    its matrix (absent: the identity).  EngineError with code OH_E_UNSUPPORTED for a depth other than 8, 9, 10 or 12, OH_E_ARG for a
+    cancelled message or pivots that are no curve.  The signal info describes the result and changes no sample."""
+    from . import annexb as A
+    if sei is None:
+        raise ValueError("remap_from_sei: no message")
+    s = sei if isinstance(sei, A.OhColourRemapSei) else A.colour_remap_to_struct(sei)
+    t = np.zeros((6, 4096), dtype=np.uint16)
+    r = OhRemap()
+    _check(lib().oh_remap_from_sei(C.byref(s), t.ctypes.data_as(C.c_void_p), C.byref(r)), "oh_remap_from_sei")
+    k = [[r.coeff[c][i] for i in range(3)] for c in range(3)]
+    return Remap(t[:3, :1 << r.in_bit_depth], k, r.log2_denom, t[3:, :1 << r.out_bit_depth], r.in_bit_depth, r.out_bit_depth)
+
+
 def convert_image_bytes(params, cv):
     """oh_convert_image_bytes (host only): bytes of one image, 0 when the combination is not valid"""
     return int(lib().oh_convert_image_bytes(C.byref(params), C.byref(cv)))
@@ -987,6 +1101,12 @@ def lib():
         L.oh_grain_smooth.restype = I32
         L.oh_grain_blend.argtypes = [I32, I32, I, I]
         L.oh_grain_blend.restype = I32
+        RP = C.POINTER(OhRemap)
+        L.oh_pics_colour_remap.argtypes = [V, IP, IP, I, RP]
+        L.oh_remap_curve.argtypes = [I, I, I, U16P, U16P, U16P]
+        L.oh_remap_sample.argtypes = [RP, U16P, U16P]
+        L.oh_remap_from_sei.argtypes = [V, V, RP]
+        L.oh_remap_luts.argtypes = [RP, V]
         L.oh_motion_blocks.argtypes = [I, I, I, IP, IP]
         L.oh_pics_motion.argtypes = [V, IP, IP, I, C.POINTER(OhMotionSearch), MVP]
         L.oh_pics_motion_compensate.argtypes = [V, IP, IP, I, I, MVP]
@@ -1732,6 +1852,30 @@ class Engine:
         buf = sd if sd.size else np.zeros(1, dtype=np.uint32)   # without pictures there is nothing to read, but a non-null pointer all the same
         self._call(self.L.oh_pics_grain(self.h, _ids(pids), _ids(out), n, C.byref(g), buf.ctypes.data_as(C.POINTER(C.c_uint32))),
                    "oh_pics_grain", made)
+        return out
+
+    def pics_colour_remap(self, pids, remap, *, out=None):
+        """finished 4:4:4 pictures of remap.in_bit_depth -> finished 4:4:4 pictures of the same size at remap.out_bit_depth, every
+        sample through the pre tables, the matrix and the post tables (oh_pics_colour_remap; the exact definition is in
+        include/ohevc_hip.h).  remap: what remap_from_sei or make_remap returned.  out: destination pictures to reuse; None allocates
+        pictures with the sources' params at the output depth.  Returns the destination ids.  Enqueued on the engine stream; does not
+        wait; the remap may be changed at once.  Other chroma formats: pics_reformat first, or pics_lut with remap.luts() where the
+        matrix is diagonal."""
+        pids = list(pids)
+        n = len(pids)
+        if not isinstance(remap, Remap):
+            raise ValueError("pics_colour_remap: remap is what remap_from_sei or make_remap returns")
+        r = remap.as_struct()
+        if out is None and n == 0:
+            return []
+
+        def at_output_depth():
+            dp = F.OhPicParams.from_buffer_copy(self._pic_params(pids[0]))
+            dp.bit_depth = remap.out_bit_depth
+            return dp
+
+        out, made = self._dsts(out, n, "sources", at_output_depth)
+        self._call(self.L.oh_pics_colour_remap(self.h, _ids(pids), _ids(out), n, C.byref(r)), "oh_pics_colour_remap", made)
         return out
 
     def pics_compose(self, dst, layers, *, fill=None):
