@@ -164,7 +164,6 @@ void launch_rgb(const OhColArgs *a, int sample, int n, hipStream_t st)
 
 } // namespace
 
-static_assert(sizeof(((OhColArgs *)nullptr)->misc) / sizeof(int32_t) == OH_COL_NMISC, "misc of oh_colour_tables");
 static_assert(OH_COLT_G >= OH_COL_NA && OH_COLT_B - OH_COLT_G >= OH_COL_NP && OH_COLT_N - OH_COLT_B >= OH_COL_NP && OH_COLT_N % 4 == 0,
               "the tables as whole 16-byte granules");
 

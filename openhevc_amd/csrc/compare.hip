@@ -17,12 +17,12 @@
  * partial results per plane, each a 64-byte line of its own, which the host combines: a 4K luma plane has a thousand tiles, and their
  * atomics on one line queue up behind each other.
  */
-#include "kernels_common.h"
+#include "pics_common.h"
 #include "compare_common.h"
 
 namespace {
 
-constexpr int THREADS = 256, WAVES = THREADS / 64;
+constexpr int WAVES = THREADS / 64;
 constexpr int BX = OH_CMP_TW / 4, BY = OH_CMP_TH / 4;           /* blocks of a tile */
 constexpr int LX = BX + 1, LY = BY + 1;                         /* with the column and the row of the neighbours' blocks */
 
@@ -50,15 +50,10 @@ __global__ __launch_bounds__(THREADS) void compare_kernel(const OhCmpArgs a)
     __shared__ unsigned long long red_sse[WAVES], red_ssim[WAVES];
     __shared__ uint32_t red_diff[WAVES], red_sad[WAVES], red_max[WAVES], red_nf[WAVES];
     const int pair = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    int tile = blockIdx.x, plane = 0;
-    const int n0 = a.k[0].tx * a.k[0].ty;
-    if (tile >= n0) {
-        const int n1 = a.k[1].tx * a.k[1].ty;
-        tile -= n0;
-        plane = 1 + tile / n1;
-        tile -= (plane - 1) * n1;
-    }
-    const OhCmpClass &k = a.k[plane != 0];
+    const int per[2] = { a.k[0].tx * a.k[0].ty, a.k[1].tx * a.k[1].ty };
+    int plane, pq;
+    const int tile = grid_row(blockIdx.x, per, plane, pq);
+    const OhCmpClass &k = a.k[pq];
     const int ty = tile / k.tx, tx = tile - ty * k.tx;
     const int w = k.w, h = k.h, nbx = w >> 2, nby = h >> 2, bx0 = tx * BX, by0 = ty * BY;
     const size_t pitch = (size_t)a.pitch[plane], org = (size_t)k.y0 * pitch + (size_t)k.x0 * sizeof(T);

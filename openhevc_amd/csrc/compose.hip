@@ -19,13 +19,11 @@
  * to nothing; the granules at a source row's ends, at a layer's left and right edge and alpha planes with another pixel stride (the
  * alpha channel of an RGBA image) go sample by sample and read nothing outside the layer.
  */
-#include "../../include/ohevc_hip.h"
-#include "kernels_common.h"
+#include "pics_common.h"
 #include "compose_common.h"
 
 namespace {
 
-constexpr int THREADS = OH_CPS_TW * OH_CPS_TH;
 #define CONSTANT __attribute__((address_space(4)))
 
 typedef uint4v uint4v_a1 __attribute__((aligned(1)));
@@ -72,16 +70,10 @@ __global__ __launch_bounds__(THREADS) void compose_kernel(const OhCpsArgs a)
 {
     constexpr int N = 16 / (int)sizeof(T);                      /* samples of a granule */
     const int pic = blockIdx.y, lane = threadIdx.x & 63, wrow = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int tile = blockIdx.x, plane = 0;
-    const int n0 = a.k[0].tx * a.k[0].ty;
-    if (tile >= n0) {
-        const int n1 = a.k[1].tx * a.k[1].ty;
-        tile -= n0;
-        plane = 1 + tile / n1;
-        tile -= (plane - 1) * n1;
-    }
-    const int q = plane != 0;
-    const OhCpsClass &kc = a.k[q];
+    const int per[2] = { a.k[0].tx * a.k[0].ty, a.k[1].tx * a.k[1].ty };
+    int plane, q;
+    const int tile = grid_row(blockIdx.x, per, plane, q);
+    const OhCpsClass kc = a.k[q];                               /* a copy: the whole block in one load, under way during the division below */
     const int ty = tile / kc.tx, tx = tile - ty * kc.tx;
     const int Y = kc.y0 + ty * OH_CPS_TH + wrow, g = kc.gx0 + tx * OH_CPS_TW + lane;
     if (Y >= kc.y1 || g >= kc.gx1)
@@ -192,9 +184,8 @@ __global__ __launch_bounds__(THREADS) void compose_kernel(const OhCpsArgs a)
 
 } // namespace
 
-static_assert(THREADS == 256 && OH_CPS_TW == 64, "a wave per tile row");
+static_assert(OH_CPS_TW * OH_CPS_TH == THREADS && OH_CPS_TW == 64, "a wave per tile row");
 static_assert(sizeof(OhCpsArgs) <= 4096, "kernel arguments");
-static_assert(sizeof(((OhCpsArgs *)nullptr)->dst) / sizeof(((OhCpsArgs *)nullptr)->dst[0]) == OH_CONV_MAX_PICS, "one launch's pictures");
 static_assert(sizeof(OhCpsLayer) % 8 == 0 && sizeof(OhCpsSrc) == 32, "the table's layout");
 
 extern "C" void ohk_compose(const OhCpsArgs *a, int n, hipStream_t st)

@@ -163,7 +163,6 @@ void launch_yuv(const OhConvArgs *a, int sample, int n, hipStream_t st)
 
 } // namespace
 
-static_assert(sizeof(((OhConvArgs *)nullptr)->src) / sizeof(((OhConvArgs *)nullptr)->src[0]) == OH_CONV_MAX_PICS, "one launch's pictures");
 
 extern "C" void ohk_convert(const OhConvArgs *a, int format, int sample, int n, hipStream_t st)
 {

@@ -1,18 +1,15 @@
 /*
  * convert_common.h — what the kernels that read pictures as images share (convert.hip: oh_pics_convert; colour.hip: oh_pics_convert_colour;
- * light.hip: oh_pics_light_level):
- * staging of source rows into LDS as 16-byte granules, the aligned store of an LDS image of the destination bytes, the chroma filter
- * and the integer matrix of DESIGN.md §3b, and the output sample types.  Device code only.
+ * light.hip: oh_pics_light_level), on top of pics_common.h: the image layouts and the output sample types, the chroma filter and the
+ * integer matrix of DESIGN.md §3b.  Device code only.
  */
 #ifndef OHEVC_CONVERT_COMMON_H
 #define OHEVC_CONVERT_COMMON_H
 
-#include "../../include/ohevc_hip.h"
-#include "kernels_common.h"
+#include "pics_common.h"
 
 namespace {
 
-constexpr int THREADS = 256;
 enum { L_PLANAR, L_SEMI, L_RGBP, L_RGBI };          /* YUV planar, YUV semi-planar, RGB planar, RGB / RGBA interleaved */
 enum { O_U8, O_U16, O_F16, O_F32 };                 /* output sample type */
 
@@ -20,37 +17,6 @@ template <int O> struct OutT { typedef uint8_t T; };
 template <> struct OutT<O_U16> { typedef uint16_t T; };
 template <> struct OutT<O_F16> { typedef uint16_t T; };
 template <> struct OutT<O_F32> { typedef float T; };
-
-/* n samples of type T at p (a plane row in HBM) -> LDS at lds, as the 16-byte granules that cover them; returns the index (in T) of
- * p[0] in lds.  lds must hold n * sizeof(T) + 30 bytes. */
-template <typename T>
-__device__ __forceinline__ int stage(uint8_t *lds, const void *p, int n)
-{
-    const uintptr_t a = (uintptr_t)p, a0 = a & ~(uintptr_t)15, a1 = (a + (uintptr_t)n * sizeof(T) + 15) & ~(uintptr_t)15;
-    const int g = (int)((a1 - a0) >> 4);
-    for (int i = threadIdx.x; i < g; i += THREADS)
-        *(uint4v *)(lds + 16 * i) = *(const GLOBAL uint4v *)(a0 + 16 * (uintptr_t)i);
-    return (int)((a - a0) / sizeof(T));
-}
-
-/* nbytes bytes to dst from img, the LDS image that holds the byte for dst + i at img[(dst & 15) + i] */
-__device__ __forceinline__ void store_out(uint8_t *dst, const uint8_t *img, int nbytes)
-{
-    const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (uintptr_t)nbytes, a0 = (d0 + 15) & ~(uintptr_t)15, a1 = d1 & ~(uintptr_t)15;
-    const int o = (int)(d0 & 15), t = threadIdx.x;
-    if (a0 >= a1) {
-        for (int i = t; i < nbytes; i += THREADS)
-            G_MUT(uint8_t, dst)[i] = img[o + i];
-        return;
-    }
-    const int head = (int)(a0 - d0), tail = (int)(d1 - a1), g = (int)((a1 - a0) >> 4);
-    if (t < head)
-        G_MUT(uint8_t, dst)[t] = img[o + t];
-    else if (t >= 64 && t - 64 < tail)
-        G_MUT(uint8_t, a1)[t - 64] = img[o + (int)(a1 - d0) + t - 64];
-    for (int i = t; i < g; i += THREADS)                        /* img + o + head is 16-byte aligned: o + head is 0 or 16 */
-        *(GLOBAL uint4v *)(a0 + 16 * (uintptr_t)i) = *(const uint4v *)(img + o + head + 16 * i);
-}
 
 /* the f16 nearest (ties to even) to a non-negative finite f32 below 65520, in integer arithmetic.  A plain conversion of the product
  * below is folded into one v_fma_mixlo_f16, which rounds the exact product to f16 once instead of rounding the f32 product. */

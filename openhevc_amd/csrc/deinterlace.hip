@@ -20,48 +20,26 @@
  * 8, 16 and 20 that the caches had to absorb (at 10 bit BLEND went from 1.15 to 1.08 of a copy's time and LOWPASS5 from 1.33 to 1.08:
  * DESIGN.md §3l).
  * ADAPTIVE, whose unit is one pair, compares seven columns of the two kept rows up / dn of cur around x: those two rows of the segment, with one granule of halo
- * on either side, are staged in LDS (convert_common.h: stage; one barrier), and a lane reads the granule of its columns and the two
+ * on either side, are staged in LDS (pics_common.h: stage; one barrier), and a lane reads the granule of its columns and the two
  * next to it (ds_read_b128: consecutive lanes read consecutive granules, no conflicts) into a window of GS + 6 samples in registers;
  * the granule at either edge of the plane takes its samples one by one, columns clamped.  Of prev, next and row y of cur it needs
  * column x only: six register granules straight from HBM.  The kept row is copied out of the staged one.
  * Templates on the stored sample type and on ADAPTIVE (LDS, more registers); the other modes are a uniform branch.
  */
 #include <algorithm>
-#include "convert_common.h"
+#include "pics_common.h"
 #include "deinterlace_common.h"
 
 namespace {
-
-#define LDS __attribute__((address_space(3)))     /* the staged rows: say so, or reads through pointers picked at run time turn flat */
 
 constexpr int SEG = OH_DI_SEG;
 
 /* pairs of rows in a unit of deint_kernel: the vertical filters take four, which share the rows between them */
 __host__ __device__ constexpr int unit_pairs(bool adaptive) { return adaptive ? 1 : 4; }
 
-/* the plane (c, class q) and the unit of it that row r of the grid stands for; per[q]: grid rows per plane of the class */
-__device__ __forceinline__ int grid_row(int r, const int per[2], int &c, int &q)
-{
-    c = 0; q = 0;
-    if (r < per[0])
-        return r;
-    r -= per[0];
-    q = 1; c = r < per[1] ? 1 : 2;
-    return r - (c - 1) * per[1];
-}
-
 /* bytes of one staged row of ADAPTIVE: a segment and a granule of halo on either side */
 template <typename T>
 constexpr int slot_bytes() { return (SEG * (int)sizeof(T) + 2 * 16 + 32 + 15) / 16 * 16; }
-
-template <typename T>
-struct Samples {
-    static constexpr int GS = 16 / (int)sizeof(T);
-    T s[GS];
-    __device__ __forceinline__ explicit Samples(uint4v v) { __builtin_memcpy(s, &v, sizeof(v)); }
-    __device__ __forceinline__ Samples() {}
-    __device__ __forceinline__ uint4v granule() const { uint4v v; __builtin_memcpy(&v, s, sizeof(v)); return v; }
-};
 
 template <typename T>
 __global__ __launch_bounds__(THREADS) void fields_kernel(const OhDiArgs a)
@@ -243,7 +221,6 @@ void launch_deint(const OhDiArgs *a, int n, hipStream_t st)
 
 } // namespace
 
-static_assert(sizeof(((OhDiArgs *)nullptr)->pic[0]) / sizeof(((OhDiArgs *)nullptr)->pic[0][0]) == OH_CONV_MAX_PICS, "one launch's pictures");
 static_assert(OH_DI_SEG % 16 == 0, "a segment is whole 16-byte granules of either sample type");
 
 extern "C" void ohk_deinterlace(const OhDiArgs *a, int n, hipStream_t st)

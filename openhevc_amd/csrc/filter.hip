@@ -27,12 +27,10 @@
  * Templates on the stored sample type, the mode class and R.
  */
 #include <algorithm>
-#include "convert_common.h"
+#include "pics_common.h"
 #include "filter_common.h"
 
 namespace {
-
-#define LDS __attribute__((address_space(3)))     /* the staged tiles: say so, or reads through pointers picked at run time turn flat */
 
 constexpr int TW = OH_FLT_TW, TH = OH_FLT_TH;
 enum { K_CONV, K_MEDIAN, K_TEMPORAL };            /* the kernels: CONVOLVE and UNSHARP share one */
@@ -49,26 +47,6 @@ struct Geo {
 
 template <typename T, int R> constexpr int tile_bytes() { return (TH + 2 * R) * Geo<T>::PITCH; }
 template <int R> constexpr int sums_bytes() { return (TH + 2 * R) * TW * 4; }
-
-template <typename T>
-struct Samples {
-    static constexpr int GS = 16 / (int)sizeof(T);
-    T s[GS];
-    __device__ __forceinline__ explicit Samples(uint4v v) { __builtin_memcpy(s, &v, sizeof(v)); }
-    __device__ __forceinline__ Samples() {}
-    __device__ __forceinline__ uint4v granule() const { uint4v v; __builtin_memcpy(&v, s, sizeof(v)); return v; }
-};
-
-/* the plane (c, class q) and the row of tiles of it that row r of the grid stands for; per[q]: grid rows per plane of the class */
-__device__ __forceinline__ int grid_row(int r, const int per[2], int &c, int &q)
-{
-    c = 0; q = 0;
-    if (r < per[0])
-        return r;
-    r -= per[0];
-    q = 1; c = r < per[1] ? 1 : 2;
-    return r - (c - 1) * per[1];
-}
 
 /* rows Y0 - R .. Y0 + TH + R - 1 (clamped) of the plane at `base`, granules X0 / GS - 1 .. X0 / GS + NG (columns clamped), into `tile` */
 template <typename T, int R>
@@ -286,7 +264,6 @@ void launch(const OhFilterArgs *a, int n, hipStream_t st)
 
 } // namespace
 
-static_assert(sizeof(((OhFilterArgs *)nullptr)->dst) / sizeof(((OhFilterArgs *)nullptr)->dst[0]) == OH_CONV_MAX_PICS, "one launch's pictures");
 static_assert(sizeof(((OhFilterArgs *)nullptr)->taps_h[0]) / sizeof(int32_t) == OH_FILTER_MAX_TAPS, "the centred taps of one class");
 static_assert(OH_FLT_TW % 16 == 0 && OH_FILTER_MAX_TAPS / 2 < 8, "a tile row is whole granules of either sample type; the halo is less than one");
 static_assert(tile_bytes<uint16_t, 7>() + sums_bytes<7>() <= 64 << 10 && 3 * tile_bytes<uint16_t, 1>() <= 64 << 10, "LDS of one workgroup");

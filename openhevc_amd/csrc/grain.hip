@@ -17,13 +17,10 @@
  * stay out of the sums.  A source sample above 2^bit depth - 1, which no decoder and no service writes, cannot take a mean past
  * the table: the mean is clamped to 255.
  */
-#include "../../include/ohevc_hip.h"
-#include "kernels_common.h"
+#include "pics_common.h"
 #include "grain_common.h"
 
 namespace {
-
-constexpr int THREADS = GRAIN_TW * GRAIN_BLOCK;
 
 template <typename T> struct Row;                               /* the 8 samples of a lane */
 template <> struct Row<uint8_t>  { typedef uint2v V; };
@@ -63,15 +60,10 @@ __global__ __launch_bounds__(THREADS) void grain_kernel(const OhGrainArgs a)
     __shared__ uint32_t sums[GRAIN_BLOCK][GRAIN_TW + 2];        /* [row][block]: 0 and GRAIN_TW + 1 the blocks beside the tile */
     __shared__ uint32_t desc[GRAIN_TW + 2];
     const int pic = blockIdx.y, t = threadIdx.x;
-    int tile = blockIdx.x, plane = 0;
-    const int n0 = a.tx[0] * a.ty[0];
-    if (tile >= n0) {
-        const int n1 = a.tx[1] * a.ty[1];
-        tile -= n0;
-        plane = 1 + tile / n1;
-        tile -= (plane - 1) * n1;
-    }
-    const int q = plane != 0, W = a.w[q], H = a.h[q];
+    const int per[2] = { a.tx[0] * a.ty[0], a.tx[1] * a.ty[1] };
+    int plane, q;
+    const int tile = grid_row(blockIdx.x, per, plane, q);
+    const int W = a.w[q], H = a.h[q];
     const int by = tile / a.tx[q], bx0 = (tile - by * a.tx[q]) * GRAIN_TW;      /* the tile's block row and its first block */
     const int r = t / GRAIN_TW, b = t % GRAIN_TW;
     const int bx = bx0 + b, x0 = bx * GRAIN_BLOCK, y = by * GRAIN_BLOCK + r;
@@ -151,7 +143,7 @@ __global__ __launch_bounds__(THREADS) void grain_kernel(const OhGrainArgs a)
 } // namespace
 
 static_assert(sizeof(OhGrainArgs) <= 4096, "kernel arguments");
-static_assert(sizeof(((OhGrainArgs *)nullptr)->dst) / sizeof(((OhGrainArgs *)nullptr)->dst[0]) == OH_CONV_MAX_PICS, "one launch's pictures");
+static_assert(GRAIN_TW * GRAIN_BLOCK == THREADS, "a lane per row of a block of the tile");
 static_assert(GRAIN_TW + 2 <= THREADS && 2 * GRAIN_BLOCK <= THREADS, "lanes for the descriptors and for the blocks beside the tile");
 
 extern "C" void ohk_grain(const OhGrainArgs *a, int n, hipStream_t st)

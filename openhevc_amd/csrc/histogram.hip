@@ -17,12 +17,11 @@
  * everywhere: no partial counter is narrower than the result.  At the end the workgroup adds its non-zero bins to the plane's zeroed
  * result with one atomic each.
  */
-#include "../../include/ohevc_hip.h"
-#include "kernels_common.h"
+#include "pics_common.h"
 
 namespace {
 
-constexpr int THREADS = 256, WAVES = THREADS / 64;
+constexpr int WAVES = THREADS / 64;
 
 /* the wave's copies of the histogram: as many as keep the LDS of a workgroup at 32 KB */
 __host__ __device__ constexpr int copies_of(int bd) { return bd > 10 ? 2 : WAVES; }
@@ -34,13 +33,10 @@ __global__ __launch_bounds__(THREADS) void histogram_kernel(const OhHistArgs a)
     constexpr uint32_t SM = (1u << SB) - 1, REP = sizeof(T) == 1 ? 0x01010101u : 0x00010001u;
     extern __shared__ uint32_t hist[];                          /* copies_of(bd) << bd */
     const int pic = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    int tile = blockIdx.x, plane = 0;
-    if (tile >= a.k[0].tiles) {
-        tile -= a.k[0].tiles;
-        plane = 1 + tile / a.k[1].tiles;
-        tile -= (plane - 1) * a.k[1].tiles;
-    }
-    const OhHistClass &k = a.k[plane != 0];
+    const int per[2] = { a.k[0].tiles, a.k[1].tiles };
+    int plane, q;
+    const int tile = grid_row(blockIdx.x, per, plane, q);
+    const OhHistClass &k = a.k[q];
     const int bins = 1 << a.bd, copies = copies_of(a.bd);
     const uint32_t M = (uint32_t)bins - 1;
     for (int i = t; i < copies * bins; i += THREADS)
@@ -65,7 +61,7 @@ __global__ __launch_bounds__(THREADS) void histogram_kernel(const OhHistArgs a)
                 uint32_t cur = 0, cnt = 0;
 #pragma unroll
                 for (int j = 0; j < GS; j++) {
-                    const uint32_t s = min((v[j * (int)sizeof(T) / 4] >> (SB * (j % (4 / (int)sizeof(T))))) & SM, M);
+                    const uint32_t s = min(unit_get<T>(&v, j) & SM, M);
                     if (j >= lo && j < hi) {
                         if (cnt && s != cur) {
                             atomicAdd(&my[cur], cnt);
@@ -101,8 +97,6 @@ __global__ __launch_bounds__(THREADS) void histogram_kernel(const OhHistArgs a)
 } // namespace
 
 static_assert(sizeof(OhHistArgs) <= 4096, "kernel arguments");
-static_assert(OH_HG_BINS == OH_HIST_BINS, "the device result has the bins of OhPlaneHist");
-static_assert(sizeof(((OhHistArgs *)nullptr)->src) / sizeof(((OhHistArgs *)nullptr)->src[0]) == OH_CONV_MAX_PICS, "one launch's pictures");
 
 extern "C" void ohk_histogram(const OhHistArgs *a, int n, hipStream_t st)
 {

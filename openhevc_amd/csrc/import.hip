@@ -272,7 +272,6 @@ void launch_rgb(const OhImpArgs *a, int sample, int n, hipStream_t st)
 
 } // namespace
 
-static_assert(sizeof(((OhImpArgs *)nullptr)->dst) / sizeof(((OhImpArgs *)nullptr)->dst[0]) == OH_CONV_MAX_PICS, "one launch's pictures");
 
 extern "C" void ohk_import(const OhImpArgs *a, int format, int sample, int n, hipStream_t st)
 {

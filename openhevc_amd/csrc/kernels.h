@@ -1,8 +1,12 @@
-/* kernels.h — launchers of the per-pass kernel files (mc / residual / intra / deblock / sao / upsample .hip) (internal to libohevc_hip.so) */
+/* kernels.h — the launchers of the kernel files and what they take (internal to libohevc_hip.so): the argument blocks of the picture
+ * services, one per .hip file and passed by value in the kernel arguments, with the tile sizes that the host shares, then the launchers
+ * of the services and of the decode passes (mc / residual / intra / deblock / sao / upsample / prep / bs .hip).  Array sizes are the
+ * public constants of include/ohevc_hip.h. */
 #ifndef OHEVC_KERNELS_H
 #define OHEVC_KERNELS_H
 
 #include <hip/hip_runtime.h>
+#include "../../include/ohevc_hip.h"
 #include "dev_frame.h"
 #include "upblock.h"
 
@@ -27,7 +31,7 @@ enum { OH_HASH_TASK = 128 << 10 };   /* packed plane bytes per CRC / checksum wo
 /* picture conversion (convert.hip): what one launch needs, passed by value in the kernel arguments (no job table in memory that a
  * later call could overwrite before the launch runs).  Every picture of a launch has the same geometry; src: its finished planes. */
 struct OhConvArgs {
-    const void *src[64][3];      /* OH_CONV_MAX_PICS pictures x planes */
+    const void *src[OH_CONV_MAX_PICS][3]; /* pictures x planes */
     void       *dst;             /* image of the launch's first picture */
     uint64_t    image_stride;    /* bytes from one image to the next */
     int32_t     pitch[3];        /* bytes between rows of each plane */
@@ -42,7 +46,7 @@ struct OhConvArgs {
 /* picture import (import.hip): the inverse of OhConvArgs.  dst: half 0 of the destination pictures, src: the image of the
  * launch's first picture in caller-owned device memory; every picture of a launch has the same geometry. */
 struct OhImpArgs {
-    void       *dst[64][3];      /* OH_CONV_MAX_PICS pictures x planes */
+    void       *dst[OH_CONV_MAX_PICS][3]; /* pictures x planes */
     const void *src;             /* image of the launch's first picture */
     uint64_t    image_stride;    /* bytes from one image to the next */
     int32_t     pitch[3];        /* bytes between rows of each plane */
@@ -62,7 +66,7 @@ enum { OH_COLT_G = 4100, OH_COLT_B = 4100 + 1604, OH_COLT_N = 4100 + 2 * 1604,
 struct OhColArgs {
     OhConvArgs     c;
     const int32_t *tab;
-    int32_t        misc[20];         /* OH_COL_NMISC */
+    int32_t        misc[OH_COL_NMISC];
 };
 
 /* light-level statistics (light.hip): the geometry and the 16-bit matrix of an RGB conversion (c.dst, c.image_stride and
@@ -73,7 +77,7 @@ enum { OH_LL_ROWS = 32,              /* image rows per workgroup: it loads the t
 struct OhLightDev {                  /* one picture's sums; cleared to zero in front of the launch */
     unsigned long long sum;
     uint32_t max, not_min;           /* not_min: the largest ~v, so that zero is the neutral start of all four */
-    uint32_t hist[258];              /* OH_LL_NBINS */
+    uint32_t hist[OH_LL_NBINS];
 };
 struct OhLightArgs {
     OhConvArgs     c;
@@ -100,7 +104,7 @@ struct OhCmpClass {
     int32_t tx, ty;                  /* tiles across and down: at least one each */
 };
 struct OhCmpArgs {
-    const void *a[64][3], *b[64][3]; /* OH_CONV_MAX_PICS pairs x planes: the finished halves */
+    const void *a[OH_CONV_MAX_PICS][3], *b[OH_CONV_MAX_PICS][3]; /* pairs x planes: the finished halves */
     OhCmpDev   *res;                 /* [pair][3][OH_CMP_SLOTS] */
     OhCmpClass  k[2];
     int32_t     pitch[3];            /* bytes between rows of each plane */
@@ -132,7 +136,7 @@ struct OhCpsClass {
     int32_t tx, ty;                  /* tiles across and down */
 };
 struct OhCpsArgs {
-    void             *dst[64][3];    /* OH_CONV_MAX_PICS destinations x planes: the finished halves */
+    void             *dst[OH_CONV_MAX_PICS][3]; /* destinations x planes: the finished halves */
     const OhCpsLayer *layers;        /* [n_layers] */
     const OhCpsSrc   *srcs;          /* [n_layers][n_pics] */
     OhCpsClass        k[2];
@@ -148,8 +152,8 @@ struct OhCpsArgs {
 enum { OH_RF_SEG = 4096 };           /* plane samples per workgroup segment: of the destination row, or of the source row where chroma is
                                         sub-sampled horizontally on the way (then OH_RF_SEG / 2 destination samples) */
 struct OhRfArgs {
-    const void *src[64][3];          /* OH_CONV_MAX_PICS pictures x planes: the finished halves */
-    void       *dst[64][3];          /* half 0 of the destinations */
+    const void *src[OH_CONV_MAX_PICS][3]; /* pictures x planes: the finished halves */
+    void       *dst[OH_CONV_MAX_PICS][3]; /* half 0 of the destinations */
     int32_t     spitch[3], dpitch[3];/* bytes between rows of each plane */
     int32_t     sw[2], sh[2];        /* coded size of the source planes (sw[1] = 0: 4:0:0) */
     int32_t     dw[2], dh[2];        /* coded size of the destination planes (dw[1] = 0: 4:0:0) */
@@ -163,8 +167,8 @@ struct OhRfArgs {
 enum { OH_OR_TILE = 64,              /* edge of the square tile of destination samples that one workgroup of the transposing kernel makes */
        OH_OR_SEG = 4096 };           /* destination samples of one row per workgroup of the row kernel (orientations 0 .. 3) */
 struct OhOrArgs {
-    const void *src[64][3];          /* OH_CONV_MAX_PICS pictures x planes: the finished halves */
-    void       *dst[64][3];          /* half 0 of the destinations */
+    const void *src[OH_CONV_MAX_PICS][3]; /* pictures x planes: the finished halves */
+    void       *dst[OH_CONV_MAX_PICS][3]; /* half 0 of the destinations */
     int32_t     spitch[3], dpitch[3];/* bytes between rows of each plane */
     int32_t     x0[2], y0[2];        /* origin of the plane's window S in the source plane */
     int32_t     ws[2], hs[2];        /* size of S, plane samples */
@@ -177,8 +181,8 @@ struct OhOrArgs {
  * in the kernel arguments; every picture of a launch has the same geometry.  Two plane classes (0 luma, 1 chroma).  The tile of one
  * workgroup and its LDS budget are WARP_TW, WARP_TH and WARP_LDS of warp_common.h, which the host's oh_warp_paths shares. */
 struct OhWarpArgs {
-    const void *src[64][3];          /* OH_CONV_MAX_PICS pictures x planes: the finished halves */
-    void       *dst[64][3];          /* half 0 of the destinations */
+    const void *src[OH_CONV_MAX_PICS][3]; /* pictures x planes: the finished halves */
+    void       *dst[OH_CONV_MAX_PICS][3]; /* half 0 of the destinations */
     int64_t     m[9];                /* OhWarp.m */
     int32_t     spitch[3], dpitch[3];/* bytes between rows of each plane */
     int32_t     x0[2], y0[2];        /* origin of the plane's window in the source plane */
@@ -201,7 +205,7 @@ struct OhWarpArgs {
 enum { OH_DI_SEG = 4096 };           /* destination samples of one row per workgroup */
 enum { OH_DI_WEAVE = 0, OH_DI_SEPARATE };
 struct OhDiArgs {
-    void       *pic[4][64][3];       /* role x OH_CONV_MAX_PICS pictures x planes */
+    void       *pic[4][OH_CONV_MAX_PICS][3]; /* role x pictures x planes */
     int32_t     pitch[3];            /* bytes between rows of each plane: of the frames (ohk_fields), of every picture (ohk_deinterlace) */
     int32_t     fpitch[3];           /* ohk_fields: bytes between rows of each plane of the fields */
     int32_t     w[2], h[2];          /* coded size of the planes: of the frames (ohk_fields), of every picture (ohk_deinterlace) */
@@ -215,9 +219,9 @@ struct OhDiArgs {
 enum { OH_FLT_TW = 128,              /* destination samples across one workgroup's tile: the horizontal unit */
        OH_FLT_TH = 32 };             /* destination rows of a tile: the vertical unit */
 struct OhFilterArgs {
-    const void *src[3][64][3];       /* prev, src, next (finished halves; prev and next are read by OH_FILTER_TEMPORAL only) x
-                                        OH_CONV_MAX_PICS pictures x planes */
-    void       *dst[64][3];          /* half 0 of the destinations */
+    const void *src[3][OH_CONV_MAX_PICS][3]; /* prev, src, next (finished halves; prev and next are read by OH_FILTER_TEMPORAL only) x
+                                        pictures x planes */
+    void       *dst[OH_CONV_MAX_PICS][3]; /* half 0 of the destinations */
     int32_t     pitch[3];            /* bytes between rows of each plane */
     int32_t     w[2], h[2];          /* coded size of the planes */
     int32_t     np, bd;              /* planes: 1 or 3; bit depth */
@@ -231,14 +235,14 @@ struct OhFilterArgs {
  * arguments, two plane classes (0 luma, 1 chroma) with the plane's window and the 16-byte granules of a row that cover it, and the bins
  * of the launch's first picture in device memory that the engine owns and clears on the stream in front of the launch. */
 enum { OH_HG_ROWS = 8,               /* window rows per workgroup: all the granules of each */
-       OH_HG_BINS = 4096 };          /* OH_HIST_BINS: uint32 per plane of a picture in res */
+       OH_HG_BINS = OH_HIST_BINS };  /* uint32 per plane of a picture in res */
 struct OhHistClass {
     int32_t x0, y0, w, h;            /* the plane's window: origin in the plane, size */
     int32_t g0, ng;                  /* the first granule of a plane row that holds a sample of the window, and how many do */
     int32_t tiles;                   /* workgroups per plane: ceil(h / OH_HG_ROWS) */
 };
 struct OhHistArgs {
-    const void *src[64][3];          /* OH_CONV_MAX_PICS pictures x planes: the finished halves */
+    const void *src[OH_CONV_MAX_PICS][3]; /* pictures x planes: the finished halves */
     uint32_t   *res;                 /* [picture][3][OH_HG_BINS] */
     OhHistClass k[2];
     int32_t     pitch[3];            /* bytes between rows of each plane */
@@ -252,8 +256,8 @@ enum { OH_LUT_ROWS = 16,             /* plane rows per workgroup: it loads its p
        OH_LUT_UNIT = 16,             /* samples a lane takes at a time: whole 16-byte granules of either sample type */
        OH_LUT_MAX = 4096 };          /* entries of a table at 12 bit */
 struct OhLutArgs {
-    const void     *src[64][3];      /* OH_CONV_MAX_PICS pictures x planes: the finished halves */
-    void           *dst[64][3];      /* half 0 of the destinations */
+    const void     *src[OH_CONV_MAX_PICS][3]; /* pictures x planes: the finished halves */
+    void           *dst[OH_CONV_MAX_PICS][3]; /* half 0 of the destinations */
     const uint16_t *tab;             /* [3][OH_LUT_MAX] */
     int32_t         spitch[3], dpitch[3];   /* bytes between rows of each plane */
     int32_t         w[2], h[2];      /* coded size of the planes */
@@ -266,8 +270,8 @@ struct OhLutArgs {
  * lie in device memory that the engine owns: the tables and seeds of the call, filled on the stream in front of the launches, and the
  * 169 patterns, filled once. */
 struct OhGrainArgs {
-    const void     *src[64][3];      /* OH_CONV_MAX_PICS pictures x planes: the finished halves */
-    void           *dst[64][3];      /* half 0 of the destinations */
+    const void     *src[OH_CONV_MAX_PICS][3]; /* pictures x planes: the finished halves */
+    void           *dst[OH_CONV_MAX_PICS][3]; /* half 0 of the destinations */
     const uint32_t *tab;             /* [3][OH_GRAIN_ENTRIES] */
     const uint32_t *seeds;           /* of the launch's first picture on */
     const int8_t   *patterns;        /* [13][13][32][32]: grain_pattern_index of grain_common.h */
@@ -284,8 +288,8 @@ struct OhGrainArgs {
 enum { OH_REMAP_ROWS = 8 };          /* picture rows per workgroup: it loads the six tables once for all of them.  Coded heights are
                                       * multiples of the minimum coding block of 8, so no band is ever cut; measured against 4, 16, 32, 64 */
 struct OhRemapArgs {
-    const void     *src[64][3];      /* OH_CONV_MAX_PICS pictures x planes: the finished halves */
-    void           *dst[64][3];      /* half 0 of the destinations */
+    const void     *src[OH_CONV_MAX_PICS][3]; /* pictures x planes: the finished halves */
+    void           *dst[OH_CONV_MAX_PICS][3]; /* half 0 of the destinations */
     const uint16_t *tab;             /* [6][OH_LUT_MAX] */
     int32_t         spitch[3], dpitch[3];   /* bytes between rows of each plane */
     int32_t         w, h;            /* coded size of every plane */
@@ -303,7 +307,7 @@ enum { OH_MO_REACH = 4 };            /* reference samples beyond the integer ran
 struct OhMoVec { int16_t x, y; };    /* a vector (quarter samples) of a field, or a centre (integer samples) */
 struct OhMoDev { int16_t x, y; uint32_t sad, sad_centre; };  /* OhMotionVector */
 struct OhMoSearchArgs {
-    const void    *cur[64], *ref[64];/* OH_CONV_MAX_PICS pairs: the finished luma planes */
+    const void    *cur[OH_CONV_MAX_PICS], *ref[OH_CONV_MAX_PICS]; /* pairs: the finished luma planes */
     const OhMoVec *centres;          /* [pair][bh][bw], or null: all zero */
     OhMoDev       *res;              /* [pair][bh][bw] */
     int32_t        pitch;            /* bytes between luma rows */
@@ -312,8 +316,8 @@ struct OhMoSearchArgs {
     int32_t        rx, ry, subpel, lambda;
 };
 struct OhMoCompArgs {
-    const void    *ref[64][3];       /* OH_CONV_MAX_PICS pictures x planes: the finished halves */
-    void          *dst[64][3];       /* half 0 of the destinations */
+    const void    *ref[OH_CONV_MAX_PICS][3]; /* pictures x planes: the finished halves */
+    void          *dst[OH_CONV_MAX_PICS][3]; /* half 0 of the destinations */
     const OhMoVec *field;            /* [picture][bh][bw] */
     int32_t        pitch[3];         /* bytes between rows of each plane */
     int32_t        w[2], h[2];       /* coded size of the planes */
@@ -346,8 +350,8 @@ struct OhResizeClass {
     const int32_t *v_k;              /* [pair][OH_RESIZE_VROWS]: (coefficient of the even row, of the odd row) of each image row, zero where a row has no tap */
 };
 struct OhResizeArgs {
-    const void *src[64][3];          /* OH_RESIZE_MAX_PICS pictures x planes: the finished half */
-    void       *dst[64][3];          /* the half the image is written to */
+    const void *src[OH_RESIZE_MAX_PICS][3]; /* pictures x planes: the finished half */
+    void       *dst[OH_RESIZE_MAX_PICS][3]; /* the half the image is written to */
     int16_t    *mid;                 /* intermediate of the launch set's first picture */
     uint64_t    mid_pic;             /* int16 from one picture's intermediate to the next */
     uint64_t    mid_plane[3];        /* int16 from there to each plane's */

@@ -118,7 +118,6 @@ __global__ __launch_bounds__(THREADS) void light_kernel(const OhLightArgs la)
 
 } // namespace
 
-static_assert(OH_LL_NBINS == sizeof(((OhLightDev *)nullptr)->hist) / sizeof(uint32_t), "hist of OhLightLevel");
 static_assert(OH_COLT_G >= OH_COL_NA && OH_COLT_G % 4 == 0, "table A as whole 16-byte granules");
 static_assert(OH_LL_NBINS <= HS, "a wave's copy of the histogram");
 

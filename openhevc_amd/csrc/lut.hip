@@ -18,29 +18,19 @@
  * bound to copies, which costs the LDS that lets more workgroups share a CU.  A source sample above 2^bit depth - 1, which no decoder
  * and no service writes, is looked up by its low bits: no read leaves the table.
  */
-#include "../../include/ohevc_hip.h"
-#include "kernels_common.h"
+#include "pics_common.h"
 
 namespace {
-
-constexpr int THREADS = 256;
 
 template <typename TI, typename TS>
 __global__ __launch_bounds__(THREADS) void lut_kernel(const OhLutArgs a)
 {
-    constexpr int U = OH_LUT_UNIT, NI = U * (int)sizeof(TI) / 16, NO = U * (int)sizeof(TS) / 16;     /* granules of a unit, in and out */
-    constexpr int SBI = 8 * (int)sizeof(TI), PI = 4 / (int)sizeof(TI), SBO = 8 * (int)sizeof(TS), PO = 4 / (int)sizeof(TS);
+    constexpr int U = OH_LUT_UNIT, NI = Unit<TI>::N, NO = Unit<TS>::N;         /* granules of a unit, in and out */
     extern __shared__ __attribute__((aligned(16))) uint16_t tab[];               /* 1 << sbd entries */
     const int pic = blockIdx.y, t = threadIdx.x;
-    int tile = blockIdx.x, plane = 0;
-    const int n0 = (a.h[0] + OH_LUT_ROWS - 1) / OH_LUT_ROWS;
-    if (tile >= n0) {
-        const int n1 = (a.h[1] + OH_LUT_ROWS - 1) / OH_LUT_ROWS;
-        tile -= n0;
-        plane = 1 + tile / n1;
-        tile -= (plane - 1) * n1;
-    }
-    const int q = plane != 0;
+    const int per[2] = { (a.h[0] + OH_LUT_ROWS - 1) / OH_LUT_ROWS, (a.h[1] + OH_LUT_ROWS - 1) / OH_LUT_ROWS };
+    int plane, q;
+    const int tile = grid_row(blockIdx.x, per, plane, q);
     const bool sel = (a.planes >> plane) & 1;                   /* the same for the whole workgroup */
     const uint32_t mask = (1u << a.sbd) - 1;
     if (sel) {
@@ -75,8 +65,7 @@ __global__ __launch_bounds__(THREADS) void lut_kernel(const OhLutArgs a)
             out[g] = uint4v{ 0, 0, 0, 0 };
 #pragma unroll
         for (int j = 0; j < U; j++) {
-            const uint32_t v = (in[j / PI / 4][j / PI % 4] >> (SBI * (j % PI))) & mask;
-            out[j / PO / 4][j / PO % 4] |= (uint32_t)tab[v] << (SBO * (j % PO));
+            unit_put<TS>(out, j, tab[unit_get<TI>(in, j) & mask]);
         }
 #pragma unroll
         for (int g = 0; g < NO; g++)
@@ -95,16 +84,9 @@ void launch(const OhLutArgs *a, int n, hipStream_t st)
 } // namespace
 
 static_assert(sizeof(OhLutArgs) <= 4096, "kernel arguments");
-static_assert(sizeof(((OhLutArgs *)nullptr)->dst) / sizeof(((OhLutArgs *)nullptr)->dst[0]) == OH_CONV_MAX_PICS, "one launch's pictures");
 static_assert(OH_LUT_UNIT == 16, "a unit is whole granules of 8-bit and of 16-bit samples, and a 256-byte row holds whole units of both");
 
 extern "C" void ohk_lut(const OhLutArgs *a, int n, hipStream_t st)
 {
-    if (a->sbd == 8) {
-        if (a->dbd == 8) launch<uint8_t, uint8_t>(a, n, st);
-        else             launch<uint8_t, uint16_t>(a, n, st);
-    } else {
-        if (a->dbd == 8) launch<uint16_t, uint8_t>(a, n, st);
-        else             launch<uint16_t, uint16_t>(a, n, st);
-    }
+    with_sample_types(a->sbd, a->dbd, [&](auto ti, auto ts) { launch<decltype(ti), decltype(ts)>(a, n, st); });
 }

@@ -27,13 +27,10 @@
  * Templates on the stored sample type.
  */
 #include <algorithm>
-#include "../../include/ohevc_hip.h"
-#include "kernels_common.h"
+#include "pics_common.h"
 #include "motion_common.h"
 
 namespace {
-
-#define LDS __attribute__((address_space(3)))     /* the staged windows: say so, or reads through pointers picked at run time turn flat */
 
 constexpr int MT = 64;                            /* lanes of a workgroup: one wave */
 constexpr int REACH = OH_MO_REACH;
@@ -254,8 +251,6 @@ __global__ __launch_bounds__(MT) void motion_compensate_kernel(const OhMoCompArg
 
 } // namespace
 
-static_assert(sizeof(((OhMoSearchArgs *)nullptr)->cur) / sizeof(void *) == OH_CONV_MAX_PICS, "one launch's pairs");
-static_assert(sizeof(((OhMoCompArgs *)nullptr)->dst) / sizeof(((OhMoCompArgs *)nullptr)->dst[0]) == OH_CONV_MAX_PICS, "one launch's pictures");
 static_assert(sizeof(OhMoDev) == sizeof(OhMotionVector) && sizeof(OhMoDev) == 12 && sizeof(OhMoVec) == 4, "the vectors as the kernels store and load them");
 static_assert(search_lds<uint16_t>(16, OH_MOTION_MAX_RANGE, OH_MOTION_MAX_RANGE) <= 64 << 10, "LDS of one workgroup");
 static_assert(4 * OH_MOTION_MAX_RANGE + 3 < 256 && 4 * OH_MOTION_MAX_CENTRE + 4 * OH_MOTION_MAX_RANGE + 3 < 32768, "the key's fields; a vector is int16");

@@ -7,7 +7,7 @@
  *
  * Orientations 0 .. 3 (I[y][x] = S[VFLIP ? Hs - 1 - y : y][HFLIP ? Ws - 1 - x : x]): orient_rows_kernel, in the shape of reformat.hip.
  * One workgroup (256 lanes) per segment of OH_OR_SEG samples of one destination row; grid (segments, rows of all planes, pictures).
- *   1. stage    the source samples of the segment go to LDS as the aligned granules that cover them (convert_common.h: stage);
+ *   1. stage    the source samples of the segment go to LDS as the aligned granules that cover them (pics_common.h: stage);
  *   2. assemble each lane makes one aligned destination granule at a time: the 16 source bytes behind it lie anywhere in LDS, so it
  *               reads the five dwords that cover them and funnel-shifts them into four (v_alignbit_b32; the shift is the same for the
  *               whole workgroup); under HFLIP the four come out in reverse order with their samples reversed (v_perm_b32 / a rotate).
@@ -35,7 +35,7 @@
  * No second pass, no LDS image of the destination.  Templates on the stored sample type; the orientation is a uniform branch.
  */
 #include <algorithm>
-#include "convert_common.h"
+#include "pics_common.h"
 
 namespace {
 
@@ -56,17 +56,6 @@ __device__ __forceinline__ uint32_t reversed(uint32_t v)
         return __builtin_amdgcn_perm(0, v, 0x00010203);
     else
         return __builtin_amdgcn_perm(0, v, 0x01000302);
-}
-
-/* the plane (c, class q) and the row of it that row r of the grid stands for; per[q]: grid rows per plane of the class */
-__device__ __forceinline__ int grid_row(int r, const int per[2], int &c, int &q)
-{
-    c = 0; q = 0;
-    if (r < per[0])
-        return r;
-    r -= per[0];
-    q = 1; c = r < per[1] ? 1 : 2;
-    return r - (c - 1) * per[1];
 }
 
 template <typename T>
@@ -108,13 +97,13 @@ __global__ __launch_bounds__(THREADS) void orient_rows_kernel(const OhOrArgs a)
             if (hf)
                 v = uint4v{ reversed<T>(v[3]), reversed<T>(v[2]), reversed<T>(v[1]), reversed<T>(v[0]) };
         } else {                                                /* behind the image's last column */
-            T o[GS];
+            Samples<T> o;
 #pragma unroll
             for (int k = 0; k < GS; k++) {
                 const int xi = min(X + k, Wi - 1);
-                o[k] = in_s[base + (hf ? Wi - 1 - xi : xi) - lo];
+                o.s[k] = in_s[base + (hf ? Wi - 1 - xi : xi) - lo];
             }
-            __builtin_memcpy(&v, o, sizeof(v));
+            v = o.granule();
         }
         *(GLOBAL uint4v *)(dst + 16 * (uintptr_t)g) = v;
     }
@@ -242,13 +231,11 @@ __global__ __launch_bounds__(TILE_THREADS, sizeof(T) == 1 ? 6 : 4) void orient_t
                 const T *rows_s = (const T *)rows;
                 for (int m = 0; m < R && yb + m < dh; m++) {
                     const int yi = min(yb + m, Hi - 1), at = (base >> (SZ - 1)) + (vf ? Ws - 1 - yi : yi) - cmin;
-                    T o[G];
+                    Samples<T> o;
 #pragma unroll
                     for (int i = 0; i < G; i++)
-                        o[i] = rows_s[i * (PD * 4 / SZ) + at];
-                    uint4v v;
-                    __builtin_memcpy(&v, o, sizeof(v));
-                    *(GLOBAL uint4v *)(dst + (size_t)m * a.dpitch[c]) = v;
+                        o.s[i] = rows_s[i * (PD * 4 / SZ) + at];
+                    *(GLOBAL uint4v *)(dst + (size_t)m * a.dpitch[c]) = o.granule();
                 }
             }
         }
@@ -277,7 +264,6 @@ void launch(const OhOrArgs *a, int n, hipStream_t st)
 
 } // namespace
 
-static_assert(sizeof(((OhOrArgs *)nullptr)->dst) / sizeof(((OhOrArgs *)nullptr)->dst[0]) == OH_CONV_MAX_PICS, "one launch's pictures");
 static_assert(OH_OR_TILE == 64, "one wave per tile: a tile row of LDS per lane of the staging loop");
 static_assert(OH_OR_SEG % 16 == 0, "a segment is whole 16-byte granules of either sample type");
 

@@ -21,12 +21,10 @@
  * and destination; depth mode, filters and the format pair are uniform branches, the horizontal form one switch outside the loop.
  */
 #include <algorithm>
-#include "convert_common.h"
+#include "pics_common.h"
 #include "reformat_common.h"
 
 namespace {
-
-#define LDS __attribute__((address_space(3)))     /* the staged rows: say so, or reads through pointers picked at run time turn flat */
 
 enum { H_COPY, H_DOWN_POINT, H_DOWN_LIN, H_UP_NEAR, H_UP_LIN };     /* what a destination sample takes of one staged source row */
 
@@ -234,16 +232,9 @@ void launch(const OhRfArgs *a, int n, hipStream_t st)
 
 } // namespace
 
-static_assert(sizeof(((OhRfArgs *)nullptr)->dst) / sizeof(((OhRfArgs *)nullptr)->dst[0]) == OH_CONV_MAX_PICS, "one launch's pictures");
 static_assert(OH_RF_SEG % 32 == 0, "half a segment is whole 16-byte granules of either sample type");
 
 extern "C" void ohk_reformat(const OhRfArgs *a, int n, hipStream_t st)
 {
-    if (a->sbd == 8) {
-        if (a->dbd == 8) launch<uint8_t, uint8_t>(a, n, st);
-        else             launch<uint8_t, uint16_t>(a, n, st);
-    } else {
-        if (a->dbd == 8) launch<uint16_t, uint8_t>(a, n, st);
-        else             launch<uint16_t, uint16_t>(a, n, st);
-    }
+    with_sample_types(a->sbd, a->dbd, [&](auto ti, auto ts) { launch<decltype(ti), decltype(ts)>(a, n, st); });
 }

@@ -13,19 +13,15 @@
  * sample above 2^bi - 1 is looked up by its low bits, a matrix result is clipped to 0 .. 2^bo - 1, and the host has seen to it that no
  * pre-table entry lies above 2^bo - 1: no read leaves a table.
  */
-#include "../../include/ohevc_hip.h"
-#include "kernels_common.h"
+#include "pics_common.h"
 #include "remap_common.h"
 
 namespace {
 
-constexpr int THREADS = 256;
-
 template <typename TI, typename TS, bool IDENT>
 __global__ __launch_bounds__(THREADS) void remap_kernel(const OhRemapArgs a)
 {
-    constexpr int U = OH_LUT_UNIT, NI = U * (int)sizeof(TI) / 16, NO = U * (int)sizeof(TS) / 16;     /* granules of a unit, in and out */
-    constexpr int SBI = 8 * (int)sizeof(TI), PI = 4 / (int)sizeof(TI), SBO = 8 * (int)sizeof(TS), PO = 4 / (int)sizeof(TS);
+    constexpr int U = OH_LUT_UNIT, NI = Unit<TI>::N, NO = Unit<TS>::N;         /* granules of a unit, in and out */
     extern __shared__ __attribute__((aligned(16))) uint16_t tab[];               /* 3 << sbd pre entries, then 3 << dbd post entries */
     const int pic = blockIdx.y, t = threadIdx.x;
     const int ni = 1 << a.sbd, no = 1 << a.dbd;
@@ -63,11 +59,11 @@ __global__ __launch_bounds__(THREADS) void remap_kernel(const OhRemapArgs a)
             uint32_t s[3], o[3];
 #pragma unroll
             for (int c = 0; c < 3; c++)
-                s[c] = in[c][j / PI / 4][j / PI % 4] >> (SBI * (j % PI));        /* remap_sample keeps the low bits */
+                s[c] = unit_get<TI>(in[c], j);                  /* remap_sample keeps the low bits */
             remap_sample<IDENT>(pre0, pre1, pre2, post0, post1, post2, a.coeff, a.log2_denom, Mi, Mo, s, o);
 #pragma unroll
             for (int c = 0; c < 3; c++)
-                out[c][j / PO / 4][j / PO % 4] |= o[c] << (SBO * (j % PO));
+                unit_put<TS>(out[c], j, o[c]);
         }
 #pragma unroll
         for (int c = 0; c < 3; c++) {
@@ -91,17 +87,10 @@ void launch(const OhRemapArgs *a, int n, hipStream_t st)
 } // namespace
 
 static_assert(sizeof(OhRemapArgs) <= 4096, "kernel arguments");
-static_assert(sizeof(((OhRemapArgs *)nullptr)->dst) / sizeof(((OhRemapArgs *)nullptr)->dst[0]) == OH_CONV_MAX_PICS, "one launch's pictures");
 static_assert(OH_LUT_UNIT == 16, "a unit is whole granules of 8-bit and of 16-bit samples, and a 256-byte row holds whole units of both");
 static_assert(6 * OH_LUT_MAX * sizeof(uint16_t) <= 64 * 1024, "the six tables at 12 -> 12 bit fit the LDS of a workgroup");
 
 extern "C" void ohk_remap(const OhRemapArgs *a, int n, hipStream_t st)
 {
-    if (a->sbd == 8) {
-        if (a->dbd == 8) launch<uint8_t, uint8_t>(a, n, st);
-        else             launch<uint8_t, uint16_t>(a, n, st);
-    } else {
-        if (a->dbd == 8) launch<uint16_t, uint8_t>(a, n, st);
-        else             launch<uint16_t, uint16_t>(a, n, st);
-    }
+    with_sample_types(a->sbd, a->dbd, [&](auto ti, auto ts) { launch<decltype(ti), decltype(ts)>(a, n, st); });
 }

@@ -186,7 +186,6 @@ void launch(const OhResizeArgs *a, int n, int pad, hipStream_t st)
 
 } // namespace
 
-static_assert(sizeof(((OhResizeArgs *)nullptr)->src) / sizeof(((OhResizeArgs *)nullptr)->src[0]) == OH_RESIZE_MAX_PICS, "one launch set's pictures");
 static_assert(sizeof(OhResizeArgs) <= 4096, "kernel arguments");
 
 extern "C" void ohk_resize(const OhResizeArgs *a, int n, int pad, hipStream_t st)

@@ -22,25 +22,12 @@
  * Templates on the stored sample type, the mode (the affine form has no 64-bit division) and the filter.
  */
 #include <algorithm>
-#include "convert_common.h"
+#include "pics_common.h"
 #include "warp_common.h"
 
 namespace {
 
-#define LDS __attribute__((address_space(3)))     /* the staged box: say so, or reads through pointers picked at run time turn flat */
-
 constexpr int TW = WARP_TW, TH = WARP_TH;
-
-/* the plane (c, class q) and the tile row of it that row r of the grid stands for; per[q]: grid rows per plane of the class */
-__device__ __forceinline__ int grid_row(int r, const int per[2], int &c, int &q)
-{
-    c = 0; q = 0;
-    if (r < per[0])
-        return r;
-    r -= per[0];
-    q = 1; c = r < per[1] ? 1 : 2;
-    return r - (c - 1) * per[1];
-}
 
 template <typename T, bool PERSP, int FILTER>
 __global__ __launch_bounds__(THREADS) void warp_kernel(const OhWarpArgs a)
@@ -126,7 +113,6 @@ void launch(const OhWarpArgs *a, int n, hipStream_t st)
 
 } // namespace
 
-static_assert(sizeof(((OhWarpArgs *)nullptr)->dst) / sizeof(((OhWarpArgs *)nullptr)->dst[0]) == OH_CONV_MAX_PICS, "one launch's pictures");
 static_assert(WARP_TW * WARP_TH == 4 * THREADS && WARP_TW == 64, "a lane makes four samples of a row: sixteen lanes a tile row");
 static_assert(WARP_NEAREST == OH_WARP_NEAREST && WARP_BILINEAR == OH_WARP_BILINEAR && WARP_BICUBIC == OH_WARP_BICUBIC, "the filters' codes");
 static_assert(8 * WARP_LDS <= 160 << 10, "eight workgroups on a CU");
