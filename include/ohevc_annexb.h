@@ -176,6 +176,35 @@ typedef struct OhColourRemapSei {
  * leading zeros or one whose value does not fit its type — in any colour remapping message of the unit, selected or not. */
 int oh_sei_colour_remap(const uint8_t *nal, size_t size, int64_t id, OhColourRemapSei *out);
 
+/* The frame packing arrangement message (payload type 45): the picture holds the two views of a stereo pair — side by side, one above
+ * the other, or one after the other in time.  The layout is the one the reference walks (decode_nal_sei_frame_packing_arrangement,
+ * hevc_sei.c:52-75; it keeps arrangement_type, quincunx_sampling_flag and content_interpretation_type and skips the rest).  Bits, MSB
+ * first, of the unescaped payload: frame_packing_arrangement_id ue(v), cancel_flag u(1); unless cancelled arrangement_type u(7),
+ * quincunx_sampling_flag u(1), content_interpretation_type u(6), spatial_flipping_flag, frame0_flipped_flag, field_views_flag,
+ * current_frame_is_frame0_flag, frame0_self_contained_flag, frame1_self_contained_flag u(1) each; only where quincunx_sampling_flag is
+ * 0 and arrangement_type is not 5 frame0_grid_position_x, frame0_grid_position_y, frame1_grid_position_x, frame1_grid_position_y
+ * u(4) each; reserved_byte u(8), persistence_flag u(1); then, cancelled or not, upsampled_aspect_ratio_flag u(1).  Every field is kept
+ * as coded; what lies behind the cancel flag, and grid positions that are not coded, are 0.  oh_packing_from_sei (ohevc_hip.h) turns
+ * the message into what oh_pics_unpack / oh_pics_pack take. */
+typedef struct OhFramePackingSei {
+    int32_t present;                  /* a message was found */
+    int32_t cancel;                   /* frame_packing_arrangement_cancel_flag */
+    uint32_t id;                      /* frame_packing_arrangement_id */
+    int32_t arrangement_type;         /* 3 side by side, 4 top-bottom, 5 temporal interleaving */
+    int32_t quincunx_sampling;
+    int32_t content_interpretation_type;      /* 0 unspecified, 1 frame 0 is the left view, 2 frame 0 is the right view */
+    int32_t spatial_flipping, frame0_flipped, field_views, current_frame_is_frame0, frame0_self_contained, frame1_self_contained;
+    int32_t frame0_grid_position_x, frame0_grid_position_y, frame1_grid_position_x, frame1_grid_position_y;
+    int32_t reserved_byte;
+    int32_t persistence;
+    int32_t upsampled_aspect_ratio;
+} OhFramePackingSei;
+/* nal[0 .. size): one (escaped) SEI NAL unit, header first.  The same message walk as oh_sei_colour_remap.  The message counts in a
+ * prefix SEI only; in a suffix SEI it is passed over.  The last message of the unit counts.  Returns 1 found, 0 none (*out is zero),
+ * or -1 (*out is zero): not an SEI NAL unit, a message that runs past the unit, a field that lies past the end of the payload, a
+ * ue(v) code of more than 32 leading zeros or one whose value does not fit 32 bits — in any frame packing message of the unit. */
+int oh_sei_frame_packing(const uint8_t *nal, size_t size, OhFramePackingSei *out);
+
 #ifdef __cplusplus
 }
 #endif

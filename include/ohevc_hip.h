@@ -851,6 +851,80 @@ struct OhColourRemapSei;
 int oh_remap_from_sei(const struct OhColourRemapSei *sei, uint16_t tables[6][4096], OhRemap *out);
 int oh_remap_luts(const OhRemap *r, uint16_t out[3][4096]);
 
+/* Frame packing: a finished picture that holds the two views of a stereo pair, as the frame packing arrangement SEI (ohevc_annexb.h:
+ * oh_sei_frame_packing) describes it, becomes two finished pictures, one per view, and two views become a packed picture (DESIGN.md
+ * §3s; the tests check every coded plane bit for bit against tests/packing_model.py).  Everything is in integers, per plane and in the
+ * plane's own coordinates.  In a plane of the packed picture, view v (constituent frame v) occupies the rectangle R_v: the left half
+ * (OH_PACK_SIDE_BY_SIDE) or the top half (OH_PACK_TOP_BOTTOM) for v = 0, the other half for v = 1.  C_v[y][x] is R_v read with the
+ * flip undone: with flip[v], columns mirrored inside R_v (side by side) or rows mirrored inside R_v (top-bottom).  The size of the
+ * views picks the mode.  With packed pictures of W x H luma samples (shifts hs, vs of the chroma planes):
+ *   half size   (W / 2) x H side by side, W x (H / 2) top-bottom: D_v = C_v, with or without quincunx.  oh_pics_pack with half-size
+ *               views is the exact inverse: it places the views and re-applies the flips.
+ *   full size   W x H, no quincunx: a 1-D up-sampling by two along the packed axis (x side by side, y top-bottom) on the phase the grid
+ *               position gives; the other axis is copied.  Taps c[16][8] for luma and c[16][4] for chroma: the 16-phase SHVC tables.
+ *               With g = grid_x[v] (side by side) or grid_y[v] (top-bottom), output index Z on the packed axis has the position p, in
+ *               1/16 of the spacing of the stored samples: p = 8 Z - g where the plane is not sub-sampled on the packed axis;
+ *               p = (16 Z - g + 1) >> 1 on a sub-sampled horizontal axis (co-sited chroma); p = (16 Z - g - 3) >> 1 on a sub-sampled
+ *               vertical axis (chroma midway between luma rows, chroma_sample_loc_type 0); >> floors.  i = p >> 4, phase = p & 15,
+ *               S = sum_k c[phase][k] C_v[clamp(i + k - 3, 0, N - 1)] with 8 taps (k - 1 with 4 taps), N the view's own stored samples
+ *               on that axis — a tap never reaches across the seam into the other view —, D = clip((S + 32) >> 6, 0, 2^bd - 1).
+ *               The other grid component (grid_y side by side, grid_x top-bottom) is carried and not applied.
+ *   quincunx    this project's reading of the lattice: side by side C_v[y][x] is the full-resolution sample (2 x + ((y + v) & 1), y),
+ *               top-bottom (x, 2 y + ((x + v) & 1)); frame 0 holds (0, 0).  Full-size views: lattice samples are copied, every other
+ *               sample is (L + R + U + D + 2) >> 2 of its four lattice neighbours, a neighbour outside the plane replaced by the
+ *               opposite one.  oh_pics_pack with quincunx takes full-size views and point-samples the lattice: it does not pre-filter.
+ * A view's picture has the packed pictures' params but for its size, whose sides are rounded up to the minimum coding block
+ * (oh_packing_view_size): the view is the top-left window of it, and the rest of the coded planes replicates the window's last column
+ * and last row, as in oh_pics_orient.  Where the half size rounds up to the full size (a packed side of one minimum coding block), the
+ * full size is meant.  oh_pics_unpack: view0_ids or view1_ids may be null, that view is then not made.  Both calls read finished
+ * halves, write half 0 of each destination and mark it finished, like oh_pics_orient; enqueued on the engine stream, they return
+ * without waiting.  n == 0: OH_OK after the checks of the descriptor.  More than OH_PK_MAX_PICS = 32 packed pictures are split into
+ * several launches.
+ * OH_E_ARG, nothing written: a null e, pk or packed id array, both view arrays null (oh_pics_pack: either), a negative n; an
+ * arrangement other than 3 or 4, quincunx or a flip outside 0 / 1, a grid position outside 0 .. 15; an unknown picture; params that
+ * differ among the packed pictures or among the views; a picture that is both source and destination, or a destination listed twice;
+ * a packed width that is no multiple of 2 << hs (side by side) or height that is no multiple of 2 << vs (top-bottom): each half is a
+ * whole number of chroma samples; views that are of neither size; oh_pics_pack with quincunx and half-size views.
+ * OH_E_UNSUPPORTED, nothing written: views of another bit depth or chroma format than the packed pictures (oh_pics_reformat first);
+ * oh_pics_pack without quincunx and full-size views: the anti-aliased 2 : 1 is oh_pics_resize's, then pack the halves. */
+enum { OH_PACK_SIDE_BY_SIDE = 3, OH_PACK_TOP_BOTTOM = 4 };     /* frame_packing_arrangement_type */
+enum { OH_PK_MAX_PICS = 32 };
+typedef struct OhPacking {
+    int32_t arrangement;              /* OH_PACK_SIDE_BY_SIDE or OH_PACK_TOP_BOTTOM */
+    int32_t quincunx;                 /* 0 / 1 */
+    int32_t flip[2];                  /* view v is stored mirrored: horizontally side by side, vertically top-bottom */
+    int32_t grid_x[2], grid_y[2];     /* 0 .. 15: the position of view v's top-left sample, in 1/16 of the stored sample spacing */
+    int32_t content_interpretation;   /* carried: 1 frame 0 is the left view, 2 frame 1 is; changes no sample */
+} OhPacking;
+int oh_pics_unpack(OhEngine *e, const int *src_ids, const int *view0_ids, const int *view1_ids, int n, const OhPacking *pk);
+int oh_pics_pack(OhEngine *e, const int *view0_ids, const int *view1_ids, const int *dst_ids, int n, const OhPacking *pk);
+/* host only: the pieces of the definition above, which the kernels share (csrc/packing_common.h).
+ *   oh_packing_from_sei     the descriptor of a message: arrangement types 3 and 4; flip[v] is 1 for the constituent frame that is stored
+ *                           mirrored (spatial_flipping_flag, and frame0_flipped_flag names frame v).  OH_E_UNSUPPORTED: type 5 (temporal
+ *                           interleaving: nothing to unpack, current_frame_is_frame0_flag says which view a picture is), types 0 .. 2
+ *                           and above 5, which HEVC does not define, field_views_flag; oh_packing_unsupported says which in words
+ *                           ("" for a message that is supported).  OH_E_ARG: a null pointer, a message that is absent or cancelled,
+ *                           a grid position outside 0 .. 15.  out is untouched then
+ *   oh_packing_view_size    the params of a view of half (full 0) or full (full 1) size of packed pictures of params `packed`.
+ *                           OH_E_ARG: a null pointer, full outside 0 / 1, what the calls refuse of the descriptor and the packed size
+ *   oh_packing_sample       *out: sample (x, y) of coded plane `plane` of view `view` of that size, from `samples`, the packed picture's
+ *                           plane `plane` (uint8_t at 8 bit, else uint16_t; `stride` samples between rows).  OH_E_ARG as above, or a
+ *                           position outside the view's coded plane
+ *   oh_packing_pack_sample  *out: sample (x, y) of plane `plane` of the packed picture from the same plane of the two views (half size,
+ *                           with quincunx full size; `stride` samples between the rows of either)
+ *   oh_packing_views        *left, *right: the constituent frame that is the left / the right view: content_interpretation 1, frame 0
+ *                           is the left view; 2, frame 1 is.  Returns 1, or 0 (nothing written) for a null pointer and where the
+ *                           interpretation is unspecified (0) or reserved */
+struct OhFramePackingSei;
+int oh_packing_from_sei(const struct OhFramePackingSei *sei, OhPacking *out);
+const char *oh_packing_unsupported(const struct OhFramePackingSei *sei);
+int oh_packing_view_size(const OhPacking *pk, const OhPicParams *packed, int full, OhPicParams *view);
+int oh_packing_sample(const OhPacking *pk, const OhPicParams *packed, int full, int view, int plane, int x, int y, const void *samples,
+                      int stride, int32_t *out);
+int oh_packing_pack_sample(const OhPacking *pk, const OhPicParams *packed, int plane, int x, int y, const void *view0, const void *view1,
+                           int stride, int32_t *out);
+int oh_packing_views(const OhPacking *pk, int *left, int *right);
+
 /* Motion: a block-matching search between two finished pictures and the motion-compensated prediction that such a field describes, in
  * HEVC's quarter-sample units with HEVC's interpolation filters, so that a vector means what it means to an HEVC decoder (DESIGN.md
  * §3o; the tests check every field and every plane bit for bit against tests/motion_model.py, which is held against the oracle's

@@ -1,4 +1,4 @@
-"""ctypes view of include/ohevc_annexb.h (libohevc_host.so): access-unit splitter, NAL scan, NAL unescape, picture-hash SEI, HDR SEIs, display-orientation SEI, picture timing SEI, film grain SEI, colour remapping SEI."""
+"""ctypes view of include/ohevc_annexb.h (libohevc_host.so): access-unit splitter, NAL scan, NAL unescape, picture-hash SEI, HDR SEIs, display-orientation SEI, picture timing SEI, film grain SEI, colour remapping SEI, frame packing SEI."""
 import ctypes as C
 import os
 
@@ -61,6 +61,17 @@ class OhColourRemapSei(C.Structure):
                 ("post_lut_coded_value", (C.c_uint16 * CRI_MAX_PIVOTS) * 3), ("post_lut_target_value", (C.c_uint16 * CRI_MAX_PIVOTS) * 3)]
 
 
+_FP_FLAGS = ("spatial_flipping", "frame0_flipped", "field_views", "current_frame_is_frame0", "frame0_self_contained", "frame1_self_contained")
+_FP_GRID = ("frame0_grid_position_x", "frame0_grid_position_y", "frame1_grid_position_x", "frame1_grid_position_y")
+
+
+class OhFramePackingSei(C.Structure):
+    _fields_ = ([("present", C.c_int32), ("cancel", C.c_int32), ("id", C.c_uint32), ("arrangement_type", C.c_int32),
+                 ("quincunx_sampling", C.c_int32), ("content_interpretation_type", C.c_int32)] +
+                [(k, C.c_int32) for k in _FP_FLAGS + _FP_GRID] +
+                [("reserved_byte", C.c_int32), ("persistence", C.c_int32), ("upsampled_aspect_ratio", C.c_int32)])
+
+
 _lib = None
 
 
@@ -93,6 +104,8 @@ def lib():
         L.oh_sei_film_grain.restype = C.c_int
         L.oh_sei_colour_remap.argtypes = [C.c_char_p, C.c_size_t, C.c_int64, C.POINTER(OhColourRemapSei)]
         L.oh_sei_colour_remap.restype = C.c_int
+        L.oh_sei_frame_packing.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(OhFramePackingSei)]
+        L.oh_sei_frame_packing.restype = C.c_int
         _lib = L
     return _lib
 
@@ -349,4 +362,58 @@ def colour_remap_to_struct(d):
         for c in range(3):
             for i in range(3):
                 r.coeffs[c][i] = int(matrix[1][c][i])
+    return r
+
+
+def frame_packing_struct(nal):
+    """None, or the OhFramePackingSei of the last frame packing arrangement message (payload type 45) of one prefix SEI NAL unit"""
+    r = OhFramePackingSei()
+    rc = lib().oh_sei_frame_packing(nal, len(nal), C.byref(r))
+    if rc < 0:
+        raise ValueError("malformed SEI NAL unit")
+    return r if rc else None
+
+
+def frame_packing(nal):
+    """None, or a dict of the frame packing arrangement message (payload type 45) of one prefix SEI NAL unit (oh_sei_frame_packing),
+    every field as coded: "id", "cancel" (bool; a cancelled message holds nothing else but "upsampled_aspect_ratio"),
+    "arrangement_type" (3 side by side, 4 top-bottom, 5 temporal interleaving), "quincunx_sampling" (bool),
+    "content_interpretation_type", the flags "spatial_flipping", "frame0_flipped", "field_views", "current_frame_is_frame0",
+    "frame0_self_contained", "frame1_self_contained" (bool), "grid": ((frame0 x, y), (frame1 x, y)), zeros where the message does not
+    code them, "reserved_byte", "persistence" (bool) and "upsampled_aspect_ratio" (bool).  engine.packing_from_sei turns the dict into
+    what Engine.pics_unpack / pics_pack take."""
+    r = frame_packing_struct(nal)
+    if r is None:
+        return None
+    if r.cancel:
+        return dict(id=int(r.id), cancel=True, upsampled_aspect_ratio=bool(r.upsampled_aspect_ratio))
+    d = dict(id=int(r.id), cancel=False, arrangement_type=int(r.arrangement_type), quincunx_sampling=bool(r.quincunx_sampling),
+             content_interpretation_type=int(r.content_interpretation_type))
+    for k in _FP_FLAGS:
+        d[k] = bool(getattr(r, k))
+    d["grid"] = ((int(r.frame0_grid_position_x), int(r.frame0_grid_position_y)), (int(r.frame1_grid_position_x), int(r.frame1_grid_position_y)))
+    d.update(reserved_byte=int(r.reserved_byte), persistence=bool(r.persistence), upsampled_aspect_ratio=bool(r.upsampled_aspect_ratio))
+    return d
+
+
+def frame_packing_to_struct(d):
+    """the OhFramePackingSei that frame_packing would have read the dict d from"""
+    r = OhFramePackingSei()
+    r.present, r.id = 1, int(d.get("id", 0))
+    r.upsampled_aspect_ratio = int(bool(d.get("upsampled_aspect_ratio", False)))
+    if d.get("cancel"):
+        r.cancel = 1
+        return r
+    r.arrangement_type = int(d["arrangement_type"])
+    r.quincunx_sampling = int(bool(d.get("quincunx_sampling", False)))
+    r.content_interpretation_type = int(d.get("content_interpretation_type", 0))
+    for k in _FP_FLAGS:
+        setattr(r, k, int(bool(d.get(k, False))))
+    grid = d.get("grid", ((0, 0), (0, 0)))
+    for k, v in zip(_FP_GRID, (grid[0][0], grid[0][1], grid[1][0], grid[1][1])):
+        if not 0 <= int(v) <= 15:
+            raise ValueError("frame packing: a grid position is a value of 4 bits")
+        setattr(r, k, int(v))
+    r.reserved_byte = int(d.get("reserved_byte", 0))
+    r.persistence = int(bool(d.get("persistence", False)))
     return r

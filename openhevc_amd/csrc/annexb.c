@@ -1,5 +1,5 @@
 /*
- * annexb.c — Annex-B byte stream: access-unit splitter, NAL scan, NAL unescape, picture-hash SEI, HDR SEIs, display-orientation, picture timing, film grain and colour remapping SEIs.  See include/ohevc_annexb.h for the
+ * annexb.c — Annex-B byte stream: access-unit splitter, NAL scan, NAL unescape, picture-hash SEI, HDR SEIs, display-orientation, picture timing, film grain, colour remapping and frame packing SEIs.  See include/ohevc_annexb.h for the
  * reference lines each entry point follows.  Plain C, no dependencies.
  */
 #include "../../include/ohevc_annexb.h"
@@ -490,6 +490,53 @@ int oh_sei_colour_remap(const uint8_t *nal, size_t size, int64_t id, OhColourRem
     struct remap_ctx r = { out, id };
     memset(out, 0, sizeof(*out));
     if (sei_walk(nal, size, remap_msg, &r) < 0) {
+        memset(out, 0, sizeof(*out));
+        return -1;
+    }
+    return out->present;
+}
+
+static int packing_msg(void *ctx, int nut, unsigned type, const uint8_t *q, unsigned len)
+{
+    OhFramePackingSei *out = (OhFramePackingSei *)ctx;
+    if (nut != NAL_SEI_PREFIX || type != 45)                  /* D.2.16 frame_packing_arrangement, as hevc_sei.c:52-75 walks it */
+        return 0;
+    struct bit_reader b = { q, (size_t)len * 8, 0, 0 };
+    OhFramePackingSei m;
+    memset(&m, 0, sizeof(m));
+    m.present = 1;
+    m.id = get_ue(&b);
+    m.cancel = (int32_t)get_bits(&b, 1);
+    if (!m.cancel) {
+        m.arrangement_type = (int32_t)get_bits(&b, 7);
+        m.quincunx_sampling = (int32_t)get_bits(&b, 1);
+        m.content_interpretation_type = (int32_t)get_bits(&b, 6);
+        m.spatial_flipping = (int32_t)get_bits(&b, 1);
+        m.frame0_flipped = (int32_t)get_bits(&b, 1);
+        m.field_views = (int32_t)get_bits(&b, 1);
+        m.current_frame_is_frame0 = (int32_t)get_bits(&b, 1);
+        m.frame0_self_contained = (int32_t)get_bits(&b, 1);
+        m.frame1_self_contained = (int32_t)get_bits(&b, 1);
+        if (!m.quincunx_sampling && m.arrangement_type != 5) {
+            m.frame0_grid_position_x = (int32_t)get_bits(&b, 4);
+            m.frame0_grid_position_y = (int32_t)get_bits(&b, 4);
+            m.frame1_grid_position_x = (int32_t)get_bits(&b, 4);
+            m.frame1_grid_position_y = (int32_t)get_bits(&b, 4);
+        }
+        m.reserved_byte = (int32_t)get_bits(&b, 8);
+        m.persistence = (int32_t)get_bits(&b, 1);
+    }
+    m.upsampled_aspect_ratio = (int32_t)get_bits(&b, 1);
+    if (b.bad)
+        return -1;
+    *out = m;                                                 /* the last message of the unit counts */
+    return 0;
+}
+
+int oh_sei_frame_packing(const uint8_t *nal, size_t size, OhFramePackingSei *out)
+{
+    memset(out, 0, sizeof(*out));
+    if (sei_walk(nal, size, packing_msg, out) < 0) {
         memset(out, 0, sizeof(*out));
         return -1;
     }

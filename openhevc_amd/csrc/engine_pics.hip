@@ -1620,6 +1620,118 @@ extern "C" int oh_pics_colour_remap(OhEngine *e, const int *src_ids, const int *
     });
 }
 
+/* ---------------- frame packing (packing.hip) ---------------- */
+/* what both calls ask of the packed pictures (P0) and the views (v0): one format, and views of the half or the full size.  *full: which;
+ * where the two sizes are one, the full size */
+static int packing_sizes(OhEngine *e, const char *who, const OhPacking *pk, const Pic *P0, const Pic *v0, int *full)
+{
+    const OhPicParams &pp = P0->p, &vp = v0->p;
+    OH_TRY(same_format(e, who, "views", vp, "packed pictures", pp));
+    PkPlane pl[2];
+    OhPicParams size[2];
+    std::string why;
+    for (int f = 0; f < 2; f++)
+        if (const int rc = packing_geometry(pk, &pp, f, pl, &size[f], &why))
+            return refuse(e, rc, who, why);
+    for (int f = 1; f >= 0; f--)
+        if (vp.width == size[f].width && vp.height == size[f].height) {
+            *full = f;
+            return OH_OK;
+        }
+    FAIL(e, OH_E_ARG, "%s: views of %dx%d, packed pictures of %dx%d (half size %dx%d, full size %dx%d)", who, vp.width, vp.height, pp.width,
+         pp.height, size[0].width, size[0].height, size[1].width, size[1].height);
+}
+
+static void packing_args(const OhPacking *pk, const Pic *P0, const Pic *v0, int full, OhPkArgs *a)
+{
+    memset(a, 0, sizeof(*a));
+    std::string why;
+    (void)packing_geometry(pk, &P0->p, full, a->pl, nullptr, &why);
+    a->np = n_planes(P0->p); a->bd = P0->p.bit_depth;
+    row_pitches(P0, a->np, a->ppitch);
+    row_pitches(v0, a->np, a->vpitch);
+    for (int v = 0; v < 2; v++) {
+        a->flip[v] = pk->flip[v];
+        a->g[v] = pk->arrangement == OH_PACK_SIDE_BY_SIDE ? pk->grid_x[v] : pk->grid_y[v];
+    }
+}
+
+extern "C" int oh_pics_unpack(OhEngine *e, const int *src_ids, const int *view0_ids, const int *view1_ids, int n, const OhPacking *pk)
+{
+    const char *who = "oh_pics_unpack";
+    if (!e || n < 0 || !pk || (n && !src_ids) || (!view0_ids && !view1_ids))
+        return OH_E_ARG;
+    std::string why;
+    if (packing_check(pk, &why))                                /* also of a call without pictures */
+        return refuse(e, OH_E_ARG, who, why);
+    if (!n)
+        return OH_OK;
+    std::vector<int> views;
+    if (view0_ids) views.insert(views.end(), view0_ids, view0_ids + n);
+    if (view1_ids) views.insert(views.end(), view1_ids, view1_ids + n);
+    const Pic *P0, *v0;
+    OH_TRY(srcs_dsts(e, who, src_ids, n, views.data(), (int)views.size(), &P0, &v0));
+    int full = 0;
+    OH_TRY(packing_sizes(e, who, pk, P0, v0, &full));
+    OhPkArgs a;
+    packing_args(pk, P0, v0, full, &a);
+    class_sizes(v0, a.np, a.dw, a.dh);
+    a.views = (view0_ids ? 1 : 0) | (view1_ids ? 2 : 0);
+    const int *const view_ids[2] = { view0_ids, view1_ids };
+    return launch_sets(e, n, [&](int i0, int m) {
+        for (int i = 0; i < m; i++) {
+            read_planes(get_pic(e, src_ids[i0 + i]), a.np, a.packed[i]);
+            for (int v = 0; v < 2; v++)
+                if (view_ids[v])
+                    write_planes(get_pic(e, view_ids[v][i0 + i]), a.np, a.view[v][i]);
+        }
+        ohk_unpack(&a, m, e->stream);
+    }, OH_PK_MAX_PICS);
+}
+
+extern "C" int oh_pics_pack(OhEngine *e, const int *view0_ids, const int *view1_ids, const int *dst_ids, int n, const OhPacking *pk)
+{
+    const char *who = "oh_pics_pack";
+    if (!e || n < 0 || !pk || (n && (!view0_ids || !view1_ids || !dst_ids)))
+        return OH_E_ARG;
+    std::string why;
+    if (packing_check(pk, &why))
+        return refuse(e, OH_E_ARG, who, why);
+    if (!n)
+        return OH_OK;
+    std::vector<int> views(view0_ids, view0_ids + n);
+    views.insert(views.end(), view1_ids, view1_ids + n);
+    const Pic *v0, *P0;
+    OH_TRY(srcs_dsts(e, who, views.data(), 2 * n, dst_ids, n, &v0, &P0));
+    int full = 0;
+    OH_TRY(packing_sizes(e, who, pk, P0, v0, &full));
+    if (!pk->quincunx) {
+        /* where the half size rounds up to the full size, the views are taken as halves: there is no other way to pack them */
+        PkPlane pl[2];
+        OhPicParams half;
+        (void)packing_geometry(pk, &P0->p, 0, pl, &half, &why);
+        if (v0->p.width == half.width && v0->p.height == half.height)
+            full = 0;
+        else
+            FAIL(e, OH_E_UNSUPPORTED, "%s: full-size views of %dx%d without quincunx sampling: packing them needs the anti-aliased 2 : 1, which is "
+                 "oh_pics_resize's; resize, then pack the halves", who, v0->p.width, v0->p.height);
+    } else if (!full)
+        FAIL(e, OH_E_ARG, "%s: half-size views of %dx%d with quincunx sampling: the lattice is taken from full-size views of %dx%d", who,
+             v0->p.width, v0->p.height, P0->p.width, P0->p.height);
+    OhPkArgs a;
+    packing_args(pk, P0, v0, full, &a);
+    class_sizes(P0, a.np, a.dw, a.dh);
+    a.views = 3;
+    return launch_sets(e, n, [&](int i0, int m) {
+        for (int i = 0; i < m; i++) {
+            read_planes(get_pic(e, view0_ids[i0 + i]), a.np, a.view[0][i]);
+            read_planes(get_pic(e, view1_ids[i0 + i]), a.np, a.view[1][i]);
+            write_planes(get_pic(e, dst_ids[i0 + i]), a.np, a.packed[i]);
+        }
+        ohk_pack(&a, m, e->stream);
+    }, OH_PK_MAX_PICS);
+}
+
 /* ---------------- motion search and compensation (motion.hip) ---------------- */
 extern "C" int oh_pics_motion(OhEngine *e, const int *cur_ids, const int *ref_ids, int n, const OhMotionSearch *ms, OhMotionVector *out)
 {

@@ -9,6 +9,7 @@
 #include "../../include/ohevc_hip.h"
 #include "dev_frame.h"
 #include "upblock.h"
+#include "packing_common.h"
 
 /* the reference's CTB up-sampling path (upsample.hip: upsample_block_kernel): planes and their geometry (g[0] luma, g[1] chroma) */
 struct OhUpBlkArgs {
@@ -299,6 +300,22 @@ struct OhRemapArgs {
     int32_t         rows;            /* picture rows per workgroup */
 };
 
+/* frame packing (packing.hip): the planes of the packed pictures and of the two views of one launch by value in the kernel
+ * arguments; every packed picture of a launch has one geometry, every view another.  Two plane classes (0 luma, 1 chroma).
+ *   ohk_unpack   packed: the finished halves; view[v]: half 0 of the views that `views` names (bit v)
+ *   ohk_pack     view[0], view[1]: the finished halves; packed: half 0 of the destinations */
+enum { OH_PK_SEG_BYTES = 4096 };     /* bytes of one destination row per workgroup: a 16-byte granule per lane */
+struct OhPkArgs {
+    void       *packed[OH_PK_MAX_PICS][3];  /* pictures x planes: 32 packed pictures and their 64 views keep the arguments below 4 KiB */
+    void       *view[2][OH_PK_MAX_PICS][3]; /* view x pictures x planes */
+    int32_t     ppitch[3], vpitch[3];/* bytes between rows of each plane: packed pictures, views */
+    int32_t     dw[2], dh[2];        /* coded size of the destination planes: the views (ohk_unpack), the packed pictures (ohk_pack) */
+    PkPlane     pl[2];               /* packing_common.h: the geometry of each plane class */
+    int32_t     flip[2], g[2];       /* per view: stored mirrored; the grid position on the packed axis */
+    int32_t     np, bd;              /* planes: 1 or 3; bit depth */
+    int32_t     views;               /* ohk_unpack: bit v: view v is made */
+};
+
 /* motion search and compensation (motion.hip): the finished planes of the pictures of one launch by value in the kernel
  * arguments; every picture of a launch has the same geometry.  The centres, the field and the results of the launch's first picture lie
  * in device memory that the engine owns and fills or clears on the stream in front of the launch. */
@@ -397,6 +414,10 @@ void ohk_lut(const OhLutArgs *a, int n, hipStream_t st);
 void ohk_grain(const OhGrainArgs *a, int n, hipStream_t st);
 /* n sources of a.src remapped into the n destinations of a.dst */
 void ohk_remap(const OhRemapArgs *a, int n, hipStream_t st);
+/* n packed pictures of a.packed unpacked into the views of a.view that a.views names */
+void ohk_unpack(const OhPkArgs *a, int n, hipStream_t st);
+/* n pairs of views of a.view packed into the n pictures of a.packed */
+void ohk_pack(const OhPkArgs *a, int n, hipStream_t st);
 /* the blocks of n pairs of a.cur / a.ref searched into a.res[0 .. n bw bh) */
 void ohk_motion_search(const OhMoSearchArgs *a, int n, hipStream_t st);
 /* n pictures of a.ref compensated by a.field[0 .. n bw bh) into the n destinations of a.dst */

@@ -31,5 +31,8 @@ OH_INTERNAL int lut_check(const OhLut *lut, int sbd, int dbd, int np, std::strin
 OH_INTERNAL int grain_check(const OhGrain *g, int np, std::string *why);
 OH_INTERNAL int remap_check(const OhRemap *r, std::string *why);
 OH_INTERNAL bool remap_is_identity(const OhRemap *r);
+struct PkPlane;
+OH_INTERNAL int packing_check(const OhPacking *pk, std::string *why);
+OH_INTERNAL int packing_geometry(const OhPacking *pk, const OhPicParams *packed, int full, PkPlane pl[2], OhPicParams *view, std::string *why);
 
 #endif

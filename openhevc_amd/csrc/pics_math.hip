@@ -1,7 +1,7 @@
 /*
  * pics_math.hip — the host arithmetic of the picture services (engine_pics.hip), with neither an engine nor a device: image sizes and
  * crop windows, the ids of a call (destinations apart from sources, neighbours in time), the integers of the RGB conversions, the colour tables of the HDR forms, light-level bins and percentiles, the SSIM window
- * and PSNR, the resize taps, the compose formulas, the reformat quantisation, the orientations' group, the pic_struct table, the adaptive deinterlacer's sample, the filters' taps and samples, and what follows from a histogram's bins with the table builders, the motion helpers, the warp's positions, taps and map builders, the film grain's hash, patterns, tables and samples, and the colour remapping's curves, samples and per-plane tables.  No kernel, no HIP runtime call: tests/pics_math_check.cpp runs it under sanitizers.
+ * and PSNR, the resize taps, the compose formulas, the reformat quantisation, the orientations' group, the pic_struct table, the adaptive deinterlacer's sample, the filters' taps and samples, and what follows from a histogram's bins with the table builders, the motion helpers, the warp's positions, taps and map builders, the film grain's hash, patterns, tables and samples, the colour remapping's curves, samples and per-plane tables, and the frame packing's descriptor, view sizes and samples.  No kernel, no HIP runtime call: tests/pics_math_check.cpp runs it under sanitizers.
  */
 #include <stdio.h>
 #include <string.h>
@@ -20,6 +20,7 @@
 #include "warp_common.h"
 #include "grain_common.h"
 #include "remap_common.h"
+#include "packing_common.h"
 #include "../../include/ohevc_annexb.h"
 
 static bool depth_ok(int bit_depth) { return bit_depth == 8 || bit_depth == 9 || bit_depth == 10 || bit_depth == 12; }
@@ -1549,5 +1550,170 @@ extern "C" int oh_remap_luts(const OhRemap *r, uint16_t out[3][4096])
             out[c][v] = r->post[c][remap_row(k, p, p, p, r->log2_denom, Mo)];
         }
     }
+    return OH_OK;
+}
+
+/* ---------------- frame packing (packing.hip): the host-only helpers and what oh_pics_unpack / oh_pics_pack check ---------------- */
+extern "C" int oh_packing_from_sei(const OhFramePackingSei *sei, OhPacking *out)
+{
+    if (!sei || !out || !sei->present || sei->cancel)
+        return OH_E_ARG;
+    if (sei->arrangement_type != OH_PACK_SIDE_BY_SIDE && sei->arrangement_type != OH_PACK_TOP_BOTTOM)
+        return OH_E_UNSUPPORTED;                                /* 5: nothing to unpack; the others: not defined by HEVC */
+    if (sei->field_views)
+        return OH_E_UNSUPPORTED;
+    OhPacking pk;
+    memset(&pk, 0, sizeof(pk));
+    pk.arrangement = sei->arrangement_type;
+    pk.quincunx = sei->quincunx_sampling != 0;
+    pk.flip[0] = sei->spatial_flipping && sei->frame0_flipped;
+    pk.flip[1] = sei->spatial_flipping && !sei->frame0_flipped;
+    pk.grid_x[0] = sei->frame0_grid_position_x; pk.grid_y[0] = sei->frame0_grid_position_y;
+    pk.grid_x[1] = sei->frame1_grid_position_x; pk.grid_y[1] = sei->frame1_grid_position_y;
+    pk.content_interpretation = sei->content_interpretation_type;
+    std::string why;
+    if (packing_check(&pk, &why))
+        return OH_E_ARG;
+    *out = pk;
+    return OH_OK;
+}
+
+extern "C" const char *oh_packing_unsupported(const OhFramePackingSei *sei)
+{
+    if (!sei || !sei->present || sei->cancel)
+        return "";
+    if (sei->arrangement_type == 5)
+        return "temporal interleaving: there is nothing to unpack, current_frame_is_frame0_flag says which view a picture is";
+    if (sei->arrangement_type != OH_PACK_SIDE_BY_SIDE && sei->arrangement_type != OH_PACK_TOP_BOTTOM)
+        return "an arrangement type that HEVC does not define (3 side by side, 4 top-bottom, 5 temporal interleaving)";
+    if (sei->field_views)
+        return "field_views_flag: the views as fields of one frame are not unpacked";
+    return "";
+}
+
+/* what oh_pics_unpack / oh_pics_pack check of the OhPacking itself */
+int packing_check(const OhPacking *pk, std::string *why)
+{
+    char buf[256];
+    if (pk->arrangement != OH_PACK_SIDE_BY_SIDE && pk->arrangement != OH_PACK_TOP_BOTTOM) {
+        snprintf(buf, sizeof(buf), "arrangement %d (3 side by side, 4 top-bottom)", pk->arrangement); *why = buf; return OH_E_ARG;
+    }
+    if ((pk->quincunx | pk->flip[0] | pk->flip[1]) & ~1) {
+        snprintf(buf, sizeof(buf), "quincunx %d, flip %d / %d (0 or 1)", pk->quincunx, pk->flip[0], pk->flip[1]); *why = buf; return OH_E_ARG;
+    }
+    for (int v = 0; v < 2; v++)
+        if ((pk->grid_x[v] | pk->grid_y[v]) & ~15) {
+            snprintf(buf, sizeof(buf), "grid position (%d, %d) of frame %d (0 .. 15)", pk->grid_x[v], pk->grid_y[v], v); *why = buf; return OH_E_ARG;
+        }
+    return OH_OK;
+}
+
+/* the plane classes of a call on packed pictures of params `packed` with views of half or full size, and (view non-null) the params of
+ * such a view: the packed pictures' with the view's size, each side rounded up to the minimum coding block */
+int packing_geometry(const OhPacking *pk, const OhPicParams *packed, int full, PkPlane pl[2], OhPicParams *view, std::string *why)
+{
+    char buf[256];
+    if (const int rc = packing_check(pk, why))
+        return rc;
+    const bool sbs = pk->arrangement == OH_PACK_SIDE_BY_SIDE;
+    const int W = packed->width, H = packed->height, hs = oh_hshift(packed, 1), vs = oh_vshift(packed, 1);
+    if (W < 1 || H < 1 || (sbs ? W % (2 << hs) : H % (2 << vs))) {
+        snprintf(buf, sizeof(buf), "packed pictures of %dx%d: each half is a whole number of chroma samples, the %s a multiple of %d", W, H,
+                 sbs ? "width" : "height", sbs ? 2 << hs : 2 << vs);
+        *why = buf; return OH_E_ARG;
+    }
+    for (int q = 0; q < 2; q++) {
+        const int qs = q ? hs : 0, qv = q ? vs : 0;
+        PkPlane &p = pl[q];
+        p.sbs = sbs; p.quincunx = pk->quincunx; p.full = full != 0; p.taps = q ? 4 : 8;
+        p.pos = sbs ? (qs ? PK_POS_COSITED : PK_POS_PLAIN) : (qv ? PK_POS_MIDWAY : PK_POS_PLAIN);
+        p.cw = (W >> qs) / (sbs ? 2 : 1); p.ch = (H >> qv) / (sbs ? 1 : 2);
+        p.vw = full ? W >> qs : p.cw; p.vh = full ? H >> qv : p.ch;
+        p.maxv = (1 << packed->bit_depth) - 1;
+    }
+    if (view) {
+        const int cb = 1 << packed->log2_min_cb_size;
+        *view = *packed;
+        view->width = (pl[0].vw + cb - 1) / cb * cb;
+        view->height = (pl[0].vh + cb - 1) / cb * cb;
+    }
+    return OH_OK;
+}
+
+extern "C" int oh_packing_view_size(const OhPacking *pk, const OhPicParams *packed, int full, OhPicParams *view)
+{
+    if (!pk || !packed || !view || (full & ~1) || packed->log2_min_cb_size < 3 || packed->log2_min_cb_size > 6 || !depth_ok(packed->bit_depth) ||
+        packed->chroma_format_idc < 0 || packed->chroma_format_idc > 3)
+        return OH_E_ARG;
+    PkPlane pl[2];
+    OhPicParams v;
+    std::string why;
+    if (const int rc = packing_geometry(pk, packed, full, pl, &v, &why))
+        return rc;
+    *view = v;
+    return OH_OK;
+}
+
+extern "C" int oh_packing_views(const OhPacking *pk, int *left, int *right)
+{
+    if (!pk || !left || !right)
+        return 0;
+    if (pk->content_interpretation != 1 && pk->content_interpretation != 2)
+        return 0;
+    *left = pk->content_interpretation == 1 ? 0 : 1;
+    *right = 1 - *left;
+    return 1;
+}
+
+template <typename T>
+static int packing_sample_t(const PkPlane &pl, int v, int flip, int g, int x, int y, const T *plane, ptrdiff_t stride)
+{
+    const T *r = plane + (pl.sbs ? (ptrdiff_t)v * pl.cw : (ptrdiff_t)v * pl.ch * stride);
+    return pk_unpack_sample(pl, v, flip, g, x, y, [=](int ry, int rx) -> int { return r[(ptrdiff_t)ry * stride + rx]; });
+}
+
+extern "C" int oh_packing_sample(const OhPacking *pk, const OhPicParams *packed, int full, int view, int plane, int x, int y,
+                                 const void *samples, int stride, int32_t *out)
+{
+    OhPicParams vp;
+    if (!samples || !out || (view & ~1) || plane < 0 || plane > 2 || oh_packing_view_size(pk, packed, full, &vp))
+        return OH_E_ARG;
+    if (plane && !packed->chroma_format_idc)
+        return OH_E_ARG;
+    PkPlane pl[2];
+    std::string why;
+    if (packing_geometry(pk, packed, full, pl, nullptr, &why))
+        return OH_E_ARG;
+    const int q = plane ? 1 : 0;
+    if (x < 0 || y < 0 || x >= vp.width >> oh_hshift(&vp, q) || y >= vp.height >> oh_vshift(&vp, q) || stride < packed->width >> oh_hshift(packed, q))
+        return OH_E_ARG;
+    const bool sbs = pk->arrangement == OH_PACK_SIDE_BY_SIDE;
+    const int flip = pk->flip[view], g = sbs ? pk->grid_x[view] : pk->grid_y[view];
+    *out = packed->bit_depth == 8 ? packing_sample_t(pl[q], view, flip, g, x, y, (const uint8_t *)samples, stride)
+                                  : packing_sample_t(pl[q], view, flip, g, x, y, (const uint16_t *)samples, stride);
+    return OH_OK;
+}
+
+extern "C" int oh_packing_pack_sample(const OhPacking *pk, const OhPicParams *packed, int plane, int x, int y, const void *view0,
+                                      const void *view1, int stride, int32_t *out)
+{
+    OhPicParams vp;
+    if (!view0 || !view1 || !out || plane < 0 || plane > 2 || !pk || oh_packing_view_size(pk, packed, pk->quincunx, &vp))
+        return OH_E_ARG;
+    if (plane && !packed->chroma_format_idc)
+        return OH_E_ARG;
+    PkPlane pl[2];
+    std::string why;
+    if (packing_geometry(pk, packed, pk->quincunx, pl, nullptr, &why))
+        return OH_E_ARG;
+    const int q = plane ? 1 : 0;
+    if (x < 0 || y < 0 || x >= packed->width >> oh_hshift(packed, q) || y >= packed->height >> oh_vshift(packed, q) || stride < pl[q].vw)
+        return OH_E_ARG;
+    const void *const views[2] = { view0, view1 };
+    const bool b8 = packed->bit_depth == 8;
+    *out = pk_pack_sample(pl[q], pk->flip, x, y, [=](int v, int sy, int sx) -> int {
+        const ptrdiff_t at = (ptrdiff_t)sy * stride + sx;
+        return b8 ? ((const uint8_t *)views[v])[at] : ((const uint16_t *)views[v])[at];
+    });
     return OH_OK;
 }

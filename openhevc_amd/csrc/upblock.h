@@ -9,6 +9,7 @@
 #define OHEVC_UPBLOCK_H
 
 #include <stdint.h>
+#include "up_taps.h"
 
 #if defined(__HIPCC__)
 #define UPB_HD  __host__ __device__ inline
@@ -154,15 +155,11 @@ UPB_HD int upb_check(const OhUpBlkGeom &g, int x0, int y0)
 #define UPB_TMP_OFF 8
 
 UPB_CONST int8_t upb_luma[21][8] = {
-    { 0, 0, 0, 64, 0, 0, 0, 0 }, { 0, 1, -3, 63, 4, -2, 1, 0 }, { -1, 2, -5, 62, 8, -3, 1, 0 }, { -1, 3, -8, 60, 13, -4, 1, 0 },
-    { -1, 4, -10, 58, 17, -5, 1, 0 }, { -1, 4, -11, 52, 26, -8, 3, -1 }, { -1, 3, -9, 47, 31, -10, 4, -1 }, { -1, 4, -11, 45, 34, -10, 4, -1 },
-    { -1, 4, -11, 40, 40, -11, 4, -1 }, { -1, 4, -10, 34, 45, -11, 4, -1 }, { -1, 4, -10, 31, 47, -9, 3, -1 }, { -1, 3, -8, 26, 52, -11, 4, -1 },
-    { 0, 1, -5, 17, 58, -10, 4, -1 }, { 0, 1, -4, 13, 60, -8, 3, -1 }, { 0, 1, -3, 8, 62, -5, 2, -1 }, { 0, 1, -2, 4, 63, -3, 1, 0 },
+    UP_TAPS_LUMA_ROWS,
     { 0, 0, 0, 64, 0, 0, 0, 0 }, { -1, 4, -11, 40, 40, -11, 4, -1 },                                            /* x2 */
     { 0, 0, 0, 64, 0, 0, 0, 0 }, { -1, 3, -8, 26, 52, -11, 4, -1 }, { -1, 4, -11, 52, 26, -8, 3, -1 } };       /* x1.5 */
 UPB_CONST int8_t upb_chroma[26][4] = {
-    { 0, 64, 0, 0 }, { -2, 62, 4, 0 }, { -2, 58, 10, -2 }, { -4, 56, 14, -2 }, { -4, 54, 16, -2 }, { -6, 52, 20, -2 }, { -6, 46, 28, -4 }, { -4, 42, 30, -4 },
-    { -4, 36, 36, -4 }, { -4, 30, 42, -4 }, { -4, 28, 46, -6 }, { -2, 20, 52, -6 }, { -2, 16, 54, -4 }, { -2, 14, 56, -4 }, { -2, 10, 58, -2 }, { 0, 4, 62, -2 },
+    UP_TAPS_CHROMA_ROWS,
     { 0, 64, 0, 0 }, { -4, 36, 36, -4 },                                   /* x2, horizontal */
     { -2, 10, 58, -2 }, { -6, 46, 28, -4 },                                /* x2, vertical */
     { 0, 64, 0, 0 }, { -2, 20, 52, -6 }, { -6, 52, 20, -2 },               /* x1.5, horizontal */

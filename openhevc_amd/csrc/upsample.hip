@@ -5,6 +5,7 @@
  */
 #include "kernels_common.h"
 #include "upblock.h"
+#include "up_taps.h"
 
 /* =========================================================================================
  * SHVC inter-layer up-sampling: upsample_base_layer_frame, hevcdsp_template.c:2164-2438 —
@@ -17,14 +18,8 @@
  * intermediate plane of the reference's two loops never exists in HBM.  Tiles come from a list (the CTBs a picture's
  * inter-layer prediction touches: oh_pic_upsample_ctbs) or are all tiles of the plane (oh_pic_upsample).
  * ======================================================================================= */
-__constant__ int8_t c_up_luma[16][8] = {
-    { 0, 0, 0, 64, 0, 0, 0, 0 }, { 0, 1, -3, 63, 4, -2, 1, 0 }, { -1, 2, -5, 62, 8, -3, 1, 0 }, { -1, 3, -8, 60, 13, -4, 1, 0 },
-    { -1, 4, -10, 58, 17, -5, 1, 0 }, { -1, 4, -11, 52, 26, -8, 3, -1 }, { -1, 3, -9, 47, 31, -10, 4, -1 }, { -1, 4, -11, 45, 34, -10, 4, -1 },
-    { -1, 4, -11, 40, 40, -11, 4, -1 }, { -1, 4, -10, 34, 45, -11, 4, -1 }, { -1, 4, -10, 31, 47, -9, 3, -1 }, { -1, 3, -8, 26, 52, -11, 4, -1 },
-    { 0, 1, -5, 17, 58, -10, 4, -1 }, { 0, 1, -4, 13, 60, -8, 3, -1 }, { 0, 1, -3, 8, 62, -5, 2, -1 }, { 0, 1, -2, 4, 63, -3, 1, 0 } };
-__constant__ int8_t c_up_chroma[16][4] = {
-    { 0, 64, 0, 0 }, { -2, 62, 4, 0 }, { -2, 58, 10, -2 }, { -4, 56, 14, -2 }, { -4, 54, 16, -2 }, { -6, 52, 20, -2 }, { -6, 46, 28, -4 }, { -4, 42, 30, -4 },
-    { -4, 36, 36, -4 }, { -4, 30, 42, -4 }, { -4, 28, 46, -6 }, { -2, 20, 52, -6 }, { -2, 16, 54, -4 }, { -2, 14, 56, -4 }, { -2, 10, 58, -2 }, { 0, 4, 62, -2 } };
+__constant__ int8_t c_up_luma[16][8] = { UP_TAPS_LUMA_ROWS };
+__constant__ int8_t c_up_chroma[16][4] = { UP_TAPS_CHROMA_ROWS };
 
 #define UP_TILE 64                    /* tile edge (luma CTB); scale <= 1 (EL >= BL): the window is at most UP_TILE + 8 */
 #define UP_WIN  (UP_TILE + 8)

@@ -949,6 +949,94 @@ def remap_from_sei(sei):
     return Remap(t[:3, :1 << r.in_bit_depth], k, r.log2_denom, t[3:, :1 << r.out_bit_depth], r.in_bit_depth, r.out_bit_depth)
 
 
+class OhPacking(C.Structure):                                 # include/ohevc_hip.h
+    _fields_ = [("arrangement", C.c_int32), ("quincunx", C.c_int32), ("flip", C.c_int32 * 2), ("grid_x", C.c_int32 * 2),
+                ("grid_y", C.c_int32 * 2), ("content_interpretation", C.c_int32)]
+
+
+PACK_ARRANGEMENTS = {"side_by_side": 3, "top_bottom": 4}      # OH_PACK_SIDE_BY_SIDE, OH_PACK_TOP_BOTTOM
+PACK_MAX_PICS = 32                                            # OH_PK_MAX_PICS: packed pictures of one launch
+
+
+class Packing:
+    """what Engine.pics_unpack / pics_pack take (OhPacking): arrangement (3 side by side, 4 top-bottom), quincunx, flip (view 0, view 1:
+    stored mirrored), grid ((x, y) of view 0, (x, y) of view 1, each 0 .. 15) and content_interpretation"""
+    __slots__ = ("arrangement", "quincunx", "flip", "grid", "content_interpretation")
+
+    def __init__(self, arrangement, quincunx=False, flip=(False, False), grid=((0, 0), (0, 0)), content_interpretation=0):
+        self.arrangement = _enum(PACK_ARRANGEMENTS, "arrangement", arrangement)
+        self.quincunx = bool(quincunx)
+        self.flip = (bool(flip[0]), bool(flip[1]))
+        self.grid = ((int(grid[0][0]), int(grid[0][1])), (int(grid[1][0]), int(grid[1][1])))
+        self.content_interpretation = int(content_interpretation)
+
+    def __repr__(self):
+        return (f"Packing(arrangement={self.arrangement}, quincunx={self.quincunx}, flip={self.flip}, grid={self.grid}, "
+                f"content_interpretation={self.content_interpretation})")
+
+    def as_struct(self):
+        pk = OhPacking(self.arrangement, int(self.quincunx))
+        for v in range(2):
+            pk.flip[v] = int(self.flip[v])
+            pk.grid_x[v], pk.grid_y[v] = self.grid[v]
+        pk.content_interpretation = self.content_interpretation
+        return pk
+
+    def view_size(self, params, full=True):
+        """oh_packing_view_size (host only): the OhPicParams of a view of packed pictures of `params`, of full or half size"""
+        pk, vp = self.as_struct(), F.OhPicParams()
+        _check(lib().oh_packing_view_size(C.byref(pk), C.byref(params), int(bool(full)), C.byref(vp)), "oh_packing_view_size")
+        return vp
+
+    def views(self):
+        """oh_packing_views (host only): (left, right), the constituent frames that are the left and the right view, or None where
+        the content interpretation does not say"""
+        pk, left, right = self.as_struct(), C.c_int(), C.c_int()
+        return (left.value, right.value) if lib().oh_packing_views(C.byref(pk), C.byref(left), C.byref(right)) else None
+
+    def sample(self, params, plane_samples, view, plane, x, y, full=True):
+        """oh_packing_sample (host only): sample (x, y) of plane `plane` of view `view` from plane_samples, that plane of the packed
+        picture as a numpy array (uint8 at 8 bit, else uint16)"""
+        a = np.ascontiguousarray(plane_samples, dtype=np.uint8 if params.bit_depth == 8 else np.uint16)
+        pk, out = self.as_struct(), C.c_int32()
+        _check(lib().oh_packing_sample(C.byref(pk), C.byref(params), int(bool(full)), int(view), int(plane), int(x), int(y),
+                                       a.ctypes.data_as(C.c_void_p), a.shape[1], C.byref(out)), "oh_packing_sample")
+        return out.value
+
+    def pack_sample(self, params, view0, view1, plane, x, y):
+        """oh_packing_pack_sample (host only): sample (x, y) of plane `plane` of the packed picture of `params` from that plane of
+        the two views, numpy arrays of one shape"""
+        dt = np.uint8 if params.bit_depth == 8 else np.uint16
+        a0, a1 = np.ascontiguousarray(view0, dtype=dt), np.ascontiguousarray(view1, dtype=dt)
+        if a0.shape != a1.shape:
+            raise ValueError("pack_sample: the planes of the two views are of one shape")
+        pk, out = self.as_struct(), C.c_int32()
+        _check(lib().oh_packing_pack_sample(C.byref(pk), C.byref(params), int(plane), int(x), int(y), a0.ctypes.data_as(C.c_void_p),
+                                            a1.ctypes.data_as(C.c_void_p), a0.shape[1], C.byref(out)), "oh_packing_pack_sample")
+        return out.value
+
+
+def make_packing(arrangement, *, quincunx=False, flip=(False, False), grid=((0, 0), (0, 0)), content_interpretation=0):
+    """a Packing from its parts.  arrangement: "side_by_side", "top_bottom" or the arrangement type (3, 4)"""
+    return Packing(arrangement, quincunx, flip, grid, content_interpretation)
+
+
+def packing_from_sei(sei):
+    """oh_packing_from_sei (host only): the dict of annexb.frame_packing (or an annexb.OhFramePackingSei) -> the Packing.  EngineError
+    with code OH_E_UNSUPPORTED and the reason for temporal interleaving, an arrangement type that HEVC does not define and field
+    views; OH_E_ARG for a cancelled message."""
+    from . import annexb as A
+    if sei is None:
+        raise ValueError("packing_from_sei: no message")
+    s = sei if isinstance(sei, A.OhFramePackingSei) else A.frame_packing_to_struct(sei)
+    pk = OhPacking()
+    rc = lib().oh_packing_from_sei(C.byref(s), C.byref(pk))
+    why = lib().oh_packing_unsupported(C.byref(s)).decode()
+    _check(rc, "oh_packing_from_sei", text="{what} failed ({rc})" + (": " + why if why else ""))
+    return Packing(pk.arrangement, pk.quincunx, tuple(pk.flip), ((pk.grid_x[0], pk.grid_y[0]), (pk.grid_x[1], pk.grid_y[1])),
+                   pk.content_interpretation)
+
+
 def convert_image_bytes(params, cv):
     """oh_convert_image_bytes (host only): bytes of one image, 0 when the combination is not valid"""
     return int(lib().oh_convert_image_bytes(C.byref(params), C.byref(cv)))
@@ -1107,6 +1195,16 @@ def lib():
         L.oh_remap_sample.argtypes = [RP, U16P, U16P]
         L.oh_remap_from_sei.argtypes = [V, V, RP]
         L.oh_remap_luts.argtypes = [RP, V]
+        PKP = C.POINTER(OhPacking)
+        L.oh_pics_unpack.argtypes = [V, IP, IP, IP, I, PKP]
+        L.oh_pics_pack.argtypes = [V, IP, IP, IP, I, PKP]
+        L.oh_packing_from_sei.argtypes = [V, PKP]
+        L.oh_packing_unsupported.argtypes = [V]
+        L.oh_packing_unsupported.restype = C.c_char_p
+        L.oh_packing_view_size.argtypes = [PKP, C.POINTER(F.OhPicParams), I, C.POINTER(F.OhPicParams)]
+        L.oh_packing_sample.argtypes = [PKP, C.POINTER(F.OhPicParams), I, I, I, I, I, V, I, C.POINTER(I32)]
+        L.oh_packing_pack_sample.argtypes = [PKP, C.POINTER(F.OhPicParams), I, I, I, V, V, I, C.POINTER(I32)]
+        L.oh_packing_views.argtypes = [PKP, IP, IP]
         L.oh_motion_blocks.argtypes = [I, I, I, IP, IP]
         L.oh_pics_motion.argtypes = [V, IP, IP, I, C.POINTER(OhMotionSearch), MVP]
         L.oh_pics_motion_compensate.argtypes = [V, IP, IP, I, I, MVP]
@@ -1876,6 +1974,65 @@ class Engine:
 
         out, made = self._dsts(out, n, "sources", at_output_depth)
         self._call(self.L.oh_pics_colour_remap(self.h, _ids(pids), _ids(out), n, C.byref(r)), "oh_pics_colour_remap", made)
+        return out
+
+    def pics_unpack(self, pids, packing, full=True, out=None, *, views=(True, True)):
+        """finished frame-packed pictures -> the two views of each as finished pictures (oh_pics_unpack; the exact definition is in
+        include/ohevc_hip.h).  packing: what packing_from_sei or make_packing returned.  full: views of the packed pictures' size,
+        up-sampled on the phase of the grid positions (quincunx: interpolated on the lattice), else the stored halves.  views: which
+        of the two to make.  out: (view 0 ids or None, view 1 ids or None) to reuse — their size picks the mode, `full` is not read;
+        None allocates pictures of packing.view_size.  Returns (view 0 ids, view 1 ids), None for a view that was not asked for.
+        Enqueued on the engine stream; does not wait."""
+        pids = list(pids)
+        n = len(pids)
+        if not isinstance(packing, Packing):
+            raise ValueError("pics_unpack: packing is what packing_from_sei or make_packing returns")
+        if n == 0:
+            raise ValueError("pics_unpack needs at least one picture (the destinations follow the pictures' params)")
+        pk = packing.as_struct()
+        made = []
+        if out is None:
+            want = [bool(views[0]), bool(views[1])]
+            if not any(want):
+                raise ValueError("pics_unpack: neither view asked for")
+            made = self._alloc_like(packing.view_size(self._pic_params(pids[0]), full), n * sum(want))
+            sides = [made[:n] if want[0] else None, made[-n:] if want[1] else None]
+        else:
+            sides = list(out)
+            if len(sides) != 2 or (sides[0] is None and sides[1] is None):
+                raise ValueError("out: a pair (view 0 ids, view 1 ids) with None for a view that is not asked for")
+            sides = [None if s is None else self._dsts(s, n, "sources", None)[0] for s in sides]
+        self._call(self.L.oh_pics_unpack(self.h, _ids(pids), None if sides[0] is None else _ids(sides[0]),
+                                         None if sides[1] is None else _ids(sides[1]), n, C.byref(pk)), "oh_pics_unpack", made)
+        return sides[0], sides[1]
+
+    def pics_pack(self, v0, v1, packing, out=None):
+        """two lists of finished views -> finished frame-packed pictures (oh_pics_pack): half-size views are placed in their halves
+        with the flips applied, the exact inverse of pics_unpack(full=False); with quincunx sampling full-size views are
+        point-sampled on the lattice.  out: destination pictures to reuse; None allocates pictures of the views' params and
+        twice their coded size on the packed axis (with quincunx: their size) — a packed size whose half is no whole number of
+        minimum coding blocks needs out=, the halves are then the top-left windows of the views.  Returns the destination ids.  Enqueued on the engine stream; does not wait."""
+        v0, v1 = list(v0), list(v1)
+        n = len(v0)
+        if not isinstance(packing, Packing):
+            raise ValueError("pics_pack: packing is what packing_from_sei or make_packing returns")
+        if len(v1) != n:
+            raise ValueError(f"pics_pack: {n} pictures of view 0, {len(v1)} of view 1")
+        if n == 0:
+            raise ValueError("pics_pack needs at least one pair (the destinations follow the pictures' params)")
+        pk = packing.as_struct()
+
+        def packed():
+            vp = F.OhPicParams.from_buffer_copy(self._pic_params(v0[0]))
+            if not packing.quincunx:
+                if packing.arrangement == PACK_ARRANGEMENTS["side_by_side"]:
+                    vp.width *= 2
+                else:
+                    vp.height *= 2
+            return vp
+
+        out, made = self._dsts(out, n, "pairs", packed)
+        self._call(self.L.oh_pics_pack(self.h, _ids(v0), _ids(v1), _ids(out), n, C.byref(pk)), "oh_pics_pack", made)
         return out
 
     def pics_compose(self, dst, layers, *, fill=None):
