@@ -121,7 +121,13 @@ typedef struct OhIntra {
     uint8_t  c_idx;
     uint8_t  log2_size;           /* 2..5                                                           */
     uint8_t  mode;                /* 0 planar, 1 DC, 2..34 angular                                  */
-    uint8_t  avail;               /* enum OhIntraAvail bits                                         */
+    uint8_t  avail;               /* enum OhIntraAvail bits.  A bit may be set only where a decoder can
+                                     set it: the neighbour samples lie inside the picture and precede the
+                                     block in decoding (z-scan, 6.4.1) order; any SUBSET of those bits is
+                                     valid (a neighbour in another slice or tile is unavailable).  Other
+                                     flag sets are outside the contract of the passes: the staged intra
+                                     kernel holds a CTU, its left column and its top row, and nothing
+                                     below the CTU's bottom edge                                       */
     uint32_t tu;                  /* index of this block's OhTu (residual added right after the
                                      prediction), OH_NO_COEFF when cbf == 0                        */
 } OhIntra;                        /* 12 bytes */

@@ -136,6 +136,41 @@ enum {
     OH_CNT_STRONG_TC2_HITS,     /* strong-filter samples whose correction was clipped to +-2 * tc          */
     OH_CNT_PER_DIR,
     OH_CNT_INTRA_STRONG_32 = 2 * OH_CNT_PER_DIR,   /* luma 32x32 intra blocks with the strong (bi-linear) smoothing */
+    /* intra_pred, appended (tests/directed_intra.py keeps its lists honest with them); per block unless stated */
+    OH_CNT_I_SUB_L,             /* substitution cascade, no bottom-left (hevcpred_template.c:251-286): from left          */
+    OH_CNT_I_SUB_UL,            /* ... from the corner                                                                     */
+    OH_CNT_I_SUB_U,             /* ... from up                                                                             */
+    OH_CNT_I_SUB_UR,            /* ... from up-right                                                                       */
+    OH_CNT_I_SUB_NONE,          /* ... nothing available: mid grey                                                         */
+    OH_CNT_I_FILL_L,            /* the four single fills after the cascade: left                                           */
+    OH_CNT_I_FILL_UL,           /* ... corner                                                                              */
+    OH_CNT_I_FILL_U,            /* ... up                                                                                  */
+    OH_CNT_I_FILL_UR,           /* ... up-right                                                                            */
+    OH_CNT_I_FILT_NONE,         /* edges not smoothed                                                                      */
+    OH_CNT_I_FILT_3TAP,         /* 3-tap smoothing                                                                         */
+    OH_CNT_I_FILT_STRONG,       /* strong smoothing (== OH_CNT_INTRA_STRONG_32)                                            */
+    OH_CNT_I_TL_PP,             /* 32x32 luma blocks that reach the smoothing decision: t < lim && l < lim                 */
+    OH_CNT_I_TL_PF,             /* t < lim, l >= lim                                                                       */
+    OH_CNT_I_TL_FP,             /* t >= lim, l < lim                                                                       */
+    OH_CNT_I_TL_FF,             /* neither                                                                                 */
+    OH_CNT_I_CLIP10_LOW,        /* mode 10 boundary filter, per SAMPLE: clipped at 0                                       */
+    OH_CNT_I_CLIP10_HIGH,       /* ... at the maximum                                                                      */
+    OH_CNT_I_CLIP10_NONE,       /* ... in range                                                                            */
+    OH_CNT_I_CLIP26_LOW,        /* mode 26, likewise                                                                       */
+    OH_CNT_I_CLIP26_HIGH,
+    OH_CNT_I_CLIP26_NONE,
+    OH_CNT_I_DC_EDGE,           /* DC blocks with the edge filter (luma, < 32)                                             */
+    OH_CNT_I_DC_PLAIN,          /* DC blocks without                                                                       */
+    OH_CNT_I_PROJECTED,         /* angular blocks that project side samples (last < -1)                                    */
+    OH_CNT_I_TR_PARTIAL,        /* up-right gathered with 0 < tr_size < n                                                  */
+    OH_CNT_I_BL_PARTIAL,        /* bottom-left gathered with 0 < bl_size < n                                               */
+    OH_CNT_I_CIP_TOP_START,     /* constrained intra pred (:185-249): nothing intra on the left side, start from the top row
+                                   (not reachable with flags a decoder can produce: tests/test_directed_intra_lists.py) */
+    OH_CNT_I_CIP_NO_LEFT,       /* ... no left-side flag at all: the search along the top row                              */
+    OH_CNT_I_CIP_X0_ZERO,       /* ... the x0 == 0 zero fill of the left column (:236)                                     */
+    OH_CNT_I_CIP_UP_SWEEP,      /* ... the up sweep of the left column                                                     */
+    OH_CNT_I_CIP_CORNER,        /* ... the corner patched from left[0]                                                     */
+    OH_CNT_I_CIP_FLAG_CLEARED,  /* ... a candidate flag cleared by the re-derivation (:126-157), per flag                  */
     OH_CNT_N
 };
 void oh_or_counters(uint64_t *out, int n, int reset);

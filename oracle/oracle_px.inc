@@ -129,6 +129,7 @@ static void FN(pred_dc)(PX *dst, const PX *top, const PX *left, ptrdiff_t stride
     for (int y = 0; y < n; y++)
         for (int x = 0; x < n; x++)
             dst[y * stride + x] = (PX)dc;
+    g_cnt[c_idx == 0 && n < 32 ? OH_CNT_I_DC_EDGE : OH_CNT_I_DC_PLAIN]++;
     if (c_idx == 0 && n < 32) {                          /* :410-416 */
         dst[0] = (PX)((left[0] + 2 * dc + top[0] + 2) >> 2);
         for (int x = 1; x < n; x++)
@@ -153,6 +154,7 @@ static void FN(pred_angular)(int bd, PX *dst, const PX *top, const PX *left, ptr
     for (int i = 0; i <= 2 * n; i++)
         ref[i] = main_[i - 1];
     if (angle < 0 && last < -1) {                        /* projected side samples :447-453, :480-486 */
+        g_cnt[OH_CNT_I_PROJECTED]++;
         int inv = oh_inv_angle[mode - 11];
         for (int i = last; i <= -1; i++)
             ref[i] = side[-1 + ((i * inv + 128) >> 8)];
@@ -169,11 +171,17 @@ static void FN(pred_angular)(int bd, PX *dst, const PX *top, const PX *left, ptr
     }
     if (c_idx == 0 && n < 32) {                          /* boundary smoothing :474-477, :501-508 */
         if (mode == 26)
-            for (int y = 0; y < n; y++)
-                dst[y * stride] = (PX)FN(clip_px)(top[0] + ((left[y] - left[-1]) >> 1), bd);
+            for (int y = 0; y < n; y++) {
+                const int v = top[0] + ((left[y] - left[-1]) >> 1);
+                g_cnt[v < 0 ? OH_CNT_I_CLIP26_LOW : v >= (1 << bd) ? OH_CNT_I_CLIP26_HIGH : OH_CNT_I_CLIP26_NONE]++;
+                dst[y * stride] = (PX)FN(clip_px)(v, bd);
+            }
         if (mode == 10)
-            for (int x = 0; x < n; x++)
-                dst[x] = (PX)FN(clip_px)(left[0] + ((top[x] - top[-1]) >> 1), bd);
+            for (int x = 0; x < n; x++) {
+                const int v = left[0] + ((top[x] - top[-1]) >> 1);
+                g_cnt[v < 0 ? OH_CNT_I_CLIP10_LOW : v >= (1 << bd) ? OH_CNT_I_CLIP10_HIGH : OH_CNT_I_CLIP10_NONE]++;
+                dst[x] = (PX)FN(clip_px)(v, bd);
+            }
     }
 }
 
@@ -223,22 +231,29 @@ static void FN(intra_pred)(const OhPicParams *p, PX *plane, ptrdiff_t stride, in
             int xl = (X0 - 1) >> lpu, yb = (Y0 + sl_v) >> lpu, mx = pu_v < mph - yb ? pu_v : mph - yb;
             a_bl = 0;
             for (int i = 0; i < mx; i += 2) a_bl |= CELL(xl, yb + i);
+            if (!a_bl) g_cnt[OH_CNT_I_CIP_FLAG_CLEARED]++;
         }
         if (a_l && on_x) {
             int xl = (X0 - 1) >> lpu, yl = Y0 >> lpu, mx = pu_v < mph - yl ? pu_v : mph - yl;
             a_l = 0;
             for (int i = 0; i < mx; i += 2) a_l |= CELL(xl, yl + i);
+            if (!a_l) g_cnt[OH_CNT_I_CIP_FLAG_CLEARED]++;
         }
-        if (a_ul) a_ul = CELL((X0 - 1) >> lpu, (Y0 - 1) >> lpu);
+        if (a_ul) {
+            a_ul = CELL((X0 - 1) >> lpu, (Y0 - 1) >> lpu);
+            if (!a_ul) g_cnt[OH_CNT_I_CIP_FLAG_CLEARED]++;
+        }
         if (a_u && on_y) {
             int xt = X0 >> lpu, yt = (Y0 - 1) >> lpu, mx = pu_h < mpw - xt ? pu_h : mpw - xt;
             a_u = 0;
             for (int i = 0; i < mx; i += 2) a_u |= CELL(xt + i, yt);
+            if (!a_u) g_cnt[OH_CNT_I_CIP_FLAG_CLEARED]++;
         }
         if (a_ur && on_y) {
             int yt = (Y0 - 1) >> lpu, xr = (X0 + sl_h) >> lpu, mx = pu_h < mpw - xr ? pu_h : mpw - xr;
             a_ur = 0;
             for (int i = 0; i < mx; i += 2) a_ur |= CELL(xr + i, yt);
+            if (!a_ur) g_cnt[OH_CNT_I_CIP_FLAG_CLEARED]++;
         }
 #undef CELL
         /* memset(left / top, 128, 64 * sizeof(pixel)): BYTES of 128, i.e. 0x8080 for 16-bit samples (:158-160) */
@@ -249,11 +264,13 @@ static void FN(intra_pred)(const OhPicParams *p, PX *plane, ptrdiff_t stride, in
     if (a_ul) left[-1] = top[-1] = src[-stride - 1];
     if (a_u)  for (int i = 0; i < n; i++) top[i] = src[-stride + i];
     if (a_ur) {
+        if (tr_size > 0 && tr_size < n) g_cnt[OH_CNT_I_TR_PARTIAL]++;
         for (int i = 0; i < tr_size; i++) top[n + i] = src[-stride + n + i];
         for (int i = tr_size; i < n; i++) top[n + i] = src[-stride + n + tr_size - 1];
     }
     if (a_l)  for (int i = 0; i < n; i++) left[i] = src[i * stride - 1];
     if (a_bl) {
+        if (bl_size > 0 && bl_size < n) g_cnt[OH_CNT_I_BL_PARTIAL]++;
         for (int i = 0; i < bl_size; i++) left[n + i] = src[(n + i) * stride - 1];
         for (int i = bl_size; i < n; i++) left[n + i] = src[(n + bl_size - 1) * stride - 1];
     }
@@ -266,6 +283,7 @@ static void FN(intra_pred)(const OhPicParams *p, PX *plane, ptrdiff_t stride, in
         if (a_bl || a_l || a_ul) {
             while (j > -1 && !ISI(-1, j)) j--;
             if (!ISI(-1, j)) {                                             /* nothing intra on the left side: take it from the top row */
+                g_cnt[OH_CNT_I_CIP_TOP_START]++;
                 j = 0;
                 while (j < size_max_x && !ISI(j, -1)) j++;
                 for (int i = j; i > -1; i--)
@@ -273,6 +291,7 @@ static void FN(intra_pred)(const OhPicParams *p, PX *plane, ptrdiff_t stride, in
                 left[-1] = top[-1];
             }
         } else {
+            g_cnt[OH_CNT_I_CIP_NO_LEFT]++;
             j = 0;
             while (j < size_max_x && !ISI(j, -1)) j++;
             if (j > 0) {
@@ -299,15 +318,18 @@ static void FN(intra_pred)(const OhPicParams *p, PX *plane, ptrdiff_t stride, in
         if (!a_bl) for (int i = 0; i < n; i++) left[n + i] = left[n - 1];
         if (x0 != 0 && y0 != 0) {                                          /* upwards from the end of the column */
             PX a = left[size_max_y - 1];
+            g_cnt[OH_CNT_I_CIP_UP_SWEEP]++;
             for (int i = size_max_y - 1; i > -1; i -= 4) {
                 if (!ISI(-1, i - 3)) { left[i - 3] = left[i - 2] = left[i - 1] = left[i] = a; }
                 else a = left[i - 3];
             }
-            if (!ISI(-1, -1)) left[-1] = left[0];
+            if (!ISI(-1, -1)) { left[-1] = left[0]; g_cnt[OH_CNT_I_CIP_CORNER]++; }
         } else if (x0 == 0) {
+            g_cnt[OH_CNT_I_CIP_X0_ZERO]++;
             for (int i = 0; i < size_max_y; i++) left[i] = 0;             /* EXTEND(left, 0, size_max_y), :236 */
         } else {
             PX a = left[size_max_y - 1];
+            g_cnt[OH_CNT_I_CIP_UP_SWEEP]++;
             for (int i = size_max_y - 1; i > -1; i -= 4) {
                 if (!ISI(-1, i - 3)) { left[i - 3] = left[i - 2] = left[i - 1] = left[i] = a; }
                 else a = left[i - 3];
@@ -326,6 +348,7 @@ static void FN(intra_pred)(const OhPicParams *p, PX *plane, ptrdiff_t stride, in
 
     /* substitution of unavailable samples (:251-286) */
     if (!a_bl) {
+        g_cnt[a_l ? OH_CNT_I_SUB_L : a_ul ? OH_CNT_I_SUB_UL : a_u ? OH_CNT_I_SUB_U : a_ur ? OH_CNT_I_SUB_UR : OH_CNT_I_SUB_NONE]++;
         if (a_l) {
             for (int i = 0; i < n; i++) left[n + i] = left[n - 1];
         } else if (a_ul) {
@@ -345,6 +368,10 @@ static void FN(intra_pred)(const OhPicParams *p, PX *plane, ptrdiff_t stride, in
             for (int i = 0; i < 2 * n; i++) top[i] = left[i] = left[-1];
         }
     }
+    if (!a_l)  g_cnt[OH_CNT_I_FILL_L]++;
+    if (!a_ul) g_cnt[OH_CNT_I_FILL_UL]++;
+    if (!a_u)  g_cnt[OH_CNT_I_FILL_U]++;
+    if (!a_ur) g_cnt[OH_CNT_I_FILL_UR]++;
     if (!a_l)  for (int i = 0; i < n; i++) left[i] = left[n];
     if (!a_ul) left[-1] = left[0];
     if (!a_u)  for (int i = 0; i < n; i++) top[i] = left[-1];
@@ -352,6 +379,7 @@ static void FN(intra_pred)(const OhPicParams *p, PX *plane, ptrdiff_t stride, in
     top[-1] = left[-1];
 
     /* smoothing (:288-326) */
+    int filtered = 0;
     if (!p->intra_smoothing_disabled && (c_idx == 0 || p->chroma_format_idc == 3) &&
         mode != 1 && n != 4) {
         static const int thresh[3] = { 7, 1, 0 };
@@ -364,9 +392,12 @@ static void FN(intra_pred)(const OhPicParams *p, PX *plane, ptrdiff_t stride, in
             if (log2 == 5) {
                 t = abs(top[-1]  + top[63]  - 2 * top[31]);
                 l = abs(left[-1] + left[63] - 2 * left[31]);
+                if (c_idx == 0)
+                    g_cnt[t < lim ? (l < lim ? OH_CNT_I_TL_PP : OH_CNT_I_TL_PF) : (l < lim ? OH_CNT_I_TL_FP : OH_CNT_I_TL_FF)]++;
             }
             if (p->strong_intra_smoothing && c_idx == 0 && log2 == 5 && t < lim && l < lim) {
                 g_cnt[OH_CNT_INTRA_STRONG_32]++;
+                filtered = 2;
                 ftop[-1] = top[-1];  ftop[63] = top[63];
                 fleft[-1] = left[-1]; fleft[63] = left[63];
                 for (int i = 0; i < 63; i++) {
@@ -374,6 +405,7 @@ static void FN(intra_pred)(const OhPicParams *p, PX *plane, ptrdiff_t stride, in
                     fleft[i] = (PX)(((63 - i) * left[-1] + (i + 1) * left[63] + 32) >> 6);
                 }
             } else {
+                filtered = 1;
                 fleft[2 * n - 1] = left[2 * n - 1];
                 ftop[2 * n - 1]  = top[2 * n - 1];
                 for (int i = 2 * n - 2; i >= 0; i--) {
@@ -387,6 +419,7 @@ static void FN(intra_pred)(const OhPicParams *p, PX *plane, ptrdiff_t stride, in
         }
     }
 
+    g_cnt[filtered == 2 ? OH_CNT_I_FILT_STRONG : filtered ? OH_CNT_I_FILT_3TAP : OH_CNT_I_FILT_NONE]++;
     if (mode == 0)      FN(pred_planar)(src, top, left, stride, log2);
     else if (mode == 1) FN(pred_dc)(src, top, left, stride, log2, c_idx);
     else                FN(pred_angular)(bd, src, top, left, stride, log2, c_idx, mode);

@@ -27,6 +27,15 @@
  * loop leaves in s->tab_slice_address, s->filter_slice_edges and pps->tile_id (hevc.c:2600, 2679; hevc_ps.c) */
 static const OhCtbMaps *g_maps;
 API void ref_set_ctb_maps(const OhCtbMaps *m) { g_maps = m; }
+/* tests/directed_intra.py: take the candidate flags lc->na of every intra block from OhIntra.avail (any subset of what 6.4.1 allows: the
+ * neighbour lies in another slice or tile) and not from the single-slice derivation below; intra_pred() still ANDs bottom-left and
+ * up-right with its own z-scan comparison (hevcpred_template.c:100-109) */
+#ifdef OH_REF_ITEM_FLAGS                /* ref_item_flags_unit.c: _ref/libohevc_ref_flags.so; libohevc_ref.so is built without it */
+static int g_item_flags;
+API void ref_set_item_flags(int on) { g_item_flags = on; }
+#else
+enum { g_item_flags = 0 };
+#endif
 
 static HEVCDSPContext  g_dsp[15];
 static HEVCPredContext g_pred[15];
@@ -309,6 +318,12 @@ API int ref_intra_picture(const OhFrame *f, uint8_t *const data[3], const ptrdif
         lc->na.cand_up_right_sap = (x0b + n_h == ctb) ? lc->ctb_up_right_flag && !y0b : lc->na.cand_up;
         lc->na.cand_up_right = lc->na.cand_up_right_sap && (x0 + n_h) < lc->end_of_tiles_x;
         lc->na.cand_bottom_left = ((y0 + n_v) >= lc->end_of_tiles_y) ? 0 : lc->na.cand_left;
+        if (g_item_flags) {
+            lc->na.cand_up = !!(it->avail & OH_AV_UP); lc->na.cand_left = !!(it->avail & OH_AV_LEFT);
+            lc->na.cand_up_left = !!(it->avail & OH_AV_UP_LEFT);
+            lc->na.cand_up_right = lc->na.cand_up_right_sap = !!(it->avail & OH_AV_UP_RIGHT);
+            lc->na.cand_bottom_left = !!(it->avail & OH_AV_BOTTOM_LEFT);
+        }
         lc->tu.intra_pred_mode = lc->tu.intra_pred_mode_c = it->mode;
 
         s->hpc.intra_pred[it->log2_size - 2](s, x0, y0, c);

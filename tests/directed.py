@@ -148,8 +148,10 @@ def params(width, height, chroma, bd):
     return F.pic_params(width, height, bit_depth=bd, chroma_format_idc=chroma, sao=0, deblock=0, transquant_bypass_enable=1)
 
 
-def record(name, p, pus, tus, seed, pinned_by=None, rec=None):
-    """the items through oh_rec_begin / oh_rec_pu / oh_rec_tu / oh_rec_intra / oh_rec_finish, in the order given"""
+def record(name, p, pus, tus, seed, pinned_by=None, rec=None, intra=(), is_intra=None, make=None):
+    """the items through oh_rec_begin / oh_rec_pu / oh_rec_tu / oh_rec_intra / oh_rec_finish, in the order given.  `intra`: blocks
+    with c, x, y, log2, mode, avail and tu (a Tu or None), recorded after `tus` (tests/directed_intra.py); `is_intra`: the min-PU map
+    of a picture with constrained intra prediction; `make`: the class of the result (DirectedList)"""
     lib = F.host()
     own = rec is None
     if own:
@@ -166,12 +168,22 @@ def record(name, p, pus, tus, seed, pinned_by=None, rec=None):
         assert idx != F.OH_NO_COEFF, t
         if t.intra:
             assert lib.oh_rec_intra(rec.h, t.c, t.x, t.y, t.log2, 1, 0, idx) == 0, t           # DC mode, no neighbour available
+    if is_intra is not None:
+        m = np.ascontiguousarray(is_intra, dtype=np.uint8)
+        assert m.shape == (p.height >> p.log2_min_pu_size, p.width >> p.log2_min_pu_size), name
+        C.memmove(lib.oh_rec_is_intra(rec.h), m.ctypes.data, m.size)
+    for b in intra:
+        idx = F.OH_NO_COEFF
+        if b.tu is not None:
+            idx = lib.oh_rec_tu(rec.h, b.c, b.x, b.y, b.log2, b.tu.kind, b.tu.flags, i16p(b.tu.coeffs))
+            assert idx != F.OH_NO_COEFF, b
+        assert lib.oh_rec_intra(rec.h, b.c, b.x, b.y, b.log2, b.mode, b.avail, idx) == 0, b
     f = lib.oh_rec_finish(rec.h)
     assert f, name
     fc = F.FrameCopy(f.contents, pinned_by=pinned_by)
     if own:
         rec.close()
-    return DirectedList(name, p, fc, list(pus), list(tus), seed)
+    return (make or DirectedList)(name, p, fc, list(pus), list(tus), seed)
 
 
 def shelf_pack(sizes, width, height):

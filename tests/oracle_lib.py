@@ -124,18 +124,24 @@ def oracle():
 CNT_NAMES = ("segments", "filter_on", "filter_on_pcm", "strong", "strong_pcm", "normal", "normal_pcm", "nd_p", "nd_q",
              "lines_skipped", "lines_px_clipped", "strong_tc2_hits")
 CNT_PER_DIR = len(CNT_NAMES)
-CNT_N = 2 * CNT_PER_DIR + 1
+INTRA_CNT_NAMES = ("sub_left", "sub_up_left", "sub_up", "sub_up_right", "sub_none", "fill_left", "fill_up_left", "fill_up",
+                   "fill_up_right", "filt_none", "filt_3tap", "filt_strong", "tl_pp", "tl_pf", "tl_fp", "tl_ff",
+                   "clip10_low", "clip10_high", "clip10_none", "clip26_low", "clip26_high", "clip26_none", "dc_edge", "dc_plain",
+                   "projected", "tr_partial", "bl_partial", "cip_top_start", "cip_no_left", "cip_x0_zero", "cip_up_sweep",
+                   "cip_corner", "cip_flag_cleared")
+CNT_N = 2 * CNT_PER_DIR + 1 + len(INTRA_CNT_NAMES)
 
 
 def oracle_counters(reset=True):
-    """{"v": {name: count}, "h": {name: count}, "intra_strong_32": count} of the pictures the oracle ran on this thread since
-    the last reset (luma deblocking segments with bs > 0; 32x32 luma intra blocks with the strong smoothing)"""
+    """{"v": {name: count}, "h": {name: count}, "intra_strong_32": count, "intra": {name: count}} of the pictures the oracle ran
+    on this thread since the last reset (luma deblocking segments with bs > 0; 32x32 luma intra blocks with the strong smoothing;
+    the branches of intra_pred, oracle.h: OH_CNT_I_*)"""
     fn = oracle().oh_or_counters
     fn.argtypes, fn.restype = [C.POINTER(C.c_uint64), C.c_int, C.c_int], None
     out = (C.c_uint64 * CNT_N)()
     fn(out, CNT_N, int(reset))
     return {"v": dict(zip(CNT_NAMES, out[:CNT_PER_DIR])), "h": dict(zip(CNT_NAMES, out[CNT_PER_DIR:2 * CNT_PER_DIR])),
-            "intra_strong_32": out[2 * CNT_PER_DIR]}
+            "intra_strong_32": out[2 * CNT_PER_DIR], "intra": dict(zip(INTRA_CNT_NAMES, out[2 * CNT_PER_DIR + 1:]))}
 
 
 def have_ref():
@@ -153,6 +159,27 @@ def ref():
             raise RuntimeError("reference tree not present; use tests/golden fixtures")
         _ref = _declare(C.CDLL(path), _REF_SIGS)
     return _ref
+
+
+_ref_flags = None
+
+
+def have_ref_flags():
+    return os.path.exists(os.path.join(ORACLE_DIR, "_ref", "libohevc_ref_flags.so")) or os.path.isdir(REF_TREE)
+
+
+def ref_flags():
+    """The reference kernels behind a harness that takes the intra candidate flags from the work list (ref_set_item_flags);
+    a library of its own (oracle/Makefile: ref_flags), built on demand when /root/reference is present."""
+    global _ref_flags
+    if _ref_flags is None:
+        path = os.path.join(ORACLE_DIR, "_ref", "libohevc_ref_flags.so")
+        if os.path.isdir(REF_TREE):
+            subprocess.check_call(["make", "-s", "-C", ORACLE_DIR, "ref_flags"])      # incremental
+        elif not os.path.exists(path):
+            raise RuntimeError("reference tree not present")
+        _ref_flags = _declare(C.CDLL(path), dict(_REF_SIGS, ref_set_item_flags=[I]))
+    return _ref_flags
 
 
 def pix_dtype(bd):
