@@ -90,9 +90,8 @@ static int engine_create(OhEngine **out, int device, hipStream_t ext, bool use_e
         delete e;
         return OH_E_HIP;
     }
-    if (const char *sl = getenv("OHEVC_SPIN_LIMIT"))          /* tests: make a waiting workgroup give up at once */
-        e->spin_limit = (uint32_t)std::max(1l, atol(sl));
-    if (getenv("OHEVC_STAMPS")) {
+    e->tuning = tuning_from_env();
+    if (e->tuning.stamps) {
         const size_t bytes = (16 + 4000 * 16) * sizeof(uint64_t);
         if (hipMalloc((void **)&e->dbg, bytes) == hipSuccess)
             (void)hipMemset(e->dbg, 0, bytes);
@@ -176,7 +175,7 @@ extern "C" void oh_engine_destroy(OhEngine *e)
     for (auto &a : e->arenas) { if (a.free_ev) (void)hipEventDestroy(a.free_ev); (void)hipFree(a.p); }
     for (auto &ev : e->sync_events) (void)hipEventDestroy(ev);
     for (void *b : e->sum_pool) (void)hipHostFree(b);
-    if (e->dl_count && getenv("OHEVC_FETCH_TIMING"))
+    if (e->dl_count && e->tuning.fetch_timing)
         fprintf(stderr, "ohevc engine: %llu output fetches, per fetch %.2f ms waiting for the picture's passes and its device-to-host copy, %.2f ms moving the rows into the caller's planes\n",
                 (unsigned long long)e->dl_count, e->dl_wait_ms / e->dl_count, e->dl_copy_ms / e->dl_count);
     delete e->copiers;
@@ -427,54 +426,34 @@ static int read_summary(OhEngine *e, OhDevFrame *df, int index)
     return OH_OK;
 }
 
-/* the CTUs' residual spans staged in LDS, or every block fetching its own from the pool one sub-level ahead (intra.hip: slots_prepare)?
- * Staging costs ~11 KB of LDS per workgroup in a launch that holds one all-intra CTU, i.e. workgroups per CU (OHEVC_INTRA_RES_LDS=0 / 1
- * forces one way: experiments) */
-static bool res_in_lds(const OhEngine *e, uint64_t workgroups)
-{
-    static const char *env = getenv("OHEVC_INTRA_RES_LDS");
-    if (env) return atoi(env) != 0;
-    /* a launch of at most a workgroup per CU is latency-bound: stage (a 4K I picture alone 6.6 ms against 7.0); any wider one runs at
-     * workgroups-per-CU x latency: keep the LDS small (all-intra batches 39.8 against 37.6 Gpix/s, the mixed bench +0.6 %) */
-    return workgroups <= (uint64_t)e->n_cu;
-}
-
-/* The intra pass of a batch (intra.hip), one launch per form:
- *   direct  a wave per CTU working on the picture in HBM — pictures whose intra blocks cover less than half of their samples
- *           (B / P pictures);
- *   dag     a workgroup per CTU with the CTU staged in LDS — the others (I pictures).
- * OHEVC_INTRA_MODE=dag / direct forces one form for every picture.  A CTU takes the schedule entry of the ticket it draws when it
- * starts and waits only for lower tickets, so the launch drains whatever the dispatch order; a wait that gives up anyway (bounded by
- * OHEVC_SPIN_LIMIT) is reported by kernel_error. */
+/* The intra pass of a batch (intra.hip), one launch per form; which form a picture takes and the staged launch's numbers are
+ * intra_plan.h's.  A CTU takes the schedule entry of the ticket it draws when it starts and waits only for lower tickets, so the
+ * launch drains whatever the dispatch order; a wait that gives up anyway (bounded by OhTuning::spin_limit) is reported by kernel_error. */
 static int intra_pass(OhEngine *e, OhDevFrame *const *fr, int nb, const OhBatch *all, hipStream_t st)
 {
     const OhPicParams *p = &fr[0]->p;
-    static const char *menv = getenv("OHEVC_INTRA_MODE");
-    const bool force_dag = menv && !strcmp(menv, "dag"), force_direct = menv && !strcmp(menv, "direct");
     OhBatch bd, bs;                                  /* direct / staged dag */
     memset(&bd, 0, sizeof(bd)); memset(&bs, 0, sizeof(bs));
     int nd = 0, ns = 0;
-    uint32_t max_ictu_d = 0, max_ictu_s = 0, max_ictu_all = 0, max_items = 1, max_sub = 1, max_res = 0;
-    uint64_t sum_items = 0, sum_sub = 0, total_entries = 0;
-    bool staged = true;
-    const uint64_t pic_samples64 = ((uint64_t)p->width * p->height * (p->chroma_format_idc == 0 ? 2 : p->chroma_format_idc == 1 ? 3 : p->chroma_format_idc == 2 ? 4 : 6) / 2) >> 6;
+    uint32_t max_ictu_d = 0, max_ictu_s = 0, max_ictu_all = 0;
+    OhIntraFigures fig;
+    fig.batch = nb;
     for (int i = 0; i < nb; i++) {
         if (!fr[i]->cnt.n_ictu)
             continue;
         max_ictu_all = std::max(max_ictu_all, fr[i]->cnt.n_ictu);
-        const bool sparse = force_direct || (!force_dag && (uint64_t)fr[i]->intra_area64 * 2 < pic_samples64);
-        if (sparse) {
+        if (intra_plan_direct(p, fr[i]->intra_area64, e->tuning)) {
             bd.f[nd++] = fr[i]->d;
             max_ictu_d = std::max(max_ictu_d, fr[i]->cnt.n_ictu);
             continue;
         }
         bs.f[ns++] = fr[i]->d;
         max_ictu_s = std::max(max_ictu_s, fr[i]->cnt.n_ictu);
-        total_entries += fr[i]->cnt.n_ictu;
+        fig.total_entries += fr[i]->cnt.n_ictu;
         const OhDevFrame &d = *fr[i];
-        max_items = std::max(max_items, d.max_items); max_sub = std::max(max_sub, d.max_sub); max_res = std::max(max_res, d.max_res);
-        sum_items += d.sum_items; sum_sub += d.sum_sub;
-        staged = staged && !d.res_scattered;
+        fig.max_items = std::max(fig.max_items, d.max_items); fig.max_sub = std::max(fig.max_sub, d.max_sub); fig.max_res = std::max(fig.max_res, d.max_res);
+        fig.sum_items += d.sum_items; fig.sum_sub += d.sum_sub;
+        fig.contiguous = fig.contiguous && !d.res_scattered;
     }
     if (!nd && !ns)
         return OH_OK;
@@ -491,31 +470,10 @@ static int intra_pass(OhEngine *e, OhDevFrame *const *fr, int nb, const OhBatch 
     ohk_intra_dag_reset(all, nb, max_ictu_all, tk, st);
     if (a) HIPCHK(e, hipEventRecord(a, st));
     if (nd)
-        ohk_intra_direct(&bd, nd, p, max_ictu_d, tk, e->spin_limit, st);
+        ohk_intra_direct(&bd, nd, p, max_ictu_d, tk, e->tuning.spin_limit, st);
     if (ns) {
-        OhIntraLaunch IL;
-        /* residual spans in LDS only while the chip holds the whole launch (a picture alone); else the blocks fetch theirs a sub-level ahead */
-        IL.staged = staged && res_in_lds(e, total_entries / 8);
-        /* waves per CTU: as many as blocks run side by side in a sub-level (more only hold LDS and wave slots); a small batch cannot
-         * fill the chip anyway: spend the waves on the single picture's latency (OHEVC_INTRA_WAVES forces them: experiments) */
-        static const char *wenv = getenv("OHEVC_INTRA_WAVES");
-        const double par = sum_sub ? (double)sum_items / (double)sum_sub : 1.0;
-        IL.waves = wenv ? (uint32_t)atoi(wenv) : par > (nb < 8 ? 2.5 : 4.5) ? 8 : par > 1.25 ? 4 : 2;
-        if (IL.waves != 2 && IL.waves != 4 && IL.waves != 8) IL.waves = 8;
-        /* sub-levels go round-robin to `phases` groups of waves (intra.hip): a group prepares its next sub-level while another
-         * finishes its own, so at least two */
-        static const char *penv = getenv("OHEVC_INTRA_PHASES");
-        IL.phases = penv ? (uint32_t)atoi(penv) : 2u;
-        if (IL.phases < 2 || IL.phases > IL.waves || IL.waves % IL.phases) IL.phases = 2;
-        const OhCtuAreas areas = oh_ctu_areas(p->log2_ctb_size, p->chroma_format_idc);
-        size_t off = align_up((size_t)areas.total * sizeof(uint16_t), 16);
-        IL.off_items = (uint32_t)off; off += (size_t)max_items * sizeof(DevIntra);
-        IL.off_sub = (uint32_t)off;   off += ((size_t)max_sub + 1) * sizeof(uint32_t);
-        IL.off_small = (uint32_t)off; off = align_up(off + (size_t)max_sub * sizeof(uint32_t), 16);
-        IL.off_res = (uint32_t)off;   off = align_up(off + (size_t)(IL.staged ? max_res : 0) * sizeof(int16_t), 16);
-        IL.off_wave = (uint32_t)off;  off += (size_t)IL.waves * OH_INTRA_WAVE_LDS;
-        IL.lds_bytes = (uint32_t)off;
-        ohk_intra_dag(&bs, ns, p, &IL, max_ictu_s, tk + OH_MAX_BATCH * 32, e->spin_limit, st);
+        const OhIntraLaunch IL = intra_plan_launch(p->log2_ctb_size, p->chroma_format_idc, fig, e->n_cu, e->tuning);
+        ohk_intra_dag(&bs, ns, p, &IL, max_ictu_s, tk + OH_MAX_BATCH * 32, e->tuning.spin_limit, st);
     }
     if (b) {
         HIPCHK(e, hipEventRecord(b, st));

@@ -139,9 +139,8 @@ static bool same_geometry(const OhPicParams &a, const OhPicParams &b)
 static CopyPool *copiers_get(OhEngine *e)
 {
     if (!e->copiers) {
-        static const char *cenv = getenv("OHEVC_COPY_THREADS");
         e->copiers = new CopyPool();
-        e->copiers->start(cenv ? std::max(0, std::min(atoi(cenv), 8)) : 2);
+        e->copiers->start(e->tuning.copy_threads);
     }
     return e->copiers;
 }

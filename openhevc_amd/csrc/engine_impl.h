@@ -2,7 +2,8 @@
  * engine_impl.h — what the engine's translation units share: the engine and picture structures, the error macros and the few
  * helpers more than one of them uses.  engine.hip: engine and picture lifecycle, staging buffers, passes, profiling;
  * engine_handover.hip: work-list hand-over and the arena pool (its host-only parts, which run on several threads, are handover_layout.h
- * and handover_host.h: the layout, the check-and-count of a list and the thread pool, none of which knows the engine); engine_pics.hip: plane transfers, hashes, conversion, import, measurement,
+ * and handover_host.h: the layout, the check-and-count of a list and the thread pool, none of which knows the engine; likewise
+ * engine_tuning.h, the OHEVC_* switches read once per engine, and intra_plan.h, the forms and the launch plan of the intra pass); engine_pics.hip: plane transfers, hashes, conversion, import, measurement,
  * comparison, resizing, composition, histograms and look-up tables of finished pictures, with the helpers those services share; engine_shvc.hip: SHVC up-sampling.
  * pics_math.hip, the services' host arithmetic, takes no engine and does not include this file (pics_math.h).
  * Internal: the C ABI is include/ohevc_hip.h.
@@ -25,6 +26,8 @@
 #include "../../include/ohevc_hip.h"
 #include "handover_layout.h"
 #include "handover_host.h"              /* CopyPool, handover_check_chunk: host-only, shared with the CPU checks */
+#include "engine_tuning.h"
+#include "intra_plan.h"
 #include "kernels.h"
 
 #define OH_INTERNAL __attribute__((visibility("hidden")))    /* shared between the engine's files, not part of the library's ABI */
@@ -116,7 +119,7 @@ struct OhEngine {
     double      host_ms[OH_N_HOST_TIMES] = {};   /* where the host time of the hand-over path goes (oh_engine_host_times) */
     uint64_t    host_calls[OH_N_HOST_TIMES] = {};
     uint64_t    up_bytes = 0;                    /* bytes of work lists sent over PCIe since the last reset */
-    uint64_t   *dbg = nullptr;           /* diagnostics (OHEVC_STAMPS=1 + a -DOH_STAMPS build) */
+    uint64_t   *dbg = nullptr;           /* diagnostics (OhTuning::stamps + a -DOH_STAMPS build) */
     /* what a kernel can tell the host when it cannot go on (the table slots and the passes have no error channel: hevcdsp.h's slots
      * return void): four words of pinned host memory, [0] OH_KE_* of the first failure, [1] picture id, [2] schedule
      * entry; read by everything that waits for the stream (kernel_error) */
@@ -132,7 +135,7 @@ struct OhEngine {
     enum { TICKET_RING = 128, TICKET_WORDS = 2 * OH_MAX_BATCH * 32 };      /* per batch: (direct, staged) x pictures, a cache line each (intra.hip: OH_TICKET_STRIDE) */
     uint32_t   *tickets = nullptr;
     uint64_t    ticket_seq = 0;
-    /* the hand-over's helper threads (handover_host.h; OHEVC_COPY_THREADS of them, default 2, 0: the submitter does everything alone
+    /* the hand-over's helper threads (handover_host.h; OhTuning::copy_threads of them, 0: the submitter does everything alone
      * on the same code path): started by the first hand-over BEFORE its check-and-count phase, which they share list by list, as they
      * share the staging copy piece by piece.  They see lists and staging memory, never the engine */
     CopyPool   *copiers = nullptr;
@@ -140,9 +143,9 @@ struct OhEngine {
      * drives the engine */
     std::mutex  dl_mu, dl_copy_mu;
     std::vector<Stage *> dl_stages;
-    CopyPool   *dl_copiers = nullptr;   /* created with the first fetch (OHEVC_FETCH_THREADS helpers, default 3) */
+    CopyPool   *dl_copiers = nullptr;   /* created with the first fetch (OhTuning::fetch_threads helpers) */
     std::vector<CopyJob> dl_jobs;
-    double      dl_wait_ms = 0, dl_copy_ms = 0;     /* OHEVC_FETCH_TIMING: where the time of the fetches went (printed when the engine is destroyed) */
+    double      dl_wait_ms = 0, dl_copy_ms = 0;     /* OhTuning::fetch_timing: where the time of the fetches went (printed when the engine is destroyed) */
     uint64_t    dl_count = 0;
     std::vector<CopyJob> copy_jobs;
     uint32_t   *kerr = nullptr;
@@ -176,7 +179,7 @@ struct OhEngine {
     Scratch     motion_centres;          /* oh_pics_motion: the centres of the call, rewritten on the stream behind the launches that read them */
     Scratch     motion_field;            /* oh_pics_motion_compensate: the vectors of the call, likewise */
     Scratch     compose_dev;           /* oh_pics_compose: the layer table of the call (OhCpsLayer, then OhCpsSrc per launch set) */
-    uint32_t    spin_limit = 1u << 22;   /* polls (with s_sleep between them, ~1 s in all) before a waiting workgroup gives up; OHEVC_SPIN_LIMIT */
+    OhTuning    tuning;                  /* the OHEVC_* switches as engine_create found them (engine_tuning.h) */
 };
 
 #define HIPCHK(e, call)                                                                           \

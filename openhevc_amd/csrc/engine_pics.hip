@@ -391,10 +391,8 @@ extern "C" int oh_download_finish(OhEngine *e, OhDownload *d, uint8_t *const pla
     if (!rc) {
         std::lock_guard<std::mutex> lk(e->dl_copy_mu);         /* one fetch at a time uses the helpers */
         if (!e->dl_copiers) {
-            const char *v = getenv("OHEVC_FETCH_THREADS");
-            const int n = v ? atoi(v) : 3;
             e->dl_copiers = new CopyPool();
-            e->dl_copiers->start(n < 0 ? 0 : (n > 15 ? 15 : n));
+            e->dl_copiers->start(e->tuning.fetch_threads);
         }
         /* pieces of at most 1 MiB (packed planes) or single rows (pitched planes), dealt round-robin to the helpers and this thread */
         std::vector<CopyJob> &jobs = e->dl_jobs;

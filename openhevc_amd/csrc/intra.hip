@@ -991,15 +991,13 @@ __global__ __launch_bounds__(256) void intra_dag_reset_kernel(const OhBatch B, u
  * ======================================================================================= */
 int ohk_init_intra(void)
 {
-    /* the staged kernel's LDS block is sized per launch and exceeds 64 KiB for 4:4:4 CTUs full of 4x4 blocks */
-    const int max_lds = 128 * 1024;
     const void *dag_kernels[8] = {
         (const void *)intra_dag_kernel<uint8_t, false, false>, (const void *)intra_dag_kernel<uint8_t, false, true>,
         (const void *)intra_dag_kernel<uint8_t, true, false>, (const void *)intra_dag_kernel<uint8_t, true, true>,
         (const void *)intra_dag_kernel<uint16_t, false, false>, (const void *)intra_dag_kernel<uint16_t, false, true>,
         (const void *)intra_dag_kernel<uint16_t, true, false>, (const void *)intra_dag_kernel<uint16_t, true, true> };
     for (const void *k : dag_kernels)
-        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds) != hipSuccess)
+        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, OH_INTRA_MAX_LDS) != hipSuccess)
             return -1;
     return 0;
 }

@@ -45,9 +45,9 @@ class World:
     """one engine; per geometry two reference pictures and the start content of a current picture; N_LISTS lists (host ids: references
     0 and 1, current picture 2), each with a current picture of its own on the engine, its checker picture and its picture decoded alone"""
 
-    def __init__(self):
+    def __init__(self, eng=None):
         from openhevc_amd.engine import Engine, remap_frame
-        self.eng = e = Engine(0)
+        self.eng = e = eng or Engine(0)
         self.params = [F.pic_params(w, h) for w, h in GEOMETRIES]
         self.recs = [F.Recorder(p) for p in self.params]
         rng = np.random.default_rng(10)

@@ -4,13 +4,11 @@ constrained intra prediction) — with the form of the intra pass the engine cho
 The in-loop filters are off, so a picture is the output of the intra pass; a difference is reported with the block that wrote
 the sample: size, plane, mode, flags, residual, recipe."""
 import gc
-import os
-import subprocess
-import sys
 
 import pytest
 
 import directed_intra as DI
+from forced_engine import forced_engine
 from test_gpu_directed import check_lists, eng  # noqa: F401  (eng: the module-scoped engine fixture)
 
 pytestmark = pytest.mark.gpu
@@ -100,41 +98,21 @@ def test_cip_masks_with_pinned_lists(eng):
     gc.collect()
 
 
-# ---- each form of the pass forced (environment switches read once per process: a fresh child process) ----
-_CHILD = r"""
-import sys
-sys.path.insert(0, {tests!r}); sys.path.insert(0, {root!r})
-import directed_intra as DI
-from test_gpu_directed import check_lists
-from openhevc_amd.engine import Engine
-eng = Engine(0)
-n = 0
-for lists in {what}:
-    assert lists
-    n += check_lists(eng, lists)
-eng.close()
-print("ok", n)
-"""
-
+# ---- each form of the pass forced (an engine reads its switches when it is created: tests/forced_engine.py) ----
 FORCED = {
-    "F": "[DI.build_f(1, 10, 0), DI.build_f(3, 8, 0)]",
-    "G": "[DI.build_g(cf, bd, w) for cf, bd in DI.G_FORMATS for w in DI.G_KINDS]",
-    "H": "[DI.build_h_thr(bd, v) for bd in DI.H_DEPTHS for v in DI.H_VARIANTS] + [DI.build_h_thr(bd, 'strong', cf, 1) for bd in DI.H_DEPTHS "
-         "for cf in (3, 1)] + [DI.build_h_clip(bd) for bd in DI.H_DEPTHS]",
-    "J": "[DI.build_j(cf, bd) for cf, bd in DI.J_FORMATS]",
-    "K": "[DI.build_k8(8, 3)]",
+    "F": lambda: [DI.build_f(1, 10, 0), DI.build_f(3, 8, 0)],
+    "G": lambda: [DI.build_g(cf, bd, w) for cf, bd in DI.G_FORMATS for w in DI.G_KINDS],
+    "H": lambda: ([DI.build_h_thr(bd, v) for bd in DI.H_DEPTHS for v in DI.H_VARIANTS] +
+                  [DI.build_h_thr(bd, "strong", cf, 1) for bd in DI.H_DEPTHS for cf in (3, 1)] + [DI.build_h_clip(bd) for bd in DI.H_DEPTHS]),
+    "J": lambda: [DI.build_j(cf, bd) for cf, bd in DI.J_FORMATS],
+    "K": lambda: [DI.build_k8(8, 3)],
 }
 
 
-def run_child(what, **env):
-    here = os.path.dirname(os.path.abspath(__file__))
-    e = dict(os.environ)
-    for k in ("OHEVC_INTRA_MODE", "OHEVC_INTRA_WAVES", "OHEVC_INTRA_PHASES", "OHEVC_INTRA_RES_LDS"):
-        e.pop(k, None)
-    e.update({k: str(v) for k, v in env.items()})
-    r = subprocess.run([sys.executable, "-c", _CHILD.format(tests=here, root=os.path.dirname(here), what=what)], env=e,
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and r.stdout.strip().split("\n")[-1].startswith("ok"), r.stdout[-2000:] + r.stderr[-4000:]
+def run_forced(family, **switches):
+    with forced_engine(**switches) as e:
+        for lists in FORCED[family]():
+            assert lists and check_lists(e, lists) == len(lists)
 
 
 @pytest.mark.parametrize("family", list(FORCED))
@@ -142,16 +120,16 @@ def run_child(what, **env):
 def test_forced_forms(mode, family):
     """part 0 of F for 4:2:0 10 bit and 4:4:4 8 bit, all of G, H and J and K's 8x8 masks through the staged form (a workgroup per CTU,
     the CTU in LDS) and through the direct form (a wave per CTU on the picture in HBM), whatever the engine would choose"""
-    run_child(FORCED[family], OHEVC_INTRA_MODE=mode)
+    run_forced(family, OHEVC_INTRA_MODE=mode)
 
 
 @pytest.mark.parametrize("waves,phases", [(2, 2), (8, 8)])
 def test_chains_under_wave_layouts(waves, phases):
     """J with the sub-levels of a CTU dealt to 2 and to 8 waves"""
-    run_child(FORCED["J"], OHEVC_INTRA_WAVES=waves, OHEVC_INTRA_PHASES=phases)
+    run_forced("J", OHEVC_INTRA_WAVES=waves, OHEVC_INTRA_PHASES=phases)
 
 
 @pytest.mark.parametrize("res_lds", [0, 1])
 def test_chains_with_residuals_staged_or_not(res_lds):
     """J through the staged form with the residuals read from HBM and staged in LDS"""
-    run_child(FORCED["J"], OHEVC_INTRA_MODE="dag", OHEVC_INTRA_RES_LDS=res_lds)
+    run_forced("J", OHEVC_INTRA_MODE="dag", OHEVC_INTRA_RES_LDS=res_lds)

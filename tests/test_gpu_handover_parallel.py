@@ -6,18 +6,14 @@ and 5 helper threads, and with two engines handing over from two threads at once
 The lists, their checker pictures and the pictures decoded from each list uploaded alone are those of test_gpu_chunk_handover.py (World:
 small 416x240 and 64x64 lists of every kind, one of them pulled from page-locked memory), made once per module.  No test provokes a
 fault: a malformed list is refused on the host before anything is enqueued, which test_gpu_chunk_handover.py covers."""
-import os
-import subprocess
-import sys
 import threading
 
 import pytest
 
 import test_gpu_chunk_handover as T
+from forced_engine import forced_engine
 
 pytestmark = pytest.mark.gpu
-
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 @pytest.fixture(scope="module")
@@ -69,28 +65,19 @@ def test_a_chunk_counted_on_all_host_threads_decodes_like_lists_uploaded_alone(w
     world.check(range(n), f"{n} lists in one call")
 
 
-_CHILD = r"""
-import sys
-sys.path.insert(0, {tests!r}); sys.path.insert(0, {root!r})
-import test_gpu_chunk_handover as T
-import test_gpu_handover_parallel as P
-w = T.World()
-w.reset_pictures(range(32))
-P.decode_chunk(w, 32)
-w.eng.sync()
-w.check(range(32), "32 lists in one call")
-w.close()
-print("ok")
-"""
-
-
 @pytest.mark.parametrize("helpers", [0, 1, 5])
 def test_a_full_chunk_with_other_numbers_of_helper_threads(helpers):
-    """OHEVC_COPY_THREADS is read once per process: a fresh child per value.  0: no helper at all, the submitting thread runs the same
-    code alone; 1 and 5: fewer and more threads than the default's three."""
-    env = dict(os.environ, OHEVC_COPY_THREADS=str(helpers))
-    r = subprocess.run([sys.executable, "-c", _CHILD.format(tests=HERE, root=os.path.dirname(HERE))], env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-2000:] + r.stderr[-4000:]
+    """OHEVC_COPY_THREADS is read when an engine is created: a world of its own per value.  0: no helper at all, the submitting thread
+    runs the same code alone; 1 and 5: fewer and more threads than the default's three."""
+    with forced_engine(OHEVC_COPY_THREADS=helpers) as e:
+        w = T.World(e)
+        try:
+            w.reset_pictures(range(32))
+            decode_chunk(w, 32)
+            w.eng.sync()
+            w.check(range(32), "32 lists in one call")
+        finally:
+            w.close()
 
 
 def test_two_engines_hand_over_chunks_from_two_threads_at_once(world):

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+from forced_engine import forced_engine
 from openhevc_amd import frame as F
 from oracle_lib import host_pic_array, oracle
 
@@ -664,58 +665,39 @@ def test_output_window_download(eng):
         eng.pic_free(pid)
 
 
-_WAVES_SCRIPT = r"""
-import sys
-sys.path.insert(0, {tests!r}); sys.path.insert(0, {root!r})
-import numpy as np
-from openhevc_amd import frame as F
-from openhevc_amd.engine import Engine
-import test_gpu_parity as T
-eng = Engine(0)
-for (w, h, bd, cf, lc, st, knobs) in [(416, 240, 8, 1, 6, 0, {{}}), (416, 240, 10, 1, 6, 2, {{"intra_pct": 60}}), (200, 136, 10, 3, 5, 0, {{"split_pct": 90}}),
-                                      (416, 240, 8, 2, 4, 0, {{"split_pct": 10}}), (1920, 1080, 10, 1, 6, 0, {{}})]:
-    p = F.pic_params(w, h, bit_depth=bd, chroma_format_idc=cf, log2_ctb_size=lc)
-    rec = F.Recorder(p)
-    f = rec.synth(F.synth_params(st, 77, **knobs), 2, [0, 1])
-    rng = np.random.default_rng(5)
-    pics = {{0: F.HostPic(p, rng=rng), 1: F.HostPic(p, rng=rng), 2: F.HostPic(p, rng=rng)}}
-    want, got = T.run_both(eng, p, f, pics)
-    T.assert_same(want, got, f"{{w}}x{{h}} {{bd}}-bit chroma {{cf}} ctb {{lc}}")
-    rec.close()
-eng.close()
-print("ok")
-"""
+FORCED_CONFIGS = [(416, 240, 8, 1, 6, 0, {}), (416, 240, 10, 1, 6, 2, {"intra_pct": 60}), (200, 136, 10, 3, 5, 0, {"split_pct": 90}),
+                  (416, 240, 8, 2, 4, 0, {"split_pct": 10}), (1920, 1080, 10, 1, 6, 0, {})]
+
+
+def run_forced(**switches):
+    """I / B pictures of several formats, with and without large blocks, through an engine created with these switches
+    (tests/forced_engine.py)"""
+    with forced_engine(**switches) as e:
+        for w, h, bd, cf, lc, st, knobs in FORCED_CONFIGS:
+            p = F.pic_params(w, h, bit_depth=bd, chroma_format_idc=cf, log2_ctb_size=lc)
+            rec = F.Recorder(p)
+            f = rec.synth(F.synth_params(st, 77, **knobs), 2, [0, 1])
+            rng = np.random.default_rng(5)
+            pics = {0: F.HostPic(p, rng=rng), 1: F.HostPic(p, rng=rng), 2: F.HostPic(p, rng=rng)}
+            want, got = run_both(e, p, f, pics)
+            assert_same(want, got, f"{w}x{h} {bd}-bit chroma {cf} ctb {lc}")
+            rec.close()
 
 
 @pytest.mark.parametrize("waves,phases", [(2, 2), (4, 2), (8, 2), (4, 4), (8, 4), (8, 8)])
 def test_intra_wave_layouts(waves, phases):
     """the intra kernel deals the sub-levels of a CTU to `phases` groups of its waves; the engine picks 2 / 4 / 8 waves per
-    launch from the content and 2 phases.  Force every layout (environment switches read once per process, hence the child
-    process) over I / B pictures of several formats, with and without large blocks."""
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    env = dict(os.environ, OHEVC_INTRA_WAVES=str(waves), OHEVC_INTRA_PHASES=str(phases))
-    r = subprocess.run([sys.executable, "-c", _WAVES_SCRIPT.format(tests=here, root=os.path.dirname(here))], env=env,
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-2000:] + r.stderr[-4000:]
+    launch from the content and 2 phases.  Force every layout over I / B pictures of several formats, with and without large
+    blocks."""
+    run_forced(OHEVC_INTRA_WAVES=waves, OHEVC_INTRA_PHASES=phases)
 
 
 @pytest.mark.parametrize("mode", ["dag", "direct"])
 def test_intra_pass_forms(mode):
     """The intra pass of a picture runs in one launch — a wave per CTU on the picture in HBM (`direct`: pictures with few intra blocks)
     or a workgroup per CTU staged in LDS (`dag`), CTUs waiting for their neighbours' flags.  The engine chooses per picture;
-    OHEVC_INTRA_MODE forces one form for every picture: I and B pictures of several formats through each (child process: the
-    switch is read once)."""
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    env = dict(os.environ, OHEVC_INTRA_MODE=mode)
-    for k in ("OHEVC_INTRA_WAVES", "OHEVC_INTRA_PHASES", "OHEVC_INTRA_RES_LDS"):
-        env.pop(k, None)
-    r = subprocess.run([sys.executable, "-c", _WAVES_SCRIPT.format(tests=here, root=os.path.dirname(here))], env=env,
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-2000:] + r.stderr[-4000:]
+    OHEVC_INTRA_MODE forces one form for every picture: I and B pictures of several formats through each."""
+    run_forced(OHEVC_INTRA_MODE=mode)
 
 
 _GIVE_UP_SCRIPT = r"""
@@ -763,16 +745,8 @@ def test_intra_wait_that_gives_up_is_reported(mode):
 def test_intra_residual_staging(res_lds):
     """The staged form (intra_dag_kernel) stages the CTUs' residual spans in LDS in launches the chip holds at once and fetches them
     per block from HBM in the prepare stage in wider ones; OHEVC_INTRA_RES_LDS forces one way.  Both over the same I / B pictures,
-    every picture through the staged form (child process: the switches are read once)."""
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    env = dict(os.environ, OHEVC_INTRA_MODE="dag", OHEVC_INTRA_RES_LDS=str(res_lds))
-    env.pop("OHEVC_INTRA_WAVES", None)
-    env.pop("OHEVC_INTRA_PHASES", None)
-    r = subprocess.run([sys.executable, "-c", _WAVES_SCRIPT.format(tests=here, root=os.path.dirname(here))], env=env,
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-2000:] + r.stderr[-4000:]
+    every picture through the staged form."""
+    run_forced(OHEVC_INTRA_MODE="dag", OHEVC_INTRA_RES_LDS=res_lds)
 
 
 @pytest.mark.parametrize("w,h,bd,lc,lcb,seed", [(416, 240, 8, 6, 3, 1), (416, 240, 10, 4, 3, 2), (200, 136, 8, 5, 3, 3), (1920, 1080, 10, 6, 3, 4),

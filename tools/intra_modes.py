@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Experiment: a batch of N pictures of one slice type on S engines (streams, one host thread each), timed as a whole and per pass.
-The intra pass's form is chosen by the environment (OHEVC_INTRA_MODE = dag | direct | unset: automatic), read once per
-process, so this runs once per form.
+The intra pass's form is chosen by the environment (OHEVC_INTRA_MODE = dag | direct | unset: automatic), which every engine
+reads when it is created: set it before this starts, one run per form.
 usage: intra_modes.py SLICE_TYPE(0 I, 1 P, 2 B) BATCH STREAMS [WIDTH HEIGHT BITDEPTH] [knob=value ...]"""
 import os
 import sys
